@@ -16,10 +16,19 @@ barrier and the max-over-ranks time only.  Rank 0 prints ONE JSON line.  Timing:
 barriers + synchronisation; when W is smaller than --settle (default 30 steps, about 25 ms of load: what the engine clocks need
 to settle) the difference runs as untimed settling steps in front of the warm-up and is reported as "settle_steps".
 
-At N=1 the same line also carries, under "secondary", measured-and-verified entries for the other BASELINE configs
-(2: 20 MHz 2-layer 64-QAM 1000-slot batch; 4: four cells x four UEs mixed MCS, 1024 cell-slots; 5: receive chain with
-8 LDPC iterations) and for config 3 with the wire-format (complex int16) OFDM output, each with its own roofline dict,
-and "cpu_baseline": the reference's CPU path timed on this host's cores.
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps, the line.  With --full the same line
+also carries the check of the last step's grid 0 and its IQ against the CPU oracle ("verified_vs_oracle"); at N=1, under
+"secondary", measured-and-verified entries for the other BASELINE configs (2: 20 MHz 2-layer 64-QAM 1000-slot batch; 4: four
+cells x four UEs mixed MCS, 1024 cell-slots; 5: receive chain with 8 LDPC iterations), for config 3 with the wire-format
+(complex int16) OFDM output, each with its own roofline dict, and the through-the-shim figures; "cpu_baseline": the
+reference's CPU path timed on this host's cores; at N > 1, config 4 sharded over the ranks.
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs bench_outputs
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step computed for a fixed, seeded sample of its slots
+(dump_outputs; with N ranks, rank 0's share of the batch) as DIR/<name>.npy; the transport blocks are seeded, so the same
+arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -177,10 +186,43 @@ def roof(name, ms, nbytes, slots=None, config=None, wire=False):
 
 EVENT_STRIDE = 4  # every fourth step of the timed region carries the HIP events of the kernel durations
 
+DUMP_SLOTS = 8               # --dump-outputs: slots of the batch in the sample (config 3: 27 MB of grids and IQ)
+DUMP_BYTES = 48 << 20        # ... and fewer where that would pass this many bytes
+DUMP_SEED = 0
 
-def run_downlink(env, config, slots, steps, warmup, wire=False):
+
+def dump_outputs(directory, torch, d_grid, d_iq, d_stats=None):
+    """--dump-outputs: what the last timed step left for a caller of the path, for a fixed, seeded sample of the batch's slots
+    (grids), as float32 / float64 .npy files in `directory`.  With N ranks, rank 0 writes its own share of the batch, and the
+    slot indices are positions in that share.
+      slots.npy   (k,)                          the sampled slot (config 4: cell-slot grid) indices, ascending
+      grid.npy    (k, ports, 14, subcarriers, 2) the resource grids, complex bf16 widened to float32 (exact)
+      iq.npy      (k, ports, slot_stride, 2)    the baseband IQ, complex float32 (wire format: the int16 values as float32)
+      iq_stats.npy (k, ports, 4)                wire format only: the amplitude controller's measurements of each buffer
+                                                (nrphy_amplitude_stats_t: sum_power, peak_power, nof_clipped, nof_samples),
+                                                as float64"""
+    slots = d_grid.shape[0]
+    per_slot = (d_grid[0].numel() * 2 + d_iq[0].numel()) * 4
+    k = max(1, min(slots, DUMP_SLOTS, DUMP_BYTES // per_slot))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(slots, size=k, replace=False))
+    sel = torch.from_numpy(idx).to(d_grid.device)
+    grid = d_grid.index_select(0, sel).cpu().numpy()
+    grid = (grid.view(np.uint16).astype(np.uint32) << 16).view(np.float32).reshape(grid.shape + (2,))
+    iq = d_iq.index_select(0, sel).cpu().numpy().astype(np.float32)
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "slots.npy"), idx.astype(np.float64))
+    np.save(os.path.join(directory, "grid.npy"), grid)
+    np.save(os.path.join(directory, "iq.npy"), iq)
+    if d_stats is not None:
+        raw = d_stats.cpu().numpy().reshape(slots, -1, 4)[idx]   # {float sum_power, float peak_power, u32 nof_clipped, u32 nof_samples}
+        stats = np.concatenate((raw[..., :2].view(np.float32), raw[..., 2:].view(np.uint32)), axis=-1, dtype=np.float64)
+        np.save(os.path.join(directory, "iq_stats.npy"), stats)
+
+
+def run_downlink(env, config, slots, steps, warmup, wire=False, check=False, dump=None):
     """Builds the workload of BASELINE config 2, 3 or 4 for this rank, times `steps` steps and returns the measurement (on
-    rank 0: the JSON fields; elsewhere None)."""
+    rank 0: the JSON fields; elsewhere None).  check: grid 0 of the last step and its IQ against the CPU oracle; dump: a
+    directory for dump_outputs (rank 0)."""
     torch, lib, abi, cases, sharding = env["torch"], env["lib"], env["abi"], env["cases"], env["sharding"]
     ctx, dist, rank, world, device = env["ctx"], env["dist"], env["rank"], env["world"], env["device"]
     if config == 4:
@@ -355,8 +397,11 @@ def run_downlink(env, config, slots, steps, warmup, wire=False):
         }
         if config == 4:
             out["config"]["sharding"] = "sharding.cell_affine_rank (cell c keeps to its ranks)"
-        # Sanity: grid 0 of the last step against the CPU oracle (checker only, outside the timed region).
         last = tb_sets[(step_no[0] - 1) % len(tb_sets)]
+        if dump:
+            dump_outputs(dump, torch, d_grid, d_iq, d_stats if wire else None)
+    if rank == 0 and check:
+        # Sanity: grid 0 of the last step against the CPU oracle (checker only, outside the timed region).
         try:
             import backends
             o = backends.oracle()
@@ -389,6 +434,7 @@ def run_downlink(env, config, slots, steps, warmup, wire=False):
                 "int16, one LSB" if wire else "f32, 1e-5 relative, all ports")
         except Exception as e:  # the oracle is optional at bench time
             out["verified_vs_oracle"] = "unavailable: %s" % e
+    if rank == 0:
         out["_first_pdu"] = (pdus[0], last[: pdus[0].tb_size_bytes].cpu().numpy().copy(), nof_ports, nof_subc, ofdm)
     plan.close()
     oplan.close()
@@ -519,8 +565,12 @@ def main():
     ap.add_argument("--config", type=int, default=3, choices=[2, 3, 4, 5],
                     help="BASELINE config measured as the line's value: 3 = the headline workload (default)")
     ap.add_argument("--wire", action="store_true", help="OFDM output as complex int16 (amplitude controller + conversion fused)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary entries (configs 2, 4, 5, wire format)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the check against the CPU oracle, the secondary entries and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary entries (configs 2, 4, 5, wire format)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (a fixed, seeded sample of its slots) as DIR/<name>.npy")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch, sharding and aggregation only (gloo, no device work): the N-rank path on a machine without GPUs")
     ap.add_argument("--rehearse-one-device", action="store_true",
@@ -529,6 +579,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be at least 1")
+    if args.dump_outputs and (args.dry_run or args.config == 5):
+        ap.error("--dump-outputs: the downlink path of configs 2, 3 and 4 only, with device work")
     if "RANK" not in os.environ:
         if args.gpus > 1:
             sys.exit(self_launch(args))  # nothing in this process has touched a GPU
@@ -575,7 +627,8 @@ def main():
            "device": torch.device("cpu") if args.rehearse_one_device else torch.device("cuda", local_rank),
            "settle": max(0, args.settle)}
 
-    head = run_downlink(env, args.config, args.slots, args.steps, args.warmup, wire=args.wire)
+    head = run_downlink(env, args.config, args.slots, args.steps, args.warmup, wire=args.wire, check=args.full,
+                        dump=args.dump_outputs)
     if rank == 0:
         first = head.pop("_first_pdu")
         out = {
@@ -591,27 +644,28 @@ def main():
                                      if args.rehearse_one_device else "rccl (torch.distributed nccl)")
     sec = {}
     s_steps, s_warm = max(3, args.steps), max(3, args.warmup)  # the same count as the headline: short runs read 5-10 % slow
-    if world == 1 and not args.no_secondary and args.config == 3 and not args.wire:
+    secondary = args.full and not args.no_secondary and args.config == 3 and not args.wire
+    if world == 1 and secondary:
         # Secondary measurements, same process and GPU; every entry is verified against the oracle.
         for name, (cfg, slots, wire) in {"config3_wire_ci16": (3, args.slots, True), "config2": (2, 1000, False),
                                          "config4": (4, 1024, False)}.items():
-            e = run_downlink(env, cfg, slots, s_steps, s_warm, wire=wire)
+            e = run_downlink(env, cfg, slots, s_steps, s_warm, wire=wire, check=True)
             e.pop("_first_pdu")
             sec[name] = e
         import rx_chain_bench
         sec["config5"] = rx_chain_bench.run_all(s_steps, s_warm)
         sec["shim"] = shim_entry(env)
-    elif world > 1 and not args.no_secondary and args.config == 3 and not args.wire:
+    elif world > 1 and secondary:
         # N ranks: BASELINE config 4 is the one quoted as a stream sharded over the GPUs -- placed by cell affinity, every
         # rank its share, whole-job totals like the headline.
-        e = run_downlink(env, 4, 1024, s_steps, s_warm)
+        e = run_downlink(env, 4, 1024, s_steps, s_warm, check=True)
         if rank == 0:
             e.pop("_first_pdu")
             sec["config4"] = e
     if rank == 0:
         if sec:
             out["secondary"] = sec
-        if world == 1 and not args.no_cpu_baseline and args.config == 3:
+        if world == 1 and args.full and not args.no_cpu_baseline and args.config == 3:
             out["cpu_baseline"] = cpu_baseline(*first)
         print(json.dumps(out), flush=True)
     if dist is not None:

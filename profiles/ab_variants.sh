@@ -5,7 +5,7 @@
 ROUNDS=$1; shift
 for i in $(seq $ROUNDS); do
   for v in "$@"; do
-    NRPHY_LIB_SO=$PWD/$v python3 bench.py --no-cpu-baseline --no-secondary --steps 20 ${BENCH_ARGS:-} 2>/dev/null | tail -1 | \
+    NRPHY_LIB_SO=$PWD/$v python3 bench.py --full --no-cpu-baseline --no-secondary --steps 20 ${BENCH_ARGS:-} 2>/dev/null | tail -1 | \
       python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v', d['kernel_ms'], round(d['value']), d.get('verified_vs_oracle'))"
   done
 done

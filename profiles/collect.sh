@@ -9,7 +9,7 @@ TAG=$1
 ROOT=$PWD
 OUT=$ROOT/gpurun_out
 mkdir -p "$OUT"
-python3 bench.py > "$OUT/${TAG}_bench.log" 2>&1 && tail -1 "$OUT/${TAG}_bench.log" > "$OUT/${TAG}_bench.json"
+python3 bench.py --full > "$OUT/${TAG}_bench.log" 2>&1 && tail -1 "$OUT/${TAG}_bench.log" > "$OUT/${TAG}_bench.json"
 echo "bench rc=$?"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_stats" -- python3 "$ROOT/bench.py" --no-cpu-baseline --no-secondary > "$OUT/${TAG}_stats.log" 2>&1

@@ -1607,11 +1607,19 @@ def test_dl_slot_pipeline_whole_slot_tb_to_iq(gpu_ctx, oracle, monkeypatch, firs
     pool.put(sid, entries)
     for e in entries:
         want.view(np.uint32).reshape(nof_ports, 14, nof_subc)[e.port, e.symbol, e.subc] = e.value
-    calls, me = [], threading.get_ident()
-    assert pool.modulate(sid, 0, lambda status, slot_id: calls.append((status, slot_id, threading.get_ident()))) == 0
+    calls, me, called = [], threading.get_ident(), threading.Event()
+
+    def on_done(status, slot_id):
+        calls.append((status, slot_id, threading.get_ident()))
+        called.set()
+
+    assert pool.modulate(sid, 0, on_done) == 0
     assert pool.modulate(sid, 0) == abi.ERR_ARGUMENT            # once per open
     assert pool.pdsch(sid, [pdsch], [tb]) == abi.ERR_ARGUMENT   # the grid has been handed over
     assert pool.wait(sid) == 0 and pool.poll(sid) == 0
+    # The runtime thread marks the slot done, then runs the handler, which needs the GIL this thread holds once wait()
+    # returns: the handler may still be on its way (the ABI orders it after the IQ copy, not before wait's return).
+    assert called.wait(10.0)
     assert len(calls) == 1 and calls[0][:2] == (0, sid) and calls[0][2] != me
     want_iq = oracle.ofdm_slot(ocfg, want, 0)
     for port in range(nof_ports):
@@ -1619,6 +1627,7 @@ def test_dl_slot_pipeline_whole_slot_tb_to_iq(gpu_ctx, oracle, monkeypatch, firs
     assert np.array_equal(pool.read_grid(sid), want)
     pool.close(sid)
     assert pool.poll(sid) == abi.ERR_ARGUMENT
+    assert len(calls) == 1   # once, also after close
     pool.destroy()
 
 

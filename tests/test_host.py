@@ -241,6 +241,17 @@ def test_bench_refuses_a_world_size_other_than_gpus():
     assert rc == 0 and len(lines) == 1 and lines[0]["n_gpus"] == 1 and lines[0]["collective_backend"].startswith("none")
 
 
+def test_bench_options_full_and_dump_outputs(tmp_path):
+    """--full is accepted (the dry run has nothing more to add); --dump-outputs is refused where no device work computes outputs
+    (the dry run, and config 5, whose path has no dump) and writes nothing there."""
+    rc, lines, err = _bench_line(["--gpus", "1", "--dry-run", "--full", "--steps", "2"])
+    assert rc == 0 and len(lines) == 1 and lines[0]["steps"] == 2, err[-3000:]
+    for argv in (["--dry-run"], ["--config", "5"]):
+        rc, lines, err = _bench_line(["--gpus", "1", "--dump-outputs", str(tmp_path / "out")] + argv)
+        assert rc == 2 and not lines and "--dump-outputs" in err
+    assert not os.path.exists(tmp_path / "out")
+
+
 def test_adaptors_compile_against_reference_headers(tmp_path):
     """The srsRAN-side adaptors (seams A, B, C) must compile against the reference's own interface headers."""
     import subprocess
