@@ -383,6 +383,82 @@ int nrphy_demodulate_soft(nrphy_ctx_t* ctx, uint32_t modulation, uint32_t nof_sp
 int nrphy_demodulate_soft_host(nrphy_ctx_t* ctx, uint32_t modulation, uint32_t nof_symbols, const float* symbols,
                                const float* noise_vars, int8_t* llr);
 
+/* ---- receive side: channel equaliser -----------------------------------------------------------------------------------
+ * Replaces channel_equalizer::equalize (R/include/srsran/phy/upper/equalization/channel_equalizer.h:86; impl
+ * R/lib/phy/upper/equalization/channel_equalizer_generic_impl.cpp:225-277 with equalize_{zf_1xn,mmse_1xn,zf_2xn}.h), the
+ * reference's scalar arithmetic with exact division:
+ *   ZF, one layer:   ports whose noise variance is not in (0, inf) are left out; the others, per RE, when |h|^2 and the
+ *                    variance are normal numbers; x = sum(y conj(h)) / (s sum|h|^2), var = sum(|h|^2 nv) / (s sum|h|^2)^2.
+ *   MMSE, one layer: h is scaled by s first; per RE and port as above; x = sum(y conj(h)) sum|h|^2 / ((sum|h|^2)^2 + sum(|h|^2 nv)),
+ *                    var = sum(|h|^2 nv) / ((sum|h|^2)^2 + sum(|h|^2 nv)) (the reference's denominator, as written).
+ *   ZF, two layers on 2 or 4 ports: the 2x2 pseudo-inverse, one noise variance for all ports (their maximum).
+ * Where the reference gives up (abnormal denominators), the symbol is 0 and its variance +inf.
+ * n_batch independent problems of nof_re RE: d_rx [batch][port][re] cbf16, d_ch [batch][layer][port][re] cbf16,
+ * d_noise_vars [batch][nof_rx_ports] f32 -> d_eq [batch][re][layer] complex f32, d_eq_nvars [batch][re][layer] f32.
+ * algorithm: NRPHY_EQ_ZF or NRPHY_EQ_MMSE; tx_scaling > 0.  Asynchronous on `stream`, capturable. */
+#define NRPHY_EQ_ZF 0u
+#define NRPHY_EQ_MMSE 1u
+int nrphy_channel_equalize(nrphy_ctx_t* ctx, uint32_t algorithm, uint32_t n_batch, uint32_t nof_re, uint32_t nof_layers,
+                           uint32_t nof_rx_ports, const void* d_rx, const void* d_ch, const float* d_noise_vars, float tx_scaling,
+                           float* d_eq, float* d_eq_nvars, void* stream);
+/* One problem from and to host memory (blocking). */
+int nrphy_channel_equalize_host(nrphy_ctx_t* ctx, uint32_t algorithm, uint32_t nof_re, uint32_t nof_layers, uint32_t nof_rx_ports,
+                                const void* rx, const void* ch, const float* noise_vars, float tx_scaling, float* eq,
+                                float* eq_nvars);
+
+/* ---- receive side: PUSCH demodulator ------------------------------------------------------------------------------------
+ * Replaces pusch_demodulator::demodulate (R/include/srsran/phy/upper/channel_processors/pusch/pusch_demodulator.h; impl
+ * R/lib/phy/upper/channel_processors/pusch/pusch_demodulator_impl.cpp:135-287): data RE of the allocation taken from the
+ * received grid and the channel estimate, equalised (nrphy_channel_equalize, tx_scaling 1), soft-demapped
+ * (nrphy_demodulate_soft, one span per OFDM symbol as the reference hands them over) and descrambled (nrphy_llr_descramble,
+ * c_init = rnti * 2^15 + n_id), in one kernel, bit for bit what the three calls give.  Codeword order: OFDM symbol, then
+ * ascending subcarrier, then layer, then bits.  DM-RS symbols lose the RE of their CDM groups without data (type 1: even
+ * or all subcarriers; type 2: pairs {0,1,6,7}, {2,3,8,9}, {4,5,10,11} per group); symbols without data RE are skipped.
+ * Receive port i reads grid port rx_ports[i].  Post-equalisation SINR (pusch_demodulator_impl.cpp:203-215, 255-262):
+ * -10 log10 of the mean of the equalised noise variances that are not infinite, +inf when there are none or their sum is
+ * not positive; reduced in a fixed order (two runs give the same bits).  Transform precoding is not supported. */
+typedef struct nrphy_pusch_demod_cfg {
+  uint32_t rnti, n_id;                    /* c_init = rnti * 2^15 + n_id */
+  uint32_t qm;                            /* 2, 4, 6, 8 */
+  uint32_t start_symbol_index, nof_symbols;
+  uint32_t dmrs_symbol_mask;              /* bit l = symbol l carries DM-RS */
+  uint32_t dmrs_type;                     /* 1 or 2 */
+  uint32_t nof_cdm_groups_without_data;   /* type 1: 1..2, type 2: 1..3 */
+  uint32_t nof_tx_layers;                 /* 1 or 2 */
+  uint32_t nof_rx_ports;                  /* 1..4 */
+  uint32_t rx_ports[NRPHY_MAX_PORTS];     /* grid port of receive port i */
+  uint32_t equalizer;                     /* NRPHY_EQ_ZF, NRPHY_EQ_MMSE (one layer only, as the reference) */
+  uint32_t transform_precoding;           /* must be 0 */
+  uint32_t reserved_;
+  uint64_t prb_mask[NRPHY_PRB_WORDS];     /* allocated PRBs, grid-indexed */
+} nrphy_pusch_demod_cfg_t;
+typedef struct nrphy_pusch_demod_plan nrphy_pusch_demod_plan_t;
+/* NRPHY_OK, or NRPHY_ERR_ARGUMENT for: transform precoding; a modulation other than QPSK..256-QAM; more than 2 layers, MMSE
+ * with 2 layers, 2 layers on other than 2 or 4 ports; a DM-RS type or CDM-group count the type does not allow; an rx port
+ * outside the grid or repeated; PRBs beyond the grid; symbols beyond the slot; an allocation without data RE.  No device work. */
+int nrphy_pusch_demod_validate(const nrphy_pusch_demod_cfg_t* cfg, uint32_t grid_nof_ports, uint32_t grid_nof_subc);
+/* G = data RE x layers x qm (0 for a configuration the structure cannot describe).  No device work. */
+uint64_t nrphy_pusch_demod_codeword_bits(const nrphy_pusch_demod_cfg_t* cfg);
+/* n PUSCHs; PUSCH i reads grid grid_index[i] of [nof_grids][grid_nof_ports][14][grid_nof_subc] cbf16 and its channel estimate
+ * at element ce_offset[i] of d_ch_est: [layer][rx port i][14][grid_nof_subc] cbf16 (the reference's channel_estimate,
+ * subcarrier fastest).  Validates every configuration, builds the work list (PUSCH, OFDM symbol, chunk of data RE) and
+ * uploads it (blocking, like nrphy_pdsch_plan_create). */
+int nrphy_pusch_demod_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_demod_cfg_t* cfgs, const uint32_t* grid_index,
+                                  uint32_t nof_grids, uint32_t grid_nof_ports, uint32_t grid_nof_subc, const uint64_t* ce_offset,
+                                  nrphy_pusch_demod_plan_t** plan);
+int nrphy_pusch_demod_plan_destroy(nrphy_pusch_demod_plan_t* plan);
+uint64_t nrphy_pusch_demod_plan_codeword_bits(const nrphy_pusch_demod_plan_t* plan, uint32_t i);
+/* d_noise_vars: [n][NRPHY_MAX_PORTS] f32 in device memory, entry i of a row = receive port i.  PUSCH i writes its G_i
+ * descrambled soft bits at d_llr + i * llr_stride (the input of nrphy_pusch_decode_batch) and, when d_sinr_db is not NULL,
+ * its SINR in dB to d_sinr_db[i].  Asynchronous on `stream`; allocates nothing and touches no host memory (capturable).
+ * Runs of one plan must be ordered (the plan owns the SINR partial sums). */
+int nrphy_pusch_demod_run(nrphy_pusch_demod_plan_t* plan, const void* d_grid, const void* d_ch_est, const float* d_noise_vars,
+                          int8_t* d_llr, uint64_t llr_stride, float* d_sinr_db, void* stream);
+/* One PUSCH from and to host memory (blocking): grid [grid_nof_ports][14][grid_nof_subc] cbf16, ch_est
+ * [layers][nof_rx_ports][14][grid_nof_subc] cbf16, noise_vars[nof_rx_ports] -> llr[G]; sinr_db may be NULL. */
+int nrphy_pusch_demodulate_host(nrphy_ctx_t* ctx, const nrphy_pusch_demod_cfg_t* cfg, const void* grid, uint32_t grid_nof_ports,
+                                uint32_t grid_nof_subc, const void* ch_est, const float* noise_vars, int8_t* llr, float* sinr_db);
+
 /* ---- other downlink grid writers ("next" row): NZP-CSI-RS generator -----------
  * Replaces nzp_csi_rs_generator::map (R/include/srsran/phy/upper/signal_processors/nzp_csi_rs_generator.h:
  * 39-90; impl R/lib/phy/upper/signal_processors/nzp_csi_rs_generator_impl.cpp:96-352 with the RE patterns of

@@ -109,6 +109,36 @@ class PuschDecoderCfg(C.Structure):
                 ("max_iterations", C.c_uint32), ("use_early_stop", C.c_uint32), ("new_data", C.c_uint32)]
 
 
+class PuschDemodCfg(C.Structure):
+    """nrphy_pusch_demod_cfg_t (pusch_demodulator::configuration + the equaliser)."""
+    _fields_ = [("rnti", C.c_uint32), ("n_id", C.c_uint32), ("qm", C.c_uint32), ("start_symbol_index", C.c_uint32),
+                ("nof_symbols", C.c_uint32), ("dmrs_symbol_mask", C.c_uint32), ("dmrs_type", C.c_uint32),
+                ("nof_cdm_groups_without_data", C.c_uint32), ("nof_tx_layers", C.c_uint32), ("nof_rx_ports", C.c_uint32),
+                ("rx_ports", C.c_uint32 * MAX_PORTS), ("equalizer", C.c_uint32), ("transform_precoding", C.c_uint32),
+                ("reserved_", C.c_uint32), ("prb_mask", C.c_uint64 * PRB_WORDS)]
+
+
+EQ_ZF = 0
+EQ_MMSE = 1
+
+
+def make_pusch_demod(*, prbs, qm=2, rnti=1, n_id=0, start_symbol=0, nof_symbols=14, dmrs_symbols=(), dmrs_type=1,
+                     nof_cdm_groups_without_data=2, nof_layers=1, rx_ports=(0,), equalizer=EQ_ZF, transform_precoding=0):
+    """A PuschDemodCfg from plain values (prbs: grid-indexed PRB numbers)."""
+    c = PuschDemodCfg()
+    c.rnti, c.n_id, c.qm = rnti, n_id, qm
+    c.start_symbol_index, c.nof_symbols = start_symbol, nof_symbols
+    c.dmrs_symbol_mask = sum(1 << l for l in set(dmrs_symbols))
+    c.dmrs_type, c.nof_cdm_groups_without_data = dmrs_type, nof_cdm_groups_without_data
+    c.nof_tx_layers, c.nof_rx_ports = nof_layers, len(rx_ports)
+    for i, p in enumerate(rx_ports):
+        c.rx_ports[i] = p
+    c.equalizer, c.transform_precoding = equalizer, transform_precoding
+    for i, w in enumerate(prb_mask_words(prbs)):
+        c.prb_mask[i] = w
+    return c
+
+
 class GridRe(C.Structure):
     """nrphy_grid_re_t: one resource element written from the host into a device grid."""
     _fields_ = [("port", C.c_uint16), ("symbol", C.c_uint16), ("subc", C.c_uint32), ("value", C.c_uint32)]
@@ -472,6 +502,15 @@ def declare(lib, prefix="nrphy_"):
     sig("dl_slot_amplitude_stats", P(AmplitudeStats), vp, u32, u32)
     sig("dl_slot_device_grid", vp, vp, u32)
     sig("dl_slot_stream", vp, vp, u32)
+    sig("channel_equalize", i32, vp, u32, u32, u32, u32, u32, vp, vp, vp, C.c_float, vp, vp, vp)
+    sig("channel_equalize_host", i32, vp, u32, u32, u32, u32, vp, vp, vp, C.c_float, vp, vp)
+    sig("pusch_demod_validate", i32, P(PuschDemodCfg), u32, u32)
+    sig("pusch_demod_codeword_bits", u64, P(PuschDemodCfg))
+    sig("pusch_demod_plan_create", i32, vp, u32, P(PuschDemodCfg), P(u32), u32, u32, u32, P(u64), P(vp))
+    sig("pusch_demod_plan_destroy", i32, vp)
+    sig("pusch_demod_plan_codeword_bits", u64, vp, u32)
+    sig("pusch_demod_run", i32, vp, vp, vp, vp, vp, u64, vp, vp)
+    sig("pusch_demodulate_host", i32, vp, P(PuschDemodCfg), vp, u32, u32, vp, vp, vp, vp)
     sig("pusch_decode_codeblock_host", i32, vp, P(LdpcRateDematcherCfg), u32, u32, C.c_float, vp, vp, i32, u8p, P(u32))
     return lib
 
@@ -504,4 +543,7 @@ ABI_SYMBOLS = [
     "nrphy_dl_slot_pdsch", "nrphy_dl_slot_pdcch", "nrphy_dl_slot_ssb", "nrphy_dl_slot_csi_rs", "nrphy_dl_slot_put",
     "nrphy_dl_slot_load_grid", "nrphy_dl_slot_modulate", "nrphy_dl_slot_poll", "nrphy_dl_slot_wait", "nrphy_dl_slot_iq",
     "nrphy_dl_slot_read_grid", "nrphy_dl_slot_device_grid", "nrphy_dl_slot_stream", "nrphy_dl_slot_amplitude_stats",
+    "nrphy_channel_equalize", "nrphy_channel_equalize_host", "nrphy_pusch_demod_validate", "nrphy_pusch_demod_codeword_bits",
+    "nrphy_pusch_demod_plan_create", "nrphy_pusch_demod_plan_destroy", "nrphy_pusch_demod_plan_codeword_bits",
+    "nrphy_pusch_demod_run", "nrphy_pusch_demodulate_host",
 ]

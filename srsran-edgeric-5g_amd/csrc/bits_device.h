@@ -226,6 +226,23 @@ __device__ __forceinline__ uint32_t wave_xor(uint32_t v)
          (uint32_t)__builtin_amdgcn_readlane((int)v, 32) ^ (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
 }
 
+// ---- Soft-bit descrambling: byte-wise sign flips (llr_descramble_kernel, the PUSCH demodulator) ----------------------
+// The four most significant bits of `nibble << 28` spread to byte masks: bit 31 -> byte 0 (lowest address) ... bit 28
+// -> byte 3.
+__device__ __forceinline__ uint32_t byte_masks_msb_first(uint32_t bits4)
+{
+  // bits4 holds the four bits in its low nibble, first soft bit in bit 3.
+  const uint32_t spread = ((bits4 >> 3) & 1u) | (((bits4 >> 2) & 1u) << 8) | (((bits4 >> 1) & 1u) << 16) | ((bits4 & 1u) << 24);
+  return spread * 0xFFu;
+}
+
+// Per byte: m ? -x : x  (m = 0xFF or 0x00 per byte).
+__device__ __forceinline__ uint32_t negate_bytes(uint32_t x, uint32_t m)
+{
+  const uint32_t a = x ^ m, b = m & 0x01010101u;
+  return ((a & 0x7F7F7F7Fu) + b) ^ (a & 0x80808080u); // b < 0x80 per byte: its top bit never takes part
+}
+
 // ---- Gold sequence (TS 38.211 Section 5.2.1) --------------------------------------------------------------
 // Generates `nwords` 32-bit words (MSB-first) of c(n) for n in [32*first_word, 32*(first_word + nwords)) into
 // the LDS array `out`, executed by one full wavefront.  x1 comes from the precomputed table, x2 from c_init:

@@ -2160,6 +2160,11 @@ bool demod_launch_params(uint32_t modulation, uint32_t span_len, DemodLaunch& p)
 
 } // namespace
 
+bool nrphy::demod_params(uint32_t modulation, uint32_t span_len, DemodLaunch& p)
+{
+  return demod_launch_params(modulation, span_len, p);
+}
+
 extern "C" int nrphy_demodulate_soft(nrphy_ctx_t* ctx, uint32_t modulation, uint32_t nof_spans, uint32_t span_len,
                                      const float* d_symbols, const float* d_noise_vars, int8_t* d_llr, void* stream)
 {

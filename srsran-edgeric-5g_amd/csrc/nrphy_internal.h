@@ -375,6 +375,52 @@ struct DemodLaunch {
 };
 hipError_t launch_demodulate_soft(const DemodLaunch& p, uint32_t nof_spans, const float* d_symbols, const float* d_noise,
                                   int8_t* d_llr, hipStream_t stream);
+// The host side of nrphy_demodulate_soft: parameters of a modulation for spans of span_len symbols (false: not one it demaps).
+bool demod_params(uint32_t modulation, uint32_t span_len, DemodLaunch& p);
+
+// ---- channel equaliser and PUSCH demodulator (receive side) -------------------------------------------------------------
+constexpr uint32_t PUSCH_DEMOD_THREADS = 256; // a work item is up to this many data RE of one OFDM symbol, one per lane
+struct PuschDemodDesc {                       // one PUSCH of a plan
+  uint32_t grid_index, nof_rx_ports, nof_layers, qm;
+  uint32_t equalizer, c_init, prb_first, dmrs_re_per_prb; // prb_first: its allocated PRBs at prbs[prb_first ...]
+  uint32_t rx_ports[NRPHY_MAX_PORTS];
+  uint8_t  dmrs_subc[NRPHY_NRE];              // the data subcarriers of a PRB on DM-RS symbols, ascending
+  uint32_t item_first, nof_items;
+  uint64_t ce_offset;                         // elements of d_ch_est
+};
+struct PuschDemodItem {
+  uint32_t pusch, symbol, dmrs;               // dmrs != 0: the symbol carries DM-RS
+  uint32_t re_first, count;                   // data RE [re_first, re_first + count) of the symbol
+  uint32_t bit_offset;                        // codeword bit of the first soft bit of the item
+  uint32_t span_pos, nof_vector;              // equalised symbols of the OFDM symbol before the item; the span's vector part
+};
+struct PuschDemodLaunch {
+  const PuschDemodDesc* desc;
+  const PuschDemodItem* items;
+  const uint16_t*       prbs;
+  const DemodLaunch*    demod;                // [4]: QPSK, 16-QAM, 64-QAM, 256-QAM
+  const GoldTables*     gold;
+  const uint32_t*       x1_words;
+  const uint32_t*       grid;
+  const uint32_t*       ch;
+  const float*          noise;                // [pusch][NRPHY_MAX_PORTS]
+  int8_t*               llr;
+  uint64_t              llr_stride;
+  double*               partial;              // [item][2]: sum and count of the finite equalised noise variances
+  float*                sinr;                 // may be null
+  uint32_t              grid_nof_ports, grid_nof_subc, n_pusch, n_items;
+};
+hipError_t launch_pusch_demod(const PuschDemodLaunch& p, hipStream_t stream);
+struct EqualizeLaunch {
+  uint32_t        algorithm, n_batch, nof_re, nof_layers, nof_rx_ports;
+  float           tx_scaling;
+  const uint32_t* rx;
+  const uint32_t* ch;
+  const float*    noise;
+  float*          eq;
+  float*          eq_nvars;
+};
+hipError_t launch_channel_equalize(const EqualizeLaunch& p, hipStream_t stream);
 hipError_t launch_grid_put(const uint32_t* d_index, const uint32_t* d_value, uint32_t n, uint32_t* d_grid, hipStream_t stream);
 
 // ---- PDCCH and SS/PBCH block ("next" row: other downlink grid writers) --------------------------------------------------

@@ -185,22 +185,6 @@ __global__ __launch_bounds__(TB_CRC_THREADS) void pusch_tb_crc_kernel(PuschAssem
 constexpr uint32_t DESCRAMBLE_CHUNK_WORDS = 2048;
 constexpr uint32_t DESCRAMBLE_THREADS     = 256;
 
-// The four most significant bits of `nibble << 28` spread to byte masks: bit 31 -> byte 0 (lowest address) ... bit 28
-// -> byte 3.
-__device__ __forceinline__ uint32_t byte_masks_msb_first(uint32_t bits4)
-{
-  // bits4 holds the four bits in its low nibble, first soft bit in bit 3.
-  const uint32_t spread = ((bits4 >> 3) & 1u) | (((bits4 >> 2) & 1u) << 8) | (((bits4 >> 1) & 1u) << 16) | ((bits4 & 1u) << 24);
-  return spread * 0xFFu;
-}
-
-// Per byte: m ? -x : x  (m = 0xFF or 0x00 per byte).
-__device__ __forceinline__ uint32_t negate_bytes(uint32_t x, uint32_t m)
-{
-  const uint32_t a = x ^ m, b = m & 0x01010101u;
-  return ((a & 0x7F7F7F7Fu) + b) ^ (a & 0x80808080u); // b < 0x80 per byte: its top bit never takes part
-}
-
 __global__ __launch_bounds__(DESCRAMBLE_THREADS) void llr_descramble_kernel(const GoldTables* gold, const uint32_t* x1_words,
                                                                             const uint32_t* __restrict__ c_init,
                                                                             const int8_t* __restrict__ in, size_t in_stride,

@@ -1,0 +1,448 @@
+// Host side of the channel equaliser and the PUSCH demodulator (pusch_demod_kernels.hip): validation, codeword sizes, the plan's
+// work list, and the host-span forms.  The plan does on the host what pusch_demodulator_impl::demodulate does before its loops
+// (pusch_demodulator_impl.cpp:135-160: the RE masks of data and DM-RS symbols, c_init) and cuts every OFDM symbol's data RE into
+// work items of up to PUSCH_DEMOD_THREADS, each with its codeword bit offset and its place in the symbol's demapper span.
+#include "nrphy_host_internal.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr uint32_t MAX_PRB_BITS = NRPHY_PRB_WORDS * 64;
+
+// Data subcarriers of a PRB on a DM-RS symbol: those dmrs_type::get_dmrs_prb_mask(cdm) leaves (R/include/srsran/phy/upper/
+// dmrs_mapping.h:76-91).  Type 1: CDM group 0 = even subcarriers, 1 = odd.  Type 2: group g = {2g, 2g+1, 2g+6, 2g+7}.
+// Returns false for a combination the type does not allow.
+bool dmrs_data_mask(uint32_t type, uint32_t cdm, uint32_t& mask)
+{
+  if (type == 1 && cdm >= 1 && cdm <= 2) {
+    mask = cdm == 1 ? 0xAAAU : 0U;
+    return true;
+  }
+  if (type == 2 && cdm >= 1 && cdm <= 3) {
+    mask = 0xFFFU;
+    for (uint32_t g = 0; g != cdm; ++g) {
+      mask &= ~((3U << (2 * g)) | (3U << (2 * g + 6)));
+    }
+    return true;
+  }
+  return false;
+}
+
+uint32_t popcount12(uint32_t m)
+{
+  return (uint32_t)__builtin_popcount(m & 0xFFFU);
+}
+
+uint32_t nof_prb(const nrphy_pusch_demod_cfg_t& c)
+{
+  uint32_t n = 0;
+  for (uint32_t w = 0; w != NRPHY_PRB_WORDS; ++w) {
+    n += (uint32_t)__builtin_popcountll(c.prb_mask[w]);
+  }
+  return n;
+}
+
+// Data RE of OFDM symbol l (0 outside the allocation's symbols).
+uint32_t symbol_re(const nrphy_pusch_demod_cfg_t& c, uint32_t l, uint32_t nprb, uint32_t dmrs_mask)
+{
+  if (l < c.start_symbol_index || l >= c.start_symbol_index + c.nof_symbols) {
+    return 0;
+  }
+  return nprb * (((c.dmrs_symbol_mask >> l) & 1U) ? popcount12(dmrs_mask) : NRPHY_NRE);
+}
+
+int validate(const nrphy_pusch_demod_cfg_t* c, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
+{
+  uint32_t dmrs_mask = 0;
+  if (c == nullptr || c->transform_precoding != 0 || !(c->qm == 2 || c->qm == 4 || c->qm == 6 || c->qm == 8) ||
+      c->nof_tx_layers < 1 || c->nof_tx_layers > 2 || c->nof_rx_ports < 1 || c->nof_rx_ports > NRPHY_MAX_PORTS ||
+      c->equalizer > NRPHY_EQ_MMSE || (c->nof_tx_layers == 2 && (c->equalizer != NRPHY_EQ_ZF ||
+                                                                  (c->nof_rx_ports != 2 && c->nof_rx_ports != 4))) ||
+      !dmrs_data_mask(c->dmrs_type, c->nof_cdm_groups_without_data, dmrs_mask)) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  if (grid_nof_subc == 0 || grid_nof_subc % NRPHY_NRE != 0 || grid_nof_subc > NRPHY_MAX_RB * NRPHY_NRE || grid_nof_ports == 0 ||
+      grid_nof_ports > NRPHY_MAX_PORTS) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  for (uint32_t i = 0; i != c->nof_rx_ports; ++i) {
+    if (c->rx_ports[i] >= grid_nof_ports) {
+      return NRPHY_ERR_ARGUMENT;
+    }
+    for (uint32_t j = 0; j != i; ++j) {
+      if (c->rx_ports[j] == c->rx_ports[i]) {
+        return NRPHY_ERR_ARGUMENT;
+      }
+    }
+  }
+  const uint32_t grid_prb = grid_nof_subc / NRPHY_NRE;
+  for (uint32_t b = grid_prb; b != MAX_PRB_BITS; ++b) {
+    if ((c->prb_mask[b / 64] >> (b % 64)) & 1U) {
+      return NRPHY_ERR_ARGUMENT;
+    }
+  }
+  if (c->start_symbol_index >= NRPHY_NSYMB || c->nof_symbols > NRPHY_NSYMB - c->start_symbol_index ||
+      (c->dmrs_symbol_mask >> NRPHY_NSYMB) != 0) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  const uint32_t nprb = nof_prb(*c);
+  uint32_t       nre  = 0;
+  for (uint32_t l = 0; l != NRPHY_NSYMB; ++l) {
+    nre += symbol_re(*c, l, nprb, dmrs_mask);
+  }
+  return nre == 0 ? NRPHY_ERR_ARGUMENT : NRPHY_OK;
+}
+
+} // namespace
+
+struct nrphy_pusch_demod_plan {
+  nrphy_ctx*            ctx = nullptr;
+  uint32_t              n = 0, n_items = 0;
+  uint32_t              nof_grids = 0, grid_nof_ports = 0, grid_nof_subc = 0;
+  std::vector<uint64_t> cw_bits;
+  void*                 d_arena   = nullptr;
+  PuschDemodDesc*       d_desc    = nullptr;
+  PuschDemodItem*       d_items   = nullptr;
+  uint16_t*             d_prbs    = nullptr;
+  DemodLaunch*          d_demod   = nullptr;
+  double*               d_partial = nullptr;
+};
+
+extern "C" int nrphy_pusch_demod_validate(const nrphy_pusch_demod_cfg_t* cfg, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
+{
+  return validate(cfg, grid_nof_ports, grid_nof_subc);
+}
+
+extern "C" uint64_t nrphy_pusch_demod_codeword_bits(const nrphy_pusch_demod_cfg_t* cfg)
+{
+  uint32_t dmrs_mask = 0;
+  if (cfg == nullptr || cfg->qm > 8 || cfg->nof_tx_layers > NRPHY_MAX_LAYERS ||
+      !dmrs_data_mask(cfg->dmrs_type, cfg->nof_cdm_groups_without_data, dmrs_mask)) {
+    return 0;
+  }
+  const uint32_t nprb = nof_prb(*cfg);
+  uint64_t       nre  = 0;
+  for (uint32_t l = 0; l != NRPHY_NSYMB; ++l) {
+    nre += symbol_re(*cfg, l, nprb, dmrs_mask);
+  }
+  return nre * cfg->nof_tx_layers * cfg->qm;
+}
+
+extern "C" int nrphy_pusch_demod_plan_destroy(nrphy_pusch_demod_plan_t* plan)
+{
+  if (plan == nullptr) {
+    return NRPHY_OK;
+  }
+  if (plan->d_arena != nullptr) {
+    (void)hipSetDevice(plan->ctx->device);
+    (void)hipFree(plan->d_arena);
+  }
+  delete plan;
+  return NRPHY_OK;
+}
+
+extern "C" int nrphy_pusch_demod_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_demod_cfg_t* cfgs,
+                                             const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports,
+                                             uint32_t grid_nof_subc, const uint64_t* ce_offset, nrphy_pusch_demod_plan_t** out)
+{
+  if (out == nullptr) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  *out = nullptr;
+  if (ctx == nullptr || n == 0 || cfgs == nullptr || grid_index == nullptr || ce_offset == nullptr || n > 65535U) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  std::vector<PuschDemodDesc> desc(n);
+  std::vector<PuschDemodItem> items;
+  std::vector<uint16_t>       prbs;
+  std::vector<uint64_t>       cw_bits(n);
+  for (uint32_t i = 0; i != n; ++i) {
+    const nrphy_pusch_demod_cfg_t& c = cfgs[i];
+    if (validate(&c, grid_nof_ports, grid_nof_subc) != NRPHY_OK || grid_index[i] >= nof_grids) {
+      return NRPHY_ERR_ARGUMENT;
+    }
+    uint32_t dmrs_mask = 0;
+    dmrs_data_mask(c.dmrs_type, c.nof_cdm_groups_without_data, dmrs_mask);
+    PuschDemodDesc& d = desc[i];
+    std::memset(&d, 0, sizeof(d));
+    d.grid_index      = grid_index[i];
+    d.nof_rx_ports    = c.nof_rx_ports;
+    d.nof_layers      = c.nof_tx_layers;
+    d.qm              = c.qm;
+    d.equalizer       = c.equalizer;
+    d.c_init          = c.rnti * (1U << 15) + c.n_id;
+    d.prb_first       = (uint32_t)prbs.size();
+    d.dmrs_re_per_prb = popcount12(dmrs_mask);
+    for (uint32_t k = 0, j = 0; k != NRPHY_NRE; ++k) {
+      if ((dmrs_mask >> k) & 1U) {
+        d.dmrs_subc[j++] = (uint8_t)k;
+      }
+    }
+    for (uint32_t k = 0; k != c.nof_rx_ports; ++k) {
+      d.rx_ports[k] = c.rx_ports[k];
+    }
+    d.ce_offset = ce_offset[i];
+    for (uint32_t b = 0; b != grid_nof_subc / NRPHY_NRE; ++b) {
+      if ((c.prb_mask[b / 64] >> (b % 64)) & 1U) {
+        prbs.push_back((uint16_t)b);
+      }
+    }
+    const uint32_t nprb = (uint32_t)prbs.size() - d.prb_first;
+    const uint32_t nb   = c.nof_tx_layers * c.qm;
+    uint32_t       bit  = 0;
+    d.item_first        = (uint32_t)items.size();
+    for (uint32_t l = 0; l != NRPHY_NSYMB; ++l) {
+      const uint32_t nre = symbol_re(c, l, nprb, dmrs_mask);
+      if (nre == 0) {
+        continue; // pusch_demodulator_impl.cpp:172-175
+      }
+      DemodLaunch dp;
+      demod_params(c.qm, nre * c.nof_tx_layers, dp);
+      for (uint32_t first = 0; first < nre; first += PUSCH_DEMOD_THREADS) {
+        PuschDemodItem it;
+        it.pusch      = i;
+        it.symbol     = l;
+        it.dmrs       = (c.dmrs_symbol_mask >> l) & 1U;
+        it.re_first   = first;
+        it.count      = std::min(PUSCH_DEMOD_THREADS, nre - first);
+        it.bit_offset = bit + first * nb;
+        it.span_pos   = first * c.nof_tx_layers;
+        it.nof_vector = dp.nof_vector;
+        items.push_back(it);
+      }
+      bit += nre * nb;
+    }
+    d.nof_items = (uint32_t)items.size() - d.item_first;
+    cw_bits[i]  = bit;
+  }
+  DemodLaunch demod[4];
+  for (uint32_t m = 0; m != 4; ++m) {
+    demod_params(2 * (m + 1), 0, demod[m]);
+  }
+  auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_desc    = 0;
+  const size_t o_items   = align(o_desc + desc.size() * sizeof(PuschDemodDesc));
+  const size_t o_prbs    = align(o_items + items.size() * sizeof(PuschDemodItem));
+  const size_t o_demod   = align(o_prbs + std::max<size_t>(prbs.size(), 1) * sizeof(uint16_t));
+  const size_t o_partial = align(o_demod + sizeof(demod));
+  const size_t bytes     = align(o_partial + items.size() * 2 * sizeof(double));
+  std::vector<uint8_t> host(o_partial, 0);
+  std::memcpy(host.data() + o_desc, desc.data(), desc.size() * sizeof(PuschDemodDesc));
+  std::memcpy(host.data() + o_items, items.data(), items.size() * sizeof(PuschDemodItem));
+  if (!prbs.empty()) {
+    std::memcpy(host.data() + o_prbs, prbs.data(), prbs.size() * sizeof(uint16_t));
+  }
+  std::memcpy(host.data() + o_demod, demod, sizeof(demod));
+  auto* plan           = new nrphy_pusch_demod_plan;
+  plan->ctx            = ctx;
+  plan->n              = n;
+  plan->n_items        = (uint32_t)items.size();
+  plan->nof_grids      = nof_grids;
+  plan->grid_nof_ports = grid_nof_ports;
+  plan->grid_nof_subc  = grid_nof_subc;
+  plan->cw_bits        = std::move(cw_bits);
+  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&plan->d_arena, bytes) != hipSuccess ||
+      hipMemcpy(plan->d_arena, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    nrphy_pusch_demod_plan_destroy(plan);
+    return NRPHY_ERR_DEVICE;
+  }
+  uint8_t* a       = (uint8_t*)plan->d_arena;
+  plan->d_desc     = (PuschDemodDesc*)(a + o_desc);
+  plan->d_items    = (PuschDemodItem*)(a + o_items);
+  plan->d_prbs     = (uint16_t*)(a + o_prbs);
+  plan->d_demod    = (DemodLaunch*)(a + o_demod);
+  plan->d_partial  = (double*)(a + o_partial);
+  *out             = plan;
+  return NRPHY_OK;
+}
+
+extern "C" uint64_t nrphy_pusch_demod_plan_codeword_bits(const nrphy_pusch_demod_plan_t* plan, uint32_t i)
+{
+  return (plan == nullptr || i >= plan->n) ? 0 : plan->cw_bits[i];
+}
+
+extern "C" int nrphy_pusch_demod_run(nrphy_pusch_demod_plan_t* plan, const void* d_grid, const void* d_ch_est,
+                                     const float* d_noise_vars, int8_t* d_llr, uint64_t llr_stride, float* d_sinr_db, void* stream)
+{
+  if (plan == nullptr || d_grid == nullptr || d_ch_est == nullptr || d_noise_vars == nullptr || d_llr == nullptr ||
+      (((uintptr_t)d_grid | (uintptr_t)d_ch_est | (uintptr_t)d_noise_vars | (uintptr_t)d_sinr_db) & 3U) != 0) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  if (plan->n > 1) {
+    for (uint64_t g : plan->cw_bits) {
+      if (llr_stride < g) {
+        return NRPHY_ERR_ARGUMENT;
+      }
+    }
+  }
+  PuschDemodLaunch p;
+  p.desc           = plan->d_desc;
+  p.items          = plan->d_items;
+  p.prbs           = plan->d_prbs;
+  p.demod          = plan->d_demod;
+  p.gold           = plan->ctx->d_gold;
+  p.x1_words       = plan->ctx->d_x1;
+  p.grid           = (const uint32_t*)d_grid;
+  p.ch             = (const uint32_t*)d_ch_est;
+  p.noise          = d_noise_vars;
+  p.llr            = d_llr;
+  p.llr_stride     = llr_stride;
+  p.partial        = plan->d_partial;
+  p.sinr           = d_sinr_db;
+  p.grid_nof_ports = plan->grid_nof_ports;
+  p.grid_nof_subc  = plan->grid_nof_subc;
+  p.n_pusch        = plan->n;
+  p.n_items        = plan->n_items;
+  HIP_TRY(hipSetDevice(plan->ctx->device));
+  HIP_TRY(launch_pusch_demod(p, stream ? (hipStream_t)stream : plan->ctx->stream));
+  return NRPHY_OK;
+}
+
+namespace {
+
+// Device buffers of a blocking host-span call, freed on every return path.
+struct DeviceBuffers {
+  std::vector<void*> ptrs;
+  void*              get(size_t bytes)
+  {
+    void* p = nullptr;
+    if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) {
+      return nullptr;
+    }
+    ptrs.push_back(p);
+    return p;
+  }
+  ~DeviceBuffers()
+  {
+    for (void* p : ptrs) {
+      (void)hipFree(p);
+    }
+  }
+};
+
+bool equalize_args_ok(uint32_t algorithm, uint32_t nof_layers, uint32_t nof_rx_ports, float tx_scaling)
+{
+  return algorithm <= NRPHY_EQ_MMSE && nof_rx_ports >= 1 && nof_rx_ports <= NRPHY_MAX_PORTS && tx_scaling > 0.f &&
+         (nof_layers == 1 || (nof_layers == 2 && algorithm == NRPHY_EQ_ZF && (nof_rx_ports == 2 || nof_rx_ports == 4)));
+}
+
+} // namespace
+
+extern "C" int nrphy_pusch_demodulate_host(nrphy_ctx_t* ctx, const nrphy_pusch_demod_cfg_t* cfg, const void* grid,
+                                           uint32_t grid_nof_ports, uint32_t grid_nof_subc, const void* ch_est,
+                                           const float* noise_vars, int8_t* llr, float* sinr_db)
+{
+  if (ctx == nullptr || grid == nullptr || ch_est == nullptr || noise_vars == nullptr || llr == nullptr ||
+      validate(cfg, grid_nof_ports, grid_nof_subc) != NRPHY_OK) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  const uint64_t G          = nrphy_pusch_demod_codeword_bits(cfg);
+  const size_t   grid_bytes = (size_t)grid_nof_ports * NRPHY_NSYMB * grid_nof_subc * 4;
+  const size_t   ce_bytes   = (size_t)cfg->nof_tx_layers * cfg->nof_rx_ports * NRPHY_NSYMB * grid_nof_subc * 4;
+  float          nv[NRPHY_MAX_PORTS] = {};
+  for (uint32_t i = 0; i != cfg->nof_rx_ports; ++i) {
+    nv[i] = noise_vars[i];
+  }
+  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
+  HIP_TRY(hipSetDevice(ctx->device));
+  DeviceBuffers buf;
+  void*   d_grid = buf.get(grid_bytes);
+  void*   d_ce   = buf.get(ce_bytes);
+  float*  d_nv   = (float*)buf.get(sizeof(nv));
+  int8_t* d_llr  = (int8_t*)buf.get(G);
+  float*  d_sinr = (float*)buf.get(sizeof(float));
+  if (d_grid == nullptr || d_ce == nullptr || d_nv == nullptr || d_llr == nullptr || d_sinr == nullptr) {
+    return NRPHY_ERR_DEVICE;
+  }
+  HIP_TRY(hipMemcpy(d_grid, grid, grid_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_ce, ch_est, ce_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_nv, nv, sizeof(nv), hipMemcpyHostToDevice));
+  const uint32_t            zero = 0;
+  const uint64_t            ce0  = 0;
+  nrphy_pusch_demod_plan_t* plan = nullptr;
+  int rc = nrphy_pusch_demod_plan_create(ctx, 1, cfg, &zero, 1, grid_nof_ports, grid_nof_subc, &ce0, &plan);
+  if (rc != NRPHY_OK) {
+    return rc;
+  }
+  rc = nrphy_pusch_demod_run(plan, d_grid, d_ce, d_nv, d_llr, G, d_sinr, ctx->stream);
+  if (rc == NRPHY_OK && (hipStreamSynchronize(ctx->stream) != hipSuccess ||
+                         hipMemcpy(llr, d_llr, G, hipMemcpyDeviceToHost) != hipSuccess ||
+                         (sinr_db != nullptr && hipMemcpy(sinr_db, d_sinr, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))) {
+    rc = NRPHY_ERR_DEVICE;
+  }
+  nrphy_pusch_demod_plan_destroy(plan);
+  return rc;
+}
+
+extern "C" int nrphy_channel_equalize(nrphy_ctx_t* ctx, uint32_t algorithm, uint32_t n_batch, uint32_t nof_re, uint32_t nof_layers,
+                                      uint32_t nof_rx_ports, const void* d_rx, const void* d_ch, const float* d_noise_vars,
+                                      float tx_scaling, float* d_eq, float* d_eq_nvars, void* stream)
+{
+  if (ctx == nullptr || !equalize_args_ok(algorithm, nof_layers, nof_rx_ports, tx_scaling) || n_batch > 65535U) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  if (n_batch == 0 || nof_re == 0) {
+    return NRPHY_OK;
+  }
+  if (d_rx == nullptr || d_ch == nullptr || d_noise_vars == nullptr || d_eq == nullptr || d_eq_nvars == nullptr ||
+      (((uintptr_t)d_rx | (uintptr_t)d_ch | (uintptr_t)d_noise_vars | (uintptr_t)d_eq_nvars) & 3U) != 0 ||
+      ((uintptr_t)d_eq & 7U) != 0) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  EqualizeLaunch p;
+  p.algorithm    = algorithm;
+  p.n_batch      = n_batch;
+  p.nof_re       = nof_re;
+  p.nof_layers   = nof_layers;
+  p.nof_rx_ports = nof_rx_ports;
+  p.tx_scaling   = tx_scaling;
+  p.rx           = (const uint32_t*)d_rx;
+  p.ch           = (const uint32_t*)d_ch;
+  p.noise        = d_noise_vars;
+  p.eq           = d_eq;
+  p.eq_nvars     = d_eq_nvars;
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(launch_channel_equalize(p, stream ? (hipStream_t)stream : ctx->stream));
+  return NRPHY_OK;
+}
+
+extern "C" int nrphy_channel_equalize_host(nrphy_ctx_t* ctx, uint32_t algorithm, uint32_t nof_re, uint32_t nof_layers,
+                                           uint32_t nof_rx_ports, const void* rx, const void* ch, const float* noise_vars,
+                                           float tx_scaling, float* eq, float* eq_nvars)
+{
+  if (ctx == nullptr || !equalize_args_ok(algorithm, nof_layers, nof_rx_ports, tx_scaling)) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  if (nof_re == 0) {
+    return NRPHY_OK;
+  }
+  if (rx == nullptr || ch == nullptr || noise_vars == nullptr || eq == nullptr || eq_nvars == nullptr) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  const size_t rx_bytes = (size_t)nof_rx_ports * nof_re * 4, ch_bytes = rx_bytes * nof_layers;
+  const size_t out      = (size_t)nof_re * nof_layers;
+  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
+  HIP_TRY(hipSetDevice(ctx->device));
+  DeviceBuffers buf;
+  void*  d_rx = buf.get(rx_bytes);
+  void*  d_ch = buf.get(ch_bytes);
+  float* d_nv = (float*)buf.get(nof_rx_ports * sizeof(float));
+  float* d_eq = (float*)buf.get(out * 8);
+  float* d_ev = (float*)buf.get(out * 4);
+  if (d_rx == nullptr || d_ch == nullptr || d_nv == nullptr || d_eq == nullptr || d_ev == nullptr) {
+    return NRPHY_ERR_DEVICE;
+  }
+  HIP_TRY(hipMemcpy(d_rx, rx, rx_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_ch, ch, ch_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_nv, noise_vars, nof_rx_ports * sizeof(float), hipMemcpyHostToDevice));
+  const int rc = nrphy_channel_equalize(ctx, algorithm, 1, nof_re, nof_layers, nof_rx_ports, d_rx, d_ch, d_nv, tx_scaling, d_eq,
+                                        d_ev, ctx->stream);
+  if (rc != NRPHY_OK) {
+    return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(hipMemcpy(eq, d_eq, out * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(eq_nvars, d_ev, out * 4, hipMemcpyDeviceToHost));
+  return NRPHY_OK;
+}

@@ -1,0 +1,384 @@
+// Channel equaliser and PUSCH demodulator for gfx950.
+//
+// Replaces channel_equalizer::equalize (R/lib/phy/upper/equalization/channel_equalizer_generic_impl.cpp:225-277 with the scalar
+// loops of equalize_zf_1xn.h:126-170, equalize_mmse_1xn.h and equalize_zf_2xn.h:182-252) and pusch_demodulator::demodulate
+// (R/lib/phy/upper/channel_processors/pusch/pusch_demodulator_impl.cpp:135-287): RE selection, equalisation, soft demapping,
+// descrambling and the post-equalisation SINR in one kernel.  The equaliser below is the one __device__ function both the
+// standalone call (nrphy_channel_equalize) and the fused kernel run; the demapper is demod_device.h's, the scrambling sequence
+// gold_sequence_blocks_wave's: the fused soft bits are those of equalise -> nrphy_demodulate_soft -> nrphy_llr_descramble.
+//
+// Work split (plan built on the host, pusch_demod_host.cpp): one workgroup per work item = up to 256 data RE of one OFDM symbol
+// of one PUSCH, one RE per lane.  A lane finds its subcarrier from the PUSCH's list of allocated PRBs and, on DM-RS symbols, the
+// data positions of a PRB; it loads its receive ports' grid words and the layers x ports estimate words (4 bytes each, lanes
+// adjacent along subcarriers), equalises in registers and demaps.  Wave 0 meanwhile generates the item's scrambling bits into
+// LDS.  The soft bits are staged in LDS with the destination's 16-byte phase and leave as 16-byte stores (bytes at the ends).
+// HBM-bound: per RE 4 (ports + layers x ports) bytes in, layers x qm bytes out.
+#include "bits_device.h"
+#include "demod_device.h"
+
+#include <hip/hip_runtime.h>
+
+namespace nrphy {
+namespace {
+
+constexpr float FLT_NORMAL_MIN = 1.17549435e-38f;
+constexpr float FLT_LARGEST    = 3.40282347e+38f;
+constexpr float F_INF          = __builtin_huge_valf();
+
+// std::isnormal
+__device__ __forceinline__ bool is_normal(float x)
+{
+  const float a = fabsf(x);
+  return a >= FLT_NORMAL_MIN && a <= FLT_LARGEST;
+}
+
+// cbf16 word (real part in the low half) -> complex float, exactly.
+__device__ __forceinline__ float2 cbf16_to_float2(uint32_t w)
+{
+  return make_float2(__uint_as_float(w << 16), __uint_as_float(w & 0xFFFF0000u));
+}
+
+// One RE of channel_equalizer::equalize, the reference's scalar arithmetic operation by operation (std::complex products written
+// out: (a + jb) conj(c + jd) = (ac + bd) + j(bc - ad)), contraction off, exact division.  y[i]: received word of receive port i;
+// h[l][i]: estimate of layer l at port i; nv[i]: port noise variances; nv_max: their maximum (std::max_element).  Out: symbol and
+// noise variance per layer.
+__device__ __forceinline__ void equalize_re(uint32_t algorithm, uint32_t nof_layers, uint32_t nof_ports, const uint32_t (&y)[NRPHY_MAX_PORTS],
+                                            const uint32_t (&h)[2][NRPHY_MAX_PORTS], const float (&nv)[NRPHY_MAX_PORTS], float nv_max,
+                                            float tx_scaling, float2 (&x)[2], float (&v)[2])
+{
+  x[0] = x[1] = make_float2(0.f, 0.f);
+  v[0] = v[1] = F_INF;
+  if (nof_layers == 1) {
+    // ZF: equalize_zf_single_tx_layer_reduction drops the ports whose variance is not in (0, inf), then equalize_zf_1xn checks
+    // every RE and port as MMSE does; together: a port counts where |h|^2 and its variance are normal and the variance positive.
+    const bool mmse   = algorithm == NRPHY_EQ_MMSE;
+    float      msq    = 0.f, nacc = 0.f;
+    float2     acc    = make_float2(0.f, 0.f);
+#pragma unroll
+    for (uint32_t i = 0; i != NRPHY_MAX_PORTS; ++i) {
+      if (i < nof_ports) {
+        const float2 r  = cbf16_to_float2(y[i]);
+        float2       c  = cbf16_to_float2(h[0][i]);
+        if (mmse) {
+          c = make_float2(__fmul_rn(c.x, tx_scaling), __fmul_rn(c.y, tx_scaling));
+        }
+        const float n = __fadd_rn(__fmul_rn(c.x, c.x), __fmul_rn(c.y, c.y));
+        if (is_normal(n) && is_normal(nv[i]) && nv[i] > 0.f) {
+          msq   = __fadd_rn(msq, n);
+          nacc  = __fadd_rn(nacc, __fmul_rn(n, nv[i]));
+          acc.x = __fadd_rn(acc.x, __fadd_rn(__fmul_rn(r.x, c.x), __fmul_rn(r.y, c.y)));
+          acc.y = __fadd_rn(acc.y, __fsub_rn(__fmul_rn(r.y, c.x), __fmul_rn(r.x, c.y)));
+        }
+      }
+    }
+    if (mmse) {
+      if (is_normal(msq) && is_normal(nacc)) {
+        const float rcp = __fdiv_rn(1.0f, __fadd_rn(__fmul_rn(msq, msq), nacc));
+        x[0]            = make_float2(__fmul_rn(__fmul_rn(acc.x, msq), rcp), __fmul_rn(__fmul_rn(acc.y, msq), rcp));
+        v[0]            = __fmul_rn(nacc, rcp);
+      }
+    } else {
+      const float d = __fmul_rn(tx_scaling, msq);
+      if (is_normal(d) && is_normal(nacc)) {
+        const float rcp = __fdiv_rn(1.0f, d);
+        x[0]            = make_float2(__fmul_rn(acc.x, rcp), __fmul_rn(acc.y, rcp));
+        v[0]            = __fmul_rn(__fmul_rn(nacc, rcp), rcp);
+      }
+    }
+    return;
+  }
+  // ZF, two layers (equalize_zf_2xn): H^H H = [n0 xi; conj(xi) n1], matched filter m = H^H y.
+  float  n0 = 0.f, n1 = 0.f;
+  float2 xi = make_float2(0.f, 0.f), m0 = make_float2(0.f, 0.f), m1 = make_float2(0.f, 0.f);
+#pragma unroll
+  for (uint32_t i = 0; i != NRPHY_MAX_PORTS; ++i) {
+    if (i < nof_ports) {
+      const float2 r = cbf16_to_float2(y[i]), c0 = cbf16_to_float2(h[0][i]), c1 = cbf16_to_float2(h[1][i]);
+      n0   = __fadd_rn(n0, __fadd_rn(__fmul_rn(c0.x, c0.x), __fmul_rn(c0.y, c0.y)));
+      n1   = __fadd_rn(n1, __fadd_rn(__fmul_rn(c1.x, c1.x), __fmul_rn(c1.y, c1.y)));
+      xi.x = __fadd_rn(xi.x, __fadd_rn(__fmul_rn(c0.x, c1.x), __fmul_rn(c0.y, c1.y)));
+      xi.y = __fadd_rn(xi.y, __fsub_rn(__fmul_rn(c0.x, c1.y), __fmul_rn(c0.y, c1.x)));
+      m0.x = __fadd_rn(m0.x, __fadd_rn(__fmul_rn(c0.x, r.x), __fmul_rn(c0.y, r.y)));
+      m0.y = __fadd_rn(m0.y, __fsub_rn(__fmul_rn(c0.x, r.y), __fmul_rn(c0.y, r.x)));
+      m1.x = __fadd_rn(m1.x, __fadd_rn(__fmul_rn(c1.x, r.x), __fmul_rn(c1.y, r.y)));
+      m1.y = __fadd_rn(m1.y, __fsub_rn(__fmul_rn(c1.x, r.y), __fmul_rn(c1.y, r.x)));
+    }
+  }
+  const float xi_sq  = __fadd_rn(__fmul_rn(xi.x, xi.x), __fmul_rn(xi.y, xi.y));
+  const float d_pinv = __fmul_rn(tx_scaling, __fsub_rn(__fmul_rn(n0, n1), xi_sq));
+  const float d_nv   = __fmul_rn(tx_scaling, d_pinv);
+  if (is_normal(d_pinv)) {
+    const float rcp = __fdiv_rn(1.0f, d_pinv), nrcp = __fdiv_rn(1.0f, d_nv);
+    // (n1 m0 - xi m1) / d and (n0 m1 - conj(xi) m0) / d
+    const float a0 = __fsub_rn(__fmul_rn(n1, m0.x), __fsub_rn(__fmul_rn(xi.x, m1.x), __fmul_rn(xi.y, m1.y)));
+    const float b0 = __fsub_rn(__fmul_rn(n1, m0.y), __fadd_rn(__fmul_rn(xi.x, m1.y), __fmul_rn(xi.y, m1.x)));
+    const float a1 = __fsub_rn(__fmul_rn(n0, m1.x), __fadd_rn(__fmul_rn(xi.x, m0.x), __fmul_rn(xi.y, m0.y)));
+    const float b1 = __fsub_rn(__fmul_rn(n0, m1.y), __fsub_rn(__fmul_rn(xi.x, m0.y), __fmul_rn(xi.y, m0.x)));
+    x[0]           = make_float2(__fmul_rn(a0, rcp), __fmul_rn(b0, rcp));
+    x[1]           = make_float2(__fmul_rn(a1, rcp), __fmul_rn(b1, rcp));
+    v[0]           = __fmul_rn(__fmul_rn(nv_max, n1), nrcp);
+    v[1]           = __fmul_rn(__fmul_rn(nv_max, n0), nrcp);
+  }
+}
+
+// std::max_element over the first n variances (the first of equal maxima; a leading NaN stays).
+__device__ __forceinline__ float max_noise(const float (&nv)[NRPHY_MAX_PORTS], uint32_t n)
+{
+  float m = nv[0];
+#pragma unroll
+  for (uint32_t i = 1; i != NRPHY_MAX_PORTS; ++i) {
+    if (i < n && m < nv[i]) {
+      m = nv[i];
+    }
+  }
+  return m;
+}
+
+__global__ __launch_bounds__(256) void channel_equalize_kernel(EqualizeLaunch p)
+{
+  const uint32_t re = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+  if (re >= p.nof_re) {
+    return;
+  }
+  const uint32_t P = p.nof_rx_ports, L = p.nof_layers;
+  uint32_t       y[NRPHY_MAX_PORTS] = {}, h[2][NRPHY_MAX_PORTS] = {};
+  float          nv[NRPHY_MAX_PORTS] = {};
+#pragma unroll
+  for (uint32_t i = 0; i != NRPHY_MAX_PORTS; ++i) {
+    if (i < P) {
+      y[i]  = p.rx[((size_t)b * P + i) * p.nof_re + re];
+      nv[i] = p.noise[(size_t)b * P + i];
+#pragma unroll
+      for (uint32_t l = 0; l != 2; ++l) {
+        if (l < L) {
+          h[l][i] = p.ch[(((size_t)b * L + l) * P + i) * p.nof_re + re];
+        }
+      }
+    }
+  }
+  float2 x[2];
+  float  v[2];
+  equalize_re(p.algorithm, L, P, y, h, nv, max_noise(nv, P), p.tx_scaling, x, v);
+  const size_t o = ((size_t)b * p.nof_re + re) * L;
+#pragma unroll
+  for (uint32_t l = 0; l != 2; ++l) {
+    if (l < L) {
+      reinterpret_cast<float2*>(p.eq)[o + l] = x[l];
+      p.eq_nvars[o + l]                      = v[l];
+    }
+  }
+}
+
+constexpr uint32_t SEQ_WORDS   = 160;                          // >= (31 + 256 * 16) / 32 + 2, and >= the 31 head words
+constexpr uint32_t STAGE_BYTES = PUSCH_DEMOD_THREADS * 16 + 16; // soft bits of an item at the destination's 16-byte phase
+
+struct PuschDemodShared {
+  Tables   t;
+  uint32_t seq[SEQ_WORDS];
+  double   red[2][PUSCH_DEMOD_THREADS / WAVE];
+  __attribute__((aligned(16))) uint8_t stage[STAGE_BYTES];
+};
+
+__device__ __forceinline__ double wave_sum(double x)
+{
+#pragma unroll
+  for (uint32_t o = WAVE / 2; o != 0; o >>= 1) {
+    x += __shfl_xor(x, o);
+  }
+  return x;
+}
+
+template <uint32_t MOD>
+__device__ __forceinline__ void pusch_demod_item(const PuschDemodLaunch& p, const PuschDemodItem& it, const PuschDemodDesc& d,
+                                                 PuschDemodShared& s)
+{
+  const DemodLaunch& dm   = p.demod[MOD / 2u - 1u];
+  const uint32_t     tid  = threadIdx.x, lane = tid % WAVE;
+  if constexpr (MOD >= NRPHY_MOD_QAM64) {
+    for (uint32_t k = tid; k < DEMOD_MAX_PAIRS * 16u; k += PUSCH_DEMOD_THREADS) {
+      s.t.line[k / 16u][k % 16u] = make_float2(dm.slope[k / 16u][k % 16u], dm.intercept[k / 16u][k % 16u]);
+    }
+  }
+  const uint32_t L = d.nof_layers, P = d.nof_rx_ports, nb = L * MOD;
+  const bool     active = tid < it.count;
+
+  // The lane's RE: data RE r of the symbol -> PRB of the allocation and subcarrier within it.
+  uint32_t y[NRPHY_MAX_PORTS] = {}, h[2][NRPHY_MAX_PORTS] = {};
+  if (active) {
+    const uint32_t r     = it.re_first + tid;
+    const uint32_t per   = it.dmrs ? d.dmrs_re_per_prb : NRPHY_NRE;
+    const uint32_t ord   = r / per, k = r - ord * per;
+    const uint32_t subc  = NRPHY_NRE * (uint32_t)p.prbs[d.prb_first + ord] + (it.dmrs ? (uint32_t)d.dmrs_subc[k] : k);
+    const size_t   nsubc = p.grid_nof_subc;
+#pragma unroll
+    for (uint32_t i = 0; i != NRPHY_MAX_PORTS; ++i) {
+      if (i < P) {
+        y[i] = p.grid[(((size_t)d.grid_index * p.grid_nof_ports + d.rx_ports[i]) * NRPHY_NSYMB + it.symbol) * nsubc + subc];
+#pragma unroll
+        for (uint32_t l = 0; l != 2; ++l) {
+          if (l < L) {
+            h[l][i] = p.ch[d.ce_offset + (((size_t)l * P + i) * NRPHY_NSYMB + it.symbol) * nsubc + subc];
+          }
+        }
+      }
+    }
+  }
+
+  // Wave 0: the item's scrambling bits c(n), n in [32 first_word, 32 (first_word + nwords)), into s.seq.
+  const uint32_t first_word = it.bit_offset >> 5;
+  const uint32_t nwords     = ((it.bit_offset & 31u) + it.count * nb + 31u) >> 5;
+  if (tid < WAVE) {
+    gold_sequence_blocks_wave(p.gold, d.c_init, first_word, nwords, s.seq, lane, [&](uint32_t base, uint32_t avail) {
+      for (uint32_t k = lane; k < avail; k += WAVE) {
+        s.seq[base + k] ^= p.x1_words[first_word + base + k];
+      }
+      wave_lds_fence();
+    });
+  }
+  __syncthreads();
+
+  LlrBytes out;
+  double   vsum = 0.0, vcnt = 0.0;
+  if (active) {
+    float nv[NRPHY_MAX_PORTS];
+#pragma unroll
+    for (uint32_t i = 0; i != NRPHY_MAX_PORTS; ++i) {
+      nv[i] = p.noise[(size_t)it.pusch * NRPHY_MAX_PORTS + i];
+    }
+    float2 x[2];
+    float  v[2];
+    equalize_re(d.equalizer, L, P, y, h, nv, max_noise(nv, P), 1.0f, x, v);
+#pragma unroll
+    for (uint32_t l = 0; l != 2; ++l) {
+      if (l < L) {
+        const uint32_t j = it.span_pos + tid * L + l; // position in the OFDM symbol's span (the reference's demapper call)
+        if (j < it.nof_vector) {
+          demodulate_symbol<MOD, true>(dm, s.t, j, x[l].x, x[l].y, v[l], out, l * MOD);
+        } else {
+          demodulate_symbol<MOD, false>(dm, s.t, j, x[l].x, x[l].y, v[l], out, l * MOD);
+        }
+        if (!__builtin_isinf(v[l])) { // pusch_demodulator_impl.cpp:203-215: the infinite variances (DC, dropped RE) are left out
+          vsum += (double)v[l];
+          vcnt += 1.0;
+        }
+      }
+    }
+    // Descrambling: this lane's nb <= 16 soft bits start at bit b0 of the sequence words.
+    const uint32_t b0   = (it.bit_offset & 31u) + tid * nb;
+    const uint64_t pair = ((uint64_t)s.seq[b0 >> 5] << 32) | s.seq[(b0 >> 5) + 1u];
+    const uint32_t bits = (uint32_t)(pair >> (48u - (b0 & 31u))) & 0xFFFFu; // first soft bit in bit 15
+#pragma unroll
+    for (uint32_t w = 0; w != 4; ++w) {
+      out.w[w] = negate_bytes(out.w[w], byte_masks_msb_first((bits >> (12u - 4u * w)) & 0xFu));
+    }
+  }
+
+  // SINR partial sums of the item: wave sums, then the four waves in order.
+  vsum = wave_sum(vsum);
+  vcnt = wave_sum(vcnt);
+  if (lane == 0) {
+    s.red[0][tid / WAVE] = vsum;
+    s.red[1][tid / WAVE] = vcnt;
+  }
+
+  // Soft bits staged at the destination's 16-byte phase.
+  int8_t*        dst   = p.llr + (size_t)it.pusch * p.llr_stride + it.bit_offset;
+  const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
+  if (active) {
+    uint8_t* st = s.stage + shift + tid * nb;
+#pragma unroll
+    for (uint32_t k = 0; k != 16; ++k) {
+      if (k < nb) {
+        st[k] = out.get(k);
+      }
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double* part = p.partial + 2u * (size_t)(blockIdx.x);
+    part[0]      = (s.red[0][0] + s.red[0][1]) + (s.red[0][2] + s.red[0][3]);
+    part[1]      = (s.red[1][0] + s.red[1][1]) + (s.red[1][2] + s.red[1][3]);
+  }
+  const uint32_t lo = shift, hi = shift + it.count * nb; // stage bytes [lo, hi) -> dst[0, hi - lo)
+  const uint32_t c_first = (lo + 15u) / 16u, c_last = hi / 16u;
+  int8_t*        base    = dst - shift; // 16-byte aligned
+  if (c_first >= c_last) {
+    for (uint32_t b = lo + tid; b < hi; b += PUSCH_DEMOD_THREADS) {
+      base[b] = (int8_t)s.stage[b];
+    }
+    return;
+  }
+  for (uint32_t c = c_first + tid; c < c_last; c += PUSCH_DEMOD_THREADS) {
+    reinterpret_cast<uint4*>(base)[c] = reinterpret_cast<const uint4*>(s.stage)[c];
+  }
+  const uint32_t head = 16u * c_first - lo, tail = hi - 16u * c_last;
+  if (tid < head) {
+    base[lo + tid] = (int8_t)s.stage[lo + tid];
+  } else if (tid >= 16u && tid < 16u + tail) {
+    const uint32_t b = 16u * c_last + (tid - 16u);
+    base[b]          = (int8_t)s.stage[b];
+  }
+}
+
+__global__ __launch_bounds__(PUSCH_DEMOD_THREADS) void pusch_demod_kernel(PuschDemodLaunch p)
+{
+  __shared__ PuschDemodShared s;
+  const PuschDemodItem  it = p.items[blockIdx.x];
+  const PuschDemodDesc& d  = p.desc[it.pusch]; // read in place: dmrs_subc is indexed per lane
+  switch (d.qm) { // workgroup-uniform
+    case NRPHY_MOD_QPSK:
+      pusch_demod_item<NRPHY_MOD_QPSK>(p, it, d, s);
+      break;
+    case NRPHY_MOD_QAM16:
+      pusch_demod_item<NRPHY_MOD_QAM16>(p, it, d, s);
+      break;
+    case NRPHY_MOD_QAM64:
+      pusch_demod_item<NRPHY_MOD_QAM64>(p, it, d, s);
+      break;
+    default:
+      pusch_demod_item<NRPHY_MOD_QAM256>(p, it, d, s);
+      break;
+  }
+}
+
+// One wave per PUSCH: its items' partial sums in a fixed order, then the SINR (pusch_demodulator_impl.cpp:255-262).
+__global__ __launch_bounds__(WAVE) void pusch_sinr_kernel(PuschDemodLaunch p)
+{
+  const uint32_t       lane = threadIdx.x;
+  const PuschDemodDesc d    = p.desc[blockIdx.x];
+  double               sum = 0.0, cnt = 0.0;
+  for (uint32_t k = lane; k < d.nof_items; k += WAVE) {
+    sum += p.partial[2u * (size_t)(d.item_first + k)];
+    cnt += p.partial[2u * (size_t)(d.item_first + k) + 1u];
+  }
+  sum = wave_sum(sum);
+  cnt = wave_sum(cnt);
+  if (lane == 0) {
+    p.sinr[blockIdx.x] = (cnt != 0.0 && sum > 0.0) ? (float)(-10.0 * log10(sum / cnt)) : F_INF;
+  }
+}
+
+} // namespace
+
+hipError_t launch_channel_equalize(const EqualizeLaunch& p, hipStream_t stream)
+{
+  if (p.n_batch == 0 || p.nof_re == 0) {
+    return hipSuccess;
+  }
+  hipLaunchKernelGGL(channel_equalize_kernel, dim3((p.nof_re + 255u) / 256u, p.n_batch), dim3(256), 0, stream, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_pusch_demod(const PuschDemodLaunch& p, hipStream_t stream)
+{
+  if (p.n_items == 0) {
+    return hipSuccess;
+  }
+  hipLaunchKernelGGL(pusch_demod_kernel, dim3(p.n_items), dim3(PUSCH_DEMOD_THREADS), 0, stream, p);
+  if (p.sinr != nullptr) {
+    hipLaunchKernelGGL(pusch_sinr_kernel, dim3(p.n_pusch), dim3(WAVE), 0, stream, p);
+  }
+  return hipGetLastError();
+}
+
+} // namespace nrphy

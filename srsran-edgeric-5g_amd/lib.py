@@ -361,6 +361,41 @@ class Context:
                                                C.byref(it)), "nrphy_ldpc_decode_host")
         return int(it.value), np.unpackbits(packed)[:k]
 
+    def channel_equalize(self, algorithm, n_batch, nof_re, nof_layers, nof_rx_ports, d_rx, d_ch, d_noise_vars, tx_scaling, d_eq,
+                         d_eq_nvars, stream=None):
+        """channel_equalizer::equalize for n_batch problems in device memory: d_rx [batch][port][re] cbf16, d_ch
+        [batch][layer][port][re] cbf16, d_noise_vars [batch][port] f32 -> d_eq [batch][re][layer] complex64, d_eq_nvars f32."""
+        _check(self.lib.nrphy_channel_equalize(self.handle, algorithm, n_batch, nof_re, nof_layers, nof_rx_ports, _dptr(d_rx),
+                                               _dptr(d_ch), _dptr(d_noise_vars), tx_scaling, _dptr(d_eq), _dptr(d_eq_nvars),
+                                               _stream(stream)), "nrphy_channel_equalize")
+
+    def channel_equalize_host(self, algorithm, rx, ch, noise_vars, tx_scaling=1.0):
+        """One problem from host memory: rx [port][re] and ch [layer][port][re] as raw cbf16 words (uint32) ->
+        (symbols complex64 [re][layer], noise variances float32 [re][layer])."""
+        rx = np.ascontiguousarray(rx, dtype=np.uint32)
+        ch = np.ascontiguousarray(ch, dtype=np.uint32)
+        noise_vars = np.ascontiguousarray(noise_vars, dtype=np.float32)
+        nof_layers, nof_ports, nof_re = ch.shape
+        eq = np.zeros((nof_re, nof_layers), np.complex64)
+        nv = np.zeros((nof_re, nof_layers), np.float32)
+        _check(self.lib.nrphy_channel_equalize_host(self.handle, algorithm, nof_re, nof_layers, nof_ports, rx.ctypes.data,
+                                                    ch.ctypes.data, noise_vars.ctypes.data, tx_scaling, eq.ctypes.data,
+                                                    nv.ctypes.data), "nrphy_channel_equalize_host")
+        return eq, nv
+
+    def pusch_demodulate_host(self, cfg, grid, ch_est, noise_vars):
+        """pusch_demodulator::demodulate for one PUSCH: grid [ports][14][subc] and ch_est [layers][rx][14][subc] as raw cbf16
+        words (uint32), noise_vars [rx] -> (descrambled int8 soft bits, SINR in dB)."""
+        grid = np.ascontiguousarray(grid, dtype=np.uint32)
+        ch_est = np.ascontiguousarray(ch_est, dtype=np.uint32)
+        nv = np.ascontiguousarray(noise_vars, dtype=np.float32)
+        out = np.zeros(pusch_demod_codeword_bits(cfg), np.int8)
+        sinr = C.c_float(0)
+        _check(self.lib.nrphy_pusch_demodulate_host(self.handle, C.byref(cfg), grid.ctypes.data, grid.shape[0], grid.shape[-1],
+                                                    ch_est.ctypes.data, nv.ctypes.data, out.ctypes.data, C.byref(sinr)),
+               "nrphy_pusch_demodulate_host")
+        return out, float(sinr.value)
+
     def dft(self, size, inverse, batch, d_in, d_out, stream=None):
         _check(self.lib.nrphy_dft_run(self.handle, size, int(inverse), batch, _dptr(d_in), _dptr(d_out), _stream(stream)),
                "nrphy_dft_run")
@@ -419,6 +454,50 @@ class PdschPlan:
             self.close()
         except Exception:
             pass
+
+
+class PuschDemodPlan:
+    """nrphy_pusch_demod_plan: PUSCHs over a batch of received grids; run() equalises, demaps and descrambles them in one launch."""
+
+    def __init__(self, ctx, cfgs, grid_indices, nof_grids, nof_ports, nof_subc, ce_offsets):
+        self.ctx = ctx
+        n = len(cfgs)
+        arr = (abi.PuschDemodCfg * n)(*cfgs)
+        gidx = (C.c_uint32 * n)(*grid_indices)
+        offs = (C.c_uint64 * n)(*ce_offsets)
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_pusch_demod_plan_create(ctx.handle, n, arr, gidx, nof_grids, nof_ports, nof_subc, offs, C.byref(h)),
+               "nrphy_pusch_demod_plan_create")
+        self.handle = h
+        self.n = n
+
+    def codeword_bits(self, i):
+        return int(self.ctx.lib.nrphy_pusch_demod_plan_codeword_bits(self.handle, i))
+
+    def run(self, d_grid, d_ch_est, d_noise_vars, d_llr, llr_stride, d_sinr=None, stream=None):
+        _check(self.ctx.lib.nrphy_pusch_demod_run(self.handle, _dptr(d_grid), _dptr(d_ch_est), _dptr(d_noise_vars), _dptr(d_llr),
+                                                  llr_stride, _dptr(d_sinr), _stream(stream)), "nrphy_pusch_demod_run")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.nrphy_pusch_demod_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pusch_demod_validate(cfg, grid_nof_ports, grid_nof_subc):
+    """nrphy_pusch_demod_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_pusch_demod_validate(C.byref(cfg), grid_nof_ports, grid_nof_subc))
+
+
+def pusch_demod_codeword_bits(cfg):
+    """G = data RE x layers x qm (host only)."""
+    return int(load().nrphy_pusch_demod_codeword_bits(C.byref(cfg)))
 
 
 class PdschAsyncQueue:
