@@ -459,6 +459,70 @@ int nrphy_pusch_demod_run(nrphy_pusch_demod_plan_t* plan, const void* d_grid, co
 int nrphy_pusch_demodulate_host(nrphy_ctx_t* ctx, const nrphy_pusch_demod_cfg_t* cfg, const void* grid, uint32_t grid_nof_ports,
                                 uint32_t grid_nof_subc, const void* ch_est, const float* noise_vars, int8_t* llr, float* sinr_db);
 
+/* ---- receive side: PUSCH DM-RS channel estimator ------------------------------------------------------------------------
+ * Replaces dmrs_pusch_estimator::estimate (R/lib/phy/upper/signal_processors/dmrs_pusch_estimator_impl.cpp:71-212, with
+ * port_channel_estimator_average_impl::compute, filter smoothing and CFO compensation on: the PUSCH processor's setting) and the
+ * PUSCH processor's DC step (pusch_processor_impl.cpp:182-199).  Per (receive port, layer): LS estimates of the DM-RS of every
+ * DM-RS symbol, the CFO from the first two, derotation and averaging, scaling by 1 / (nof DM-RS symbols x scaling), virtual
+ * pilots and the raised-cosine FIR, RSRP, EPRE, noise variance and SNR, the time alignment from a 4096-point inverse DFT (bins
+ * [0, 144) against [3952, 4096), delay on ties), linear interpolation to every subcarrier, cbf16 rounding, the per-symbol CFO
+ * rotation (rounded again, as the reference does) and the DC subcarrier zeroed.  DM-RS type 1 only (ports 1000 and 1001: layer 1
+ * takes w_f = -1 on every odd pilot), normal cyclic prefix, no frequency hopping.  Receive port i reads grid port rx_ports[i]. */
+#define NRPHY_PUSCH_CHEST_NO_DC 0xFFFFFFFFu
+#define NRPHY_PUSCH_CHEST_MAX_LAYERS 2
+typedef struct nrphy_pusch_chest_cfg {
+  uint32_t numerology;                /* 0..4 */
+  uint32_t slot_index;                /* slot within the frame: < 10 * 2^numerology */
+  uint32_t scrambling_id;             /* N_ID, 0..65535 */
+  uint32_t n_scid;                    /* 0 or 1 */
+  float    scaling;                   /* beta: DM-RS-to-data amplitude, > 0 and finite */
+  uint32_t dmrs_type;                 /* must be 1 */
+  uint32_t dmrs_symbol_mask;          /* bit l = symbol l carries DM-RS; every bit inside [start, start + nof) */
+  uint32_t start_symbol_index, nof_symbols;
+  uint32_t nof_tx_layers;             /* 1 or 2 */
+  uint32_t nof_rx_ports;              /* 1..4 */
+  uint32_t rx_ports[NRPHY_MAX_PORTS]; /* grid port of receive port i */
+  uint32_t dc_position;               /* grid subcarrier of DC, or NRPHY_PUSCH_CHEST_NO_DC */
+  uint64_t prb_mask[NRPHY_PRB_WORDS]; /* allocated PRBs, grid-indexed */
+} nrphy_pusch_chest_cfg_t;
+/* What channel_estimate holds per (PUSCH, receive port, layer). */
+typedef struct nrphy_pusch_chest_meas {
+  float    noise_var; /* sum |rx - beta h pilot e^{j 2 pi epoch cfo}|^2 / (pilots - 1), at least rsrp / 1e10 */
+  float    rsrp;      /* mean |beta h|^2 over the pilots */
+  float    epre;      /* mean |rx|^2 over the pilots */
+  float    snr;       /* linear: (rsrp / beta^2) / noise_var */
+  float    ta_s;      /* time alignment, seconds: ta_bins / (4096 SCS) */
+  int32_t  ta_bins;   /* signed inverse-DFT bin of the peak */
+  float    cfo_hz;    /* NaN with a single DM-RS symbol */
+  uint32_t reserved_;
+} nrphy_pusch_chest_meas_t;
+typedef struct nrphy_pusch_chest_plan nrphy_pusch_chest_plan_t;
+/* NRPHY_OK, or NRPHY_ERR_ARGUMENT for: DM-RS type other than 1; layers other than 1 or 2; no rx port, more than 4, one outside
+ * the grid or repeated; PRBs beyond the grid or none; symbols beyond the slot; no DM-RS symbol in [start, start + nof) or a
+ * DM-RS bit outside it; numerology above 4 or slot_index >= 10 * 2^numerology; scrambling_id above 65535, n_scid above 1;
+ * scaling not positive and finite; dc_position neither NRPHY_PUSCH_CHEST_NO_DC nor inside the grid.  No device work. */
+int nrphy_pusch_chest_validate(const nrphy_pusch_chest_cfg_t* cfg, uint32_t grid_nof_ports, uint32_t grid_nof_subc);
+/* n PUSCHs; PUSCH i reads grid grid_index[i] of [nof_grids][grid_nof_ports][14][grid_nof_subc] cbf16 and writes its estimate at
+ * element ce_offset[i] of d_ch_est: [layer][rx port i][14][grid_nof_subc] cbf16, the convention of nrphy_pusch_demod_plan_create
+ * (one buffer feeds both).  Validates every configuration, precomputes the filter taps, c_init per DM-RS symbol and the symbol
+ * epochs, and allocates the plan's scratch (blocking). */
+int nrphy_pusch_chest_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_chest_cfg_t* cfgs, const uint32_t* grid_index,
+                                  uint32_t nof_grids, uint32_t grid_nof_ports, uint32_t grid_nof_subc, const uint64_t* ce_offset,
+                                  nrphy_pusch_chest_plan_t** plan);
+int nrphy_pusch_chest_plan_destroy(nrphy_pusch_chest_plan_t* plan);
+/* Writes, for every PUSCH, layer and receive port, the allocated PRBs' subcarriers of symbols [start, start + nof) of the
+ * estimate and nothing else; d_noise_vars: [n][NRPHY_MAX_PORTS] f32, entry i of row p = layer 0's noise variance of receive port
+ * i (what nrphy_pusch_demod_run reads; the other entries are left alone); d_meas (may be NULL):
+ * [n][NRPHY_MAX_PORTS][NRPHY_PUSCH_CHEST_MAX_LAYERS].  Asynchronous on `stream`; allocates nothing and touches no host memory
+ * (capturable).  Runs of one plan must be ordered: the plan owns its scratch. */
+int nrphy_pusch_chest_run(nrphy_pusch_chest_plan_t* plan, const void* d_grid, void* d_ch_est, float* d_noise_vars,
+                          nrphy_pusch_chest_meas_t* d_meas, void* stream);
+/* One PUSCH from and to host memory (blocking, on the GPU): grid [grid_nof_ports][14][grid_nof_subc] cbf16 -> ch_est
+ * [layers][nof_rx_ports][14][grid_nof_subc] cbf16 (only the allocated region is written), noise_vars[nof_rx_ports], meas
+ * [nof_rx_ports][NRPHY_PUSCH_CHEST_MAX_LAYERS] (may be NULL). */
+int nrphy_pusch_chest_host(nrphy_ctx_t* ctx, const nrphy_pusch_chest_cfg_t* cfg, const void* grid, uint32_t grid_nof_ports,
+                           uint32_t grid_nof_subc, void* ch_est, float* noise_vars, nrphy_pusch_chest_meas_t* meas);
+
 /* ---- other downlink grid writers ("next" row): NZP-CSI-RS generator -----------
  * Replaces nzp_csi_rs_generator::map (R/include/srsran/phy/upper/signal_processors/nzp_csi_rs_generator.h:
  * 39-90; impl R/lib/phy/upper/signal_processors/nzp_csi_rs_generator_impl.cpp:96-352 with the RE patterns of

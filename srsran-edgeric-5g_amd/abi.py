@@ -139,6 +139,40 @@ def make_pusch_demod(*, prbs, qm=2, rnti=1, n_id=0, start_symbol=0, nof_symbols=
     return c
 
 
+PUSCH_CHEST_NO_DC = 0xFFFFFFFF
+PUSCH_CHEST_MAX_LAYERS = 2
+
+
+class PuschChestCfg(C.Structure):
+    """nrphy_pusch_chest_cfg_t (dmrs_pusch_estimator::configuration + the PUSCH processor's DC position)."""
+    _fields_ = [("numerology", C.c_uint32), ("slot_index", C.c_uint32), ("scrambling_id", C.c_uint32), ("n_scid", C.c_uint32),
+                ("scaling", C.c_float), ("dmrs_type", C.c_uint32), ("dmrs_symbol_mask", C.c_uint32),
+                ("start_symbol_index", C.c_uint32), ("nof_symbols", C.c_uint32), ("nof_tx_layers", C.c_uint32),
+                ("nof_rx_ports", C.c_uint32), ("rx_ports", C.c_uint32 * MAX_PORTS), ("dc_position", C.c_uint32),
+                ("prb_mask", C.c_uint64 * PRB_WORDS)]
+
+
+class PuschChestMeas(C.Structure):
+    """nrphy_pusch_chest_meas_t: what channel_estimate holds per (PUSCH, receive port, layer)."""
+    _fields_ = [("noise_var", C.c_float), ("rsrp", C.c_float), ("epre", C.c_float), ("snr", C.c_float), ("ta_s", C.c_float),
+                ("ta_bins", C.c_int32), ("cfo_hz", C.c_float), ("reserved_", C.c_uint32)]
+
+
+def make_pusch_chest(*, prbs, numerology=0, slot_index=0, scrambling_id=0, n_scid=0, scaling=1.0, dmrs_type=1,
+                     dmrs_symbols=(2,), start_symbol=0, nof_symbols=14, nof_layers=1, rx_ports=(0,), dc_position=None):
+    """A PuschChestCfg from plain values (prbs: grid-indexed PRB numbers; dc_position None: no DC)."""
+    c = PuschChestCfg()
+    c.numerology, c.slot_index, c.scrambling_id, c.n_scid, c.scaling = numerology, slot_index, scrambling_id, n_scid, scaling
+    c.dmrs_type, c.dmrs_symbol_mask = dmrs_type, sum(1 << l for l in set(dmrs_symbols))
+    c.start_symbol_index, c.nof_symbols, c.nof_tx_layers, c.nof_rx_ports = start_symbol, nof_symbols, nof_layers, len(rx_ports)
+    for i, p in enumerate(rx_ports):
+        c.rx_ports[i] = p
+    c.dc_position = PUSCH_CHEST_NO_DC if dc_position is None else dc_position
+    for i, w in enumerate(prb_mask_words(prbs)):
+        c.prb_mask[i] = w
+    return c
+
+
 class GridRe(C.Structure):
     """nrphy_grid_re_t: one resource element written from the host into a device grid."""
     _fields_ = [("port", C.c_uint16), ("symbol", C.c_uint16), ("subc", C.c_uint32), ("value", C.c_uint32)]
@@ -511,6 +545,11 @@ def declare(lib, prefix="nrphy_"):
     sig("pusch_demod_plan_codeword_bits", u64, vp, u32)
     sig("pusch_demod_run", i32, vp, vp, vp, vp, vp, u64, vp, vp)
     sig("pusch_demodulate_host", i32, vp, P(PuschDemodCfg), vp, u32, u32, vp, vp, vp, vp)
+    sig("pusch_chest_validate", i32, P(PuschChestCfg), u32, u32)
+    sig("pusch_chest_plan_create", i32, vp, u32, P(PuschChestCfg), P(u32), u32, u32, u32, P(u64), P(vp))
+    sig("pusch_chest_plan_destroy", i32, vp)
+    sig("pusch_chest_run", i32, vp, vp, vp, vp, vp, vp)
+    sig("pusch_chest_host", i32, vp, P(PuschChestCfg), vp, u32, u32, vp, vp, vp)
     sig("pusch_decode_codeblock_host", i32, vp, P(LdpcRateDematcherCfg), u32, u32, C.c_float, vp, vp, i32, u8p, P(u32))
     return lib
 
@@ -546,4 +585,6 @@ ABI_SYMBOLS = [
     "nrphy_channel_equalize", "nrphy_channel_equalize_host", "nrphy_pusch_demod_validate", "nrphy_pusch_demod_codeword_bits",
     "nrphy_pusch_demod_plan_create", "nrphy_pusch_demod_plan_destroy", "nrphy_pusch_demod_plan_codeword_bits",
     "nrphy_pusch_demod_run", "nrphy_pusch_demodulate_host",
+    "nrphy_pusch_chest_validate", "nrphy_pusch_chest_plan_create", "nrphy_pusch_chest_plan_destroy", "nrphy_pusch_chest_run",
+    "nrphy_pusch_chest_host",
 ]

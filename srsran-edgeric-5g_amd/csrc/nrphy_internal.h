@@ -421,6 +421,42 @@ struct EqualizeLaunch {
   float*          eq_nvars;
 };
 hipError_t launch_channel_equalize(const EqualizeLaunch& p, hipStream_t stream);
+// ---- PUSCH DM-RS channel estimator (receive side) -----------------------------------------------------------------------
+constexpr uint32_t PUSCH_CHEST_TA_WINDOW  = 144;  // time_alignment_estimator_dft_impl: (144 / 2) * 4096 / 2048 bins per side
+constexpr uint32_t PUSCH_CHEST_MAX_LAYERS = 2;
+struct PuschChestDesc {                        // one PUSCH of a plan
+  uint32_t grid_index, nof_rx_ports, nof_layers, nprb;
+  uint32_t prb_first;                          // its allocated PRBs at prbs[prb_first ...]
+  uint32_t first_symbol, nof_symbols, nof_dmrs; // nof_dmrs: DM-RS symbols, dmrs_symbol[0 .. nof_dmrs)
+  uint32_t nwords;                             // Gold words per DM-RS symbol (from c(0), up to the last allocated PRB)
+  uint32_t ntaps, nof_v;                       // FIR taps (5, 11, 15) and virtual pilots per side
+  uint32_t dc;                                 // grid subcarrier whose estimate is zeroed (NRPHY_PUSCH_CHEST_NO_DC: none)
+  uint32_t scs_hz;
+  uint32_t rx_ports[NRPHY_MAX_PORTS];
+  uint32_t dmrs_symbol[NRPHY_NSYMB];
+  uint32_t c_init[NRPHY_NSYMB];                // per DM-RS symbol
+  float    epoch[NRPHY_NSYMB];                 // symbol start epochs (initialize_symbol_start_epochs), in symbols
+  float    taps[16];
+  float    beta, ls_scale;                     // ls_scale = 1 / (nof_dmrs * beta), in float
+  uint64_t ce_offset;                          // elements of d_ch_est
+  uint64_t row_offset;                         // words of the scratch rows: [port][layer][12 nprb]
+};
+struct PuschChestLaunch {
+  const PuschChestDesc*     desc;
+  const uint32_t*           jobs;              // (pusch << 8) | (port << 4) | layer
+  const uint16_t*           prbs;
+  const float2*             twiddle;           // [2048]: e^{j 2 pi i / 2048}
+  const GoldTables*         gold;
+  const uint32_t*           x1_words;
+  const uint32_t*           grid;
+  uint32_t*                 ch;
+  float*                    noise_vars;        // [pusch][NRPHY_MAX_PORTS]
+  nrphy_pusch_chest_meas_t* meas;              // [pusch][NRPHY_MAX_PORTS][PUSCH_CHEST_MAX_LAYERS], may be null
+  uint32_t*                 rows;              // scratch: interpolated rows, cbf16
+  float2*                   rot;               // scratch: [job][14] CFO phasors
+  uint32_t                  grid_nof_ports, grid_nof_subc, n_jobs;
+};
+hipError_t launch_pusch_chest(const PuschChestLaunch& p, hipStream_t stream);
 hipError_t launch_grid_put(const uint32_t* d_index, const uint32_t* d_value, uint32_t n, uint32_t* d_grid, hipStream_t stream);
 
 // ---- PDCCH and SS/PBCH block ("next" row: other downlink grid writers) --------------------------------------------------

@@ -1,0 +1,323 @@
+// Host side of the PUSCH DM-RS channel estimator (pusch_chest_kernels.hip): validation, and the plan's per-PUSCH constants --
+// what dmrs_pusch_estimator_impl and port_channel_estimator_average_impl compute before touching the grid: c_init per DM-RS
+// symbol (dmrs_pusch_estimator_impl.cpp:136-149), the symbol start epochs (initialize_symbol_start_epochs,
+// port_channel_estimator_average_impl.cpp:454-466) and the raised-cosine taps (filter_type, :62-111), in float32 and in the
+// reference's order of operations.
+#include "nrphy_host_internal.h"
+
+#include <cmath>
+
+namespace {
+
+constexpr uint32_t MAX_PRB_BITS = NRPHY_PRB_WORDS * 64;
+
+// port_channel_estimator_average_impl.cpp:41-47
+constexpr float RC_FILTER[31] = {-0.0641253f, -0.0660711f, -0.0611526f, -0.0485918f, -0.0281126f, 0.0000000f, 0.0348830f, 0.0751249f,
+                                 0.1188406f,  0.1637874f,  0.2075139f,  0.2475302f,  0.2814857f,  0.3073415f, 0.3235207f, 0.3290274f,
+                                 0.3235207f,  0.3073415f,  0.2814857f,  0.2475302f,  0.2075139f,  0.1637874f, 0.1188406f, 0.0751249f,
+                                 0.0348830f,  0.0000000f,  -0.0281126f, -0.0485918f, -0.0611526f, -0.0660711f, -0.0641253f};
+
+uint32_t nof_prb(const nrphy_pusch_chest_cfg_t& c)
+{
+  uint32_t n = 0;
+  for (uint32_t w = 0; w != NRPHY_PRB_WORDS; ++w) {
+    n += (uint32_t)__builtin_popcountll(c.prb_mask[w]);
+  }
+  return n;
+}
+
+int validate(const nrphy_pusch_chest_cfg_t* c, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
+{
+  if (c == nullptr || c->dmrs_type != 1 || c->nof_tx_layers < 1 || c->nof_tx_layers > NRPHY_PUSCH_CHEST_MAX_LAYERS ||
+      c->nof_rx_ports < 1 || c->nof_rx_ports > NRPHY_MAX_PORTS || c->numerology > 4 ||
+      c->slot_index >= (10U << c->numerology) || c->scrambling_id > 65535U || c->n_scid > 1 || !std::isfinite(c->scaling) ||
+      !(c->scaling > 0.f)) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  if (grid_nof_subc == 0 || grid_nof_subc % NRPHY_NRE != 0 || grid_nof_subc > NRPHY_MAX_RB * NRPHY_NRE || grid_nof_ports == 0 ||
+      grid_nof_ports > NRPHY_MAX_PORTS) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  for (uint32_t i = 0; i != c->nof_rx_ports; ++i) {
+    if (c->rx_ports[i] >= grid_nof_ports) {
+      return NRPHY_ERR_ARGUMENT;
+    }
+    for (uint32_t j = 0; j != i; ++j) {
+      if (c->rx_ports[j] == c->rx_ports[i]) {
+        return NRPHY_ERR_ARGUMENT;
+      }
+    }
+  }
+  const uint32_t grid_prb = grid_nof_subc / NRPHY_NRE;
+  for (uint32_t b = grid_prb; b != MAX_PRB_BITS; ++b) {
+    if ((c->prb_mask[b / 64] >> (b % 64)) & 1U) {
+      return NRPHY_ERR_ARGUMENT;
+    }
+  }
+  if (nof_prb(*c) == 0) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  if (c->nof_symbols == 0 || c->start_symbol_index >= NRPHY_NSYMB || c->nof_symbols > NRPHY_NSYMB - c->start_symbol_index) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  // The reference sizes its pilot buffer from the whole mask and reads only the symbols of [start, start + nof).
+  const uint32_t inside = ((1U << c->nof_symbols) - 1U) << c->start_symbol_index;
+  if ((c->dmrs_symbol_mask & inside) == 0 || (c->dmrs_symbol_mask & ~inside) != 0) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  if (c->dc_position != NRPHY_PUSCH_CHEST_NO_DC && c->dc_position >= grid_nof_subc) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  return NRPHY_OK;
+}
+
+// filter_type(nof_rb, stride 2): taps resampled from RC_FILTER and normalised, in float as the reference does.
+uint32_t filter_taps(uint32_t nof_rb, float* taps)
+{
+  const uint32_t stride = 2;
+  nof_rb                = std::min(nof_rb, 3U);
+  uint32_t nof_out      = (nof_rb * 10 + 1) / 2 / stride;
+  uint32_t n            = 31 / 2 - nof_out * stride;
+  nof_out               = 2 * nof_out + 1;
+  float total           = 0;
+  for (uint32_t i = 0; i != nof_out; ++i) {
+    taps[i] = RC_FILTER[n];
+    total += taps[i];
+    n += stride;
+  }
+  const float rcp = 1 / total;
+  for (uint32_t i = 0; i != nof_out; ++i) {
+    taps[i] = taps[i] * rcp;
+  }
+  return nof_out;
+}
+
+} // namespace
+
+struct nrphy_pusch_chest_plan {
+  nrphy_ctx*      ctx = nullptr;
+  uint32_t        n = 0, n_jobs = 0;
+  uint32_t        nof_grids = 0, grid_nof_ports = 0, grid_nof_subc = 0;
+  void*           d_arena = nullptr;
+  PuschChestDesc* d_desc  = nullptr;
+  uint32_t*       d_jobs  = nullptr;
+  uint16_t*       d_prbs  = nullptr;
+  float2*         d_tw    = nullptr;
+  uint32_t*       d_rows  = nullptr;
+  float2*         d_rot   = nullptr;
+};
+
+extern "C" int nrphy_pusch_chest_validate(const nrphy_pusch_chest_cfg_t* cfg, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
+{
+  return validate(cfg, grid_nof_ports, grid_nof_subc);
+}
+
+extern "C" int nrphy_pusch_chest_plan_destroy(nrphy_pusch_chest_plan_t* plan)
+{
+  if (plan == nullptr) {
+    return NRPHY_OK;
+  }
+  if (plan->d_arena != nullptr) {
+    (void)hipSetDevice(plan->ctx->device);
+    (void)hipFree(plan->d_arena);
+  }
+  delete plan;
+  return NRPHY_OK;
+}
+
+extern "C" int nrphy_pusch_chest_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_chest_cfg_t* cfgs,
+                                             const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports,
+                                             uint32_t grid_nof_subc, const uint64_t* ce_offset, nrphy_pusch_chest_plan_t** out)
+{
+  if (out == nullptr) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  *out = nullptr;
+  if (ctx == nullptr || n == 0 || cfgs == nullptr || grid_index == nullptr || ce_offset == nullptr || n > 65535U) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  std::vector<PuschChestDesc> desc(n);
+  std::vector<uint32_t>       jobs;
+  std::vector<uint16_t>       prbs;
+  uint64_t                    row_words = 0;
+  for (uint32_t i = 0; i != n; ++i) {
+    const nrphy_pusch_chest_cfg_t& c = cfgs[i];
+    if (validate(&c, grid_nof_ports, grid_nof_subc) != NRPHY_OK || grid_index[i] >= nof_grids) {
+      return NRPHY_ERR_ARGUMENT;
+    }
+    PuschChestDesc& d = desc[i];
+    std::memset(&d, 0, sizeof(d));
+    d.grid_index   = grid_index[i];
+    d.nof_rx_ports = c.nof_rx_ports;
+    d.nof_layers   = c.nof_tx_layers;
+    d.prb_first    = (uint32_t)prbs.size();
+    for (uint32_t b = 0; b != grid_nof_subc / NRPHY_NRE; ++b) {
+      if ((c.prb_mask[b / 64] >> (b % 64)) & 1U) {
+        prbs.push_back((uint16_t)b);
+      }
+    }
+    d.nprb         = (uint32_t)prbs.size() - d.prb_first;
+    d.nwords       = (NRPHY_NRE * ((uint32_t)prbs.back() + 1) + 31) / 32;
+    d.first_symbol = c.start_symbol_index;
+    d.nof_symbols  = c.nof_symbols;
+    for (uint32_t l = 0; l != NRPHY_NSYMB; ++l) {
+      if ((c.dmrs_symbol_mask >> l) & 1U) {
+        const uint64_t nid = c.scrambling_id;
+        d.dmrs_symbol[d.nof_dmrs] = l;
+        d.c_init[d.nof_dmrs]      = (uint32_t)(((NRPHY_NSYMB * (uint64_t)c.slot_index + l + 1) * (2 * nid + 1) * (1ULL << 17) +
+                                           2 * nid + c.n_scid) %
+                                          (1ULL << 31));
+        ++d.nof_dmrs;
+      }
+    }
+    // Cyclic prefix lengths in units of kappa (cyclic_prefix::get_length, normal CP), as fractions of a symbol.
+    double e = 0;
+    for (uint32_t l = 0; l != NRPHY_NSYMB; ++l) {
+      const uint32_t cp = (144U >> c.numerology) + ((l == 0 || l == 7U * (1U << c.numerology)) ? 16U : 0U);
+      e += (double)cp * (double)(1U << c.numerology) / 2048.0 + (l == 0 ? 0.0 : 1.0);
+      d.epoch[l] = (float)e;
+    }
+    d.ntaps = filter_taps(d.nprb, d.taps);
+    d.nof_v = d.nprb == 1 ? 6U : std::min(12U, d.ntaps / 2);
+    d.dc    = c.dc_position;
+    d.scs_hz = 15000U << c.numerology;
+    for (uint32_t k = 0; k != c.nof_rx_ports; ++k) {
+      d.rx_ports[k] = c.rx_ports[k];
+    }
+    d.beta       = c.scaling;
+    d.ls_scale   = 1.0f / ((float)d.nof_dmrs * c.scaling);
+    d.ce_offset  = ce_offset[i];
+    d.row_offset = row_words;
+    row_words += (uint64_t)c.nof_rx_ports * c.nof_tx_layers * NRPHY_NRE * d.nprb;
+    for (uint32_t p = 0; p != c.nof_rx_ports; ++p) {
+      for (uint32_t l = 0; l != c.nof_tx_layers; ++l) {
+        jobs.push_back((i << 8) | (p << 4) | l);
+      }
+    }
+  }
+  std::vector<float2> tw(2048);
+  for (uint32_t i = 0; i != 2048; ++i) {
+    const double a = 2.0 * M_PI * i / 2048.0;
+    tw[i]          = make_float2((float)std::cos(a), (float)std::sin(a));
+  }
+  auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o_desc = 0;
+  const size_t o_jobs = align(o_desc + desc.size() * sizeof(PuschChestDesc));
+  const size_t o_prbs = align(o_jobs + jobs.size() * sizeof(uint32_t));
+  const size_t o_tw   = align(o_prbs + prbs.size() * sizeof(uint16_t));
+  const size_t o_rows = align(o_tw + tw.size() * sizeof(float2));
+  const size_t o_rot  = align(o_rows + row_words * sizeof(uint32_t));
+  const size_t bytes  = align(o_rot + jobs.size() * NRPHY_NSYMB * sizeof(float2));
+  std::vector<uint8_t> host(o_rows, 0);
+  std::memcpy(host.data() + o_desc, desc.data(), desc.size() * sizeof(PuschChestDesc));
+  std::memcpy(host.data() + o_jobs, jobs.data(), jobs.size() * sizeof(uint32_t));
+  std::memcpy(host.data() + o_prbs, prbs.data(), prbs.size() * sizeof(uint16_t));
+  std::memcpy(host.data() + o_tw, tw.data(), tw.size() * sizeof(float2));
+  auto* plan           = new nrphy_pusch_chest_plan;
+  plan->ctx            = ctx;
+  plan->n              = n;
+  plan->n_jobs         = (uint32_t)jobs.size();
+  plan->nof_grids      = nof_grids;
+  plan->grid_nof_ports = grid_nof_ports;
+  plan->grid_nof_subc  = grid_nof_subc;
+  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&plan->d_arena, bytes) != hipSuccess ||
+      hipMemcpy(plan->d_arena, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    nrphy_pusch_chest_plan_destroy(plan);
+    return NRPHY_ERR_DEVICE;
+  }
+  uint8_t* a   = (uint8_t*)plan->d_arena;
+  plan->d_desc = (PuschChestDesc*)(a + o_desc);
+  plan->d_jobs = (uint32_t*)(a + o_jobs);
+  plan->d_prbs = (uint16_t*)(a + o_prbs);
+  plan->d_tw   = (float2*)(a + o_tw);
+  plan->d_rows = (uint32_t*)(a + o_rows);
+  plan->d_rot  = (float2*)(a + o_rot);
+  *out         = plan;
+  return NRPHY_OK;
+}
+
+extern "C" int nrphy_pusch_chest_run(nrphy_pusch_chest_plan_t* plan, const void* d_grid, void* d_ch_est, float* d_noise_vars,
+                                     nrphy_pusch_chest_meas_t* d_meas, void* stream)
+{
+  if (plan == nullptr || d_grid == nullptr || d_ch_est == nullptr || d_noise_vars == nullptr ||
+      (((uintptr_t)d_grid | (uintptr_t)d_ch_est | (uintptr_t)d_noise_vars | (uintptr_t)d_meas) & 3U) != 0) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  PuschChestLaunch p;
+  p.desc           = plan->d_desc;
+  p.jobs           = plan->d_jobs;
+  p.prbs           = plan->d_prbs;
+  p.twiddle        = plan->d_tw;
+  p.gold           = plan->ctx->d_gold;
+  p.x1_words       = plan->ctx->d_x1;
+  p.grid           = (const uint32_t*)d_grid;
+  p.ch             = (uint32_t*)d_ch_est;
+  p.noise_vars     = d_noise_vars;
+  p.meas           = d_meas;
+  p.rows           = plan->d_rows;
+  p.rot            = plan->d_rot;
+  p.grid_nof_ports = plan->grid_nof_ports;
+  p.grid_nof_subc  = plan->grid_nof_subc;
+  p.n_jobs         = plan->n_jobs;
+  HIP_TRY(hipSetDevice(plan->ctx->device));
+  HIP_TRY(launch_pusch_chest(p, stream ? (hipStream_t)stream : plan->ctx->stream));
+  return NRPHY_OK;
+}
+
+extern "C" int nrphy_pusch_chest_host(nrphy_ctx_t* ctx, const nrphy_pusch_chest_cfg_t* cfg, const void* grid,
+                                      uint32_t grid_nof_ports, uint32_t grid_nof_subc, void* ch_est, float* noise_vars,
+                                      nrphy_pusch_chest_meas_t* meas)
+{
+  if (ctx == nullptr || grid == nullptr || ch_est == nullptr || noise_vars == nullptr ||
+      validate(cfg, grid_nof_ports, grid_nof_subc) != NRPHY_OK) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  const size_t grid_bytes = (size_t)grid_nof_ports * NRPHY_NSYMB * grid_nof_subc * 4;
+  const size_t ce_bytes   = (size_t)cfg->nof_tx_layers * cfg->nof_rx_ports * NRPHY_NSYMB * grid_nof_subc * 4;
+  const size_t meas_bytes = NRPHY_MAX_PORTS * NRPHY_PUSCH_CHEST_MAX_LAYERS * sizeof(nrphy_pusch_chest_meas_t);
+  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
+  HIP_TRY(hipSetDevice(ctx->device));
+  void *d_grid = nullptr, *d_ce = nullptr, *d_nv = nullptr, *d_meas = nullptr;
+  auto  release = [&]() {
+    for (void* q : {d_grid, d_ce, d_nv, d_meas}) {
+      if (q != nullptr) {
+        (void)hipFree(q);
+      }
+    }
+  };
+  if (hipMalloc(&d_grid, grid_bytes) != hipSuccess || hipMalloc(&d_ce, ce_bytes) != hipSuccess ||
+      hipMalloc(&d_nv, NRPHY_MAX_PORTS * sizeof(float)) != hipSuccess || hipMalloc(&d_meas, meas_bytes) != hipSuccess) {
+    release();
+    return NRPHY_ERR_DEVICE;
+  }
+  const uint32_t            zero = 0;
+  const uint64_t            ce0  = 0;
+  nrphy_pusch_chest_plan_t* plan = nullptr;
+  int                       rc   = NRPHY_ERR_DEVICE;
+  if (hipMemcpy(d_grid, grid, grid_bytes, hipMemcpyHostToDevice) == hipSuccess &&
+      hipMemcpy(d_ce, ch_est, ce_bytes, hipMemcpyHostToDevice) == hipSuccess) {
+    rc = nrphy_pusch_chest_plan_create(ctx, 1, cfg, &zero, 1, grid_nof_ports, grid_nof_subc, &ce0, &plan);
+  }
+  if (rc == NRPHY_OK) {
+    rc = nrphy_pusch_chest_run(plan, d_grid, d_ce, (float*)d_nv, (nrphy_pusch_chest_meas_t*)d_meas, ctx->stream);
+  }
+  if (rc == NRPHY_OK) {
+    std::vector<nrphy_pusch_chest_meas_t> m(NRPHY_MAX_PORTS * NRPHY_PUSCH_CHEST_MAX_LAYERS);
+    float                                 nv[NRPHY_MAX_PORTS];
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipMemcpy(ch_est, d_ce, ce_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(nv, d_nv, sizeof(nv), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(m.data(), d_meas, meas_bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+      rc = NRPHY_ERR_DEVICE;
+    } else {
+      for (uint32_t i = 0; i != cfg->nof_rx_ports; ++i) {
+        noise_vars[i] = nv[i];
+      }
+      if (meas != nullptr) {
+        std::memcpy(meas, m.data(), cfg->nof_rx_ports * NRPHY_PUSCH_CHEST_MAX_LAYERS * sizeof(nrphy_pusch_chest_meas_t));
+      }
+    }
+  }
+  nrphy_pusch_chest_plan_destroy(plan);
+  release();
+  return rc;
+}

@@ -1,0 +1,419 @@
+// PUSCH DM-RS channel estimator for gfx950.
+//
+// Replaces dmrs_pusch_estimator_impl::estimate (R/lib/phy/upper/signal_processors/dmrs_pusch_estimator_impl.cpp:71-212) with
+// port_channel_estimator_average_impl::compute (port_channel_estimator_average_impl.cpp, filter smoothing and CFO compensation
+// on) and the DC step of pusch_processor_impl (pusch_processor_impl.cpp:182-199).  DM-RS type 1, one or two layers.
+//
+// Two kernels (plan built on the host, pusch_chest_host.cpp):
+//  (A) pusch_chest_kernel: one 256-thread workgroup per (PUSCH, receive port, layer).  Pilots from the Gold sequence
+//      (gold_sequence_wave, one DM-RS symbol per wave); LS estimates, EPRE, CFO from the first two DM-RS symbols, CFO
+//      derotation and averaging; virtual pilots and the raised-cosine FIR in LDS; RSRP, noise and SNR; the time alignment as a
+//      direct 288-bin partial inverse DFT; the linear interpolation (the reference's running sum, one lane per component),
+//      rounded to cbf16 into the plan's scratch row, and the per-symbol CFO rotations.  Every reduction is a per-thread
+//      double partial sum folded in a fixed order: two runs give the same bits.
+//  (B) pusch_chest_expand_kernel: one workgroup per (job, OFDM symbol): the scratch row rotated by the symbol's CFO phasor and
+//      rounded again (the reference rounds twice), DC zeroed, written to the allocated PRBs with 16-byte stores.
+// Transcendentals (atan2, hypot, cos, sin) are evaluated in double and rounded once to float.  Contraction is off; the only
+// fused multiply-adds are the partial DFT's, which feed a comparison and nothing else.
+#include "bits_device.h"
+
+#include <hip/hip_runtime.h>
+
+namespace nrphy {
+namespace {
+
+constexpr uint32_t CHEST_THREADS = 256;
+constexpr uint32_t MAX_PILOTS    = NRPHY_MAX_RB * 6;
+constexpr uint32_t V_MARGIN      = 12;                            // MAX_V_PILOTS: room for virtual pilots at each end
+constexpr uint32_t MAX_SEQ_WORDS = (NRPHY_MAX_RB * NRPHY_NRE + 31) / 32;
+constexpr uint32_t TA_BINS       = 2 * PUSCH_CHEST_TA_WINDOW;
+constexpr float    TWOPI_F       = 6.28318548f;                   // 2.0F * static_cast<float>(M_PI)
+constexpr float    PI_F          = 3.14159274f;
+constexpr float    SQRT1_2_F     = 0.707106769f;
+
+struct ChestShared {
+  uint32_t seq[NRPHY_NSYMB][MAX_SEQ_WORDS];  // Gold words c(0 ...) of every DM-RS symbol
+  uint32_t gold_scratch[4][MAX_SEQ_WORDS];
+  uint16_t prbs[NRPHY_MAX_RB];
+  float2   a[MAX_PILOTS + 2 * V_MARGIN];     // enlarged LS; later the interpolator's half steps (two planes)
+  float2   b[MAX_PILOTS];                    // LS of the second DM-RS symbol; later the filtered pilots
+  union {
+    float2 tw[2048];                         // e^{j 2 pi i / 2048}
+    float  out[2][2 * MAX_PILOTS];           // interpolated response, one plane per component
+  } u;
+  float    mag[TA_BINS];
+  double   red[4][2];
+  float    vp_abs[2][V_MARGIN], vp_arg[2][V_MARGIN];
+};
+
+__device__ __forceinline__ uint32_t bf16_rne(float x)
+{
+  const uint32_t u = __float_as_uint(x);
+  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+__device__ __forceinline__ uint32_t to_cbf16(float re, float im)
+{
+  return bf16_rne(re) | (bf16_rne(im) << 16);
+}
+
+__device__ __forceinline__ float2 from_cbf16(uint32_t w)
+{
+  return make_float2(__uint_as_float(w << 16), __uint_as_float(w & 0xFFFF0000u));
+}
+
+// std::polar(1.0F, x) with cos and sin evaluated in double and rounded once.
+__device__ __forceinline__ float2 phasor(float x)
+{
+  return make_float2((float)cos((double)x), (float)sin((double)x));
+}
+
+// (a + jb)(c + jd) as std::complex<float> writes it.
+__device__ __forceinline__ float2 cmul(float2 x, float2 h)
+{
+  return make_float2(__fsub_rn(__fmul_rn(x.x, h.x), __fmul_rn(x.y, h.y)), __fadd_rn(__fmul_rn(x.x, h.y), __fmul_rn(x.y, h.x)));
+}
+
+__device__ __forceinline__ double wave_sum_d(double v)
+{
+#pragma unroll
+  for (int o = 32; o != 0; o >>= 1) {
+    v += __shfl_xor(v, o);
+  }
+  return v;
+}
+
+// Workgroup sum of two doubles in a fixed order; every thread gets the result.
+__device__ __forceinline__ double2 block_sum2(double x, double y, ChestShared& s, uint32_t tid)
+{
+  x = wave_sum_d(x);
+  y = wave_sum_d(y);
+  __syncthreads();
+  if ((tid & 63u) == 0) {
+    s.red[tid >> 6][0] = x;
+    s.red[tid >> 6][1] = y;
+  }
+  __syncthreads();
+  return make_double2((s.red[0][0] + s.red[1][0]) + (s.red[2][0] + s.red[3][0]),
+                      (s.red[0][1] + s.red[1][1]) + (s.red[2][1] + s.red[3][1]));
+}
+
+// Pilot q of DM-RS symbol d (layer 0): r(6n + k) of PRB n = prbs[q / 6], k = q % 6, on grid subcarrier 12 n + 2 k.
+__device__ __forceinline__ float2 pilot(const ChestShared& s, uint32_t d, uint32_t q, uint32_t layer, uint32_t& subc)
+{
+  const uint32_t n = s.prbs[q / 6u], k = q % 6u;
+  const uint32_t b = 12u * n + 2u * k;
+  subc             = b;
+  const uint32_t w0 = s.seq[d][b >> 5];
+  const uint32_t c0 = (w0 >> (31u - (b & 31u))) & 1u, c1 = (w0 >> (30u - (b & 31u))) & 1u; // b even: same word
+  float2         p  = make_float2(c0 ? -SQRT1_2_F : SQRT1_2_F, c1 ? -SQRT1_2_F : SQRT1_2_F);
+  if (layer == 1 && (q & 1u)) { // w_f = -1 on the odd pilots of layer 1 (port 1001)
+    p = make_float2(-p.x, -p.y);
+  }
+  return p;
+}
+
+// compute_v_pilots: a linear fit of |.| and of the unwrapped argument of n pilots, evaluated at i + offset.
+__device__ void virtual_pilots(const float* abs_, float* arg, uint32_t n, int offset, float2* out)
+{
+  // unwrap_list (R/lib/srsvec/unwrap.cpp)
+  float k = 0.f;
+  for (uint32_t i = 0; i + 1 < n; ++i) {
+    const float old_a = arg[i], next_a = arg[i + 1];
+    arg[i]            = __fadd_rn(arg[i], __fmul_rn(__fmul_rn(2.0f, k), PI_F));
+    const float jump  = __fsub_rn(next_a, old_a);
+    if (fabsf(jump) > PI_F) {
+      k = __fsub_rn(k, jump < 0.f ? -1.0f : 1.0f);
+    }
+  }
+  arg[n - 1] = __fadd_rn(arg[n - 1], __fmul_rn(__fmul_rn(2.0f, k), PI_F));
+  const float nf        = (float)n;
+  const float mean_x    = __fdiv_rn(__fdiv_rn((float)(n * (n - 1)), 2.0f), nf);
+  const float norm_x_sq = __fdiv_rn((float)((n - 1) * n * (2 * n - 1)), 6.0f);
+  const float den       = __fsub_rn(norm_x_sq, __fmul_rn(__fmul_rn(nf, mean_x), mean_x));
+  float       sa = 0.f, sg = 0.f, da = 0.f, dg = 0.f;
+  for (uint32_t i = 0; i != n; ++i) {
+    sa = __fadd_rn(sa, abs_[i]);
+    sg = __fadd_rn(sg, arg[i]);
+    da = __fadd_rn(da, __fmul_rn(abs_[i], (float)i));
+    dg = __fadd_rn(dg, __fmul_rn(arg[i], (float)i));
+  }
+  const float mean_abs = __fdiv_rn(sa, nf), mean_arg = __fdiv_rn(sg, nf);
+  const float slope_abs = __fdiv_rn(__fsub_rn(da, __fmul_rn(__fmul_rn(mean_x, mean_abs), nf)), den);
+  const float slope_arg = __fdiv_rn(__fsub_rn(dg, __fmul_rn(__fmul_rn(mean_x, mean_arg), nf)), den);
+  const float icp_abs   = __fsub_rn(mean_abs, __fmul_rn(slope_abs, mean_x));
+  const float icp_arg   = __fsub_rn(mean_arg, __fmul_rn(slope_arg, mean_x));
+  for (uint32_t i = 0; i != n; ++i) {
+    const float  x = (float)((int)i + offset);
+    const float  r = __fadd_rn(__fmul_rn(slope_abs, x), icp_abs);
+    const float2 e = phasor(__fadd_rn(__fmul_rn(slope_arg, x), icp_arg));
+    out[i]         = make_float2(__fmul_rn(r, e.x), __fmul_rn(r, e.y));
+  }
+}
+
+__global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_kernel(PuschChestLaunch p)
+{
+  __shared__ ChestShared s;
+  const uint32_t       tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+  const uint32_t       job = p.jobs[blockIdx.x];
+  const uint32_t       ip = job >> 8, port = (job >> 4) & 15u, layer = job & 15u;
+  const PuschChestDesc& d = p.desc[ip];
+  const uint32_t       N = 6u * d.nprb, nd = d.nof_dmrs;
+
+  for (uint32_t j = tid; j < d.nprb; j += CHEST_THREADS) {
+    s.prbs[j] = p.prbs[d.prb_first + j];
+  }
+  for (uint32_t i = tid; i < 2048u; i += CHEST_THREADS) {
+    s.u.tw[i] = p.twiddle[i];
+  }
+  for (uint32_t dd = wave; dd < nd; dd += 4u) { // wave-uniform
+    gold_sequence_wave(p.gold, p.x1_words, d.c_init[dd], d.nwords, s.seq[dd], s.gold_scratch[wave], lane);
+  }
+  __syncthreads();
+
+  const uint32_t* grid  = p.grid + ((size_t)d.grid_index * p.grid_nof_ports + d.rx_ports[port]) * NRPHY_NSYMB * p.grid_nof_subc;
+  float2*         A     = s.a + V_MARGIN;
+  double          epre  = 0.0;
+  float           cfo   = 0.f;
+  // ---- LS estimates, EPRE, CFO (preprocess_pilots_and_cfo) --------------------------------------------------------------
+  for (uint32_t dd = 0; dd != nd; ++dd) {
+    const uint32_t* row = grid + (size_t)d.dmrs_symbol[dd] * p.grid_nof_subc;
+    double          dr = 0.0, di = 0.0;
+    for (uint32_t q = tid; q < N; q += CHEST_THREADS) {
+      uint32_t     k;
+      const float2 pl = pilot(s, dd, q, layer, k);
+      const float2 y  = from_cbf16(row[k]);
+      epre += (double)__fadd_rn(__fmul_rn(y.x, y.x), __fmul_rn(y.y, y.y));
+      const float2 ls = make_float2(__fadd_rn(__fmul_rn(y.x, pl.x), __fmul_rn(y.y, pl.y)),
+                                    __fsub_rn(__fmul_rn(y.y, pl.x), __fmul_rn(y.x, pl.y)));
+      if (dd == 0) {
+        A[q] = ls;
+      } else if (dd == 1) {
+        s.b[q] = ls;
+        const float2 l0 = A[q]; // dot_prod(LS1, LS0) = sum LS1 conj(LS0)
+        dr += (double)__fadd_rn(__fmul_rn(ls.x, l0.x), __fmul_rn(ls.y, l0.y));
+        di += (double)__fsub_rn(__fmul_rn(ls.y, l0.x), __fmul_rn(ls.x, l0.y));
+      } else {
+        const float2 r = phasor(__fmul_rn(__fmul_rn(-TWOPI_F, d.epoch[d.dmrs_symbol[dd]]), cfo));
+        const float2 a = A[q], c = cmul(ls, r);
+        A[q]                     = make_float2(__fadd_rn(a.x, c.x), __fadd_rn(a.y, c.y));
+      }
+    }
+    if (dd == 1) {
+      const double2 dot   = block_sum2(dr, di, s, tid);
+      const float   phase = (float)atan2((double)(float)dot.y, (double)(float)dot.x);
+      cfo = __fdiv_rn(__fdiv_rn(phase, TWOPI_F), __fsub_rn(d.epoch[d.dmrs_symbol[1]], d.epoch[d.dmrs_symbol[0]]));
+      const float2 r0 = phasor(__fmul_rn(__fmul_rn(-TWOPI_F, d.epoch[d.dmrs_symbol[0]]), cfo));
+      const float2 r1 = phasor(__fmul_rn(__fmul_rn(-TWOPI_F, d.epoch[d.dmrs_symbol[1]]), cfo));
+      for (uint32_t q = tid; q < N; q += CHEST_THREADS) {
+        const float2 a = cmul(A[q], r0), c = cmul(s.b[q], r1);
+        A[q]           = make_float2(__fadd_rn(a.x, c.x), __fadd_rn(a.y, c.y));
+      }
+    }
+    __syncthreads();
+  }
+  // Average and DM-RS-to-data gain.
+  for (uint32_t q = tid; q < N; q += CHEST_THREADS) {
+    A[q] = make_float2(__fmul_rn(A[q].x, d.ls_scale), __fmul_rn(A[q].y, d.ls_scale));
+  }
+  __syncthreads();
+
+  // ---- virtual pilots (add_v_pilots) and the FIR (convolution_same), the middle N outputs into b ------------------------
+  const uint32_t nv = d.nof_v;
+  if (tid < 2u * nv) {
+    const uint32_t side = tid / nv, i = tid % nv;
+    const float2   v    = A[side == 0 ? i : N - nv + i];
+    const double   re = v.x, im = v.y;
+    s.vp_abs[side][i] = (float)sqrt(re * re + im * im);
+    s.vp_arg[side][i] = (float)atan2(im, re);
+  }
+  __syncthreads();
+  if (tid < 2u) {
+    virtual_pilots(s.vp_abs[tid], s.vp_arg[tid], nv, tid == 0 ? -(int)nv : (int)nv, tid == 0 ? A - nv : A + N);
+  }
+  __syncthreads();
+  const uint32_t T = d.ntaps, mid = T / 2u;
+  double         pw = 0.0;
+  for (uint32_t q = tid; q < N; q += CHEST_THREADS) {
+    const float2* x  = A + q - mid;
+    float2        acc = make_float2(0.f, 0.f);
+    for (uint32_t i = 0; i != T; ++i) {
+      const float h = d.taps[T - 1u - i];
+      acc           = make_float2(__fadd_rn(acc.x, __fmul_rn(x[i].x, h)), __fadd_rn(acc.y, __fmul_rn(x[i].y, h)));
+    }
+    s.b[q] = acc;
+    pw += (double)__fadd_rn(__fmul_rn(acc.x, acc.x), __fmul_rn(acc.y, acc.y));
+  }
+  const double2 pe   = block_sum2(pw, epre, s, tid); // (also orders the writes of b)
+  const float   rsrp = (float)(pe.x * (double)d.beta * (double)d.beta / (double)N);
+
+  // ---- noise (estimate_noise) ------------------------------------------------------------------------------------------
+  double ne = 0.0;
+  for (uint32_t dd = 0; dd != nd; ++dd) {
+    const uint32_t* row = grid + (size_t)d.dmrs_symbol[dd] * p.grid_nof_subc;
+    const float2    r   = phasor(__fmul_rn(__fmul_rn(TWOPI_F, d.epoch[d.dmrs_symbol[dd]]), cfo));
+    for (uint32_t q = tid; q < N; q += CHEST_THREADS) {
+      uint32_t     k;
+      const float2 pl = pilot(s, dd, q, layer, k);
+      const float2 y  = from_cbf16(row[k]);
+      const float2 f  = s.b[q];
+      float2       e  = cmul(make_float2(__fmul_rn(f.x, -d.beta), __fmul_rn(f.y, -d.beta)), pl);
+      if (nd >= 2u) {
+        e = cmul(e, r);
+      }
+      e = make_float2(__fadd_rn(e.x, y.x), __fadd_rn(e.y, y.y));
+      ne += (double)__fadd_rn(__fmul_rn(e.x, e.x), __fmul_rn(e.y, e.y));
+    }
+  }
+  const double2 nz = block_sum2(ne, 0.0, s, tid);
+
+  // ---- time alignment: |IDFT_4096|^2 of the filtered pilots at their grid subcarriers, bins [0, 144) and [3952, 4096) ------
+  {
+    float2 acc0 = make_float2(0.f, 0.f), acc1 = make_float2(0.f, 0.f);
+    const uint32_t n0 = tid < PUSCH_CHEST_TA_WINDOW ? tid : 4096u - TA_BINS + tid;
+    const uint32_t b1 = tid + CHEST_THREADS, n1 = 4096u - TA_BINS + b1;
+    const bool     two = b1 < TA_BINS;
+    for (uint32_t j = 0; j != d.nprb; ++j) {
+      const uint32_t m0 = 6u * s.prbs[j];
+      uint32_t       i0 = (m0 * n0) & 2047u, i1 = (m0 * n1) & 2047u;
+#pragma unroll
+      for (uint32_t k = 0; k != 6; ++k) {
+        const float2 f = s.b[6u * j + k];
+        const float2 w = s.u.tw[i0];
+        acc0.x         = __fmaf_rn(f.x, w.x, __fmaf_rn(-f.y, w.y, acc0.x));
+        acc0.y         = __fmaf_rn(f.x, w.y, __fmaf_rn(f.y, w.x, acc0.y));
+        if (two) {
+          const float2 v = s.u.tw[i1];
+          acc1.x         = __fmaf_rn(f.x, v.x, __fmaf_rn(-f.y, v.y, acc1.x));
+          acc1.y         = __fmaf_rn(f.x, v.y, __fmaf_rn(f.y, v.x, acc1.y));
+        }
+        i0 = (i0 + n0) & 2047u;
+        i1 = (i1 + n1) & 2047u;
+      }
+    }
+    s.mag[tid] = __fadd_rn(__fmul_rn(acc0.x, acc0.x), __fmul_rn(acc0.y, acc0.y));
+    if (two) {
+      s.mag[b1] = __fadd_rn(__fmul_rn(acc1.x, acc1.x), __fmul_rn(acc1.y, acc1.y));
+    }
+  }
+  __syncthreads(); // (the twiddles are dead from here on: u.out reuses them)
+
+  // ---- linear interpolation (interpolator_linear_impl, offset 0, stride 2): half steps in parallel, the running sum serial
+  float* half = reinterpret_cast<float*>(s.a); // two planes of N - 1
+  for (uint32_t q = tid; q + 1u < N; q += CHEST_THREADS) {
+    half[q]             = __fmul_rn(__fsub_rn(s.b[q + 1u].x, s.b[q].x), 0.5f);
+    half[MAX_PILOTS + q] = __fmul_rn(__fsub_rn(s.b[q + 1u].y, s.b[q].y), 0.5f);
+  }
+  __syncthreads();
+  if (tid < 2u) { // lane 0: real part, lane 1: imaginary part
+    const float* h   = half + tid * MAX_PILOTS;
+    float*       out = s.u.out[tid];
+    float        v   = tid == 0 ? s.b[0].x : s.b[0].y;
+    out[0]           = v;
+    for (uint32_t i = 0; i + 1u < N; ++i) {
+      const float j  = h[i];
+      const float v1 = __fadd_rn(v, j);
+      v              = __fadd_rn(v1, j);
+      out[2u * i + 1u] = v1;
+      out[2u * i + 2u] = v;
+    }
+    out[2u * N - 1u] = tid == 0 ? s.b[N - 1u].x : s.b[N - 1u].y;
+  } else if (tid == 64u) { // meanwhile: the measurements
+    float best_d = -1.f, best_a = -1.f;
+    int   id = 0, ia = 0;
+    for (uint32_t b = 0; b != PUSCH_CHEST_TA_WINDOW; ++b) {
+      if (s.mag[b] > best_d) {
+        best_d = s.mag[b];
+        id     = (int)b;
+      }
+      if (s.mag[PUSCH_CHEST_TA_WINDOW + b] > best_a) {
+        best_a = s.mag[PUSCH_CHEST_TA_WINDOW + b];
+        ia     = (int)b;
+      }
+    }
+    const int   ta_bins   = best_d >= best_a ? id : ia - (int)PUSCH_CHEST_TA_WINDOW;
+    const float epre_f    = (float)(pe.y / (double)(N * nd));
+    const float nvar_raw  = (float)(nz.x / (double)(N * nd - 1u));
+    const float min_noise = __fdiv_rn(rsrp, 1e10f);
+    const float noise_var = nvar_raw > min_noise ? nvar_raw : min_noise;
+    const float datarp    = __fdiv_rn(__fdiv_rn(rsrp, d.beta), d.beta);
+    const float snr       = noise_var != 0.f ? __fdiv_rn(datarp, noise_var) : 1000.f;
+    if (layer == 0) {
+      p.noise_vars[(size_t)ip * NRPHY_MAX_PORTS + port] = noise_var;
+    }
+    if (p.meas != nullptr) {
+      nrphy_pusch_chest_meas_t m;
+      m.noise_var = noise_var;
+      m.rsrp      = rsrp;
+      m.epre      = epre_f;
+      m.snr       = snr;
+      m.ta_s      = (float)((double)ta_bins / (4096.0 * (double)d.scs_hz));
+      m.ta_bins   = ta_bins;
+      m.cfo_hz    = nd >= 2u ? __fmul_rn(__fmul_rn(cfo, (float)(d.scs_hz / 1000u)), 1000.f) : __builtin_nanf("");
+      m.reserved_ = 0;
+      p.meas[((size_t)ip * NRPHY_MAX_PORTS + port) * PUSCH_CHEST_MAX_LAYERS + layer] = m;
+    }
+  } else if (tid >= 128u && tid < 128u + NRPHY_NSYMB) { // the per-symbol CFO phasors of the expand kernel
+    const uint32_t l = tid - 128u;
+    p.rot[(size_t)blockIdx.x * NRPHY_NSYMB + l] = nd >= 2u ? phasor(__fmul_rn(__fmul_rn(TWOPI_F, d.epoch[l]), cfo))
+                                                             : make_float2(1.f, 0.f);
+  }
+  __syncthreads();
+  uint32_t* row = p.rows + d.row_offset + (size_t)(port * d.nof_layers + layer) * 12u * d.nprb;
+  for (uint32_t k = tid; k < 12u * d.nprb; k += CHEST_THREADS) {
+    row[k] = to_cbf16(s.u.out[0][k], s.u.out[1][k]);
+  }
+}
+
+// One workgroup per (job, OFDM symbol): 16-byte chunks of 4 RE, 3 per PRB.
+__global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_expand_kernel(PuschChestLaunch p)
+{
+  const uint32_t        j = blockIdx.x, l = blockIdx.y;
+  const uint32_t        job = p.jobs[j];
+  const uint32_t        ip = job >> 8, port = (job >> 4) & 15u, layer = job & 15u;
+  const PuschChestDesc& d = p.desc[ip];
+  if (l < d.first_symbol || l >= d.first_symbol + d.nof_symbols) {
+    return;
+  }
+  const uint32_t* src = p.rows + d.row_offset + (size_t)(port * d.nof_layers + layer) * 12u * d.nprb;
+  uint32_t*       dst = p.ch + d.ce_offset + (((size_t)layer * d.nof_rx_ports + port) * NRPHY_NSYMB + l) * p.grid_nof_subc;
+  const bool      rot = d.nof_dmrs >= 2u, wide = (((uintptr_t)dst) & 15u) == 0; // rows of a PUSCH share their phase
+  const float2    r   = p.rot[(size_t)j * NRPHY_NSYMB + l];
+  for (uint32_t c = threadIdx.x; c < 3u * d.nprb; c += CHEST_THREADS) {
+    uint4          w  = reinterpret_cast<const uint4*>(src)[c];
+    const uint32_t k0 = 12u * p.prbs[d.prb_first + c / 3u] + 4u * (c % 3u);
+    uint32_t*      v  = &w.x;
+#pragma unroll
+    for (uint32_t i = 0; i != 4; ++i) {
+      if (rot) {
+        const float2 e = cmul(from_cbf16(v[i]), r);
+        v[i]           = to_cbf16(e.x, e.y);
+      }
+      if (k0 + i == d.dc) {
+        v[i] = 0u;
+      }
+    }
+    if (wide) {
+      reinterpret_cast<uint4*>(dst + k0)[0] = w;
+    } else {
+      dst[k0] = w.x;
+      dst[k0 + 1u] = w.y;
+      dst[k0 + 2u] = w.z;
+      dst[k0 + 3u] = w.w;
+    }
+  }
+}
+
+} // namespace
+
+hipError_t launch_pusch_chest(const PuschChestLaunch& p, hipStream_t stream)
+{
+  if (p.n_jobs == 0) {
+    return hipSuccess;
+  }
+  hipLaunchKernelGGL(pusch_chest_kernel, dim3(p.n_jobs), dim3(CHEST_THREADS), 0, stream, p);
+  hipLaunchKernelGGL(pusch_chest_expand_kernel, dim3(p.n_jobs, NRPHY_NSYMB), dim3(CHEST_THREADS), 0, stream, p);
+  return hipGetLastError();
+}
+
+} // namespace nrphy

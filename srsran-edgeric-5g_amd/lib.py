@@ -396,6 +396,22 @@ class Context:
                "nrphy_pusch_demodulate_host")
         return out, float(sinr.value)
 
+    def pusch_chest_host(self, cfg, grid, ch_est=None):
+        """dmrs_pusch_estimator::estimate + the processor's DC step for one PUSCH: grid [ports][14][subc] raw cbf16 words ->
+        (ch_est [layers][rx][14][subc] cbf16 words, noise_vars [rx], measurements [rx][2] of abi.PuschChestMeas).  ch_est: the
+        buffer to write into (only the allocated region changes); zeros when None."""
+        grid = np.ascontiguousarray(grid, dtype=np.uint32)
+        shape = (cfg.nof_tx_layers, cfg.nof_rx_ports, 14, grid.shape[-1])
+        ce = np.zeros(shape, np.uint32) if ch_est is None else np.array(ch_est, dtype=np.uint32, order="C")
+        if ce.shape != shape:
+            raise ValueError("ch_est must be %s" % (shape,))
+        nv = np.zeros(cfg.nof_rx_ports, np.float32)
+        meas = (abi.PuschChestMeas * (cfg.nof_rx_ports * abi.PUSCH_CHEST_MAX_LAYERS))()
+        _check(self.lib.nrphy_pusch_chest_host(self.handle, C.byref(cfg), grid.ctypes.data, grid.shape[0], grid.shape[-1],
+                                               ce.ctypes.data, nv.ctypes.data, meas), "nrphy_pusch_chest_host")
+        m = [[meas[i * abi.PUSCH_CHEST_MAX_LAYERS + l] for l in range(abi.PUSCH_CHEST_MAX_LAYERS)] for i in range(cfg.nof_rx_ports)]
+        return ce, nv, m
+
     def dft(self, size, inverse, batch, d_in, d_out, stream=None):
         _check(self.lib.nrphy_dft_run(self.handle, size, int(inverse), batch, _dptr(d_in), _dptr(d_out), _stream(stream)),
                "nrphy_dft_run")
@@ -488,6 +504,44 @@ class PuschDemodPlan:
             self.close()
         except Exception:
             pass
+
+
+class PuschChestPlan:
+    """nrphy_pusch_chest_plan: PUSCHs over a batch of received grids; run() writes their channel estimates (the layout
+    PuschDemodPlan reads), the noise variances PuschDemodPlan.run takes and, optionally, the measurements."""
+
+    def __init__(self, ctx, cfgs, grid_indices, nof_grids, nof_ports, nof_subc, ce_offsets):
+        self.ctx = ctx
+        n = len(cfgs)
+        arr = (abi.PuschChestCfg * n)(*cfgs)
+        gidx = (C.c_uint32 * n)(*grid_indices)
+        offs = (C.c_uint64 * n)(*ce_offsets)
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_pusch_chest_plan_create(ctx.handle, n, arr, gidx, nof_grids, nof_ports, nof_subc, offs, C.byref(h)),
+               "nrphy_pusch_chest_plan_create")
+        self.handle = h
+        self.n = n
+
+    def run(self, d_grid, d_ch_est, d_noise_vars, d_meas=None, stream=None):
+        """d_noise_vars: [n][4] f32; d_meas: [n][4][2] x 32 bytes (abi.PuschChestMeas) or None."""
+        _check(self.ctx.lib.nrphy_pusch_chest_run(self.handle, _dptr(d_grid), _dptr(d_ch_est), _dptr(d_noise_vars), _dptr(d_meas),
+                                                  _stream(stream)), "nrphy_pusch_chest_run")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.nrphy_pusch_chest_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pusch_chest_validate(cfg, grid_nof_ports, grid_nof_subc):
+    """nrphy_pusch_chest_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_pusch_chest_validate(C.byref(cfg), grid_nof_ports, grid_nof_subc))
 
 
 def pusch_demod_validate(cfg, grid_nof_ports, grid_nof_subc):
