@@ -726,4 +726,20 @@ __device__ __forceinline__ uint32_t to_bf16_bits(float v)
   return u >> 16;
 }
 
+// cbf16 word (real part in the low half) -> complex float, exactly.
+__device__ __forceinline__ float2 cbf16_to_float2(uint32_t w)
+{
+  return make_float2(__uint_as_float(w << 16), __uint_as_float(w & 0xFFFF0000u));
+}
+
+// Sum over the wave in a fixed order (the receive side's double-precision reductions); every lane gets the result.
+__device__ __forceinline__ double wave_sum(double x)
+{
+#pragma unroll
+  for (int o = WAVE / 2; o != 0; o >>= 1) {
+    x += __shfl_xor(x, o);
+  }
+  return x;
+}
+
 } // namespace nrphy

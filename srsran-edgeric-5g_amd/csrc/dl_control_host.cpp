@@ -527,21 +527,19 @@ namespace {
 template <class Launch>
 int with_host_grid(nrphy_ctx_t* ctx, void* grid, uint32_t nof_ports, uint32_t nof_subc, Launch launch)
 {
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-  HIP_TRY(hipSetDevice(ctx->device));
+  HostCall     call(ctx);
   const size_t bytes  = (size_t)nof_ports * NRPHY_NSYMB * nof_subc * 4;
-  void*        d_grid = ctx_scratch(ctx, SCRATCH_GRID, bytes);
+  void*        d_grid = call.mem(SCRATCH_GRID, bytes);
   if (d_grid == nullptr) {
     return NRPHY_ERR_DEVICE;
   }
   HIP_TRY(hipMemcpyAsync(d_grid, grid, bytes, hipMemcpyHostToDevice, ctx->stream));
   const int rc = launch(d_grid);
   if (rc != NRPHY_OK) {
-    (void)hipStreamSynchronize(ctx->stream);
     return rc;
   }
   HIP_TRY(hipMemcpyAsync(grid, d_grid, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(call.sync());
   return NRPHY_OK;
 }
 
@@ -589,9 +587,8 @@ extern "C" int nrphy_pdcch_encode_host(nrphy_ctx_t* ctx, const uint8_t* payload,
   w.payload_offset = 0;
   st.bytes.assign(payload, payload + payload_size);
   st.pdcch.push_back(w);
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-  HIP_TRY(hipSetDevice(ctx->device));
-  uint8_t* d_enc = (uint8_t*)ctx_scratch(ctx, SCRATCH_SMALL, 2048);
+  HostCall call(ctx);
+  uint8_t* d_enc = call.mem<uint8_t>(SCRATCH_SMALL, 2048);
   if (d_enc == nullptr) {
     return NRPHY_ERR_DEVICE;
   }
@@ -600,7 +597,7 @@ extern "C" int nrphy_pdcch_encode_host(nrphy_ctx_t* ctx, const uint8_t* payload,
     return rc;
   }
   HIP_TRY(hipMemcpyAsync(encoded, d_enc, rm_length, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(call.sync());
   return NRPHY_OK;
 }
 
@@ -691,9 +688,8 @@ extern "C" int nrphy_pbch_encode_host(nrphy_ctx_t* ctx, const nrphy_ssb_pdu_t* p
   if (!add_pbch_tables(st, &src_offset, &crcw_offset) || !add_ssb(st, src_offset, crcw_offset, *pdu, 0, 0, 0, false, 0)) {
     return NRPHY_ERR_DEVICE;
   }
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-  HIP_TRY(hipSetDevice(ctx->device));
-  uint8_t* d_enc = (uint8_t*)ctx_scratch(ctx, SCRATCH_SMALL, 2048);
+  HostCall call(ctx);
+  uint8_t* d_enc = call.mem<uint8_t>(SCRATCH_SMALL, 2048);
   if (d_enc == nullptr) {
     return NRPHY_ERR_DEVICE;
   }
@@ -702,6 +698,6 @@ extern "C" int nrphy_pbch_encode_host(nrphy_ctx_t* ctx, const nrphy_ssb_pdu_t* p
     return rc;
   }
   HIP_TRY(hipMemcpyAsync(encoded, d_enc, 864, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(call.sync());
   return NRPHY_OK;
 }

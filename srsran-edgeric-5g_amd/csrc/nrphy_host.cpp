@@ -298,66 +298,6 @@ void build_gold_tables(GoldTables& t, std::vector<uint32_t>& x1_words)
   }
 }
 
-
-// All tables of a plan in ONE device allocation filled by ONE copy (a plan of a single PDU used to spend most of its
-// creation time in a dozen hipMalloc / hipMemcpy pairs).  add() registers a table; commit() allocates, copies and
-// points every registered device pointer into the block, followed by `scratch_bytes` of uninitialised device memory.
-class DeviceArena
-{
-public:
-  template <typename T>
-  void add(T** dptr, const void* src, size_t bytes)
-  {
-    items.push_back({(void**)dptr, src, bytes, total});
-    total += (bytes + 255) & ~(size_t)255;
-  }
-  size_t bytes() const { return std::max<size_t>(total, 256); }
-  // The same layout in memory the caller owns: the tables are written to `h_base`, the device pointers point into
-  // `d_base`; copying [h_base, h_base + bytes()) there is the caller's business (no HIP call here).
-  void place(uint8_t* h_base, uint8_t* d_base)
-  {
-    for (const Item& it : items) {
-      if (it.bytes != 0) {
-        std::memcpy(h_base + it.offset, it.src, it.bytes);
-      }
-      *it.dptr = d_base + it.offset;
-    }
-  }
-  hipError_t commit(void** base, size_t scratch_bytes, void** scratch)
-  {
-    std::vector<uint8_t> staging(std::max<size_t>(total, 256), 0);
-    for (const Item& it : items) {
-      if (it.bytes != 0) {
-        std::memcpy(&staging[it.offset], it.src, it.bytes);
-      }
-    }
-    hipError_t e = hipMalloc(base, staging.size() + scratch_bytes);
-    if (e != hipSuccess) {
-      return e;
-    }
-    for (const Item& it : items) {
-      *it.dptr = (uint8_t*)*base + it.offset;
-    }
-    *scratch = (uint8_t*)*base + staging.size();
-    return hipMemcpy(*base, staging.data(), staging.size(), hipMemcpyHostToDevice);
-  }
-
-private:
-  struct Item {
-    void**      dptr;
-    const void* src;
-    size_t      bytes, offset;
-  };
-  std::vector<Item> items;
-  size_t            total = 0;
-};
-
-} // namespace
-
-
-namespace {
-
-
 } // namespace
 
 struct nrphy_pdsch_plan {
@@ -1695,6 +1635,7 @@ extern "C" int nrphy_pdsch_process_host(nrphy_ctx_t* ctx, const nrphy_pdsch_pdu_
   if (ctx == nullptr || pdu == nullptr || tb == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
+  HostCall            call(ctx);
   nrphy_pdsch_plan_t* plan   = nullptr;
   uint64_t            tb_off = 0;
   uint32_t            gi     = 0;
@@ -1705,11 +1646,10 @@ extern "C" int nrphy_pdsch_process_host(nrphy_ctx_t* ctx, const nrphy_pdsch_pdu_
   const size_t tb_alloc   = ((size_t)pdu->tb_size_bytes + 7) & ~(size_t)3;
   const size_t grid_bytes = (size_t)grid_nof_ports * NRPHY_NSYMB * grid_nof_subc * 4;
   const size_t cw_bytes   = (size_t)(plan->cw_bits / 8);
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-  uint8_t* d_tb   = (uint8_t*)ctx_scratch(ctx, SCRATCH_TB, tb_alloc);
-  uint8_t* d_grid = grid ? (uint8_t*)ctx_scratch(ctx, SCRATCH_GRID, grid_bytes) : nullptr;
-  uint8_t* d_rm   = cw_rm ? (uint8_t*)ctx_scratch(ctx, SCRATCH_CW_RM, cw_bytes) : nullptr;
-  uint8_t* d_scr  = cw_scrambled ? (uint8_t*)ctx_scratch(ctx, SCRATCH_CW_SCR, cw_bytes) : nullptr;
+  uint8_t* d_tb   = call.mem<uint8_t>(SCRATCH_TB, tb_alloc);
+  uint8_t* d_grid = grid ? call.mem<uint8_t>(SCRATCH_GRID, grid_bytes) : nullptr;
+  uint8_t* d_rm   = cw_rm ? call.mem<uint8_t>(SCRATCH_CW_RM, cw_bytes) : nullptr;
+  uint8_t* d_scr  = cw_scrambled ? call.mem<uint8_t>(SCRATCH_CW_SCR, cw_bytes) : nullptr;
   rc = NRPHY_ERR_DEVICE;
   do {
     if (d_tb == nullptr || (grid && d_grid == nullptr) || (cw_rm && d_rm == nullptr) ||
@@ -1741,7 +1681,7 @@ extern "C" int nrphy_pdsch_process_host(nrphy_ctx_t* ctx, const nrphy_pdsch_pdu_
     if (cw_scrambled && hipMemcpyAsync(cw_scrambled, d_scr, cw_out, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
       break;
     }
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
+    if (call.sync() != hipSuccess) {
       break;
     }
     rc = NRPHY_OK;
@@ -1770,15 +1710,15 @@ extern "C" int nrphy_pdsch_process_slot_host(nrphy_ctx_t* ctx, uint32_t n_pdu, c
     tb_off[i] = tb_total;
     tb_total += ((size_t)pdus[i].tb_size_bytes + 7) & ~(size_t)3; // readable to the next multiple of 4
   }
+  HostCall            call(ctx);
   nrphy_pdsch_plan_t* plan = nullptr;
   int rc = nrphy_pdsch_plan_create(ctx, n_pdu, pdus, tb_off.data(), grid_of.data(), 1, grid_nof_ports, grid_nof_subc, &plan);
   if (rc != NRPHY_OK) {
     return rc;
   }
   const size_t grid_bytes = (size_t)grid_nof_ports * NRPHY_NSYMB * grid_nof_subc * 4;
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-  uint8_t* d_tb   = (uint8_t*)ctx_scratch(ctx, SCRATCH_TB, tb_total + 8);
-  uint8_t* d_grid = (uint8_t*)ctx_scratch(ctx, SCRATCH_GRID, grid_bytes);
+  uint8_t* d_tb   = call.mem<uint8_t>(SCRATCH_TB, tb_total + 8);
+  uint8_t* d_grid = call.mem<uint8_t>(SCRATCH_GRID, grid_bytes);
   rc              = NRPHY_ERR_DEVICE;
   do {
     if (d_tb == nullptr || d_grid == nullptr || hipMemsetAsync(d_tb, 0, tb_total + 8, ctx->stream) != hipSuccess) {
@@ -1797,7 +1737,7 @@ extern "C" int nrphy_pdsch_process_slot_host(nrphy_ctx_t* ctx, uint32_t n_pdu, c
     }
     rc = NRPHY_ERR_DEVICE;
     if (hipMemcpyAsync(grid, d_grid, grid_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        call.sync() != hipSuccess) {
       break;
     }
     rc = NRPHY_OK;
@@ -1826,6 +1766,8 @@ extern "C" int nrphy_pdsch_encode_host(nrphy_ctx_t* ctx, const nrphy_pdsch_encod
   pdu.prg_size_rb     = NRPHY_MAX_RB;
   pdu.tbs_lbrm_bytes  = 1; // unused: N_ref is given
   const EncodeOnly    enc    = {cfg->nof_ch_symbols / cfg->nof_layers, cfg->nref};
+  std::vector<uint8_t> packed_local; // a copy target: declared before `call`, so that it outlives the drain
+  HostCall             call(ctx);
   nrphy_pdsch_plan_t* plan   = nullptr;
   uint64_t            tb_off = 0;
   uint32_t            gi     = 0;
@@ -1836,35 +1778,31 @@ extern "C" int nrphy_pdsch_encode_host(nrphy_ctx_t* ctx, const nrphy_pdsch_encod
   const size_t cw_bits  = (size_t)cfg->nof_ch_symbols * cfg->qm;
   const size_t cw_bytes = (size_t)(plan->cw_bits / 8);
   const size_t tb_alloc = ((size_t)cfg->tb_size_bytes + 7) & ~(size_t)3;
-  std::vector<uint8_t> packed_local;
-  uint8_t*             packed = codeword_packed;
+  uint8_t*     packed   = codeword_packed;
   if (packed == nullptr) {
     packed_local.resize((cw_bits + 7) / 8);
     packed = packed_local.data();
   }
-  {
-    std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-    uint8_t* d_tb = (uint8_t*)ctx_scratch(ctx, SCRATCH_TB, tb_alloc);
-    uint8_t* d_rm = (uint8_t*)ctx_scratch(ctx, SCRATCH_CW_RM, cw_bytes);
-    rc            = NRPHY_ERR_DEVICE;
-    do {
-      if (d_tb == nullptr || d_rm == nullptr ||
-          hipMemsetAsync(d_tb + (tb_alloc - 8), 0, 8, ctx->stream) != hipSuccess ||
-          hipMemcpyAsync(d_tb, tb, cfg->tb_size_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-        break;
-      }
-      rc = nrphy_pdsch_run(plan, d_tb, nullptr, d_rm, nullptr, 0, ctx->stream);
-      if (rc != NRPHY_OK) {
-        break;
-      }
-      rc = NRPHY_ERR_DEVICE;
-      if (hipMemcpyAsync(packed, d_rm, (cw_bits + 7) / 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-          hipStreamSynchronize(ctx->stream) != hipSuccess) {
-        break;
-      }
-      rc = NRPHY_OK;
-    } while (false);
-  }
+  uint8_t* d_tb = call.mem<uint8_t>(SCRATCH_TB, tb_alloc);
+  uint8_t* d_rm = call.mem<uint8_t>(SCRATCH_CW_RM, cw_bytes);
+  rc            = NRPHY_ERR_DEVICE;
+  do {
+    if (d_tb == nullptr || d_rm == nullptr ||
+        hipMemsetAsync(d_tb + (tb_alloc - 8), 0, 8, ctx->stream) != hipSuccess ||
+        hipMemcpyAsync(d_tb, tb, cfg->tb_size_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
+      break;
+    }
+    rc = nrphy_pdsch_run(plan, d_tb, nullptr, d_rm, nullptr, 0, ctx->stream);
+    if (rc != NRPHY_OK) {
+      break;
+    }
+    rc = NRPHY_ERR_DEVICE;
+    if (hipMemcpyAsync(packed, d_rm, (cw_bits + 7) / 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        call.sync() != hipSuccess) {
+      break;
+    }
+    rc = NRPHY_OK;
+  } while (false);
   nrphy_pdsch_plan_destroy(plan);
   if (rc == NRPHY_OK && codeword_bits != nullptr) { // the reference's codeword span: one bit per byte
     for (size_t i = 0; i != cw_bits; ++i) {
@@ -2036,29 +1974,21 @@ extern "C" int nrphy_ldpc_rate_dematch_host(nrphy_ctx_t* ctx, const nrphy_ldpc_r
     return NRPHY_ERR_ARGUMENT;
   }
   const unsigned block_length = ((cfg->base_graph == 1) ? 66U : 50U) * cfg->lifting_size;
-  int8_t *       d_in = nullptr, *d_soft = nullptr;
-  int            rc = NRPHY_ERR_DEVICE;
-  do {
-    if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&d_in, cfg->rm_length + 16) != hipSuccess ||
-        hipMalloc((void**)&d_soft, block_length + 16) != hipSuccess ||
-        hipMemcpy(d_in, in, cfg->rm_length, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_soft, soft_buffer, block_length, hipMemcpyHostToDevice) != hipSuccess) {
-      break;
-    }
-    rc = nrphy_ldpc_rate_dematch(ctx, cfg, 1, d_in, cfg->rm_length, d_soft, block_length, new_data, ctx->stream);
-    if (rc != NRPHY_OK) {
-      break;
-    }
-    rc = NRPHY_ERR_DEVICE;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
-        hipMemcpy(soft_buffer, d_soft, block_length, hipMemcpyDeviceToHost) != hipSuccess) {
-      break;
-    }
-    rc = NRPHY_OK;
-  } while (false);
-  (void)hipFree(d_in);
-  (void)hipFree(d_soft);
-  return rc;
+  HostCall       call(ctx);
+  uint8_t*       d[2]; // in, soft buffer
+  if (!call.carve(SCRATCH_RX, {(size_t)cfg->rm_length + 16, (size_t)block_length + 16}, d)) {
+    return NRPHY_ERR_DEVICE;
+  }
+  int8_t *d_in = (int8_t*)d[0], *d_soft = (int8_t*)d[1];
+  HIP_TRY(hipMemcpy(d_in, in, cfg->rm_length, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_soft, soft_buffer, block_length, hipMemcpyHostToDevice));
+  const int rc = nrphy_ldpc_rate_dematch(ctx, cfg, 1, d_in, cfg->rm_length, d_soft, block_length, new_data, ctx->stream);
+  if (rc != NRPHY_OK) {
+    return rc;
+  }
+  HIP_TRY(call.sync());
+  HIP_TRY(hipMemcpy(soft_buffer, d_soft, block_length, hipMemcpyDeviceToHost));
+  return NRPHY_OK;
 }
 
 namespace {
@@ -2197,15 +2127,13 @@ extern "C" int nrphy_demodulate_soft_host(nrphy_ctx_t* ctx, uint32_t modulation,
     return NRPHY_ERR_ARGUMENT;
   }
   const uint32_t              qm = modulation == NRPHY_MOD_PI2_BPSK ? 1U : modulation;
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-  HIP_TRY(hipSetDevice(ctx->device));
-  StreamStaging sym(ctx->stream), nv(ctx->stream), out(ctx->stream);
-  float*  d_sym = (float*)sym.alloc((size_t)nof_symbols * 8);
-  float*  d_nv  = (float*)nv.alloc((size_t)nof_symbols * 4);
-  int8_t* d_out = (int8_t*)out.alloc((size_t)nof_symbols * qm + 16);
-  if (d_sym == nullptr || d_nv == nullptr || d_out == nullptr) {
+  HostCall call(ctx);
+  uint8_t* d[3]; // symbols, noise variances, soft bits
+  if (!call.carve(SCRATCH_RX, {(size_t)nof_symbols * 8, (size_t)nof_symbols * 4, (size_t)nof_symbols * qm + 16}, d)) {
     return NRPHY_ERR_DEVICE;
   }
+  float * d_sym = (float*)d[0], *d_nv = (float*)d[1];
+  int8_t* d_out = (int8_t*)d[2];
   HIP_TRY(hipMemcpyAsync(d_sym, symbols, (size_t)nof_symbols * 8, hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(hipMemcpyAsync(d_nv, noise_vars, (size_t)nof_symbols * 4, hipMemcpyHostToDevice, ctx->stream));
   const int rc = nrphy_demodulate_soft(ctx, modulation, 1, nof_symbols, d_sym, d_nv, d_out, ctx->stream);
@@ -2213,7 +2141,7 @@ extern "C" int nrphy_demodulate_soft_host(nrphy_ctx_t* ctx, uint32_t modulation,
     return rc;
   }
   HIP_TRY(hipMemcpyAsync(llr, d_out, (size_t)nof_symbols * qm, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(call.sync());
   return NRPHY_OK;
 }
 
@@ -2245,28 +2173,22 @@ extern "C" int nrphy_llr_descramble_host(nrphy_ctx_t* ctx, uint32_t c_init, uint
   if (length == 0) {
     return NRPHY_OK;
   }
-  int8_t*   d_buf = nullptr;
-  uint32_t* d_ci  = nullptr;
-  int       rc    = NRPHY_ERR_DEVICE;
-  do {
-    if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&d_buf, (size_t)length + 16) != hipSuccess ||
-        hipMalloc((void**)&d_ci, 16) != hipSuccess || hipMemcpy(d_buf, in, length, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_ci, &c_init, sizeof(c_init), hipMemcpyHostToDevice) != hipSuccess) {
-      break;
-    }
-    rc = nrphy_llr_descramble(ctx, 1, d_ci, length, d_buf, length, d_buf, length, ctx->stream); // in place, as the caller does
-    if (rc != NRPHY_OK) {
-      break;
-    }
-    rc = NRPHY_ERR_DEVICE;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipMemcpy(out, d_buf, length, hipMemcpyDeviceToHost) != hipSuccess) {
-      break;
-    }
-    rc = NRPHY_OK;
-  } while (false);
-  (void)hipFree(d_buf);
-  (void)hipFree(d_ci);
-  return rc;
+  HostCall call(ctx);
+  uint8_t* d[2]; // soft bits, c_init
+  if (!call.carve(SCRATCH_RX, {(size_t)length + 16, 16}, d)) {
+    return NRPHY_ERR_DEVICE;
+  }
+  int8_t*   d_buf = (int8_t*)d[0];
+  uint32_t* d_ci  = (uint32_t*)d[1];
+  HIP_TRY(hipMemcpy(d_buf, in, length, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_ci, &c_init, sizeof(c_init), hipMemcpyHostToDevice));
+  const int rc = nrphy_llr_descramble(ctx, 1, d_ci, length, d_buf, length, d_buf, length, ctx->stream); // in place, as the caller does
+  if (rc != NRPHY_OK) {
+    return rc;
+  }
+  HIP_TRY(call.sync());
+  HIP_TRY(hipMemcpy(out, d_buf, length, hipMemcpyDeviceToHost));
+  return NRPHY_OK;
 }
 
 namespace {
@@ -2609,45 +2531,35 @@ extern "C" int nrphy_ldpc_decode_host(nrphy_ctx_t* ctx, const nrphy_ldpc_decoder
     return NRPHY_ERR_ARGUMENT;
   }
   const unsigned K     = ((cfg->base_graph == 1) ? 22U : 10U) * cfg->lifting_size;
-  int8_t*        d_llr = nullptr;
-  uint8_t*       d_out = nullptr;
-  void*          d_scratch = nullptr;
-  int            rc    = NRPHY_ERR_DEVICE;
-  do {
-    if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&d_llr, cfg->nof_llr + 16) != hipSuccess ||
-        hipMalloc((void**)&d_out, (K + 7) / 8 + 16) != hipSuccess ||
-        hipMemcpy(d_llr, llr, cfg->nof_llr, hipMemcpyHostToDevice) != hipSuccess) {
-      break;
-    }
-    uint32_t* d_it = (uint32_t*)(d_out + (((K + 7) / 8 + 3) & ~3U));
-    uint64_t  scratch_bytes = 0;
-    if (nrphy_ldpc_decoder_scratch_bytes(ctx, cfg, 1, &scratch_bytes) != NRPHY_OK) {
-      rc = NRPHY_ERR_ARGUMENT;
-      break;
-    }
-    if (hipMalloc(&d_scratch, scratch_bytes) != hipSuccess) {
-      break;
-    }
-    rc = nrphy_ldpc_decode(ctx, cfg, 1, d_llr, cfg->nof_llr, d_out, (K + 7) / 8, d_it, d_scratch, ctx->stream);
-    if (rc != NRPHY_OK) {
-      break;
-    }
-    rc = NRPHY_ERR_DEVICE;
-    uint32_t it = 0;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
-        hipMemcpy(message_packed, d_out, (K + 7) / 8, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(&it, d_it, sizeof(it), hipMemcpyDeviceToHost) != hipSuccess) {
-      break;
-    }
-    if (iterations) {
-      *iterations = it;
-    }
-    rc = NRPHY_OK;
-  } while (false);
-  (void)hipFree(d_llr);
-  (void)hipFree(d_out);
-  (void)hipFree(d_scratch);
-  return rc;
+  HostCall       call(ctx);
+  uint8_t*       d[2]; // soft bits; message, then the iteration count at the next multiple of 4
+  if (!call.carve(SCRATCH_RX, {(size_t)cfg->nof_llr + 16, (size_t)(K + 7) / 8 + 16}, d)) {
+    return NRPHY_ERR_DEVICE;
+  }
+  int8_t*   d_llr = (int8_t*)d[0];
+  uint8_t*  d_out = d[1];
+  uint32_t* d_it  = (uint32_t*)(d_out + (((K + 7) / 8 + 3) & ~3U));
+  HIP_TRY(hipMemcpy(d_llr, llr, cfg->nof_llr, hipMemcpyHostToDevice));
+  uint64_t scratch_bytes = 0;
+  if (nrphy_ldpc_decoder_scratch_bytes(ctx, cfg, 1, &scratch_bytes) != NRPHY_OK) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  void* d_scratch = call.mem(SCRATCH_DECODER, scratch_bytes);
+  if (d_scratch == nullptr) {
+    return NRPHY_ERR_DEVICE;
+  }
+  const int rc = nrphy_ldpc_decode(ctx, cfg, 1, d_llr, cfg->nof_llr, d_out, (K + 7) / 8, d_it, d_scratch, ctx->stream);
+  if (rc != NRPHY_OK) {
+    return rc;
+  }
+  uint32_t it = 0;
+  HIP_TRY(call.sync());
+  HIP_TRY(hipMemcpy(message_packed, d_out, (K + 7) / 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&it, d_it, sizeof(it), hipMemcpyDeviceToHost));
+  if (iterations) {
+    *iterations = it;
+  }
+  return NRPHY_OK;
 }
 
 // One codeblock through rate dematcher and decoder with one round trip over the link: what a per-codeblock
@@ -2665,13 +2577,8 @@ extern "C" int nrphy_pusch_decode_codeblock_host(nrphy_ctx_t* ctx, const nrphy_l
   const unsigned k = ((dm->base_graph == 1) ? 22U : 10U) * zc, kbytes = (k + 7) / 8;
   const size_t   off_soft = ((size_t)dm->rm_length + 63) & ~(size_t)63, off_out = off_soft + (((size_t)n + 63) & ~(size_t)63);
   const size_t   off_it = off_out + (((size_t)kbytes + 63) & ~(size_t)63);
-  std::lock_guard<std::recursive_mutex> host_lock(ctx->host_mutex);
-  HIP_TRY(hipSetDevice(ctx->device));
-  uint8_t* base = nullptr;
-  {
-    std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-    base = (uint8_t*)ctx_scratch(ctx, SCRATCH_RX, off_it + 64);
-  }
+  HostCall call(ctx);
+  uint8_t* base = call.mem<uint8_t>(SCRATCH_RX, off_it + 64);
   if (base == nullptr) {
     return NRPHY_ERR_DEVICE;
   }
@@ -2694,7 +2601,7 @@ extern "C" int nrphy_pusch_decode_codeblock_host(nrphy_ctx_t* ctx, const nrphy_l
   if (nrphy_ldpc_decoder_scratch_bytes(ctx, &dec, 1, &scratch_bytes) != NRPHY_OK) {
     return NRPHY_ERR_ARGUMENT;
   }
-  void* d_scratch = ctx_scratch(ctx, SCRATCH_DECODER, scratch_bytes); // host_mutex is held for the whole call
+  void* d_scratch = call.mem(SCRATCH_DECODER, scratch_bytes);
   if (d_scratch == nullptr) {
     return NRPHY_ERR_DEVICE;
   }
@@ -2707,7 +2614,7 @@ extern "C" int nrphy_pusch_decode_codeblock_host(nrphy_ctx_t* ctx, const nrphy_l
   HIP_TRY(hipMemcpyAsync(soft_buffer, base + off_soft, n, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipMemcpyAsync(message_packed, base + off_out, kbytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipMemcpyAsync(&it, base + off_it, sizeof(it), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(call.sync());
   if (iterations) {
     *iterations = it;
   }
@@ -3090,25 +2997,19 @@ extern "C" int nrphy_csi_rs_map_host(nrphy_ctx_t* ctx, const nrphy_csi_rs_cfg_t*
   if (ctx == nullptr || cfg == nullptr || grid == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
-  std::lock_guard<std::recursive_mutex> host_lock(ctx->host_mutex);
+  HostCall     call(ctx);
   const size_t bytes  = (size_t)nof_ports * NRPHY_NSYMB * nof_subc * 4;
-  void*        d_grid = nullptr;
-  HIP_TRY(hipSetDevice(ctx->device));
-  {
-    std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-    d_grid = ctx_scratch(ctx, SCRATCH_GRID, bytes);
-  }
+  void*        d_grid = call.mem(SCRATCH_GRID, bytes);
   if (d_grid == nullptr) {
     return NRPHY_ERR_DEVICE;
   }
   HIP_TRY(hipMemcpyAsync(d_grid, grid, bytes, hipMemcpyHostToDevice, ctx->stream));
   const int rc = nrphy_csi_rs_map(ctx, 1, cfg, nullptr, d_grid, nof_ports, nof_subc, ctx->stream);
   if (rc != NRPHY_OK) {
-    (void)hipStreamSynchronize(ctx->stream);
     return rc;
   }
   HIP_TRY(hipMemcpyAsync(grid, d_grid, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(call.sync());
   return NRPHY_OK;
 }
 
@@ -3431,10 +3332,9 @@ extern "C" int nrphy_amplitude_control_host(nrphy_ctx_t* ctx, const nrphy_amplit
   if (ctx == nullptr || cfg == nullptr || in == nullptr || out == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-  HIP_TRY(hipSetDevice(ctx->device));
+  HostCall     call(ctx);
   const size_t bytes = (size_t)nof_samples * sizeof(float2);
-  float*       d_buf = (float*)ctx_scratch(ctx, SCRATCH_IQ, bytes + 64);
+  float*       d_buf = call.mem<float>(SCRATCH_IQ, bytes + 64);
   if (d_buf == nullptr) {
     return NRPHY_ERR_DEVICE;
   }
@@ -3447,7 +3347,7 @@ extern "C" int nrphy_amplitude_control_host(nrphy_ctx_t* ctx, const nrphy_amplit
   nrphy_amplitude_stats_t st;
   HIP_TRY(hipMemcpyAsync(out, d_buf, bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIP_TRY(hipMemcpyAsync(&st, d_stats, sizeof(st), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(call.sync());
   return metrics ? nrphy_amplitude_metrics(cfg, &st, metrics) : NRPHY_OK;
 }
 
@@ -3472,10 +3372,9 @@ extern "C" int nrphy_iq_convert_ci16_host(nrphy_ctx_t* ctx, const float* in, uin
   if (ctx == nullptr || in == nullptr || out == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-  HIP_TRY(hipSetDevice(ctx->device));
+  HostCall     call(ctx);
   const size_t bytes = (size_t)nof_samples * sizeof(float2), obytes = (size_t)nof_samples * 4;
-  uint8_t*     d_buf = (uint8_t*)ctx_scratch(ctx, SCRATCH_IQ, bytes + obytes + 64);
+  uint8_t*     d_buf = call.mem<uint8_t>(SCRATCH_IQ, bytes + obytes + 64);
   if (d_buf == nullptr) {
     return NRPHY_ERR_DEVICE;
   }
@@ -3486,7 +3385,7 @@ extern "C" int nrphy_iq_convert_ci16_host(nrphy_ctx_t* ctx, const float* in, uin
     return rc;
   }
   HIP_TRY(hipMemcpyAsync(out, d_out, obytes, hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(call.sync());
   return NRPHY_OK;
 }
 
@@ -3532,10 +3431,9 @@ extern "C" int nrphy_ofh_compress_host(nrphy_ctx_t* ctx, const nrphy_ofh_compres
   if (ctx == nullptr || cfg == nullptr || prbs == nullptr || out == nullptr || nof_prb == 0 || nof_prb > NRPHY_MAX_RB) {
     return NRPHY_ERR_ARGUMENT;
   }
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-  HIP_TRY(hipSetDevice(ctx->device));
+  HostCall     call(ctx);
   const size_t in_bytes = (size_t)nof_prb * 48, out_bytes = (size_t)nof_prb * 49;
-  uint8_t*     d_buf    = (uint8_t*)ctx_scratch(ctx, SCRATCH_GRID, in_bytes + out_bytes + 64);
+  uint8_t*     d_buf    = call.mem<uint8_t>(SCRATCH_GRID, in_bytes + out_bytes + 64);
   if (d_buf == nullptr) {
     return NRPHY_ERR_DEVICE;
   }
@@ -3546,7 +3444,7 @@ extern "C" int nrphy_ofh_compress_host(nrphy_ctx_t* ctx, const nrphy_ofh_compres
     return rc;
   }
   HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)nof_prb * nrphy_ofh_compressed_prb_bytes(cfg), hipMemcpyDeviceToHost, ctx->stream));
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(call.sync());
   return NRPHY_OK;
 }
 
@@ -3607,39 +3505,29 @@ extern "C" int nrphy_ofdm_demodulate_slot_host(nrphy_ofdm_plan_t* plan, const fl
     return NRPHY_ERR_ARGUMENT;
   }
   nrphy_ctx*   ctx        = plan->ctx;
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
+  HostCall     call(ctx);
   const size_t grid_words = (size_t)plan->nof_ports * NRPHY_NSYMB * 12 * plan->cfg.bw_rb;
   const size_t slot_size  = nrphy_ofdm_slot_size(&plan->cfg, slot_index);
-  uint32_t *   d_grid = nullptr, *d_slot = nullptr;
-  float2*      d_iq   = nullptr;
-  int          rc     = NRPHY_ERR_DEVICE;
-  do {
-    if (hipSetDevice(ctx->device) != hipSuccess || (d_grid = (uint32_t*)ctx_scratch(ctx, SCRATCH_GRID, grid_words * 4)) == nullptr ||
-        (d_iq = (float2*)ctx_scratch(ctx, SCRATCH_IQ, (size_t)plan->nof_ports * plan->slot_stride * sizeof(float2))) == nullptr ||
-        (d_slot = (uint32_t*)ctx_scratch(ctx, SCRATCH_SMALL, 16)) == nullptr ||
-        hipMemcpy(d_slot, &slot_index, sizeof(slot_index), hipMemcpyHostToDevice) != hipSuccess) {
-      break;
-    }
-    // Host: ports back to back, slot_size samples each; device: slot_stride apart.
-    if (hipMemcpy2D(d_iq, (size_t)plan->slot_stride * sizeof(float2), iq, slot_size * sizeof(float2),
-                    slot_size * sizeof(float2), plan->nof_ports, hipMemcpyHostToDevice) != hipSuccess) {
-      break;
-    }
-    rc = nrphy_ofdm_demod_run(plan, 1, (const float*)d_iq, d_slot, window_offset, d_grid, ctx->stream);
-    if (rc != NRPHY_OK) {
-      break;
-    }
-    rc = NRPHY_ERR_DEVICE;
-    // Only the symbols a slot has (12 with extended cyclic prefix) are written, as by the reference's demodulator.
-    const size_t port_bytes = (size_t)NRPHY_NSYMB * 12 * plan->cfg.bw_rb * 4;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
-        hipMemcpy2D(grid, port_bytes, d_grid, port_bytes, (size_t)plan->nsymb * 12 * plan->cfg.bw_rb * 4,
-                    plan->nof_ports, hipMemcpyDeviceToHost) != hipSuccess) {
-      break;
-    }
-    rc = NRPHY_OK;
-  } while (false);
-  return rc;
+  uint32_t*    d_grid     = call.mem<uint32_t>(SCRATCH_GRID, grid_words * 4);
+  float2*      d_iq       = call.mem<float2>(SCRATCH_IQ, (size_t)plan->nof_ports * plan->slot_stride * sizeof(float2));
+  uint32_t*    d_slot     = call.mem<uint32_t>(SCRATCH_SMALL, 16);
+  if (d_grid == nullptr || d_iq == nullptr || d_slot == nullptr) {
+    return NRPHY_ERR_DEVICE;
+  }
+  HIP_TRY(hipMemcpy(d_slot, &slot_index, sizeof(slot_index), hipMemcpyHostToDevice));
+  // Host: ports back to back, slot_size samples each; device: slot_stride apart.
+  HIP_TRY(hipMemcpy2D(d_iq, (size_t)plan->slot_stride * sizeof(float2), iq, slot_size * sizeof(float2),
+                      slot_size * sizeof(float2), plan->nof_ports, hipMemcpyHostToDevice));
+  const int rc = nrphy_ofdm_demod_run(plan, 1, (const float*)d_iq, d_slot, window_offset, d_grid, ctx->stream);
+  if (rc != NRPHY_OK) {
+    return rc;
+  }
+  // Only the symbols a slot has (12 with extended cyclic prefix) are written, as by the reference's demodulator.
+  const size_t port_bytes = (size_t)NRPHY_NSYMB * 12 * plan->cfg.bw_rb * 4;
+  HIP_TRY(call.sync());
+  HIP_TRY(hipMemcpy2D(grid, port_bytes, d_grid, port_bytes, (size_t)plan->nsymb * 12 * plan->cfg.bw_rb * 4, plan->nof_ports,
+                      hipMemcpyDeviceToHost));
+  return NRPHY_OK;
 }
 
 extern "C" int nrphy_ofdm_demodulate_symbol_host(nrphy_ofdm_plan_t* plan, const float* input, uint32_t input_size,
@@ -3652,36 +3540,26 @@ extern "C" int nrphy_ofdm_demodulate_symbol_host(nrphy_ofdm_plan_t* plan, const 
   // One symbol of one port: the samples are placed where the slot kernel expects them (the other symbols of the
   // staging slot transform zeros), the symbol's row is read back.
   nrphy_ctx*     ctx  = plan->ctx;
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
+  HostCall       call(ctx);
   const uint32_t rg   = 12 * plan->cfg.bw_rb;
   const uint32_t slot = symbol_index / plan->nsymb, l = symbol_index % plan->nsymb;
   const size_t   iq_samples = (size_t)plan->nof_ports * plan->slot_stride;
-  uint32_t *     d_grid = nullptr, *d_slot = nullptr;
-  float2*        d_iq   = nullptr;
-  int            rc     = NRPHY_ERR_DEVICE;
-  do {
-    if (hipSetDevice(ctx->device) != hipSuccess ||
-        (d_grid = (uint32_t*)ctx_scratch(ctx, SCRATCH_GRID, (size_t)plan->nof_ports * NRPHY_NSYMB * rg * 4)) == nullptr ||
-        (d_iq = (float2*)ctx_scratch(ctx, SCRATCH_IQ, iq_samples * sizeof(float2))) == nullptr ||
-        hipMemset(d_iq, 0, iq_samples * sizeof(float2)) != hipSuccess ||
-        hipMemcpy(d_iq + plan->off[symbol_index], input, (size_t)input_size * sizeof(float2),
-                  hipMemcpyHostToDevice) != hipSuccess ||
-        (d_slot = (uint32_t*)ctx_scratch(ctx, SCRATCH_SMALL, 16)) == nullptr ||
-        hipMemcpy(d_slot, &slot, sizeof(slot), hipMemcpyHostToDevice) != hipSuccess) {
-      break;
-    }
-    rc = nrphy_ofdm_demod_run(plan, 1, (const float*)d_iq, d_slot, window_offset, d_grid, ctx->stream);
-    if (rc != NRPHY_OK) {
-      break;
-    }
-    rc = NRPHY_ERR_DEVICE;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
-        hipMemcpy(grid_row, d_grid + (size_t)l * rg, (size_t)rg * 4, hipMemcpyDeviceToHost) != hipSuccess) {
-      break;
-    }
-    rc = NRPHY_OK;
-  } while (false);
-  return rc;
+  uint32_t*      d_grid     = call.mem<uint32_t>(SCRATCH_GRID, (size_t)plan->nof_ports * NRPHY_NSYMB * rg * 4);
+  float2*        d_iq       = call.mem<float2>(SCRATCH_IQ, iq_samples * sizeof(float2));
+  uint32_t*      d_slot     = call.mem<uint32_t>(SCRATCH_SMALL, 16);
+  if (d_grid == nullptr || d_iq == nullptr || d_slot == nullptr) {
+    return NRPHY_ERR_DEVICE;
+  }
+  HIP_TRY(hipMemset(d_iq, 0, iq_samples * sizeof(float2)));
+  HIP_TRY(hipMemcpy(d_iq + plan->off[symbol_index], input, (size_t)input_size * sizeof(float2), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_slot, &slot, sizeof(slot), hipMemcpyHostToDevice));
+  const int rc = nrphy_ofdm_demod_run(plan, 1, (const float*)d_iq, d_slot, window_offset, d_grid, ctx->stream);
+  if (rc != NRPHY_OK) {
+    return rc;
+  }
+  HIP_TRY(call.sync());
+  HIP_TRY(hipMemcpy(grid_row, d_grid + (size_t)l * rg, (size_t)rg * 4, hipMemcpyDeviceToHost));
+  return NRPHY_OK;
 }
 
 extern "C" int nrphy_ofdm_plan_enable_timing(nrphy_ofdm_plan_t* plan, uint32_t max_runs)
@@ -3740,37 +3618,27 @@ extern "C" int nrphy_ofdm_modulate_symbol_host(nrphy_ofdm_plan_t* plan, const vo
       output_size != plan->cp[symbol_index] + plan->cfg.dft_size) { // ofdm_modulator_impl.cpp:68-75
     return NRPHY_ERR_ARGUMENT;
   }
-  nrphy_ctx*   ctx        = plan->ctx;
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-  const size_t grid_words = (size_t)plan->nof_ports * NRPHY_NSYMB * 12 * plan->cfg.bw_rb;
-  const size_t iq_samples = (size_t)plan->nof_ports * plan->slot_stride;
-  uint32_t *   d_grid = nullptr, *d_slot = nullptr;
-  float2*      d_iq   = nullptr;
-  const uint32_t slot = symbol_index / plan->nsymb;
-  int            rc   = NRPHY_ERR_DEVICE;
-  do {
-    if ((d_grid = (uint32_t*)ctx_scratch(ctx, SCRATCH_GRID, grid_words * 4)) == nullptr ||
-        hipMemcpy(d_grid, grid, grid_words * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        (d_iq = (float2*)ctx_scratch(ctx, SCRATCH_IQ, iq_samples * sizeof(float2))) == nullptr ||
-        (d_slot = (uint32_t*)ctx_scratch(ctx, SCRATCH_SMALL, 16)) == nullptr ||
-        hipMemcpy(d_slot, &slot, sizeof(slot), hipMemcpyHostToDevice) != hipSuccess) {
-      break;
-    }
-    rc = nrphy_ofdm_run(plan, 1, d_grid, d_slot, (float*)d_iq, ctx->stream);
-    if (rc != NRPHY_OK) {
-      break;
-    }
-    rc = NRPHY_ERR_DEVICE;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
-      break;
-    }
-    const size_t src = (size_t)port_index * plan->slot_stride + plan->off[symbol_index];
-    if (hipMemcpy(output, d_iq + src, (size_t)output_size * sizeof(float2), hipMemcpyDeviceToHost) != hipSuccess) {
-      break;
-    }
-    rc = NRPHY_OK;
-  } while (false);
-  return rc;
+  nrphy_ctx*     ctx        = plan->ctx;
+  HostCall       call(ctx);
+  const size_t   grid_words = (size_t)plan->nof_ports * NRPHY_NSYMB * 12 * plan->cfg.bw_rb;
+  const size_t   iq_samples = (size_t)plan->nof_ports * plan->slot_stride;
+  const uint32_t slot       = symbol_index / plan->nsymb;
+  uint32_t*      d_grid     = call.mem<uint32_t>(SCRATCH_GRID, grid_words * 4);
+  float2*        d_iq       = call.mem<float2>(SCRATCH_IQ, iq_samples * sizeof(float2));
+  uint32_t*      d_slot     = call.mem<uint32_t>(SCRATCH_SMALL, 16);
+  if (d_grid == nullptr || d_iq == nullptr || d_slot == nullptr) {
+    return NRPHY_ERR_DEVICE;
+  }
+  HIP_TRY(hipMemcpy(d_grid, grid, grid_words * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_slot, &slot, sizeof(slot), hipMemcpyHostToDevice));
+  const int rc = nrphy_ofdm_run(plan, 1, d_grid, d_slot, (float*)d_iq, ctx->stream);
+  if (rc != NRPHY_OK) {
+    return rc;
+  }
+  HIP_TRY(call.sync());
+  const size_t src = (size_t)port_index * plan->slot_stride + plan->off[symbol_index];
+  HIP_TRY(hipMemcpy(output, d_iq + src, (size_t)output_size * sizeof(float2), hipMemcpyDeviceToHost));
+  return NRPHY_OK;
 }
 
 extern "C" int nrphy_dft_run(nrphy_ctx_t* ctx, uint32_t size, int inverse, uint32_t batch, const float* d_in,
@@ -3807,28 +3675,19 @@ extern "C" int nrphy_dft_run_host(nrphy_ctx_t* ctx, uint32_t size, int inverse, 
     return NRPHY_ERR_ARGUMENT;
   }
   const size_t bytes = (size_t)size * sizeof(float2);
-  float *      d_in = nullptr, *d_out = nullptr;
-  int          rc   = NRPHY_ERR_DEVICE;
-  do {
-    if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc((void**)&d_in, bytes) != hipSuccess ||
-        hipMalloc((void**)&d_out, bytes) != hipSuccess ||
-        hipMemcpy(d_in, in, bytes, hipMemcpyHostToDevice) != hipSuccess) {
-      break;
-    }
-    rc = nrphy_dft_run(ctx, size, inverse, 1, d_in, d_out, ctx->stream);
-    if (rc != NRPHY_OK) {
-      break;
-    }
-    rc = NRPHY_ERR_DEVICE;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess ||
-        hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
-      break;
-    }
-    rc = NRPHY_OK;
-  } while (false);
-  (void)hipFree(d_in);
-  (void)hipFree(d_out);
-  return rc;
+  HostCall     call(ctx);
+  uint8_t*     d[2]; // in, out
+  if (!call.carve(SCRATCH_IQ, {bytes, bytes}, d)) {
+    return NRPHY_ERR_DEVICE;
+  }
+  HIP_TRY(hipMemcpy(d[0], in, bytes, hipMemcpyHostToDevice));
+  const int rc = nrphy_dft_run(ctx, size, inverse, 1, (const float*)d[0], (float*)d[1], ctx->stream);
+  if (rc != NRPHY_OK) {
+    return rc;
+  }
+  HIP_TRY(call.sync());
+  HIP_TRY(hipMemcpy(out, d[1], bytes, hipMemcpyDeviceToHost));
+  return NRPHY_OK;
 }
 
 extern "C" int nrphy_ofdm_modulate_slot_host(nrphy_ofdm_plan_t* plan, const void* grid, uint32_t slot_index, float* iq)
@@ -3837,34 +3696,25 @@ extern "C" int nrphy_ofdm_modulate_slot_host(nrphy_ofdm_plan_t* plan, const void
     return NRPHY_ERR_ARGUMENT;
   }
   nrphy_ctx*     ctx        = plan->ctx;
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
+  HostCall       call(ctx);
   const size_t   grid_words = (size_t)plan->nof_ports * NRPHY_NSYMB * 12 * plan->cfg.bw_rb;
   const size_t   iq_samples = (size_t)plan->nof_ports * plan->slot_stride;
   const uint32_t slot_size  = nrphy_ofdm_slot_size(&plan->cfg, slot_index);
-  uint32_t *     d_grid = nullptr, *d_slot = nullptr;
-  float2*        d_iq   = nullptr;
-  int            rc     = NRPHY_ERR_DEVICE;
-  do {
-    if (hipSetDevice(ctx->device) != hipSuccess || (d_grid = (uint32_t*)ctx_scratch(ctx, SCRATCH_GRID, grid_words * 4)) == nullptr ||
-        hipMemcpy(d_grid, grid, grid_words * 4, hipMemcpyHostToDevice) != hipSuccess ||
-        (d_iq = (float2*)ctx_scratch(ctx, SCRATCH_IQ, iq_samples * sizeof(float2))) == nullptr ||
-        (d_slot = (uint32_t*)ctx_scratch(ctx, SCRATCH_SMALL, 16)) == nullptr ||
-        hipMemcpy(d_slot, &slot_index, sizeof(slot_index), hipMemcpyHostToDevice) != hipSuccess) {
-      break;
-    }
-    rc = nrphy_ofdm_run(plan, 1, d_grid, d_slot, (float*)d_iq, ctx->stream);
-    if (rc != NRPHY_OK) {
-      break;
-    }
-    rc = NRPHY_ERR_DEVICE;
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess) {
-      break;
-    }
-    // Ports back to back on the host, slot_stride apart on the device: one strided copy.
-    if (hipMemcpy2D(iq, (size_t)slot_size * sizeof(float2), d_iq, (size_t)plan->slot_stride * sizeof(float2),
-                    (size_t)slot_size * sizeof(float2), plan->nof_ports, hipMemcpyDeviceToHost) == hipSuccess) {
-      rc = NRPHY_OK;
-    }
-  } while (false);
-  return rc;
+  uint32_t*      d_grid     = call.mem<uint32_t>(SCRATCH_GRID, grid_words * 4);
+  float2*        d_iq       = call.mem<float2>(SCRATCH_IQ, iq_samples * sizeof(float2));
+  uint32_t*      d_slot     = call.mem<uint32_t>(SCRATCH_SMALL, 16);
+  if (d_grid == nullptr || d_iq == nullptr || d_slot == nullptr) {
+    return NRPHY_ERR_DEVICE;
+  }
+  HIP_TRY(hipMemcpy(d_grid, grid, grid_words * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_slot, &slot_index, sizeof(slot_index), hipMemcpyHostToDevice));
+  const int rc = nrphy_ofdm_run(plan, 1, d_grid, d_slot, (float*)d_iq, ctx->stream);
+  if (rc != NRPHY_OK) {
+    return rc;
+  }
+  HIP_TRY(call.sync());
+  // Ports back to back on the host, slot_stride apart on the device: one strided copy.
+  HIP_TRY(hipMemcpy2D(iq, (size_t)slot_size * sizeof(float2), d_iq, (size_t)plan->slot_stride * sizeof(float2),
+                      (size_t)slot_size * sizeof(float2), plan->nof_ports, hipMemcpyDeviceToHost));
+  return NRPHY_OK;
 }

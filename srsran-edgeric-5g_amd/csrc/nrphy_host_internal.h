@@ -1,5 +1,6 @@
-// Host-side internals shared by the translation units behind the C ABI (nrphy_host.cpp, dl_control_host.cpp,
-// lower_phy_host.cpp): the context, its staging buffers, small helpers.  Not part of the ABI.
+// Host-side internals shared by the translation units behind the C ABI (nrphy_host.cpp, dl_control_host.cpp, pdsch_async.cpp,
+// dl_slot_async.cpp, pusch_demod_host.cpp, pusch_chest_host.cpp): the context, its staging buffers, small helpers.  Not part
+// of the ABI.
 #pragma once
 
 #include "nrphy_internal.h"
@@ -73,6 +74,59 @@ hipError_t upload(T** dptr, const void* src, size_t bytes)
   return hipMemcpy(*dptr, src, bytes, hipMemcpyHostToDevice);
 }
 
+// All tables of a plan in ONE device allocation filled by ONE copy (a plan of a single PDU used to spend most of its
+// creation time in a dozen hipMalloc / hipMemcpy pairs).  add() registers a table; commit() allocates, copies and
+// points every registered device pointer into the block, followed by `scratch_bytes` of uninitialised device memory.
+class DeviceArena
+{
+public:
+  template <typename T>
+  void add(T** dptr, const void* src, size_t bytes)
+  {
+    items.push_back({(void**)dptr, src, bytes, total});
+    total += (bytes + 255) & ~(size_t)255;
+  }
+  size_t bytes() const { return std::max<size_t>(total, 256); }
+  // The same layout in memory the caller owns: the tables are written to `h_base`, the device pointers point into
+  // `d_base`; copying [h_base, h_base + bytes()) there is the caller's business (no HIP call here).
+  void place(uint8_t* h_base, uint8_t* d_base)
+  {
+    for (const Item& it : items) {
+      if (it.bytes != 0) {
+        std::memcpy(h_base + it.offset, it.src, it.bytes);
+      }
+      *it.dptr = d_base + it.offset;
+    }
+  }
+  hipError_t commit(void** base, size_t scratch_bytes, void** scratch)
+  {
+    std::vector<uint8_t> staging(std::max<size_t>(total, 256), 0);
+    for (const Item& it : items) {
+      if (it.bytes != 0) {
+        std::memcpy(&staging[it.offset], it.src, it.bytes);
+      }
+    }
+    hipError_t e = hipMalloc(base, staging.size() + scratch_bytes);
+    if (e != hipSuccess) {
+      return e;
+    }
+    for (const Item& it : items) {
+      *it.dptr = (uint8_t*)*base + it.offset;
+    }
+    *scratch = (uint8_t*)*base + staging.size();
+    return hipMemcpy(*base, staging.data(), staging.size(), hipMemcpyHostToDevice);
+  }
+
+private:
+  struct Item {
+    void**      dptr;
+    const void* src;
+    size_t      bytes, offset;
+  };
+  std::vector<Item> items;
+  size_t            total = 0;
+};
+
 } // namespace
 
 // Environment knobs (INTEGRATION.md section 5 lists them): A/B and test aids, none changes a result.  Read ONCE, when the
@@ -96,6 +150,9 @@ struct Tunables {
 };
 Tunables read_tunables();
 
+enum ScratchSlot { SCRATCH_TB = 0, SCRATCH_GRID, SCRATCH_CW_RM, SCRATCH_CW_SCR, SCRATCH_IQ, SCRATCH_SMALL,
+                   SCRATCH_DECODER, SCRATCH_RX, SCRATCH_COUNT };
+
 struct nrphy_ctx {
   int          device   = 0;
   Tunables     tune;
@@ -113,11 +170,11 @@ struct nrphy_ctx {
   std::vector<LiftedGraph> graphs; // host copy (plan creation sizes the LDS staging of graph rows from it)
   // Device staging of the host-span entry points (*_host): grow-only buffers, one call at a time per context.
   // One lock for everything context-owned and shared: the staging buffers below and the lazily built tables.  The
-  // host-span entry points (*_host) hold it from their first staging access to their last copy, so two of them never
-  // interleave on a buffer; it is recursive because they are built from device-pointer calls that take it briefly.
+  // host-span entry points (*_host) hold it for the whole call (HostCall below), so two of them never interleave on a
+  // buffer; it is recursive because they are built from device-pointer calls that take it briefly.
   std::recursive_mutex host_mutex;
-  void*      scratch[8]       = {};
-  size_t     scratch_bytes[8] = {};
+  void*      scratch[SCRATCH_COUNT]       = {};
+  size_t     scratch_bytes[SCRATCH_COUNT] = {};
 };
 
 // ---- PDSCH plans in caller-owned memory (the asynchronous queue) ----------------------------------------------------------
@@ -145,8 +202,6 @@ int nrphy_pdsch_plan_create_placed(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy
 namespace {
 
 // Staging buffer `slot` of the context with room for `bytes` (reallocated only when it has to grow).
-enum ScratchSlot { SCRATCH_TB = 0, SCRATCH_GRID, SCRATCH_CW_RM, SCRATCH_CW_SCR, SCRATCH_IQ, SCRATCH_SMALL,
-                   SCRATCH_DECODER, SCRATCH_RX, SCRATCH_COUNT };
 void* ctx_scratch(nrphy_ctx* ctx, ScratchSlot slot, size_t bytes)
 {
   if (bytes > ctx->scratch_bytes[slot]) {
@@ -162,9 +217,62 @@ void* ctx_scratch(nrphy_ctx* ctx, ScratchSlot slot, size_t bytes)
   return ctx->scratch[slot];
 }
 
-// Device staging that lives for ONE call: host-built work lists a kernel of this call reads.  Allocated and released
-// in stream order (hipMallocAsync / hipFreeAsync), so calls in flight on different streams never share a buffer and
-// nothing waits for the device.  Usage: alloc(), copy + launch on the same stream, then the destructor frees.
+// The one way a blocking host-span entry point (*_host) gets the lock, the device and its device memory: what
+// include/mi355_nrphy.h promises about all of them.  From construction to return it holds ctx->host_mutex, with ctx->device
+// made current.  Device memory comes from the context's grow-only staging: mem() for a whole slot, carve() for several
+// 256-byte aligned pieces of one slot with every size given at once, because growth frees the old buffer.  For the same
+// reason a call asks for a slot once, and a host form never calls another host form (none does).  Both return null when the
+// device could not be made current, so NRPHY_ERR_DEVICE on null covers that too.  sync() is the success path's one
+// hipStreamSynchronize.  A return before it -- HIP_TRY's included -- drains ctx->stream in the destructor: no copy into a
+// caller's span or into a local of the entry point outlives the call (a container that an asynchronous copy targets is
+// declared before the HostCall, so that it is destroyed after the drain).
+class HostCall
+{
+public:
+  explicit HostCall(nrphy_ctx* c) : ctx(c), lock(c->host_mutex), device_set(hipSetDevice(c->device) == hipSuccess) {}
+  HostCall(const HostCall&)            = delete;
+  HostCall& operator=(const HostCall&) = delete;
+  ~HostCall()
+  {
+    if (!drained) {
+      (void)hipStreamSynchronize(ctx->stream);
+    }
+  }
+  template <typename T = void>
+  T* mem(ScratchSlot slot, size_t bytes)
+  {
+    return device_set ? (T*)ctx_scratch(ctx, slot, bytes) : nullptr;
+  }
+  template <size_t N>
+  bool carve(ScratchSlot slot, const size_t (&bytes)[N], uint8_t* (&piece)[N])
+  {
+    size_t offset[N + 1] = {};
+    for (size_t i = 0; i != N; ++i) {
+      offset[i + 1] = offset[i] + ((bytes[i] + 255) & ~(size_t)255);
+    }
+    uint8_t* base = mem<uint8_t>(slot, offset[N]);
+    for (size_t i = 0; i != N; ++i) {
+      piece[i] = base ? base + offset[i] : nullptr;
+    }
+    return base != nullptr;
+  }
+  hipError_t sync()
+  {
+    drained = true;
+    return hipStreamSynchronize(ctx->stream);
+  }
+
+private:
+  nrphy_ctx*                            ctx;
+  std::lock_guard<std::recursive_mutex> lock;
+  bool                                  device_set;
+  bool                                  drained = false;
+};
+
+// Device staging that lives for ONE device-pointer call on the caller's stream: host-built work lists a kernel of this call
+// reads.  Allocated and released in stream order (hipMallocAsync / hipFreeAsync), so calls in flight on different streams
+// never share a buffer and nothing waits for the device.  Usage: alloc(), copy + launch on the same stream, then the
+// destructor frees.  The host-span forms do not use it: they block anyway and reuse the context's staging (HostCall).
 class StreamStaging
 {
 public:

@@ -3,13 +3,11 @@
 // symbol (dmrs_pusch_estimator_impl.cpp:136-149), the symbol start epochs (initialize_symbol_start_epochs,
 // port_channel_estimator_average_impl.cpp:454-466) and the raised-cosine taps (filter_type, :62-111), in float32 and in the
 // reference's order of operations.
-#include "nrphy_host_internal.h"
+#include "pusch_alloc_host.h"
 
 #include <cmath>
 
 namespace {
-
-constexpr uint32_t MAX_PRB_BITS = NRPHY_PRB_WORDS * 64;
 
 // port_channel_estimator_average_impl.cpp:41-47
 constexpr float RC_FILTER[31] = {-0.0641253f, -0.0660711f, -0.0611526f, -0.0485918f, -0.0281126f, 0.0000000f, 0.0348830f, 0.0751249f,
@@ -17,47 +15,15 @@ constexpr float RC_FILTER[31] = {-0.0641253f, -0.0660711f, -0.0611526f, -0.04859
                                  0.3235207f,  0.3073415f,  0.2814857f,  0.2475302f,  0.2075139f,  0.1637874f, 0.1188406f, 0.0751249f,
                                  0.0348830f,  0.0000000f,  -0.0281126f, -0.0485918f, -0.0611526f, -0.0660711f, -0.0641253f};
 
-uint32_t nof_prb(const nrphy_pusch_chest_cfg_t& c)
-{
-  uint32_t n = 0;
-  for (uint32_t w = 0; w != NRPHY_PRB_WORDS; ++w) {
-    n += (uint32_t)__builtin_popcountll(c.prb_mask[w]);
-  }
-  return n;
-}
-
 int validate(const nrphy_pusch_chest_cfg_t* c, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
 {
   if (c == nullptr || c->dmrs_type != 1 || c->nof_tx_layers < 1 || c->nof_tx_layers > NRPHY_PUSCH_CHEST_MAX_LAYERS ||
-      c->nof_rx_ports < 1 || c->nof_rx_ports > NRPHY_MAX_PORTS || c->numerology > 4 ||
-      c->slot_index >= (10U << c->numerology) || c->scrambling_id > 65535U || c->n_scid > 1 || !std::isfinite(c->scaling) ||
-      !(c->scaling > 0.f)) {
+      c->numerology > 4 || c->slot_index >= (10U << c->numerology) || c->scrambling_id > 65535U || c->n_scid > 1 ||
+      !std::isfinite(c->scaling) || !(c->scaling > 0.f)) {
     return NRPHY_ERR_ARGUMENT;
   }
-  if (grid_nof_subc == 0 || grid_nof_subc % NRPHY_NRE != 0 || grid_nof_subc > NRPHY_MAX_RB * NRPHY_NRE || grid_nof_ports == 0 ||
-      grid_nof_ports > NRPHY_MAX_PORTS) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  for (uint32_t i = 0; i != c->nof_rx_ports; ++i) {
-    if (c->rx_ports[i] >= grid_nof_ports) {
-      return NRPHY_ERR_ARGUMENT;
-    }
-    for (uint32_t j = 0; j != i; ++j) {
-      if (c->rx_ports[j] == c->rx_ports[i]) {
-        return NRPHY_ERR_ARGUMENT;
-      }
-    }
-  }
-  const uint32_t grid_prb = grid_nof_subc / NRPHY_NRE;
-  for (uint32_t b = grid_prb; b != MAX_PRB_BITS; ++b) {
-    if ((c->prb_mask[b / 64] >> (b % 64)) & 1U) {
-      return NRPHY_ERR_ARGUMENT;
-    }
-  }
-  if (nof_prb(*c) == 0) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  if (c->nof_symbols == 0 || c->start_symbol_index >= NRPHY_NSYMB || c->nof_symbols > NRPHY_NSYMB - c->start_symbol_index) {
+  const PuschAllocation a = pusch_allocation(*c);
+  if (!allocation_fits_grid(a, grid_nof_ports, grid_nof_subc) || nof_prb(a) == 0 || c->nof_symbols == 0) {
     return NRPHY_ERR_ARGUMENT;
   }
   // The reference sizes its pilot buffer from the whole mask and reads only the symbols of [start, start + nof).
@@ -151,12 +117,7 @@ extern "C" int nrphy_pusch_chest_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
     d.nof_rx_ports = c.nof_rx_ports;
     d.nof_layers   = c.nof_tx_layers;
     d.prb_first    = (uint32_t)prbs.size();
-    for (uint32_t b = 0; b != grid_nof_subc / NRPHY_NRE; ++b) {
-      if ((c.prb_mask[b / 64] >> (b % 64)) & 1U) {
-        prbs.push_back((uint16_t)b);
-      }
-    }
-    d.nprb         = (uint32_t)prbs.size() - d.prb_first;
+    d.nprb         = append_prbs(pusch_allocation(c), grid_nof_subc, prbs);
     d.nwords       = (NRPHY_NRE * ((uint32_t)prbs.back() + 1) + 31) / 32;
     d.first_symbol = c.start_symbol_index;
     d.nof_symbols  = c.nof_symbols;
@@ -200,19 +161,6 @@ extern "C" int nrphy_pusch_chest_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
     const double a = 2.0 * M_PI * i / 2048.0;
     tw[i]          = make_float2((float)std::cos(a), (float)std::sin(a));
   }
-  auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_desc = 0;
-  const size_t o_jobs = align(o_desc + desc.size() * sizeof(PuschChestDesc));
-  const size_t o_prbs = align(o_jobs + jobs.size() * sizeof(uint32_t));
-  const size_t o_tw   = align(o_prbs + prbs.size() * sizeof(uint16_t));
-  const size_t o_rows = align(o_tw + tw.size() * sizeof(float2));
-  const size_t o_rot  = align(o_rows + row_words * sizeof(uint32_t));
-  const size_t bytes  = align(o_rot + jobs.size() * NRPHY_NSYMB * sizeof(float2));
-  std::vector<uint8_t> host(o_rows, 0);
-  std::memcpy(host.data() + o_desc, desc.data(), desc.size() * sizeof(PuschChestDesc));
-  std::memcpy(host.data() + o_jobs, jobs.data(), jobs.size() * sizeof(uint32_t));
-  std::memcpy(host.data() + o_prbs, prbs.data(), prbs.size() * sizeof(uint16_t));
-  std::memcpy(host.data() + o_tw, tw.data(), tw.size() * sizeof(float2));
   auto* plan           = new nrphy_pusch_chest_plan;
   plan->ctx            = ctx;
   plan->n              = n;
@@ -220,19 +168,20 @@ extern "C" int nrphy_pusch_chest_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
   plan->nof_grids      = nof_grids;
   plan->grid_nof_ports = grid_nof_ports;
   plan->grid_nof_subc  = grid_nof_subc;
-  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&plan->d_arena, bytes) != hipSuccess ||
-      hipMemcpy(plan->d_arena, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+  // One allocation, one upload of the host-built tables; behind them what the kernels write: the rows, then the rotations.
+  DeviceArena arena;
+  arena.add(&plan->d_desc, desc.data(), desc.size() * sizeof(PuschChestDesc));
+  arena.add(&plan->d_jobs, jobs.data(), jobs.size() * sizeof(uint32_t));
+  arena.add(&plan->d_prbs, prbs.data(), prbs.size() * sizeof(uint16_t));
+  arena.add(&plan->d_tw, tw.data(), tw.size() * sizeof(float2));
+  const size_t rows_bytes = (row_words * sizeof(uint32_t) + 255) & ~(size_t)255;
+  if (hipSetDevice(ctx->device) != hipSuccess ||
+      arena.commit(&plan->d_arena, rows_bytes + jobs.size() * NRPHY_NSYMB * sizeof(float2), (void**)&plan->d_rows) != hipSuccess) {
     nrphy_pusch_chest_plan_destroy(plan);
     return NRPHY_ERR_DEVICE;
   }
-  uint8_t* a   = (uint8_t*)plan->d_arena;
-  plan->d_desc = (PuschChestDesc*)(a + o_desc);
-  plan->d_jobs = (uint32_t*)(a + o_jobs);
-  plan->d_prbs = (uint16_t*)(a + o_prbs);
-  plan->d_tw   = (float2*)(a + o_tw);
-  plan->d_rows = (uint32_t*)(a + o_rows);
-  plan->d_rot  = (float2*)(a + o_rot);
-  *out         = plan;
+  plan->d_rot = (float2*)((uint8_t*)plan->d_rows + rows_bytes);
+  *out        = plan;
   return NRPHY_OK;
 }
 
@@ -275,49 +224,36 @@ extern "C" int nrphy_pusch_chest_host(nrphy_ctx_t* ctx, const nrphy_pusch_chest_
   const size_t grid_bytes = (size_t)grid_nof_ports * NRPHY_NSYMB * grid_nof_subc * 4;
   const size_t ce_bytes   = (size_t)cfg->nof_tx_layers * cfg->nof_rx_ports * NRPHY_NSYMB * grid_nof_subc * 4;
   const size_t meas_bytes = NRPHY_MAX_PORTS * NRPHY_PUSCH_CHEST_MAX_LAYERS * sizeof(nrphy_pusch_chest_meas_t);
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-  HIP_TRY(hipSetDevice(ctx->device));
-  void *d_grid = nullptr, *d_ce = nullptr, *d_nv = nullptr, *d_meas = nullptr;
-  auto  release = [&]() {
-    for (void* q : {d_grid, d_ce, d_nv, d_meas}) {
-      if (q != nullptr) {
-        (void)hipFree(q);
-      }
-    }
-  };
-  if (hipMalloc(&d_grid, grid_bytes) != hipSuccess || hipMalloc(&d_ce, ce_bytes) != hipSuccess ||
-      hipMalloc(&d_nv, NRPHY_MAX_PORTS * sizeof(float)) != hipSuccess || hipMalloc(&d_meas, meas_bytes) != hipSuccess) {
-    release();
+  HostCall call(ctx);
+  uint8_t* d[4]; // grid, estimates, noise variances, measurements
+  if (!call.carve(SCRATCH_RX, {grid_bytes, ce_bytes, NRPHY_MAX_PORTS * sizeof(float), meas_bytes}, d)) {
     return NRPHY_ERR_DEVICE;
   }
+  HIP_TRY(hipMemcpy(d[0], grid, grid_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d[1], ch_est, ce_bytes, hipMemcpyHostToDevice)); // the kernels write the allocation's part only
   const uint32_t            zero = 0;
   const uint64_t            ce0  = 0;
   nrphy_pusch_chest_plan_t* plan = nullptr;
-  int                       rc   = NRPHY_ERR_DEVICE;
-  if (hipMemcpy(d_grid, grid, grid_bytes, hipMemcpyHostToDevice) == hipSuccess &&
-      hipMemcpy(d_ce, ch_est, ce_bytes, hipMemcpyHostToDevice) == hipSuccess) {
-    rc = nrphy_pusch_chest_plan_create(ctx, 1, cfg, &zero, 1, grid_nof_ports, grid_nof_subc, &ce0, &plan);
+  int rc = nrphy_pusch_chest_plan_create(ctx, 1, cfg, &zero, 1, grid_nof_ports, grid_nof_subc, &ce0, &plan);
+  if (rc != NRPHY_OK) {
+    return rc;
   }
-  if (rc == NRPHY_OK) {
-    rc = nrphy_pusch_chest_run(plan, d_grid, d_ce, (float*)d_nv, (nrphy_pusch_chest_meas_t*)d_meas, ctx->stream);
-  }
-  if (rc == NRPHY_OK) {
-    std::vector<nrphy_pusch_chest_meas_t> m(NRPHY_MAX_PORTS * NRPHY_PUSCH_CHEST_MAX_LAYERS);
-    float                                 nv[NRPHY_MAX_PORTS];
-    if (hipStreamSynchronize(ctx->stream) != hipSuccess || hipMemcpy(ch_est, d_ce, ce_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(nv, d_nv, sizeof(nv), hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(m.data(), d_meas, meas_bytes, hipMemcpyDeviceToHost) != hipSuccess) {
-      rc = NRPHY_ERR_DEVICE;
-    } else {
-      for (uint32_t i = 0; i != cfg->nof_rx_ports; ++i) {
-        noise_vars[i] = nv[i];
-      }
-      if (meas != nullptr) {
-        std::memcpy(meas, m.data(), cfg->nof_rx_ports * NRPHY_PUSCH_CHEST_MAX_LAYERS * sizeof(nrphy_pusch_chest_meas_t));
-      }
-    }
+  rc = nrphy_pusch_chest_run(plan, d[0], d[1], (float*)d[2], (nrphy_pusch_chest_meas_t*)d[3], ctx->stream);
+  std::vector<nrphy_pusch_chest_meas_t> m(NRPHY_MAX_PORTS * NRPHY_PUSCH_CHEST_MAX_LAYERS);
+  float                                 nv[NRPHY_MAX_PORTS];
+  if (rc == NRPHY_OK && (call.sync() != hipSuccess || hipMemcpy(ch_est, d[1], ce_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(nv, d[2], sizeof(nv), hipMemcpyDeviceToHost) != hipSuccess ||
+                         hipMemcpy(m.data(), d[3], meas_bytes, hipMemcpyDeviceToHost) != hipSuccess)) {
+    rc = NRPHY_ERR_DEVICE;
   }
   nrphy_pusch_chest_plan_destroy(plan);
-  release();
+  if (rc == NRPHY_OK) {
+    for (uint32_t i = 0; i != cfg->nof_rx_ports; ++i) {
+      noise_vars[i] = nv[i];
+    }
+    if (meas != nullptr) {
+      std::memcpy(meas, m.data(), cfg->nof_rx_ports * NRPHY_PUSCH_CHEST_MAX_LAYERS * sizeof(nrphy_pusch_chest_meas_t));
+    }
+  }
   return rc;
 }

@@ -46,20 +46,9 @@ struct ChestShared {
   float    vp_abs[2][V_MARGIN], vp_arg[2][V_MARGIN];
 };
 
-__device__ __forceinline__ uint32_t bf16_rne(float x)
-{
-  const uint32_t u = __float_as_uint(x);
-  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-
 __device__ __forceinline__ uint32_t to_cbf16(float re, float im)
 {
-  return bf16_rne(re) | (bf16_rne(im) << 16);
-}
-
-__device__ __forceinline__ float2 from_cbf16(uint32_t w)
-{
-  return make_float2(__uint_as_float(w << 16), __uint_as_float(w & 0xFFFF0000u));
+  return to_bf16_bits(re) | (to_bf16_bits(im) << 16);
 }
 
 // std::polar(1.0F, x) with cos and sin evaluated in double and rounded once.
@@ -74,20 +63,11 @@ __device__ __forceinline__ float2 cmul(float2 x, float2 h)
   return make_float2(__fsub_rn(__fmul_rn(x.x, h.x), __fmul_rn(x.y, h.y)), __fadd_rn(__fmul_rn(x.x, h.y), __fmul_rn(x.y, h.x)));
 }
 
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-  for (int o = 32; o != 0; o >>= 1) {
-    v += __shfl_xor(v, o);
-  }
-  return v;
-}
-
 // Workgroup sum of two doubles in a fixed order; every thread gets the result.
 __device__ __forceinline__ double2 block_sum2(double x, double y, ChestShared& s, uint32_t tid)
 {
-  x = wave_sum_d(x);
-  y = wave_sum_d(y);
+  x = wave_sum(x);
+  y = wave_sum(y);
   __syncthreads();
   if ((tid & 63u) == 0) {
     s.red[tid >> 6][0] = x;
@@ -182,7 +162,7 @@ __global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_kernel(PuschChestLa
     for (uint32_t q = tid; q < N; q += CHEST_THREADS) {
       uint32_t     k;
       const float2 pl = pilot(s, dd, q, layer, k);
-      const float2 y  = from_cbf16(row[k]);
+      const float2 y  = cbf16_to_float2(row[k]);
       epre += (double)__fadd_rn(__fmul_rn(y.x, y.x), __fmul_rn(y.y, y.y));
       const float2 ls = make_float2(__fadd_rn(__fmul_rn(y.x, pl.x), __fmul_rn(y.y, pl.y)),
                                     __fsub_rn(__fmul_rn(y.y, pl.x), __fmul_rn(y.x, pl.y)));
@@ -255,7 +235,7 @@ __global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_kernel(PuschChestLa
     for (uint32_t q = tid; q < N; q += CHEST_THREADS) {
       uint32_t     k;
       const float2 pl = pilot(s, dd, q, layer, k);
-      const float2 y  = from_cbf16(row[k]);
+      const float2 y  = cbf16_to_float2(row[k]);
       const float2 f  = s.b[q];
       float2       e  = cmul(make_float2(__fmul_rn(f.x, -d.beta), __fmul_rn(f.y, -d.beta)), pl);
       if (nd >= 2u) {
@@ -386,7 +366,7 @@ __global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_expand_kernel(Pusch
 #pragma unroll
     for (uint32_t i = 0; i != 4; ++i) {
       if (rot) {
-        const float2 e = cmul(from_cbf16(v[i]), r);
+        const float2 e = cmul(cbf16_to_float2(v[i]), r);
         v[i]           = to_cbf16(e.x, e.y);
       }
       if (k0 + i == d.dc) {

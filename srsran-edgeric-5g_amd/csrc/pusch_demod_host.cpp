@@ -2,13 +2,11 @@
 // work list, and the host-span forms.  The plan does on the host what pusch_demodulator_impl::demodulate does before its loops
 // (pusch_demodulator_impl.cpp:135-160: the RE masks of data and DM-RS symbols, c_init) and cuts every OFDM symbol's data RE into
 // work items of up to PUSCH_DEMOD_THREADS, each with its codeword bit offset and its place in the symbol's demapper span.
-#include "nrphy_host_internal.h"
+#include "pusch_alloc_host.h"
 
 #include <cmath>
 
 namespace {
-
-constexpr uint32_t MAX_PRB_BITS = NRPHY_PRB_WORDS * 64;
 
 // Data subcarriers of a PRB on a DM-RS symbol: those dmrs_type::get_dmrs_prb_mask(cdm) leaves (R/include/srsran/phy/upper/
 // dmrs_mapping.h:76-91).  Type 1: CDM group 0 = even subcarriers, 1 = odd.  Type 2: group g = {2g, 2g+1, 2g+6, 2g+7}.
@@ -34,15 +32,6 @@ uint32_t popcount12(uint32_t m)
   return (uint32_t)__builtin_popcount(m & 0xFFFU);
 }
 
-uint32_t nof_prb(const nrphy_pusch_demod_cfg_t& c)
-{
-  uint32_t n = 0;
-  for (uint32_t w = 0; w != NRPHY_PRB_WORDS; ++w) {
-    n += (uint32_t)__builtin_popcountll(c.prb_mask[w]);
-  }
-  return n;
-}
-
 // Data RE of OFDM symbol l (0 outside the allocation's symbols).
 uint32_t symbol_re(const nrphy_pusch_demod_cfg_t& c, uint32_t l, uint32_t nprb, uint32_t dmrs_mask)
 {
@@ -56,37 +45,16 @@ int validate(const nrphy_pusch_demod_cfg_t* c, uint32_t grid_nof_ports, uint32_t
 {
   uint32_t dmrs_mask = 0;
   if (c == nullptr || c->transform_precoding != 0 || !(c->qm == 2 || c->qm == 4 || c->qm == 6 || c->qm == 8) ||
-      c->nof_tx_layers < 1 || c->nof_tx_layers > 2 || c->nof_rx_ports < 1 || c->nof_rx_ports > NRPHY_MAX_PORTS ||
-      c->equalizer > NRPHY_EQ_MMSE || (c->nof_tx_layers == 2 && (c->equalizer != NRPHY_EQ_ZF ||
-                                                                  (c->nof_rx_ports != 2 && c->nof_rx_ports != 4))) ||
+      c->nof_tx_layers < 1 || c->nof_tx_layers > 2 || c->equalizer > NRPHY_EQ_MMSE ||
+      (c->nof_tx_layers == 2 && (c->equalizer != NRPHY_EQ_ZF || (c->nof_rx_ports != 2 && c->nof_rx_ports != 4))) ||
       !dmrs_data_mask(c->dmrs_type, c->nof_cdm_groups_without_data, dmrs_mask)) {
     return NRPHY_ERR_ARGUMENT;
   }
-  if (grid_nof_subc == 0 || grid_nof_subc % NRPHY_NRE != 0 || grid_nof_subc > NRPHY_MAX_RB * NRPHY_NRE || grid_nof_ports == 0 ||
-      grid_nof_ports > NRPHY_MAX_PORTS) {
+  const PuschAllocation a = pusch_allocation(*c);
+  if (!allocation_fits_grid(a, grid_nof_ports, grid_nof_subc) || (c->dmrs_symbol_mask >> NRPHY_NSYMB) != 0) {
     return NRPHY_ERR_ARGUMENT;
   }
-  for (uint32_t i = 0; i != c->nof_rx_ports; ++i) {
-    if (c->rx_ports[i] >= grid_nof_ports) {
-      return NRPHY_ERR_ARGUMENT;
-    }
-    for (uint32_t j = 0; j != i; ++j) {
-      if (c->rx_ports[j] == c->rx_ports[i]) {
-        return NRPHY_ERR_ARGUMENT;
-      }
-    }
-  }
-  const uint32_t grid_prb = grid_nof_subc / NRPHY_NRE;
-  for (uint32_t b = grid_prb; b != MAX_PRB_BITS; ++b) {
-    if ((c->prb_mask[b / 64] >> (b % 64)) & 1U) {
-      return NRPHY_ERR_ARGUMENT;
-    }
-  }
-  if (c->start_symbol_index >= NRPHY_NSYMB || c->nof_symbols > NRPHY_NSYMB - c->start_symbol_index ||
-      (c->dmrs_symbol_mask >> NRPHY_NSYMB) != 0) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  const uint32_t nprb = nof_prb(*c);
+  const uint32_t nprb = nof_prb(a);
   uint32_t       nre  = 0;
   for (uint32_t l = 0; l != NRPHY_NSYMB; ++l) {
     nre += symbol_re(*c, l, nprb, dmrs_mask);
@@ -121,7 +89,7 @@ extern "C" uint64_t nrphy_pusch_demod_codeword_bits(const nrphy_pusch_demod_cfg_
       !dmrs_data_mask(cfg->dmrs_type, cfg->nof_cdm_groups_without_data, dmrs_mask)) {
     return 0;
   }
-  const uint32_t nprb = nof_prb(*cfg);
+  const uint32_t nprb = nof_prb(pusch_allocation(*cfg));
   uint64_t       nre  = 0;
   for (uint32_t l = 0; l != NRPHY_NSYMB; ++l) {
     nre += symbol_re(*cfg, l, nprb, dmrs_mask);
@@ -183,12 +151,7 @@ extern "C" int nrphy_pusch_demod_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
       d.rx_ports[k] = c.rx_ports[k];
     }
     d.ce_offset = ce_offset[i];
-    for (uint32_t b = 0; b != grid_nof_subc / NRPHY_NRE; ++b) {
-      if ((c.prb_mask[b / 64] >> (b % 64)) & 1U) {
-        prbs.push_back((uint16_t)b);
-      }
-    }
-    const uint32_t nprb = (uint32_t)prbs.size() - d.prb_first;
+    const uint32_t nprb = append_prbs(pusch_allocation(c), grid_nof_subc, prbs);
     const uint32_t nb   = c.nof_tx_layers * c.qm;
     uint32_t       bit  = 0;
     d.item_first        = (uint32_t)items.size();
@@ -220,20 +183,6 @@ extern "C" int nrphy_pusch_demod_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
   for (uint32_t m = 0; m != 4; ++m) {
     demod_params(2 * (m + 1), 0, demod[m]);
   }
-  auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o_desc    = 0;
-  const size_t o_items   = align(o_desc + desc.size() * sizeof(PuschDemodDesc));
-  const size_t o_prbs    = align(o_items + items.size() * sizeof(PuschDemodItem));
-  const size_t o_demod   = align(o_prbs + std::max<size_t>(prbs.size(), 1) * sizeof(uint16_t));
-  const size_t o_partial = align(o_demod + sizeof(demod));
-  const size_t bytes     = align(o_partial + items.size() * 2 * sizeof(double));
-  std::vector<uint8_t> host(o_partial, 0);
-  std::memcpy(host.data() + o_desc, desc.data(), desc.size() * sizeof(PuschDemodDesc));
-  std::memcpy(host.data() + o_items, items.data(), items.size() * sizeof(PuschDemodItem));
-  if (!prbs.empty()) {
-    std::memcpy(host.data() + o_prbs, prbs.data(), prbs.size() * sizeof(uint16_t));
-  }
-  std::memcpy(host.data() + o_demod, demod, sizeof(demod));
   auto* plan           = new nrphy_pusch_demod_plan;
   plan->ctx            = ctx;
   plan->n              = n;
@@ -242,18 +191,18 @@ extern "C" int nrphy_pusch_demod_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
   plan->grid_nof_ports = grid_nof_ports;
   plan->grid_nof_subc  = grid_nof_subc;
   plan->cw_bits        = std::move(cw_bits);
-  if (hipSetDevice(ctx->device) != hipSuccess || hipMalloc(&plan->d_arena, bytes) != hipSuccess ||
-      hipMemcpy(plan->d_arena, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+  // One allocation, one upload of the host-built tables; behind them what the kernel writes: two partial sums per item.
+  DeviceArena arena;
+  arena.add(&plan->d_desc, desc.data(), desc.size() * sizeof(PuschDemodDesc));
+  arena.add(&plan->d_items, items.data(), items.size() * sizeof(PuschDemodItem));
+  arena.add(&plan->d_prbs, prbs.data(), prbs.size() * sizeof(uint16_t));
+  arena.add(&plan->d_demod, demod, sizeof(demod));
+  if (hipSetDevice(ctx->device) != hipSuccess ||
+      arena.commit(&plan->d_arena, items.size() * 2 * sizeof(double), (void**)&plan->d_partial) != hipSuccess) {
     nrphy_pusch_demod_plan_destroy(plan);
     return NRPHY_ERR_DEVICE;
   }
-  uint8_t* a       = (uint8_t*)plan->d_arena;
-  plan->d_desc     = (PuschDemodDesc*)(a + o_desc);
-  plan->d_items    = (PuschDemodItem*)(a + o_items);
-  plan->d_prbs     = (uint16_t*)(a + o_prbs);
-  plan->d_demod    = (DemodLaunch*)(a + o_demod);
-  plan->d_partial  = (double*)(a + o_partial);
-  *out             = plan;
+  *out = plan;
   return NRPHY_OK;
 }
 
@@ -301,26 +250,6 @@ extern "C" int nrphy_pusch_demod_run(nrphy_pusch_demod_plan_t* plan, const void*
 
 namespace {
 
-// Device buffers of a blocking host-span call, freed on every return path.
-struct DeviceBuffers {
-  std::vector<void*> ptrs;
-  void*              get(size_t bytes)
-  {
-    void* p = nullptr;
-    if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) {
-      return nullptr;
-    }
-    ptrs.push_back(p);
-    return p;
-  }
-  ~DeviceBuffers()
-  {
-    for (void* p : ptrs) {
-      (void)hipFree(p);
-    }
-  }
-};
-
 bool equalize_args_ok(uint32_t algorithm, uint32_t nof_layers, uint32_t nof_rx_ports, float tx_scaling)
 {
   return algorithm <= NRPHY_EQ_MMSE && nof_rx_ports >= 1 && nof_rx_ports <= NRPHY_MAX_PORTS && tx_scaling > 0.f &&
@@ -344,17 +273,15 @@ extern "C" int nrphy_pusch_demodulate_host(nrphy_ctx_t* ctx, const nrphy_pusch_d
   for (uint32_t i = 0; i != cfg->nof_rx_ports; ++i) {
     nv[i] = noise_vars[i];
   }
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-  HIP_TRY(hipSetDevice(ctx->device));
-  DeviceBuffers buf;
-  void*   d_grid = buf.get(grid_bytes);
-  void*   d_ce   = buf.get(ce_bytes);
-  float*  d_nv   = (float*)buf.get(sizeof(nv));
-  int8_t* d_llr  = (int8_t*)buf.get(G);
-  float*  d_sinr = (float*)buf.get(sizeof(float));
-  if (d_grid == nullptr || d_ce == nullptr || d_nv == nullptr || d_llr == nullptr || d_sinr == nullptr) {
+  HostCall call(ctx);
+  uint8_t* d[5]; // grid, estimates, noise variances, soft bits, SINR
+  if (!call.carve(SCRATCH_RX, {grid_bytes, ce_bytes, sizeof(nv), (size_t)G, sizeof(float)}, d)) {
     return NRPHY_ERR_DEVICE;
   }
+  void *  d_grid = d[0], *d_ce = d[1];
+  float*  d_nv   = (float*)d[2];
+  int8_t* d_llr  = (int8_t*)d[3];
+  float*  d_sinr = (float*)d[4];
   HIP_TRY(hipMemcpy(d_grid, grid, grid_bytes, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_ce, ch_est, ce_bytes, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_nv, nv, sizeof(nv), hipMemcpyHostToDevice));
@@ -366,7 +293,7 @@ extern "C" int nrphy_pusch_demodulate_host(nrphy_ctx_t* ctx, const nrphy_pusch_d
     return rc;
   }
   rc = nrphy_pusch_demod_run(plan, d_grid, d_ce, d_nv, d_llr, G, d_sinr, ctx->stream);
-  if (rc == NRPHY_OK && (hipStreamSynchronize(ctx->stream) != hipSuccess ||
+  if (rc == NRPHY_OK && (call.sync() != hipSuccess ||
                          hipMemcpy(llr, d_llr, G, hipMemcpyDeviceToHost) != hipSuccess ||
                          (sinr_db != nullptr && hipMemcpy(sinr_db, d_sinr, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))) {
     rc = NRPHY_ERR_DEVICE;
@@ -422,17 +349,13 @@ extern "C" int nrphy_channel_equalize_host(nrphy_ctx_t* ctx, uint32_t algorithm,
   }
   const size_t rx_bytes = (size_t)nof_rx_ports * nof_re * 4, ch_bytes = rx_bytes * nof_layers;
   const size_t out      = (size_t)nof_re * nof_layers;
-  std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
-  HIP_TRY(hipSetDevice(ctx->device));
-  DeviceBuffers buf;
-  void*  d_rx = buf.get(rx_bytes);
-  void*  d_ch = buf.get(ch_bytes);
-  float* d_nv = (float*)buf.get(nof_rx_ports * sizeof(float));
-  float* d_eq = (float*)buf.get(out * 8);
-  float* d_ev = (float*)buf.get(out * 4);
-  if (d_rx == nullptr || d_ch == nullptr || d_nv == nullptr || d_eq == nullptr || d_ev == nullptr) {
+  HostCall call(ctx);
+  uint8_t* d[5]; // received RE, estimates, noise variances, equalised RE, their noise variances
+  if (!call.carve(SCRATCH_RX, {rx_bytes, ch_bytes, nof_rx_ports * sizeof(float), out * 8, out * 4}, d)) {
     return NRPHY_ERR_DEVICE;
   }
+  void * d_rx = d[0], *d_ch = d[1];
+  float *d_nv = (float*)d[2], *d_eq = (float*)d[3], *d_ev = (float*)d[4];
   HIP_TRY(hipMemcpy(d_rx, rx, rx_bytes, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_ch, ch, ch_bytes, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_nv, noise_vars, nof_rx_ports * sizeof(float), hipMemcpyHostToDevice));
@@ -441,7 +364,7 @@ extern "C" int nrphy_channel_equalize_host(nrphy_ctx_t* ctx, uint32_t algorithm,
   if (rc != NRPHY_OK) {
     return rc;
   }
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(call.sync());
   HIP_TRY(hipMemcpy(eq, d_eq, out * 8, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(eq_nvars, d_ev, out * 4, hipMemcpyDeviceToHost));
   return NRPHY_OK;

@@ -32,12 +32,6 @@ __device__ __forceinline__ bool is_normal(float x)
   return a >= FLT_NORMAL_MIN && a <= FLT_LARGEST;
 }
 
-// cbf16 word (real part in the low half) -> complex float, exactly.
-__device__ __forceinline__ float2 cbf16_to_float2(uint32_t w)
-{
-  return make_float2(__uint_as_float(w << 16), __uint_as_float(w & 0xFFFF0000u));
-}
-
 // One RE of channel_equalizer::equalize, the reference's scalar arithmetic operation by operation (std::complex products written
 // out: (a + jb) conj(c + jd) = (ac + bd) + j(bc - ad)), contraction off, exact division.  y[i]: received word of receive port i;
 // h[l][i]: estimate of layer l at port i; nv[i]: port noise variances; nv_max: their maximum (std::max_element).  Out: symbol and
@@ -178,15 +172,6 @@ struct PuschDemodShared {
   double   red[2][PUSCH_DEMOD_THREADS / WAVE];
   __attribute__((aligned(16))) uint8_t stage[STAGE_BYTES];
 };
-
-__device__ __forceinline__ double wave_sum(double x)
-{
-#pragma unroll
-  for (uint32_t o = WAVE / 2; o != 0; o >>= 1) {
-    x += __shfl_xor(x, o);
-  }
-  return x;
-}
 
 template <uint32_t MOD>
 __device__ __forceinline__ void pusch_demod_item(const PuschDemodLaunch& p, const PuschDemodItem& it, const PuschDemodDesc& d,

@@ -44,6 +44,16 @@ def from_cbf16(w):
     return (re + 1j * im).astype(np.complex64)
 
 
+# ---- what the GPU tests of the receive side hand to the library -----------------------------------------------------------
+def dev(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def as_i32(a):
+    return np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)
+
+
 # ---- sequences and constants -----------------------------------------------------------------------------------------------
 def gold(c_init, n):
     """c(0 .. n) of TS 38.211 Section 5.2.1."""

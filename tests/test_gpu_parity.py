@@ -12,6 +12,7 @@ import pytest
 
 import backends
 import cases
+from pusch_chest_model import dev
 
 abi = backends.abi
 lib = backends.pkg.lib
@@ -22,11 +23,6 @@ LIFTING_SIZES = cases.LIFTING_SIZES
 
 def sha(a):
     return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
-
-
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

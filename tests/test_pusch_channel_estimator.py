@@ -148,13 +148,7 @@ def test_restatement_pilots_equal_the_oracle_gold_sequence(oracle):
 # =======================================================================================================================
 # GPU
 # =======================================================================================================================
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def as_i32(a):
-    return np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)
+dev, as_i32 = model.dev, model.as_i32
 
 
 def run_plan(ctx, cfgs, grids, grid_index, nports, nsubc, stream=None):

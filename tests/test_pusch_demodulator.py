@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import backends
+from pusch_chest_model import as_i32, dev, from_cbf16, to_cbf16
 
 abi = backends.abi
 lib = backends.pkg.lib
@@ -55,22 +56,6 @@ def data_subcarriers(cfg, l):
     prbs = [b for b in range(abi.PRB_WORDS * 64) if (cfg.prb_mask[b // 64] >> (b % 64)) & 1]
     ks = dmrs_data_subcarriers(cfg.dmrs_type, cfg.nof_cdm_groups_without_data) if (cfg.dmrs_symbol_mask >> l) & 1 else range(12)
     return np.array([12 * p + k for p in prbs for k in ks], np.int64)
-
-
-# ---- cbf16 ------------------------------------------------------------------------------------------------------------
-def to_bf16(x):
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    return ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint32)
-
-
-def to_cbf16(z):
-    z = np.asarray(z, np.complex64)
-    return (to_bf16(z.real) | (to_bf16(z.imag) << 16)).astype(np.uint32)
-
-
-def from_cbf16(w):
-    w = np.asarray(w, np.uint32)
-    return ((w << 16).view(np.float32) + 1j * (w & 0xFFFF0000).view(np.float32)).astype(np.complex64)
 
 
 # ---- the reference's scalar equaliser loops, restated in float32 -----------------------------------------------------
@@ -253,15 +238,6 @@ def test_extractor_reproduces_the_committed_configurations():
 # =======================================================================================================================
 # GPU
 # =======================================================================================================================
-def dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def as_i32(a):
-    return np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)
-
-
 def composed(ctx, cfg, grid, ce, noise_vars):
     """REs extracted in NumPy -> nrphy_channel_equalize -> nrphy_demodulate_soft (one span per OFDM symbol) ->
     nrphy_llr_descramble; also the float64 SINR of the equalised noise variances."""
