@@ -523,6 +523,87 @@ int nrphy_pusch_chest_run(nrphy_pusch_chest_plan_t* plan, const void* d_grid, vo
 int nrphy_pusch_chest_host(nrphy_ctx_t* ctx, const nrphy_pusch_chest_cfg_t* cfg, const void* grid, uint32_t grid_nof_ports,
                            uint32_t grid_nof_subc, void* ch_est, float* noise_vars, nrphy_pusch_chest_meas_t* meas);
 
+/* ---- receive side: PRACH detector -----------------------------------------------------------------------------------------
+ * Replaces prach_detector_generic_impl::detect (R/lib/phy/upper/channel_processors/prach_detector_generic_impl.cpp:89-359, with
+ * symbol combining on: the factory's setting) and prach_generator_impl::generate (prach_generator_impl.cpp:97-287).  Per
+ * occasion: the RSSI; per monitored root sequence and receive port, the sum of the occasion's symbols times the conjugate of the
+ * root's frequency-domain sequence, a 1024-point (long preambles) or 256-point (short) inverse DFT, |.|^2 / (N L^2); per cyclic
+ * shift window, the reference energy over the window and its margins, numerator and noise estimate accumulated over the ports in
+ * port order; per preamble, the metric num / |den|, its maximum (lowest index on a tie) and the three detection conditions.
+ * Unrestricted sets only; the thresholds are the reference's table (prach_detector_generic_thresholds.h) or the caller's. */
+enum {
+  NRPHY_PRACH_FORMAT_0 = 0, NRPHY_PRACH_FORMAT_1, NRPHY_PRACH_FORMAT_2, NRPHY_PRACH_FORMAT_3, NRPHY_PRACH_FORMAT_A1,
+  NRPHY_PRACH_FORMAT_A2, NRPHY_PRACH_FORMAT_A3, NRPHY_PRACH_FORMAT_B1, NRPHY_PRACH_FORMAT_B4, NRPHY_PRACH_FORMAT_C0,
+  NRPHY_PRACH_FORMAT_C2, NRPHY_PRACH_FORMAT_A1_B1, NRPHY_PRACH_FORMAT_A2_B2, NRPHY_PRACH_FORMAT_A3_B3, NRPHY_PRACH_FORMAT_COUNT
+};
+enum {
+  NRPHY_PRACH_SCS_15 = 0, NRPHY_PRACH_SCS_30, NRPHY_PRACH_SCS_60, NRPHY_PRACH_SCS_120, NRPHY_PRACH_SCS_1_25, NRPHY_PRACH_SCS_5,
+  NRPHY_PRACH_SCS_COUNT
+};
+#define NRPHY_PRACH_MAX_PREAMBLES 64
+typedef struct nrphy_prach_cfg {
+  uint32_t format;                /* NRPHY_PRACH_FORMAT_* */
+  uint32_t ra_scs;                /* NRPHY_PRACH_SCS_*: 1.25 kHz for formats 0..2, 5 kHz for format 3, 15..120 kHz for the short ones */
+  uint32_t restricted_set;        /* must be 0 (unrestricted) */
+  uint32_t root_sequence_index;   /* logical index: 0..837 (long), 0..137 (short) */
+  uint32_t zero_correlation_zone; /* 0..15 */
+  uint32_t start_preamble_index, nof_preamble_indices; /* the monitored preambles: start + nof <= 64, nof >= 1 */
+  uint32_t nof_rx_ports;          /* 1..4 */
+  float    threshold;             /* both 0: the library's table; both non-zero: the caller's threshold and margin */
+  uint32_t win_margin;
+} nrphy_prach_cfg_t;
+typedef struct nrphy_prach_result { /* one per occasion */
+  float    rssi_dB;
+  float    time_resolution_s;     /* one correlation sample, rounded to T_c as phy_time_unit does */
+  float    time_advance_max_s;    /* 0.8 x the largest delay of a window */
+  uint32_t nof_detected;
+  uint64_t detected_mask;         /* bit i: preamble i was detected */
+} nrphy_prach_result_t;
+typedef struct nrphy_prach_preamble { /* one per (occasion, preamble index) */
+  uint32_t detected;
+  uint32_t delay_samples;         /* index of the metric's maximum within the window */
+  float    time_advance_s;        /* delay_samples / sampling rate, rounded to T_c */
+  float    peak;                  /* the metric's maximum */
+  float    detection_metric;      /* peak / threshold */
+} nrphy_prach_preamble_t;
+typedef struct nrphy_prach_plan nrphy_prach_plan_t;
+/* The library's restatement of the reference's table: NRPHY_OK and the row's threshold, window margin and flag (0 red: not
+ * suitable for detection, 1 orange, 2 green) where the table has a row for exactly (nof_rx_ports, ra_scs, format,
+ * zero_correlation_zone); NRPHY_ERR_ARGUMENT where it has none (no neighbouring row is substituted).  Outputs may be NULL. */
+int nrphy_prach_threshold(const nrphy_prach_cfg_t* cfg, float* threshold, uint32_t* win_margin, uint32_t* flag);
+/* NRPHY_OK, or NRPHY_ERR_ARGUMENT for: a restricted set; an unknown format or spacing, or a spacing that is not the format's;
+ * a zero-correlation zone above 15 (reserved N_CS); start + nof above 64 or nof = 0; no rx port or more than 4; a root sequence
+ * index outside 0..837 (long) / 0..137 (short); exactly one of threshold and win_margin set, or a threshold that is not
+ * positive and finite, or a margin that makes a reference window longer than the transform; without a caller's threshold, no
+ * exact row in the table or a red one (what prach_detector_validator_impl::is_valid refuses).  No device work. */
+int nrphy_prach_validate(const nrphy_prach_cfg_t* cfg);
+/* n occasions; occasion i reads complex f32 samples at element sym_offset[i] + port * port_stride + symbol * symbol_stride + k,
+ * k < L_RA, of d_symbols: a prach_buffer tensor (re, symbol, td occasion, fd occasion, port; re fastest) is read in place, one
+ * (td, fd) occasion per item.  Validates every configuration and precomputes, in the reference's order of operations, N_CS, the
+ * number of shifts and sequences, window width, largest delay, threshold and margin and the monitored sequence numbers. */
+int nrphy_prach_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_prach_cfg_t* cfgs, const uint64_t* sym_offset,
+                            uint64_t port_stride, uint64_t symbol_stride, nrphy_prach_plan_t** plan);
+int nrphy_prach_plan_destroy(nrphy_prach_plan_t* plan);
+/* Floats per preamble of d_metric: the widest window of the plan's occasions. */
+uint32_t nrphy_prach_plan_metric_stride(const nrphy_prach_plan_t* plan);
+/* d_result: [n]; d_preambles: [n][64], written for every monitored index whether detected or not and zeroed for the others;
+ * d_metric (may be NULL): [n][64][metric_stride] f32, the whole metric window of every monitored preamble, zeros elsewhere.  A
+ * non-normal RSSI (an all-zero occasion) gives the result header and no detections.  Asynchronous on `stream`; allocates
+ * nothing, touches no host memory, uses no atomics (capturable; two runs give identical bytes).  Runs of one plan must be
+ * ordered: the plan owns one word of scratch per occasion. */
+int nrphy_prach_run(nrphy_prach_plan_t* plan, const void* d_symbols, nrphy_prach_result_t* d_result,
+                    nrphy_prach_preamble_t* d_preambles, float* d_metric, void* stream);
+/* Floats per preamble of the metric of a plan of this one configuration (its window width in correlation samples); 0 where
+ * nrphy_prach_validate refuses it.  No device work. */
+uint32_t nrphy_prach_window_width(const nrphy_prach_cfg_t* cfg);
+/* One occasion from and to host memory (blocking, on the GPU): symbols hold port p, symbol s at element p * port_stride +
+ * s * symbol_stride; preambles[64]; metric (may be NULL): [64][nrphy_prach_window_width(cfg)]. */
+int nrphy_prach_detect_host(nrphy_ctx_t* ctx, const nrphy_prach_cfg_t* cfg, const void* symbols, uint64_t port_stride,
+                            uint64_t symbol_stride, nrphy_prach_result_t* result, nrphy_prach_preamble_t* preambles, float* metric);
+/* The frequency-domain sequence of one preamble from the device's generator (what prach_generator::generate returns): y holds
+ * L_RA complex f32.  The detection fields of cfg (ports, monitored range, threshold) are not looked at. */
+int nrphy_prach_generate_host(nrphy_ctx_t* ctx, const nrphy_prach_cfg_t* cfg, uint32_t preamble_index, float* y);
+
 /* ---- other downlink grid writers ("next" row): NZP-CSI-RS generator -----------
  * Replaces nzp_csi_rs_generator::map (R/include/srsran/phy/upper/signal_processors/nzp_csi_rs_generator.h:
  * 39-90; impl R/lib/phy/upper/signal_processors/nzp_csi_rs_generator_impl.cpp:96-352 with the RE patterns of

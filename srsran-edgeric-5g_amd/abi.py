@@ -173,6 +173,45 @@ def make_pusch_chest(*, prbs, numerology=0, slot_index=0, scrambling_id=0, n_sci
     return c
 
 
+PRACH_FORMATS = ("0", "1", "2", "3", "A1", "A2", "A3", "B1", "B4", "C0", "C2", "A1/B1", "A2/B2", "A3/B3")  # NRPHY_PRACH_FORMAT_*
+PRACH_SPACINGS = ("15", "30", "60", "120", "1.25", "5")  # NRPHY_PRACH_SCS_*, kHz
+PRACH_MAX_PREAMBLES = 64
+
+
+class PrachCfg(C.Structure):
+    """nrphy_prach_cfg_t (prach_detector::configuration + an optional threshold and window margin of the caller's)."""
+    _fields_ = [("format", C.c_uint32), ("ra_scs", C.c_uint32), ("restricted_set", C.c_uint32), ("root_sequence_index", C.c_uint32),
+                ("zero_correlation_zone", C.c_uint32), ("start_preamble_index", C.c_uint32), ("nof_preamble_indices", C.c_uint32),
+                ("nof_rx_ports", C.c_uint32), ("threshold", C.c_float), ("win_margin", C.c_uint32)]
+
+
+class PrachResult(C.Structure):
+    """nrphy_prach_result_t: one per occasion."""
+    _fields_ = [("rssi_dB", C.c_float), ("time_resolution_s", C.c_float), ("time_advance_max_s", C.c_float),
+                ("nof_detected", C.c_uint32), ("detected_mask", C.c_uint64)]
+
+
+class PrachPreamble(C.Structure):
+    """nrphy_prach_preamble_t: one per (occasion, preamble index)."""
+    _fields_ = [("detected", C.c_uint32), ("delay_samples", C.c_uint32), ("time_advance_s", C.c_float), ("peak", C.c_float),
+                ("detection_metric", C.c_float)]
+
+
+def make_prach(*, format, ra_scs=None, root_sequence_index=0, zero_correlation_zone=0, start_preamble_index=0,
+               nof_preamble_indices=64, nof_rx_ports=1, restricted_set=0, threshold=0.0, win_margin=0):
+    """A PrachCfg from plain values: format and ra_scs by name ("B4", "15") or number; ra_scs None: 1.25 / 5 kHz for the long
+    formats, 15 kHz for the short ones."""
+    c = PrachCfg()
+    c.format = PRACH_FORMATS.index(format) if isinstance(format, str) else format
+    if ra_scs is None:
+        ra_scs = "5" if c.format == 3 else "1.25" if c.format < 3 else "15"
+    c.ra_scs = PRACH_SPACINGS.index(ra_scs) if isinstance(ra_scs, str) else ra_scs
+    c.restricted_set, c.root_sequence_index, c.zero_correlation_zone = restricted_set, root_sequence_index, zero_correlation_zone
+    c.start_preamble_index, c.nof_preamble_indices, c.nof_rx_ports = start_preamble_index, nof_preamble_indices, nof_rx_ports
+    c.threshold, c.win_margin = threshold, win_margin
+    return c
+
+
 class GridRe(C.Structure):
     """nrphy_grid_re_t: one resource element written from the host into a device grid."""
     _fields_ = [("port", C.c_uint16), ("symbol", C.c_uint16), ("subc", C.c_uint32), ("value", C.c_uint32)]
@@ -550,6 +589,15 @@ def declare(lib, prefix="nrphy_"):
     sig("pusch_chest_plan_destroy", i32, vp)
     sig("pusch_chest_run", i32, vp, vp, vp, vp, vp, vp)
     sig("pusch_chest_host", i32, vp, P(PuschChestCfg), vp, u32, u32, vp, vp, vp)
+    sig("prach_threshold", i32, P(PrachCfg), P(C.c_float), P(u32), P(u32))
+    sig("prach_validate", i32, P(PrachCfg))
+    sig("prach_window_width", u32, P(PrachCfg))
+    sig("prach_plan_create", i32, vp, u32, P(PrachCfg), P(u64), u64, u64, P(vp))
+    sig("prach_plan_destroy", i32, vp)
+    sig("prach_plan_metric_stride", u32, vp)
+    sig("prach_run", i32, vp, vp, vp, vp, vp, vp)
+    sig("prach_detect_host", i32, vp, P(PrachCfg), vp, u64, u64, P(PrachResult), P(PrachPreamble), vp)
+    sig("prach_generate_host", i32, vp, P(PrachCfg), u32, vp)
     sig("pusch_decode_codeblock_host", i32, vp, P(LdpcRateDematcherCfg), u32, u32, C.c_float, vp, vp, i32, u8p, P(u32))
     return lib
 
@@ -587,4 +635,6 @@ ABI_SYMBOLS = [
     "nrphy_pusch_demod_run", "nrphy_pusch_demodulate_host",
     "nrphy_pusch_chest_validate", "nrphy_pusch_chest_plan_create", "nrphy_pusch_chest_plan_destroy", "nrphy_pusch_chest_run",
     "nrphy_pusch_chest_host",
+    "nrphy_prach_threshold", "nrphy_prach_validate", "nrphy_prach_window_width", "nrphy_prach_plan_create", "nrphy_prach_plan_destroy",
+    "nrphy_prach_plan_metric_stride", "nrphy_prach_run", "nrphy_prach_detect_host", "nrphy_prach_generate_host",
 ]

@@ -739,6 +739,7 @@ extern "C" int nrphy_destroy(nrphy_ctx_t* ctx)
     (void)hipFree(kv.second);
   }
   (void)hipFree(ctx->d_x1);
+  (void)hipFree(ctx->d_prach);
   for (auto& kv : ctx->d_twiddle) {
     (void)hipFree(kv.second);
   }

@@ -1,5 +1,5 @@
 // Host-side internals shared by the translation units behind the C ABI (nrphy_host.cpp, dl_control_host.cpp, pdsch_async.cpp,
-// dl_slot_async.cpp, pusch_demod_host.cpp, pusch_chest_host.cpp): the context, its staging buffers, small helpers.  Not part
+// dl_slot_async.cpp, pusch_demod_host.cpp, pusch_chest_host.cpp, prach_host.cpp): the context, its staging buffers, small helpers.  Not part
 // of the ABI.
 #pragma once
 
@@ -163,6 +163,7 @@ struct nrphy_ctx {
   TbCrcTables* d_tbcrc  = nullptr;
   uint32_t*    d_x1     = nullptr;
   std::map<uint32_t, float2*> d_twiddle; // exp(+j 2 pi k / N) per DFT size, built on first use (under host_mutex)
+  PrachTables* d_prach = nullptr;        // PRACH generator's exponentials and the detector's twiddles, built on first use
   DecoderGraph* d_dec_graph[NOF_GRAPHS] = {}; // decoder graphs, built on first use
   uint32_t*     d_dec_addr[NOF_GRAPHS]  = {}; // ... and, for even lifting sizes, the soft-bit addresses of every (edge, pair of checks)
   std::map<uint64_t, uint32_t*> d_dec_crc;     // early-stop CRC weights per (polynomial, message length)

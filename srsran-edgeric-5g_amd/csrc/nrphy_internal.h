@@ -457,6 +457,47 @@ struct PuschChestLaunch {
   uint32_t                  grid_nof_ports, grid_nof_subc, n_jobs;
 };
 hipError_t launch_pusch_chest(const PuschChestLaunch& p, hipStream_t stream);
+// ---- PRACH detector (receive side) ----------------------------------------------------------------------------------------
+constexpr uint32_t PRACH_L_LONG = 839, PRACH_L_SHORT = 139, PRACH_N_LONG = 1024, PRACH_N_SHORT = 256;
+struct PrachTables {                           // per context
+  float2 cexp_long[4 * PRACH_L_LONG];          // polar(sqrtf(L), float(2 pi) float(i) / float(4 L)): complex_exponential_table
+  float2 cexp_short[4 * PRACH_L_SHORT];
+  float2 tw_long[PRACH_N_LONG];                // exp(+j 2 pi k / N)
+  float2 tw_short[PRACH_N_SHORT];
+};
+struct PrachSequence {                         // what the generator needs for one preamble or root
+  uint16_t u, factor, offset, shift;           // sequence number, u^-1 mod L, phase index of y[0], cyclic shift C_v
+};
+struct PrachDesc {                             // one occasion of a plan
+  uint64_t sym_offset;                         // elements of d_symbols
+  double   sample_rate_hz;                     // N x spacing
+  uint32_t is_long, nof_symbols, nof_rx_ports;
+  uint32_t n_cs, nof_shifts, nof_sequences;
+  uint32_t win_width, win_margin, max_delay;   // correlation samples
+  uint32_t delay_end;                          // a delay is reported below ceil(float(max_delay) * 0.8)
+  uint32_t start, end;                         // monitored preambles [start, end)
+  uint32_t group_log2;                         // lanes per window: the smallest power of two >= win_width, at most 64
+  float    threshold;
+  float    modsq_scale, win_scale;             // 1 / float(N L L), float(N) / float(L)
+  float    time_resolution_s, time_advance_max_s;
+  PrachSequence seq[NRPHY_PRACH_MAX_PREAMBLES]; // the root of sequence i (shift 0)
+};
+struct PrachLaunch {
+  const PrachDesc*        desc;
+  const uint32_t*         jobs_long;           // (occasion << 8) | sequence
+  const uint32_t*         jobs_short;
+  const PrachTables*      tables;
+  const float2*           symbols;
+  nrphy_prach_result_t*   result;              // [n]
+  nrphy_prach_preamble_t* preambles;           // [n][64]
+  float*                  metric;              // [n][64][metric_stride], may be null
+  uint32_t*               rssi_ok;             // scratch [n]: the RSSI is a normal number
+  uint64_t                port_stride, symbol_stride;
+  uint32_t                n, n_jobs_long, n_jobs_short, metric_stride;
+};
+hipError_t launch_prach_detect(const PrachLaunch& p, hipStream_t stream);
+// y[n], n < L, of one sequence into d_y (blocking forms only).
+hipError_t launch_prach_generate(const PrachTables* tables, PrachSequence seq, uint32_t is_long, float2* d_y, hipStream_t stream);
 hipError_t launch_grid_put(const uint32_t* d_index, const uint32_t* d_value, uint32_t n, uint32_t* d_grid, hipStream_t stream);
 
 // ---- PDCCH and SS/PBCH block ("next" row: other downlink grid writers) --------------------------------------------------

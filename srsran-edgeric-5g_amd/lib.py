@@ -412,6 +412,27 @@ class Context:
         m = [[meas[i * abi.PUSCH_CHEST_MAX_LAYERS + l] for l in range(abi.PUSCH_CHEST_MAX_LAYERS)] for i in range(cfg.nof_rx_ports)]
         return ce, nv, m
 
+    def prach_detect_host(self, cfg, symbols, with_metric=False):
+        """prach_detector::detect for one occasion: symbols [ports][symbols][L_RA] complex64 -> (abi.PrachResult, the 64
+        abi.PrachPreamble slots, and with_metric the metric windows [64][window width] f32 or None)."""
+        symbols = np.ascontiguousarray(symbols, dtype=np.complex64)
+        if symbols.ndim != 3 or symbols.shape[0] < cfg.nof_rx_ports:
+            raise ValueError("symbols must be [ports][symbols][L_RA]")
+        width = int(self.lib.nrphy_prach_window_width(C.byref(cfg)))
+        result = abi.PrachResult()
+        pre = (abi.PrachPreamble * abi.PRACH_MAX_PREAMBLES)()
+        metric = np.zeros((abi.PRACH_MAX_PREAMBLES, width), np.float32) if with_metric else None
+        _check(self.lib.nrphy_prach_detect_host(self.handle, C.byref(cfg), symbols.ctypes.data, symbols.shape[1] * symbols.shape[2],
+                                                symbols.shape[2], C.byref(result), pre,
+                                                metric.ctypes.data if with_metric else None), "nrphy_prach_detect_host")
+        return result, pre, metric
+
+    def prach_generate_host(self, cfg, preamble_index):
+        """prach_generator::generate: the frequency-domain sequence of one preamble, L_RA complex64."""
+        y = np.zeros(839 if cfg.format < 4 else 139, np.complex64)
+        _check(self.lib.nrphy_prach_generate_host(self.handle, C.byref(cfg), preamble_index, y.ctypes.data), "nrphy_prach_generate_host")
+        return y
+
     def dft(self, size, inverse, batch, d_in, d_out, stream=None):
         _check(self.lib.nrphy_dft_run(self.handle, size, int(inverse), batch, _dptr(d_in), _dptr(d_out), _stream(stream)),
                "nrphy_dft_run")
@@ -537,6 +558,57 @@ class PuschChestPlan:
             self.close()
         except Exception:
             pass
+
+
+class PrachPlan:
+    """nrphy_prach_plan: occasions of one buffer of complex64 samples; occasion i reads element sym_offsets[i] + port *
+    port_stride + symbol * symbol_stride + k.  run() writes [n] abi.PrachResult, [n][64] abi.PrachPreamble and, optionally,
+    [n][64][metric_stride] f32."""
+
+    def __init__(self, ctx, cfgs, sym_offsets, port_stride, symbol_stride):
+        self.ctx = ctx
+        n = len(cfgs)
+        arr = (abi.PrachCfg * n)(*cfgs)
+        offs = (C.c_uint64 * n)(*sym_offsets)
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_prach_plan_create(ctx.handle, n, arr, offs, port_stride, symbol_stride, C.byref(h)),
+               "nrphy_prach_plan_create")
+        self.handle = h
+        self.n = n
+        self.metric_stride = int(ctx.lib.nrphy_prach_plan_metric_stride(h))
+
+    def run(self, d_symbols, d_result, d_preambles, d_metric=None, stream=None):
+        _check(self.ctx.lib.nrphy_prach_run(self.handle, _dptr(d_symbols), _dptr(d_result), _dptr(d_preambles), _dptr(d_metric),
+                                            _stream(stream)), "nrphy_prach_run")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.nrphy_prach_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def prach_validate(cfg):
+    """nrphy_prach_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_prach_validate(C.byref(cfg)))
+
+
+def prach_threshold(cfg):
+    """nrphy_prach_threshold: (threshold, win_margin, flag) of the table's exact row, or None where it has none (host only)."""
+    th, margin, flag = C.c_float(), C.c_uint32(), C.c_uint32()
+    if int(load().nrphy_prach_threshold(C.byref(cfg), C.byref(th), C.byref(margin), C.byref(flag))) != abi.OK:
+        return None
+    return float(th.value), int(margin.value), int(flag.value)
+
+
+def prach_window_width(cfg):
+    """nrphy_prach_window_width: correlation samples per metric window, 0 for a refused configuration (host only)."""
+    return int(load().nrphy_prach_window_width(C.byref(cfg)))
 
 
 def pusch_chest_validate(cfg, grid_nof_ports, grid_nof_subc):
