@@ -604,6 +604,104 @@ int nrphy_prach_detect_host(nrphy_ctx_t* ctx, const nrphy_prach_cfg_t* cfg, cons
  * L_RA complex f32.  The detection fields of cfg (ports, monitored range, threshold) are not looked at. */
 int nrphy_prach_generate_host(nrphy_ctx_t* ctx, const nrphy_prach_cfg_t* cfg, uint32_t preamble_index, float* y);
 
+/* ---- receive side: PUCCH formats 0 and 1 ----------------------------------------------------------------------------------
+ * Replaces pucch_processor_impl::process for format0_configuration and format1_configuration
+ * (R/lib/phy/upper/channel_processors/pucch_processor_impl.cpp:29-129): grid to HARQ-ACK, SR and channel state information.
+ *
+ * Format 0 (pucch_detector_format0::detect, pucch_detector_format0.cpp:66-202): one or two symbols of one PRB each (the second
+ * symbol on second_hop_prb when there is one), the EPRE over every (symbol, port), and per candidate cyclic shift m_cs of the
+ * reference's five tables (SR only; 1 or 2 ACK bits, each with and without an SR opportunity) the correlation with the
+ * conjugate low-PAPR sequence: per (symbol, port) avg_pwr, corr = |sum / 12|^2 and noise_var = max(0, avg_pwr - corr), sum_corr
+ * and sum_noise_var += noise_var corr accumulated symbol outer, port inner; metric = sum_corr^2 / sum_noise_var where that is a
+ * normal number, else 0.  The best candidate wins by strict >, and is valid above 4.0.  SINR = 10 log10(best metric), RSRP from
+ * the best candidate's sum_corr.
+ *
+ * Format 1: the estimator (dmrs_pucch_processor_format1_impl::estimate, dmrs_pucch_processor_format1_impl.cpp:158-222, on
+ * port_channel_estimator_average_impl::compute with smoothing strategy `mean` and CFO compensation off, the setting of
+ * signal_processor_factories.cpp:124-126) and the detector (pucch_detector_format1::detect, pucch_detector_format1.cpp:92-293).
+ * Per receive port and hop: the LS products of the DM-RS symbols (even symbols of the allocation, z = w_i(m) r_uv^alpha), EPRE,
+ * the CFO from the first two DM-RS symbols of the hop, the sum scaled by 1 / nof DM-RS symbols, its mean over the 12 pilots
+ * (the estimate: one value per port and hop, rounded to cbf16), RSRP and the noise energy (noise_no_cfo); hops merged as compute
+ * does (CFO averaged over the hops that have one, noise floor rsrp / 1e10).  The data symbols (odd symbols) are equalised by ZF
+ * with beta 1 over the ports' estimates and noise variances -- the arithmetic of nrphy_channel_equalize --, multiplied by the
+ * conjugate OCC (one per hop, of the hop's length) and low-PAPR sequence and averaged; detect_bits, threshold 4.0 and the status
+ * of pucch_detector_format1.cpp:162-183 (`unknown` only with SR only and bit 1).  The channel state information is
+ * channel_estimate::get_channel_state_information's: EPRE and RSRP averaged over the ports, CFO of the best-SNR port, the
+ * layer-average SINR.
+ *
+ * Time alignment: the reference runs time_alignment_estimator_dft_impl on the smoothed pilots, which under the `mean` strategy
+ * are 12 equal values c on consecutive subcarriers.  Their 4096-point inverse DFT has magnitude |c| |sin(12 pi n / 4096) /
+ * sin(pi n / 4096)|, whose maximum over the searched bins [0, 144) and [3952, 4096) is at n = 0, 2.8e-5 (relative, in power)
+ * above bins 1 and 4095 -- some hundreds of float32 ulps (6e-8), where a transform of 12 log2 4096 stages is expected, not measured, to
+ * err by a few tens --, ties go to the delay side and an
+ * all-zero input returns index 0.  The peak is bin 0 whatever the grid holds, so the time alignment is 0 and no transform is
+ * computed.
+ *
+ * Group and sequence: u = n_id % 30, v = 0 (group hopping `neither`, as both reference detectors assert).  Cyclic shift
+ * alpha_idx = (initial_cyclic_shift + m_cs + n_cs) % 12, n_cs from the Gold sequence with c_init = n_id
+ * (R/include/srsran/phy/upper/pucch_helper.h:79-108), computed per symbol at plan creation.  Normal cyclic prefix only.  Receive
+ * port i reads grid port rx_ports[i].  Formats 2, 3 and 4 and the srsRAN-side adaptor stay with the caller. */
+#define NRPHY_PUCCH_FORMAT_0 0u
+#define NRPHY_PUCCH_FORMAT_1 1u
+#define NRPHY_PUCCH_NO_HOP 0xFFFFFFFFu
+#define NRPHY_PUCCH_STATUS_UNKNOWN 0u /* uci_status */
+#define NRPHY_PUCCH_STATUS_VALID 1u
+#define NRPHY_PUCCH_STATUS_INVALID 2u
+typedef struct nrphy_pucch_cfg {
+  uint32_t format;                    /* NRPHY_PUCCH_FORMAT_0 or _1 */
+  uint32_t numerology;                /* 0..4 */
+  uint32_t slot_index;                /* slot within the frame: < 10 * 2^numerology */
+  uint32_t bwp_size_rb, bwp_start_rb; /* the PRBs below are relative to bwp_start_rb */
+  uint32_t starting_prb;
+  uint32_t second_hop_prb;            /* NRPHY_PUCCH_NO_HOP: no frequency hopping */
+  uint32_t start_symbol_index, nof_symbols; /* format 0: 1..2 symbols; format 1: 4..14, start <= 10 */
+  uint32_t initial_cyclic_shift;      /* m_0: 0..11 */
+  uint32_t time_domain_occ;           /* format 1: 0..6 and below the number of data symbols of a hop; format 0: must be 0 */
+  uint32_t n_id;                      /* 0..1023 */
+  uint32_t nof_harq_ack;              /* 0..2 */
+  uint32_t sr_opportunity;            /* format 0: 0 or 1 (with nof_harq_ack = 0 it must be 1); format 1: must be 0 */
+  uint32_t nof_rx_ports;              /* 1..4 */
+  uint32_t rx_ports[NRPHY_MAX_PORTS]; /* grid port of receive port i */
+  uint32_t reserved_;
+} nrphy_pucch_cfg_t;
+typedef struct nrphy_pucch_result { /* one per PUCCH */
+  uint32_t status;                    /* NRPHY_PUCCH_STATUS_* */
+  uint32_t harq_ack[2];               /* the first nof_harq_ack entries; the others 0 */
+  uint32_t sr;                        /* format 0 with an SR opportunity: the SR bit; else 0 */
+  float    detection_metric;          /* format 1: metric / 4; format 0: the best metric */
+  float    sinr_dB, rsrp_dB, epre_dB;
+  float    time_alignment_s;          /* 0 (see above) */
+  float    cfo_hz;                    /* NaN where the reference has none: format 0, and hops of a single DM-RS symbol */
+} nrphy_pucch_result_t;
+typedef struct nrphy_pucch_plan nrphy_pucch_plan_t;
+/* NRPHY_OK, or NRPHY_ERR_ARGUMENT for what pucch_pdu_validator_impl::is_valid and the two detectors' assertions refuse: an
+ * unknown format; bwp_start_rb + bwp_size_rb beyond the grid; starting_prb or second_hop_prb outside the BWP; symbols beyond
+ * the slot; format 0 with other than 1 or 2 symbols; format 1 with start_symbol_index above 10 or other than 4 to 14 symbols;
+ * an initial cyclic shift above 11; n_id above 1023; more than 2 ACK bits; format 0 without payload (no ACK bit and no SR
+ * opportunity) or an sr_opportunity other than 0 or 1; time_domain_occ above 6 or not below the number of data symbols of the
+ * (first) hop, or non-zero for format 0; sr_opportunity set for format 1; no rx port, more than 4, one outside the grid or
+ * repeated; numerology above 4 or slot_index >= 10 * 2^numerology.  No device work. */
+int nrphy_pucch_validate(const nrphy_pucch_cfg_t* cfg, uint32_t grid_nof_ports, uint32_t grid_nof_subc);
+/* n PUCCHs of either format; PUCCH i reads grid grid_index[i] of [nof_grids][grid_nof_ports][14][grid_nof_subc] cbf16: the
+ * convention of nrphy_pusch_chest_plan_create, one uplink grid buffer feeds PUSCH and PUCCH.  ce_offset may be NULL; where it
+ * is not, a format 1 PUCCH writes its estimate at element ce_offset[i] of d_ch_est: [rx port i][14][grid_nof_subc] cbf16.
+ * Validates every configuration, computes n_cs per symbol and uploads the descriptors and the sequence tables (blocking). */
+int nrphy_pucch_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pucch_cfg_t* cfgs, const uint32_t* grid_index,
+                            uint32_t nof_grids, uint32_t grid_nof_ports, uint32_t grid_nof_subc, const uint64_t* ce_offset,
+                            nrphy_pucch_plan_t** plan);
+int nrphy_pucch_plan_destroy(nrphy_pucch_plan_t* plan);
+/* d_result: [n].  d_meas (may be NULL): [n][NRPHY_MAX_PORTS], format 1's per-port measurements in the layout of
+ * nrphy_pusch_chest_meas_t, with ta_s and ta_bins 0; zeros for format 0 and for ports the PUCCH does not have.  d_ch_est (may be
+ * NULL; needs a plan created with ce_offset): format 1 writes the 12 subcarriers of the hop's PRB on symbols [start, start +
+ * nof) of every receive port and nothing else.  One wavefront per PUCCH.  Asynchronous on `stream`; allocates nothing,
+ * touches no host memory, uses no atomics and no scratch (capturable; two runs give identical bytes). */
+int nrphy_pucch_run(nrphy_pucch_plan_t* plan, const void* d_grid, nrphy_pucch_result_t* d_result,
+                    nrphy_pusch_chest_meas_t* d_meas, void* d_ch_est, void* stream);
+/* One PUCCH from and to host memory (blocking, on the GPU): grid [grid_nof_ports][14][grid_nof_subc] cbf16 -> result; meas
+ * [nof_rx_ports] (may be NULL); ch_est [nof_rx_ports][14][grid_nof_subc] cbf16 (may be NULL; format 1 writes its region). */
+int nrphy_pucch_host(nrphy_ctx_t* ctx, const nrphy_pucch_cfg_t* cfg, const void* grid, uint32_t grid_nof_ports,
+                     uint32_t grid_nof_subc, nrphy_pucch_result_t* result, nrphy_pusch_chest_meas_t* meas, void* ch_est);
+
 /* ---- other downlink grid writers ("next" row): NZP-CSI-RS generator -----------
  * Replaces nzp_csi_rs_generator::map (R/include/srsran/phy/upper/signal_processors/nzp_csi_rs_generator.h:
  * 39-90; impl R/lib/phy/upper/signal_processors/nzp_csi_rs_generator_impl.cpp:96-352 with the RE patterns of

@@ -212,6 +212,46 @@ def make_prach(*, format, ra_scs=None, root_sequence_index=0, zero_correlation_z
     return c
 
 
+PUCCH_FORMAT_0 = 0
+PUCCH_FORMAT_1 = 1
+PUCCH_NO_HOP = 0xFFFFFFFF
+PUCCH_STATUS_UNKNOWN, PUCCH_STATUS_VALID, PUCCH_STATUS_INVALID = 0, 1, 2  # uci_status
+
+
+class PucchCfg(C.Structure):
+    """nrphy_pucch_cfg_t (pucch_processor::format0_configuration / format1_configuration)."""
+    _fields_ = [("format", C.c_uint32), ("numerology", C.c_uint32), ("slot_index", C.c_uint32), ("bwp_size_rb", C.c_uint32),
+                ("bwp_start_rb", C.c_uint32), ("starting_prb", C.c_uint32), ("second_hop_prb", C.c_uint32),
+                ("start_symbol_index", C.c_uint32), ("nof_symbols", C.c_uint32), ("initial_cyclic_shift", C.c_uint32),
+                ("time_domain_occ", C.c_uint32), ("n_id", C.c_uint32), ("nof_harq_ack", C.c_uint32), ("sr_opportunity", C.c_uint32),
+                ("nof_rx_ports", C.c_uint32), ("rx_ports", C.c_uint32 * MAX_PORTS), ("reserved_", C.c_uint32)]
+
+
+class PucchResult(C.Structure):
+    """nrphy_pucch_result_t: one per PUCCH."""
+    _fields_ = [("status", C.c_uint32), ("harq_ack", C.c_uint32 * 2), ("sr", C.c_uint32), ("detection_metric", C.c_float),
+                ("sinr_dB", C.c_float), ("rsrp_dB", C.c_float), ("epre_dB", C.c_float), ("time_alignment_s", C.c_float),
+                ("cfo_hz", C.c_float)]
+
+
+def make_pucch(*, format, starting_prb, nof_symbols, start_symbol=0, second_hop_prb=None, bwp_size_rb=None, bwp_start_rb=0,
+               numerology=0, slot_index=0, initial_cyclic_shift=0, time_domain_occ=0, n_id=0, nof_harq_ack=1, sr_opportunity=False,
+               rx_ports=(0,)):
+    """A PucchCfg from plain values (second_hop_prb None: no frequency hopping; bwp_size_rb None: the largest BWP, 275 PRBs less
+    its start)."""
+    c = PucchCfg()
+    c.format, c.numerology, c.slot_index = format, numerology, slot_index
+    c.bwp_size_rb = 275 - bwp_start_rb if bwp_size_rb is None else bwp_size_rb
+    c.bwp_start_rb, c.starting_prb = bwp_start_rb, starting_prb
+    c.second_hop_prb = PUCCH_NO_HOP if second_hop_prb is None else second_hop_prb
+    c.start_symbol_index, c.nof_symbols = start_symbol, nof_symbols
+    c.initial_cyclic_shift, c.time_domain_occ, c.n_id = initial_cyclic_shift, time_domain_occ, n_id
+    c.nof_harq_ack, c.sr_opportunity, c.nof_rx_ports = nof_harq_ack, int(sr_opportunity), len(rx_ports)
+    for i, q in enumerate(rx_ports):
+        c.rx_ports[i] = q
+    return c
+
+
 class GridRe(C.Structure):
     """nrphy_grid_re_t: one resource element written from the host into a device grid."""
     _fields_ = [("port", C.c_uint16), ("symbol", C.c_uint16), ("subc", C.c_uint32), ("value", C.c_uint32)]
@@ -598,6 +638,11 @@ def declare(lib, prefix="nrphy_"):
     sig("prach_run", i32, vp, vp, vp, vp, vp, vp)
     sig("prach_detect_host", i32, vp, P(PrachCfg), vp, u64, u64, P(PrachResult), P(PrachPreamble), vp)
     sig("prach_generate_host", i32, vp, P(PrachCfg), u32, vp)
+    sig("pucch_validate", i32, P(PucchCfg), u32, u32)
+    sig("pucch_plan_create", i32, vp, u32, P(PucchCfg), P(u32), u32, u32, u32, P(u64), P(vp))
+    sig("pucch_plan_destroy", i32, vp)
+    sig("pucch_run", i32, vp, vp, vp, vp, vp, vp)
+    sig("pucch_host", i32, vp, P(PucchCfg), vp, u32, u32, P(PucchResult), vp, vp)
     sig("pusch_decode_codeblock_host", i32, vp, P(LdpcRateDematcherCfg), u32, u32, C.c_float, vp, vp, i32, u8p, P(u32))
     return lib
 
@@ -637,4 +682,5 @@ ABI_SYMBOLS = [
     "nrphy_pusch_chest_host",
     "nrphy_prach_threshold", "nrphy_prach_validate", "nrphy_prach_window_width", "nrphy_prach_plan_create", "nrphy_prach_plan_destroy",
     "nrphy_prach_plan_metric_stride", "nrphy_prach_run", "nrphy_prach_detect_host", "nrphy_prach_generate_host",
+    "nrphy_pucch_validate", "nrphy_pucch_plan_create", "nrphy_pucch_plan_destroy", "nrphy_pucch_run", "nrphy_pucch_host",
 ]

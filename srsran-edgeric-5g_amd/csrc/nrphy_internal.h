@@ -498,6 +498,36 @@ struct PrachLaunch {
 hipError_t launch_prach_detect(const PrachLaunch& p, hipStream_t stream);
 // y[n], n < L, of one sequence into d_y (blocking forms only).
 hipError_t launch_prach_generate(const PrachTables* tables, PrachSequence seq, uint32_t is_long, float2* d_y, hipStream_t stream);
+// ---- PUCCH formats 0 and 1 (receive side) ---------------------------------------------------------------------------------
+struct PucchTables {                           // per plan
+  float2 base[30][NRPHY_NRE];                  // exp(j phi(n) pi / 4) of group u: the reference's 8-entry exponential table
+  float2 shift[24];                            // polar(1, float(2 pi) float(i) / 24): cyclic shift alpha n = entry (2 alpha n) % 24
+  float2 occ[7][7][7];                         // w_i(m) of length N at [N - 1][i][m]: polar(1, TWOPI phi / N)
+};
+struct PucchDesc {                             // one PUCCH of a plan
+  uint32_t format, grid_index, nof_rx_ports;
+  uint32_t first_symbol, nof_symbols;
+  uint32_t prb[2];                             // grid PRB of the first and of the second hop (equal without hopping)
+  uint32_t hopping;                            // format 1: 1 = the second hop starts at first_symbol + nof_symbols / 2
+  uint32_t u, occ;                             // sequence group n_id % 30; time-domain OCC index
+  uint32_t nof_harq_ack, sr_opportunity;
+  uint32_t scs_khz;
+  float    cfo_dt[2];                          // per hop: epoch of its second DM-RS symbol minus that of its first, in symbols
+  uint8_t  rx_ports[NRPHY_MAX_PORTS];
+  uint8_t  alpha[NRPHY_NSYMB];                 // (m_0 + n_cs(l)) % 12 of allocation symbol l - first_symbol (m_cs = 0)
+  uint8_t  pad_[2];
+  uint64_t ce_offset;                          // elements of d_ch_est
+};
+struct PucchLaunch {
+  const PucchDesc*          desc;
+  const PucchTables*        tables;
+  const uint32_t*           grid;
+  nrphy_pucch_result_t*     result;            // [n]
+  nrphy_pusch_chest_meas_t* meas;              // [n][NRPHY_MAX_PORTS], may be null
+  uint32_t*                 ch;                // may be null
+  uint32_t                  grid_nof_ports, grid_nof_subc, n;
+};
+hipError_t launch_pucch(const PucchLaunch& p, hipStream_t stream);
 hipError_t launch_grid_put(const uint32_t* d_index, const uint32_t* d_value, uint32_t n, uint32_t* d_grid, hipStream_t stream);
 
 // ---- PDCCH and SS/PBCH block ("next" row: other downlink grid writers) --------------------------------------------------

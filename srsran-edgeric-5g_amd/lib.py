@@ -433,6 +433,23 @@ class Context:
         _check(self.lib.nrphy_prach_generate_host(self.handle, C.byref(cfg), preamble_index, y.ctypes.data), "nrphy_prach_generate_host")
         return y
 
+    def pucch_host(self, cfg, grid, with_estimate=False, ch_est=None):
+        """pucch_processor::process (format 0 or 1) for one PUCCH: grid [ports][14][subc] raw cbf16 words -> (abi.PucchResult,
+        measurements [rx] of abi.PuschChestMeas, and with_estimate format 1's ch_est [rx][14][subc] cbf16 words or None).  ch_est:
+        the buffer to write into (only the allocated region changes); zeros when None."""
+        grid = np.ascontiguousarray(grid, dtype=np.uint32)
+        result = abi.PucchResult()
+        meas = (abi.PuschChestMeas * cfg.nof_rx_ports)()
+        ce = None
+        if with_estimate:
+            shape = (cfg.nof_rx_ports, 14, grid.shape[-1])
+            ce = np.zeros(shape, np.uint32) if ch_est is None else np.array(ch_est, dtype=np.uint32, order="C")
+            if ce.shape != shape:
+                raise ValueError("ch_est must be %s" % (shape,))
+        _check(self.lib.nrphy_pucch_host(self.handle, C.byref(cfg), grid.ctypes.data, grid.shape[0], grid.shape[-1], C.byref(result),
+                                         meas, ce.ctypes.data if with_estimate else None), "nrphy_pucch_host")
+        return result, list(meas), ce
+
     def dft(self, size, inverse, batch, d_in, d_out, stream=None):
         _check(self.lib.nrphy_dft_run(self.handle, size, int(inverse), batch, _dptr(d_in), _dptr(d_out), _stream(stream)),
                "nrphy_dft_run")
@@ -593,6 +610,39 @@ class PrachPlan:
             pass
 
 
+class PucchPlan:
+    """nrphy_pucch_plan: PUCCHs of formats 0 and 1 over a batch of received grids (the grid buffer PuschChestPlan reads); run()
+    writes [n] abi.PucchResult and, optionally, [n][4] abi.PuschChestMeas and format 1's channel estimates (ce_offsets given)."""
+
+    def __init__(self, ctx, cfgs, grid_indices, nof_grids, nof_ports, nof_subc, ce_offsets=None):
+        self.ctx = ctx
+        n = len(cfgs)
+        arr = (abi.PucchCfg * n)(*cfgs)
+        gidx = (C.c_uint32 * n)(*grid_indices)
+        offs = (C.c_uint64 * n)(*ce_offsets) if ce_offsets is not None else None
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_pucch_plan_create(ctx.handle, n, arr, gidx, nof_grids, nof_ports, nof_subc, offs, C.byref(h)),
+               "nrphy_pucch_plan_create")
+        self.handle = h
+        self.n = n
+
+    def run(self, d_grid, d_result, d_meas=None, d_ch_est=None, stream=None):
+        """d_result: [n] x 40 bytes; d_meas: [n][4] x 32 bytes or None; d_ch_est: what ce_offsets index, or None."""
+        _check(self.ctx.lib.nrphy_pucch_run(self.handle, _dptr(d_grid), _dptr(d_result), _dptr(d_meas), _dptr(d_ch_est),
+                                            _stream(stream)), "nrphy_pucch_run")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.nrphy_pucch_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def prach_validate(cfg):
     """nrphy_prach_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
     return int(load().nrphy_prach_validate(C.byref(cfg)))
@@ -609,6 +659,11 @@ def prach_threshold(cfg):
 def prach_window_width(cfg):
     """nrphy_prach_window_width: correlation samples per metric window, 0 for a refused configuration (host only)."""
     return int(load().nrphy_prach_window_width(C.byref(cfg)))
+
+
+def pucch_validate(cfg, grid_nof_ports, grid_nof_subc):
+    """nrphy_pucch_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_pucch_validate(C.byref(cfg), grid_nof_ports, grid_nof_subc))
 
 
 def pusch_chest_validate(cfg, grid_nof_ports, grid_nof_subc):
