@@ -702,6 +702,106 @@ int nrphy_pucch_run(nrphy_pucch_plan_t* plan, const void* d_grid, nrphy_pucch_re
 int nrphy_pucch_host(nrphy_ctx_t* ctx, const nrphy_pucch_cfg_t* cfg, const void* grid, uint32_t grid_nof_ports,
                      uint32_t grid_nof_subc, nrphy_pucch_result_t* result, nrphy_pusch_chest_meas_t* meas, void* ch_est);
 
+/* ---- receive side: UCI decoder (short blocks and polar) -----------------------------------------------------------------------
+ * Replaces uci_decoder_impl::decode (R/lib/phy/upper/channel_processors/uci/uci_decoder_impl.cpp): the soft bits of one UCI
+ * message (HARQ-ACK, CSI part 1 or part 2 taken out of a PUSCH codeword, or later a PUCCH format 2 to 4 payload) to its bits and a
+ * status.  Everything is integer arithmetic on int8 soft bits in the reference's domain -- finite values -120..120 and +-127 for
+ * infinity --, so the result equals the reference's bit for bit.
+ *
+ * 1 to 11 bits: short_block_detector_impl::detect (R/lib/phy/upper/channel_coding/short/short_block_detector_impl.cpp).  The rate
+ * de-matcher adds the repetitions of each position in ascending order with the saturating sum; an all-zero input gives an all-ones
+ * message and INVALID; 1 bit is the sign of the first soft bit (always VALID), 2 bits the best of the four 3-bit codewords over the
+ * soft bits the modulation's placement leaves, 3 to 11 bits the first of the 2^(A-1) even-valued codewords of the (32, A) code of
+ * TS 38.212 Table 5.3.3.3-1 with the largest |correlation|, whose sign is bit 0.  VALID when the reference's detection metric
+ * exceeds its threshold, decided in integers.
+ *
+ * 12 to 1706 bits: per block (two when A >= 1013, or A >= 360 with E >= 1088; an odd A then gives the first block one filler bit)
+ * the channel de-interleaver, bit de-selection (repetitions added with the promoting sum, punctured positions 0, shortened ones
+ * +127), the sub-block de-interleaver, the simplified successive cancellation decoder of polar_decoder_impl on the code of
+ * polar_code_impl::set(K, E, 10) -- parity-check positions for K = 18..25, which the decoder treats as information and the
+ * de-allocator skips --, and the 6- or 11-bit CRC over filler, message and CRC.  VALID when the remainder is 0.  The message is
+ * written whether or not the CRC holds.  A failed first block ends the message: status INVALID and the second block's
+ * ceil(A / 2) bytes are NOT written, they keep what the buffer held; a failed second block gives INVALID too. */
+#define NRPHY_UCI_STATUS_UNKNOWN 0u /* uci_status */
+#define NRPHY_UCI_STATUS_VALID 1u
+#define NRPHY_UCI_STATUS_INVALID 2u
+typedef struct nrphy_uci_decoder_cfg {
+  uint32_t message_length; /* A, 1..1706 payload bits */
+  uint32_t llr_length;     /* E, soft bits of this message */
+  uint32_t modulation;     /* NRPHY_MOD_*; only read for A <= 2 */
+  uint32_t reserved_;
+} nrphy_uci_decoder_cfg_t;
+typedef struct nrphy_uci_decoder_plan nrphy_uci_decoder_plan_t;
+/* NRPHY_OK, or NRPHY_ERR_ARGUMENT for what the reference asserts on: A outside 1..1706; for A <= 2 an unknown modulation or E
+ * below its bits per symbol; for A in 3..11 E <= A; for A >= 12, per block of K = ceil(A / C) + CRC bits and E / C soft bits, what
+ * polar_code_impl::set refuses: K outside 18..25 and 31..1023, more than 8192 soft bits, K + 3 >= E (K <= 25) or K >= E, K not
+ * below the code length.  No device work. */
+int nrphy_uci_decoder_validate(const nrphy_uci_decoder_cfg_t* cfg);
+/* n messages of any mix of sizes; message i reads llr_length soft bits at d_llr + llr_offset[i] and writes message_length bytes
+ * (one bit each) at d_message + message_offset[i].  Validates every configuration, builds each distinct polar code (K, E) once and
+ * uploads the tables (blocking). */
+int nrphy_uci_decoder_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_uci_decoder_cfg_t* cfgs, const uint64_t* llr_offset,
+                                  const uint64_t* message_offset, nrphy_uci_decoder_plan_t** plan);
+int nrphy_uci_decoder_plan_destroy(nrphy_uci_decoder_plan_t* plan);
+/* d_status: [n] NRPHY_UCI_STATUS_*.  One launch, one wavefront per message.  Asynchronous on `stream`; allocates nothing, touches no
+ * host memory, uses no atomics and no scratch (capturable; two runs give identical bytes). */
+int nrphy_uci_decoder_run(nrphy_uci_decoder_plan_t* plan, const int8_t* d_llr, uint8_t* d_message, uint32_t* d_status, void* stream);
+/* One message from and to host memory (blocking, on the GPU).  `message` is read as well: bytes the decoder does not write (the
+ * second block behind a failed first one) come back as they went in.  Makes and releases a one-message plan inside the call (code
+ * construction, an allocation and a blocking upload each time): for more than a few messages make one plan over all of them. */
+int nrphy_uci_decode_host(nrphy_ctx_t* ctx, const nrphy_uci_decoder_cfg_t* cfg, const int8_t* llr, uint8_t* message,
+                          uint32_t* status);
+
+/* ---- receive side: UL-SCH demultiplexer (UCI on PUSCH, TS 38.212 Section 6.2.7) -----------------------------------------------
+ * Replaces ulsch_demultiplex::demultiplex + set_csi_part2 and the pusch_codeword_buffer it returns
+ * (R/lib/phy/upper/channel_processors/pusch/ulsch_demultiplex_impl.cpp): the descrambled soft bits of a codeword, as
+ * nrphy_pusch_demod_run writes them (symbol by symbol, subcarrier ascending, nof_layers * Qm per resource element), to the four
+ * streams the reference hands to its decoder buffers, in its order.  The UL-SCH stream goes to nrphy_pusch_decode_batch, the other
+ * three to nrphy_uci_decoder_run, on the same stream with no host step.  HARQ-ACK of 1 or 2 bits punctures: its REs stay in the
+ * UL-SCH stream (or in CSI part 2, where that took a reserved RE) as zeros.  Streams whose payload is 1 or 2 bits get the
+ * placeholder corrections of on_uci_placeholder_1bit / _2bit, which re-apply or swap scrambling signs; they need rnti and n_id.
+ * The fields are ulsch_demultiplex::configuration plus set_csi_part2's sizes, which have to be known when the plan is made: this
+ * equals the reference when set_csi_part2 precedes the first block.  Deriving them from a decoded CSI part 1 is the caller's
+ * business (a second plan).  Soft bits are expected in the reference's domain, -127..127. */
+typedef struct nrphy_ulsch_demux_cfg {
+  uint32_t modulation, nof_layers, nof_prb, start_symbol_index, nof_symbols; /* NRPHY_MOD_*; 1..4; 1..275; symbols of the slot */
+  uint32_t dmrs_type, dmrs_symbol_mask, nof_cdm_groups_without_data; /* 0 = type 1, 1 = type 2; bit l = symbol l carries DM-RS */
+  uint32_t nof_harq_ack_rvd;                                         /* G^ACK_rvd, soft bits reserved for HARQ-ACK of <= 2 bits */
+  uint32_t nof_harq_ack_bits, nof_enc_harq_ack_bits;                 /* O^ACK, G^ACK */
+  uint32_t nof_csi_part1_bits, nof_enc_csi_part1_bits;
+  uint32_t nof_csi_part2_bits, nof_enc_csi_part2_bits; /* known when the plan is made; 0 = none */
+  uint32_t rnti, n_id;                                 /* the codeword's scrambling, as the demodulator's */
+} nrphy_ulsch_demux_cfg_t;
+typedef struct nrphy_ulsch_demux_sizes {
+  uint32_t nof_sch_bits, nof_codeword_bits; /* soft bits of the UL-SCH stream (zeroed ones included) and of the input */
+} nrphy_ulsch_demux_sizes_t;
+typedef struct nrphy_ulsch_demux_plan nrphy_ulsch_demux_plan_t;
+/* NRPHY_OK, or NRPHY_ERR_ARGUMENT for what the reference asserts on or cannot finish: an unknown modulation; layers outside 1..4;
+ * PRBs outside 1..275; symbols beyond the slot; a DM-RS type above 1 or CDM groups without data outside 1..2 (type 1) or 1..3
+ * (type 2); a DM-RS mask without a DM-RS symbol, without a later symbol free of DM-RS, or with bits above symbol 13; a UCI part
+ * with payload bits but no soft bits or the reverse; soft bits of a part that the placement cannot take exactly (not a multiple
+ * of nof_layers * Qm, or more than the symbols hold: on_end_codeword's assertions).  Also refused, because the reference's
+ * unsigned arithmetic goes wrong there: a reserved set next to HARQ-ACK of more than 2 bits.  No device work. */
+int nrphy_ulsch_demux_validate(const nrphy_ulsch_demux_cfg_t* cfg);
+int nrphy_ulsch_demux_sizes(const nrphy_ulsch_demux_cfg_t* cfg, nrphy_ulsch_demux_sizes_t* sizes);
+/* n codewords of any mix of configurations; codeword i reads nof_codeword_bits soft bits at d_codeword_llr + in_offset[i] and
+ * writes its streams at d_sch + sch_offset[i], d_harq_ack + harq_offset[i], d_csi1 + csi1_offset[i], d_csi2 + csi2_offset[i]
+ * (nof_sch_bits and the nof_enc_* bits of the configuration).  An offset array may be NULL when no codeword has that part.
+ * rnti up to 65535, n_id up to 1023.  The placement is computed here and uploaded as an index table, 4 bytes per resource
+ * element (blocking).  Offsets that are multiples of 16 let the kernel move 16 bytes per thread. */
+int nrphy_ulsch_demux_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_ulsch_demux_cfg_t* cfgs, const uint64_t* in_offset,
+                                  const uint64_t* sch_offset, const uint64_t* harq_offset, const uint64_t* csi1_offset,
+                                  const uint64_t* csi2_offset, nrphy_ulsch_demux_plan_t** plan);
+int nrphy_ulsch_demux_plan_destroy(nrphy_ulsch_demux_plan_t* plan);
+/* One launch.  A stream pointer may be NULL when no codeword of the plan has that part.  Every byte of every stream is written.
+ * Asynchronous on `stream`; allocates nothing, touches no host memory, uses no atomics and no scratch (capturable; two runs give
+ * identical bytes). */
+int nrphy_ulsch_demux_run(nrphy_ulsch_demux_plan_t* plan, const int8_t* d_codeword_llr, int8_t* d_sch, int8_t* d_harq_ack,
+                          int8_t* d_csi1, int8_t* d_csi2, void* stream);
+/* One codeword from and to host memory (blocking, on the GPU).  Makes and releases a plan inside the call. */
+int nrphy_ulsch_demultiplex_host(nrphy_ctx_t* ctx, const nrphy_ulsch_demux_cfg_t* cfg, const int8_t* codeword_llr, int8_t* sch,
+                                 int8_t* harq_ack, int8_t* csi1, int8_t* csi2);
+
 /* ---- other downlink grid writers ("next" row): NZP-CSI-RS generator -----------
  * Replaces nzp_csi_rs_generator::map (R/include/srsran/phy/upper/signal_processors/nzp_csi_rs_generator.h:
  * 39-90; impl R/lib/phy/upper/signal_processors/nzp_csi_rs_generator_impl.cpp:96-352 with the RE patterns of

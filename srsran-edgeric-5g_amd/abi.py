@@ -252,6 +252,43 @@ def make_pucch(*, format, starting_prb, nof_symbols, start_symbol=0, second_hop_
     return c
 
 
+UCI_STATUS_UNKNOWN, UCI_STATUS_VALID, UCI_STATUS_INVALID = 0, 1, 2  # uci_status
+
+
+class UciDecoderCfg(C.Structure):
+    """nrphy_uci_decoder_cfg_t (uci_decoder::decode's message and soft-bit lengths, uci_decoder::configuration's modulation)."""
+    _fields_ = [("message_length", C.c_uint32), ("llr_length", C.c_uint32), ("modulation", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class UlschDemuxCfg(C.Structure):
+    """nrphy_ulsch_demux_cfg_t (ulsch_demultiplex::configuration, set_csi_part2's sizes and the codeword's scrambling)."""
+    _fields_ = [(n, C.c_uint32) for n in (
+        "modulation", "nof_layers", "nof_prb", "start_symbol_index", "nof_symbols", "dmrs_type", "dmrs_symbol_mask",
+        "nof_cdm_groups_without_data", "nof_harq_ack_rvd", "nof_harq_ack_bits", "nof_enc_harq_ack_bits", "nof_csi_part1_bits",
+        "nof_enc_csi_part1_bits", "nof_csi_part2_bits", "nof_enc_csi_part2_bits", "rnti", "n_id")]
+
+
+class UlschDemuxSizes(C.Structure):
+    """nrphy_ulsch_demux_sizes_t."""
+    _fields_ = [("nof_sch_bits", C.c_uint32), ("nof_codeword_bits", C.c_uint32)]
+
+
+def make_ulsch_demux(**fields):
+    """An UlschDemuxCfg from keyword fields (those not given are 0)."""
+    c = UlschDemuxCfg()
+    for k, v in fields.items():
+        assert hasattr(c, k), k
+        setattr(c, k, int(v))
+    return c
+
+
+def make_uci_decoder(message_length, llr_length, modulation=2):
+    """A UciDecoderCfg; modulation is an NRPHY_MOD_* code (0 pi/2-BPSK, 1 BPSK, else the bits per symbol)."""
+    c = UciDecoderCfg()
+    c.message_length, c.llr_length, c.modulation = message_length, llr_length, modulation
+    return c
+
+
 class GridRe(C.Structure):
     """nrphy_grid_re_t: one resource element written from the host into a device grid."""
     _fields_ = [("port", C.c_uint16), ("symbol", C.c_uint16), ("subc", C.c_uint32), ("value", C.c_uint32)]
@@ -643,6 +680,17 @@ def declare(lib, prefix="nrphy_"):
     sig("pucch_plan_destroy", i32, vp)
     sig("pucch_run", i32, vp, vp, vp, vp, vp, vp)
     sig("pucch_host", i32, vp, P(PucchCfg), vp, u32, u32, P(PucchResult), vp, vp)
+    sig("uci_decoder_validate", i32, P(UciDecoderCfg))
+    sig("uci_decoder_plan_create", i32, vp, u32, P(UciDecoderCfg), P(u64), P(u64), P(vp))
+    sig("uci_decoder_plan_destroy", i32, vp)
+    sig("uci_decoder_run", i32, vp, vp, vp, vp, vp)
+    sig("uci_decode_host", i32, vp, P(UciDecoderCfg), vp, vp, P(u32))
+    sig("ulsch_demux_validate", i32, P(UlschDemuxCfg))
+    sig("ulsch_demux_sizes", i32, P(UlschDemuxCfg), P(UlschDemuxSizes))
+    sig("ulsch_demux_plan_create", i32, vp, u32, P(UlschDemuxCfg), P(u64), P(u64), P(u64), P(u64), P(u64), P(vp))
+    sig("ulsch_demux_plan_destroy", i32, vp)
+    sig("ulsch_demux_run", i32, vp, vp, vp, vp, vp, vp, vp)
+    sig("ulsch_demultiplex_host", i32, vp, P(UlschDemuxCfg), vp, vp, vp, vp, vp)
     sig("pusch_decode_codeblock_host", i32, vp, P(LdpcRateDematcherCfg), u32, u32, C.c_float, vp, vp, i32, u8p, P(u32))
     return lib
 
@@ -683,4 +731,8 @@ ABI_SYMBOLS = [
     "nrphy_prach_threshold", "nrphy_prach_validate", "nrphy_prach_window_width", "nrphy_prach_plan_create", "nrphy_prach_plan_destroy",
     "nrphy_prach_plan_metric_stride", "nrphy_prach_run", "nrphy_prach_detect_host", "nrphy_prach_generate_host",
     "nrphy_pucch_validate", "nrphy_pucch_plan_create", "nrphy_pucch_plan_destroy", "nrphy_pucch_run", "nrphy_pucch_host",
+    "nrphy_uci_decoder_validate", "nrphy_uci_decoder_plan_create", "nrphy_uci_decoder_plan_destroy", "nrphy_uci_decoder_run",
+    "nrphy_uci_decode_host",
+    "nrphy_ulsch_demux_validate", "nrphy_ulsch_demux_sizes", "nrphy_ulsch_demux_plan_create", "nrphy_ulsch_demux_plan_destroy",
+    "nrphy_ulsch_demux_run", "nrphy_ulsch_demultiplex_host",
 ]

@@ -15,8 +15,7 @@ namespace {
 const CrcField CRC24C_FIELD = {0x1B2B117U, 24};
 
 // TS 38.212 Table 5.4.1.1-1.
-const uint8_t SUBBLOCK_PATTERN[32] = {0,  1,  2,  4,  3,  5,  6,  7,  8,  16, 9,  17, 10, 18, 11, 19,
-                                      12, 20, 13, 21, 14, 22, 15, 23, 24, 25, 26, 28, 27, 29, 30, 31};
+const uint8_t SUBBLOCK_PATTERN[32] = NR_POLAR_SUBBLOCK_PATTERN;
 
 // The polar code of a downlink channel (n_max = 9, no parity-check bits): code length, how the rate matcher selects
 // bits, and for every polar input position the message bit it carries (after the interleaver of TS 38.212 Section

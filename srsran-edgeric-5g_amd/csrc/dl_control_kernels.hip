@@ -21,8 +21,7 @@
 namespace nrphy {
 
 // TS 38.212 Table 5.4.1.1-1: sub-block interleaver pattern P(i).
-__constant__ uint8_t SUBBLOCK_P[32] = {0,  1,  2,  4,  3,  5,  6,  7,  8,  16, 9,  17, 10, 18, 11, 19,
-                                       12, 20, 13, 21, 14, 22, 15, 23, 24, 25, 26, 28, 27, 29, 30, 31};
+__constant__ uint8_t SUBBLOCK_P[32] = NR_POLAR_SUBBLOCK_PATTERN;
 
 // J(n) = P(floor(32 n / N)) * (N / 32) + n mod (N / 32), N = 2^log_n >= 32.
 __device__ __forceinline__ uint32_t subblock_j(uint32_t n, uint32_t log_n)

@@ -29,6 +29,12 @@ struct LiftedGraph {
   uint32_t edge[MAX_BG_EDGES];       // (column * Zc) << 16 | lifted shift; core rows: systematic columns only
 };
 
+// ---- Polar codes ---------------------------------------------------------------------------------------------------
+// TS 38.212 Table 5.4.1.1-1, the sub-block interleaver pattern P(i): the one copy that the downlink (PDCCH, PBCH) and uplink (UCI)
+// constructions and kernels initialise their tables from.
+#define NR_POLAR_SUBBLOCK_PATTERN                                                                                       \
+  {0, 1, 2, 4, 3, 5, 6, 7, 8, 16, 9, 17, 10, 18, 11, 19, 12, 20, 13, 21, 14, 22, 15, 23, 24, 25, 26, 28, 27, 29, 30, 31}
+
 // ---- Gold sequence tables -----------------------------------------------------------------------------------
 // x2 jump matrices: row r of (M2)^(2^k) as a 31-bit mask, k = 0..GOLD_JUMP_BITS-1 (state bit j = x2(n + j)).
 constexpr int GOLD_JUMP_BITS  = 24;
@@ -529,6 +535,71 @@ struct PucchLaunch {
 };
 hipError_t launch_pucch(const PucchLaunch& p, hipStream_t stream);
 hipError_t launch_grid_put(const uint32_t* d_index, const uint32_t* d_value, uint32_t n, uint32_t* d_grid, hipStream_t stream);
+
+// ---- UCI decoder (receive side: short blocks and polar) -------------------------------------------------------------------
+// One wavefront per message.  A polar code (K, E) is built once per plan: its offsets index the plan's tab16 and ops tables.
+constexpr uint32_t UCI_NO_CODE = 0xFFFFFFFFu;
+enum UciOp : uint32_t { UCI_OP_F = 0, UCI_OP_G = 1, UCI_OP_RATE1 = 2, UCI_OP_XOR = 3 }; // op word: kind | stage << 2 | position << 6
+struct UciCodeDesc {
+  uint32_t n, K, E;                            // code length 2^n, bits of a block (filler + message + CRC), soft bits of a block
+  uint32_t mode;                               // 0 repetition, 1 puncturing, 2 shortening
+  uint32_t nof_ops, ops_offset;                // the decoder's walk over the tree, in order
+  uint32_t ch_offset;                          // tab16[E]: input position of position i behind the channel de-interleaver
+  uint32_t info_offset;                        // tab16[K]: decoder output position of block bit k (parity-check positions left out)
+  uint32_t crc_offset;                         // tab16[K]: x^(K - 1 - k) mod g, the share of block bit k in the CRC remainder
+  uint32_t crc_size;
+};
+struct UciMsgDesc {
+  uint32_t A, E;
+  uint32_t bps;                                // bits per symbol of the modulation (messages of 1 and 2 bits)
+  uint32_t code;                               // index of the polar code, UCI_NO_CODE for a short block
+  uint32_t nof_blocks;
+  uint32_t pad_;
+  uint64_t llr_offset, message_offset;
+};
+struct UciLaunch {
+  const UciMsgDesc*  msg;
+  const UciCodeDesc* code;
+  const uint16_t*    tab16;
+  const uint32_t*    ops;
+  const int8_t*      llr;
+  uint8_t*           message;
+  uint32_t*          status;
+  uint32_t           n;
+};
+hipError_t launch_uci_decoder(const UciLaunch& p, hipStream_t stream);
+
+// ---- UL-SCH demultiplexer (ulsch_kernels.hip) ---------------------------------------------------------------------------------
+// One descriptor per codeword.  map[map_offset + r]: where input RE r goes (ulsch_placement_host.h); special[special_offset + i]:
+// the REs that take a placeholder correction or a second destination.  `unit`: bytes a thread moves at once (1, 4 or 16: the
+// largest that divides bits_per_re and every offset).
+constexpr uint32_t ULSCH_THREADS = 256, ULSCH_UNITS_PER_THREAD = 4;
+// Map entry of an input RE: stream << 29 | flags | RE index within the stream.
+constexpr uint32_t ULSCH_MAP_ZERO_BIT   = 1u << 28; // the stream receives zeros (the RE was punctured by HARQ-ACK of 1 or 2 bits)
+constexpr uint32_t ULSCH_MAP_SKIP_BIT   = 1u << 27; // written by a special entry instead (placeholder corrections)
+constexpr uint32_t ULSCH_MAP_INDEX_MASK = ULSCH_MAP_SKIP_BIT - 1u;
+struct UlschCwDesc {
+  uint64_t in_offset, out_offset[4];
+  uint32_t nof_re, bits_per_re, qm, unit;
+  uint32_t map_offset, special_offset, nof_special, c_init;
+  uint32_t first_block, nof_copy_blocks; // the codeword's blocks: copy blocks first, then the special ones
+};
+struct UlschSpecialDev {
+  uint32_t src, dst, stream, fix;
+};
+struct UlschLaunch {
+  const UlschCwDesc*     cw;
+  const uint32_t*        block_cw; // codeword of every block
+  const uint32_t*        map;
+  const UlschSpecialDev* special;
+  const GoldTables*      gold;
+  const uint32_t*        x1_words;
+  const int8_t*          in;
+  int8_t*                out[4];
+  uint32_t               nof_blocks;
+  uint32_t               ptr_unit; // 16, 4 or 1: what the alignment of the five pointers allows
+};
+hipError_t launch_ulsch_demux(const UlschLaunch& p, hipStream_t stream);
 
 // ---- PDCCH and SS/PBCH block ("next" row: other downlink grid writers) --------------------------------------------------
 // One wavefront per DCI.  Offsets index the launch's shared tables: tab16 (gather table of the polar input, PRB list),

@@ -450,6 +450,34 @@ class Context:
                                          meas, ce.ctypes.data if with_estimate else None), "nrphy_pucch_host")
         return result, list(meas), ce
 
+    def uci_decode_host(self, cfg, llr, fill=0):
+        """uci_decoder::decode for one message: llr int8 [llr_length] -> (message uint8 [message_length], one bit per byte, status).
+        Bytes the decoder does not write (a second block behind a failed first one) hold `fill`."""
+        llr = np.ascontiguousarray(llr, dtype=np.int8)
+        if llr.size != cfg.llr_length:
+            raise ValueError("llr must hold %d soft bits" % cfg.llr_length)
+        message = np.full(cfg.message_length, fill, np.uint8)
+        status = C.c_uint32()
+        _check(self.lib.nrphy_uci_decode_host(self.handle, C.byref(cfg), llr.ctypes.data, message.ctypes.data, C.byref(status)),
+               "nrphy_uci_decode_host")
+        return message, int(status.value)
+
+    def ulsch_demultiplex_host(self, cfg, codeword_llr, fill=0):
+        """ulsch_demultiplex for one codeword: int8 [nof_codeword_bits] -> (sch, harq_ack, csi1, csi2) int8 arrays of
+        nof_sch_bits and the configuration's nof_enc_* bits, allocated holding `fill`."""
+        sizes = ulsch_demux_sizes(cfg)
+        if sizes is None:
+            raise NrphyError(abi.ERR_ARGUMENT, "nrphy_ulsch_demux_sizes")
+        llr = np.ascontiguousarray(codeword_llr, dtype=np.int8)
+        if llr.size != sizes[1]:
+            raise ValueError("the codeword must hold %d soft bits" % sizes[1])
+        out = [np.full(n, fill, np.int8) for n in (sizes[0], cfg.nof_enc_harq_ack_bits, cfg.nof_enc_csi_part1_bits,
+                                                   cfg.nof_enc_csi_part2_bits)]
+        _check(self.lib.nrphy_ulsch_demultiplex_host(self.handle, C.byref(cfg), llr.ctypes.data, *[o.ctypes.data if o.size else None
+                                                                                                  for o in out]),
+               "nrphy_ulsch_demultiplex_host")
+        return tuple(out)
+
     def dft(self, size, inverse, batch, d_in, d_out, stream=None):
         _check(self.lib.nrphy_dft_run(self.handle, size, int(inverse), batch, _dptr(d_in), _dptr(d_out), _stream(stream)),
                "nrphy_dft_run")
@@ -641,6 +669,87 @@ class PucchPlan:
             self.close()
         except Exception:
             pass
+
+
+class UciDecoderPlan:
+    """nrphy_uci_decoder_plan: a batch of UCI messages of any sizes (short blocks and polar); run() writes every message, one
+    bit per byte, and [n] uint32 statuses in one launch."""
+
+    def __init__(self, ctx, cfgs, llr_offsets, message_offsets):
+        self.ctx = ctx
+        n = len(cfgs)
+        arr = (abi.UciDecoderCfg * n)(*cfgs)
+        lo = (C.c_uint64 * n)(*llr_offsets)
+        mo = (C.c_uint64 * n)(*message_offsets)
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_uci_decoder_plan_create(ctx.handle, n, arr, lo, mo, C.byref(h)), "nrphy_uci_decoder_plan_create")
+        self.handle = h
+        self.n = n
+
+    def run(self, d_llr, d_message, d_status, stream=None):
+        """d_llr: int8 soft bits; d_message: uint8; d_status: [n] uint32 (int32 tensors do)."""
+        _check(self.ctx.lib.nrphy_uci_decoder_run(self.handle, _dptr(d_llr), _dptr(d_message), _dptr(d_status), _stream(stream)),
+               "nrphy_uci_decoder_run")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.nrphy_uci_decoder_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class UlschDemuxPlan:
+    """nrphy_ulsch_demux_plan: a batch of PUSCH codewords with UCI; run() splits every codeword's soft bits into its UL-SCH,
+    HARQ-ACK, CSI part 1 and CSI part 2 streams in one launch."""
+
+    def __init__(self, ctx, cfgs, in_offsets, sch_offsets, harq_offsets=None, csi1_offsets=None, csi2_offsets=None):
+        self.ctx = ctx
+        n = len(cfgs)
+        arr = (abi.UlschDemuxCfg * n)(*cfgs)
+        offs = [None if o is None else (C.c_uint64 * n)(*o) for o in (in_offsets, sch_offsets, harq_offsets, csi1_offsets, csi2_offsets)]
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_ulsch_demux_plan_create(ctx.handle, n, arr, *offs, C.byref(h)), "nrphy_ulsch_demux_plan_create")
+        self.handle = h
+        self.n = n
+
+    def run(self, d_codeword_llr, d_sch, d_harq_ack=None, d_csi1=None, d_csi2=None, stream=None):
+        """int8 device buffers; a stream no codeword of the plan has may be None."""
+        ptr = [None if t is None else _dptr(t) for t in (d_codeword_llr, d_sch, d_harq_ack, d_csi1, d_csi2)]
+        _check(self.ctx.lib.nrphy_ulsch_demux_run(self.handle, *ptr, _stream(stream)), "nrphy_ulsch_demux_run")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.nrphy_ulsch_demux_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ulsch_demux_validate(cfg):
+    """nrphy_ulsch_demux_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_ulsch_demux_validate(C.byref(cfg)))
+
+
+def ulsch_demux_sizes(cfg):
+    """nrphy_ulsch_demux_sizes: (nof_sch_bits, nof_codeword_bits), or None for a refused configuration (host only)."""
+    s = abi.UlschDemuxSizes()
+    if int(load().nrphy_ulsch_demux_sizes(C.byref(cfg), C.byref(s))) != abi.OK:
+        return None
+    return int(s.nof_sch_bits), int(s.nof_codeword_bits)
+
+
+def uci_decoder_validate(cfg):
+    """nrphy_uci_decoder_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_uci_decoder_validate(C.byref(cfg)))
 
 
 def prach_validate(cfg):
