@@ -579,7 +579,8 @@ int nrphy_prach_threshold(const nrphy_prach_cfg_t* cfg, float* threshold, uint32
 int nrphy_prach_validate(const nrphy_prach_cfg_t* cfg);
 /* n occasions; occasion i reads complex f32 samples at element sym_offset[i] + port * port_stride + symbol * symbol_stride + k,
  * k < L_RA, of d_symbols: a prach_buffer tensor (re, symbol, td occasion, fd occasion, port; re fastest) is read in place, one
- * (td, fd) occasion per item.  Validates every configuration and precomputes, in the reference's order of operations, N_CS, the
+ * (td, fd) occasion per item; nrphy_prach_demod_run (below) produces that tensor from baseband samples on the same stream.
+ * Validates every configuration and precomputes, in the reference's order of operations, N_CS, the
  * number of shifts and sequences, window width, largest delay, threshold and margin and the monitored sequence numbers. */
 int nrphy_prach_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_prach_cfg_t* cfgs, const uint64_t* sym_offset,
                             uint64_t port_stride, uint64_t symbol_stride, nrphy_prach_plan_t** plan);
@@ -603,6 +604,66 @@ int nrphy_prach_detect_host(nrphy_ctx_t* ctx, const nrphy_prach_cfg_t* cfg, cons
 /* The frequency-domain sequence of one preamble from the device's generator (what prach_generator::generate returns): y holds
  * L_RA complex f32.  The detection fields of cfg (ports, monitored range, threshold) are not looked at. */
 int nrphy_prach_generate_host(nrphy_ctx_t* ctx, const nrphy_prach_cfg_t* cfg, uint32_t preamble_index, float* y);
+
+/* ---- receive side: OFDM PRACH demodulator ---------------------------------------------------------------------------------
+ * Replaces ofdm_prach_demodulator_impl::demodulate (R/lib/phy/lower/modulation/ofdm_prach_demodulator_impl.cpp:31-203): baseband
+ * samples of a PRACH window to the frequency-domain symbols of a prach_buffer, for every time- and frequency-domain occasion and
+ * receive port of a configuration.  Time-domain occasion i_td starts start_symbol + duration * i_td PUSCH symbols of
+ * (144 + 2048) >> mu kappa into the window, 16 kappa later when that is after 0 and 16 more when it is after 0.5 ms; its preamble
+ * is get_prach_preamble_long_info / _short_info (RA spacing = PUSCH spacing; the mixed formats change in the last occasion), with a
+ * short format's cyclic prefix 16 kappa longer for an occasion across time 0 and across 0.5 ms.  Symbol s is the dft_size =
+ * srate / ra_scs samples behind the prefix at dft_size * s; its transform is direct and unnormalised, with no phase or frequency
+ * correction.  With K = pusch_scs / ra_scs, grid = nof_prb_ul_grid * K * 12 and k_start = K * 12 * (rb_offset + N_RB^RA * i_fd) +
+ * k_bar (TS 38.211 Table 6.3.3.2-1), element i < L_RA of frequency-domain occasion i_fd is transform bin
+ * (k_start + i - grid / 2) mod dft_size.  Unrestricted by set; float samples only. */
+typedef struct nrphy_prach_demod_cfg {
+  uint32_t srate_hz;              /* sampling rate; srate_hz / ra_scs must be a size nrphy_dft_run has */
+  uint32_t format;                /* NRPHY_PRACH_FORMAT_* */
+  uint32_t nof_td_occasions;      /* 1 for the long formats; start_symbol + duration * nof_td_occasions <= 14 for the short ones */
+  uint32_t nof_fd_occasions;      /* 1..8 */
+  uint32_t start_symbol;          /* 0..13, of the first time-domain occasion, in PUSCH symbols */
+  uint32_t rb_offset;             /* PRACH frequency location, in PUSCH resource blocks */
+  uint32_t nof_prb_ul_grid;       /* 1..275 */
+  uint32_t pusch_numerology;      /* mu: 15 kHz << mu, 0..3 */
+  uint32_t nof_rx_ports;          /* 1..4 */
+} nrphy_prach_demod_cfg_t;
+typedef struct nrphy_prach_demod_sizes {
+  uint32_t dft_size;              /* samples per PRACH symbol */
+  uint32_t sequence_length;       /* L_RA: 839 or 139 */
+  uint32_t nof_symbols;           /* per occasion */
+  uint32_t window_samples;        /* the smallest input length per port: the end of the last occasion, and for the short formats
+                                     not less than get_prach_window_duration */
+} nrphy_prach_demod_sizes_t;
+typedef struct nrphy_prach_demod_plan nrphy_prach_demod_plan_t;
+/* NRPHY_OK, or NRPHY_ERR_ARGUMENT for what the reference asserts on: an unknown format or numerology; no time-domain occasion, more
+ * than one on a long format, more short ones than fit the slot from start_symbol (a start symbol above 13); no frequency-domain
+ * occasion or more than 8; a reserved (RA spacing, PUSCH spacing) row of the mapping table; a sampling rate that is no multiple of
+ * the RA spacing or whose srate / ra_scs is not a size nrphy_dft_run supports; a dft_size not above the grid; a last
+ * frequency-domain occasion with k_start + L_RA >= grid; a start, prefix, length or window that is not a whole number of samples at
+ * the rate (phy_time_unit::is_sample_accurate); ports outside 1..4 or PRB outside 1..275.  No device work. */
+int nrphy_prach_demod_validate(const nrphy_prach_demod_cfg_t* cfg);
+/* NRPHY_ERR_ARGUMENT (sizes untouched) where nrphy_prach_demod_validate refuses the configuration.  No device work. */
+int nrphy_prach_demod_sizes(const nrphy_prach_demod_cfg_t* cfg, nrphy_prach_demod_sizes_t* sizes);
+/* n configurations; item i reads port p's complex f32 samples at element in_offset[i] + p * in_port_stride (window_samples of
+ * them) of d_samples and writes element k < L_RA of (port p, frequency-domain occasion fd, time-domain occasion td, symbol s) to
+ * element out_offset[i] + p * port_stride + fd * fd_stride + td * td_stride + s * symbol_stride + k of d_symbols: a prach_buffer
+ * tensor (re, symbol, fd occasion, td occasion, port; re fastest) that nrphy_prach_plan_create reads in place, one (td, fd) occasion
+ * per detector item.  Validates every configuration; all window and bin arithmetic happens here.  On an error *plan is NULL. */
+int nrphy_prach_demod_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_prach_demod_cfg_t* cfgs, const uint64_t* in_offset,
+                                  uint64_t in_port_stride, const uint64_t* out_offset, uint64_t port_stride, uint64_t fd_stride,
+                                  uint64_t td_stride, uint64_t symbol_stride, nrphy_prach_demod_plan_t** plan);
+int nrphy_prach_demod_plan_destroy(nrphy_prach_demod_plan_t* plan);
+/* One workgroup per (item, port, time-domain occasion, symbol), one launch per transform size in the plan.  Writes the k < L_RA
+ * elements of its items' (port, td, fd, symbol) and nothing else.  Asynchronous on `stream`; allocates nothing, touches no host
+ * memory, uses no atomics (capturable; two runs give identical bytes).  The plan owns no scratch, so runs of one plan need no
+ * ordering among themselves unless they write the same d_symbols: a split transform (dft_size above 6144) accumulates its partial
+ * sums in the output elements themselves. */
+int nrphy_prach_demod_run(nrphy_prach_demod_plan_t* plan, const void* d_samples, void* d_symbols, void* stream);
+/* One configuration from and to host memory (blocking, on the GPU): samples hold port p at element p * in_port_stride
+ * (window_samples each); symbols is addressed like d_symbols with out_offset 0, and the elements the run does not write keep what
+ * the caller had there. */
+int nrphy_prach_demodulate_host(nrphy_ctx_t* ctx, const nrphy_prach_demod_cfg_t* cfg, const void* samples, uint64_t in_port_stride,
+                                void* symbols, uint64_t port_stride, uint64_t fd_stride, uint64_t td_stride, uint64_t symbol_stride);
 
 /* ---- receive side: PUCCH formats 0 and 1 ----------------------------------------------------------------------------------
  * Replaces pucch_processor_impl::process for format0_configuration and format1_configuration

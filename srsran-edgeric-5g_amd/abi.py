@@ -212,6 +212,29 @@ def make_prach(*, format, ra_scs=None, root_sequence_index=0, zero_correlation_z
     return c
 
 
+class PrachDemodCfg(C.Structure):
+    """nrphy_prach_demod_cfg_t (the sampling rate + ofdm_prach_demodulator::configuration, with ports in place of one port)."""
+    _fields_ = [("srate_hz", C.c_uint32), ("format", C.c_uint32), ("nof_td_occasions", C.c_uint32), ("nof_fd_occasions", C.c_uint32),
+                ("start_symbol", C.c_uint32), ("rb_offset", C.c_uint32), ("nof_prb_ul_grid", C.c_uint32),
+                ("pusch_numerology", C.c_uint32), ("nof_rx_ports", C.c_uint32)]
+
+
+class PrachDemodSizes(C.Structure):
+    """nrphy_prach_demod_sizes_t."""
+    _fields_ = [("dft_size", C.c_uint32), ("sequence_length", C.c_uint32), ("nof_symbols", C.c_uint32), ("window_samples", C.c_uint32)]
+
+
+def make_prach_demod(*, srate_hz, format, nof_td_occasions=1, nof_fd_occasions=1, start_symbol=0, rb_offset=0, nof_prb_ul_grid,
+                     pusch_numerology=0, nof_rx_ports=1):
+    """A PrachDemodCfg from plain values: format by name ("B4") or number."""
+    c = PrachDemodCfg()
+    c.srate_hz = srate_hz
+    c.format = PRACH_FORMATS.index(format) if isinstance(format, str) else format
+    c.nof_td_occasions, c.nof_fd_occasions, c.start_symbol, c.rb_offset = nof_td_occasions, nof_fd_occasions, start_symbol, rb_offset
+    c.nof_prb_ul_grid, c.pusch_numerology, c.nof_rx_ports = nof_prb_ul_grid, pusch_numerology, nof_rx_ports
+    return c
+
+
 PUCCH_FORMAT_0 = 0
 PUCCH_FORMAT_1 = 1
 PUCCH_NO_HOP = 0xFFFFFFFF
@@ -675,6 +698,12 @@ def declare(lib, prefix="nrphy_"):
     sig("prach_run", i32, vp, vp, vp, vp, vp, vp)
     sig("prach_detect_host", i32, vp, P(PrachCfg), vp, u64, u64, P(PrachResult), P(PrachPreamble), vp)
     sig("prach_generate_host", i32, vp, P(PrachCfg), u32, vp)
+    sig("prach_demod_validate", i32, P(PrachDemodCfg))
+    sig("prach_demod_sizes", i32, P(PrachDemodCfg), P(PrachDemodSizes))
+    sig("prach_demod_plan_create", i32, vp, u32, P(PrachDemodCfg), P(u64), u64, P(u64), u64, u64, u64, u64, P(vp))
+    sig("prach_demod_plan_destroy", i32, vp)
+    sig("prach_demod_run", i32, vp, vp, vp, vp)
+    sig("prach_demodulate_host", i32, vp, P(PrachDemodCfg), vp, u64, vp, u64, u64, u64, u64)
     sig("pucch_validate", i32, P(PucchCfg), u32, u32)
     sig("pucch_plan_create", i32, vp, u32, P(PucchCfg), P(u32), u32, u32, u32, P(u64), P(vp))
     sig("pucch_plan_destroy", i32, vp)
@@ -730,6 +759,8 @@ ABI_SYMBOLS = [
     "nrphy_pusch_chest_host",
     "nrphy_prach_threshold", "nrphy_prach_validate", "nrphy_prach_window_width", "nrphy_prach_plan_create", "nrphy_prach_plan_destroy",
     "nrphy_prach_plan_metric_stride", "nrphy_prach_run", "nrphy_prach_detect_host", "nrphy_prach_generate_host",
+    "nrphy_prach_demod_validate", "nrphy_prach_demod_sizes", "nrphy_prach_demod_plan_create", "nrphy_prach_demod_plan_destroy",
+    "nrphy_prach_demod_run", "nrphy_prach_demodulate_host",
     "nrphy_pucch_validate", "nrphy_pucch_plan_create", "nrphy_pucch_plan_destroy", "nrphy_pucch_run", "nrphy_pucch_host",
     "nrphy_uci_decoder_validate", "nrphy_uci_decoder_plan_create", "nrphy_uci_decoder_plan_destroy", "nrphy_uci_decoder_run",
     "nrphy_uci_decode_host",

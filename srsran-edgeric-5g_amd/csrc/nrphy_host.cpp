@@ -759,8 +759,6 @@ extern "C" int nrphy_synchronize(nrphy_ctx_t* ctx, void* stream)
   return NRPHY_OK;
 }
 
-namespace {
-
 // exp(+j 2 pi k / N) computed in double precision and rounded once.
 const float2* get_twiddle(nrphy_ctx* ctx, uint32_t size)
 {
@@ -784,8 +782,6 @@ const float2* get_twiddle(nrphy_ctx* ctx, uint32_t size)
   ctx->d_twiddle[size] = d;
   return d;
 }
-
-} // namespace
 
 // ================================================================================================================
 // PDSCH plan

@@ -1,5 +1,5 @@
 // Host-side internals shared by the translation units behind the C ABI (nrphy_host.cpp, dl_control_host.cpp, pdsch_async.cpp,
-// dl_slot_async.cpp, pusch_demod_host.cpp, pusch_chest_host.cpp, prach_host.cpp, pucch_host.cpp, uci_host.cpp): the context, its staging buffers, small helpers.  Not part
+// dl_slot_async.cpp, pusch_demod_host.cpp, pusch_chest_host.cpp, prach_host.cpp, prach_demod_host.cpp, pucch_host.cpp, uci_host.cpp): the context, its staging buffers, small helpers.  Not part
 // of the ABI.
 #pragma once
 
@@ -177,6 +177,10 @@ struct nrphy_ctx {
   void*      scratch[SCRATCH_COUNT]       = {};
   size_t     scratch_bytes[SCRATCH_COUNT] = {};
 };
+
+// The context's table exp(+j 2 pi k / size) of a size nrphy_dft_run supports, built on first use with the context's device
+// current; null for another size or when the upload fails.  It lives as long as the context.
+const float2* get_twiddle(nrphy_ctx* ctx, uint32_t size);
 
 // ---- PDSCH plans in caller-owned memory (the asynchronous queue) ----------------------------------------------------------
 // nrphy_pdsch_plan_create allocates device memory and copies the plan's tables there with a blocking copy: right for a

@@ -504,6 +504,27 @@ struct PrachLaunch {
 hipError_t launch_prach_detect(const PrachLaunch& p, hipStream_t stream);
 // y[n], n < L, of one sequence into d_y (blocking forms only).
 hipError_t launch_prach_generate(const PrachTables* tables, PrachSequence seq, uint32_t is_long, float2* d_y, hipStream_t stream);
+// ---- OFDM PRACH demodulator (receive side) --------------------------------------------------------------------------------
+struct PrachDemodDesc {                        // one configuration of a plan
+  const float2* tw_total;                      // exp(+j 2 pi k / dft_size), the context's table
+  uint64_t      fd_stride;
+  uint32_t      n1, n_total;                   // dft_size = n_total = n1 x the LDS transform's size
+  uint32_t      seq_len, spacing, span;        // L_RA; bins between frequency-domain occasions; (nof_fd - 1) spacing + L_RA
+  uint32_t      first_bin, first_bin_lds;      // bin of element 0 of occasion 0, and the same modulo the LDS transform's size
+};
+struct PrachDemodJob {                         // one workgroup: a symbol of (item, port, time-domain occasion)
+  uint64_t in_offset, out_offset;              // first sample of the symbol; element 0 of frequency-domain occasion 0
+  uint32_t desc, reserved;
+};
+struct PrachDemodLaunch {
+  const PrachDemodDesc* desc;
+  const PrachDemodJob*  jobs;                  // the jobs of this transform size
+  const float2*         tw_lds;                // the table of the LDS transform's size
+  const float2*         samples;
+  float2*               symbols;
+  uint32_t              n_jobs;
+};
+hipError_t launch_prach_demod(uint32_t lds_size, const PrachDemodLaunch& p, hipStream_t stream);
 // ---- PUCCH formats 0 and 1 (receive side) ---------------------------------------------------------------------------------
 struct PucchTables {                           // per plan
   float2 base[30][NRPHY_NRE];                  // exp(j phi(n) pi / 4) of group u: the reference's 8-entry exponential table

@@ -433,6 +433,25 @@ class Context:
         _check(self.lib.nrphy_prach_generate_host(self.handle, C.byref(cfg), preamble_index, y.ctypes.data), "nrphy_prach_generate_host")
         return y
 
+    def prach_demodulate_host(self, cfg, samples, symbols=None):
+        """ofdm_prach_demodulator::demodulate for every port of one configuration: samples [ports][>= window_samples] complex64 ->
+        symbols [ports][td][fd][symbols][L_RA] complex64 (the prach_buffer's order).  symbols: a larger C-contiguous buffer of five
+        dimensions to write into (only the configuration's elements change); zeros of the exact size when None."""
+        samples = np.ascontiguousarray(samples, dtype=np.complex64)
+        sz = prach_demod_sizes(cfg)
+        if sz is None:
+            raise ValueError("nrphy_prach_demod_validate refuses the configuration")
+        if samples.ndim != 2 or samples.shape[0] < cfg.nof_rx_ports or samples.shape[1] < sz.window_samples:
+            raise ValueError("samples must be [ports][>= %d]" % sz.window_samples)
+        shape = (cfg.nof_rx_ports, cfg.nof_td_occasions, cfg.nof_fd_occasions, sz.nof_symbols, sz.sequence_length)
+        out = np.zeros(shape, np.complex64) if symbols is None else np.array(symbols, dtype=np.complex64, order="C")
+        if out.ndim != 5 or any(a < b for a, b in zip(out.shape, shape)):
+            raise ValueError("symbols must be at least %s" % (shape,))
+        st = [v // 8 for v in out.strides]  # port, td, fd, symbol, re
+        _check(self.lib.nrphy_prach_demodulate_host(self.handle, C.byref(cfg), samples.ctypes.data, samples.shape[1], out.ctypes.data,
+                                                    st[0], st[2], st[1], st[3]), "nrphy_prach_demodulate_host")
+        return out
+
     def pucch_host(self, cfg, grid, with_estimate=False, ch_est=None):
         """pucch_processor::process (format 0 or 1) for one PUCCH: grid [ports][14][subc] raw cbf16 words -> (abi.PucchResult,
         measurements [rx] of abi.PuschChestMeas, and with_estimate format 1's ch_est [rx][14][subc] cbf16 words or None).  ch_est:
@@ -750,6 +769,50 @@ def ulsch_demux_sizes(cfg):
 def uci_decoder_validate(cfg):
     """nrphy_uci_decoder_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
     return int(load().nrphy_uci_decoder_validate(C.byref(cfg)))
+
+
+class PrachDemodPlan:
+    """nrphy_prach_demod_plan: item i reads port p's complex64 samples at element in_offsets[i] + p * in_port_stride and writes
+    element out_offsets[i] + p * port_stride + fd * fd_stride + td * td_stride + s * symbol_stride + k of the symbols."""
+
+    def __init__(self, ctx, cfgs, in_offsets, in_port_stride, out_offsets, port_stride, fd_stride, td_stride, symbol_stride):
+        self.ctx = ctx
+        self.handle = None
+        n = len(cfgs)
+        arr = (abi.PrachDemodCfg * n)(*cfgs)
+        ins = (C.c_uint64 * n)(*in_offsets)
+        outs = (C.c_uint64 * n)(*out_offsets)
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_prach_demod_plan_create(ctx.handle, n, arr, ins, in_port_stride, outs, port_stride, fd_stride, td_stride,
+                                                     symbol_stride, C.byref(h)), "nrphy_prach_demod_plan_create")
+        self.handle = h
+        self.n = n
+
+    def run(self, d_samples, d_symbols, stream=None):
+        _check(self.ctx.lib.nrphy_prach_demod_run(self.handle, _dptr(d_samples), _dptr(d_symbols), _stream(stream)),
+               "nrphy_prach_demod_run")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.nrphy_prach_demod_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def prach_demod_validate(cfg):
+    """nrphy_prach_demod_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_prach_demod_validate(C.byref(cfg)))
+
+
+def prach_demod_sizes(cfg):
+    """nrphy_prach_demod_sizes: abi.PrachDemodSizes, or None for a refused configuration (host only)."""
+    sz = abi.PrachDemodSizes()
+    return sz if int(load().nrphy_prach_demod_sizes(C.byref(cfg), C.byref(sz))) == abi.OK else None
 
 
 def prach_validate(cfg):
