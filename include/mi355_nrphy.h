@@ -701,7 +701,8 @@ int nrphy_prach_demodulate_host(nrphy_ctx_t* ctx, const nrphy_prach_demod_cfg_t*
  * Group and sequence: u = n_id % 30, v = 0 (group hopping `neither`, as both reference detectors assert).  Cyclic shift
  * alpha_idx = (initial_cyclic_shift + m_cs + n_cs) % 12, n_cs from the Gold sequence with c_init = n_id
  * (R/include/srsran/phy/upper/pucch_helper.h:79-108), computed per symbol at plan creation.  Normal cyclic prefix only.  Receive
- * port i reads grid port rx_ports[i].  Formats 2, 3 and 4 and the srsRAN-side adaptor stay with the caller. */
+ * port i reads grid port rx_ports[i].  Format 2 is nrphy_pf2_* below; formats 3 and 4 and the srsRAN-side adaptor stay with the
+ * caller. */
 #define NRPHY_PUCCH_FORMAT_0 0u
 #define NRPHY_PUCCH_FORMAT_1 1u
 #define NRPHY_PUCCH_NO_HOP 0xFFFFFFFFu
@@ -765,7 +766,7 @@ int nrphy_pucch_host(nrphy_ctx_t* ctx, const nrphy_pucch_cfg_t* cfg, const void*
 
 /* ---- receive side: UCI decoder (short blocks and polar) -----------------------------------------------------------------------
  * Replaces uci_decoder_impl::decode (R/lib/phy/upper/channel_processors/uci/uci_decoder_impl.cpp): the soft bits of one UCI
- * message (HARQ-ACK, CSI part 1 or part 2 taken out of a PUSCH codeword, or later a PUCCH format 2 to 4 payload) to its bits and a
+ * message (HARQ-ACK, CSI part 1 or part 2 taken out of a PUSCH codeword, or a PUCCH format 2 payload: nrphy_pf2_run) to its bits and a
  * status.  Everything is integer arithmetic on int8 soft bits in the reference's domain -- finite values -120..120 and +-127 for
  * infinity --, so the result equals the reference's bit for bit.
  *
@@ -812,6 +813,88 @@ int nrphy_uci_decoder_run(nrphy_uci_decoder_plan_t* plan, const int8_t* d_llr, u
  * construction, an allocation and a blocking upload each time): for more than a few messages make one plan over all of them. */
 int nrphy_uci_decode_host(nrphy_ctx_t* ctx, const nrphy_uci_decoder_cfg_t* cfg, const int8_t* llr, uint8_t* message,
                           uint32_t* status);
+
+/* ---- receive side: PUCCH format 2 -----------------------------------------------------------------------------------------------
+ * Replaces pucch_processor_impl::process for format2_configuration
+ * (R/lib/phy/upper/channel_processors/pucch_processor_impl.cpp:131-215): grid to UCI payload, status and channel state
+ * information.  (The names say pf2: the nrphy_pucch_* calls above stay the format 0 and 1 receivers.)
+ *
+ * DM-RS (dmrs_pucch_processor_format2_impl.cpp): pilots on subcarriers 1, 4, 7 and 10 of every PRB of every symbol of the
+ * allocation; per symbol l the Gold sequence with c_init = ((14 n_slot + l + 1)(2 n_id_0 + 1) 2^17 + 2 n_id_0) mod 2^31, advanced by
+ * 8 (bwp_start_rb + starting_prb) bits, as QPSK of amplitude 1 / sqrt(2), real part from the even bits.
+ *
+ * Estimator: port_channel_estimator_average_impl::compute per receive port with the `filter` smoothing strategy and CFO
+ * compensation on (the factory's defaults), one layer, one hop, beta 1 -- the steps of nrphy_pusch_chest_run with pilots every
+ * third subcarrier: LS products and EPRE; with two symbols the CFO from their dot product, derotation and sum; scale 1 /
+ * nof_symbols; filter_type(min(nof_prb, 3), 3) = 3, 7 or 11 taps; 4, 3 or 5 virtual pilots per side for 1, 2 or more PRBs;
+ * convolution_same; RSRP; noise energy (with the CFO phasor when there is one), noise variance floored at rsrp / 1e10, SNR; time
+ * alignment from the 4096-point inverse DFT of the pilots at their grid subcarriers, bins [0, 144) against [3952, 4096), delay on
+ * ties; linear interpolation with offset 1 and stride 3 (interpolator_linear_impl.cpp:58-78: the first two outputs hold pilot 0,
+ * then a running sum of (next - this) / 3 that carries on from the accumulated value, the last output holds the last pilot);
+ * cbf16 rounding; per symbol the product with the CFO phasor, rounded again.
+ *
+ * Demodulator (pucch_demodulator_impl.cpp:31-87): the data REs are the subcarriers k with k mod 3 != 1, symbol by symbol and
+ * ascending; ZF over the ports with tx_scaling 1 and the ports' noise variances (the arithmetic of nrphy_channel_equalize), the
+ * QPSK demapper of nrphy_demodulate_soft over one span of all data REs, descrambling with c_init = rnti 2^15 + n_id: E = 16
+ * nof_prb nof_symbols soft bits, those of equalise -> nrphy_demodulate_soft -> nrphy_llr_descramble on the estimate and noise
+ * variances the same run writes out.  Decoder: nrphy_uci_decoder_run with QPSK over A = nof_harq_ack + nof_sr + nof_csi_part1
+ * bits, in that order.  Channel state information: channel_estimate::get_channel_state_information's, as for format 1, with the
+ * best-SNR port's time alignment.  Normal cyclic prefix only.  Receive port i reads grid port rx_ports[i]. */
+typedef struct nrphy_pf2_cfg {
+  uint32_t numerology;                /* 0..4 */
+  uint32_t slot_index;                /* slot within the frame: < 10 * 2^numerology */
+  uint32_t bwp_size_rb, bwp_start_rb; /* starting_prb is relative to bwp_start_rb */
+  uint32_t starting_prb, nof_prb;     /* nof_prb: 1..16 */
+  uint32_t start_symbol_index, nof_symbols; /* 1..2 symbols */
+  uint32_t rnti;                      /* 0..65535 */
+  uint32_t n_id;                      /* data scrambling identity, 0..1023 */
+  uint32_t n_id_0;                    /* DM-RS scrambling identity, 0..65535 */
+  uint32_t nof_harq_ack, nof_sr, nof_csi_part1;
+  uint32_t nof_csi_part2;             /* must be 0 */
+  uint32_t nof_rx_ports;              /* 1..4 */
+  uint32_t rx_ports[NRPHY_MAX_PORTS]; /* grid port of receive port i */
+} nrphy_pf2_cfg_t;
+typedef struct nrphy_pf2_csi { /* one per PUCCH: channel_state_information */
+  float    sinr_dB, rsrp_dB, epre_dB;
+  float    time_alignment_s;          /* of the receive port with the best SNR */
+  float    cfo_hz;                    /* of the same port; NaN with one symbol */
+  uint32_t reserved_[3];
+} nrphy_pf2_csi_t;
+typedef struct nrphy_pf2_plan nrphy_pf2_plan_t;
+/* NRPHY_OK, or NRPHY_ERR_ARGUMENT for what pucch_pdu_validator_impl::is_valid(format2_configuration), assert_format2_config and
+ * the demodulator's assertions refuse: bwp_start_rb + bwp_size_rb beyond the grid; starting_prb + nof_prb beyond the BWP; nof_prb
+ * outside 1..16; other than 1 or 2 symbols, or symbols beyond the slot; nof_csi_part2 other than 0; A = nof_harq_ack + nof_sr +
+ * nof_csi_part1 outside 3..1706; an effective code rate float(A + CRC bits) / float(E) above 0.8f; and whatever
+ * nrphy_uci_decoder_validate refuses for (A, E, QPSK).  Also: no rx port, more than 4, one outside the grid or repeated;
+ * numerology above 4 or slot_index >= 10 * 2^numerology; rnti or n_id_0 above 65535, n_id above 1023.  No device work. */
+int nrphy_pf2_validate(const nrphy_pf2_cfg_t* cfg, uint32_t grid_nof_ports, uint32_t grid_nof_subc);
+/* E = 16 nof_prb nof_symbols soft bits and A payload bits of a configuration nrphy_pf2_validate accepts (any grid). */
+int nrphy_pf2_sizes(const nrphy_pf2_cfg_t* cfg, uint32_t* nof_llr, uint32_t* nof_payload_bits);
+/* n PUCCHs; PUCCH i reads grid grid_index[i] of [nof_grids][grid_nof_ports][14][grid_nof_subc] cbf16 (the convention of
+ * nrphy_pucch_plan_create: one uplink grid buffer feeds PUSCH and every PUCCH format; grid_nof_subc a multiple of 4), writes its
+ * E soft bits at d_llr + llr_offset[i] and its A payload bits, one per byte, at d_message + message_offset[i].  ce_offset may be
+ * NULL; where it is not, PUCCH i writes its estimate at element ce_offset[i] of d_ch_est: [rx port i][14][grid_nof_subc] cbf16.
+ * Validates every configuration, computes the DM-RS and scrambling seeds, the taps and the epochs, and makes one UCI decoder plan
+ * over the n messages (nrphy_uci_decoder_plan_create) (blocking). */
+int nrphy_pf2_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pf2_cfg_t* cfgs, const uint32_t* grid_index, uint32_t nof_grids,
+                          uint32_t grid_nof_ports, uint32_t grid_nof_subc, const uint64_t* llr_offset,
+                          const uint64_t* message_offset, const uint64_t* ce_offset, nrphy_pf2_plan_t** plan);
+int nrphy_pf2_plan_destroy(nrphy_pf2_plan_t* plan);
+/* Two launches on `stream`: the receiver (one workgroup per PUCCH), then the UCI decoder reading d_llr in place.  d_grid: 16-byte
+ * aligned.  d_status: [n] NRPHY_UCI_STATUS_*; d_message and d_status may both be NULL: the receiver launch alone, for a caller
+ * that decodes d_llr with a UCI decoder plan of its own.  d_csi: [n]; d_meas (may be NULL): [n][NRPHY_MAX_PORTS], the per-port measurements
+ * (zeros for ports the PUCCH does not have); d_ch_est (may be NULL; needs a plan created with ce_offset): the 12 nof_prb
+ * subcarriers of the allocation on its symbols for every receive port, and nothing else -- exactly the words the soft bits were
+ * equalised with, as d_meas holds exactly the noise variances.  Asynchronous; allocates nothing, touches no host memory, uses no
+ * atomics and no scratch (capturable; two runs give identical bytes). */
+int nrphy_pf2_run(nrphy_pf2_plan_t* plan, const void* d_grid, int8_t* d_llr, uint8_t* d_message, uint32_t* d_status,
+                  nrphy_pf2_csi_t* d_csi, nrphy_pusch_chest_meas_t* d_meas, void* d_ch_est, void* stream);
+/* One PUCCH from and to host memory (blocking, on the GPU): grid [grid_nof_ports][14][grid_nof_subc] cbf16 -> message [A] (read
+ * as well: see nrphy_uci_decode_host), status, csi; meas [nof_rx_ports] (may be NULL); ch_est [nof_rx_ports][14][grid_nof_subc]
+ * cbf16 (may be NULL; only the allocation is written); llr [E] (may be NULL). */
+int nrphy_pf2_host(nrphy_ctx_t* ctx, const nrphy_pf2_cfg_t* cfg, const void* grid, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
+                   uint8_t* message, uint32_t* status, nrphy_pf2_csi_t* csi, nrphy_pusch_chest_meas_t* meas, void* ch_est,
+                   int8_t* llr);
 
 /* ---- receive side: UL-SCH demultiplexer (UCI on PUSCH, TS 38.212 Section 6.2.7) -----------------------------------------------
  * Replaces ulsch_demultiplex::demultiplex + set_csi_part2 and the pusch_codeword_buffer it returns

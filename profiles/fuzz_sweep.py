@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Larger randomised sweeps than the test-suite runs, GPU against the oracle through the C ABI (the numbers DESIGN.md section
-2 quotes).  Usage (GPU box, repository root): python3 profiles/fuzz_sweep.py [pdsch] [mutated] [mutated_ctrl] [encode] [batched] [slot] [dlslot] [async] [ctrl_batched] [plan] [pusch] [rx] [ofdm] [wire] [csi] [dlctrl] [demod] [lower]   (default: all)"""
+2 quotes).  Usage (GPU box, repository root): python3 profiles/fuzz_sweep.py [pdsch] [mutated] [mutated_ctrl] [encode] [batched] [slot] [dlslot] [async] [ctrl_batched] [plan] [pusch] [rx] [ofdm] [wire] [csi] [dlctrl] [demod] [lower] [pf2]   (default: all)"""
 import ctypes as C
 import os
 import sys
@@ -884,8 +884,63 @@ def lower():
     return bad
 
 
+def pf2():
+    """PUCCH format 2 receiver: random valid configurations (1..16 PRB, 1..2 symbols, 1..4 permuted ports, every payload size the
+    code rate admits) on seeded grids at random SNR, delay and CFO, in batches of 32: soft bits, payload and status against the
+    restatement (tests/pucch2_model.py) byte for byte, the estimate word for word (the tests allow the estimate 1 bf16 ulp: a
+    mismatch there alone is printed with a soft-bit count of 0)."""
+    import pucch2_model as model
+    import torch
+    rng = np.random.default_rng(BASE + 848484)
+    ports, nprb_grid = 4, 52
+    nsubc = 12 * nprb_grid
+    bad = n = 0
+    for batch in range(10):
+        cfgs, grids, sent = [], [], []
+        while len(cfgs) < 32:
+            nprb, ns = int(rng.choice([1, 2, 3, 4, 7, 16])), int(rng.integers(1, 3))
+            start = int(rng.integers(0, nprb_grid - nprb + 1))
+            sizes = [int(x) for x in rng.multinomial(int(rng.integers(3, 400)), [0.4, 0.1, 0.5])]
+            cfg = model.make_cfg(start, nprb, ns, int(rng.integers(0, 15 - ns)), bwp_size_rb=nprb_grid, numerology=int(rng.integers(0, 2)),
+                                 slot_index=int(rng.integers(0, 10)), rnti=int(rng.integers(0, 65536)), n_id=int(rng.integers(0, 1024)),
+                                 n_id_0=int(rng.integers(0, 65536)), nof_harq_ack=sizes[0], nof_sr=sizes[1], nof_csi_part1=sizes[2],
+                                 rx_ports=tuple(int(q) for q in rng.permutation(ports)[:int(rng.integers(1, ports + 1))]))
+            if not model.validate(cfg, ports, nsubc):
+                continue
+            message = rng.integers(0, 2, model.payload_bits(cfg)).astype(np.uint8)
+            grid = model.received_grid(rng, cfg, message, ports, nsubc, snr_db=float(rng.uniform(-5, 30)), delay=float(rng.uniform(-8, 8)),
+                                       cfo=float(rng.uniform(-0.01, 0.01)), taps=int(rng.integers(1, 3)))
+            cfgs.append(cfg)
+            grids.append(model.quantize(grid))
+            sent.append(message)
+        k = len(cfgs)
+        plan = lib.Pf2Plan(ctx, [model.to_abi(abi, c) for c in cfgs], list(range(k)), k, ports, nsubc, [512 * i for i in range(k)],
+                           [400 * i for i in range(k)], [ports * 14 * nsubc * i for i in range(k)])
+        d_grid = torch.from_numpy(np.stack(grids).view(np.int32)).cuda()
+        d = dict(llr=torch.zeros(512 * k, dtype=torch.int8, device="cuda"), msg=torch.zeros(400 * k, dtype=torch.uint8, device="cuda"),
+                 status=torch.zeros(k, dtype=torch.int32, device="cuda"), csi=torch.zeros(8 * k, dtype=torch.int32, device="cuda"),
+                 ce=torch.zeros(ports * 14 * nsubc * k, dtype=torch.int32, device="cuda"))
+        plan.run(d_grid, d["llr"], d["msg"], d["status"], d["csi"], None, d["ce"])
+        ctx.synchronize()
+        plan.close()
+        llr, msg, status = d["llr"].cpu().numpy().reshape(k, 512), d["msg"].cpu().numpy().reshape(k, 400), d["status"].cpu().numpy()
+        ce = d["ce"].cpu().numpy().view(np.uint32).reshape(k, ports, 14, nsubc)
+        for i, cfg in enumerate(cfgs):
+            want = model.process(cfg, grids[i], o)
+            E, A = model.nof_llr(cfg), model.payload_bits(cfg)
+            k0, s0 = 12 * model.first_prb(cfg), cfg["start_symbol_index"]
+            est = ce[i, :len(cfg["rx_ports"]), s0:s0 + cfg["nof_symbols"], k0:k0 + 12 * cfg["nof_prb"]]
+            n += 1
+            if not (np.array_equal(llr[i, :E], want["llr"]) and np.array_equal(msg[i, :A], want["message"]) and
+                    int(status[i]) == want["status"] and np.array_equal(est, want["est"])):
+                bad += 1
+                print("PF2 MISMATCH", cfg, int((llr[i, :E] != want["llr"]).sum()), int((est != want["est"]).sum()), flush=True)
+    print("PUCCH format 2: %d random PUCCHs, %d mismatches" % (n, bad), flush=True)
+    return bad
+
+
 if __name__ == "__main__":
-    legs = {"pdsch": pdsch, "mutated": mutated, "mutated_ctrl": mutated_ctrl, "encode": encode, "batched": batched, "slot": slot, "dlslot": dlslot, "async": async_queue, "ctrl_batched": ctrl_batched, "plan": plan, "pusch": pusch, "rx": rx, "ofdm": ofdm, "wire": wire, "csi": csi, "dlctrl": dlctrl, "demod": demod, "lower": lower}
+    legs = {"pdsch": pdsch, "mutated": mutated, "mutated_ctrl": mutated_ctrl, "encode": encode, "batched": batched, "slot": slot, "dlslot": dlslot, "async": async_queue, "ctrl_batched": ctrl_batched, "plan": plan, "pusch": pusch, "rx": rx, "ofdm": ofdm, "wire": wire, "csi": csi, "dlctrl": dlctrl, "demod": demod, "lower": lower, "pf2": pf2}
     if "--oracle-only" in sys.argv:   # the oracle side of the mutated leg alone, for the CPU sanitizer build
         sys.exit(mutated(device=False) + mutated_ctrl(device=False))
     which = sys.argv[1:] or list(legs)

@@ -275,6 +275,37 @@ def make_pucch(*, format, starting_prb, nof_symbols, start_symbol=0, second_hop_
     return c
 
 
+class Pf2Cfg(C.Structure):
+    """nrphy_pf2_cfg_t (pucch_processor::format2_configuration)."""
+    _fields_ = [("numerology", C.c_uint32), ("slot_index", C.c_uint32), ("bwp_size_rb", C.c_uint32), ("bwp_start_rb", C.c_uint32),
+                ("starting_prb", C.c_uint32), ("nof_prb", C.c_uint32), ("start_symbol_index", C.c_uint32), ("nof_symbols", C.c_uint32),
+                ("rnti", C.c_uint32), ("n_id", C.c_uint32), ("n_id_0", C.c_uint32), ("nof_harq_ack", C.c_uint32), ("nof_sr", C.c_uint32),
+                ("nof_csi_part1", C.c_uint32), ("nof_csi_part2", C.c_uint32), ("nof_rx_ports", C.c_uint32),
+                ("rx_ports", C.c_uint32 * MAX_PORTS)]
+
+
+class Pf2Csi(C.Structure):
+    """nrphy_pf2_csi_t: one per PUCCH format 2."""
+    _fields_ = [("sinr_dB", C.c_float), ("rsrp_dB", C.c_float), ("epre_dB", C.c_float), ("time_alignment_s", C.c_float),
+                ("cfo_hz", C.c_float), ("reserved_", C.c_uint32 * 3)]
+
+
+def make_pf2(*, starting_prb, nof_prb, nof_symbols, start_symbol=0, bwp_size_rb=None, bwp_start_rb=0, numerology=0, slot_index=0,
+             rnti=1, n_id=0, n_id_0=0, nof_harq_ack=0, nof_sr=0, nof_csi_part1=0, nof_csi_part2=0, rx_ports=(0,)):
+    """A Pf2Cfg from plain values (bwp_size_rb None: the largest BWP, 275 PRBs less its start)."""
+    c = Pf2Cfg()
+    c.numerology, c.slot_index = numerology, slot_index
+    c.bwp_size_rb = 275 - bwp_start_rb if bwp_size_rb is None else bwp_size_rb
+    c.bwp_start_rb, c.starting_prb, c.nof_prb = bwp_start_rb, starting_prb, nof_prb
+    c.start_symbol_index, c.nof_symbols = start_symbol, nof_symbols
+    c.rnti, c.n_id, c.n_id_0 = rnti, n_id, n_id_0
+    c.nof_harq_ack, c.nof_sr, c.nof_csi_part1, c.nof_csi_part2 = nof_harq_ack, nof_sr, nof_csi_part1, nof_csi_part2
+    c.nof_rx_ports = len(rx_ports)
+    for i, q in enumerate(rx_ports):
+        c.rx_ports[i] = q
+    return c
+
+
 UCI_STATUS_UNKNOWN, UCI_STATUS_VALID, UCI_STATUS_INVALID = 0, 1, 2  # uci_status
 
 
@@ -714,6 +745,12 @@ def declare(lib, prefix="nrphy_"):
     sig("uci_decoder_plan_destroy", i32, vp)
     sig("uci_decoder_run", i32, vp, vp, vp, vp, vp)
     sig("uci_decode_host", i32, vp, P(UciDecoderCfg), vp, vp, P(u32))
+    sig("pf2_validate", i32, P(Pf2Cfg), u32, u32)
+    sig("pf2_sizes", i32, P(Pf2Cfg), P(u32), P(u32))
+    sig("pf2_plan_create", i32, vp, u32, P(Pf2Cfg), P(u32), u32, u32, u32, P(u64), P(u64), P(u64), P(vp))
+    sig("pf2_plan_destroy", i32, vp)
+    sig("pf2_run", i32, vp, vp, vp, vp, vp, vp, vp, vp, vp)
+    sig("pf2_host", i32, vp, P(Pf2Cfg), vp, u32, u32, vp, P(u32), P(Pf2Csi), vp, vp, vp)
     sig("ulsch_demux_validate", i32, P(UlschDemuxCfg))
     sig("ulsch_demux_sizes", i32, P(UlschDemuxCfg), P(UlschDemuxSizes))
     sig("ulsch_demux_plan_create", i32, vp, u32, P(UlschDemuxCfg), P(u64), P(u64), P(u64), P(u64), P(u64), P(vp))
@@ -766,4 +803,5 @@ ABI_SYMBOLS = [
     "nrphy_uci_decode_host",
     "nrphy_ulsch_demux_validate", "nrphy_ulsch_demux_sizes", "nrphy_ulsch_demux_plan_create", "nrphy_ulsch_demux_plan_destroy",
     "nrphy_ulsch_demux_run", "nrphy_ulsch_demultiplex_host",
+    "nrphy_pf2_validate", "nrphy_pf2_sizes", "nrphy_pf2_plan_create", "nrphy_pf2_plan_destroy", "nrphy_pf2_run", "nrphy_pf2_host",
 ]

@@ -555,6 +555,41 @@ struct PucchLaunch {
   uint32_t                  grid_nof_ports, grid_nof_subc, n;
 };
 hipError_t launch_pucch(const PucchLaunch& p, hipStream_t stream);
+// ---- PUCCH format 2 (receive side) ------------------------------------------------------------------------------------------
+constexpr uint32_t PF2_MAX_PRB = 16, PF2_MAX_SYMBOLS = 2;
+constexpr uint32_t PF2_PILOTS_PER_PRB = 4, PF2_DATA_PER_PRB = 8; // subcarriers 1, 4, 7, 10 carry DM-RS, the other eight data
+constexpr uint32_t PF2_TW_WORDS = 1024;                       // e^{j 2 pi i / 4096}, i < 1024: the other quadrants by symmetry
+struct Pf2Desc {                                              // one PUCCH of a plan
+  uint32_t grid_index, nof_rx_ports, nprb, prb0;              // prb0: first grid PRB (bwp_start_rb + starting_prb)
+  uint32_t first_symbol, nof_symbols;
+  uint32_t c_init_dmrs[PF2_MAX_SYMBOLS];                      // per symbol of the allocation
+  uint32_t c_init_data;                                       // rnti 2^15 + n_id
+  uint32_t dmrs_words;                                        // Gold words per symbol, from c(0) up to the last pilot's bits
+  uint32_t ntaps, nof_v;                                      // FIR taps (3, 7, 11) and virtual pilots per side (4, 3, 5)
+  uint32_t scs_hz;
+  uint32_t nof_vector;                                        // leading data REs that take the demapper's vector arithmetic
+  uint32_t rx_ports[NRPHY_MAX_PORTS];
+  float    epoch[PF2_MAX_SYMBOLS];                            // start epochs of the allocation's symbols, in symbols
+  float    taps[12];
+  float    ls_scale;                                          // 1 / nof_symbols, in float
+  uint32_t pad_;
+  uint64_t llr_offset;                                        // bytes of d_llr
+  uint64_t ce_offset;                                         // elements of d_ch_est
+};
+struct Pf2Launch {
+  const Pf2Desc*            desc;
+  const float2*             twiddle;                          // [PF2_TW_WORDS]
+  const GoldTables*         gold;
+  const uint32_t*           x1_words;
+  const uint32_t*           grid;
+  int8_t*                   llr;
+  nrphy_pf2_csi_t*          csi;                              // [n]
+  nrphy_pusch_chest_meas_t* meas;                             // [n][NRPHY_MAX_PORTS], may be null
+  uint32_t*                 ch;                               // may be null
+  float                     demod_range, demod_scale;         // the QPSK demapper's quantisation range and 120 / range
+  uint32_t                  grid_nof_ports, grid_nof_subc, n;
+};
+hipError_t launch_pf2(const Pf2Launch& p, hipStream_t stream);
 hipError_t launch_grid_put(const uint32_t* d_index, const uint32_t* d_value, uint32_t n, uint32_t* d_grid, hipStream_t stream);
 
 // ---- UCI decoder (receive side: short blocks and polar) -------------------------------------------------------------------

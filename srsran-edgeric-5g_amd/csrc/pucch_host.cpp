@@ -3,7 +3,7 @@
 // plan's per-PUCCH constants (the cyclic shift index of every symbol, pucch_helper.h:79-108; the hop geometry of
 // dmrs_pucch_processor_format1_impl.cpp:106-136; the symbol epochs the CFO estimate divides by) and the sequence tables in the
 // reference's float expressions (complex_exponential_table, pucch_orthogonal_sequence).
-#include "nrphy_host_internal.h"
+#include "chest_host.h"
 
 #include <array>
 #include <cmath>
@@ -89,17 +89,6 @@ void cyclic_shift_hops(uint32_t n_id, uint32_t n_slot, uint8_t (&n_cs)[NRPHY_NSY
     }
     x1 = (x1 >> 1) | (((x1 ^ (x1 >> 3)) & 1U) << 30);
     x2 = (x2 >> 1) | (((x2 ^ (x2 >> 1) ^ (x2 >> 2) ^ (x2 >> 3)) & 1U) << 30);
-  }
-}
-
-// initialize_symbol_start_epochs (port_channel_estimator_average_impl.cpp:454-466), normal cyclic prefix, in symbols.
-void symbol_epochs(uint32_t numerology, float (&epoch)[NRPHY_NSYMB])
-{
-  double e = 0;
-  for (uint32_t l = 0; l != NRPHY_NSYMB; ++l) {
-    const uint32_t cp = (144U >> numerology) + ((l == 0 || l == 7U * (1U << numerology)) ? 16U : 0U);
-    e += (double)cp * (double)(1U << numerology) / 2048.0 + (l == 0 ? 0.0 : 1.0);
-    epoch[l] = (float)e;
   }
 }
 
@@ -206,7 +195,7 @@ extern "C" int nrphy_pucch_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy
     }
     if (c.format == NRPHY_PUCCH_FORMAT_1) {
       float epoch[NRPHY_NSYMB];
-      symbol_epochs(c.numerology, epoch);
+      chest_symbol_epochs(c.numerology, epoch);
       // The first DM-RS symbol of each hop (an even symbol of the allocation) and the next DM-RS symbol of the slot.
       const uint32_t half = d.hopping ? c.nof_symbols / 2 : 0;
       const uint32_t s1   = c.start_symbol_index + ((half + 1U) & ~1U);

@@ -1,19 +1,12 @@
 // Host side of the PUSCH DM-RS channel estimator (pusch_chest_kernels.hip): validation, and the plan's per-PUSCH constants --
 // what dmrs_pusch_estimator_impl and port_channel_estimator_average_impl compute before touching the grid: c_init per DM-RS
-// symbol (dmrs_pusch_estimator_impl.cpp:136-149), the symbol start epochs (initialize_symbol_start_epochs,
-// port_channel_estimator_average_impl.cpp:454-466) and the raised-cosine taps (filter_type, :62-111), in float32 and in the
-// reference's order of operations.
+// symbol (dmrs_pusch_estimator_impl.cpp:136-149), and the symbol start epochs and raised-cosine taps of chest_host.h.
+#include "chest_host.h"
 #include "pusch_alloc_host.h"
 
 #include <cmath>
 
 namespace {
-
-// port_channel_estimator_average_impl.cpp:41-47
-constexpr float RC_FILTER[31] = {-0.0641253f, -0.0660711f, -0.0611526f, -0.0485918f, -0.0281126f, 0.0000000f, 0.0348830f, 0.0751249f,
-                                 0.1188406f,  0.1637874f,  0.2075139f,  0.2475302f,  0.2814857f,  0.3073415f, 0.3235207f, 0.3290274f,
-                                 0.3235207f,  0.3073415f,  0.2814857f,  0.2475302f,  0.2075139f,  0.1637874f, 0.1188406f, 0.0751249f,
-                                 0.0348830f,  0.0000000f,  -0.0281126f, -0.0485918f, -0.0611526f, -0.0660711f, -0.0641253f};
 
 int validate(const nrphy_pusch_chest_cfg_t* c, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
 {
@@ -35,27 +28,6 @@ int validate(const nrphy_pusch_chest_cfg_t* c, uint32_t grid_nof_ports, uint32_t
     return NRPHY_ERR_ARGUMENT;
   }
   return NRPHY_OK;
-}
-
-// filter_type(nof_rb, stride 2): taps resampled from RC_FILTER and normalised, in float as the reference does.
-uint32_t filter_taps(uint32_t nof_rb, float* taps)
-{
-  const uint32_t stride = 2;
-  nof_rb                = std::min(nof_rb, 3U);
-  uint32_t nof_out      = (nof_rb * 10 + 1) / 2 / stride;
-  uint32_t n            = 31 / 2 - nof_out * stride;
-  nof_out               = 2 * nof_out + 1;
-  float total           = 0;
-  for (uint32_t i = 0; i != nof_out; ++i) {
-    taps[i] = RC_FILTER[n];
-    total += taps[i];
-    n += stride;
-  }
-  const float rcp = 1 / total;
-  for (uint32_t i = 0; i != nof_out; ++i) {
-    taps[i] = taps[i] * rcp;
-  }
-  return nof_out;
 }
 
 } // namespace
@@ -131,15 +103,9 @@ extern "C" int nrphy_pusch_chest_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
         ++d.nof_dmrs;
       }
     }
-    // Cyclic prefix lengths in units of kappa (cyclic_prefix::get_length, normal CP), as fractions of a symbol.
-    double e = 0;
-    for (uint32_t l = 0; l != NRPHY_NSYMB; ++l) {
-      const uint32_t cp = (144U >> c.numerology) + ((l == 0 || l == 7U * (1U << c.numerology)) ? 16U : 0U);
-      e += (double)cp * (double)(1U << c.numerology) / 2048.0 + (l == 0 ? 0.0 : 1.0);
-      d.epoch[l] = (float)e;
-    }
-    d.ntaps = filter_taps(d.nprb, d.taps);
-    d.nof_v = d.nprb == 1 ? 6U : std::min(12U, d.ntaps / 2);
+    chest_symbol_epochs(c.numerology, d.epoch);
+    d.ntaps = chest_filter_taps(d.nprb, 2, d.taps);
+    d.nof_v = chest_nof_virtual_pilots(d.nprb, 6, d.ntaps);
     d.dc    = c.dc_position;
     d.scs_hz = 15000U << c.numerology;
     for (uint32_t k = 0; k != c.nof_rx_ports; ++k) {

@@ -14,8 +14,10 @@
 //  (B) pusch_chest_expand_kernel: one workgroup per (job, OFDM symbol): the scratch row rotated by the symbol's CFO phasor and
 //      rounded again (the reference rounds twice), DC zeroed, written to the allocated PRBs with 16-byte stores.
 // Transcendentals (atan2, hypot, cos, sin) are evaluated in double and rounded once to float.  Contraction is off; the only
-// fused multiply-adds are the partial DFT's, which feed a comparison and nothing else.
+// fused multiply-adds are the partial DFT's, which feed a comparison and nothing else.  The virtual pilots, the phasor and the
+// measurements' arithmetic are chest_device.h's, shared with the PUCCH format 2 receiver.
 #include "bits_device.h"
+#include "chest_device.h"
 
 #include <hip/hip_runtime.h>
 
@@ -26,10 +28,7 @@ constexpr uint32_t CHEST_THREADS = 256;
 constexpr uint32_t MAX_PILOTS    = NRPHY_MAX_RB * 6;
 constexpr uint32_t V_MARGIN      = 12;                            // MAX_V_PILOTS: room for virtual pilots at each end
 constexpr uint32_t MAX_SEQ_WORDS = (NRPHY_MAX_RB * NRPHY_NRE + 31) / 32;
-constexpr uint32_t TA_BINS       = 2 * PUSCH_CHEST_TA_WINDOW;
-constexpr float    TWOPI_F       = 6.28318548f;                   // 2.0F * static_cast<float>(M_PI)
-constexpr float    PI_F          = 3.14159274f;
-constexpr float    SQRT1_2_F     = 0.707106769f;
+constexpr uint32_t TA_BINS       = CHEST_TA_BINS;
 
 struct ChestShared {
   uint32_t seq[NRPHY_NSYMB][MAX_SEQ_WORDS];  // Gold words c(0 ...) of every DM-RS symbol
@@ -45,23 +44,6 @@ struct ChestShared {
   double   red[4][2];
   float    vp_abs[2][V_MARGIN], vp_arg[2][V_MARGIN];
 };
-
-__device__ __forceinline__ uint32_t to_cbf16(float re, float im)
-{
-  return to_bf16_bits(re) | (to_bf16_bits(im) << 16);
-}
-
-// std::polar(1.0F, x) with cos and sin evaluated in double and rounded once.
-__device__ __forceinline__ float2 phasor(float x)
-{
-  return make_float2((float)cos((double)x), (float)sin((double)x));
-}
-
-// (a + jb)(c + jd) as std::complex<float> writes it.
-__device__ __forceinline__ float2 cmul(float2 x, float2 h)
-{
-  return make_float2(__fsub_rn(__fmul_rn(x.x, h.x), __fmul_rn(x.y, h.y)), __fadd_rn(__fmul_rn(x.x, h.y), __fmul_rn(x.y, h.x)));
-}
 
 // Workgroup sum of two doubles in a fixed order; every thread gets the result.
 __device__ __forceinline__ double2 block_sum2(double x, double y, ChestShared& s, uint32_t tid)
@@ -91,44 +73,6 @@ __device__ __forceinline__ float2 pilot(const ChestShared& s, uint32_t d, uint32
     p = make_float2(-p.x, -p.y);
   }
   return p;
-}
-
-// compute_v_pilots: a linear fit of |.| and of the unwrapped argument of n pilots, evaluated at i + offset.
-__device__ void virtual_pilots(const float* abs_, float* arg, uint32_t n, int offset, float2* out)
-{
-  // unwrap_list (R/lib/srsvec/unwrap.cpp)
-  float k = 0.f;
-  for (uint32_t i = 0; i + 1 < n; ++i) {
-    const float old_a = arg[i], next_a = arg[i + 1];
-    arg[i]            = __fadd_rn(arg[i], __fmul_rn(__fmul_rn(2.0f, k), PI_F));
-    const float jump  = __fsub_rn(next_a, old_a);
-    if (fabsf(jump) > PI_F) {
-      k = __fsub_rn(k, jump < 0.f ? -1.0f : 1.0f);
-    }
-  }
-  arg[n - 1] = __fadd_rn(arg[n - 1], __fmul_rn(__fmul_rn(2.0f, k), PI_F));
-  const float nf        = (float)n;
-  const float mean_x    = __fdiv_rn(__fdiv_rn((float)(n * (n - 1)), 2.0f), nf);
-  const float norm_x_sq = __fdiv_rn((float)((n - 1) * n * (2 * n - 1)), 6.0f);
-  const float den       = __fsub_rn(norm_x_sq, __fmul_rn(__fmul_rn(nf, mean_x), mean_x));
-  float       sa = 0.f, sg = 0.f, da = 0.f, dg = 0.f;
-  for (uint32_t i = 0; i != n; ++i) {
-    sa = __fadd_rn(sa, abs_[i]);
-    sg = __fadd_rn(sg, arg[i]);
-    da = __fadd_rn(da, __fmul_rn(abs_[i], (float)i));
-    dg = __fadd_rn(dg, __fmul_rn(arg[i], (float)i));
-  }
-  const float mean_abs = __fdiv_rn(sa, nf), mean_arg = __fdiv_rn(sg, nf);
-  const float slope_abs = __fdiv_rn(__fsub_rn(da, __fmul_rn(__fmul_rn(mean_x, mean_abs), nf)), den);
-  const float slope_arg = __fdiv_rn(__fsub_rn(dg, __fmul_rn(__fmul_rn(mean_x, mean_arg), nf)), den);
-  const float icp_abs   = __fsub_rn(mean_abs, __fmul_rn(slope_abs, mean_x));
-  const float icp_arg   = __fsub_rn(mean_arg, __fmul_rn(slope_arg, mean_x));
-  for (uint32_t i = 0; i != n; ++i) {
-    const float  x = (float)((int)i + offset);
-    const float  r = __fadd_rn(__fmul_rn(slope_abs, x), icp_abs);
-    const float2 e = phasor(__fadd_rn(__fmul_rn(slope_arg, x), icp_arg));
-    out[i]         = make_float2(__fmul_rn(r, e.x), __fmul_rn(r, e.y));
-  }
 }
 
 __global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_kernel(PuschChestLaunch p)
@@ -312,25 +256,12 @@ __global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_kernel(PuschChestLa
       }
     }
     const int   ta_bins   = best_d >= best_a ? id : ia - (int)PUSCH_CHEST_TA_WINDOW;
-    const float epre_f    = (float)(pe.y / (double)(N * nd));
-    const float nvar_raw  = (float)(nz.x / (double)(N * nd - 1u));
-    const float min_noise = __fdiv_rn(rsrp, 1e10f);
-    const float noise_var = nvar_raw > min_noise ? nvar_raw : min_noise;
-    const float datarp    = __fdiv_rn(__fdiv_rn(rsrp, d.beta), d.beta);
-    const float snr       = noise_var != 0.f ? __fdiv_rn(datarp, noise_var) : 1000.f;
+    const nrphy_pusch_chest_meas_t m = chest_measurements(rsrp, (float)(pe.y / (double)(N * nd)), (float)(nz.x / (double)(N * nd - 1u)),
+                                                          d.beta, ta_bins, nd >= 2u, cfo, d.scs_hz);
     if (layer == 0) {
-      p.noise_vars[(size_t)ip * NRPHY_MAX_PORTS + port] = noise_var;
+      p.noise_vars[(size_t)ip * NRPHY_MAX_PORTS + port] = m.noise_var;
     }
     if (p.meas != nullptr) {
-      nrphy_pusch_chest_meas_t m;
-      m.noise_var = noise_var;
-      m.rsrp      = rsrp;
-      m.epre      = epre_f;
-      m.snr       = snr;
-      m.ta_s      = (float)((double)ta_bins / (4096.0 * (double)d.scs_hz));
-      m.ta_bins   = ta_bins;
-      m.cfo_hz    = nd >= 2u ? __fmul_rn(__fmul_rn(cfo, (float)(d.scs_hz / 1000u)), 1000.f) : __builtin_nanf("");
-      m.reserved_ = 0;
       p.meas[((size_t)ip * NRPHY_MAX_PORTS + port) * PUSCH_CHEST_MAX_LAYERS + layer] = m;
     }
   } else if (tid >= 128u && tid < 128u + NRPHY_NSYMB) { // the per-symbol CFO phasors of the expand kernel

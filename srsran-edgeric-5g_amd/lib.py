@@ -469,6 +469,32 @@ class Context:
                                          meas, ce.ctypes.data if with_estimate else None), "nrphy_pucch_host")
         return result, list(meas), ce
 
+    def pf2_host(self, cfg, grid, with_estimate=False, ch_est=None, fill=0):
+        """pucch_processor::process (format 2) for one PUCCH: grid [ports][14][subc] raw cbf16 words -> dict of message uint8 [A]
+        (one bit per byte; bytes the decoder does not write hold `fill`), status, csi (abi.Pf2Csi), meas [rx] of abi.PuschChestMeas,
+        llr int8 [E] and, with_estimate, ch_est [rx][14][subc] cbf16 words (else None).  ch_est: the buffer to write into (only the
+        allocation changes); zeros when None."""
+        grid = np.ascontiguousarray(grid, dtype=np.uint32)
+        sizes = pf2_sizes(cfg)
+        if sizes is None:
+            raise ValueError("nrphy_pf2_validate refuses the configuration")
+        E, A = sizes
+        message = np.full(A, fill, np.uint8)
+        llr = np.zeros(E, np.int8)
+        status = C.c_uint32()
+        csi = abi.Pf2Csi()
+        meas = (abi.PuschChestMeas * cfg.nof_rx_ports)()
+        ce = None
+        if with_estimate:
+            shape = (cfg.nof_rx_ports, 14, grid.shape[-1])
+            ce = np.zeros(shape, np.uint32) if ch_est is None else np.array(ch_est, dtype=np.uint32, order="C")
+            if ce.shape != shape:
+                raise ValueError("ch_est must be %s" % (shape,))
+        _check(self.lib.nrphy_pf2_host(self.handle, C.byref(cfg), grid.ctypes.data, grid.shape[0], grid.shape[-1], message.ctypes.data,
+                                       C.byref(status), C.byref(csi), meas, ce.ctypes.data if with_estimate else None,
+                                       llr.ctypes.data), "nrphy_pf2_host")
+        return {"message": message, "status": int(status.value), "csi": csi, "meas": list(meas), "llr": llr, "ch_est": ce}
+
     def uci_decode_host(self, cfg, llr, fill=0):
         """uci_decoder::decode for one message: llr int8 [llr_length] -> (message uint8 [message_length], one bit per byte, status).
         Bytes the decoder does not write (a second block behind a failed first one) hold `fill`."""
@@ -690,6 +716,42 @@ class PucchPlan:
             pass
 
 
+class Pf2Plan:
+    """nrphy_pf2_plan: PUCCHs of format 2 over a batch of received grids (the grid buffer PuschChestPlan and PucchPlan read);
+    run() writes every PUCCH's soft bits, payload bits, status and channel state information with two launches."""
+
+    def __init__(self, ctx, cfgs, grid_indices, nof_grids, nof_ports, nof_subc, llr_offsets, message_offsets, ce_offsets=None):
+        self.ctx = ctx
+        n = len(cfgs)
+        arr = (abi.Pf2Cfg * n)(*cfgs)
+        gidx = (C.c_uint32 * n)(*grid_indices)
+        lo = (C.c_uint64 * n)(*llr_offsets)
+        mo = (C.c_uint64 * n)(*message_offsets)
+        offs = (C.c_uint64 * n)(*ce_offsets) if ce_offsets is not None else None
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_pf2_plan_create(ctx.handle, n, arr, gidx, nof_grids, nof_ports, nof_subc, lo, mo, offs, C.byref(h)),
+               "nrphy_pf2_plan_create")
+        self.handle = h
+        self.n = n
+
+    def run(self, d_grid, d_llr, d_message, d_status, d_csi, d_meas=None, d_ch_est=None, stream=None):
+        """d_llr int8, d_message uint8, d_status [n] u32 (both None: the receiver launch alone), d_csi [n] Pf2Csi; d_meas [n][4]
+        PuschChestMeas or None; d_ch_est or None."""
+        _check(self.ctx.lib.nrphy_pf2_run(self.handle, _dptr(d_grid), _dptr(d_llr), _dptr(d_message), _dptr(d_status), _dptr(d_csi),
+                                          _dptr(d_meas), _dptr(d_ch_est), _stream(stream)), "nrphy_pf2_run")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.ctx.lib.nrphy_pf2_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class UciDecoderPlan:
     """nrphy_uci_decoder_plan: a batch of UCI messages of any sizes (short blocks and polar); run() writes every message, one
     bit per byte, and [n] uint32 statuses in one launch."""
@@ -836,6 +898,19 @@ def prach_window_width(cfg):
 def pucch_validate(cfg, grid_nof_ports, grid_nof_subc):
     """nrphy_pucch_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
     return int(load().nrphy_pucch_validate(C.byref(cfg), grid_nof_ports, grid_nof_subc))
+
+
+def pf2_validate(cfg, grid_nof_ports, grid_nof_subc):
+    """nrphy_pf2_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_pf2_validate(C.byref(cfg), grid_nof_ports, grid_nof_subc))
+
+
+def pf2_sizes(cfg):
+    """nrphy_pf2_sizes: (E soft bits, A payload bits), or None for a configuration the validator refuses (host only)."""
+    e, a = C.c_uint32(), C.c_uint32()
+    if load().nrphy_pf2_sizes(C.byref(cfg), C.byref(e), C.byref(a)) != abi.OK:
+        return None
+    return int(e.value), int(a.value)
 
 
 def pusch_chest_validate(cfg, grid_nof_ports, grid_nof_subc):
