@@ -1,6 +1,6 @@
 #!/bin/bash
 # PMC counters of the LDPC decoder launch (BASELINE config 5, 64 slots, 8 fixed iterations) with the library as built and
-# the environment given: rx_pmc_env.sh <outdir> [NAME=VALUE ...]   (e.g. NRPHY_DECODER_LDSMSG=0 for the record kernel)
+# the environment given: rx_pmc_env.sh <outdir> [NAME=VALUE ...]   (e.g. NRPHY_DECODER_LDSMSG=0 for the messages in the slots)
 OUT=$(realpath -m "$1"); shift; mkdir -p "$OUT"; ROOT=$PWD
 for kv in "$@"; do export "$kv"; done
 cd /tmp && export TMPDIR=/tmp

@@ -15,13 +15,13 @@
 // written only by the thread that owns the check (coalesced, L2 resident; the next layer's record is prefetched).
 // This is the reference's arithmetic re-indexed by check instead of by variable position; the values are the same.
 //
-// Three forms of the kernel, same values in each: one check per lane (ldpc_decode_kernel: odd lifting sizes); two checks per
-// lane in packed 16-bit arithmetic (ldpc_decode_pairs_kernel); and two checks per lane with the messages of every edge kept in
-// LDS and the soft-bit addresses read from a table (ldpc_decode_pairs_lm_kernel: codeblocks that run few layers -- high code
-// rates --, decided per codeblock; see "messages kept per edge in LDS" below).
+// Two forms, same values in each.  One check per lane with the compressed records above (ldpc_decode_kernel: odd lifting
+// sizes and Zc = 2).  Two checks per lane in packed 16-bit arithmetic (every other even lifting size), with the message of every
+// edge kept as a byte and the soft-bit addresses read from a table, one kernel per base graph and per place the messages live in:
+// behind the soft bits in LDS when the layers a launch expects leave room there (ldpc_decode_msg_bg{1,2}_kernel; a codeblock
+// that runs more layers than that takes its slot), else in the codeblock's slot of the caller's scratch
+// (ldpc_decode_msg_bg{1,2}_slot_kernel).  See "Two checks per lane" below.
 #include "bits_device.h"
-
-#include <type_traits>
 
 namespace nrphy {
 
@@ -48,7 +48,7 @@ __device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c)
   return r;
 }
 
-// LDS accesses of the pair kernels by LDS address (an integer): through a pointer into the kernel's LDS array every access
+// LDS accesses of the two-checks-per-lane kernels by LDS address (an integer): through a pointer into the kernel's LDS array every access
 // carries an addition of the array's (link-time) address -- "v_add 0, x" once per soft bit read and written.
 typedef __attribute__((address_space(3))) int8_t   lds_i8_t;
 typedef __attribute__((address_space(3))) uint32_t lds_u32_t;
@@ -169,20 +169,9 @@ __device__ __forceinline__ uint2 process_layer(uint32_t deg, int8_t* soft, const
 // ---- Two checks per lane ----------------------------------------------------------------------------------------------
 // For an even lifting size thread j owns checks j and j + Zc / 2 of every layer and carries their values as the two 16-bit
 // halves of one register: the arithmetic of the min-sum rule (subtractions, clamps, magnitudes, the two running minima as
-// 16-bit keys, the promotion of the new soft bit) is one packed instruction for both checks, the sign and minimum-owner masks
-// of an edge come out of the record with two packed shifts for both, and the second check's soft-bit address is the first's
-// plus or minus Zc / 2.  Per check and edge that is about 22 vector instructions instead of 31 (PMC: 93.8 k instead of 114.7 k
-// per config-3 codeblock and 8 iterations; the per-layer work of a lane -- record, table look-ups, parity -- does not shrink)
-// -- the kernel is bound by vector issue -- for exactly the same values: every operation is the 16-bit image of the one in
-// process_check (values stay within
-// +-633, keys within 16 bits because magnitudes beyond 255 -- an infinite soft bit's -- are clamped to 255, which like them is
-// above LLR_MAX and never a minimum).
-//
-// Record of a pair of checks (16 bytes: the size of two single records):
-//   x = m1A | m2A << 8 | m1B << 16 | m2B << 24     scaled minima of check A (= j) and B (= j + Zc / 2)
-//   y = idxA | idxB << 16                           edge holding the minimum (0xFF: none)
-//   z = signs of edges 0 .. 15, A in the low half, B in the high half (bit t: message of edge t is negative)
-//   w = the same for edges 16 .. (at most 19 edges per check)
+// 16-bit keys, the promotion of the new soft bit) is one packed instruction for both checks -- the kernel is bound by vector
+// issue -- for exactly the same values: every operation is the 16-bit image of the one in process_check (values stay within
+// +-633, and a key holds ten bits of magnitude over five of edge index).
 typedef short          s16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ s16x2 as_s16x2(uint32_t x)
@@ -205,46 +194,10 @@ __device__ __forceinline__ s16x2 splat_s16(int v)
 {
   return s16x2{(short)v, (short)v};
 }
-// 0xFFFF in every half of `word` whose bit `bit` (< 16) is set, else 0: two packed shifts.
-__device__ __forceinline__ uint32_t half_masks(uint32_t word, uint32_t bit)
-{
-  return as_word((as_s16x2(word) << splat_s16((int)(15u - bit))) >> splat_s16(15));
-}
 __device__ __forceinline__ s16x2 clamp_s16x2(s16x2 x, int lim)
 {
   return __builtin_elementwise_max(__builtin_elementwise_min(x, splat_s16(lim)), splat_s16(-lim));
 }
-// llr_sub for both halves (a: soft bits, c: old messages).
-__device__ __forceinline__ s16x2 llr_sub_pair(s16x2 a, s16x2 c)
-{
-  const s16x2 d   = clamp_s16x2(a - c, LLR_MAX_V);
-  const s16x2 big = a - clamp_s16x2(a, LLR_MAX_V); // 0, or +-1 for an infinite soft bit
-  return (big << splat_s16(9)) + d;
-}
-__device__ __forceinline__ s16x2 llr_sub_pair_first(s16x2 a)
-{
-  const s16x2 d = clamp_s16x2(a, LLR_MAX_V);
-  return ((a - d) << splat_s16(9)) + d;
-}
-
-// The messages of the pair on edge t from a record's fields: m1 / m2 = (m1A | m1B << 16) / (m2A | m2B << 16), hot0 / hot1 =
-// one-hot minimum owners, signs0 / signs1 = the record's z / w.
-template <uint32_t T>
-__device__ __forceinline__ s16x2 pair_message(uint32_t m1, uint32_t m2, uint32_t hot0, uint32_t hot1, uint32_t signs0, uint32_t signs1)
-{
-  const uint32_t sel = half_masks(T < 16u ? hot0 : hot1, T & 15u);
-  const uint32_t sg  = half_masks(T < 16u ? signs0 : signs1, T & 15u);
-  const uint32_t mag = __builtin_amdgcn_bitop3_b32(sel, m2, m1, 0xCA);
-  return as_s16x2(mag ^ sg) - as_s16x2(sg);
-}
-__device__ __forceinline__ void pair_one_hot(uint32_t y, uint32_t& hot0, uint32_t& hot1)
-{
-  const uint32_t ia = y & 0xFFu, ib = (y >> 16) & 0xFFu;
-  const uint32_t ha = ia < 32u ? 1u << ia : 0u, hb = ib < 32u ? 1u << ib : 0u;
-  hot0              = (ha & 0xFFFFu) | (hb << 16);
-  hot1              = (ha >> 16) | (hb & 0xFFFF0000u);
-}
-
 // The soft bits (or messages) of both checks on edges B .. B + 9 of a layer, read together and combined into packed pairs
 // (low halves: A | B << 16).  The empty asm statement makes all twenty values be in their registers at one point: without it
 // the compiler's scheduler sinks every pair of LDS reads to its use and reuses two temporaries -- a chain of DEG dependent LDS
@@ -273,112 +226,17 @@ __device__ __forceinline__ void load_pairs10(uint32_t (&out)[DEG], AddrA addr_a,
 // (ds_read_i8_d16 / _d16_hi would place the two bytes in the halves of one register without the v_perm -- not on this device:
 // with SRAM ECC enabled, as on MI300 / MI355X, a d16 load writes the whole register and clears the other half, which is why the
 // compiler never selects them; tried in assembly in round 4, wrong results.)
-template <uint32_t DEG, uint32_t T, bool FIRST>
-struct PairEdges {
-  // Pass 1 over edges T .. DEG - 1: v2c messages, running minima, sign bits.
-  static __device__ __forceinline__ void forward(const uint32_t (&a)[DEG], uint32_t (&x)[DEG], uint32_t m1, uint32_t m2, uint32_t hot0,
-                                                 uint32_t hot1, uint32_t z, uint32_t w, uint32_t& k1, uint32_t& k2, uint32_t& nz,
-                                                 uint32_t& nw)
-  {
-    if constexpr (T < DEG) {
-      const s16x2 v = FIRST ? llr_sub_pair_first(as_s16x2(a[T]))
-                            : llr_sub_pair(as_s16x2(a[T]), pair_message<T>(m1, m2, hot0, hot1, z, w));
-      x[T]          = as_word(v);
-      const s16x2    mag = __builtin_elementwise_max(v, splat_s16(0) - v);
-      const uint32_t cap = as_word(__builtin_elementwise_min(as_u16x2(as_word(mag)), u16x2{255, 255}));
-      const uint32_t key = (cap << 8) | (T * 0x00010001u);
-      k2 = as_word(__builtin_elementwise_min(__builtin_elementwise_max(as_u16x2(key), as_u16x2(k1)), as_u16x2(k2)));
-      k1 = as_word(__builtin_elementwise_min(as_u16x2(key), as_u16x2(k1)));
-      const uint32_t neg = as_word(as_u16x2(as_word(v)) >> u16x2{15, 15}); // 1 in a half whose value is negative
-      if (T < 16u) {
-        nz |= neg << (T & 15u);
-      } else {
-        nw |= neg << (T & 15u);
-      }
-      PairEdges<DEG, T + 1, FIRST>::forward(a, x, m1, m2, hot0, hot1, z, w, k1, k2, nz, nw);
-    }
-  }
-  // Pass 2: new soft bits = new message + v2c message, promoted, back to where they came from.
-  static __device__ __forceinline__ void backward(const uint32_t (&addr1)[DEG], const uint32_t (&addr2)[DEG],
-                                                  const uint32_t (&x)[DEG], uint32_t m1, uint32_t m2, uint32_t hot0, uint32_t hot1,
-                                                  uint32_t z, uint32_t w)
-  {
-    if constexpr (T < DEG) {
-      const s16x2    sum = pair_message<T>(m1, m2, hot0, hot1, z, w) + as_s16x2(x[T]);
-      const uint32_t out = as_word(clamp_s16x2(sum, LLR_INF_V));
-      lds_store_i8(addr1[T], out);
-      lds_store_i8(addr2[T], out >> 16);
-      PairEdges<DEG, T + 1, FIRST>::backward(addr1, addr2, x, m1, m2, hot0, hot1, z, w);
-    }
-  }
-};
 
-// Checks j and j + half of one layer (degree DEG); j < half = Zc / 2; jm = j - Zc (wraps).
-template <uint32_t DEG, bool FIRST>
-__device__ __forceinline__ uint4 process_check_pair(uint32_t soft, const uint8_t* scaled, const NRPHY_CONSTANT uint32_t* edge,
-                                                    uint32_t half, uint32_t minus_half, uint32_t j, uint32_t jm, uint4 old)
-{
-  uint32_t addr1[DEG], addr2[DEG], a[DEG], x[DEG];
-#pragma unroll
-  for (uint32_t t = 0; t != DEG; ++t) {
-    const uint32_t e = edge[t], shift = e & 0xFFFFu;
-    const uint32_t pos = min(j + shift, jm + shift);   // (j + shift) mod Zc
-    addr1[t]           = (soft + (e >> 16)) + pos;     // LDS address (the graph holds node * Zc; the sum in brackets is scalar)
-    addr2[t]           = addr1[t] + (pos < half ? half : minus_half); // (j + Zc / 2 + shift) mod Zc
-  }
-  load_pairs10<DEG, 0>(a, [&](uint32_t t) { return addr1[t]; }, [&](uint32_t t) { return addr2[t]; });
-  load_pairs10<DEG, 10>(a, [&](uint32_t t) { return addr1[t]; }, [&](uint32_t t) { return addr2[t]; });
-  uint32_t m1 = 0, m2 = 0, hot0 = 0, hot1 = 0;
-  if (!FIRST) {
-    m1 = old.x & 0x00FF00FFu;
-    m2 = (old.x >> 8) & 0x00FF00FFu;
-    pair_one_hot(old.y, hot0, hot1);
-  }
-  uint32_t k1 = (((uint32_t)LLR_MAX_V << 8) | 0xFFu) * 0x00010001u, k2 = k1, nz = 0, nw = 0;
-  PairEdges<DEG, 0, FIRST>::forward(a, x, m1, m2, hot0, hot1, old.z, old.w, k1, k2, nz, nw);
-  // scale_llr of the four minima through the table; sign of a message = parity of the OTHER signs
-  const uint32_t s1a = scaled[(k1 >> 8) & 0xFFu], s1b = scaled[k1 >> 24], s2a = scaled[(k2 >> 8) & 0xFFu], s2b = scaled[k2 >> 24];
-  const uint32_t n1 = s1a | (s1b << 16), n2 = s2a | (s2b << 16);
-  const uint32_t sa = (nz & 0xFFFFu) | (nw << 16), sb = (nz >> 16) | (nw & 0xFFFF0000u);
-  const uint32_t flip = ((0u - (__popc(sa) & 1u)) & 0xFFFFu) | ((0u - (__popc(sb) & 1u)) << 16);
-  constexpr uint32_t ZBITS = DEG >= 16u ? 0xFFFFu : (1u << DEG) - 1u, WBITS = DEG > 16u ? (1u << (DEG - 16u)) - 1u : 0u;
-  nz ^= flip & (ZBITS * 0x00010001u);
-  nw ^= flip & (WBITS * 0x00010001u);
-  const uint4 mine = make_uint4(n1 | (n2 << 8), k1 & 0x00FF00FFu, nz, nw);
-  uint32_t    nh0, nh1;
-  pair_one_hot(mine.y, nh0, nh1);
-  PairEdges<DEG, 0, FIRST>::backward(addr1, addr2, x, n1, n2, nh0, nh1, nz, nw);
-  return mine;
-}
-
-template <bool FIRST>
-__device__ __forceinline__ uint4 process_layer_pair(uint32_t deg, uint32_t soft, const uint8_t* scaled,
-                                                    const NRPHY_CONSTANT uint32_t* edge, uint32_t half, uint32_t minus_half, uint32_t j,
-                                                    uint32_t jm, uint4 old)
-{
-  switch (deg) {
-    case 3: return process_check_pair<3, FIRST>(soft, scaled, edge, half, minus_half, j, jm, old);
-    case 4: return process_check_pair<4, FIRST>(soft, scaled, edge, half, minus_half, j, jm, old);
-    case 5: return process_check_pair<5, FIRST>(soft, scaled, edge, half, minus_half, j, jm, old);
-    case 6: return process_check_pair<6, FIRST>(soft, scaled, edge, half, minus_half, j, jm, old);
-    case 7: return process_check_pair<7, FIRST>(soft, scaled, edge, half, minus_half, j, jm, old);
-    case 8: return process_check_pair<8, FIRST>(soft, scaled, edge, half, minus_half, j, jm, old);
-    case 9: return process_check_pair<9, FIRST>(soft, scaled, edge, half, minus_half, j, jm, old);
-    case 10: return process_check_pair<10, FIRST>(soft, scaled, edge, half, minus_half, j, jm, old);
-    default: return process_check_pair<19, FIRST>(soft, scaled, edge, half, minus_half, j, jm, old);
-  }
-}
-
-// ---- Two checks per lane, check-to-variable messages kept per edge in LDS ------------------------------------------------
-// When the layers a codeblock needs are few enough (high code rates: BASELINE config 5 runs 4 layers of degree 19), the
-// messages of every edge fit the LDS next to the soft bits: one byte per (edge, check), the messages of two edges and the
-// two checks of a lane in one word -- bytes (edge t: check j, check j + Zc / 2; edge t + 1: the same), word r = t / 2 of a
-// layer at its row r, lane j.  The edge passes then read the old message instead of rebuilding it from a compressed record
-// (7 vector instructions per pair of checks and edge in the forward pass), the sign of a new message comes from the sign of
-// the variable-to-check value it answers (new = P * sign(x) * magnitude with P the parity of all signs, folded into the two
-// magnitudes once per layer), no record is packed, stored or prefetched, and the scaling of the minima is arithmetic where the
-// host has checked that it equals the table (a table look-up is one more LDS round trip per layer, and under this kernel's
-// LDS load a round trip costs several hundred cycles).  Same values as process_check_pair, operation for operation.
+// ---- Messages kept per edge ---------------------------------------------------------------------------------------------
+// With two checks per lane the check-to-variable messages are not compressed into records: one byte per (edge, check), the
+// messages of two edges and the two checks of a lane in one word -- bytes (edge t: check j, check j + Zc / 2; edge t + 1: the
+// same), word r = t / 2 of a layer at its row r, lane j.  When the layers a codeblock needs are few enough (high code rates:
+// BASELINE config 5 runs 4 layers of degree 19) the words fit the LDS next to the soft bits, else they live in the codeblock's
+// slot (MsgLds / MsgSlot below).  The edge passes read the old message as it is, the sign of a new message comes from the
+// sign of the variable-to-check value it answers (new = P * sign(x) * magnitude with P the parity of all signs, folded into
+// the two magnitudes once per layer), and the scaling of the minima is arithmetic where the host has checked that it equals
+// the table (a table look-up is one more LDS round trip per layer, and under this kernel's LDS load a round trip costs several
+// hundred cycles).  Same values as process_check, operation for operation in its 16-bit image.
 __device__ __forceinline__ uint32_t pk_mad_i16(uint32_t a, uint32_t b, uint32_t c)
 {
   uint32_t r;
@@ -457,9 +315,6 @@ struct Trace;
 #define TR(k)
 #endif
 
-#ifndef NRPHY_DEC_SELECT_BY_MASK
-#define NRPHY_DEC_SELECT_BY_MASK 0 // 1: the message magnitude selected through a full-width mask (the form until late round 4), for A/B
-#endif
 template <uint32_t DEG, uint32_t T, bool FIRST>
 struct LmEdges {
   static __device__ __forceinline__ void forward(const uint32_t (&c)[DEG], uint32_t (&x)[DEG], uint32_t k512, uint32_t& k1, uint32_t& k2,
@@ -484,23 +339,17 @@ struct LmEdges {
       LmEdges<DEG, T + 1, FIRST>::forward(c, x, k512, k1, k2, par);
     }
   }
-  // The new message of the pair on edge T and the soft bits it leads to; m1 / m2: the scaled minima of the pair with the
-  // parity of the signs applied (negative when odd).
+  // The new message of the pair on edge T and the soft bits it leads to; m1: the scaled first minima of the pair with the
+  // parity of the signs applied (negative when odd), m2: the second minima, likewise, minus the first.
   static __device__ __forceinline__ uint32_t answer(const uint32_t (&addr1)[DEG], const uint32_t (&addr2)[DEG],
                                                     const uint32_t (&x)[DEG], uint32_t m1, uint32_t m2, uint32_t hot0, uint32_t hot1)
   {
     const uint32_t s   = as_word(as_s16x2(x[T]) >> splat_s16(15)) | 0x00010001u; // -1 / +1: the sign of the value answered
-#if NRPHY_DEC_SELECT_BY_MASK
-    const uint32_t sel = half_masks(T < 16u ? hot0 : hot1, T & 15u);
-    const uint32_t mag = __builtin_amdgcn_bitop3_b32(sel, m2, m1, 0xCA);
-#else
-    // the second minimum for the edge that holds the first: m1 + bit * (m2 - m1) in every half, `m2` arriving here as the
-    // difference (process_check_pair_lm) -- a shift and a mask (plain VOP2) and one packed multiply-add instead of two packed
-    // shifts for a full-width mask and a select
+    // the second minimum for the edge that holds the first: m1 + bit * m2 in every half -- a shift and a mask (plain VOP2) and
+    // one packed multiply-add instead of two packed shifts for a full-width mask and a select
     const uint32_t bit = ((T < 16u ? hot0 : hot1) >> (T & 15u)) & 0x00010001u;
     uint32_t       mag;
     asm("v_pk_mad_u16 %0, %1, %2, %3" : "=v"(mag) : "v"(bit), "v"(m2), "v"(m1));
-#endif
     const s16x2    msg = as_s16x2(as_word(as_u16x2(mag) * as_u16x2(s)));
     const uint32_t out = as_word(clamp_s16x2(msg + as_s16x2(x[T]), LLR_INF_V));
     lds_store_i8(addr1[T], out);
@@ -610,11 +459,7 @@ __device__ __forceinline__ void process_check_pair_lm(const Msg& msg, const Scal
   key_one_hot<DEG>(k1, hot0, hot1);
   ahead();
   TR(5);
-#if NRPHY_DEC_SELECT_BY_MASK
-  LmEdges<DEG, 0, FIRST>::backward(msg, addr1, addr2, x, m1, m2, hot0, hot1);
-#else
   LmEdges<DEG, 0, FIRST>::backward(msg, addr1, addr2, x, m1, as_word(as_s16x2(m2) - as_s16x2(m1)), hot0, hot1);
-#endif
   TR(6);
 }
 
@@ -674,11 +519,11 @@ __device__ __forceinline__ uint32_t hard_word(const int8_t* soft, uint32_t w, ui
   return word;
 }
 
-// The check records of a codeblock live in a slot of the caller's scratch.  A batch larger than the pool shares it: a
-// workgroup claims a free slot (one flag word per slot) when it starts and gives it back when it is done.  Workgroup b first
-// tries slot b mod nof_slots -- free for the workgroups that start a launch, and usually given back by workgroup
-// b - nof_slots by the time b starts -- and walks on from there.  The pool holds at least as many slots as workgroups fit the
-// device at once, so a free one always exists and the search ends; should that bound ever be wrong the search gives up
+// The check records of a codeblock (or its messages per edge) live in a slot of the caller's scratch.  A batch larger than the
+// pool shares it: a workgroup claims a free slot (one flag word per slot) when it starts and gives it back when it is done.
+// Workgroup b first tries slot b mod nof_slots -- free for the workgroups that start a launch, and usually given back by
+// workgroup b - nof_slots by the time b starts -- and walks on from there.  The pool holds at least as many slots as workgroups
+// fit the device at once, so a free one always exists and the search ends; should that bound ever be wrong the search gives up
 // after a fixed number of probes and the codeblock is reported as not decoded (never a hang).
 //
 // Handing a slot from one workgroup to the next needs no cache maintenance: a workgroup never reads a record it has not
@@ -706,22 +551,86 @@ __device__ __forceinline__ void store_record(uint2* rec, uint2 v)
   __hip_atomic_store(reinterpret_cast<uint64_t*>(rec), (uint64_t)v.x | ((uint64_t)v.y << 32), __ATOMIC_RELAXED,
                      __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ void store_record(uint4* rec, uint4 v) // a pair of checks: two write-through stores
+
+// Early stop (ldpc_decoder_impl.cpp:118-126): every hard bit decided and the CRC of the significant bits zero, i.e. the message
+// a multiple of the generator polynomial (crc_at_end: the CRC alone decides).  Thread w owns hard-bit word w; the tables of its
+// weight x^(bits after the word) mod g come from the host.  K: bits of the message with its filler bits, n_msg: without,
+// nw_k: words of K bits.  s_flag[1] and s_flag[2] are the workgroup's scratch: a barrier before the next call.
+__device__ __forceinline__ bool message_checks_out(const LdpcDecodeLaunch& p, const int8_t* soft, uint32_t* s_flag, uint32_t j, uint32_t T,
+                                                   uint32_t K, uint32_t n_msg, uint32_t nw_k)
 {
-  uint64_t* q = reinterpret_cast<uint64_t*>(rec);
-  __hip_atomic_store(q, (uint64_t)v.x | ((uint64_t)v.y << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __hip_atomic_store(q + 1, (uint64_t)v.z | ((uint64_t)v.w << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (j < 2) {
+    s_flag[1 + j] = 0;
+  }
+  lds_barrier();
+  bool     zero_seen = false;
+  uint32_t part      = 0;
+  for (uint32_t w = j; w < nw_k; w += T) { // thread w owns hard-bit word w (one trip, two with two checks per lane)
+    const uint32_t word = hard_word(soft, w, K, zero_seen);
+    if (32u * w < n_msg) {
+      const uint32_t w_bits = n_msg - 32u * w < 32u ? n_msg - 32u * w : 32u;
+      // word * x^(bits after it) mod g: eight nibble tables of this word (L2), independent look-ups
+      const uint32_t  v = word >> (32u - w_bits);
+      const uint32_t* t = p.crc_weight + (size_t)w * DEC_CRC_TABLE_WORDS;
+      part ^= t[v & 15u] ^ t[16u + ((v >> 4) & 15u)] ^ t[32u + ((v >> 8) & 15u)] ^ t[48u + ((v >> 12) & 15u)] ^
+              t[64u + ((v >> 16) & 15u)] ^ t[80u + ((v >> 20) & 15u)] ^ t[96u + ((v >> 24) & 15u)] ^ t[112u + (v >> 28)];
+    }
+  }
+  for (int o = WAVE / 2; o != 0; o >>= 1) {
+    part ^= __shfl_xor(part, o);
+  }
+  if ((j & (WAVE - 1)) == 0 && part != 0) {
+    atomicXor(&s_flag[2], part);
+  }
+  if (zero_seen) {
+    atomicOr(&s_flag[1], 1u);
+  }
+  lds_barrier();
+  return (s_flag[1] == 0 || p.crc_at_end) && s_flag[2] == 0;
 }
 
-// PAIR: two checks per lane (even lifting sizes: Zc / 2 threads per codeblock), see process_check_pair.
-// LM: the check-to-variable messages kept per edge instead of as compressed records -- behind the soft bits in LDS when the
-// layers a codeblock runs leave room for them there, else in the codeblock's slot of the caller's scratch (decided per
-// codeblock; the record path is not part of such a kernel).
-// MAXDEG (LM only): the largest row degree of the base graph -- 19 (base graph 1) or 10 (base graph 2).
-// SLOT_ONLY (LM only): a launch without room for messages in LDS -- every codeblock keeps them in its slot, the first rows of a
-// layer's old messages requested a layer ahead; otherwise the launch's LDS was sized for the messages of the expected layers and
-// only a codeblock that runs more than those (stale soft bits in a HARQ buffer) takes its slot, without the requests ahead.
-template <bool PAIR, bool LM = false, uint32_t MAXDEG = 19, bool SLOT_ONLY = false>
+// Gives the workgroup's slot (*s_slot, in LDS) back once every store of this workgroup to it has completed (see acquire_slot):
+// every wave waits for its own outstanding stores -- s_waitcnt vmcnt(0), written out because a workgroup-scope release fence
+// only has to order them with respect to this workgroup (it compiles to a wait for LDS traffic) -- then the barrier, then the
+// flag.
+__device__ __forceinline__ void release_slot(uint32_t* flags, const uint32_t* s_slot, uint32_t j)
+{
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __syncthreads();
+  if (j == 0) {
+    __hip_atomic_store(&flags[*s_slot], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// Hard bits of the message (K bits, nw_k words), packed MSB first (all-zero input: soft <= 0 everywhere, every bit one as in
+// ldpc_decoder_impl.cpp:91-96).
+__device__ __forceinline__ void write_hard_bits(uint8_t* out, const int8_t* soft, uint32_t j, uint32_t T, uint32_t K, uint32_t nw_k)
+{
+  for (uint32_t w = j; w < nw_k; w += T) {
+    bool           unused = false;
+    const uint32_t word   = hard_word(soft, w, K, unused) & topmask(K - 32u * w < 32u ? K - 32u * w : 32u);
+    const uint32_t nbytes = (K + 7u) / 8u;
+#pragma unroll
+    for (uint32_t b = 0; b != 4; ++b) {
+      if (4u * w + b < nbytes) {
+        out[4u * w + b] = (uint8_t)(word >> (24u - 8u * b));
+      }
+    }
+  }
+}
+
+// The two forms of the decoder.  RECORDS: one check per lane (Zc threads per codeblock), the messages as compressed check
+// records in the codeblock's slot.  MESSAGES: two checks per lane (even lifting sizes: Zc / 2 threads per codeblock), the
+// messages kept per edge -- behind the soft bits in LDS when the layers a codeblock runs leave room for them there, else in
+// the codeblock's slot of the caller's scratch (decided per codeblock).
+enum class Form { RECORDS, MESSAGES };
+
+// MAXDEG (MESSAGES only): the largest row degree of the base graph -- 19 (base graph 1) or 10 (base graph 2).
+// SLOT_ONLY (MESSAGES only): a launch without room for messages in LDS -- every codeblock keeps them in its slot, the first rows
+// of a layer's old messages requested a layer ahead; otherwise the launch's LDS was sized for the messages of the expected layers
+// and only a codeblock that runs more than those (stale soft bits in a HARQ buffer) takes its slot, without the requests ahead.
+template <Form FORM, uint32_t MAXDEG = 19, bool SLOT_ONLY = false>
 __device__ __forceinline__ void ldpc_decode_body(const LdpcDecodeLaunch& p)
 {
   // All of the kernel's LDS is the launch's dynamic allocation, the soft bits at its start: with a static variable in front
@@ -739,7 +648,8 @@ __device__ __forceinline__ void ldpc_decode_body(const LdpcDecodeLaunch& p)
   const auto*   graph  = to_constant(p.graph); // wave-uniform reads: scalar loads
   const int8_t* llr    = p.llr + (size_t)blockIdx.x * p.llr_stride;
   const uint32_t half = zc >> 1;
-  const bool    active = PAIR ? j < half : j < zc;
+  constexpr bool LM    = FORM == Form::MESSAGES;
+  const bool    active = LM ? j < half : j < zc;
   const bool    pooled = p.nof_slots < gridDim.x; // fewer slots than codeblocks: claim one
   // With two checks per lane the messages may live in LDS instead (decided below, once the layers are known): the claim
   // then waits until it is known to be needed; otherwise its latency hides behind the loads.
@@ -749,7 +659,8 @@ __device__ __forceinline__ void ldpc_decode_body(const LdpcDecodeLaunch& p)
   }
 
   // load_soft_bits (ldpc_decoder_impl.cpp:128-164): two punctured nodes, then the input.  The last non-zero soft bit
-  // decides how many layers take part (:88-116).
+  // decides how many layers take part (:88-116).  (Inline, unlike the stages above: as a function of its own this one changed
+  // the instruction schedule of the record kernel and of the two slot kernels.)
   uint32_t       last_nz   = 0;
   const uint32_t T         = blockDim.x;
   const uint32_t clamp_end = (p.nof_llr / zc) * zc; // whole nodes
@@ -800,7 +711,7 @@ __device__ __forceinline__ void ldpc_decode_body(const LdpcDecodeLaunch& p)
   if (((reinterpret_cast<uintptr_t>(llr) & 15u) | (zc & 7u)) == 0) {
     // sixteen soft bits per lane and load, up to twelve (four) loads of a lane in flight: the whole codeblock in one or two trips to
     // memory (four-byte loads unrolled by four took eight trips for a config-3 codeblock)
-    constexpr uint32_t U   = PAIR ? 12 : 4; // (the one-check kernel runs at 64 registers)
+    constexpr uint32_t U   = LM ? 12 : 4; // (the one-check kernel runs at 64 registers)
     const uint32_t     nq  = p.nof_llr >> 4;
     const uint4*       src = reinterpret_cast<const uint4*>(llr);
     uint4*             dst = reinterpret_cast<uint4*>(soft + 2u * zc);
@@ -869,10 +780,8 @@ __device__ __forceinline__ void ldpc_decode_body(const LdpcDecodeLaunch& p)
   const uint32_t nw_k       = (K + 31u) >> 5;
   uint32_t       iterations = 0;
 
-  // Early stop: the message is a multiple of the generator polynomial.  Thread w owns hard-bit word w; the tables of its
-  // weight x^(bits after the word) mod g come from the host.
-  const uint32_t n_msg  = K - p.nof_filler;
-  const uint32_t jm = j - zc;
+  const uint32_t n_msg  = K - p.nof_filler; // what the CRC covers
+  const uint32_t jm = j - zc;               // (one check per lane) see process_check
 
   if (input_size != 0) { // workgroup-uniform
     uint32_t cb_len = input_size + 2u * zc;
@@ -907,10 +816,7 @@ __device__ __forceinline__ void ldpc_decode_body(const LdpcDecodeLaunch& p)
     Trace* tr = nullptr;
 #endif
 
-    typedef typename std::conditional<PAIR, uint4, uint2>::type Record; // a pair of checks per lane has a record of twice the size
-    Record*        recs        = reinterpret_cast<Record*>(slot_mem);
-    const uint32_t rec_stride  = PAIR ? half : zc;                       // records of one layer
-    const uint32_t minus_half  = 0u - half;
+    uint2* const recs = reinterpret_cast<uint2*>(slot_mem); // (one check per lane) [layer][check]
     constexpr uint32_t NQ = MAXDEG > 12u ? 5u : 3u; // rows of four soft-bit addresses a layer can have
     constexpr uint32_t PF  = SLOT_ONLY ? (MAXDEG > 12u ? 5u : 3u) : 0u; // rows of messages requested a layer ahead (messages in the slot)
     constexpr uint32_t PFA = PF != 0u ? PF : 1u;    // (array extent)
@@ -1034,7 +940,7 @@ __device__ __forceinline__ void ldpc_decode_body(const LdpcDecodeLaunch& p)
           wrap_pre[r] = pre[r];
         }
       } else {
-        Record next = {};
+        uint2 next = {};
         if (it != 0 && active) {
           next = recs[j];
         }
@@ -1042,58 +948,24 @@ __device__ __forceinline__ void ldpc_decode_body(const LdpcDecodeLaunch& p)
         for (uint32_t m = 0; m != nof_layers; ++m) {
           const uint32_t e2  = graph->row_ptr[m + 2u]; // (the array has a spare element) a layer ahead: off the critical path
           const uint32_t deg = e1 - e0;
-          const Record   old = next;
+          const uint2    old = next;
           if (it != 0 && active && m + 1u != nof_layers) {
-            next = recs[(size_t)(m + 1u) * rec_stride + j];
+            next = recs[(size_t)(m + 1u) * zc + j];
           }
           if (active) {
             const auto* edge = graph->edge + e0;
-            if constexpr (PAIR) {
-              const uint4 mine = it == 0 ? process_layer_pair<true>(deg, soft_a, s_scaled, edge, half, minus_half, j, jm, old)
-                                         : process_layer_pair<false>(deg, soft_a, s_scaled, edge, half, minus_half, j, jm, old);
-              store_record(&recs[(size_t)m * rec_stride + j], mine);
-            } else {
-              const uint2 mine = it == 0 ? process_layer<true>(deg, soft, s_scaled, edge, zc, j, jm, old)
-                                         : process_layer<false>(deg, soft, s_scaled, edge, zc, j, jm, old);
-              store_record(&recs[(size_t)m * rec_stride + j], mine);
-            }
+            const uint2 mine = it == 0 ? process_layer<true>(deg, soft, s_scaled, edge, zc, j, jm, old)
+                                       : process_layer<false>(deg, soft, s_scaled, edge, zc, j, jm, old);
+            store_record(&recs[(size_t)m * zc + j], mine);
           }
           lds_barrier();
           e0 = e1;
           e1 = e2;
         }
       }
-      // Early stop (ldpc_decoder_impl.cpp:118-126): every hard bit decided and the CRC of the significant bits zero.
-      // crc_at_end (pusch_codeblock_decoder.cpp:59-68): no check until the last iteration, then the CRC alone decides.
+      // Early stop; crc_at_end (pusch_codeblock_decoder.cpp:59-68): no check until the last iteration.
       if (p.crc_order != 0 && (!p.crc_at_end || it + 1u == max_iterations)) {
-        if (j < 2) {
-          s_flag[1 + j] = 0;
-        }
-        lds_barrier();
-        bool     zero_seen = false;
-        uint32_t part      = 0;
-        for (uint32_t w = j; w < nw_k; w += T) { // thread w owns hard-bit word w (one trip, two with two checks per lane)
-          const uint32_t word = hard_word(soft, w, K, zero_seen);
-          if (32u * w < n_msg) {
-            const uint32_t w_bits = n_msg - 32u * w < 32u ? n_msg - 32u * w : 32u;
-            // word * x^(bits after it) mod g: eight nibble tables of this word (L2), independent look-ups
-            const uint32_t  v = word >> (32u - w_bits);
-            const uint32_t* t = p.crc_weight + (size_t)w * DEC_CRC_TABLE_WORDS;
-            part ^= t[v & 15u] ^ t[16u + ((v >> 4) & 15u)] ^ t[32u + ((v >> 8) & 15u)] ^ t[48u + ((v >> 12) & 15u)] ^
-                    t[64u + ((v >> 16) & 15u)] ^ t[80u + ((v >> 20) & 15u)] ^ t[96u + ((v >> 24) & 15u)] ^ t[112u + (v >> 28)];
-          }
-        }
-        for (int o = WAVE / 2; o != 0; o >>= 1) {
-          part ^= __shfl_xor(part, o);
-        }
-        if ((j & (WAVE - 1)) == 0 && part != 0) {
-          atomicXor(&s_flag[2], part);
-        }
-        if (zero_seen) {
-          atomicOr(&s_flag[1], 1u);
-        }
-        lds_barrier();
-        if ((s_flag[1] == 0 || p.crc_at_end) && s_flag[2] == 0) {
+        if (message_checks_out(p, soft, s_flag, j, T, K, n_msg, nw_k)) {
           iterations = it + 1u;
         }
         lds_barrier(); // the flags are cleared again at the top of the next check
@@ -1108,30 +980,9 @@ __device__ __forceinline__ void ldpc_decode_body(const LdpcDecodeLaunch& p)
 #endif
   }
   if (pooled && s_flag[3] != 0xFFFFFFFFu) { // workgroup-uniform
-    // Give the slot back once every record store of this workgroup has completed (see acquire_slot): every wave waits for
-    // its own outstanding stores -- s_waitcnt vmcnt(0), written out because a workgroup-scope release fence only has to
-    // order them with respect to this workgroup (it compiles to a wait for LDS traffic) -- then the barrier, then the flag.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    if (j == 0) {
-      __hip_atomic_store(&p.slot_flags[s_flag[3]], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    release_slot(p.slot_flags, &s_flag[3], j);
   }
-  // Hard bits of the message, packed MSB first (all-zero input: soft <= 0 everywhere, every bit one as in
-  // ldpc_decoder_impl.cpp:91-96).
-  uint8_t* out = p.out + (size_t)blockIdx.x * p.out_stride;
-  for (uint32_t w = j; w < nw_k; w += T) {
-    bool           unused = false;
-    const uint32_t word   = hard_word(soft, w, K, unused) & topmask(K - 32u * w < 32u ? K - 32u * w : 32u);
-    const uint32_t nbytes = (K + 7u) / 8u;
-#pragma unroll
-    for (uint32_t b = 0; b != 4; ++b) {
-      if (4u * w + b < nbytes) {
-        out[4u * w + b] = (uint8_t)(word >> (24u - 8u * b));
-      }
-    }
-  }
+  write_hard_bits(p.out + (size_t)blockIdx.x * p.out_stride, soft, j, T, K, nw_k);
   if (j == 0 && p.iterations) {
     p.iterations[blockIdx.x] = iterations;
   }
@@ -1142,43 +993,32 @@ __device__ __forceinline__ void ldpc_decode_body(const LdpcDecodeLaunch& p)
 
 __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(5))) void ldpc_decode_kernel(LdpcDecodeLaunch p)
 {
-  ldpc_decode_body<false>(p);
+  ldpc_decode_body<Form::RECORDS>(p);
 }
 
-// Two checks per lane: half the threads, registers for twice the values per lane (two address arrays, one packed value
-// array of 19 edges each).  Measured on one box, BASELINE config 5 with 8 fixed iterations, nrphy_pusch_decode_batch per 256
-// slots (profiles/r03_decoder_pairs.txt): one check per lane 6.14 ms; two per lane with the registers of 6 waves per SIMD
-// (80 VGPRs, 26 spilled) 5.69, of 5 waves (96, 19 spilled) 5.35, of 4 waves (128, 6 spilled) 5.24, of 3 (153, none) 5.27.
-#ifndef NRPHY_DECODER_PAIR_WAVES
-#define NRPHY_DECODER_PAIR_WAVES 4
-#endif
-__global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(NRPHY_DECODER_PAIR_WAVES))) void ldpc_decode_pairs_kernel(LdpcDecodeLaunch p)
-{
-  ldpc_decode_body<true>(p);
-}
-// ... with the messages kept per edge (LDS or slot), one kernel per base graph: base graph 1 has four rows of degree 19 --
-// two address arrays, a value array and the words of old messages for nineteen edges -- and runs with the registers of three
-// waves per SIMD (all that the LDS of a high-rate launch holds anyway: four workgroups of three waves per CU at BASELINE config
-// 5; with 128 registers the compiler serialises the LDS reads of an edge pass through two temporaries); base graph 2 stops at
-// degree 10 and fits the registers of four.
+// Two checks per lane: half the threads, registers for twice the values per lane.  One kernel per base graph and per place the
+// messages live in (LDS or slot): base graph 1 has four rows of degree 19 -- two address arrays, a value array and the words of
+// old messages for nineteen edges -- and runs with the registers of three waves per SIMD (all that the LDS of a high-rate launch
+// holds anyway: four workgroups of three waves per CU at BASELINE config 5; with 128 registers the compiler serialises the LDS
+// reads of an edge pass through two temporaries); base graph 2 stops at degree 10 and fits the registers of four.
 #ifndef NRPHY_DECODER_BG1_SLOT_WAVES
 #define NRPHY_DECODER_BG1_SLOT_WAVES 3
 #endif
 __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(3))) void ldpc_decode_msg_bg1_kernel(LdpcDecodeLaunch p)
 {
-  ldpc_decode_body<true, true, 19, false>(p);
+  ldpc_decode_body<Form::MESSAGES, 19, false>(p);
 }
 __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(NRPHY_DECODER_BG1_SLOT_WAVES))) void ldpc_decode_msg_bg1_slot_kernel(LdpcDecodeLaunch p)
 {
-  ldpc_decode_body<true, true, 19, true>(p);
+  ldpc_decode_body<Form::MESSAGES, 19, true>(p);
 }
 __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(4))) void ldpc_decode_msg_bg2_kernel(LdpcDecodeLaunch p)
 {
-  ldpc_decode_body<true, true, 10, false>(p);
+  ldpc_decode_body<Form::MESSAGES, 10, false>(p);
 }
 __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(4))) void ldpc_decode_msg_bg2_slot_kernel(LdpcDecodeLaunch p)
 {
-  ldpc_decode_body<true, true, 10, true>(p);
+  ldpc_decode_body<Form::MESSAGES, 10, true>(p);
 }
 
 constexpr uint32_t LDS_TAIL_BYTES = 16u + 128u;
@@ -1194,16 +1034,19 @@ hipError_t launch_ldpc_decode(const LdpcDecodeLaunch& p_in, uint32_t n_cb, hipSt
     return hipSuccess;
   }
   LdpcDecodeLaunch p = p_in;
-  // NRPHY_DECODER_PAIRS=0 (read when the context is created): one check per lane whatever the lifting size (A/B runs; the results are identical).
-  const bool         pairs     = (p.zc & 1u) == 0 && p.zc >= 4u && p.knob_pairs != 0;
-  const uint32_t     checks    = pairs ? p.zc / 2u : p.zc;
+  // Two checks per lane with the messages per edge for every even lifting size from 4 (the graph comes with its table of soft-bit
+  // addresses then), else one check per lane with records.  NRPHY_DECODER_PAIRS=0 (read when the context is created): one check
+  // per lane whatever the lifting size (tests and A/B runs; the results are identical).
+  const bool         msg       = (p.zc & 1u) == 0 && p.zc >= 4u && p.knob_pairs != 0;
+  if (msg && p.pair_addr == nullptr) {
+    return hipErrorInvalidValue;
+  }
+  const uint32_t     checks    = msg ? p.zc / 2u : p.zc;
   const uint32_t     threads   = ((checks + WAVE - 1) / WAVE) * WAVE;
   size_t             lds       = ldpc_decode_lds_bytes(p);
-  // Two checks per lane: messages per edge (NRPHY_DECODER_MSG=0: compressed records instead, the round-3 form, for A/B runs).
-  // Behind the soft bits in LDS when the expected layers leave the CU at least twelve wavefronts (three per SIMD, where the
-  // edge passes still hide their LDS round trips) -- NRPHY_DECODER_LDSMSG=2: whenever a workgroup's LDS can hold them at all
-  // (tests), =0: never --, else in the codeblock's slot of the scratch.
-  const bool         msg       = pairs && p.pair_addr != nullptr && (p.bg_k == 22u || p.bg_k == 10u) && p.knob_msg != 0;
+  // The messages live behind the soft bits in LDS when the expected layers leave the CU at least twelve wavefronts (three per
+  // SIMD, where the edge passes still hide their LDS round trips) -- NRPHY_DECODER_LDSMSG=2: whenever a workgroup's LDS can hold
+  // them at all (tests), =0: never --, else in the codeblock's slot of the scratch.
   const uint32_t     waves     = threads / WAVE;
   const uint32_t     lm_cap    = p.knob_ldsmsg == 2 ? 160u * 1024u : ((160u * 1024u) / ((12u + waves - 1u) / waves)) & ~255u;
   if (msg && p.lm_lds_bytes != 0 && p.lm_lds_bytes + LDS_TAIL_BYTES <= lm_cap && p.knob_ldsmsg != 0) {
@@ -1216,10 +1059,9 @@ hipError_t launch_ldpc_decode(const LdpcDecodeLaunch& p_in, uint32_t n_cb, hipSt
   lds += LDS_TAIL_BYTES;
   typedef void (*kernel_t)(LdpcDecodeLaunch);
   const bool         in_lds    = p.lm_lds_bytes != 0;
-  const kernel_t     kernel    = msg     ? (p.bg_k == 22u ? (in_lds ? ldpc_decode_msg_bg1_kernel : ldpc_decode_msg_bg1_slot_kernel)
-                                                          : (in_lds ? ldpc_decode_msg_bg2_kernel : ldpc_decode_msg_bg2_slot_kernel))
-                                 : pairs ? ldpc_decode_pairs_kernel
-                                         : ldpc_decode_kernel;
+  const kernel_t     kernel    = !msg           ? ldpc_decode_kernel
+                                 : p.bg_k == 22u ? (in_lds ? ldpc_decode_msg_bg1_kernel : ldpc_decode_msg_bg1_slot_kernel)
+                                                 : (in_lds ? ldpc_decode_msg_bg2_kernel : ldpc_decode_msg_bg2_slot_kernel);
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) {

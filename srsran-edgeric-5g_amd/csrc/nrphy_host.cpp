@@ -654,7 +654,6 @@ Tunables read_tunables()
   t.extras_nt         = (uint32_t)number("NRPHY_EXTRAS_NT", 1);
   t.prologue_order    = (uint32_t)number("NRPHY_PROLOGUE_ORDER", 0);
   t.decoder_pairs     = number("NRPHY_DECODER_PAIRS", -1);
-  t.decoder_msg       = number("NRPHY_DECODER_MSG", -1);
   t.decoder_ldsmsg    = number("NRPHY_DECODER_LDSMSG", -1);
   t.decoder_slots_all = number("NRPHY_DECODER_SLOTS_ALL", 0) == 1;
 #ifdef NRPHY_PROBES
@@ -2309,17 +2308,49 @@ int ldpc_decode_batch(nrphy_ctx_t* ctx, const nrphy_ldpc_decoder_cfg_t* cfg, uin
                       const uint8_t* d_skip, uint8_t* d_ok_flags, bool crc_at_end, void* d_scratch, void* stream,
                       uint32_t expected_extent = 0);
 
-// The caller-owned scratch of a decoder launch: a pool of check-record slots + the bitmap that hands them out.
+// What every entry point of the decoder asks of a configuration: base graph 1 or 2 at one of the 51 lifting sizes.
+bool decoder_graph_valid(const nrphy_ldpc_decoder_cfg_t& cfg)
+{
+  return (cfg.base_graph == 1 || cfg.base_graph == 2) && lifting_position(cfg.lifting_size) >= 0;
+}
+unsigned decoder_bg_k(const nrphy_ldpc_decoder_cfg_t& cfg) { return (cfg.base_graph == 1) ? 22 : 10; } // message nodes
+// cfg.crc_poly (0: no early stop, 16, 0x24A, 0x24B) -> generator polynomial and order; false: none of these.
+bool decoder_crc(uint32_t id, uint32_t& poly, uint32_t& order)
+{
+  poly  = id == 16 ? 0x11021U : id == 0x24A ? 0x1864CFBU : id == 0x24B ? 0x1800063U : 0;
+  order = poly == 0 ? 0 : id == 16 ? 16 : 24;
+  return id == 0 || poly != 0;
+}
+// Rows of two edges that the messages per edge of a base graph's first `layers` layers take (ldpc_decoder.hip): the sum of
+// ceil(degree / 2).
+uint32_t decoder_message_rows(unsigned base_graph, uint32_t layers)
+{
+  const nr_ldpc_edge_t* edges   = (base_graph == 1) ? NR_LDPC_BG1_EDGES : NR_LDPC_BG2_EDGES;
+  const unsigned        n_edges = (base_graph == 1) ? NR_LDPC_BG1_NOF_EDGES : NR_LDPC_BG2_NOF_EDGES;
+  std::vector<uint32_t> degree(layers, 0);
+  for (unsigned e = 0; e != n_edges; ++e) {
+    if (edges[e].row < layers) {
+      ++degree[edges[e].row];
+    }
+  }
+  uint32_t rows = 0;
+  for (uint32_t dg : degree) {
+    rows += (dg + 1) / 2;
+  }
+  return rows;
+}
+
+// The caller-owned scratch of a decoder launch: a pool of slots (check records or messages per edge) + their flags.
 struct DecoderScratch {
   uint32_t nof_slots, nof_layers_max;
   uint64_t slot_bytes, records_bytes, flags_bytes, total_bytes;
 };
 bool decoder_scratch_layout(const nrphy_ctx_t* ctx, const nrphy_ldpc_decoder_cfg_t& cfg, uint32_t n_cb, DecoderScratch& s)
 {
-  const unsigned bg_k = (cfg.base_graph == 1) ? 22 : 10, zc = cfg.lifting_size;
-  if ((cfg.base_graph != 1 && cfg.base_graph != 2) || lifting_position(zc) < 0 || n_cb == 0) {
+  if (!decoder_graph_valid(cfg) || n_cb == 0) {
     return false;
   }
+  const unsigned bg_k = decoder_bg_k(cfg), zc = cfg.lifting_size;
   const uint32_t nof_nodes = std::max<uint32_t>(divide_ceil(cfg.nof_llr, zc) + 2, bg_k + 4);
   s.nof_layers_max         = nof_nodes - bg_k;
   // Workgroups of the decoder the device can hold at once: 32 wavefronts per CU (the kernel is built for 8 per SIMD),
@@ -2332,21 +2363,8 @@ bool decoder_scratch_layout(const nrphy_ctx_t* ctx, const nrphy_ldpc_decoder_cfg
   }
   // A slot holds a codeblock's check records (8 bytes per lifted check and layer) or, with two checks per lane, its messages
   // per edge: rows of two edges, 2 Zc bytes each, five spare rows (the kernel requests five rows from a layer's first).
-  {
-    const nr_ldpc_edge_t* edges   = (cfg.base_graph == 1) ? NR_LDPC_BG1_EDGES : NR_LDPC_BG2_EDGES;
-    const unsigned        n_edges = (cfg.base_graph == 1) ? NR_LDPC_BG1_NOF_EDGES : NR_LDPC_BG2_NOF_EDGES;
-    std::vector<uint32_t> degree(s.nof_layers_max, 0);
-    for (unsigned e = 0; e != n_edges; ++e) {
-      if (edges[e].row < s.nof_layers_max) {
-        ++degree[edges[e].row];
-      }
-    }
-    uint64_t rows = 5;
-    for (uint32_t dg : degree) {
-      rows += (dg + 1) / 2;
-    }
-    s.slot_bytes = (std::max<uint64_t>((uint64_t)s.nof_layers_max * zc * sizeof(uint2), rows * 2 * zc) + 255) & ~(uint64_t)255;
-  }
+  const uint64_t rows     = 5 + (uint64_t)decoder_message_rows(cfg.base_graph, s.nof_layers_max);
+  s.slot_bytes            = (std::max<uint64_t>((uint64_t)s.nof_layers_max * zc * sizeof(uint2), rows * 2 * zc) + 255) & ~(uint64_t)255;
   s.records_bytes         = (uint64_t)s.nof_slots * s.slot_bytes;
   s.flags_bytes           = ((uint64_t)s.nof_slots * 4 + 255) & ~(uint64_t)255;
   s.total_bytes           = ((s.records_bytes + 255) & ~(uint64_t)255) + s.flags_bytes;
@@ -2367,8 +2385,8 @@ extern "C" int nrphy_ldpc_decoder_scratch_bytes(nrphy_ctx_t* ctx, const nrphy_ld
 
 extern "C" int nrphy_ldpc_decoder_prepare(nrphy_ctx_t* ctx, const nrphy_ldpc_decoder_cfg_t* cfg)
 {
-  if (ctx == nullptr || cfg == nullptr || (cfg->base_graph != 1 && cfg->base_graph != 2) || lifting_position(cfg->lifting_size) < 0 ||
-      (cfg->crc_poly != 0 && cfg->crc_poly != 16 && cfg->crc_poly != 0x24A && cfg->crc_poly != 0x24B)) {
+  uint32_t poly, order;
+  if (ctx == nullptr || cfg == nullptr || !decoder_graph_valid(*cfg) || !decoder_crc(cfg->crc_poly, poly, order)) {
     return NRPHY_ERR_ARGUMENT;
   }
   HIP_TRY(hipSetDevice(ctx->device));
@@ -2376,10 +2394,8 @@ extern "C" int nrphy_ldpc_decoder_prepare(nrphy_ctx_t* ctx, const nrphy_ldpc_dec
   if (get_decoder_graph(ctx, cfg->base_graph, cfg->lifting_size) == nullptr) {
     return NRPHY_ERR_DEVICE;
   }
-  if (cfg->crc_poly != 0) {
-    const uint32_t order = cfg->crc_poly == 16 ? 16 : 24;
-    const uint32_t poly  = (cfg->crc_poly == 16) ? 0x11021U : (cfg->crc_poly == 0x24B ? 0x1800063U : 0x1864CFBU);
-    const uint32_t K     = ((cfg->base_graph == 1) ? 22U : 10U) * cfg->lifting_size;
+  if (order != 0) {
+    const uint32_t K = decoder_bg_k(*cfg) * cfg->lifting_size;
     if (cfg->nof_filler_bits >= K || get_decoder_crc_weights(ctx, poly, order, K - cfg->nof_filler_bits) == nullptr) {
       return NRPHY_ERR_DEVICE;
     }
@@ -2402,21 +2418,20 @@ int ldpc_decode_batch(nrphy_ctx_t* ctx, const nrphy_ldpc_decoder_cfg_t* cfg, uin
                       const uint8_t* d_skip, uint8_t* d_ok_flags, bool crc_at_end, void* d_scratch, void* stream,
                       uint32_t expected_extent)
 {
+  LdpcDecodeLaunch p;
   if (ctx == nullptr || cfg == nullptr || d_llr == nullptr || d_out == nullptr || d_scratch == nullptr ||
-      (cfg->base_graph != 1 && cfg->base_graph != 2) || cfg->max_iterations == 0 ||
-      !(cfg->scaling_factor > 0.0F && cfg->scaling_factor < 1.0F) ||
-      (cfg->crc_poly != 0 && cfg->crc_poly != 16 && cfg->crc_poly != 0x24A && cfg->crc_poly != 0x24B)) {
+      !decoder_graph_valid(*cfg) || cfg->max_iterations == 0 ||
+      !(cfg->scaling_factor > 0.0F && cfg->scaling_factor < 1.0F) || !decoder_crc(cfg->crc_poly, p.crc_poly, p.crc_order)) {
     return NRPHY_ERR_ARGUMENT;
   }
-  const unsigned bg_k = (cfg->base_graph == 1) ? 22 : 10, n_full = (cfg->base_graph == 1) ? 68 : 52;
+  const unsigned bg_k = decoder_bg_k(*cfg), n_full = (cfg->base_graph == 1) ? 68 : 52;
   const unsigned zc = cfg->lifting_size, K = bg_k * zc;
   // ldpc_decoder_impl.cpp:70-86: between the message plus two blocks and the whole (shortened) codeblock.
-  if (lifting_position(zc) < 0 || cfg->nof_llr < K + 2 * zc || cfg->nof_llr > (n_full - 2) * zc ||
+  if (cfg->nof_llr < K + 2 * zc || cfg->nof_llr > (n_full - 2) * zc ||
       cfg->nof_filler_bits >= K || llr_stride_bytes < cfg->nof_llr || out_stride_bytes < (K + 7) / 8) {
     return NRPHY_ERR_ARGUMENT;
   }
   HIP_TRY(hipSetDevice(ctx->device));
-  LdpcDecodeLaunch p;
   {
     std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
     p.graph     = get_decoder_graph(ctx, cfg->base_graph, zc);
@@ -2433,8 +2448,6 @@ int ldpc_decode_batch(nrphy_ctx_t* ctx, const nrphy_ldpc_decoder_cfg_t* cfg, uin
   p.llr_stride     = llr_stride_bytes;
   p.out_stride     = out_stride_bytes;
   p.nof_filler     = cfg->nof_filler_bits;
-  p.crc_order      = (cfg->crc_poly == 0) ? 0 : (cfg->crc_poly == 16 ? 16 : 24);
-  p.crc_poly       = (cfg->crc_poly == 16) ? 0x11021U : (cfg->crc_poly == 0x24B ? 0x1800063U : 0x1864CFBU);
   p.max_iterations = cfg->max_iterations;
   p.scaling_factor = cfg->scaling_factor;
   p.llr            = d_llr;
@@ -2444,7 +2457,6 @@ int ldpc_decode_batch(nrphy_ctx_t* ctx, const nrphy_ldpc_decoder_cfg_t* cfg, uin
   p.ok_flags       = d_ok_flags;
   p.crc_at_end     = crc_at_end ? 1U : 0U;
   p.knob_pairs     = ctx->tune.decoder_pairs;
-  p.knob_msg       = ctx->tune.decoder_msg;
   p.knob_ldsmsg    = ctx->tune.decoder_ldsmsg;
   {
     // LDS for the messages-per-edge form (ldpc_decoder.hip) at the expected extent: the soft bits of the layers it needs (the
@@ -2452,20 +2464,7 @@ int ldpc_decode_batch(nrphy_ctx_t* ctx, const nrphy_ldpc_decoder_cfg_t* cfg, uin
     const uint32_t extent = (expected_extent == 0 || expected_extent > cfg->nof_llr) ? cfg->nof_llr : expected_extent;
     uint32_t       cb_len = std::max<uint32_t>(extent + 2 * zc, K + 4 * zc);
     cb_len                = divide_ceil(cb_len, zc) * zc;
-    const uint32_t        layers  = cb_len / zc - bg_k;
-    const nr_ldpc_edge_t* edges   = (cfg->base_graph == 1) ? NR_LDPC_BG1_EDGES : NR_LDPC_BG2_EDGES;
-    const unsigned        n_edges = (cfg->base_graph == 1) ? NR_LDPC_BG1_NOF_EDGES : NR_LDPC_BG2_NOF_EDGES;
-    std::vector<uint32_t> degree(layers, 0);
-    for (unsigned e = 0; e != n_edges; ++e) {
-      if (edges[e].row < layers) {
-        ++degree[edges[e].row];
-      }
-    }
-    uint32_t rows = 0; // of two edges each
-    for (uint32_t dg : degree) {
-      rows += (dg + 1) / 2;
-    }
-    p.lm_lds_bytes = ((cb_len + 48U + 15U) & ~15U) + rows * 2 * zc;
+    p.lm_lds_bytes        = ((cb_len + 48U + 15U) & ~15U) + decoder_message_rows(cfg->base_graph, cb_len / zc - bg_k) * 2 * zc;
     // The scaling of the minima by arithmetic instead of a table look-up, where it gives the table's values
     // (round half away from zero: ldpc_decoder_generic.cpp:69-79).
     p.scale_arithmetic = 1;
@@ -2497,7 +2496,7 @@ int ldpc_decode_batch(nrphy_ctx_t* ctx, const nrphy_ldpc_decoder_cfg_t* cfg, uin
   if (n_cb == 0) {
     return NRPHY_OK;
   }
-  // Check records: the caller's scratch, a pool of slots shared by the workgroups resident at once.
+  // Check records or messages per edge: the caller's scratch, a pool of slots shared by the workgroups resident at once.
   DecoderScratch sl;
   if (!decoder_scratch_layout(ctx, *cfg, n_cb, sl)) {
     return NRPHY_ERR_ARGUMENT;
@@ -2522,12 +2521,11 @@ int ldpc_decode_batch(nrphy_ctx_t* ctx, const nrphy_ldpc_decoder_cfg_t* cfg, uin
 extern "C" int nrphy_ldpc_decode_host(nrphy_ctx_t* ctx, const nrphy_ldpc_decoder_cfg_t* cfg, const int8_t* llr,
                                       uint8_t* message_packed, uint32_t* iterations)
 {
-  if (ctx == nullptr || cfg == nullptr || llr == nullptr || message_packed == nullptr ||
-      (cfg->base_graph != 1 && cfg->base_graph != 2) || lifting_position(cfg->lifting_size) < 0 ||
+  if (ctx == nullptr || cfg == nullptr || llr == nullptr || message_packed == nullptr || !decoder_graph_valid(*cfg) ||
       cfg->nof_llr > 66U * cfg->lifting_size) {
     return NRPHY_ERR_ARGUMENT;
   }
-  const unsigned K     = ((cfg->base_graph == 1) ? 22U : 10U) * cfg->lifting_size;
+  const unsigned K     = decoder_bg_k(*cfg) * cfg->lifting_size;
   HostCall       call(ctx);
   uint8_t*       d[2]; // soft bits; message, then the iteration count at the next multiple of 4
   if (!call.carve(SCRATCH_RX, {(size_t)cfg->nof_llr + 16, (size_t)(K + 7) / 8 + 16}, d)) {

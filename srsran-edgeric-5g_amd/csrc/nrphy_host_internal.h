@@ -139,7 +139,6 @@ struct Tunables {
   uint32_t extras_nt       = 1;  // NRPHY_EXTRAS_NT=0: DM-RS / zero-fill stores with the default cache policy
   uint32_t prologue_order  = 0;  // NRPHY_PROLOGUE_ORDER=1: sequence workgroups spread among the TB-CRC workgroups
   int      decoder_pairs   = -1; // NRPHY_DECODER_PAIRS=0: one check per lane whatever the lifting size
-  int      decoder_msg     = -1; // NRPHY_DECODER_MSG=0: compressed check records instead of messages per edge
   int      decoder_ldsmsg  = -1; // NRPHY_DECODER_LDSMSG: 0 = messages never in LDS, 2 = wherever a workgroup's LDS can hold them
   bool     decoder_slots_all = false; // NRPHY_DECODER_SLOTS_ALL=1: a scratch slot per codeblock (no pooling)
 #ifdef NRPHY_PROBES

@@ -294,7 +294,7 @@ struct LdpcDecodeLaunch {
   uint32_t            max_iterations;
   float               scaling_factor;
   // Two checks per lane with the messages per edge in LDS: in = the LDS bytes that takes for the layers the caller expects
-  // (0: not wanted); launch_ldpc_decode() turns it into the launch's LDS size, or 0 when the kernel keeps to its records.
+  // (0: not wanted); launch_ldpc_decode() turns it into the launch's LDS size, or 0 when the messages stay in the slots.
   // Each codeblock decides by the layers its own soft bits ask for whether it fits.
   uint32_t            lm_lds_bytes;
   uint32_t            lds_tail_off;     // set by launch_ldpc_decode(): where the kernel's flags and scaling table sit in its LDS
@@ -302,9 +302,9 @@ struct LdpcDecodeLaunch {
   // 16-bit arithmetic, 1 = (unsigned)(m * scaling_factor + 0.5f), 0 = the table in LDS -- the cheapest the host has verified.
   uint32_t            scale_arithmetic;
   uint32_t            scale_fixed;
-  // The context's A/B knobs (Tunables): -1 = not set.  pairs 0: one check per lane; msg 0: check records instead of messages;
-  // ldsmsg 0: messages never in LDS, 2: wherever a workgroup's LDS can hold them.
-  int                 knob_pairs, knob_msg, knob_ldsmsg;
+  // The context's knobs (Tunables) for launch_ldpc_decode(), -1 = not set; no kernel reads them.  pairs 0: one check per lane
+  // whatever the lifting size; ldsmsg 0: messages never in LDS, 2: wherever a workgroup's LDS can hold them.
+  int                 knob_pairs, knob_ldsmsg;
 };
 hipError_t launch_ldpc_decode(const LdpcDecodeLaunch& p, uint32_t n_cb, hipStream_t stream);
 

@@ -801,8 +801,7 @@ DECODER_KERNELS = {  # environment a context is created under -> which form of t
     "default": {},                                  # two checks per lane, messages per edge: in LDS where the occupancy rule allows, else in the scratch slot
     "lds-messages": {"NRPHY_DECODER_LDSMSG": "2"},  # ... in LDS wherever a workgroup's LDS can hold them
     "slot-messages": {"NRPHY_DECODER_LDSMSG": "0"}, # ... always in the codeblock's slot of the caller's scratch
-    "records": {"NRPHY_DECODER_MSG": "0"},          # two checks per lane, compressed records in the caller's scratch (round 3's form)
-    "one-check": {"NRPHY_DECODER_PAIRS": "0"},      # one check per lane (what odd lifting sizes always take)
+    "one-check": {"NRPHY_DECODER_PAIRS": "0"},      # one check per lane, compressed records in the slot (what odd lifting sizes always take)
 }
 
 
@@ -810,8 +809,8 @@ DECODER_KERNELS = {  # environment a context is created under -> which form of t
 @pytest.mark.parametrize("case", cases.LDPC_DECODE_CASES)
 def test_ldpc_decoder_vs_oracle(gpu_ctx_for, oracle, case, kernel):
     """Every form of the decoder kernel: two checks per lane in packed 16-bit arithmetic (even lifting sizes) with the messages
-    per edge in LDS or as compressed records, and one check per lane -- hard bits and iteration counts of all equal the
-    oracle's."""
+    per edge in LDS or in the codeblock's slot, and one check per lane with compressed records -- hard bits and iteration counts
+    of all equal the oracle's."""
     gpu_ctx = gpu_ctx_for(DECODER_KERNELS[kernel])
     bg, zc, extra, tail, crc_id, filler, amp, sigma = case
     rng = np.random.default_rng(zc * 1000 + extra)
@@ -902,7 +901,7 @@ def test_ldpc_decoder_batch_and_argument_checks(gpu_ctx, oracle):
 
 
 def test_ldpc_decoder_scratch_pool_streams_and_graph(gpu_ctx, oracle):
-    """The decoder's check records live in a caller-owned pool that stops growing with the batch: a batch far larger than
+    """The decoder's messages per edge live in a caller-owned pool that stops growing with the batch: a batch far larger than
     the pool (workgroups claim and release slots), two decodes in flight on two streams with a scratch each, and a decode
     captured in a hipGraph after nrphy_ldpc_decoder_prepare -- all bit-exact against the oracle."""
     import torch
