@@ -194,6 +194,11 @@ int nrphy_pdsch_plan_destroy(nrphy_pdsch_plan_t* plan);
 uint32_t nrphy_pdsch_plan_nof_codeblocks(const nrphy_pdsch_plan_t* plan);
 uint64_t nrphy_pdsch_plan_codeword_bits(const nrphy_pdsch_plan_t* plan);
 uint64_t nrphy_pdsch_plan_codeword_offset(const nrphy_pdsch_plan_t* plan, uint32_t pdu);
+/* The numbers of distinct scrambling sequences and of distinct sets of DM-RS sequences a run of the plan
+ * generates: PDUs with the same scrambling initialisation and codeword layout (codeblock count and lengths,
+ * bits per resource element) share one sequence, PDUs with the same DM-RS symbols, initialisations and
+ * length one set -- the slots of one UE in a batch, for instance.  Either pointer may be NULL. */
+int nrphy_pdsch_plan_nof_sequences(const nrphy_pdsch_plan_t* plan, uint32_t* scrambling, uint32_t* dmrs);
 
 /* Runs the whole PDSCH path of every PDU of the plan: TB CRC, segmentation, CB CRC, LDPC encoding,
  * rate matching, bit interleaving, scrambling, modulation, layer mapping, precoding, RE mapping and

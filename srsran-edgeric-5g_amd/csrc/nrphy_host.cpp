@@ -15,6 +15,7 @@
 #include <map>
 #include <mutex>
 #include <new>
+#include <unordered_map>
 #include <vector>
 
 using namespace nrphy;
@@ -298,6 +299,33 @@ void build_gold_tables(GoldTables& t, std::vector<uint32_t>& x1_words)
   }
 }
 
+// What decides the sequences a PDU asks the prologue for (plan_create).  scr: c_init, C, n_short, e_short, e_long, bits per
+// resource element -- the sequence and where the work items' seeds lie in it (with RE_CHUNK).  dmrs: symbol mask, words per
+// symbol, c_init of the DM-RS symbols.
+struct SeqKey {
+  std::array<uint32_t, 6>               scr;
+  std::array<uint32_t, 2 + NRPHY_NSYMB> dmrs;
+  bool operator==(const SeqKey& o) const { return scr == o.scr && dmrs == o.dmrs; }
+};
+struct SeqKeyHash {
+  size_t operator()(const SeqKey& k) const
+  {
+    uint64_t h = 0xCBF29CE484222325ULL; // FNV-1a over the words
+    for (uint32_t w : k.scr) {
+      h = (h ^ w) * 0x100000001B3ULL;
+    }
+    for (uint32_t w : k.dmrs) {
+      h = (h ^ w) * 0x100000001B3ULL;
+    }
+    return (size_t)(h ^ (h >> 32));
+  }
+};
+struct SeqShare {
+  uint32_t seed_first;      // PduDev::seed_first of the PDUs that share the scrambling sequence
+  uint32_t dmrs_seq_offset; // PduDev::dmrs_seq_offset of those that share the DM-RS sequences
+};
+constexpr uint8_t SEQ_NEW_SCR = 1, SEQ_NEW_DMRS = 2;
+
 } // namespace
 
 struct nrphy_pdsch_plan {
@@ -317,10 +345,11 @@ struct nrphy_pdsch_plan {
   CrcWork*              d_crc_work = nullptr;
   ScrWork*              d_scr_work = nullptr;
   uint32_t              n_scr_work = 0;
+  uint32_t              n_scr_seq = 0, n_dmrs_seq = 0; // distinct scrambling sequences / DM-RS sequence sets a run generates
   ZeroWork*             d_zero_work = nullptr;
   ZeroSeg*              d_zero_segs = nullptr;
   uint32_t*             d_scr = nullptr;    // scrambling sequences, rewritten by every run's prologue
-  uint64_t              scr_words = 0;   // words of the run's scratch: DM-RS sequences, then the work items' seeds
+  uint64_t              scr_words = 0;   // words of the run's scratch: the distinct DM-RS sequences, then the seeds of the distinct scrambling sequences
   uint64_t              seed_offset = 0; // where the seeds start
   uint32_t              n_zero_work = 0;
   bool                  encode_only = false;   // seam B plan: no RE mapping, nrphy_pdsch_run only with d_grid = NULL
@@ -901,6 +930,9 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus,
   std::vector<uint64_t> remap_sig;
   std::map<std::vector<uint64_t>, ReMapping> remap_cache;
   std::vector<ScrWork>  scr_work;
+  std::unordered_map<SeqKey, SeqShare, SeqKeyHash> seq_shares; // the sequences earlier PDUs of the plan ask for
+  std::vector<uint8_t>  seq_fresh;      // per PDU: SEQ_NEW_SCR / SEQ_NEW_DMRS -- the first PDU that asks for the sequence generates it
+  uint32_t              seed_slots = 0; // seed slots handed out: one per work item of every distinct scrambling sequence
   std::vector<std::vector<uint32_t>> pdus_of_grid(nof_grids);
   std::vector<float>    weights;
   std::vector<uint16_t> re_table;
@@ -1107,33 +1139,9 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus,
       plan->dmrs_separate = true; // data is mapped on RE that also carry DM-RS: the reference lets DM-RS win
     }
     pdus_of_grid[g].push_back(i);
-    // TB-CRC work: the transport block in 16 KiB regions, a workgroup per run of regions.  A small batch gets a workgroup
-    // per region (latency); a big one has workgroups enough and lets each walk several regions, the next one's words in
-    // flight while it reduces the current one (a workgroup per region spent two thirds of its time waiting for its loads:
-    // profiles/r03_prologue_trace.txt).
-    {
-      const CrcField& f = (d.nof_tb_crc_bits == 16) ? CRC16_FIELD : CRC24A_FIELD;
-      const uint32_t  n = pdu.tb_size_bytes;
-      const uint32_t  regions = divide_ceil(n, TB_CRC_REGION_BYTES);
-      const uint32_t  want  = std::max<uint32_t>(1, std::min<uint32_t>(regions, TB_CRC_TARGET_WORK / std::max<uint32_t>(1, n_pdu)));
-      uint32_t        per   = std::min<uint32_t>(TB_CRC_MAX_REGIONS_PER_WORK, divide_ceil(regions, want));
-      if (ctx->tune.crc_regions > 0) { // (A/B and test knob: regions per workgroup)
-        per = std::max(1, std::min((int)TB_CRC_MAX_REGIONS_PER_WORK, ctx->tune.crc_regions));
-      }
-      pd.crc_first      = (uint32_t)crc_work.size();
-      pd.crc_count      = divide_ceil(regions, per);
-      if (pd.crc_count > 64) { // one lane of the attaching wave per share
-        status = NRPHY_ERR_INVALID_PDU;
-        break;
-      }
-      for (uint32_t region = 0; region < regions; region += per) {
-        const uint32_t count      = std::min(per, regions - region);
-        const int64_t  region_end = (int64_t)(region + count) * TB_CRC_REGION_BYTES;
-        crc_work.push_back({i, region, f.xpow((int64_t)f.order + 8 * ((int64_t)n - region_end)), count});
-      }
-    }
     // Work items: every codeblock owns a whole number of RE (rm_length is a multiple of nof_layers * Qm).
     const unsigned lq = pdu.nof_layers * pdu.qm;
+    const size_t   work_before = work.size();
     for (unsigned cb = 0; cb != d.nof_codeblocks; ++cb) {
       const unsigned nre = ((cb < d.nof_short_segments) ? d.rm_length_short : d.rm_length_long) / lq;
       for (unsigned begin = 0; begin < nre; begin += RE_CHUNK) {
@@ -1163,26 +1171,117 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus,
     // the work items' seeds are stored (behind the DM-RS sequences, below).
     pd.scr_words  = (d.codeword_bits + 31U) / 32U + 1U + 31U;
     // One DM-RS sequence per DM-RS symbol.
-    pd.dmrs_seq_offset = (uint32_t)plan->scr_words;
     pd.dmrs_seq_words  = (12U * (pd.end_prb - pd.dmrs_ref_rb) + 31U) / 32U + 1U;
-    plan->scr_words += ((uint64_t)pd.dmrs_seq_words * (unsigned)__builtin_popcount(pdu.dmrs_symbol_mask) + 3U) & ~3ULL;
     {
-      // A big batch has enough PDUs to fill the device with one workgroup each (seeding a generator is the costly
-      // part: measured 0.111 / 0.098 / 0.096 ms per 1024 config-3 PDUs with 4 / 2 / 1 parts); a small one is split
-      // for latency.
-      // (A/B and test knob: parts of a sequence in a big batch)
-      const uint32_t     parts_big = ctx->tune.scr_parts_big > 0 ? (uint32_t)std::min((int)SCR_PARTS, ctx->tune.scr_parts_big) : 1U;
-      const uint32_t parts_max = n_pdu >= 128 ? parts_big : SCR_PARTS;
-      const uint32_t parts     = std::min<uint32_t>(parts_max, std::max<uint32_t>(1, pd.scr_words >> 11));
-      const uint32_t chunk = divide_ceil(pd.scr_words, parts);
-      for (uint32_t first = 0, k = 0; first < pd.scr_words; first += chunk, ++k) {
-        scr_work.push_back({i, first, std::min(chunk, pd.scr_words - first), k == 0 ? 1U : 0U});
+      // Sequences are generated once per run and distinct sequence, not once per PDU: a batch of slots of one UE asks for the
+      // same scrambling seeds in every slot and for the same DM-RS sequences in every frame.  The seeds depend on c_init and on
+      // where the work items start in the codeword; the DM-RS sequences on the DM-RS symbols' c_init and on their length.  One
+      // look-up per PDU (both keys at once); what a new pair shares with earlier PDUs is found by a look-up per half.  Nothing
+      // here outlives the plan's creation, and every run still computes every distinct sequence from scratch.
+      const uint32_t nof_dmrs_words = (uint32_t)(((uint64_t)pd.dmrs_seq_words * (unsigned)__builtin_popcount(pdu.dmrs_symbol_mask) + 3U) & ~3ULL);
+      const uint32_t nof_items      = (uint32_t)(work.size() - work_before);
+      uint8_t        fresh          = (uint8_t)(SEQ_NEW_SCR | (nof_dmrs_words != 0 ? SEQ_NEW_DMRS : 0));
+      SeqShare       share          = {seed_slots, (uint32_t)plan->scr_words};
+      if (n_pdu != 1) {
+        SeqKey key;
+        key.scr  = {pd.c_init, pd.C, pd.n_short, pd.e_short, pd.e_long, lq};
+        key.dmrs = {};
+        key.dmrs[0] = pdu.dmrs_symbol_mask;
+        key.dmrs[1] = pd.dmrs_seq_words;
+        for (unsigned l = 0; l != NRPHY_NSYMB; ++l) {
+          key.dmrs[2 + l] = ((pdu.dmrs_symbol_mask >> l) & 1U) ? pd.dmrs_c_init[l] : 0U;
+        }
+        auto both = seq_shares.find(key);
+        if (both != seq_shares.end()) {
+          share = both->second;
+          fresh = 0;
+        } else {
+          SeqKey half = key;
+          half.dmrs   = {};
+          half.dmrs[1] = ~0U; // (no DM-RS sequence has this length)
+          auto scr_known = seq_shares.insert({half, share});
+          if (!scr_known.second) {
+            share.seed_first = scr_known.first->second.seed_first;
+            fresh &= (uint8_t)~SEQ_NEW_SCR;
+          }
+          if (nof_dmrs_words != 0) {
+            half     = key;
+            half.scr = {}; // (no codeword has zero bits per resource element)
+            auto dmrs_known = seq_shares.insert({half, share});
+            if (!dmrs_known.second) {
+              share.dmrs_seq_offset = dmrs_known.first->second.dmrs_seq_offset;
+              fresh &= (uint8_t)~SEQ_NEW_DMRS;
+            }
+          }
+          seq_shares.insert({key, share});
+        }
       }
+      pd.seed_first      = share.seed_first;
+      pd.dmrs_seq_offset = share.dmrs_seq_offset;
+      if (fresh & SEQ_NEW_SCR) {
+        seed_slots += nof_items;
+        ++plan->n_scr_seq;
+      }
+      if (fresh & SEQ_NEW_DMRS) {
+        plan->scr_words += nof_dmrs_words;
+        ++plan->n_dmrs_seq;
+      }
+      seq_fresh.push_back(fresh);
     }
     plan->n_cb += d.nof_codeblocks;
     plan->cw_offset.push_back(cw_bits);
     cw_bits += (d.codeword_bits + 31U) & ~31ULL;
     plan->pdus.push_back(pd);
+  }
+  // Sequence work: a workgroup per distinct scrambling sequence -- the first PDU that asks for it walks it -- with that
+  // PDU's DM-RS sequences on its spare waves if they are new too; a PDU that shares its scrambling sequence and has DM-RS
+  // sequences of its own (another slot of the same UE) gets a workgroup that generates those alone.
+  if (status == NRPHY_OK) {
+    // A plan with many sequences fills the device with one workgroup each (seeding a generator is the costly part:
+    // measured 0.111 / 0.098 / 0.096 ms per 1024 distinct config-3 sequences with 4 / 2 / 1 parts); one with few is split
+    // for latency.
+    // (A/B and test knob: parts of a sequence in a plan of many)
+    const uint32_t parts_big = ctx->tune.scr_parts_big > 0 ? (uint32_t)std::min((int)SCR_PARTS, ctx->tune.scr_parts_big) : 1U;
+    const uint32_t parts_max = plan->n_scr_seq >= 128 ? parts_big : SCR_PARTS;
+    for (uint32_t i = 0; i != n_pdu; ++i) {
+      const PduDev&  pd       = plan->pdus[i];
+      const uint32_t own_dmrs = (seq_fresh[i] & SEQ_NEW_DMRS) ? 1U : 0U;
+      if (seq_fresh[i] & SEQ_NEW_SCR) {
+        const uint32_t parts = std::min<uint32_t>(parts_max, std::max<uint32_t>(1, pd.scr_words >> 11));
+        const uint32_t chunk = divide_ceil(pd.scr_words, parts);
+        for (uint32_t first = 0, k = 0; first < pd.scr_words; first += chunk, ++k) {
+          scr_work.push_back({i, first, std::min(chunk, pd.scr_words - first), k == 0 ? own_dmrs : 0U});
+        }
+      } else if (own_dmrs) {
+        scr_work.push_back({i, 0U, 0U, 1U});
+      }
+    }
+  }
+  // TB-CRC work: the transport block in 16 KiB regions, a workgroup per run of regions.  A small batch gets a workgroup
+  // per region (latency); a big one has workgroups enough and lets each walk several regions, the next one's words in
+  // flight while it reduces the current one (a workgroup per region spent two thirds of its time waiting for its loads:
+  // profiles/r03_prologue_trace.txt).
+  for (uint32_t i = 0; i != n_pdu && status == NRPHY_OK; ++i) {
+    PduDev&         pd = plan->pdus[i];
+    const CrcField& f  = (pd.tb_crc_bits == 16) ? CRC16_FIELD : CRC24A_FIELD;
+    const uint32_t  n  = pd.tb_bytes;
+    const uint32_t  regions = divide_ceil(n, TB_CRC_REGION_BYTES);
+    const uint32_t  want  = std::max<uint32_t>(1, std::min<uint32_t>(regions, TB_CRC_TARGET_WORK / std::max<uint32_t>(1, n_pdu)));
+    uint32_t        per   = std::min<uint32_t>(TB_CRC_MAX_REGIONS_PER_WORK, divide_ceil(regions, want));
+    if (ctx->tune.crc_regions > 0) { // (A/B and test knob: regions per workgroup)
+      per = std::max(1, std::min((int)TB_CRC_MAX_REGIONS_PER_WORK, ctx->tune.crc_regions));
+    }
+    pd.crc_first      = (uint32_t)crc_work.size();
+    pd.crc_count      = divide_ceil(regions, per);
+    if (pd.crc_count > 64) { // one lane of the attaching wave per share
+      status = NRPHY_ERR_INVALID_PDU;
+      break;
+    }
+    for (uint32_t region = 0; region < regions; region += per) {
+      const uint32_t count      = std::min(per, regions - region);
+      const int64_t  region_end = (int64_t)(region + count) * TB_CRC_REGION_BYTES;
+      crc_work.push_back({i, region, f.xpow((int64_t)f.order + 8 * ((int64_t)n - region_end)), count});
+    }
   }
   if (status != NRPHY_OK) {
     delete plan;
@@ -1328,10 +1427,10 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus,
     for (size_t k = work.size(); k-- != 0;) {
       plan->pdus[work[k].pdu].item_first = (uint32_t)k;
     }
-    // The seeds of the work items' scrambling sequences: 32 words each, behind the DM-RS sequences.
+    // The seeds of the distinct scrambling sequences, 32 words per work item, behind the DM-RS sequences.
     plan->scr_words  = (plan->scr_words + 3U) & ~3ULL;
     plan->seed_offset = plan->scr_words;
-    plan->scr_words += 32ULL * work.size();
+    plan->scr_words += 32ULL * seed_slots;
     // The codeblock waves load 2 * NRPHY_MAX_PORTS * layers weights whatever the port count (pdsch_kernels.hip, phase_b).
     weights.insert(weights.end(), 2 * NRPHY_MAX_PORTS * NRPHY_MAX_PORTS, 0.0F);
   }
@@ -1440,6 +1539,20 @@ extern "C" int nrphy_pdsch_plan_destroy(nrphy_pdsch_plan_t* plan)
 extern "C" uint32_t nrphy_pdsch_plan_nof_codeblocks(const nrphy_pdsch_plan_t* plan)
 {
   return plan ? plan->n_cb : 0;
+}
+
+extern "C" int nrphy_pdsch_plan_nof_sequences(const nrphy_pdsch_plan_t* plan, uint32_t* scrambling, uint32_t* dmrs)
+{
+  if (plan == nullptr) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  if (scrambling != nullptr) {
+    *scrambling = plan->n_scr_seq;
+  }
+  if (dmrs != nullptr) {
+    *dmrs = plan->n_dmrs_seq;
+  }
+  return NRPHY_OK;
 }
 
 extern "C" uint64_t nrphy_pdsch_plan_codeword_bits(const nrphy_pdsch_plan_t* plan)

@@ -100,6 +100,7 @@ struct PduDev {
   uint32_t nof_ports;
   uint32_t c_init;         // scrambling sequence initialisation
   uint32_t item_first;     // index of the PDU's first work item in the plan's (bucket-sorted) work list; its items follow in codeblock / chunk order
+  uint32_t seed_first;     // seed slot of that first item; the others follow.  PDUs whose scrambling sequence and codeword layout are the same share their slots
   uint32_t scr_words;      // words of the scrambling sequence the prologue walks: ceil(G / 32) + read-ahead + a seed's length
   uint32_t nof_re;
   uint32_t weights_offset; // floats: data weights (scaled) [nof_prg][P][L][2] in the plan's weight array
@@ -116,7 +117,7 @@ struct PduDev {
   uint32_t dmrs_zero_other_group; // 1: CDM group 1 is reserved but unused by this PDU -> the DM-RS waves write its zeros
   uint32_t dmrs_c_init[NRPHY_NSYMB];
   uint32_t dmrs_ref_rb;
-  uint32_t dmrs_seq_offset; // word offset of the DM-RS sequences (one per DM-RS symbol, in symbol order)
+  uint32_t dmrs_seq_offset; // word offset of the DM-RS sequences (one per DM-RS symbol, in symbol order); PDUs that ask for the same ones share them
   uint32_t dmrs_seq_words;  // words per DM-RS symbol: sequence bits [0, 12 * (end_prb - dmrs_ref_rb))
   float    dmrs_amplitude;
   uint32_t prb_mask[2 * NRPHY_PRB_WORDS];
@@ -166,7 +167,9 @@ struct DmrsWork {
 
 // One 256-thread workgroup of the sequence role: wave 0 walks words [first, first + count) of the PDU's scrambling sequence
 // and stores the seeds of the work items that start there; the PDU's first workgroup also generates its DM-RS sequences
-// (waves 1-3).  Long sequences are split over up to SCR_PARTS workgroups in a small batch.
+// (waves 1-3, with_dmrs).  Long sequences are split over up to SCR_PARTS workgroups when the plan has few of them.  Only the
+// first PDU that asks for a sequence gets work: a PDU that shares its scrambling sequence but not its DM-RS has one entry
+// with count == 0 and with_dmrs set.
 struct ScrWork {
   uint32_t pdu;
   uint32_t first;
@@ -212,8 +215,8 @@ struct PdschLaunch {
   uint32_t           n_zero_work;     // zero-fill waves appended to the codeblock launch (0: caller cleared the grids)
   uint32_t           n_dmrs_in_launch; // DM-RS waves appended to the codeblock launch (0: separate launch)
   uint32_t*          scr;             // DM-RS sequences c(n) of every PDU, MSB-first words (prologue -> DM-RS waves)
-  uint32_t*          scr_seed;        // [n_work][32]: the first 31 words of the x2 part of the scrambling sequence of every work item
-                                      // (prologue -> codeblock waves, which expand them: gold_expand_seed_wave)
+  uint32_t*          scr_seed;        // [seed slot][32]: the first 31 words of the x2 part of the scrambling sequence of every work item
+                                      // (PduDev::seed_first; prologue -> codeblock waves, which expand them: gold_expand_seed_wave)
   const PduDev*      pdus;
   const CbWork*      work;
   const DmrsWork*    dmrs_work;
@@ -230,7 +233,7 @@ struct PdschLaunch {
   uint32_t*          tb_crc_part; // [n_crc_work] share of every 16 KiB region in its PDU's CRC, rewritten by every run
   uint32_t           n_pdu;
   uint32_t           n_work;
-  uint32_t           work_base;      // index of work[0] in the plan's whole work list (a bucket launch starts inside it): the seeds' index
+  uint32_t           work_base;      // index of work[0] in the plan's whole work list (a bucket launch starts inside it): PduDev::item_first counts from there
   uint32_t           n_dmrs_work;
   uint32_t           grid_nof_ports;
   uint32_t           grid_nof_subc;

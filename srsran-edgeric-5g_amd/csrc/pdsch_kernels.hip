@@ -44,9 +44,10 @@ namespace nrphy {
 //
 // Scrambling sequences (seeds per work item) and DM-RS sequences: see gold_sequence_blocks_wave() and gold_sequence_wave().
 // ================================================================================================================
-// Blocks [0, n_scr_work): the seeds of the scrambling sequence of one PDU (a part of them in a small batch) and its DM-RS
-// sequences (TS 38.211 Sections 7.3.1.1, 7.4.1.1.1; reference: pdsch_modulator_impl.cpp:43-60,
-// dmrs_pdsch_processor_impl.cpp:84-106).  The blocks after them: transport-block CRC.
+// Blocks [0, n_scr_work): the seeds of the scrambling sequence of one PDU (a part of them where the plan has few sequences) and
+// its DM-RS sequences (TS 38.211 Sections 7.3.1.1, 7.4.1.1.1; reference: pdsch_modulator_impl.cpp:43-60,
+// dmrs_pdsch_processor_impl.cpp:84-106) -- once per distinct sequence of the plan: the PDUs that ask for the same one read the
+// same seeds (PduDev::seed_first) and DM-RS words (dmrs_seq_offset).  The blocks after them: transport-block CRC.
 __global__ __launch_bounds__(TB_CRC_THREADS) void prologue_kernel(PdschLaunch p, const uint8_t* __restrict__ d_tb)
 {
   constexpr uint32_t LDS_WORDS = TB_CRC_LDS_WORDS; // CRC role: four tables and two buffers of partials (18 KB: 8 workgroups per CU)
@@ -89,19 +90,23 @@ __global__ __launch_bounds__(TB_CRC_THREADS) void prologue_kernel(PdschLaunch p,
     // scrambling sequence (its x2 part: the codeblock waves add the x1 words, which every sequence shares) with the
     // recurrence in registers (gold_sequence_blocks_wave) and stores, for every work item of the PDU, the 31 words that
     // start at the word the item's first codeword bit lies in: the codeblock wave expands them to the few hundred words it
-    // needs (gold_expand_seed_wave).  13 MB of seeds per 1024 config-3 slots instead of 121 MB of sequences out and back.
+    // needs (gold_expand_seed_wave).  13 MB of seeds per 1024 config-3 slots instead of 121 MB of sequences out and back -- and
+    // 13 KB where the slots are one UE's and share the sequence.
     constexpr uint32_t DMRS_WAVES = TB_CRC_THREADS / WAVE - 1, DMRS_SCRATCH = (GOLD_RING_WORDS - 2048u) / DMRS_WAVES;
     static_assert(GOLD_SEED_WORDS <= 2048u && GOLD_RING_WORDS > 2048u, "LDS of the sequence role");
     static_assert((12u * NRPHY_MAX_RB + 31u) / 32u + 1u <= DMRS_SCRATCH, "DM-RS scratch per wave");
     if (wave == 0) {
+      if (count == 0) { // a PDU that shares its scrambling sequence and has DM-RS sequences of its own
+        return;
+      }
       // The PDU's work items in the order the plan lists them (nrphy_host.cpp: codeblock by codeblock, RE_CHUNK resource
       // elements per item), walked with scalar arithmetic alongside the blocks: w0 = the word of the item's first bit.
       const uint32_t lq = pd.qm * pd.nof_layers, n_short = pd.n_short, e_short = pd.e_short, e_long = pd.e_long, C = pd.C;
       const uint32_t nre_short = e_short / lq, nre_long = e_long / lq; // (the only divisions: the walk itself has none)
       struct Cursor {
-        uint32_t cb, re_begin, item, bit_cb, nre;
+        uint32_t cb, re_begin, item, bit_cb, nre; // item: its seed slot
       };
-      Cursor resume = {0u, 0u, pd.item_first, 0u, n_short != 0 ? nre_short : nre_long}; // the first item whose seed is not complete yet
+      Cursor resume = {0u, 0u, pd.seed_first, 0u, n_short != 0 ? nre_short : nre_long}; // the first item whose seed is not complete yet
       auto   advance = [&](Cursor& c) {
         c.re_begin += RE_CHUNK;
         if (c.re_begin >= c.nre) {
@@ -877,7 +882,8 @@ __device__ __forceinline__ void map_chunk(const PdschLaunch& p, PduRef pd, const
   cm.aligned = (g.bit0 & 31u) == 0;
   // The work item's seed (the 31 x2 words from the one its first bit lies in; prologue) and the x1 words of the chunk's
   // first 64 RE are requested here: their trip to memory rides under rate matching.
-  const uint32_t seed_word   = lane < 31u ? p.scr_seed[(size_t)item * 32u + lane] : 0u;
+  const uint32_t seed_slot   = pd.seed_first + (item - pd.item_first); // the PDU's own items, or those of the PDU it shares with
+  const uint32_t seed_word   = lane < 31u ? p.scr_seed[(size_t)seed_slot * 32u + lane] : 0u;
   const uint32_t first_gbits = x1_bits<QM, L>(p, g, cm, wk.re_count, lane);
   {
     const RmIndex rm = rm_index_init(pd);

@@ -555,6 +555,13 @@ class PdschPlan:
     def codeword_offset(self, pdu):
         return int(self.ctx.lib.nrphy_pdsch_plan_codeword_offset(self.handle, pdu))
 
+    @property
+    def nof_sequences(self):
+        """(distinct scrambling sequences, distinct DM-RS sequence sets) a run of the plan generates."""
+        scr, dmrs = C.c_uint32(0), C.c_uint32(0)
+        _check(self.ctx.lib.nrphy_pdsch_plan_nof_sequences(self.handle, C.byref(scr), C.byref(dmrs)), "nrphy_pdsch_plan_nof_sequences")
+        return int(scr.value), int(dmrs.value)
+
     def run(self, d_tb, d_grid, d_cw_rm=None, d_cw_scr=None, zero_grids=True, stream=None):
         _check(self.ctx.lib.nrphy_pdsch_run(self.handle, _dptr(d_tb), _dptr(d_grid), _dptr(d_cw_rm), _dptr(d_cw_scr),
                                             int(zero_grids), _stream(stream)), "nrphy_pdsch_run")
