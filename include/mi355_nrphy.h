@@ -1316,6 +1316,89 @@ int nrphy_ofh_compress(nrphy_ctx_t* ctx, const nrphy_ofh_compression_cfg_t* cfg,
 int nrphy_ofh_compress_host(nrphy_ctx_t* ctx, const nrphy_ofh_compression_cfg_t* cfg, uint32_t nof_prb, const void* prbs,
                             uint8_t* out);
 
+/* Open Fronthaul IQ decompression: the receive half.  Replaces iq_decompressor::decompress
+ * (R/lib/ofh/compression/iq_compression_none_impl.cpp:56-73, iq_compression_bfp_impl.cpp:98-135 with quantizer.h,
+ * compressed_prb_unpacker.cpp and to_bf16 of R/include/srsran/adt/bf16.h:39-56; the reference's SIMD classes delegate
+ * decompress to these, so there is one behaviour).  The records are the ones nrphy_ofh_compress writes.  Per value: v = the
+ * data_width-bit field sign-extended; none: float(v) / float(2^(data_width - 1) - 1); BFP: float(v * scaler) / 32767.0f in
+ * 32-bit integer arithmetic, scaler = (int16_t)(1 << udCompParam) as the reference built by gcc evaluates it -- 2^e for
+ * e <= 14, -32768 for e = 15 (the sign flip included), 0 for 16 <= e <= 30.  For e >= 31 the reference is undefined; this
+ * library's rule is scaler = 0.  The division is IEEE single precision, correctly rounded; the result is rounded to bf16 as
+ * to_bf16 does.  Every result is byte for byte the reference's.
+ * Widths: BFP 1..16, none 2..16.  none with 1 bit has a quantiser gain of 0 and the reference produces NaN and infinities
+ * whose bit patterns differ between hosts: NRPHY_ERR_ARGUMENT.  cfg->iq_scaling is not used (the reference's decompressors
+ * ignore theirs).
+ * n_rows rows of nof_prb PRBs: row r reads nof_prb records at d_in + r * in_row_stride bytes (any byte alignment; only
+ * the rows' own bytes are read) and writes 12 * nof_prb cbf16 at d_prbs + r * row_stride (in cbf16 words; d_prbs 4-byte
+ * aligned).  Asynchronous on `stream`, capturable.  The host form goes through the context's staging like every _host
+ * call. */
+int nrphy_ofh_decompress(nrphy_ctx_t* ctx, const nrphy_ofh_compression_cfg_t* cfg, uint32_t n_rows, uint32_t nof_prb,
+                         const uint8_t* d_in, size_t in_row_stride /* bytes */, void* d_prbs, size_t row_stride /* cbf16 words */,
+                         void* stream);
+int nrphy_ofh_decompress_host(nrphy_ctx_t* ctx, const nrphy_ofh_compression_cfg_t* cfg, uint32_t nof_prb, const uint8_t* in,
+                              void* prbs);
+
+/* Open Fronthaul uplink receive: the sections of decoded user-plane messages -- of any number of messages, slots and
+ * cells -- decompressed from packet payload in device memory straight into the receive grid
+ * [nof_grids][grid_nof_ports][14][grid_nof_subc] cbf16 that nrphy_pusch_chest_run, nrphy_pucch_run and nrphy_pf2_run read.
+ * Replaces uplane_message_decoder_impl::decode_iq_data + uplane_rx_symbol_data_flow_writer::write_to_resource_grid
+ * (R/lib/ofh/receiver/ofh_uplane_rx_symbol_data_flow_writer.cpp:53-80).  Header parsing, the sequence and window checks
+ * and the context repositories stay with the caller: one descriptor per section says where its records are and where
+ * they belong. */
+typedef struct nrphy_ofh_ul_section {
+  uint64_t payload_offset; /* byte offset in d_payload of the section's first PRB record */
+  uint32_t grid_index;     /* the uplink slot context */
+  uint16_t port;           /* resource-grid port = position of the eAxC in the cell's list */
+  uint16_t symbol;         /* 0..13 */
+  uint16_t start_prb;      /* as decoded from the section header, 0..1023 */
+  uint16_t nof_prbs;       /* as decoded, after the reference's "0 means ru_nof_prbs, start 0" rule; 1..MAX_NOF_PRBS */
+  uint8_t  type;           /* 0 none, 1 BFP: the section's udCompHdr (static or dynamic compression alike) */
+  uint8_t  data_width;
+  uint16_t reserved_;      /* 0 */
+} nrphy_ofh_ul_section_t;
+/* Clipping is the reference's, with du_nof_prbs = grid_nof_subc / 12: a section with start_prb >= du_nof_prbs writes
+ * nothing, any other writes min(nof_prbs, du_nof_prbs - start_prb) PRBs from subcarrier 12 * start_prb on; every other
+ * resource element of every grid is left untouched.
+ * nrphy_ofh_ul_validate is host only (no device work).  NRPHY_ERR_ARGUMENT for: an unknown type, a width outside the
+ * ranges of nrphy_ofh_decompress, symbol >= 14, port >= grid_nof_ports, grid_index >= nof_grids, nof_prbs of 0 or above
+ * 275 (MAX_NOF_PRBS), a non-zero reserved_, grid_nof_subc that is no multiple of 12, a section whose nof_prbs records --
+ * all of them as sent, not only the clipped part (check_iq_data_size) -- do not lie inside [0, payload_bytes), and two
+ * sections of one call whose clipped ranges share a resource element: the reference writes sections in order, one launch
+ * cannot, so a caller with duplicates makes two calls on the same stream.
+ * nrphy_ofh_ul_write_grid validates, then launches; n = 0 is NRPHY_OK with no work.  `sections` is a host array, copied
+ * at the call into staging that lives in stream order, as nrphy_grid_put does: asynchronous on `stream`, NOT capturable.
+ * The kernel reads no byte outside the sections' records and writes nothing outside the clipped ranges.  d_grid is 4-byte
+ * aligned; d_payload may have any alignment. */
+int nrphy_ofh_ul_validate(uint32_t n, const nrphy_ofh_ul_section_t* sections, uint64_t payload_bytes, uint32_t nof_grids,
+                          uint32_t grid_nof_ports, uint32_t grid_nof_subc);
+int nrphy_ofh_ul_write_grid(nrphy_ctx_t* ctx, uint32_t n, const nrphy_ofh_ul_section_t* sections, const uint8_t* d_payload,
+                            uint64_t payload_bytes, void* d_grid, uint32_t nof_grids, uint32_t grid_nof_ports,
+                            uint32_t grid_nof_subc, void* stream);
+
+/* The same into the PRACH buffer that nrphy_prach_run reads in place (the tensor nrphy_prach_plan_create describes:
+ * sym_offset, port_stride, symbol_stride).  Replaces uplane_prach_symbol_data_flow_writer::write_to_prach_buffer
+ * (R/lib/ofh/receiver/ofh_uplane_prach_symbol_data_flow_writer.cpp:56-112): its range arithmetic -- the PRACH's PRBs, the two
+ * skip conditions, the PRBs to write, start_re, the trimming of the last PRB, iq_start_re, iq_size_re -- is done on the
+ * host per section in the reference's order and integer widths, from the two values of the reference's prach_context that
+ * the caller passes.  Resource elements [iq_start_re, iq_start_re + iq_size_re) of the section are decompressed to cbf16
+ * as above, each half is widened to float (srsvec::convert(cf, cbf16)), and element i goes to
+ * d_symbols[dst_offset + start_re + i]. */
+typedef struct nrphy_ofh_ul_prach_section {
+  nrphy_ofh_ul_section_t section;   /* grid_index, port, symbol unused by the arithmetic: must be 0 */
+  uint64_t dst_offset;              /* element (complex f32) of d_symbols where RE 0 of this (port, symbol, occasion) lives */
+  uint32_t prach_nof_re;            /* prach_context::get_prach_nof_re(): 839 or 139 */
+  uint32_t offset_to_first_re;      /* prach_context::get_prach_offset_to_first_re() */
+} nrphy_ofh_ul_prach_section_t;
+/* Refused like nrphy_ofh_ul_validate where that applies (type, width, nof_prbs, reserved_, the records inside the
+ * payload), and: non-zero grid_index, port or symbol, prach_nof_re other than 139 or 839, a range of the section's samples
+ * that the reference's subspan would refuse, a destination range outside [0, symbols_elems), destinations of one call
+ * that overlap.  d_symbols is 8-byte aligned.  Asynchronous on `stream`, not capturable (the host array is staged as
+ * above). */
+int nrphy_ofh_ul_prach_validate(uint32_t n, const nrphy_ofh_ul_prach_section_t* sections, uint64_t payload_bytes,
+                                uint64_t symbols_elems);
+int nrphy_ofh_ul_write_prach(nrphy_ctx_t* ctx, uint32_t n, const nrphy_ofh_ul_prach_section_t* sections, const uint8_t* d_payload,
+                             uint64_t payload_bytes, void* d_symbols, uint64_t symbols_elems, void* stream);
+
 /* dft_processor::run (R/include/srsran/phy/generic_functions/dft_processor.h:34-73; generic impl
  * dft_processor_generic_impl.cpp:14-218).  Unnormalised DFT of `size` complex floats, `batch` of them
  * back to back.  inverse != 0 uses exp(+j...).  Sizes: every size of the reference's generic implementation

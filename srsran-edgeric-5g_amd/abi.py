@@ -503,6 +503,18 @@ class OfhCompressionCfg(C.Structure):
     _fields_ = [("type", C.c_uint32), ("data_width", C.c_uint32), ("iq_scaling", C.c_float)]
 
 
+class OfhUlSection(C.Structure):
+    """nrphy_ofh_ul_section_t: one section of a decoded uplink user-plane message."""
+    _fields_ = [("payload_offset", C.c_uint64), ("grid_index", C.c_uint32), ("port", C.c_uint16), ("symbol", C.c_uint16),
+                ("start_prb", C.c_uint16), ("nof_prbs", C.c_uint16), ("type", C.c_uint8), ("data_width", C.c_uint8),
+                ("reserved_", C.c_uint16)]
+
+
+class OfhUlPrachSection(C.Structure):
+    """nrphy_ofh_ul_prach_section_t: a section for the PRACH buffer with the two values of the reference's prach_context."""
+    _fields_ = [("section", OfhUlSection), ("dst_offset", C.c_uint64), ("prach_nof_re", C.c_uint32), ("offset_to_first_re", C.c_uint32)]
+
+
 class OfdmConfig(C.Structure):
     _fields_ = [
         ("numerology", C.c_uint32),
@@ -685,6 +697,12 @@ def declare(lib, prefix="nrphy_"):
     sig("ofh_compressed_prb_bytes", u32, P(OfhCompressionCfg))
     sig("ofh_compress", i32, vp, P(OfhCompressionCfg), u32, u32, vp, C.c_size_t, vp, C.c_size_t, vp)
     sig("ofh_compress_host", i32, vp, P(OfhCompressionCfg), u32, vp, vp)
+    sig("ofh_decompress", i32, vp, P(OfhCompressionCfg), u32, u32, vp, C.c_size_t, vp, C.c_size_t, vp)
+    sig("ofh_decompress_host", i32, vp, P(OfhCompressionCfg), u32, vp, vp)
+    sig("ofh_ul_validate", i32, u32, P(OfhUlSection), u64, u32, u32, u32)
+    sig("ofh_ul_write_grid", i32, vp, u32, P(OfhUlSection), vp, u64, vp, u32, u32, u32, vp)
+    sig("ofh_ul_prach_validate", i32, u32, P(OfhUlPrachSection), u64, u64)
+    sig("ofh_ul_write_prach", i32, vp, u32, P(OfhUlPrachSection), vp, u64, vp, u64, vp)
     sig("pusch_decoder_sizes", i32, vp, P(PuschDecoderCfg), u32, P(u64), P(u64), P(u64), P(u32))
     sig("pusch_decoder_prepare", i32, vp, P(PuschDecoderCfg))
     sig("pusch_decode_batch", i32, vp, P(PuschDecoderCfg), u32, vp, u64, vp, vp, vp, vp, u32, vp, vp)
@@ -786,7 +804,8 @@ ABI_SYMBOLS = [
     "nrphy_pdsch_async_count_done",
     "nrphy_amplitude_control", "nrphy_amplitude_metrics", "nrphy_amplitude_control_host", "nrphy_iq_convert_ci16",
     "nrphy_iq_convert_ci16_host", "nrphy_ofdm_run_ci16", "nrphy_ofh_compressed_prb_bytes", "nrphy_ofh_compress",
-    "nrphy_ofh_compress_host",
+    "nrphy_ofh_compress_host", "nrphy_ofh_decompress", "nrphy_ofh_decompress_host", "nrphy_ofh_ul_validate", "nrphy_ofh_ul_write_grid",
+    "nrphy_ofh_ul_prach_validate", "nrphy_ofh_ul_write_prach",
     "nrphy_dl_slots_create", "nrphy_dl_slots_destroy", "nrphy_dl_slots_wait_free", "nrphy_dl_slot_open", "nrphy_dl_slot_close",
     "nrphy_dl_slot_pdsch", "nrphy_dl_slot_pdcch", "nrphy_dl_slot_ssb", "nrphy_dl_slot_csi_rs", "nrphy_dl_slot_put",
     "nrphy_dl_slot_load_grid", "nrphy_dl_slot_modulate", "nrphy_dl_slot_poll", "nrphy_dl_slot_wait", "nrphy_dl_slot_iq",

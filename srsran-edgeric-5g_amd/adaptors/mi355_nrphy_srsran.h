@@ -46,6 +46,7 @@
 #include "srsran/srsvec/bit.h"
 
 #include "srsran/ofh/compression/iq_compressor.h"
+#include "srsran/ofh/compression/iq_decompressor.h"
 #include "srsran/phy/lower/amplitude_controller/amplitude_controller.h"
 #include "srsran/phy/lower/amplitude_controller/amplitude_controller_factories.h"
 #include "srsran/phy/support/re_buffer.h"
@@ -2093,6 +2094,42 @@ public:
 private:
   std::shared_ptr<context> ctx;
   float                    iq_scaling;
+  std::vector<uint8_t>     packed;
+};
+
+/// ofh::iq_decompressor over nrphy_ofh_decompress_host, the reverse of iq_compressor_adaptor: each compressed_prb's parameter
+/// and packed bytes are serialised into the wire records the library reads (the device-resident forms,
+/// nrphy_ofh_ul_write_grid and nrphy_ofh_ul_write_prach, read the user-plane payload itself).  The compression type maps as
+/// in iq_compressor_adaptor; on failure the samples come out as zeros.
+class iq_decompressor_adaptor : public srsran::ofh::iq_decompressor
+{
+public:
+  explicit iq_decompressor_adaptor(std::shared_ptr<context> ctx_) : ctx(std::move(ctx_)) {}
+  void decompress(srsran::span<srsran::cbf16_t>                   iq_data,
+                  srsran::span<const srsran::ofh::compressed_prb> compressed_prbs,
+                  const srsran::ofh::ru_compression_params&       params) override
+  {
+    using namespace srsran;
+    nrphy_ofh_compression_cfg_t cfg = {params.type == ofh::compression_type::BFP ? 1U : 0U, params.data_width, 1.0F};
+    const unsigned              rec = nrphy_ofh_compressed_prb_bytes(&cfg), nof_prb = compressed_prbs.size();
+    srsran_assert(iq_data.size() >= static_cast<size_t>(nof_prb) * NOF_SUBCARRIERS_PER_RB, "Output span is too small.");
+    packed.assign(static_cast<size_t>(rec) * nof_prb, 0);
+    for (unsigned i = 0; i != nof_prb; ++i) {
+      uint8_t* r = &packed[static_cast<size_t>(i) * rec];
+      if (cfg.type == 1) {
+        *r++ = compressed_prbs[i].get_compression_param();
+      }
+      std::memcpy(r, compressed_prbs[i].get_byte_buffer().data(), 3 * params.data_width);
+    }
+    int rc = nrphy_ofh_decompress_host(ctx->get(), &cfg, nof_prb, packed.data(), iq_data.data());
+    report_failure("nrphy_ofh_decompress_host", rc);
+    if (rc != NRPHY_OK) {
+      std::fill(iq_data.begin(), iq_data.begin() + static_cast<size_t>(nof_prb) * NOF_SUBCARRIERS_PER_RB, cbf16_t());
+    }
+  }
+
+private:
+  std::shared_ptr<context> ctx;
   std::vector<uint8_t>     packed;
 };
 

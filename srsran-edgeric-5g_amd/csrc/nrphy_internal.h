@@ -747,6 +747,25 @@ struct OfhCompressLaunch {
   float           scale;     // quantiser gain * iq_scaling
 };
 hipError_t launch_ofh_compress(const OfhCompressLaunch& p, uint32_t n_rows, hipStream_t stream);
+// ---- Open Fronthaul uplink receive (ofh_ul_kernels.hip) -----------------------------------------------------------------
+constexpr uint32_t OFH_UL_PRBS_PER_WG = 16; // records per workgroup (one wave: three resource elements per lane)
+struct OfhDecompressLaunch {
+  const uint8_t* in;
+  uint32_t*      prbs;      // cbf16 words
+  size_t         in_row_stride, row_stride; // bytes / words between rows
+  uint32_t       nof_prb, data_width, bfp;
+};
+hipError_t launch_ofh_decompress(const OfhDecompressLaunch& p, uint32_t n_rows, hipStream_t stream);
+// One run of records and the resource elements of it that are written: elements [re_skip, re_skip + nof_re) counted from
+// the first record at payload byte `src` go to destination elements dst, dst + 1, ... (cbf16 words of the grid, complex
+// floats of the PRACH buffer).  Workgroups first_chunk ... of the launch take OFH_UL_PRBS_PER_WG records each.
+struct OfhUlItem {
+  uint64_t src, dst;
+  uint32_t nof_re, re_skip, first_chunk;
+  uint16_t data_width, bfp;
+};
+hipError_t launch_ofh_ul_sections(const OfhUlItem* d_items, uint32_t n, uint32_t nof_chunks, const uint8_t* d_payload, void* d_dst,
+                                  bool prach, hipStream_t stream);
 hipError_t launch_ofdm(const OfdmLaunch& p, uint32_t nof_grids, const uint32_t* d_grid, const uint32_t* d_slot_index,
                        float2* d_iq, hipStream_t stream);
 // OFDM demodulation (the receive-side mirror of launch_ofdm): `p.phase` is the receive table (conjugate phase x scale),

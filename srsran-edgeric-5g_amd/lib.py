@@ -306,6 +306,36 @@ class Context:
         _check(self.lib.nrphy_ofh_compress(self.handle, C.byref(cfg), n_rows, nof_prb, _dptr(d_prbs), row_stride or 12 * nof_prb,
                                            _dptr(d_out), out_row_stride or rec * nof_prb, _stream(stream)), "nrphy_ofh_compress")
 
+    def ofh_decompress_host(self, cfg, data):
+        """iq_decompressor::decompress on serialised records: bytes -> prbs [nof_prb][12][2] uint16 (raw cbf16)."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        nof_prb = data.size // self.lib.nrphy_ofh_compressed_prb_bytes(C.byref(cfg))
+        out = np.zeros((nof_prb, 12, 2), np.uint16)
+        _check(self.lib.nrphy_ofh_decompress_host(self.handle, C.byref(cfg), nof_prb, data.ctypes.data, out.ctypes.data),
+               "nrphy_ofh_decompress_host")
+        return out
+
+    def ofh_decompress(self, cfg, n_rows, nof_prb, d_in, d_prbs, in_row_stride=None, row_stride=None, stream=None):
+        """d_in: a device pointer (int) or a tensor -- the records may start at any byte."""
+        rec = self.lib.nrphy_ofh_compressed_prb_bytes(C.byref(cfg))
+        d_in = C.c_void_p(d_in) if isinstance(d_in, int) else _dptr(d_in)
+        _check(self.lib.nrphy_ofh_decompress(self.handle, C.byref(cfg), n_rows, nof_prb, d_in, in_row_stride or rec * nof_prb,
+                                             _dptr(d_prbs), row_stride or 12 * nof_prb, _stream(stream)), "nrphy_ofh_decompress")
+
+    def ofh_ul_write_grid(self, sections, d_payload, d_grid, nof_grids, grid_nof_ports, grid_nof_subc, payload_bytes=None, stream=None):
+        """sections: a list of abi.OfhUlSection; d_payload: a uint8 tensor; returns the status (NRPHY_OK or NRPHY_ERR_ARGUMENT)."""
+        arr = (abi.OfhUlSection * max(len(sections), 1))(*sections)
+        payload_bytes = d_payload.numel() if payload_bytes is None else payload_bytes
+        return self.lib.nrphy_ofh_ul_write_grid(self.handle, len(sections), arr, _dptr(d_payload), payload_bytes, _dptr(d_grid), nof_grids,
+                                                grid_nof_ports, grid_nof_subc, _stream(stream))
+
+    def ofh_ul_write_prach(self, sections, d_payload, d_symbols, symbols_elems, payload_bytes=None, stream=None):
+        """sections: a list of abi.OfhUlPrachSection; d_symbols: the PRACH buffer, complex float; returns the status."""
+        arr = (abi.OfhUlPrachSection * max(len(sections), 1))(*sections)
+        payload_bytes = d_payload.numel() if payload_bytes is None else payload_bytes
+        return self.lib.nrphy_ofh_ul_write_prach(self.handle, len(sections), arr, _dptr(d_payload), payload_bytes, _dptr(d_symbols),
+                                                 symbols_elems, _stream(stream))
+
     def pusch_decoder_sizes(self, cfg, n_tb):
         """(soft-buffer bytes per transport block, state bytes of the batch, codeblocks per transport block)."""
         soft, state, scratch, ncb = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_uint32(0)
@@ -833,6 +863,16 @@ def ulsch_demux_sizes(cfg):
     if int(load().nrphy_ulsch_demux_sizes(C.byref(cfg), C.byref(s))) != abi.OK:
         return None
     return int(s.nof_sch_bits), int(s.nof_codeword_bits)
+
+
+def ofh_ul_validate(sections, payload_bytes, nof_grids, grid_nof_ports, grid_nof_subc):
+    arr = (abi.OfhUlSection * max(len(sections), 1))(*sections)
+    return load().nrphy_ofh_ul_validate(len(sections), arr, payload_bytes, nof_grids, grid_nof_ports, grid_nof_subc)
+
+
+def ofh_ul_prach_validate(sections, payload_bytes, symbols_elems):
+    arr = (abi.OfhUlPrachSection * max(len(sections), 1))(*sections)
+    return load().nrphy_ofh_ul_prach_validate(len(sections), arr, payload_bytes, symbols_elems)
 
 
 def uci_decoder_validate(cfg):
