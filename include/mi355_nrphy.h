@@ -1399,6 +1399,74 @@ int nrphy_ofh_ul_prach_validate(uint32_t n, const nrphy_ofh_ul_prach_section_t* 
 int nrphy_ofh_ul_write_prach(nrphy_ctx_t* ctx, uint32_t n, const nrphy_ofh_ul_prach_section_t* sections, const uint8_t* d_payload,
                              uint64_t payload_bytes, void* d_symbols, uint64_t symbols_elems, void* stream);
 
+/* Open Fronthaul downlink transmit: OFDM symbols of the device-resident downlink grid
+ * [nof_grids][grid_nof_ports][14][grid_nof_subc] cbf16 (what every downlink writer here produces) to complete, ready-to-send
+ * Ethernet frames in device (or pinned) memory, byte for byte those of
+ * data_flow_uplane_downlink_data_impl::enqueue_section_type_1_message
+ * (R/lib/ofh/transmitter/ofh_data_flow_uplane_downlink_data_impl.cpp) with vlan_frame_builder_impl, ecpri::packet_builder_impl, the
+ * static or the dynamic user-plane message builder and the AVX2 compressors.  One descriptor is one OFDM symbol of one eAxC;
+ * one launch takes any number of them, of any slots, cells and compressions.  The control plane, the frame pool and the send
+ * stay with the caller.
+ * A symbol's ru_nof_prbs PRBs are cut into fragments of floor((mtu - headers) / record bytes) PRBs (the last one shorter),
+ * headers = 18 (VLAN Ethernet) + 8 (eCPRI) + 8 or 10 (radio application and section header, + udCompHdr and a reserved byte
+ * for the dynamic builder).  Fragment f is one frame at frame_offset + f * frame_stride:
+ *   dst MAC, src MAC, 0x8100, tci, eth_type | 0x10, 0x00 (iq_data), payload size (all after these four bytes), eaxc,
+ *   (seq_id + f) mod 256, 0x80 | 0x90, sfn & 0xFF, subframe << 4 | slot >> 2, (slot & 3) << 6 | symbol | 0x00,
+ *   start_prb >> 8, start_prb & 0xFF, nof_prbs (0 above 255) | [data_width << 4 | type (low 8 bits), 0x00] | the PRB records
+ * and zeros up to 64 bytes when it is shorter.  The records of a fragment are those of nrphy_ofh_compress for ONE row that
+ * consists of the fragment's PRBs -- the reference calls compress() per fragment, and where the vector loop of a call ends
+ * decides the rounding of its last values -- so they differ from a slice of a whole-symbol row.  PRBs at or beyond
+ * grid_nof_subc / 12 are zero samples.  The reference's `symbol_end = symbol_range.length()` loop bound is not reproduced: the
+ * caller passes one descriptor per symbol. */
+typedef struct nrphy_ofh_dl_flow {          /* data_flow_uplane_downlink_data_impl_config + its builders: one per cell/compression */
+  uint8_t  mac_dst[6], mac_src[6];
+  uint16_t tci, eth_type;                   /* vlan_frame_params */
+  uint32_t mtu;                             /* bytes of one frame buffer, Ethernet header included (eth_frame_pool's mtu) */
+  uint32_t ru_nof_prbs;                     /* 1..275 */
+  uint32_t static_compression;              /* 1: static builder, no udCompHdr (OFH header 8 B); 0: dynamic (10 B) */
+  nrphy_ofh_compression_cfg_t compression;  /* type none|BFP, data_width, iq_scaling: as nrphy_ofh_compress */
+} nrphy_ofh_dl_flow_t;
+typedef struct nrphy_ofh_dl_fragment {
+  uint16_t start_prb, nof_prbs;
+  uint32_t frame_bytes;                     /* frame_buffer::set_size: max(64, headers + records) */
+} nrphy_ofh_dl_fragment_t;
+typedef struct nrphy_ofh_dl_symbol {        /* one OFDM symbol of one eAxC */
+  uint64_t frame_offset;  /* byte offset in d_frames of this symbol's first frame; fragment f at + f * frame_stride */
+  uint32_t flow, grid_index;
+  uint16_t port, eaxc;    /* grid port; eCPRI pc_id */
+  uint16_t sfn;
+  uint8_t  subframe, slot /* subframe_slot_index */, symbol, seq_id /* of the first fragment */;
+  uint8_t  reserved_[2];  /* 0 */
+} nrphy_ofh_dl_symbol_t;
+/* The reference's fragmentation of one symbol of `flow` (ofh_uplane_fragment_size_calculator driven with mtu - headers as
+ * the data flow drives it): up to `max` entries to `out`, the number of fragments to *n.  Host only.  It depends on the flow
+ * alone, so every frame's place and length are known before the launch.  NRPHY_ERR_ARGUMENT for a flow that
+ * nrphy_ofh_dl_validate refuses and for max below the number of fragments (*n is set all the same). */
+int nrphy_ofh_dl_fragments(const nrphy_ofh_dl_flow_t* flow, uint32_t max, nrphy_ofh_dl_fragment_t* out, uint32_t* n);
+/* Host only (no device work).  NRPHY_ERR_ARGUMENT for: an unknown compression type, a width outside 8..16 or an iq_scaling
+ * that is not finite (what nrphy_ofh_compress refuses), ru_nof_prbs of 0 or above 275, static_compression above 1, mtu
+ * above 9600 (MAX_ETH_FRAME_LENGTH), below 64 (the reference pads inside the buffer) or below headers + one PRB record (the
+ * reference would ask its pool for frames for ever), grid_nof_subc that is no multiple of 12 or above 12 * ru_nof_prbs of a
+ * flow a descriptor uses (the reference's first() would assert), flow >= n_flows, grid_index >= nof_grids,
+ * port >= grid_nof_ports, symbol >= 14, subframe >= 10, slot >= 16, sfn >= 1024, non-zero reserved_ bytes, frame_stride
+ * below a used flow's mtu or no multiple of 16, a symbol's frames -- frame_bytes of each -- not inside [0, frames_bytes),
+ * and frames of two descriptors that overlap. */
+int nrphy_ofh_dl_validate(uint32_t n_flows, const nrphy_ofh_dl_flow_t* flows, uint32_t n, const nrphy_ofh_dl_symbol_t* symbols,
+                          uint32_t nof_grids, uint32_t grid_nof_ports, uint32_t grid_nof_subc, uint64_t frames_bytes,
+                          uint32_t frame_stride);
+/* Validates, stages the two host arrays' digest in stream order (as nrphy_ofh_ul_write_grid and nrphy_grid_put do) and does
+ * ONE launch for the whole batch: asynchronous on `stream`, NOT capturable.  n = 0 is NRPHY_OK with no work.  The kernel
+ * writes frame_bytes bytes of every frame and no other byte of d_frames, as aligned 16-byte stores wherever a frame's
+ * address allows; it reads the grid rows of the descriptors only.  d_grid and d_frames are 16-byte aligned. */
+int nrphy_ofh_dl_write_frames(nrphy_ctx_t* ctx, uint32_t n_flows, const nrphy_ofh_dl_flow_t* flows, uint32_t n,
+                              const nrphy_ofh_dl_symbol_t* symbols, const void* d_grid, uint32_t nof_grids, uint32_t grid_nof_ports,
+                              uint32_t grid_nof_subc, uint8_t* d_frames, uint64_t frames_bytes, uint32_t frame_stride, void* stream);
+/* Host-span form for one symbol (blocking): `row` is the symbol's grid_nof_subc cbf16 on the host, so symbol->flow,
+ * grid_index and port must be 0; `frames` is a host buffer of frames_bytes of which only the frames' own bytes are
+ * written.  Through the context's staging like every _host call. */
+int nrphy_ofh_dl_frames_host(nrphy_ctx_t* ctx, const nrphy_ofh_dl_flow_t* flow, const nrphy_ofh_dl_symbol_t* symbol, const void* row,
+                             uint32_t grid_nof_subc, uint8_t* frames, uint64_t frames_bytes, uint32_t frame_stride);
+
 /* dft_processor::run (R/include/srsran/phy/generic_functions/dft_processor.h:34-73; generic impl
  * dft_processor_generic_impl.cpp:14-218).  Unnormalised DFT of `size` complex floats, `batch` of them
  * back to back.  inverse != 0 uses exp(+j...).  Sizes: every size of the reference's generic implementation

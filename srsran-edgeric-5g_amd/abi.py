@@ -515,6 +515,24 @@ class OfhUlPrachSection(C.Structure):
     _fields_ = [("section", OfhUlSection), ("dst_offset", C.c_uint64), ("prach_nof_re", C.c_uint32), ("offset_to_first_re", C.c_uint32)]
 
 
+class OfhDlFlow(C.Structure):
+    """nrphy_ofh_dl_flow_t: one downlink user-plane data flow (addresses, MTU, RU bandwidth, builder, compression)."""
+    _fields_ = [("mac_dst", C.c_uint8 * 6), ("mac_src", C.c_uint8 * 6), ("tci", C.c_uint16), ("eth_type", C.c_uint16),
+                ("mtu", C.c_uint32), ("ru_nof_prbs", C.c_uint32), ("static_compression", C.c_uint32), ("compression", OfhCompressionCfg)]
+
+
+class OfhDlFragment(C.Structure):
+    """nrphy_ofh_dl_fragment_t: the PRBs and the length of one frame of a symbol."""
+    _fields_ = [("start_prb", C.c_uint16), ("nof_prbs", C.c_uint16), ("frame_bytes", C.c_uint32)]
+
+
+class OfhDlSymbol(C.Structure):
+    """nrphy_ofh_dl_symbol_t: one OFDM symbol of one eAxC and where its frames go."""
+    _fields_ = [("frame_offset", C.c_uint64), ("flow", C.c_uint32), ("grid_index", C.c_uint32), ("port", C.c_uint16),
+                ("eaxc", C.c_uint16), ("sfn", C.c_uint16), ("subframe", C.c_uint8), ("slot", C.c_uint8), ("symbol", C.c_uint8),
+                ("seq_id", C.c_uint8), ("reserved_", C.c_uint8 * 2)]
+
+
 class OfdmConfig(C.Structure):
     _fields_ = [
         ("numerology", C.c_uint32),
@@ -703,6 +721,10 @@ def declare(lib, prefix="nrphy_"):
     sig("ofh_ul_write_grid", i32, vp, u32, P(OfhUlSection), vp, u64, vp, u32, u32, u32, vp)
     sig("ofh_ul_prach_validate", i32, u32, P(OfhUlPrachSection), u64, u64)
     sig("ofh_ul_write_prach", i32, vp, u32, P(OfhUlPrachSection), vp, u64, vp, u64, vp)
+    sig("ofh_dl_fragments", i32, P(OfhDlFlow), u32, P(OfhDlFragment), P(u32))
+    sig("ofh_dl_validate", i32, u32, P(OfhDlFlow), u32, P(OfhDlSymbol), u32, u32, u32, u64, u32)
+    sig("ofh_dl_write_frames", i32, vp, u32, P(OfhDlFlow), u32, P(OfhDlSymbol), vp, u32, u32, u32, vp, u64, u32, vp)
+    sig("ofh_dl_frames_host", i32, vp, P(OfhDlFlow), P(OfhDlSymbol), vp, u32, vp, u64, u32)
     sig("pusch_decoder_sizes", i32, vp, P(PuschDecoderCfg), u32, P(u64), P(u64), P(u64), P(u32))
     sig("pusch_decoder_prepare", i32, vp, P(PuschDecoderCfg))
     sig("pusch_decode_batch", i32, vp, P(PuschDecoderCfg), u32, vp, u64, vp, vp, vp, vp, u32, vp, vp)
@@ -806,6 +828,7 @@ ABI_SYMBOLS = [
     "nrphy_iq_convert_ci16_host", "nrphy_ofdm_run_ci16", "nrphy_ofh_compressed_prb_bytes", "nrphy_ofh_compress",
     "nrphy_ofh_compress_host", "nrphy_ofh_decompress", "nrphy_ofh_decompress_host", "nrphy_ofh_ul_validate", "nrphy_ofh_ul_write_grid",
     "nrphy_ofh_ul_prach_validate", "nrphy_ofh_ul_write_prach",
+    "nrphy_ofh_dl_fragments", "nrphy_ofh_dl_validate", "nrphy_ofh_dl_write_frames", "nrphy_ofh_dl_frames_host",
     "nrphy_dl_slots_create", "nrphy_dl_slots_destroy", "nrphy_dl_slots_wait_free", "nrphy_dl_slot_open", "nrphy_dl_slot_close",
     "nrphy_dl_slot_pdsch", "nrphy_dl_slot_pdcch", "nrphy_dl_slot_ssb", "nrphy_dl_slot_csi_rs", "nrphy_dl_slot_put",
     "nrphy_dl_slot_load_grid", "nrphy_dl_slot_modulate", "nrphy_dl_slot_poll", "nrphy_dl_slot_wait", "nrphy_dl_slot_iq",

@@ -766,6 +766,25 @@ struct OfhUlItem {
 };
 hipError_t launch_ofh_ul_sections(const OfhUlItem* d_items, uint32_t n, uint32_t nof_chunks, const uint8_t* d_payload, void* d_dst,
                                   bool prach, hipStream_t stream);
+// ---- Open Fronthaul downlink transmit (ofh_dl_kernels.hip) --------------------------------------------------------------
+constexpr uint32_t OFH_DL_MAX_HEADER = 36; // VLAN Ethernet 18 + eCPRI 8 + radio application, section and udCompHdr 10
+// One OFDM symbol of one eAxC as the kernel reads it.  Its fragments are frames of `stride` bytes apart from byte
+// `frame` of d_frames on; all but the last hold prbs_per_frag PRBs.  A workgroup takes one window of `window` bytes of one
+// frame, cut at 16-byte boundaries of the frame's address: windows_per_frag for every fragment but the last, workgroups
+// first_wg ... of the launch in fragment order.
+struct OfhDlSymbol {
+  uint64_t frame;         // byte offset in d_frames of fragment 0
+  uint64_t row;           // cbf16 word of the grid where the symbol's row starts
+  uint32_t first_wg, stride, window, windows_per_frag;
+  uint16_t nof_frags, prbs_per_frag, nof_prbs, grid_prbs; // ru_nof_prbs; PRBs the grid row has (the others are zeros)
+  uint8_t  data_width, bfp, whole_span, header_bytes;
+  float    scale;         // quantiser gain * iq_scaling
+  uint8_t  header[OFH_DL_MAX_HEADER]; // of fragment 0; the kernel sets size, sequence, start and number of PRBs per fragment
+  uint32_t pad_;
+};
+static_assert(sizeof(OfhDlSymbol) == 88, "read as words by the kernel");
+hipError_t launch_ofh_dl_frames(const OfhDlSymbol* d_symbols, uint32_t n, uint32_t nof_wgs, const uint32_t* d_grid, uint8_t* d_frames,
+                                hipStream_t stream);
 hipError_t launch_ofdm(const OfdmLaunch& p, uint32_t nof_grids, const uint32_t* d_grid, const uint32_t* d_slot_index,
                        float2* d_iq, hipStream_t stream);
 // OFDM demodulation (the receive-side mirror of launch_ofdm): `p.phase` is the receive table (conjugate phase x scale),

@@ -329,6 +329,23 @@ class Context:
         return self.lib.nrphy_ofh_ul_write_grid(self.handle, len(sections), arr, _dptr(d_payload), payload_bytes, _dptr(d_grid), nof_grids,
                                                 grid_nof_ports, grid_nof_subc, _stream(stream))
 
+    def ofh_dl_write_frames(self, flows, symbols, d_grid, nof_grids, grid_nof_ports, grid_nof_subc, d_frames, frame_stride,
+                            frames_bytes=None, stream=None):
+        """flows: a list of abi.OfhDlFlow; symbols: a list of abi.OfhDlSymbol; d_frames: a uint8 tensor; returns the status."""
+        f_arr = (abi.OfhDlFlow * max(len(flows), 1))(*flows)
+        s_arr = (abi.OfhDlSymbol * max(len(symbols), 1))(*symbols)
+        frames_bytes = d_frames.numel() * d_frames.element_size() if frames_bytes is None else frames_bytes
+        return self.lib.nrphy_ofh_dl_write_frames(self.handle, len(flows), f_arr, len(symbols), s_arr, _dptr(d_grid), nof_grids,
+                                                  grid_nof_ports, grid_nof_subc, _dptr(d_frames), frames_bytes, frame_stride,
+                                                  _stream(stream))
+
+    def ofh_dl_frames_host(self, flow, symbol, row, frames, frame_stride):
+        """One symbol's row (raw cbf16, uint16 [nof_subc][2]) into the uint8 array `frames` in place; returns the status."""
+        row = np.ascontiguousarray(row, dtype=np.uint16)
+        assert frames.dtype == np.uint8 and frames.flags.c_contiguous
+        return self.lib.nrphy_ofh_dl_frames_host(self.handle, C.byref(flow), C.byref(symbol), row.ctypes.data, row.size // 2,
+                                                 frames.ctypes.data, frames.size, frame_stride)
+
     def ofh_ul_write_prach(self, sections, d_payload, d_symbols, symbols_elems, payload_bytes=None, stream=None):
         """sections: a list of abi.OfhUlPrachSection; d_symbols: the PRACH buffer, complex float; returns the status."""
         arr = (abi.OfhUlPrachSection * max(len(sections), 1))(*sections)
@@ -868,6 +885,22 @@ def ulsch_demux_sizes(cfg):
 def ofh_ul_validate(sections, payload_bytes, nof_grids, grid_nof_ports, grid_nof_subc):
     arr = (abi.OfhUlSection * max(len(sections), 1))(*sections)
     return load().nrphy_ofh_ul_validate(len(sections), arr, payload_bytes, nof_grids, grid_nof_ports, grid_nof_subc)
+
+
+def ofh_dl_fragments(flow):
+    """nrphy_ofh_dl_fragments: [(start_prb, nof_prbs, frame_bytes)] of one symbol of the flow, or None for a refused flow."""
+    out = (abi.OfhDlFragment * 275)()
+    n = C.c_uint32(0)
+    if int(load().nrphy_ofh_dl_fragments(C.byref(flow), 275, out, C.byref(n))) != abi.OK:
+        return None
+    return [(int(f.start_prb), int(f.nof_prbs), int(f.frame_bytes)) for f in out[:n.value]]
+
+
+def ofh_dl_validate(flows, symbols, nof_grids, grid_nof_ports, grid_nof_subc, frames_bytes, frame_stride):
+    f_arr = (abi.OfhDlFlow * max(len(flows), 1))(*flows)
+    s_arr = (abi.OfhDlSymbol * max(len(symbols), 1))(*symbols)
+    return int(load().nrphy_ofh_dl_validate(len(flows), f_arr, len(symbols), s_arr, nof_grids, grid_nof_ports, grid_nof_subc,
+                                            frames_bytes, frame_stride))
 
 
 def ofh_ul_prach_validate(sections, payload_bytes, symbols_elems):
