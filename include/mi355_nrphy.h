@@ -901,6 +901,84 @@ int nrphy_pf2_host(nrphy_ctx_t* ctx, const nrphy_pf2_cfg_t* cfg, const void* gri
                    uint8_t* message, uint32_t* status, nrphy_pf2_csi_t* csi, nrphy_pusch_chest_meas_t* meas, void* ch_est,
                    int8_t* llr);
 
+/* ---- receive side: SRS channel estimator ----------------------------------------------------------------------------------------
+ * Replaces srs_estimator_generic_impl::estimate (R/lib/phy/upper/signal_processors/srs/srs_estimator_generic_impl.cpp:62-193):
+ * grid to the wideband channel matrix and the time alignment of one sounding reference signal.
+ *
+ * Mapping (get_srs_information, R/lib/ran/srs/srs_information.cpp:39-105): m_SRS and N from TS 38.211 Table 6.4.1.4.3-1; sequence
+ * length M = 12 m_SRS / comb; group u = sequence_id mod 30, number 0; n_cs_max = 8 (comb 2) or 12 (comb 4); antenna port p has
+ * cyclic shift (cyclic_shift + n_cs_max p / nof_antenna_ports) mod n_cs_max and sits on subcarriers k0 + comb n, n < M, with
+ * k0 = 12 freq_shift + k_TC + sum_b comb M_b ((4 freq_position / m_SRS,b) mod N_b); ports 1 and 3 of a four-port SRS whose
+ * cyclic shift is at least n_cs_max / 2 take k_TC = (comb_offset + comb / 2) mod comb.
+ *
+ * Sequence (low_papr_sequence_generator_impl): r(n) = table[arg(n)] with the table polar(1, float(2 pi) n / size) -- size 8 and
+ * arg = phi(n) of TS 38.211 Table 5.2.2.2-2 / -4 for M = 12 / 24; size 2 N_zc and arg = -(q m (m + 1) mod 2 N_zc), m = n mod N_zc,
+ * N_zc the largest prime below M, for M >= 36 --, times entry (n n_cs 24 / n_cs_max) mod 24 of the 24-point unit circle where
+ * the port's cyclic shift is not 0.
+ *
+ * Estimate: per receive port and antenna port the LS products y conj(r) of every symbol, added in symbol order and scaled by
+ * float(1.0 / nof_symbols) when there is more than one symbol; the time alignment of each path from the 4096-point inverse DFT of
+ * the products at inputs comb n: the largest |X|^2 of bins [0, W) against bins [4096 - W, 4096), W = floor(4096 / (n_cs_max
+ * comb)) = 256 or 85, the lower bin among equals, the delay on ties; their average in double, antenna port outer and receive port
+ * inner; then the products times entry round(1024 (n ps + offset) / 2 pi) mod 1024 of the 1024-point unit circle with ps =
+ * float(2 pi ta scs comb) and offset = ps (k0 mod comb) / comb, the index evaluated in single precision operation by operation;
+ * their mean is the coefficient.  The reference never writes noise_variance: it is not part of the result.  Normal cyclic
+ * prefix.  Receive port i reads grid port rx_ports[i]. */
+typedef struct nrphy_srs_cfg {
+  uint32_t numerology;                /* 0..4 */
+  uint32_t nof_antenna_ports;         /* 1, 2, 4 */
+  uint32_t nof_symbols;               /* 1, 2, 4 */
+  uint32_t start_symbol;              /* start_symbol + nof_symbols <= 14 */
+  uint32_t configuration_index;       /* C_SRS, 0..63 */
+  uint32_t sequence_id;               /* 0..1023 */
+  uint32_t bandwidth_index;           /* B_SRS, 0..3 */
+  uint32_t comb_size;                 /* 2, 4 */
+  uint32_t comb_offset;               /* < comb_size */
+  uint32_t cyclic_shift;              /* 0..7 with comb 2, 0..11 with comb 4 */
+  uint32_t freq_position;             /* n_RRC, 0..67 */
+  uint32_t freq_shift;                /* n_shift, 0..268 */
+  uint32_t freq_hopping;              /* b_hop, 0..3; must not be below bandwidth_index (no frequency hopping) */
+  uint32_t hopping;                   /* group or sequence hopping: must be 0 */
+  uint32_t nof_rx_ports;              /* 1..4 */
+  uint32_t rx_ports[NRPHY_MAX_PORTS]; /* grid port of receive port i */
+} nrphy_srs_cfg_t;
+typedef struct nrphy_srs_result { /* one per SRS */
+  float   h_re[4][4], h_im[4][4];     /* [rx][tx]; zeros beyond the configured ports */
+  int32_t ta_bins[4][4];              /* [rx][tx]: the path's time alignment in bins of the 4096-point inverse DFT (1 / (4096 scs)
+                                         seconds each), negative for an advance; zeros beyond the configured ports */
+  double  time_alignment_s;           /* the average over the paths */
+  uint32_t reserved_[2];
+} nrphy_srs_result_t;
+typedef struct nrphy_srs_plan nrphy_srs_plan_t;
+/* NRPHY_OK, or NRPHY_ERR_ARGUMENT for what srs_validator_generic_impl::is_valid refuses -- a comb offset not below the comb size,
+ * a cyclic shift above 7 with comb 2, freq_hopping < bandwidth_index, hopping != 0, no receive port -- and for what the
+ * estimator's assertions refuse: symbols beyond the slot; a field outside its range; port or symbol counts other than 1, 2 or 4;
+ * a comb other than 2 or 4; more than 4 receive ports, a repeated one or one outside the grid; a last subcarrier k0 + comb (M - 1)
+ * beyond the grid for any antenna port.  No device work. */
+int nrphy_srs_validate(const nrphy_srs_cfg_t* cfg, uint32_t grid_nof_ports, uint32_t grid_nof_subc);
+/* The values of get_srs_information for one antenna port of a configuration whose fields are in range (the grid is not looked at):
+ * sequence length M, first subcarrier k0, the port's cyclic shift and its maximum, the sequence group.  No device work. */
+int nrphy_srs_info(const nrphy_srs_cfg_t* cfg, uint32_t antenna_port, uint32_t* sequence_length, uint32_t* initial_subcarrier,
+                   uint32_t* n_cs, uint32_t* n_cs_max, uint32_t* u);
+/* n SRS; SRS i reads grid grid_index[i] of [nof_grids][grid_nof_ports][14][grid_nof_subc] cbf16, the buffer nrphy_pusch_chest_run,
+ * nrphy_pucch_run and nrphy_pf2_run read.  Validates every configuration and computes everything that does not depend on the
+ * grid: per antenna port M, k0 and the cyclic-shift step, N_zc and the Zadoff-Chu root (in single precision, as zc_sequence_q
+ * does), the search window, the unit circles (blocking). */
+int nrphy_srs_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_srs_cfg_t* cfgs, const uint32_t* grid_index, uint32_t nof_grids,
+                          uint32_t grid_nof_ports, uint32_t grid_nof_subc, nrphy_srs_plan_t** plan);
+int nrphy_srs_plan_destroy(nrphy_srs_plan_t* plan);
+/* Two launches on `stream`, each of one workgroup per (SRS, receive port, antenna port): the per-path time alignment, then the
+ * common time alignment, its compensation and the coefficients.  d_result: [n], 8-byte aligned; every byte of it is written.
+ * Asynchronous; allocates nothing, touches no host memory, uses no atomics and no scratch (capturable; two runs give identical
+ * bytes). */
+int nrphy_srs_run(nrphy_srs_plan_t* plan, const void* d_grid, nrphy_srs_result_t* d_result, void* stream);
+/* One SRS from and to host memory (blocking, on the GPU): grid [grid_nof_ports][14][grid_nof_subc] cbf16 -> result. */
+int nrphy_srs_host(nrphy_ctx_t* ctx, const nrphy_srs_cfg_t* cfg, const void* grid, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
+                   nrphy_srs_result_t* result);
+/* The low-PAPR sequence of one antenna port, cyclic shift included, from the device generator the estimator's kernels use
+ * (blocking): out [M] complex float (re, im). */
+int nrphy_srs_sequence_host(nrphy_ctx_t* ctx, const nrphy_srs_cfg_t* cfg, uint32_t antenna_port, float* out);
+
 /* ---- receive side: UL-SCH demultiplexer (UCI on PUSCH, TS 38.212 Section 6.2.7) -----------------------------------------------
  * Replaces ulsch_demultiplex::demultiplex + set_csi_part2 and the pusch_codeword_buffer it returns
  * (R/lib/phy/upper/channel_processors/pusch/ulsch_demultiplex_impl.cpp): the descrambled soft bits of a codeword, as

@@ -306,6 +306,36 @@ def make_pf2(*, starting_prb, nof_prb, nof_symbols, start_symbol=0, bwp_size_rb=
     return c
 
 
+class SrsCfg(C.Structure):
+    """nrphy_srs_cfg_t (srs_estimator_configuration)."""
+    _fields_ = [("numerology", C.c_uint32), ("nof_antenna_ports", C.c_uint32), ("nof_symbols", C.c_uint32), ("start_symbol", C.c_uint32),
+                ("configuration_index", C.c_uint32), ("sequence_id", C.c_uint32), ("bandwidth_index", C.c_uint32),
+                ("comb_size", C.c_uint32), ("comb_offset", C.c_uint32), ("cyclic_shift", C.c_uint32), ("freq_position", C.c_uint32),
+                ("freq_shift", C.c_uint32), ("freq_hopping", C.c_uint32), ("hopping", C.c_uint32), ("nof_rx_ports", C.c_uint32),
+                ("rx_ports", C.c_uint32 * MAX_PORTS)]
+
+
+class SrsResult(C.Structure):
+    """nrphy_srs_result_t: one per SRS; the matrices are [rx][tx]."""
+    _fields_ = [("h_re", (C.c_float * 4) * 4), ("h_im", (C.c_float * 4) * 4), ("ta_bins", (C.c_int32 * 4) * 4),
+                ("time_alignment_s", C.c_double), ("reserved_", C.c_uint32 * 2)]
+
+
+def make_srs(*, configuration_index, bandwidth_index=0, comb_size=2, comb_offset=0, cyclic_shift=0, nof_antenna_ports=1, nof_symbols=1,
+             start_symbol=13, sequence_id=0, freq_position=0, freq_shift=0, freq_hopping=None, hopping=0, numerology=0, rx_ports=(0,)):
+    """An SrsCfg from plain values (freq_hopping None: b_hop = 3, no frequency hopping whatever the bandwidth index)."""
+    c = SrsCfg()
+    c.numerology, c.nof_antenna_ports, c.nof_symbols, c.start_symbol = numerology, nof_antenna_ports, nof_symbols, start_symbol
+    c.configuration_index, c.sequence_id, c.bandwidth_index = configuration_index, sequence_id, bandwidth_index
+    c.comb_size, c.comb_offset, c.cyclic_shift = comb_size, comb_offset, cyclic_shift
+    c.freq_position, c.freq_shift = freq_position, freq_shift
+    c.freq_hopping, c.hopping = 3 if freq_hopping is None else freq_hopping, hopping
+    c.nof_rx_ports = len(rx_ports)
+    for i, q in enumerate(rx_ports[:MAX_PORTS]):
+        c.rx_ports[i] = q
+    return c
+
+
 UCI_STATUS_UNKNOWN, UCI_STATUS_VALID, UCI_STATUS_INVALID = 0, 1, 2  # uci_status
 
 
@@ -792,6 +822,13 @@ def declare(lib, prefix="nrphy_"):
     sig("pf2_plan_destroy", i32, vp)
     sig("pf2_run", i32, vp, vp, vp, vp, vp, vp, vp, vp, vp)
     sig("pf2_host", i32, vp, P(Pf2Cfg), vp, u32, u32, vp, P(u32), P(Pf2Csi), vp, vp, vp)
+    sig("srs_validate", i32, P(SrsCfg), u32, u32)
+    sig("srs_info", i32, P(SrsCfg), u32, P(u32), P(u32), P(u32), P(u32), P(u32))
+    sig("srs_plan_create", i32, vp, u32, P(SrsCfg), P(u32), u32, u32, u32, P(vp))
+    sig("srs_plan_destroy", i32, vp)
+    sig("srs_run", i32, vp, vp, vp, vp)
+    sig("srs_host", i32, vp, P(SrsCfg), vp, u32, u32, P(SrsResult))
+    sig("srs_sequence_host", i32, vp, P(SrsCfg), u32, vp)
     sig("ulsch_demux_validate", i32, P(UlschDemuxCfg))
     sig("ulsch_demux_sizes", i32, P(UlschDemuxCfg), P(UlschDemuxSizes))
     sig("ulsch_demux_plan_create", i32, vp, u32, P(UlschDemuxCfg), P(u64), P(u64), P(u64), P(u64), P(u64), P(vp))
@@ -848,4 +885,6 @@ ABI_SYMBOLS = [
     "nrphy_ulsch_demux_validate", "nrphy_ulsch_demux_sizes", "nrphy_ulsch_demux_plan_create", "nrphy_ulsch_demux_plan_destroy",
     "nrphy_ulsch_demux_run", "nrphy_ulsch_demultiplex_host",
     "nrphy_pf2_validate", "nrphy_pf2_sizes", "nrphy_pf2_plan_create", "nrphy_pf2_plan_destroy", "nrphy_pf2_run", "nrphy_pf2_host",
+    "nrphy_srs_validate", "nrphy_srs_info", "nrphy_srs_plan_create", "nrphy_srs_plan_destroy", "nrphy_srs_run", "nrphy_srs_host",
+    "nrphy_srs_sequence_host",
 ]

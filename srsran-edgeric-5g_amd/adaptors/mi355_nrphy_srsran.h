@@ -42,6 +42,10 @@
 #include "srsran/phy/upper/channel_processors/channel_processor_factories.h"
 #include "srsran/phy/upper/channel_processors/pdsch_processor.h"
 #include "srsran/phy/upper/signal_processors/nzp_csi_rs_generator.h"
+#include "srsran/phy/upper/signal_processors/srs/srs_estimator.h"
+#include "srsran/phy/upper/signal_processors/srs/srs_estimator_configuration.h"
+#include "srsran/phy/upper/signal_processors/srs/srs_estimator_configuration_validator.h"
+#include "srsran/phy/upper/signal_processors/srs/srs_estimator_result.h"
 #include "srsran/ran/csi_rs/csi_rs_pattern.h"
 #include "srsran/srsvec/bit.h"
 
@@ -62,11 +66,14 @@
 #include "srsran/phy/upper/vrb_to_prb_mapper.h"
 #include "srsran/ran/sch/sch_dmrs_power.h"
 
+#include <algorithm>
 #include <array>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -2405,6 +2412,101 @@ private:
   std::vector<const uint8_t*>     tbs;
   std::vector<std::vector<float>> weights;
   std::vector<srsran::cbf16_t>    staging;
+};
+
+// ---- SRS channel estimator --------------------------------------------------------------------------------------------------
+/// srs_estimator_configuration -> POD.  Receive port i of the POD reads grid port \c rx_ports[i].
+inline nrphy_srs_cfg_t to_pod(const srsran::srs_estimator_configuration& config)
+{
+  const srsran::srs_resource_configuration& r = config.resource;
+  nrphy_srs_cfg_t                           c;
+  std::memset(&c, 0, sizeof(c));
+  c.numerology          = config.slot.numerology();
+  c.nof_antenna_ports   = static_cast<unsigned>(r.nof_antenna_ports);
+  c.nof_symbols         = static_cast<unsigned>(r.nof_symbols);
+  c.start_symbol        = r.start_symbol.value();
+  c.configuration_index = r.configuration_index.value();
+  c.sequence_id         = r.sequence_id.value();
+  c.bandwidth_index     = r.bandwidth_index.value();
+  c.comb_size           = static_cast<unsigned>(r.comb_size);
+  c.comb_offset         = r.comb_offset.value();
+  c.cyclic_shift        = r.cyclic_shift.value();
+  c.freq_position       = r.freq_position.value();
+  c.freq_shift          = r.freq_shift.value();
+  c.freq_hopping        = r.freq_hopping.value();
+  c.hopping             = static_cast<unsigned>(r.hopping);
+  c.nof_rx_ports        = config.ports.size();
+  for (unsigned i = 0; i != config.ports.size() && i != NRPHY_MAX_PORTS; ++i) {
+    c.rx_ports[i] = config.ports[i];
+  }
+  return c;
+}
+
+/// srs_estimator_configuration_validator over nrphy_srs_validate with the largest grid, 275 PRB (the grid is not known here; the
+/// estimator adaptor validates against the grid it is given).  Where it differs from srs_validator_generic_impl::is_valid: that
+/// one looks at the comb offset, the cyclic shift, the two kinds of hopping and the port list only, so it accepts a
+/// configuration whose last subcarrier lies beyond 275 PRB, or with more than four receive ports, and leaves it to the
+/// estimator's assertions and the grid reader; this one refuses both, as everything else the estimator asserts on.
+class srs_estimator_validator_adaptor : public srsran::srs_estimator_configuration_validator
+{
+public:
+  bool is_valid(const srsran::srs_estimator_configuration& config) const override
+  {
+    if (config.ports.empty() || config.ports.size() > NRPHY_MAX_PORTS) {
+      return false;
+    }
+    const nrphy_srs_cfg_t c = to_pod(config);
+    return nrphy_srs_validate(&c, 256, srsran::MAX_RB * srsran::NRE) == NRPHY_OK;
+  }
+};
+
+/// srs_estimator over nrphy_srs_host: the SRS symbols of the receive ports are read through the reader into a staging grid of
+/// nof_rx_ports ports (receive port i becomes grid port i), the estimate runs on the device.  The bounds and the resolution of
+/// the time alignment depend on the configuration alone and are computed here, as time_alignment_estimator_dft_impl computes
+/// them -- the reference's minimum starts from numeric_limits<double>::min() under a max() and therefore stays there; the
+/// reference never writes noise_variance, and neither does this.  On failure the matrix is zero.
+class srs_estimator_adaptor : public srsran::srs_estimator
+{
+public:
+  explicit srs_estimator_adaptor(std::shared_ptr<context> ctx_) : ctx(std::move(ctx_)) {}
+  srsran::srs_estimator_result estimate(const srsran::resource_grid_reader& grid, const srsran::srs_estimator_configuration& config) override
+  {
+    using namespace srsran;
+    nrphy_srs_cfg_t c        = to_pod(config);
+    const unsigned  nof_subc = grid.get_nof_subc(), nof_rx = std::min<unsigned>(c.nof_rx_ports, NRPHY_MAX_PORTS);
+    staging.assign(static_cast<size_t>(nof_rx) * MAX_NSYMB_PER_SLOT * nof_subc, cbf16_t());
+    for (unsigned i = 0; i != nof_rx; ++i) {
+      for (unsigned l = c.start_symbol; l < c.start_symbol + c.nof_symbols && l < MAX_NSYMB_PER_SLOT; ++l) {
+        grid.get(span<cbf16_t>(&staging[(static_cast<size_t>(i) * MAX_NSYMB_PER_SLOT + l) * nof_subc], nof_subc), config.ports[i], l, 0);
+      }
+      c.rx_ports[i] = i;
+    }
+    srs_estimator_result result;
+    result.channel_matrix = srs_channel_matrix(config.ports.size(), c.nof_antenna_ports);
+    nrphy_srs_result_t r;
+    std::memset(&r, 0, sizeof(r));
+    int rc = nrphy_srs_host(ctx->get(), &c, staging.data(), nof_rx, nof_subc, &r);
+    report_failure("nrphy_srs_host", rc);
+    for (unsigned i = 0; i != nof_rx; ++i) {
+      for (unsigned p = 0; p != c.nof_antenna_ports && p != NRPHY_MAX_PORTS; ++p) {
+        result.channel_matrix.set_coefficient(rc == NRPHY_OK ? cf_t(r.h_re[i][p], r.h_im[i][p]) : cf_t(), i, p);
+      }
+    }
+    // max_ta and max_ta_samples as the estimator and time_alignment_estimator_dft_impl evaluate them, in double.
+    const unsigned scs_khz        = 15U << c.numerology, n_cs_max = c.comb_size == 4 ? 12 : 8;
+    const double   max_ta         = 1.0 / static_cast<double>(n_cs_max * scs_khz * 1000 * c.comb_size);
+    const unsigned max_ta_samples = static_cast<unsigned>(std::floor(max_ta * static_cast<double>(scs_khz * 1000 * 4096)));
+    const double   rate           = static_cast<double>(4096 * scs_khz * 1000);
+    result.time_alignment.time_alignment = rc == NRPHY_OK ? r.time_alignment_s : 0.0;
+    result.time_alignment.min            = std::numeric_limits<double>::min();
+    result.time_alignment.max            = static_cast<double>(max_ta_samples) / rate;
+    result.time_alignment.resolution     = 1.0 / rate;
+    return result;
+  }
+
+private:
+  std::shared_ptr<context>     ctx;
+  std::vector<srsran::cbf16_t> staging;
 };
 
 } // namespace mi355

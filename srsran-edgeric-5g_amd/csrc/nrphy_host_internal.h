@@ -1,5 +1,5 @@
 // Host-side internals shared by the translation units behind the C ABI (nrphy_host.cpp, dl_control_host.cpp, pdsch_async.cpp,
-// dl_slot_async.cpp, pusch_demod_host.cpp, pusch_chest_host.cpp, prach_host.cpp, prach_demod_host.cpp, pucch_host.cpp, pucch2_host.cpp, uci_host.cpp): the context, its staging buffers, small helpers.  Not part
+// dl_slot_async.cpp, pusch_demod_host.cpp, pusch_chest_host.cpp, prach_host.cpp, prach_demod_host.cpp, pucch_host.cpp, pucch2_host.cpp, srs_host.cpp, uci_host.cpp): the context, its staging buffers, small helpers.  Not part
 // of the ABI.
 #pragma once
 

@@ -593,6 +593,37 @@ struct Pf2Launch {
   uint32_t                  grid_nof_ports, grid_nof_subc, n;
 };
 hipError_t launch_pf2(const Pf2Launch& p, hipStream_t stream);
+// ---- SRS channel estimator (receive side) ----------------------------------------------------------------------------------
+constexpr uint32_t SRS_DFT_SIZE    = 4096;                    // the time alignment estimator's inverse DFT
+constexpr uint32_t SRS_MAX_SEQ     = 272 * NRPHY_NRE / 2;     // 1632: C_SRS 63, B_SRS 0, comb 2
+constexpr uint32_t SRS_CEXP_SIZE   = 1024;                    // the compensation's unit circle
+constexpr uint32_t SRS_CS_SIZE     = 24;                      // the cyclic shifts' unit circle
+constexpr uint32_t SRS_PATHS       = NRPHY_MAX_PORTS * NRPHY_MAX_PORTS; // workgroups per SRS: [rx][tx]
+struct SrsDesc {                                              // one SRS of a plan
+  uint32_t grid_index, nof_rx_ports, nof_tx_ports;
+  uint32_t first_symbol, nof_symbols;
+  uint32_t comb, M;                                           // sequence length, common to the antenna ports
+  uint32_t window;                                            // searched bins on each side: floor(max_ta scs 4096)
+  uint32_t n_zc, q;                                           // M >= 36: largest prime below M and the Zadoff-Chu root
+  uint32_t scs_hz;
+  float    symbol_scale;                                      // float(1.0 / nof_symbols)
+  uint32_t rx_ports[NRPHY_MAX_PORTS];
+  uint32_t k0[NRPHY_MAX_PORTS];                               // first subcarrier of antenna port p
+  uint32_t cs_step[NRPHY_MAX_PORTS];                          // n_cs 24 / n_cs_max of antenna port p
+  int8_t   phi[24];                                           // M = 12, 24: phi(n) of group u
+};
+struct SrsLaunch {
+  const SrsDesc*      desc;
+  const float2*       twiddle;                                // the context's exp(+j 2 pi k / 4096)
+  const float2*       cs_table;                               // [SRS_CS_SIZE] polar(1, float(2 pi) n / 24)
+  const float2*       cexp_table;                             // [SRS_CEXP_SIZE]
+  const uint32_t*     grid;
+  nrphy_srs_result_t* result;                                 // [n]
+  uint32_t            grid_nof_ports, grid_nof_subc, n;
+};
+hipError_t launch_srs(const SrsLaunch& p, hipStream_t stream);
+// out[n] = the sequence of antenna port `port` of desc[0], n < M.
+hipError_t launch_srs_sequence(const SrsDesc* desc, const float2* cs_table, uint32_t port, uint32_t M, float2* out, hipStream_t stream);
 hipError_t launch_grid_put(const uint32_t* d_index, const uint32_t* d_value, uint32_t n, uint32_t* d_grid, hipStream_t stream);
 
 // ---- UCI decoder (receive side: short blocks and polar) -------------------------------------------------------------------

@@ -542,6 +542,23 @@ class Context:
                                        llr.ctypes.data), "nrphy_pf2_host")
         return {"message": message, "status": int(status.value), "csi": csi, "meas": list(meas), "llr": llr, "ch_est": ce}
 
+    def srs_host(self, cfg, grid):
+        """srs_estimator::estimate for one SRS: grid [ports][14][subc] raw cbf16 words -> abi.SrsResult."""
+        grid = np.ascontiguousarray(grid, dtype=np.uint32)
+        result = abi.SrsResult()
+        _check(self.lib.nrphy_srs_host(self.handle, C.byref(cfg), grid.ctypes.data, grid.shape[0], grid.shape[-1], C.byref(result)),
+               "nrphy_srs_host")
+        return result
+
+    def srs_sequence_host(self, cfg, antenna_port):
+        """The low-PAPR sequence of one antenna port, cyclic shift included, from the estimator's device generator: complex64 [M]."""
+        info = srs_info(cfg, antenna_port)
+        if info is None:
+            raise ValueError("nrphy_srs_info refuses the configuration")
+        out = np.zeros(info["sequence_length"], np.complex64)
+        _check(self.lib.nrphy_srs_sequence_host(self.handle, C.byref(cfg), antenna_port, out.ctypes.data), "nrphy_srs_sequence_host")
+        return out
+
     def uci_decode_host(self, cfg, llr, fill=0):
         """uci_decoder::decode for one message: llr int8 [llr_length] -> (message uint8 [message_length], one bit per byte, status).
         Bytes the decoder does not write (a second block behind a failed first one) hold `fill`."""
@@ -770,6 +787,37 @@ class PucchPlan:
             pass
 
 
+class SrsPlan:
+    """nrphy_srs_plan: sounding reference signals over a batch of received grids (the grid buffer PuschChestPlan, PucchPlan and
+    Pf2Plan read); run() writes every SRS's channel matrix and time alignment with two launches."""
+
+    def __init__(self, ctx, cfgs, grid_indices, nof_grids, nof_ports, nof_subc):
+        self.ctx = ctx
+        n = len(cfgs)
+        arr = (abi.SrsCfg * n)(*cfgs)
+        gidx = (C.c_uint32 * n)(*grid_indices)
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_srs_plan_create(ctx.handle, n, arr, gidx, nof_grids, nof_ports, nof_subc, C.byref(h)),
+               "nrphy_srs_plan_create")
+        self.handle = h
+        self.n = n
+
+    def run(self, d_grid, d_result, stream=None):
+        """d_result: [n] abi.SrsResult (208 bytes each), 8-byte aligned."""
+        _check(self.ctx.lib.nrphy_srs_run(self.handle, _dptr(d_grid), _dptr(d_result), _stream(stream)), "nrphy_srs_run")
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.ctx.lib.nrphy_srs_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Pf2Plan:
     """nrphy_pf2_plan: PUCCHs of format 2 over a batch of received grids (the grid buffer PuschChestPlan and PucchPlan read);
     run() writes every PUCCH's soft bits, payload bits, status and channel state information with two launches."""
@@ -983,6 +1031,19 @@ def pucch_validate(cfg, grid_nof_ports, grid_nof_subc):
 def pf2_validate(cfg, grid_nof_ports, grid_nof_subc):
     """nrphy_pf2_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
     return int(load().nrphy_pf2_validate(C.byref(cfg), grid_nof_ports, grid_nof_subc))
+
+
+def srs_validate(cfg, grid_nof_ports, grid_nof_subc):
+    """nrphy_srs_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_srs_validate(C.byref(cfg), grid_nof_ports, grid_nof_subc))
+
+
+def srs_info(cfg, antenna_port):
+    """nrphy_srs_info: get_srs_information's values as a dict, or None for a configuration out of range (host only)."""
+    v = [C.c_uint32() for _ in range(5)]
+    if load().nrphy_srs_info(C.byref(cfg), antenna_port, *[C.byref(x) for x in v]) != abi.OK:
+        return None
+    return dict(zip(("sequence_length", "initial_subcarrier", "n_cs", "n_cs_max", "u"), (int(x.value) for x in v)))
 
 
 def pf2_sizes(cfg):
