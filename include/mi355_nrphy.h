@@ -200,6 +200,11 @@ uint64_t nrphy_pdsch_plan_codeword_offset(const nrphy_pdsch_plan_t* plan, uint32
  * length one set -- the slots of one UE in a batch, for instance.  Either pointer may be NULL. */
 int nrphy_pdsch_plan_nof_sequences(const nrphy_pdsch_plan_t* plan, uint32_t* scrambling, uint32_t* dmrs);
 
+/* The form in which a run of the plan hands its distinct scrambling sequences from the prologue to the codeblock
+ * waves: 1 = whole words (the sequences of the plan fit a level-2 cache), 0 = one 31-word seed per work item,
+ * which the waves expand.  The outputs do not depend on it.  -1: plan is NULL. */
+int nrphy_pdsch_plan_scrambling_form(const nrphy_pdsch_plan_t* plan);
+
 /* Runs the whole PDSCH path of every PDU of the plan: TB CRC, segmentation, CB CRC, LDPC encoding,
  * rate matching, bit interleaving, scrambling, modulation, layer mapping, precoding, RE mapping and
  * DM-RS generation.  d_grid may be NULL (encode only, seam B semantics).  Optional taps, either may be

@@ -48,4 +48,6 @@ out = {"pdus": n, "steps": steps, "warmup": warmup, "prologue_ms": round(ms[0], 
        "run_ms_events": round(ms[3], 4), "ms_per_run_wall": round(1e3 * (t1 - t0) / steps, 4), "timed_runs": runs}
 if hasattr(plan, "nof_sequences") and getattr(ctx.lib, "nrphy_pdsch_plan_nof_sequences", None) is not None:
     out["nof_sequences"] = plan.nof_sequences
+if getattr(ctx.lib, "nrphy_pdsch_plan_scrambling_form", None) is not None:
+    out["scrambling_form"] = plan.scrambling_form
 print(json.dumps(out))

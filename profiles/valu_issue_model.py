@@ -38,7 +38,7 @@ COSTS = [
 DEFAULT = (4.33, "other VOP3 / DPP / SDWA")   # v_med3, v_alignbit, v_mad_u32_u24, v_bfe, v_lshl_or, v_add3, v_cndmask, v_perm ...
 
 KERNELS = {   # bench.py's name -> (source, mangled-name pattern, contraction flag)
-    "codeblock_kernel": ("pdsch_kernels.hip", r"codeblock_kernel_tILi8ELi4E", "-ffp-contract=off"),
+    "codeblock_kernel": ("pdsch_kernels.hip", r"codeblock_words_kernel_tILi8ELi4E", "-ffp-contract=off"),
     "prologue_kernel": ("pdsch_kernels.hip", r"prologue_kernel", "-ffp-contract=off"),
     "ofdm_kernel<4096>": ("ofdm_kernels.hip", r"ofdm_kernelILi4096ELi1ELb0E", "-ffp-contract=off"),
     "ofdm_kernel<4096, ci16>": ("ofdm_kernels.hip", r"ofdm_kernelILi4096ELi2ELb1E", "-ffp-contract=off"),

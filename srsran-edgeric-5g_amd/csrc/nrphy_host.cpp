@@ -321,10 +321,15 @@ struct SeqKeyHash {
   }
 };
 struct SeqShare {
-  uint32_t seed_first;      // PduDev::seed_first of the PDUs that share the scrambling sequence
+  uint32_t seed_first;      // PduDev::seed_first of the PDUs that share the scrambling sequence (seeds form)
+  uint32_t scr_word_offset; // PduDev::scr_word_offset of the same PDUs (words form)
   uint32_t dmrs_seq_offset; // PduDev::dmrs_seq_offset of those that share the DM-RS sequences
 };
 constexpr uint8_t SEQ_NEW_SCR = 1, SEQ_NEW_DMRS = 2;
+// A plan stores its distinct scrambling sequences as words while they take no more than this: one XCD's L2, so that the words,
+// written once by the prologue, are served from every L2 like the x1 table.  Beyond it a plan stores seeds (a batch of 1024
+// PDUs that share nothing would write and read back 121 MB of sequences).
+constexpr uint64_t SCR_WORDS_BUDGET_BYTES = 4ULL << 20;
 
 } // namespace
 
@@ -349,8 +354,9 @@ struct nrphy_pdsch_plan {
   ZeroWork*             d_zero_work = nullptr;
   ZeroSeg*              d_zero_segs = nullptr;
   uint32_t*             d_scr = nullptr;    // scrambling sequences, rewritten by every run's prologue
-  uint64_t              scr_words = 0;   // words of the run's scratch: the distinct DM-RS sequences, then the seeds of the distinct scrambling sequences
-  uint64_t              seed_offset = 0; // where the seeds start
+  uint64_t              scr_words = 0;   // words of the run's scratch: the distinct DM-RS sequences, then the distinct scrambling sequences (seeds or words)
+  uint64_t              seed_offset = 0; // where the scrambling sequences start
+  bool                  scr_as_words = false; // the form of the scrambling sequences: words (true) or seeds (PdschLaunch::scr_as_words)
   uint32_t              n_zero_work = 0;
   bool                  encode_only = false;   // seam B plan: no RE mapping, nrphy_pdsch_run only with d_grid = NULL
   bool                  dmrs_separate = false; // DM-RS must overwrite data RE: keep it in its own, later launch
@@ -680,6 +686,7 @@ Tunables read_tunables()
   t.cb_dispatch       = number("NRPHY_CB_DISPATCH", 0);
   t.crc_regions       = number("NRPHY_CRC_REGIONS", 0);
   t.scr_parts_big     = number("NRPHY_SCR_PARTS_BIG", 0);
+  t.scr_words         = number("NRPHY_SCR_WORDS", -1);
   t.extras_nt         = (uint32_t)number("NRPHY_EXTRAS_NT", 1);
   t.prologue_order    = (uint32_t)number("NRPHY_PROLOGUE_ORDER", 0);
   t.decoder_pairs     = number("NRPHY_DECODER_PAIRS", -1);
@@ -933,6 +940,9 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus,
   std::unordered_map<SeqKey, SeqShare, SeqKeyHash> seq_shares; // the sequences earlier PDUs of the plan ask for
   std::vector<uint8_t>  seq_fresh;      // per PDU: SEQ_NEW_SCR / SEQ_NEW_DMRS -- the first PDU that asks for the sequence generates it
   uint32_t              seed_slots = 0; // seed slots handed out: one per work item of every distinct scrambling sequence
+  uint64_t              seq_words = 0;  // the same sequences as words: where the next one would start, and their plain sum (the rule)
+  uint64_t              seq_words_sum = 0;
+  bool                  seq_words_fit = true; // every sequence within the x1 table and the 32-bit offsets
   std::vector<std::vector<uint32_t>> pdus_of_grid(nof_grids);
   std::vector<float>    weights;
   std::vector<uint16_t> re_table;
@@ -1167,8 +1177,8 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus,
     plan->lds_graph_words = std::max<uint32_t>(
         plan->lds_graph_words, (48U + ctx->graphs[pd.graph].row_ptr[std::min<uint32_t>(pd.nof_rows, MAX_BG_ROWS)] + 3U) & ~3U);
     // Scrambling sequence of the PDU: one word per 32 codeword bits plus the word a misaligned read runs into, plus the
-    // length of a seed (the last work item's 31 words may reach beyond the codeword; the sequence simply goes on).  Only
-    // the work items' seeds are stored (behind the DM-RS sequences, below).
+    // length of a seed (the last work item's 31 words may reach beyond the codeword; the sequence simply goes on).  Stored
+    // are these words or only the work items' seeds, one form per plan (behind the DM-RS sequences, below).
     pd.scr_words  = (d.codeword_bits + 31U) / 32U + 1U + 31U;
     // One DM-RS sequence per DM-RS symbol.
     pd.dmrs_seq_words  = (12U * (pd.end_prb - pd.dmrs_ref_rb) + 31U) / 32U + 1U;
@@ -1181,7 +1191,7 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus,
       const uint32_t nof_dmrs_words = (uint32_t)(((uint64_t)pd.dmrs_seq_words * (unsigned)__builtin_popcount(pdu.dmrs_symbol_mask) + 3U) & ~3ULL);
       const uint32_t nof_items      = (uint32_t)(work.size() - work_before);
       uint8_t        fresh          = (uint8_t)(SEQ_NEW_SCR | (nof_dmrs_words != 0 ? SEQ_NEW_DMRS : 0));
-      SeqShare       share          = {seed_slots, (uint32_t)plan->scr_words};
+      SeqShare       share          = {seed_slots, (uint32_t)seq_words, (uint32_t)plan->scr_words};
       if (n_pdu != 1) {
         SeqKey key;
         key.scr  = {pd.c_init, pd.C, pd.n_short, pd.e_short, pd.e_long, lq};
@@ -1201,7 +1211,8 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus,
           half.dmrs[1] = ~0U; // (no DM-RS sequence has this length)
           auto scr_known = seq_shares.insert({half, share});
           if (!scr_known.second) {
-            share.seed_first = scr_known.first->second.seed_first;
+            share.seed_first      = scr_known.first->second.seed_first;
+            share.scr_word_offset = scr_known.first->second.scr_word_offset;
             fresh &= (uint8_t)~SEQ_NEW_SCR;
           }
           if (nof_dmrs_words != 0) {
@@ -1217,9 +1228,13 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus,
         }
       }
       pd.seed_first      = share.seed_first;
+      pd.scr_word_offset = share.scr_word_offset;
       pd.dmrs_seq_offset = share.dmrs_seq_offset;
       if (fresh & SEQ_NEW_SCR) {
         seed_slots += nof_items;
+        seq_words_sum += pd.scr_words;
+        seq_words += (pd.scr_words + 15U) & ~15ULL; // every sequence starts a 64-byte line
+        seq_words_fit = seq_words_fit && pd.scr_words <= (uint32_t)GOLD_X1_WORDS && seq_words <= 0xFFFFFFFFULL;
         ++plan->n_scr_seq;
       }
       if (fresh & SEQ_NEW_DMRS) {
@@ -1427,10 +1442,18 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus,
     for (size_t k = work.size(); k-- != 0;) {
       plan->pdus[work[k].pdu].item_first = (uint32_t)k;
     }
-    // The seeds of the distinct scrambling sequences, 32 words per work item, behind the DM-RS sequences.
-    plan->scr_words  = (plan->scr_words + 3U) & ~3ULL;
+    // The distinct scrambling sequences behind the DM-RS sequences: their words while those stay within the budget, else their
+    // seeds, 32 words per work item.  One form per plan, so that a launch has one.  The sharing key is the same in both forms
+    // (the words alone would need only c_init).  (A/B and test knob: NRPHY_SCR_WORDS = 0 always seeds, 1 always words.)
+    const uint64_t words_offset = (plan->scr_words + 15U) & ~15ULL; // the words start a 64-byte line
+    plan->scr_as_words = seq_words_fit && (ctx->tune.scr_words < 0 ? seq_words_sum * 4U <= SCR_WORDS_BUDGET_BYTES : ctx->tune.scr_words != 0);
+    if (plan->scr_as_words && place != nullptr &&
+        words_offset + seq_words + std::max<size_t>(4, crc_work.size()) > place->scratch_capacity_words) {
+      plan->scr_as_words = false; // caller-owned scratch sized for seeds
+    }
+    plan->scr_words   = plan->scr_as_words ? words_offset : (plan->scr_words + 3U) & ~3ULL;
     plan->seed_offset = plan->scr_words;
-    plan->scr_words += 32ULL * seed_slots;
+    plan->scr_words += plan->scr_as_words ? seq_words : 32ULL * seed_slots;
     // The codeblock waves load 2 * NRPHY_MAX_PORTS * layers weights whatever the port count (pdsch_kernels.hip, phase_b).
     weights.insert(weights.end(), 2 * NRPHY_MAX_PORTS * NRPHY_MAX_PORTS, 0.0F);
   }
@@ -1555,6 +1578,11 @@ extern "C" int nrphy_pdsch_plan_nof_sequences(const nrphy_pdsch_plan_t* plan, ui
   return NRPHY_OK;
 }
 
+extern "C" int nrphy_pdsch_plan_scrambling_form(const nrphy_pdsch_plan_t* plan)
+{
+  return plan == nullptr ? -1 : (plan->scr_as_words ? 1 : 0);
+}
+
 extern "C" uint64_t nrphy_pdsch_plan_codeword_bits(const nrphy_pdsch_plan_t* plan)
 {
   return plan ? plan->cw_bits : 0;
@@ -1593,7 +1621,8 @@ extern "C" int nrphy_pdsch_run(nrphy_pdsch_plan_t* plan, const uint8_t* d_tb, vo
   p.zero_work          = plan->d_zero_work;
   p.zero_segs          = plan->d_zero_segs;
   p.scr                = plan->d_scr;
-  p.scr_seed           = plan->d_scr + plan->seed_offset;
+  p.scr_seq            = plan->d_scr + plan->seed_offset;
+  p.scr_as_words       = plan->scr_as_words ? 1U : 0U;
   p.n_zero_work        = (d_grid != nullptr && zero_grids) ? plan->n_zero_work : 0;
   p.zero_fill          = (d_grid != nullptr && zero_grids) ? 1U : 0U;
   p.n_dmrs_in_launch   = merge_dmrs ? plan->n_dmrs : 0;

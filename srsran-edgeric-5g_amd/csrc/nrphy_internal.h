@@ -102,6 +102,7 @@ struct PduDev {
   uint32_t item_first;     // index of the PDU's first work item in the plan's (bucket-sorted) work list; its items follow in codeblock / chunk order
   uint32_t seed_first;     // seed slot of that first item; the others follow.  PDUs whose scrambling sequence and codeword layout are the same share their slots
   uint32_t scr_words;      // words of the scrambling sequence the prologue walks: ceil(G / 32) + read-ahead + a seed's length
+  uint32_t scr_word_offset; // words form (PdschLaunch::scr_as_words): the first word of the PDU's sequence in scr_seq; PDUs that share the sequence share it
   uint32_t nof_re;
   uint32_t weights_offset; // floats: data weights (scaled) [nof_prg][P][L][2] in the plan's weight array
   uint32_t dmrs_weights_offset; // floats: unscaled weights, same shape
@@ -166,7 +167,7 @@ struct DmrsWork {
 };
 
 // One 256-thread workgroup of the sequence role: wave 0 walks words [first, first + count) of the PDU's scrambling sequence
-// and stores the seeds of the work items that start there; the PDU's first workgroup also generates its DM-RS sequences
+// and stores them (words form) or the seeds of the work items that start there (seeds form); the PDU's first workgroup also generates its DM-RS sequences
 // (waves 1-3, with_dmrs).  Long sequences are split over up to SCR_PARTS workgroups when the plan has few of them.  Only the
 // first PDU that asks for a sequence gets work: a PDU that shares its scrambling sequence but not its DM-RS has one entry
 // with count == 0 and with_dmrs set.
@@ -215,8 +216,13 @@ struct PdschLaunch {
   uint32_t           n_zero_work;     // zero-fill waves appended to the codeblock launch (0: caller cleared the grids)
   uint32_t           n_dmrs_in_launch; // DM-RS waves appended to the codeblock launch (0: separate launch)
   uint32_t*          scr;             // DM-RS sequences c(n) of every PDU, MSB-first words (prologue -> DM-RS waves)
-  uint32_t*          scr_seed;        // [seed slot][32]: the first 31 words of the x2 part of the scrambling sequence of every work item
-                                      // (PduDev::seed_first; prologue -> codeblock waves, which expand them: gold_expand_seed_wave)
+  // The plan's distinct scrambling sequences (prologue -> codeblock waves), in one of two forms for the whole launch:
+  //   seeds  [seed slot][32]: the first 31 words of the x2 part of the sequence from every work item's first word on
+  //          (PduDev::seed_first; the codeblock waves expand them, gold_expand_seed_wave, and add the x1 table's words);
+  //   words  the PduDev::scr_words words of every sequence, c = x1 ^ x2 (PduDev::scr_word_offset): taken while all of them fit
+  //          an L2 (nrphy_host.cpp, SCR_WORDS_BUDGET_BYTES), read by the codeblock waves like the x1 table.
+  uint32_t*          scr_seq;
+  uint32_t           scr_as_words;    // 1: words, 0: seeds
   const PduDev*      pdus;
   const CbWork*      work;
   const DmrsWork*    dmrs_work;

@@ -1,8 +1,9 @@
 // PDSCH processor kernels for gfx950 (MI355X).
 //
 //   prologue_kernel    per-PDU work the codeblock waves consume: the transport-block CRC (a workgroup per run of 16 KiB
-//                      regions, Horner's rule through byte tables in LDS, one share per workgroup), a 31-word seed of
-//                      the scrambling sequence per codeblock work item, and the DM-RS sequences
+//                      regions, Horner's rule through byte tables in LDS, one share per workgroup), every distinct scrambling
+//                      sequence (its words, or a 31-word seed per codeblock work item where the words of all sequences
+//                      would not stay in an L2: PdschLaunch::scr_as_words), and the DM-RS sequences
 //   codeblock_kernel   one wavefront per codeblock (or per 512-RE chunk of it): segmentation, CB-CRC, LDPC
 //                      base-graph expansion in LDS, rate matching + bit interleaving as a word-level bit-matrix
 //                      transposition, Gold scrambling, QAM mapping through an LDS table, layer mapping, precoding
@@ -42,12 +43,12 @@ namespace nrphy {
 // 64 lanes step with yz = x^(8 * 16384), and only once per workgroup do they pay for a multiplication by a per-lane
 // constant.
 //
-// Scrambling sequences (seeds per work item) and DM-RS sequences: see gold_sequence_blocks_wave() and gold_sequence_wave().
+// Scrambling sequences (words, or seeds per work item) and DM-RS sequences: see gold_sequence_blocks_wave() and gold_sequence_wave().
 // ================================================================================================================
-// Blocks [0, n_scr_work): the seeds of the scrambling sequence of one PDU (a part of them where the plan has few sequences) and
+// Blocks [0, n_scr_work): the scrambling sequence of one PDU, as words or as seeds (a part of it where the plan has few sequences) and
 // its DM-RS sequences (TS 38.211 Sections 7.3.1.1, 7.4.1.1.1; reference: pdsch_modulator_impl.cpp:43-60,
 // dmrs_pdsch_processor_impl.cpp:84-106) -- once per distinct sequence of the plan: the PDUs that ask for the same one read the
-// same seeds (PduDev::seed_first) and DM-RS words (dmrs_seq_offset).  The blocks after them: transport-block CRC.
+// same words (PduDev::scr_word_offset) or seeds (seed_first) and DM-RS words (dmrs_seq_offset).  The blocks after them: transport-block CRC.
 __global__ __launch_bounds__(TB_CRC_THREADS) void prologue_kernel(PdschLaunch p, const uint8_t* __restrict__ d_tb)
 {
   constexpr uint32_t LDS_WORDS = TB_CRC_LDS_WORDS; // CRC role: four tables and two buffers of partials (18 KB: 8 workgroups per CU)
@@ -99,6 +100,36 @@ __global__ __launch_bounds__(TB_CRC_THREADS) void prologue_kernel(PdschLaunch p,
       if (count == 0) { // a PDU that shares its scrambling sequence and has DM-RS sequences of its own
         return;
       }
+      if (p.scr_as_words != 0) { // launch-uniform
+        // Words form: the part's words [first, first + count) of the whole sequence c = x1 ^ x2, 64 consecutive words per
+        // store, where every codeblock wave of every PDU that shares the sequence reads them (served from L2 like the x1
+        // table: the plan takes this form only while all its sequences fit one).  The parts of a sequence are disjoint and
+        // cover [0, scr_words), and the blocks of a part are: every word is written once.
+        constexpr uint32_t SCR_STORE_ROWS = 8;
+        uint32_t*       out = p.scr_seq + pd.scr_word_offset + first;
+        const uint32_t* x1  = p.x1_words + first;
+        // The x1 words of SCR_STORE_ROWS rows are requested together: one trip to memory per batch instead of one per row
+        // (a row at a time, the walk of the headline's sequence took longer than the whole TB-CRC role beside it).
+        gold_sequence_blocks_wave(p.gold, pd.c_init, first, count, lds, lane, [&](uint32_t base, uint32_t avail) {
+          for (uint32_t k0 = lane; k0 < avail; k0 += SCR_STORE_ROWS * WAVE) { // (k0 - lane is wave-uniform)
+            uint32_t x[SCR_STORE_ROWS];
+#pragma unroll
+            for (uint32_t i = 0; i != SCR_STORE_ROWS; ++i) {
+              const uint32_t k = k0 + i * WAVE;
+              x[i]             = k < avail ? x1[base + k] : 0u;
+            }
+#pragma unroll
+            for (uint32_t i = 0; i != SCR_STORE_ROWS; ++i) {
+              const uint32_t k = k0 + i * WAVE;
+              if (k < avail) {
+                out[base + k] = lds[k] ^ x[i];
+              }
+            }
+          }
+        });
+        NRPHY_WG_TRACE_MARK(6);
+        return;
+      }
       // The PDU's work items in the order the plan lists them (nrphy_host.cpp: codeblock by codeblock, RE_CHUNK resource
       // elements per item), walked with scalar arithmetic alongside the blocks: w0 = the word of the item's first bit.
       const uint32_t lq = pd.qm * pd.nof_layers, n_short = pd.n_short, e_short = pd.e_short, e_long = pd.e_long, C = pd.C;
@@ -132,7 +163,7 @@ __global__ __launch_bounds__(TB_CRC_THREADS) void prologue_kernel(PdschLaunch p,
           if (w0 + 31u > lo) {
             const uint32_t k = w0 + lane;
             if (lane < 31u && k >= lo && k < hi) {
-              p.scr_seed[(size_t)c.item * 32u + lane] = lds[k - lo];
+              p.scr_seq[(size_t)c.item * 32u + lane] = lds[k - lo];
             }
           }
           if (w0 + 31u > hi && !resuming) {
@@ -632,26 +663,29 @@ struct ChunkMap {
   uint32_t re0;      // first RE of the chunk within the PDU
   uint32_t word0;    // first scrambling word of the chunk (valid when the chunk starts on a word and L * Qm = 32)
   bool     aligned;  // L * Qm = 32 and the chunk starts on a word boundary: one scrambling word per RE
+  const uint32_t* gwords; // the scrambling words in global memory: the PDU's sequence (words form) or the x1 table (seeds form)
 };
 
-// The L * Qm scrambling bits of RE r of the chunk (MSB first) are the XOR of two parts.  x1 is the same for every sequence:
-// a table in global memory (L2), requested a trip ahead; zero beyond the chunk.  L * Qm = 32 with a word-aligned chunk (the
-// headline shape) makes the bits one word of each part.
+// The L * Qm scrambling bits of RE r of the chunk (MSB first), or their x1 part, from global memory (L2), requested a trip
+// ahead; zero beyond the chunk.  Words form: cm.gwords is the PDU's whole sequence c = x1 ^ x2, which the prologue wrote once
+// for all the PDUs that share it, and these are the bits.  Seeds form: cm.gwords is the x1 table every sequence shares, and
+// the x2 part is XORed in from LDS (x2_bits).  L * Qm = 32 with a word-aligned chunk (the headline shape) makes the bits one
+// word.  The last read stays inside the sequence: a misaligned read of the chunk's last bits runs one word past the word of
+// the codeword's last bit at most, and PduDev::scr_words counts that word and 31 more.
 template <int QM, int L>
-__device__ __forceinline__ uint32_t x1_bits(const PdschLaunch& p, const ChunkGeom& g, const ChunkMap& cm, uint32_t re_count,
-                                            uint32_t r)
+__device__ __forceinline__ uint32_t global_bits(const ChunkGeom& g, const ChunkMap& cm, uint32_t re_count, uint32_t r)
 {
   uint32_t bits = 0;
   if (r < re_count) {
     if (QM * L == 32 && cm.aligned) { // wave-uniform: scalar base, small per-lane index
-      bits = (p.x1_words + cm.word0)[r];
+      bits = (cm.gwords + cm.word0)[r];
     } else {
-      bits = ext32(p.x1_words, g.bit0 + r * (uint32_t)(QM * L));
+      bits = ext32(cm.gwords, g.bit0 + r * (uint32_t)(QM * L));
     }
   }
   return bits;
 }
-// x2 depends on the PDU: the wave has expanded its seed into LDS, x2[0] = the word the chunk's first bit lies in (r < re_count).
+// Seeds form: x2 depends on the PDU: the wave has expanded its seed into LDS, x2[0] = the word the chunk's first bit lies in (r < re_count).
 template <int QM, int L>
 __device__ __forceinline__ uint32_t x2_bits(const uint32_t* x2, const ChunkGeom& g, const ChunkMap& cm, uint32_t r)
 {
@@ -662,8 +696,8 @@ __device__ __forceinline__ uint32_t x2_bits(const uint32_t* x2, const ChunkGeom&
 }
 
 // The RE's L symbol bytes (first in the MSB) and its L*Qm scrambling bits.  Four layers make the first a whole word.
-template <int QM, int L>
-__device__ __forceinline__ void re_bits(const PdschLaunch& p, const CbShared& sh, const ChunkGeom& g, const ChunkMap& cm,
+template <int QM, int L, bool WORDS>
+__device__ __forceinline__ void re_bits(const CbShared& sh, const ChunkGeom& g, const ChunkMap& cm,
                                         uint32_t re_count, uint32_t r, uint32_t& bytes, uint32_t& gbits)
 {
   if constexpr (L == 4) {
@@ -671,12 +705,15 @@ __device__ __forceinline__ void re_bits(const PdschLaunch& p, const CbShared& sh
   } else {
     bytes = ext32(sh.symb, 8u * r * L);
   }
-  gbits = x1_bits<QM, L>(p, g, cm, re_count, r) ^ x2_bits<QM, L>(sh.lin, g, cm, r);
+  gbits = global_bits<QM, L>(g, cm, re_count, r);
+  if constexpr (!WORDS) {
+    gbits ^= x2_bits<QM, L>(sh.lin, g, cm, r);
+  }
 }
 
 // The grid loop of phase B for P ports with wideband precoding (every weight in a scalar register pair for the whole
 // loop, no guards, no loads), or -- P = 0 -- for any port count with weights per PRG read from memory per RE.
-template <int QM, int L, int P>
+template <int QM, int L, int P, bool WORDS>
 __device__ __forceinline__ void phase_b_grid(const PdschLaunch& p, PduRef pd, const PduDev* __restrict__ pd_global,
                                              const CbWork& wk, const CbShared& sh, const ChunkGeom& g, const ChunkMap& cm,
                                              uint32_t first_gbits, uint32_t lane, uint32_t* __restrict__ d_grid)
@@ -717,15 +754,15 @@ __device__ __forceinline__ void phase_b_grid(const PdschLaunch& p, PduRef pd, co
   uint32_t cur_start = pd.sym_re_start[l_cur], cur_end = pd.sym_re_start[l_cur + 1u];
   uint32_t cur_arg = pd.sym_arg[l_cur], cur_row = l_cur * p.grid_nof_subc;
   bool     cur_table = pd.sym_kind[l_cur] == SYM_TABLE;
-  // The x1 part of the scrambling bits comes from global memory (L2): the words of the NEXT 64 RE are requested before a
-  // trip's arithmetic starts, those of the first 64 RE were requested before rate matching (map_chunk).  The x2 part is in
-  // LDS (sh.lin, expanded from the work item's seed).
+  // The scrambling bits (seeds form: their x1 part) come from global memory (L2): the words of the NEXT 64 RE are requested
+  // before a trip's arithmetic starts, those of the first 64 RE were requested before rate matching (map_chunk).  Seeds form:
+  // the x2 part is in LDS (sh.lin, expanded from the work item's seed).
   uint32_t gbits_next = first_gbits;
 
   for (uint32_t r0 = 0; r0 < wk.re_count; r0 += WAVE) { // r0 is wave-uniform
     const uint32_t r        = r0 + lane;
-    const uint32_t x1       = gbits_next;
-    gbits_next              = x1_bits<QM, L>(p, g, cm, wk.re_count, r + WAVE);
+    const uint32_t gcur     = gbits_next;
+    gbits_next              = global_bits<QM, L>(g, cm, wk.re_count, r + WAVE);
     const uint32_t re_first = cm.re0 + r0;
     const uint32_t re_last  = re_first + ((wk.re_count - r0 < WAVE ? wk.re_count - r0 : WAVE) - 1u);
     if (re_first >= cur_end && l_cur + 1u < NRPHY_NSYMB) { // wave-uniform
@@ -743,7 +780,10 @@ __device__ __forceinline__ void phase_b_grid(const PdschLaunch& p, PduRef pd, co
       continue;
     }
     __builtin_assume(r < (uint32_t)RE_CHUNK + WAVE);
-    const uint32_t gbits = x1 ^ x2_bits<QM, L>(sh.lin, g, cm, r);
+    uint32_t gbits = gcur;
+    if constexpr (!WORDS) {
+      gbits ^= x2_bits<QM, L>(sh.lin, g, cm, r);
+    }
     // The RE's L symbol bytes (first in the MSB): four layers make them a whole word.
     uint32_t bytes;
     if constexpr (L == 4) {
@@ -817,7 +857,7 @@ __device__ __forceinline__ void phase_b_grid(const PdschLaunch& p, PduRef pd, co
   }
 }
 
-template <int QM, int L>
+template <int QM, int L, bool WORDS>
 __device__ __forceinline__ void phase_b(const PdschLaunch& p, PduRef pd, const PduDev* __restrict__ pd_global,
                                         const CbWork& wk, const CbShared& sh, const ChunkGeom& g, const ChunkMap& cm,
                                         uint32_t first_gbits, uint32_t lane, uint32_t* __restrict__ d_grid,
@@ -829,7 +869,7 @@ __device__ __forceinline__ void phase_b(const PdschLaunch& p, PduRef pd, const P
     const uint64_t cw_bit0 = pd.cw_bit_offset + g.cw_cb + (uint64_t)wk.re_begin * LQ;
     for (uint32_t r = lane; r < wk.re_count; r += WAVE) {
       uint32_t bytes, gbits;
-      re_bits<QM, L>(p, sh, g, cm, wk.re_count, r, bytes, gbits);
+      re_bits<QM, L, WORDS>(sh, g, cm, wk.re_count, r, bytes, gbits);
       uint32_t v_rm = 0;
 #pragma unroll
       for (int l = 0; l != L; ++l) {
@@ -850,20 +890,20 @@ __device__ __forceinline__ void phase_b(const PdschLaunch& p, PduRef pd, const P
   // One copy of the grid loop per port count (wave-uniform): straight-line port code with its weights in registers.
   const uint32_t nof_ports = pd.nof_prg == 1 ? pd.nof_ports : 0u;
   if (nof_ports == 4u) {
-    phase_b_grid<QM, L, 4>(p, pd, pd_global, wk, sh, g, cm, first_gbits, lane, d_grid);
+    phase_b_grid<QM, L, 4, WORDS>(p, pd, pd_global, wk, sh, g, cm, first_gbits, lane, d_grid);
   } else if (L <= 3 && nof_ports == 3u) {
-    phase_b_grid<QM, (L <= 3 ? L : 1), 3>(p, pd, pd_global, wk, sh, g, cm, first_gbits, lane, d_grid);
+    phase_b_grid<QM, (L <= 3 ? L : 1), 3, WORDS>(p, pd, pd_global, wk, sh, g, cm, first_gbits, lane, d_grid);
   } else if (L <= 2 && nof_ports == 2u) {
-    phase_b_grid<QM, (L <= 2 ? L : 1), 2>(p, pd, pd_global, wk, sh, g, cm, first_gbits, lane, d_grid);
+    phase_b_grid<QM, (L <= 2 ? L : 1), 2, WORDS>(p, pd, pd_global, wk, sh, g, cm, first_gbits, lane, d_grid);
   } else if (L == 1 && nof_ports == 1u) {
-    phase_b_grid<QM, 1, 1>(p, pd, pd_global, wk, sh, g, cm, first_gbits, lane, d_grid);
+    phase_b_grid<QM, 1, 1, WORDS>(p, pd, pd_global, wk, sh, g, cm, first_gbits, lane, d_grid);
   } else {
-    phase_b_grid<QM, L, 0>(p, pd, pd_global, wk, sh, g, cm, first_gbits, lane, d_grid); // weights per PRG (or fewer ports than layers)
+    phase_b_grid<QM, L, 0, WORDS>(p, pd, pd_global, wk, sh, g, cm, first_gbits, lane, d_grid); // weights per PRG (or fewer ports than layers)
   }
 }
 
 // Stages 3 and 4 of a codeblock wave for one (Qm, layers): this wave's slice of the codeword, rate matching ... RE mapping.
-template <int QM, int L>
+template <int QM, int L, bool WORDS>
 __device__ __forceinline__ void map_chunk(const PdschLaunch& p, PduRef pd, const PduDev* pd_global, const CbWork& wk,
                                           uint32_t item, const CbShared& sh, uint32_t lane, uint32_t* d_grid,
                                           uint32_t* d_cw_rm, uint32_t* d_cw_scr)
@@ -880,11 +920,15 @@ __device__ __forceinline__ void map_chunk(const PdschLaunch& p, PduRef pd, const
   cm.re0     = g.cw_cb / (uint32_t)(QM * L) + wk.re_begin;
   cm.word0   = g.bit0 >> 5;
   cm.aligned = (g.bit0 & 31u) == 0;
-  // The work item's seed (the 31 x2 words from the one its first bit lies in; prologue) and the x1 words of the chunk's
-  // first 64 RE are requested here: their trip to memory rides under rate matching.
-  const uint32_t seed_slot   = pd.seed_first + (item - pd.item_first); // the PDU's own items, or those of the PDU it shares with
-  const uint32_t seed_word   = lane < 31u ? p.scr_seed[(size_t)seed_slot * 32u + lane] : 0u;
-  const uint32_t first_gbits = x1_bits<QM, L>(p, g, cm, wk.re_count, lane);
+  cm.gwords  = WORDS ? p.scr_seq + pd.scr_word_offset : p.x1_words;
+  // The global words of the chunk's first 64 RE and, in the seeds form, the work item's seed (the 31 x2 words from the one its
+  // first bit lies in; prologue) are requested here: their trip to memory rides under rate matching.
+  uint32_t seed_word = 0u;
+  if constexpr (!WORDS) {
+    const uint32_t seed_slot = pd.seed_first + (item - pd.item_first); // the PDU's own items, or those of the PDU it shares with
+    seed_word                = lane < 31u ? p.scr_seq[(size_t)seed_slot * 32u + lane] : 0u;
+  }
+  const uint32_t first_gbits = global_bits<QM, L>(g, cm, wk.re_count, lane);
   {
     const RmIndex rm = rm_index_init(pd);
     if (rm.rank0 + g.E > rm.n_valid) { // wave-uniform: the selection wraps around Ncb
@@ -897,30 +941,32 @@ __device__ __forceinline__ void map_chunk(const PdschLaunch& p, PduRef pd, const
     return;
   }
   NRPHY_WG_TRACE_MARK(3); // rate matched and interleaved
-  // The codeblock's LDS is free now: the chunk's x2 words go there, from the word its first bit lies in up to the word a
-  // misaligned read of its last bits runs into (the plan sized the region for it).
-  static_assert((31u + (uint32_t)RE_CHUNK * 32u + 31u) / 32u + 1u <= GOLD_EXPAND_MAX_WORDS, "a work item's scrambling words");
-  gold_expand_seed_wave(sh.lin, seed_word, ((g.bit0 & 31u) + wk.re_count * (uint32_t)(QM * L) + 31u) / 32u + 1u, lane);
-  phase_b<QM, L>(p, pd, pd_global, wk, sh, g, cm, first_gbits, lane, d_grid, d_cw_rm, d_cw_scr);
+  if constexpr (!WORDS) {
+    // The codeblock's LDS is free now: the chunk's x2 words go there, from the word its first bit lies in up to the word a
+    // misaligned read of its last bits runs into (the plan sized the region for it).
+    static_assert((31u + (uint32_t)RE_CHUNK * 32u + 31u) / 32u + 1u <= GOLD_EXPAND_MAX_WORDS, "a work item's scrambling words");
+    gold_expand_seed_wave(sh.lin, seed_word, ((g.bit0 & 31u) + wk.re_count * (uint32_t)(QM * L) + 31u) / 32u + 1u, lane);
+  }
+  phase_b<QM, L, WORDS>(p, pd, pd_global, wk, sh, g, cm, first_gbits, lane, d_grid, d_cw_rm, d_cw_scr);
 }
 
-template <int QM>
+template <int QM, bool WORDS>
 __device__ __forceinline__ void map_chunk_layers(const PdschLaunch& p, PduRef pd, const PduDev* pd_global,
                                                  const CbWork& wk, uint32_t item, const CbShared& sh, uint32_t lane,
                                                  uint32_t* d_grid, uint32_t* d_cw_rm, uint32_t* d_cw_scr)
 {
   switch (pd.nof_layers) { // wave-uniform
     case 1:
-      map_chunk<QM, 1>(p, pd, pd_global, wk, item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
+      map_chunk<QM, 1, WORDS>(p, pd, pd_global, wk, item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
       break;
     case 2:
-      map_chunk<QM, 2>(p, pd, pd_global, wk, item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
+      map_chunk<QM, 2, WORDS>(p, pd, pd_global, wk, item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
       break;
     case 3:
-      map_chunk<QM, 3>(p, pd, pd_global, wk, item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
+      map_chunk<QM, 3, WORDS>(p, pd, pd_global, wk, item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
       break;
     default:
-      map_chunk<QM, 4>(p, pd, pd_global, wk, item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
+      map_chunk<QM, 4, WORDS>(p, pd, pd_global, wk, item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
       break;
   }
 }
@@ -1216,12 +1262,13 @@ __device__ __forceinline__ bool codeblock_front(const PdschLaunch& p, PduRef pd,
   return NRPHY_STAGE(p) != 2;
 }
 
-template <int QM, int L>
-__global__ __launch_bounds__(WAVE * CB_WAVES) void codeblock_kernel_t(PdschLaunch p, const uint8_t* __restrict__ d_tb,
-                                                              uint32_t* __restrict__ d_grid, uint32_t* __restrict__ d_cw_rm,
-                                                              uint32_t* __restrict__ d_cw_scr)
+// One codeblock wave of a bucket launch.  WORDS: the form of the launch's scrambling sequences (PdschLaunch::scr_as_words) as a
+// compile-time constant -- the words form has no seed load, no expansion in LDS and no x2 read per 64 RE at all.
+template <int QM, int L, bool WORDS>
+__device__ __forceinline__ void codeblock_wave_t(const PdschLaunch& p, const uint8_t* __restrict__ d_tb,
+                                                 uint32_t* __restrict__ d_grid, uint32_t* __restrict__ d_cw_rm,
+                                                 uint32_t* __restrict__ d_cw_scr, uint32_t* dyn_lds)
 {
-  extern __shared__ __attribute__((aligned(16))) uint32_t dyn_lds[];
   const CbWave   w    = cb_wave(p, dyn_lds);
   const uint32_t lane = w.lane;
   CbShared       sh;
@@ -1245,15 +1292,35 @@ __global__ __launch_bounds__(WAVE * CB_WAVES) void codeblock_kernel_t(PdschLaunc
   if (!codeblock_front(p, pd, wk, sh, d_tb, lane)) {
     return;
   }
-  map_chunk<QM, L>(p, pd, &p.pdus[wk.pdu], wk, p.work_base + item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
+  map_chunk<QM, L, WORDS>(p, pd, &p.pdus[wk.pdu], wk, p.work_base + item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
   NRPHY_WG_TRACE_MARK(6);
 }
 
-__global__ __launch_bounds__(WAVE * CB_WAVES) void codeblock_kernel(PdschLaunch p, const uint8_t* __restrict__ d_tb,
-                                                         uint32_t* __restrict__ d_grid, uint32_t* __restrict__ d_cw_rm,
-                                                         uint32_t* __restrict__ d_cw_scr)
+// Seeds form ...
+template <int QM, int L>
+__global__ __launch_bounds__(WAVE * CB_WAVES) void codeblock_kernel_t(PdschLaunch p, const uint8_t* __restrict__ d_tb,
+                                                              uint32_t* __restrict__ d_grid, uint32_t* __restrict__ d_cw_rm,
+                                                              uint32_t* __restrict__ d_cw_scr)
 {
   extern __shared__ __attribute__((aligned(16))) uint32_t dyn_lds[];
+  codeblock_wave_t<QM, L, false>(p, d_tb, d_grid, d_cw_rm, d_cw_scr, dyn_lds);
+}
+// ... and words form of the plan's scrambling sequences.
+template <int QM, int L>
+__global__ __launch_bounds__(WAVE * CB_WAVES) void codeblock_words_kernel_t(PdschLaunch p, const uint8_t* __restrict__ d_tb,
+                                                                    uint32_t* __restrict__ d_grid, uint32_t* __restrict__ d_cw_rm,
+                                                                    uint32_t* __restrict__ d_cw_scr)
+{
+  extern __shared__ __attribute__((aligned(16))) uint32_t dyn_lds[];
+  codeblock_wave_t<QM, L, true>(p, d_tb, d_grid, d_cw_rm, d_cw_scr, dyn_lds);
+}
+
+// One codeblock wave of the one-launch mixed kernel: the output stage is selected per wave.
+template <bool WORDS>
+__device__ __forceinline__ void codeblock_wave_mixed(const PdschLaunch& p, const uint8_t* __restrict__ d_tb,
+                                                     uint32_t* __restrict__ d_grid, uint32_t* __restrict__ d_cw_rm,
+                                                     uint32_t* __restrict__ d_cw_scr, uint32_t* dyn_lds)
+{
   const CbWave   w    = cb_wave(p, dyn_lds);
   const uint32_t lane = w.lane;
   CbShared       sh;
@@ -1277,30 +1344,50 @@ __global__ __launch_bounds__(WAVE * CB_WAVES) void codeblock_kernel(PdschLaunch 
   }
   switch (pd.qm) { // wave-uniform
     case 2:
-      map_chunk_layers<2>(p, pd, &p.pdus[wk.pdu], wk, p.work_base + item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
+      map_chunk_layers<2, WORDS>(p, pd, &p.pdus[wk.pdu], wk, p.work_base + item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
       break;
     case 4:
-      map_chunk_layers<4>(p, pd, &p.pdus[wk.pdu], wk, p.work_base + item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
+      map_chunk_layers<4, WORDS>(p, pd, &p.pdus[wk.pdu], wk, p.work_base + item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
       break;
     case 6:
-      map_chunk_layers<6>(p, pd, &p.pdus[wk.pdu], wk, p.work_base + item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
+      map_chunk_layers<6, WORDS>(p, pd, &p.pdus[wk.pdu], wk, p.work_base + item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
       break;
     default:
-      map_chunk_layers<8>(p, pd, &p.pdus[wk.pdu], wk, p.work_base + item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
+      map_chunk_layers<8, WORDS>(p, pd, &p.pdus[wk.pdu], wk, p.work_base + item, sh, lane, d_grid, d_cw_rm, d_cw_scr);
       break;
   }
 }
 
+__global__ __launch_bounds__(WAVE * CB_WAVES) void codeblock_kernel(PdschLaunch p, const uint8_t* __restrict__ d_tb,
+                                                         uint32_t* __restrict__ d_grid, uint32_t* __restrict__ d_cw_rm,
+                                                         uint32_t* __restrict__ d_cw_scr)
+{
+  extern __shared__ __attribute__((aligned(16))) uint32_t dyn_lds[];
+  codeblock_wave_mixed<false>(p, d_tb, d_grid, d_cw_rm, d_cw_scr, dyn_lds);
+}
+__global__ __launch_bounds__(WAVE * CB_WAVES) void codeblock_words_kernel(PdschLaunch p, const uint8_t* __restrict__ d_tb,
+                                                               uint32_t* __restrict__ d_grid, uint32_t* __restrict__ d_cw_rm,
+                                                               uint32_t* __restrict__ d_cw_scr)
+{
+  extern __shared__ __attribute__((aligned(16))) uint32_t dyn_lds[];
+  codeblock_wave_mixed<true>(p, d_tb, d_grid, d_cw_rm, d_cw_scr, dyn_lds);
+}
+
 typedef void (*CodeblockKernel)(PdschLaunch, const uint8_t*, uint32_t*, uint32_t*, uint32_t*);
 
-static CodeblockKernel bucket_kernel(uint32_t bucket)
+static CodeblockKernel bucket_kernel(uint32_t bucket, bool words)
 {
-  static const CodeblockKernel table[CB_BUCKETS] = {
+  static const CodeblockKernel seeds_table[CB_BUCKETS] = {
       codeblock_kernel_t<2, 1>, codeblock_kernel_t<2, 2>, codeblock_kernel_t<2, 3>, codeblock_kernel_t<2, 4>,
       codeblock_kernel_t<4, 1>, codeblock_kernel_t<4, 2>, codeblock_kernel_t<4, 3>, codeblock_kernel_t<4, 4>,
       codeblock_kernel_t<6, 1>, codeblock_kernel_t<6, 2>, codeblock_kernel_t<6, 3>, codeblock_kernel_t<6, 4>,
       codeblock_kernel_t<8, 1>, codeblock_kernel_t<8, 2>, codeblock_kernel_t<8, 3>, codeblock_kernel_t<8, 4>};
-  return table[bucket];
+  static const CodeblockKernel words_table[CB_BUCKETS] = {
+      codeblock_words_kernel_t<2, 1>, codeblock_words_kernel_t<2, 2>, codeblock_words_kernel_t<2, 3>, codeblock_words_kernel_t<2, 4>,
+      codeblock_words_kernel_t<4, 1>, codeblock_words_kernel_t<4, 2>, codeblock_words_kernel_t<4, 3>, codeblock_words_kernel_t<4, 4>,
+      codeblock_words_kernel_t<6, 1>, codeblock_words_kernel_t<6, 2>, codeblock_words_kernel_t<6, 3>, codeblock_words_kernel_t<6, 4>,
+      codeblock_words_kernel_t<8, 1>, codeblock_words_kernel_t<8, 2>, codeblock_words_kernel_t<8, 3>, codeblock_words_kernel_t<8, 4>};
+  return words ? words_table[bucket] : seeds_table[bucket];
 }
 
 // bucket_begin[b] .. bucket_begin[b + 1]: the work items of bucket b = cb_bucket(Qm, layers) (the plan sorts them).
@@ -1329,8 +1416,8 @@ hipError_t launch_codeblocks(const PdschLaunch& p, const uint32_t* bucket_begin,
   const uint32_t extras    = d_grid ? p.n_dmrs_in_launch + p.n_zero_work : 0u;
   uint32_t       nof_buckets = 0;
   if (!codeblocks_take_bucket_launches(p, bucket_begin, dispatch, &nof_buckets)) {
-    hipLaunchKernelGGL(codeblock_kernel, dim3(cb_blocks(p.n_work) + cb_blocks(extras)), dim3(WAVE * CB_WAVES), lds_bytes, streams[0], p,
-                       d_tb, d_grid, d_cw_rm, d_cw_scr);
+    hipLaunchKernelGGL(p.scr_as_words != 0 ? codeblock_words_kernel : codeblock_kernel, dim3(cb_blocks(p.n_work) + cb_blocks(extras)),
+                       dim3(WAVE * CB_WAVES), lds_bytes, streams[0], p, d_tb, d_grid, d_cw_rm, d_cw_scr);
     return hipGetLastError();
   }
   uint32_t order[CB_BUCKETS], n_order = 0; // non-empty buckets, biggest first
@@ -1354,7 +1441,7 @@ hipError_t launch_codeblocks(const PdschLaunch& p, const uint32_t* bucket_begin,
       q.n_zero_work      = 0;
     }
     const uint32_t blocks = cb_blocks(n) + (i == 0 ? cb_blocks(extras) : 0u);
-    hipLaunchKernelGGL(bucket_kernel(b), dim3(blocks), dim3(WAVE * CB_WAVES), lds_bytes, streams[n_streams > 1 ? i % n_streams : 0], q,
+    hipLaunchKernelGGL(bucket_kernel(b, p.scr_as_words != 0), dim3(blocks), dim3(WAVE * CB_WAVES), lds_bytes, streams[n_streams > 1 ? i % n_streams : 0], q,
                        d_tb, d_grid, d_cw_rm, d_cw_scr);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

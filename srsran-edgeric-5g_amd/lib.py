@@ -626,6 +626,14 @@ class PdschPlan:
         _check(self.ctx.lib.nrphy_pdsch_plan_nof_sequences(self.handle, C.byref(scr), C.byref(dmrs)), "nrphy_pdsch_plan_nof_sequences")
         return int(scr.value), int(dmrs.value)
 
+    @property
+    def scrambling_form(self):
+        """"words" or "seeds": how a run hands the distinct scrambling sequences to the codeblock waves."""
+        form = int(self.ctx.lib.nrphy_pdsch_plan_scrambling_form(self.handle))
+        if form < 0:
+            raise NrphyError(abi.ERR_ARGUMENT, "nrphy_pdsch_plan_scrambling_form")
+        return "words" if form else "seeds"
+
     def run(self, d_tb, d_grid, d_cw_rm=None, d_cw_scr=None, zero_grids=True, stream=None):
         _check(self.ctx.lib.nrphy_pdsch_run(self.handle, _dptr(d_tb), _dptr(d_grid), _dptr(d_cw_rm), _dptr(d_cw_scr),
                                             int(zero_grids), _stream(stream)), "nrphy_pdsch_run")
