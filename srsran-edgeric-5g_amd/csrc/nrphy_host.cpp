@@ -1,9 +1,9 @@
 // Host side of libmi355nrphy.so: the C ABI of include/mi355_nrphy.h.
 //
-// Per-PDU scalar derivation (what pdsch_processor_impl / ldpc_segmenter_impl / ldpc_rate_matcher_impl compute on
-// the CPU before their loops), plan construction and kernel launches.  No compute happens here and there is no CPU
-// fallback: every entry point that produces PHY output needs a HIP device.
-#include "nrphy_host_internal.h"
+// The context and its tables, the OFDM plan, the LDPC encoder, dematcher and decoders and the PUSCH decoder: plan construction
+// and kernel launches (the PDSCH plan lives in pdsch_plan_build.cpp and pdsch_host.cpp).  No compute happens here and there is
+// no CPU fallback: every entry point that produces PHY output needs a HIP device.
+#include "pdsch_plan.h"
 #include "nrphy_trace.h"
 
 #include <algorithm>
@@ -29,20 +29,6 @@ struct nr_ldpc_edge_t {
 };
 #include "nr_ldpc_bg.inc"
 
-const uint16_t LIFTING_SIZES[NOF_LIFTING_SIZES] = {
-    2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13,  14,  15,  16,  18,  20,  22,  24,  26,  28,  30,  32,  36,  40, 44,
-    48, 52, 56, 60, 64, 72, 80, 88, 96, 104, 112, 120, 128, 144, 160, 176, 192, 208, 224, 240, 256, 288, 320, 352, 384};
-
-int lifting_position(unsigned zc)
-{
-  for (int i = 0; i != NOF_LIFTING_SIZES; ++i) {
-    if (LIFTING_SIZES[i] == zc) {
-      return i;
-    }
-  }
-  return -1;
-}
-
 // Lifting-set index i_LS: Zc = a * 2^j, a in {2, 3, 5, 7, 9, 11, 13, 15} (TS 38.212 Table 5.3.2-1).
 int lifting_set_index(unsigned zc)
 {
@@ -57,36 +43,7 @@ int lifting_set_index(unsigned zc)
   return -1;
 }
 
-unsigned divide_ceil(unsigned a, unsigned b)
-{
-  return (a + b - 1) / b;
-}
-
-bool mask_test(const uint64_t* w, unsigned i)
-{
-  return (w[i >> 6] >> (i & 63)) & 1U;
-}
-
-int mask_lowest(const uint64_t* w)
-{
-  for (unsigned i = 0; i != 64 * NRPHY_PRB_WORDS; ++i) {
-    if (mask_test(w, i)) {
-      return (int)i;
-    }
-  }
-  return -1;
-}
-
-int mask_highest(const uint64_t* w)
-{
-  int hi = -1;
-  for (unsigned i = 0; i != 64 * NRPHY_PRB_WORDS; ++i) {
-    if (mask_test(w, i)) {
-      hi = (int)i;
-    }
-  }
-  return hi;
-}
+} // namespace
 
 void build_lifted_graph(unsigned bg, unsigned zc, LiftedGraph& g)
 {
@@ -136,6 +93,8 @@ void build_lifted_graph(unsigned bg, unsigned zc, LiftedGraph& g)
   g.core_s3  = (uint16_t)s3;
   g.core_b   = (uint16_t)((s0 == s3) ? sm : ((s0 == sm) ? s3 : s0));
 }
+
+namespace {
 
 // ---- Gold sequence tables (TS 38.211 Section 5.2.1) -----------------------------------------------------------
 // 31x31 matrices over GF(2) as 31 row masks.
@@ -299,83 +258,7 @@ void build_gold_tables(GoldTables& t, std::vector<uint32_t>& x1_words)
   }
 }
 
-// What decides the sequences a PDU asks the prologue for (plan_create).  scr: c_init, C, n_short, e_short, e_long, bits per
-// resource element -- the sequence and where the work items' seeds lie in it (with RE_CHUNK).  dmrs: symbol mask, words per
-// symbol, c_init of the DM-RS symbols.
-struct SeqKey {
-  std::array<uint32_t, 6>               scr;
-  std::array<uint32_t, 2 + NRPHY_NSYMB> dmrs;
-  bool operator==(const SeqKey& o) const { return scr == o.scr && dmrs == o.dmrs; }
-};
-struct SeqKeyHash {
-  size_t operator()(const SeqKey& k) const
-  {
-    uint64_t h = 0xCBF29CE484222325ULL; // FNV-1a over the words
-    for (uint32_t w : k.scr) {
-      h = (h ^ w) * 0x100000001B3ULL;
-    }
-    for (uint32_t w : k.dmrs) {
-      h = (h ^ w) * 0x100000001B3ULL;
-    }
-    return (size_t)(h ^ (h >> 32));
-  }
-};
-struct SeqShare {
-  uint32_t seed_first;      // PduDev::seed_first of the PDUs that share the scrambling sequence (seeds form)
-  uint32_t scr_word_offset; // PduDev::scr_word_offset of the same PDUs (words form)
-  uint32_t dmrs_seq_offset; // PduDev::dmrs_seq_offset of those that share the DM-RS sequences
-};
-constexpr uint8_t SEQ_NEW_SCR = 1, SEQ_NEW_DMRS = 2;
-// A plan stores its distinct scrambling sequences as words while they take no more than this: one XCD's L2, so that the words,
-// written once by the prologue, are served from every L2 like the x1 table.  Beyond it a plan stores seeds (a batch of 1024
-// PDUs that share nothing would write and read back 121 MB of sequences).
-constexpr uint64_t SCR_WORDS_BUDGET_BYTES = 4ULL << 20;
-
 } // namespace
-
-struct nrphy_pdsch_plan {
-  nrphy_ctx*            ctx = nullptr;
-  std::vector<PduDev>   pdus;
-  std::vector<uint64_t> cw_offset;
-  uint64_t              cw_bits = 0;
-  uint32_t              nof_grids = 0, grid_nof_ports = 0, grid_nof_subc = 0;
-  void*                 d_arena = nullptr; // the one device allocation every d_* pointer below points into
-  bool                  arena_external = false; // the tables live in memory the caller owns (nrphy_pdsch_plan_create_placed)
-  PduDev*               d_pdus = nullptr;
-  CbWork*               d_work = nullptr;
-  DmrsWork*             d_dmrs = nullptr;
-  float*                d_weights = nullptr;
-  uint16_t*             d_re_table = nullptr;
-  uint32_t*             d_tb_crc = nullptr;
-  CrcWork*              d_crc_work = nullptr;
-  ScrWork*              d_scr_work = nullptr;
-  uint32_t              n_scr_work = 0;
-  uint32_t              n_scr_seq = 0, n_dmrs_seq = 0; // distinct scrambling sequences / DM-RS sequence sets a run generates
-  ZeroWork*             d_zero_work = nullptr;
-  ZeroSeg*              d_zero_segs = nullptr;
-  uint32_t*             d_scr = nullptr;    // scrambling sequences, rewritten by every run's prologue
-  uint64_t              scr_words = 0;   // words of the run's scratch: the distinct DM-RS sequences, then the distinct scrambling sequences (seeds or words)
-  uint64_t              seed_offset = 0; // where the scrambling sequences start
-  bool                  scr_as_words = false; // the form of the scrambling sequences: words (true) or seeds (PdschLaunch::scr_as_words)
-  uint32_t              n_zero_work = 0;
-  bool                  encode_only = false;   // seam B plan: no RE mapping, nrphy_pdsch_run only with d_grid = NULL
-  bool                  dmrs_separate = false; // DM-RS must overwrite data RE: keep it in its own, later launch
-  uint32_t              n_work = 0, n_dmrs = 0, n_cb = 0, n_crc_work = 0;
-  uint32_t              lds_lin_words = 0, lds_symb_words = 0, lds_graph_words = 0, lds_u_words = 0;
-  uint32_t              bucket_begin[CB_BUCKETS + 1] = {}; // work items sorted by (modulation order, layers)
-  // A batch with several big buckets runs their launches side by side on streams of the plan's own (created at the first
-  // such run), forked from and joined to the caller's stream with events.
-  static constexpr uint32_t MAX_AUX = 3;
-  hipStream_t           aux_stream[MAX_AUX] = {};
-  hipEvent_t            fork_event = nullptr, join_event[MAX_AUX] = {};
-  uint32_t              n_aux = 0;
-  std::vector<hipEvent_t> events; // 4 per recorded run: start, after tb_crc, after codeblocks, after dmrs (only when a DM-RS launch follows)
-  std::vector<uint8_t>  timed_dmrs; // per recorded run: its fourth event was recorded
-  uint32_t              timed_runs = 0, max_timed_runs = 0;
-  uint32_t              timing_stride = 1, timing_counter = 0; // every timing_stride-th run is recorded
-};
-
-static bool plan_side_streams(nrphy_pdsch_plan* plan, uint32_t want);
 
 struct nrphy_ofdm_plan {
   nrphy_ctx*          ctx = nullptr;
@@ -425,218 +308,6 @@ extern "C" const char* nrphy_strerror(int status)
     default:
       return "unknown status";
   }
-}
-
-// pdsch_processor_validator_impl::is_valid (R/lib/phy/upper/channel_processors/pdsch_processor_validator_impl.cpp:99-181),
-// plus the checks the reference leaves to assertions deeper in the chain (modulation, rv, base graph, sizes).
-extern "C" int nrphy_pdsch_validate(const nrphy_pdsch_pdu_t* pdu)
-{
-  if (pdu == nullptr) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  const unsigned nsymb = pdu->cp ? 12 : 14;
-  const int      lo = mask_lowest(pdu->prb_mask), hi = mask_highest(pdu->prb_mask);
-  if (lo < 0 || (unsigned)lo < pdu->bwp_start_rb || (unsigned)hi >= pdu->bwp_start_rb + pdu->bwp_size_rb ||
-      pdu->bwp_start_rb + pdu->bwp_size_rb > NRPHY_MAX_RB) {
-    return NRPHY_ERR_INVALID_PDU; // freq_alloc.is_bwp_valid
-  }
-  if (pdu->dmrs_symbol_mask == 0 || (pdu->dmrs_symbol_mask >> nsymb) != 0) {
-    return NRPHY_ERR_INVALID_PDU;
-  }
-  const unsigned first_dmrs = (unsigned)__builtin_ctz(pdu->dmrs_symbol_mask);
-  const unsigned last_dmrs  = 31U - (unsigned)__builtin_clz(pdu->dmrs_symbol_mask);
-  if (first_dmrs < pdu->start_symbol_index || last_dmrs >= pdu->start_symbol_index + pdu->nof_symbols ||
-      nsymb < pdu->start_symbol_index + pdu->nof_symbols) {
-    return NRPHY_ERR_INVALID_PDU;
-  }
-  if (pdu->dmrs_type != 1 || pdu->nof_cdm_groups_without_data > 2 || !pdu->vrb_contiguous) {
-    return NRPHY_ERR_INVALID_PDU;
-  }
-  for (int prb = lo; prb <= hi; ++prb) { // "only contiguous allocation": the flag and the mask must tell the same story
-    if (!mask_test(pdu->prb_mask, (unsigned)prb)) {
-      return NRPHY_ERR_INVALID_PDU;
-    }
-  }
-  if (pdu->nof_ports == 0 || pdu->nof_ports > NRPHY_MAX_PORTS || pdu->nof_layers == 0 ||
-      pdu->nof_layers > pdu->nof_ports) {
-    return NRPHY_ERR_INVALID_PDU;
-  }
-  if (pdu->nof_codewords != 1 || pdu->tbs_lbrm_bytes == 0 || pdu->nof_reserved > NRPHY_MAX_RESERVED) {
-    return NRPHY_ERR_INVALID_PDU;
-  }
-  for (unsigned r = 0; r != pdu->nof_reserved; ++r) {
-    if (pdu->reserved[r].symbol_mask & pdu->dmrs_symbol_mask) {
-      return NRPHY_ERR_INVALID_PDU; // check_dmrs_and_reserved_collision
-    }
-  }
-  if ((pdu->qm != 2 && pdu->qm != 4 && pdu->qm != 6 && pdu->qm != 8) || pdu->rv > 3 ||
-      (pdu->ldpc_base_graph != 1 && pdu->ldpc_base_graph != 2) || pdu->tb_size_bytes == 0 ||
-      pdu->tb_size_bytes > NRPHY_MAX_TB_BYTES || pdu->nof_prg == 0 || pdu->nof_prg > NRPHY_MAX_PRG || pdu->prg_size_rb == 0 || pdu->prg_size_rb > NRPHY_MAX_RB || pdu->precoding == nullptr || pdu->cp > 1) {
-    // (nof_prg sizes the read of the caller's weight array: at most one PRG per resource block)
-    return NRPHY_ERR_INVALID_PDU;
-  }
-  return NRPHY_OK;
-}
-
-namespace {
-
-// Data-RE mask of OFDM symbol l: allocation minus reserved minus DM-RS pattern
-// (pdsch_modulator_impl.cpp:52-106, re_pattern.cpp:27-60, dmrs_mapping.h:69-123).
-void data_re_mask(const nrphy_pdsch_pdu_t& pdu, unsigned l, std::vector<uint8_t>& mask)
-{
-  std::fill(mask.begin(), mask.end(), 0);
-  if (l < pdu.start_symbol_index || l >= pdu.start_symbol_index + pdu.nof_symbols) {
-    return;
-  }
-  const unsigned nof_prb = (unsigned)mask.size() / 12;
-  for (unsigned p = 0; p != nof_prb; ++p) {
-    if (mask_test(pdu.prb_mask, p)) {
-      std::fill(mask.begin() + 12 * p, mask.begin() + 12 * p + 12, 1);
-    }
-  }
-  for (unsigned r = 0; r != pdu.nof_reserved; ++r) {
-    const nrphy_re_pattern_t& pat = pdu.reserved[r];
-    if (!((pat.symbol_mask >> l) & 1U)) {
-      continue;
-    }
-    for (unsigned p = 0; p != nof_prb; ++p) {
-      if (!mask_test(pat.prb_mask, p)) {
-        continue;
-      }
-      for (unsigned k = 0; k != 12; ++k) {
-        if ((pat.re_mask >> k) & 1U) {
-          mask[12 * p + k] = 0;
-        }
-      }
-    }
-  }
-  if ((pdu.dmrs_symbol_mask >> l) & 1U) {
-    for (unsigned p = pdu.bwp_start_rb; p < pdu.bwp_start_rb + pdu.bwp_size_rb && p < nof_prb; ++p) {
-      for (unsigned k = 0; k != 12; ++k) {
-        if ((k % 2) < pdu.nof_cdm_groups_without_data) {
-          mask[12 * p + k] = 0;
-        }
-      }
-    }
-  }
-}
-
-// nref_override: the limited-buffer size given directly (seam B hands N_ref, not TBS_LBRM); nullptr = from the PDU.
-void derive(const nrphy_pdsch_pdu_t& pdu, unsigned nof_re, nrphy_pdsch_derived_t& d,
-            const uint32_t* nref_override = nullptr)
-{
-  const unsigned bg      = pdu.ldpc_base_graph;
-  const unsigned tb_bits = 8 * pdu.tb_size_bytes;
-  const unsigned tb_crc  = (tb_bits <= 3824) ? 16 : 24;
-  const unsigned b       = tb_bits + tb_crc;
-  const unsigned kcb     = (bg == 1) ? 8448 : 3840;
-  const unsigned C       = (b <= kcb) ? 1 : divide_ceil(b, kcb - 24);
-  const unsigned b_out   = b + ((C > 1) ? 24 * C : 0);
-  unsigned       ref_len = 22;
-  if (bg == 2) {
-    ref_len = (b > 640) ? 10 : (b > 560) ? 9 : (b > 192) ? 8 : 6;
-  }
-  unsigned zc = 0;
-  for (unsigned i = 0; i != NOF_LIFTING_SIZES; ++i) {
-    if (LIFTING_SIZES[i] * C * ref_len >= b_out) {
-      zc = LIFTING_SIZES[i];
-      break;
-    }
-  }
-  const unsigned K      = ((bg == 1) ? 22 : 10) * zc;
-  const unsigned cb_crc = (C > 1) ? 24 : 0;
-  const unsigned info   = divide_ceil(b_out, C) - cb_crc;
-  const unsigned N      = ((bg == 1) ? 66 : 50) * zc;
-  uint64_t       nref   = ((uint64_t)pdu.tbs_lbrm_bytes * 8 * 3) / (2 * C); // ldpc::compute_N_ref
-  if (nref_override != nullptr) {
-    nref = *nref_override;
-  }
-  nref                  = std::min<uint64_t>(nref, 66 * 384);
-  d.nof_re              = nof_re;
-  d.nof_codeblocks      = C;
-  d.lifting_size        = zc;
-  d.segment_length      = K;
-  d.cb_info_bits        = info;
-  d.nof_filler_bits     = K - info - cb_crc;
-  d.nof_tb_crc_bits     = tb_crc;
-  d.nof_cb_crc_bits     = cb_crc;
-  d.zero_pad            = (info + cb_crc) * C - b_out;
-  d.full_length         = N;
-  d.n_ref               = (uint32_t)nref;
-  d.n_cb                = (nref > 0 && nref < N) ? (uint32_t)nref : N;
-  static const double shift_bg1[4] = {0, 17, 33, 56};
-  static const double shift_bg2[4] = {0, 13, 25, 43};
-  const double tmp      = (((bg == 1) ? shift_bg1 : shift_bg2)[pdu.rv] * d.n_cb) / N; // ldpc_rate_matcher_impl.cpp:89-90
-  d.k0                  = (uint32_t)((uint16_t)std::floor(tmp)) * zc;
-  d.nof_short_segments  = C - (nof_re % C);
-  d.rm_length_short     = (nof_re / C) * pdu.nof_layers * pdu.qm;
-  d.rm_length_long      = divide_ceil(nof_re, C) * pdu.nof_layers * pdu.qm;
-  d.codeword_bits       = nof_re * pdu.nof_layers * pdu.qm;
-}
-
-unsigned count_data_re(const nrphy_pdsch_pdu_t& pdu)
-{
-  std::vector<uint8_t> mask(NRPHY_MAX_RB * 12);
-  unsigned             count = 0;
-  for (unsigned l = 0; l != NRPHY_NSYMB; ++l) {
-    data_re_mask(pdu, l, mask);
-    for (uint8_t m : mask) {
-      count += m;
-    }
-  }
-  return count;
-}
-
-} // namespace
-
-extern "C" int nrphy_pdsch_derive(const nrphy_pdsch_pdu_t* pdu, nrphy_pdsch_derived_t* out)
-{
-  if (pdu == nullptr || out == nullptr || pdu->tb_size_bytes == 0 || pdu->nof_layers == 0 || pdu->qm == 0 ||
-      (pdu->ldpc_base_graph != 1 && pdu->ldpc_base_graph != 2) || pdu->rv > 3) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  derive(*pdu, count_data_re(*pdu), *out);
-  return NRPHY_OK;
-}
-
-// TS 38.214 Section 5.1.3.2 (tbs_calculator_calculate, R/lib/ran/sch/tbs_calculator.cpp:31-144).
-extern "C" uint32_t nrphy_tbs_calculate(uint32_t nof_symb_sh, uint32_t nof_dmrs_prb, uint32_t nof_oh_prb, uint32_t qm,
-                                        float target_code_rate, uint32_t nof_layers, uint32_t n_prb)
-{
-  static const uint16_t table[93] = {
-      24,   32,   40,   48,   56,   64,   72,   80,   88,   96,   104,  112,  120,  128,  136,  144,  152,  160,  168,
-      176,  184,  192,  208,  224,  240,  256,  272,  288,  304,  320,  336,  352,  368,  384,  408,  432,  456,  480,
-      504,  528,  552,  576,  608,  640,  672,  704,  736,  768,  808,  848,  888,  928,  984,  1032, 1064, 1128, 1160,
-      1192, 1224, 1256, 1288, 1320, 1352, 1416, 1480, 1544, 1608, 1672, 1736, 1800, 1864, 1928, 2024, 2088, 2152, 2216,
-      2280, 2408, 2472, 2536, 2600, 2664, 2728, 2792, 2856, 2976, 3104, 3240, 3368, 3496, 3624, 3752, 3824};
-  const unsigned nof_re_prime = 12 * nof_symb_sh - nof_dmrs_prb - nof_oh_prb;
-  const unsigned nof_re       = std::min(nof_re_prime, 156U) * n_prb;
-  const float    tcr          = target_code_rate * (1.F / 1024);
-  const float    nof_info     = 1.0F * (float)nof_re * tcr * (float)qm * (float)nof_layers;
-  if (nof_info <= 3824) {
-    unsigned n = 3;
-    if (nof_info > 512) {
-      n = (unsigned)std::floor(std::log2(nof_info)) - 6U;
-    }
-    const unsigned p2    = 1U << n;
-    const unsigned prime = std::max(24U, p2 * (unsigned)std::floor(nof_info / (float)p2));
-    for (uint16_t v : table) {
-      if (v >= prime) {
-        return v;
-      }
-    }
-    return 3824;
-  }
-  const unsigned n     = (unsigned)(std::floor(std::log2(nof_info - 24)) - 5.0F);
-  const unsigned p2    = 1U << n;
-  const unsigned prime = std::max(3840U, p2 * (unsigned)std::round((nof_info - 24) / (float)p2));
-  unsigned       C     = 1;
-  if (tcr <= 0.25F) {
-    C = divide_ceil(prime + 24, 3816);
-  } else if (prime > 8424) {
-    C = divide_ceil(prime + 24, 8424);
-  }
-  return 8 * C * divide_ceil(prime + 24, 8 * C) - 24;
 }
 
 namespace {
@@ -816,1138 +487,6 @@ const float2* get_twiddle(nrphy_ctx* ctx, uint32_t size)
   }
   ctx->d_twiddle[size] = d;
   return d;
-}
-
-// ================================================================================================================
-// PDSCH plan
-// ================================================================================================================
-namespace {
-
-// Everything the RE mapping of a PDU depends on (data_re_mask + the DM-RS comb): PDUs of a batch that repeat an
-// allocation share its tables instead of rebuilding them.
-void append_allocation_signature(const nrphy_pdsch_pdu_t& pdu, std::vector<uint64_t>& sig)
-{
-  sig.insert(sig.end(), std::begin(pdu.prb_mask), std::end(pdu.prb_mask));
-  sig.push_back(((uint64_t)pdu.start_symbol_index << 48) | ((uint64_t)pdu.nof_symbols << 40) |
-                ((uint64_t)pdu.nof_cdm_groups_without_data << 36) | ((uint64_t)pdu.nof_layers << 32) |
-                pdu.dmrs_symbol_mask);
-  sig.push_back(((uint64_t)pdu.bwp_start_rb << 32) | ((uint64_t)pdu.bwp_size_rb << 8) | pdu.nof_reserved);
-  for (unsigned r = 0; r != pdu.nof_reserved; ++r) {
-    sig.insert(sig.end(), std::begin(pdu.reserved[r].prb_mask), std::end(pdu.reserved[r].prb_mask));
-    sig.push_back(((uint64_t)pdu.reserved[r].re_mask << 32) | pdu.reserved[r].symbol_mask);
-  }
-}
-
-struct ReMapping {
-  uint32_t sym_re_start[NRPHY_NSYMB + 1];
-  uint32_t sym_kind[NRPHY_NSYMB];
-  uint32_t sym_arg[NRPHY_NSYMB];
-};
-
-} // namespace
-
-// What a plan derives from the SHAPE of its PDUs alone -- allocation, symbols, DM-RS and reserved patterns, ports and
-// layers -- kept across plans by a caller that builds one plan per PDU (the asynchronous queue): RE mapping tables and
-// zero-fill run lists.  Everything else in a plan (slot index, RNTI, scrambling identities, transport-block size and
-// the sizes derived from it, weights) is per PDU and rebuilt every time; it costs a few microseconds.
-struct PlanShapeCache {
-  struct Remap {
-    ReMapping             m;     // sym_arg of SYM_TABLE symbols relative to `table`
-    std::vector<uint16_t> table;
-  };
-  struct Zero {
-    std::vector<ZeroSeg> segs; // long runs first
-    uint32_t             nof_long = 0;
-  };
-  std::map<std::vector<uint64_t>, Remap> remap;
-  std::map<std::vector<uint64_t>, Zero>  zero; // key: grid size + port + the allocation signatures of the PDUs on the port
-  static constexpr size_t MAX_ENTRIES = 256;   // shapes in use at a time are few; a full cache starts over
-};
-
-PlanShapeCache* plan_shape_cache_create()
-{
-  return new (std::nothrow) PlanShapeCache;
-}
-void plan_shape_cache_destroy(PlanShapeCache* c)
-{
-  delete c;
-}
-
-namespace {
-
-// Seam B (encode + rate match + interleave only): the codeword size and N_ref are given, there is no allocation.
-struct EncodeOnly {
-  uint32_t nof_re; // channel symbols per layer
-  uint32_t nref;
-};
-
-int plan_create(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus, const uint64_t* tb_offset,
-                const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
-                const EncodeOnly* enc, nrphy_pdsch_plan_t** out, PlanPlacement* place = nullptr);
-
-} // namespace
-
-int nrphy_pdsch_plan_create_placed(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus, const uint64_t* tb_offset,
-                                   const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports,
-                                   uint32_t grid_nof_subc, PlanPlacement* place, nrphy_pdsch_plan_t** out)
-{
-  return plan_create(ctx, n_pdu, pdus, tb_offset, grid_index, nof_grids, grid_nof_ports, grid_nof_subc, nullptr, out, place);
-}
-
-extern "C" int nrphy_pdsch_plan_create(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus,
-                                       const uint64_t* tb_offset, const uint32_t* grid_index, uint32_t nof_grids,
-                                       uint32_t grid_nof_ports, uint32_t grid_nof_subc, nrphy_pdsch_plan_t** out)
-{
-  return plan_create(ctx, n_pdu, pdus, tb_offset, grid_index, nof_grids, grid_nof_ports, grid_nof_subc, nullptr, out);
-}
-
-namespace {
-
-int plan_create(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus, const uint64_t* tb_offset,
-                const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
-                const EncodeOnly* enc, nrphy_pdsch_plan_t** out, PlanPlacement* place)
-{
-  if (ctx == nullptr || out == nullptr || (n_pdu != 0 && (pdus == nullptr || tb_offset == nullptr)) ||
-      grid_nof_ports == 0 || grid_nof_ports > NRPHY_MAX_PORTS || grid_nof_subc == 0 || grid_nof_subc % 12 != 0 ||
-      grid_nof_subc > NRPHY_MAX_RB * 12) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  *out = nullptr;
-  if (place == nullptr) {
-    HIP_TRY(hipSetDevice(ctx->device));
-  }
-  nrphy_pdsch_plan* plan = new (std::nothrow) nrphy_pdsch_plan;
-  if (plan == nullptr) {
-    return NRPHY_ERR_CAPACITY;
-  }
-  PlanShapeCache* shapes = place ? place->cache : nullptr;
-  if (shapes != nullptr && shapes->remap.size() + shapes->zero.size() > PlanShapeCache::MAX_ENTRIES) {
-    shapes->remap.clear();
-    shapes->zero.clear();
-  }
-  plan->ctx            = ctx;
-  plan->nof_grids      = nof_grids;
-  plan->grid_nof_ports = grid_nof_ports;
-  plan->grid_nof_subc  = grid_nof_subc;
-  plan->encode_only    = enc != nullptr;
-
-  std::vector<CbWork>   work;
-  std::vector<DmrsWork> dmrs;
-  std::vector<CrcWork>  crc_work;
-  std::vector<uint64_t> remap_sig;
-  std::map<std::vector<uint64_t>, ReMapping> remap_cache;
-  std::vector<ScrWork>  scr_work;
-  std::unordered_map<SeqKey, SeqShare, SeqKeyHash> seq_shares; // the sequences earlier PDUs of the plan ask for
-  std::vector<uint8_t>  seq_fresh;      // per PDU: SEQ_NEW_SCR / SEQ_NEW_DMRS -- the first PDU that asks for the sequence generates it
-  uint32_t              seed_slots = 0; // seed slots handed out: one per work item of every distinct scrambling sequence
-  uint64_t              seq_words = 0;  // the same sequences as words: where the next one would start, and their plain sum (the rule)
-  uint64_t              seq_words_sum = 0;
-  bool                  seq_words_fit = true; // every sequence within the x1 table and the 32-bit offsets
-  std::vector<std::vector<uint32_t>> pdus_of_grid(nof_grids);
-  std::vector<float>    weights;
-  std::vector<uint16_t> re_table;
-  std::vector<uint8_t>  mask(grid_nof_subc);
-  std::vector<uint16_t> list;
-  uint64_t              cw_bits = 0;
-  int                   status  = NRPHY_OK;
-
-  for (uint32_t i = 0; i != n_pdu && status == NRPHY_OK; ++i) {
-    const nrphy_pdsch_pdu_t& pdu = pdus[i];
-    if (enc == nullptr ? nrphy_pdsch_validate(&pdu) != NRPHY_OK
-                       : (pdu.qm < 2 || pdu.qm > 8 || (pdu.qm & 1U) || pdu.rv > 3 || pdu.nof_layers == 0 ||
-                          pdu.nof_layers > NRPHY_MAX_LAYERS || pdu.tb_size_bytes == 0 ||
-                          pdu.tb_size_bytes > NRPHY_MAX_TB_BYTES || (pdu.ldpc_base_graph != 1 && pdu.ldpc_base_graph != 2))) {
-      status = NRPHY_ERR_INVALID_PDU;
-      break;
-    }
-    const uint32_t g = grid_index ? grid_index[i] : 0;
-    if (g >= nof_grids || pdu.nof_ports > grid_nof_ports || (tb_offset[i] & 3U) != 0 ||
-        (enc == nullptr && 12U * (unsigned)(mask_highest(pdu.prb_mask) + 1) > grid_nof_subc)) {
-      status = NRPHY_ERR_ARGUMENT;
-      break;
-    }
-    PduDev pd;
-    std::memset(&pd, 0, sizeof(pd));
-    // RE mapping tables (shared by the PDUs of the batch that repeat this allocation).
-    unsigned nof_re = 0;
-    remap_sig.clear();
-    append_allocation_signature(pdu, remap_sig);
-    auto cached = remap_cache.find(remap_sig);
-    if (enc != nullptr) {
-      nof_re = enc[i].nof_re; // no RE mapping: every symbol empty, the count given
-      for (unsigned l = 0; l <= NRPHY_NSYMB; ++l) {
-        pd.sym_re_start[l] = (l == NRPHY_NSYMB) ? nof_re : 0;
-      }
-    } else if (cached != remap_cache.end()) {
-      std::memcpy(pd.sym_re_start, cached->second.sym_re_start, sizeof(pd.sym_re_start));
-      std::memcpy(pd.sym_kind, cached->second.sym_kind, sizeof(pd.sym_kind));
-      std::memcpy(pd.sym_arg, cached->second.sym_arg, sizeof(pd.sym_arg));
-      nof_re = pd.sym_re_start[NRPHY_NSYMB];
-    } else {
-      // The mapping with its table entries numbered from zero (`rel`): from the caller's shape cache, or built here.
-      PlanShapeCache::Remap        built;
-      const PlanShapeCache::Remap* rel = nullptr;
-      if (shapes != nullptr) {
-        auto known = shapes->remap.find(remap_sig);
-        if (known != shapes->remap.end()) {
-          rel = &known->second;
-        }
-      }
-      if (rel == nullptr) {
-        for (unsigned l = 0; l != NRPHY_NSYMB; ++l) {
-          built.m.sym_re_start[l] = nof_re;
-          built.m.sym_arg[l]      = 0;
-          data_re_mask(pdu, l, mask);
-          list.clear();
-          for (unsigned k = 0; k != grid_nof_subc; ++k) {
-            if (mask[k]) {
-              list.push_back((uint16_t)k);
-            }
-          }
-          if (list.empty()) {
-            built.m.sym_kind[l] = SYM_NONE;
-          } else if ((unsigned)(list.back() - list.front()) + 1 == list.size()) {
-            built.m.sym_kind[l] = SYM_CONTIGUOUS;
-            built.m.sym_arg[l]  = list.front();
-          } else {
-            built.m.sym_kind[l] = SYM_TABLE;
-            built.m.sym_arg[l]  = (uint32_t)built.table.size();
-            // Reuse an earlier symbol's list when identical (the common case).
-            for (unsigned lp = 0; lp != l; ++lp) {
-              if (built.m.sym_kind[lp] == SYM_TABLE && built.m.sym_re_start[lp + 1] - built.m.sym_re_start[lp] == list.size() &&
-                  std::equal(list.begin(), list.end(), built.table.begin() + built.m.sym_arg[lp])) {
-                built.m.sym_arg[l] = built.m.sym_arg[lp];
-                break;
-              }
-            }
-            if (built.m.sym_arg[l] == built.table.size()) {
-              built.table.insert(built.table.end(), list.begin(), list.end());
-            }
-          }
-          nof_re += (unsigned)list.size();
-          built.m.sym_re_start[l + 1] = nof_re;
-        }
-        rel = &built;
-        if (shapes != nullptr) {
-          rel = &shapes->remap.insert({remap_sig, built}).first->second;
-        }
-      }
-      // Into this plan: the table entries behind what the plan holds already.
-      const uint32_t base = (uint32_t)re_table.size();
-      re_table.insert(re_table.end(), rel->table.begin(), rel->table.end());
-      std::memcpy(pd.sym_re_start, rel->m.sym_re_start, sizeof(pd.sym_re_start));
-      std::memcpy(pd.sym_kind, rel->m.sym_kind, sizeof(pd.sym_kind));
-      for (unsigned l = 0; l != NRPHY_NSYMB; ++l) {
-        pd.sym_arg[l] = rel->m.sym_arg[l] + (rel->m.sym_kind[l] == SYM_TABLE ? base : 0U);
-      }
-      nof_re = pd.sym_re_start[NRPHY_NSYMB];
-      ReMapping m;
-      std::memcpy(m.sym_re_start, pd.sym_re_start, sizeof(m.sym_re_start));
-      std::memcpy(m.sym_kind, pd.sym_kind, sizeof(m.sym_kind));
-      std::memcpy(m.sym_arg, pd.sym_arg, sizeof(m.sym_arg));
-      remap_cache.insert({remap_sig, m});
-    }
-    if (nof_re == 0) {
-      status = NRPHY_ERR_INVALID_PDU;
-      break;
-    }
-    nrphy_pdsch_derived_t d;
-    derive(pdu, nof_re, d, enc ? &enc[i].nref : nullptr);
-    if (d.lifting_size == 0 || d.nof_codeblocks > NRPHY_MAX_CODEBLOCKS || d.nof_codeblocks > nof_re ||
-        d.rm_length_short == 0) {
-      status = NRPHY_ERR_INVALID_PDU;
-      break;
-    }
-    const unsigned kb = (pdu.ldpc_base_graph == 1) ? 22 : 10;
-    pd.tb_offset      = tb_offset[i];
-    pd.cw_bit_offset  = cw_bits;
-    pd.tb_bytes       = pdu.tb_size_bytes;
-    pd.grid_index     = g;
-    pd.graph          = (pdu.ldpc_base_graph - 1) * NOF_LIFTING_SIZES + (uint32_t)lifting_position(d.lifting_size);
-    pd.zc             = d.lifting_size;
-    pd.kb             = kb;
-    pd.K              = d.segment_length;
-    pd.info_bits      = d.cb_info_bits;
-    pd.filler         = d.nof_filler_bits;
-    pd.tb_crc_bits    = d.nof_tb_crc_bits;
-    pd.cb_crc_bits    = d.nof_cb_crc_bits;
-    pd.zero_pad       = d.zero_pad;
-    pd.C              = d.nof_codeblocks;
-    pd.n_short        = d.nof_short_segments;
-    pd.e_short        = d.rm_length_short;
-    pd.e_long         = d.rm_length_long;
-    pd.n_cb           = d.n_cb;
-    pd.k0             = d.k0;
-    pd.qm             = pdu.qm;
-    pd.nof_layers     = pdu.nof_layers;
-    pd.nof_ports      = pdu.nof_ports;
-    pd.c_init         = (pdu.rnti << 15) + pdu.n_id; // q = 0 (pdsch_modulator_impl.cpp:35)
-    pd.nof_re         = nof_re;
-    // Parity rows rate matching can reach (the reference always computes all of them, pdsch_encoder_impl.cpp:52).
-    {
-      const unsigned nsys = (kb - 2) * d.lifting_size;
-      unsigned       fs = std::min(nsys - d.nof_filler_bits, d.n_cb), fe = std::min(nsys, d.n_cb);
-      const unsigned flen = fe - fs, n_valid = d.n_cb - flen;
-      const unsigned rank0 = d.k0 < fs ? d.k0 : (d.k0 < fe ? fs : d.k0 - flen);
-      unsigned       last; // highest circular-buffer position read
-      if (rank0 + d.rm_length_long > n_valid) {
-        last = d.n_cb - 1;
-      } else {
-        unsigned u = rank0 + d.rm_length_long - 1;
-        last       = u < fs ? u : u + flen;
-      }
-      const unsigned nodes = divide_ceil(last + 1 + 2 * d.lifting_size, d.lifting_size);
-      pd.nof_rows          = std::max(4U, nodes > kb ? nodes - kb : 0U);
-    }
-    // Precoding weights: data weights carry the modulation and power scaling (pdsch_modulator_impl.cpp:98-102).
-    {
-      const float avg     = (pdu.qm == 2) ? 2.0F : (pdu.qm == 4) ? 10.0F : (pdu.qm == 6) ? 42.0F : 170.0F;
-      float       scaling = std::sqrt(1 / avg);
-      const float cfg     = std::pow(10.0F, -pdu.ratio_pdsch_data_to_sss_dB / 20.0F);
-      if (std::isnormal(cfg)) {
-        scaling *= cfg;
-      }
-      const unsigned nw      = 2 * pdu.nof_prg * pdu.nof_ports * pdu.nof_layers;
-      pd.weights_offset      = (uint32_t)weights.size();
-      for (unsigned k = 0; k != nw; ++k) {
-        weights.push_back(pdu.precoding ? pdu.precoding[k] * scaling : 0.0F); // no weights in an encode-only plan
-      }
-      pd.dmrs_weights_offset = (uint32_t)weights.size();
-      for (unsigned k = 0; k != nw; ++k) {
-        weights.push_back(pdu.precoding ? pdu.precoding[k] : 0.0F);
-      }
-      pd.nof_prg       = pdu.nof_prg;
-      pd.prg_size_subc = pdu.prg_size_rb * 12;
-    }
-    // DM-RS (dmrs_pdsch_processor_impl.cpp:84-106).
-    pd.dmrs_symbol_mask = pdu.dmrs_symbol_mask;
-    pd.dmrs_zero_other_group = (pdu.nof_cdm_groups_without_data == 2 && (pdu.nof_layers + 1) / 2 == 1) ? 1U : 0U;
-    pd.dmrs_ref_rb      = (pdu.ref_point == 1) ? pdu.bwp_start_rb : 0;
-    {
-      const float amp   = std::pow(10.0F, -pdu.ratio_pdsch_dmrs_to_sss_dB / 20.0F);
-      pd.dmrs_amplitude = (float)(M_SQRT1_2 * (double)amp);
-    }
-    for (unsigned l = 0; l != NRPHY_NSYMB; ++l) {
-      // 14 symbols per slot also with extended cyclic prefix: the reference takes get_nsymb_per_slot(NORMAL) here
-      // (dmrs_pdsch_processor_impl.cpp:95), and a drop-in has to produce the same pilots.
-      const uint64_t a  = (uint64_t)(14 * pdu.slot_index + l + 1) * (2 * pdu.scrambling_id + 1);
-      pd.dmrs_c_init[l] = (uint32_t)(((a << 17) + (2 * pdu.scrambling_id + (pdu.n_scid ? 1 : 0))) & 0x7FFFFFFFULL);
-      if ((pdu.dmrs_symbol_mask >> l) & 1U) {
-        const uint32_t first = (uint32_t)mask_lowest(pdu.prb_mask), end = (uint32_t)mask_highest(pdu.prb_mask) + 1;
-        for (uint32_t b = first; b < end; b += DMRS_PRB_CHUNK) {
-          dmrs.push_back({i, l, b, std::min<uint32_t>(end, b + DMRS_PRB_CHUNK)});
-        }
-      }
-    }
-    for (unsigned w = 0; w != NRPHY_PRB_WORDS; ++w) {
-      pd.prb_mask[2 * w]     = (uint32_t)pdu.prb_mask[w];
-      pd.prb_mask[2 * w + 1] = (uint32_t)(pdu.prb_mask[w] >> 32);
-    }
-    pd.first_prb = (uint32_t)mask_lowest(pdu.prb_mask);
-    pd.end_prb   = (uint32_t)mask_highest(pdu.prb_mask) + 1;
-    if (pdu.nof_cdm_groups_without_data < (pdu.nof_layers + 1) / 2) {
-      plan->dmrs_separate = true; // data is mapped on RE that also carry DM-RS: the reference lets DM-RS win
-    }
-    pdus_of_grid[g].push_back(i);
-    // Work items: every codeblock owns a whole number of RE (rm_length is a multiple of nof_layers * Qm).
-    const unsigned lq = pdu.nof_layers * pdu.qm;
-    const size_t   work_before = work.size();
-    for (unsigned cb = 0; cb != d.nof_codeblocks; ++cb) {
-      const unsigned nre = ((cb < d.nof_short_segments) ? d.rm_length_short : d.rm_length_long) / lq;
-      for (unsigned begin = 0; begin < nre; begin += RE_CHUNK) {
-        const unsigned count = std::min<unsigned>(RE_CHUNK, nre - begin);
-        work.push_back({i, cb, begin, count});
-        {
-          // The wave expands its scrambling words from a 31-word seed into the LDS that held the codeblock: room for them
-          // (the chunk's words from the one its first bit lies in, plus the word a misaligned read runs into).
-          const uint64_t bit0 = (uint64_t)(cb < d.nof_short_segments ? cb * d.rm_length_short
-                                                                     : d.nof_short_segments * d.rm_length_short +
-                                                                           (cb - d.nof_short_segments) * d.rm_length_long) +
-                                (uint64_t)begin * lq;
-          const uint32_t need = std::max<uint32_t>(31U, (uint32_t)(((bit0 & 31U) + (uint64_t)count * lq + 31U) / 32U) + 1U);
-          plan->lds_lin_words = std::max<uint32_t>(plan->lds_lin_words, (need + 3U) & ~3U);
-        }
-        // LDS the wave needs for the symbol bytes (32 per block + 8 words).
-        plan->lds_symb_words = std::max<uint32_t>(plan->lds_symb_words,
-                                                  (((count * pdu.nof_layers + 31) / 32) * 8 + 8 + 3) & ~3U);
-      }
-    }
-    plan->lds_lin_words = std::max<uint32_t>(plan->lds_lin_words,
-                                             ((((kb + pd.nof_rows) * d.lifting_size + 31) / 32) + 2 + 3) & ~3U);
-    plan->lds_graph_words = std::max<uint32_t>(
-        plan->lds_graph_words, (48U + ctx->graphs[pd.graph].row_ptr[std::min<uint32_t>(pd.nof_rows, MAX_BG_ROWS)] + 3U) & ~3U);
-    // Scrambling sequence of the PDU: one word per 32 codeword bits plus the word a misaligned read runs into, plus the
-    // length of a seed (the last work item's 31 words may reach beyond the codeword; the sequence simply goes on).  Stored
-    // are these words or only the work items' seeds, one form per plan (behind the DM-RS sequences, below).
-    pd.scr_words  = (d.codeword_bits + 31U) / 32U + 1U + 31U;
-    // One DM-RS sequence per DM-RS symbol.
-    pd.dmrs_seq_words  = (12U * (pd.end_prb - pd.dmrs_ref_rb) + 31U) / 32U + 1U;
-    {
-      // Sequences are generated once per run and distinct sequence, not once per PDU: a batch of slots of one UE asks for the
-      // same scrambling seeds in every slot and for the same DM-RS sequences in every frame.  The seeds depend on c_init and on
-      // where the work items start in the codeword; the DM-RS sequences on the DM-RS symbols' c_init and on their length.  One
-      // look-up per PDU (both keys at once); what a new pair shares with earlier PDUs is found by a look-up per half.  Nothing
-      // here outlives the plan's creation, and every run still computes every distinct sequence from scratch.
-      const uint32_t nof_dmrs_words = (uint32_t)(((uint64_t)pd.dmrs_seq_words * (unsigned)__builtin_popcount(pdu.dmrs_symbol_mask) + 3U) & ~3ULL);
-      const uint32_t nof_items      = (uint32_t)(work.size() - work_before);
-      uint8_t        fresh          = (uint8_t)(SEQ_NEW_SCR | (nof_dmrs_words != 0 ? SEQ_NEW_DMRS : 0));
-      SeqShare       share          = {seed_slots, (uint32_t)seq_words, (uint32_t)plan->scr_words};
-      if (n_pdu != 1) {
-        SeqKey key;
-        key.scr  = {pd.c_init, pd.C, pd.n_short, pd.e_short, pd.e_long, lq};
-        key.dmrs = {};
-        key.dmrs[0] = pdu.dmrs_symbol_mask;
-        key.dmrs[1] = pd.dmrs_seq_words;
-        for (unsigned l = 0; l != NRPHY_NSYMB; ++l) {
-          key.dmrs[2 + l] = ((pdu.dmrs_symbol_mask >> l) & 1U) ? pd.dmrs_c_init[l] : 0U;
-        }
-        auto both = seq_shares.find(key);
-        if (both != seq_shares.end()) {
-          share = both->second;
-          fresh = 0;
-        } else {
-          SeqKey half = key;
-          half.dmrs   = {};
-          half.dmrs[1] = ~0U; // (no DM-RS sequence has this length)
-          auto scr_known = seq_shares.insert({half, share});
-          if (!scr_known.second) {
-            share.seed_first      = scr_known.first->second.seed_first;
-            share.scr_word_offset = scr_known.first->second.scr_word_offset;
-            fresh &= (uint8_t)~SEQ_NEW_SCR;
-          }
-          if (nof_dmrs_words != 0) {
-            half     = key;
-            half.scr = {}; // (no codeword has zero bits per resource element)
-            auto dmrs_known = seq_shares.insert({half, share});
-            if (!dmrs_known.second) {
-              share.dmrs_seq_offset = dmrs_known.first->second.dmrs_seq_offset;
-              fresh &= (uint8_t)~SEQ_NEW_DMRS;
-            }
-          }
-          seq_shares.insert({key, share});
-        }
-      }
-      pd.seed_first      = share.seed_first;
-      pd.scr_word_offset = share.scr_word_offset;
-      pd.dmrs_seq_offset = share.dmrs_seq_offset;
-      if (fresh & SEQ_NEW_SCR) {
-        seed_slots += nof_items;
-        seq_words_sum += pd.scr_words;
-        seq_words += (pd.scr_words + 15U) & ~15ULL; // every sequence starts a 64-byte line
-        seq_words_fit = seq_words_fit && pd.scr_words <= (uint32_t)GOLD_X1_WORDS && seq_words <= 0xFFFFFFFFULL;
-        ++plan->n_scr_seq;
-      }
-      if (fresh & SEQ_NEW_DMRS) {
-        plan->scr_words += nof_dmrs_words;
-        ++plan->n_dmrs_seq;
-      }
-      seq_fresh.push_back(fresh);
-    }
-    plan->n_cb += d.nof_codeblocks;
-    plan->cw_offset.push_back(cw_bits);
-    cw_bits += (d.codeword_bits + 31U) & ~31ULL;
-    plan->pdus.push_back(pd);
-  }
-  // Sequence work: a workgroup per distinct scrambling sequence -- the first PDU that asks for it walks it -- with that
-  // PDU's DM-RS sequences on its spare waves if they are new too; a PDU that shares its scrambling sequence and has DM-RS
-  // sequences of its own (another slot of the same UE) gets a workgroup that generates those alone.
-  if (status == NRPHY_OK) {
-    // A plan with many sequences fills the device with one workgroup each (seeding a generator is the costly part:
-    // measured 0.111 / 0.098 / 0.096 ms per 1024 distinct config-3 sequences with 4 / 2 / 1 parts); one with few is split
-    // for latency.
-    // (A/B and test knob: parts of a sequence in a plan of many)
-    const uint32_t parts_big = ctx->tune.scr_parts_big > 0 ? (uint32_t)std::min((int)SCR_PARTS, ctx->tune.scr_parts_big) : 1U;
-    const uint32_t parts_max = plan->n_scr_seq >= 128 ? parts_big : SCR_PARTS;
-    for (uint32_t i = 0; i != n_pdu; ++i) {
-      const PduDev&  pd       = plan->pdus[i];
-      const uint32_t own_dmrs = (seq_fresh[i] & SEQ_NEW_DMRS) ? 1U : 0U;
-      if (seq_fresh[i] & SEQ_NEW_SCR) {
-        const uint32_t parts = std::min<uint32_t>(parts_max, std::max<uint32_t>(1, pd.scr_words >> 11));
-        const uint32_t chunk = divide_ceil(pd.scr_words, parts);
-        for (uint32_t first = 0, k = 0; first < pd.scr_words; first += chunk, ++k) {
-          scr_work.push_back({i, first, std::min(chunk, pd.scr_words - first), k == 0 ? own_dmrs : 0U});
-        }
-      } else if (own_dmrs) {
-        scr_work.push_back({i, 0U, 0U, 1U});
-      }
-    }
-  }
-  // TB-CRC work: the transport block in 16 KiB regions, a workgroup per run of regions.  A small batch gets a workgroup
-  // per region (latency); a big one has workgroups enough and lets each walk several regions, the next one's words in
-  // flight while it reduces the current one (a workgroup per region spent two thirds of its time waiting for its loads:
-  // profiles/r03_prologue_trace.txt).
-  for (uint32_t i = 0; i != n_pdu && status == NRPHY_OK; ++i) {
-    PduDev&         pd = plan->pdus[i];
-    const CrcField& f  = (pd.tb_crc_bits == 16) ? CRC16_FIELD : CRC24A_FIELD;
-    const uint32_t  n  = pd.tb_bytes;
-    const uint32_t  regions = divide_ceil(n, TB_CRC_REGION_BYTES);
-    const uint32_t  want  = std::max<uint32_t>(1, std::min<uint32_t>(regions, TB_CRC_TARGET_WORK / std::max<uint32_t>(1, n_pdu)));
-    uint32_t        per   = std::min<uint32_t>(TB_CRC_MAX_REGIONS_PER_WORK, divide_ceil(regions, want));
-    if (ctx->tune.crc_regions > 0) { // (A/B and test knob: regions per workgroup)
-      per = std::max(1, std::min((int)TB_CRC_MAX_REGIONS_PER_WORK, ctx->tune.crc_regions));
-    }
-    pd.crc_first      = (uint32_t)crc_work.size();
-    pd.crc_count      = divide_ceil(regions, per);
-    if (pd.crc_count > 64) { // one lane of the attaching wave per share
-      status = NRPHY_ERR_INVALID_PDU;
-      break;
-    }
-    for (uint32_t region = 0; region < regions; region += per) {
-      const uint32_t count      = std::min(per, regions - region);
-      const int64_t  region_end = (int64_t)(region + count) * TB_CRC_REGION_BYTES;
-      crc_work.push_back({i, region, f.xpow((int64_t)f.order + 8 * ((int64_t)n - region_end)), count});
-    }
-  }
-  if (status != NRPHY_OK) {
-    delete plan;
-    return status;
-  }
-  // Zero-fill work: per (grid, port) the runs of subcarriers no PDU maps (data or DM-RS).
-  std::vector<ZeroWork> zero_work;
-  std::vector<ZeroSeg>  zero_segs;
-  {
-    std::map<std::vector<uint64_t>, std::array<uint32_t, 3>> seen; // segment list -> (begin, count, long runs)
-    std::vector<uint8_t>  cov((size_t)NRPHY_NSYMB * grid_nof_subc);
-    std::vector<uint64_t> key, sig;
-    std::map<std::vector<uint64_t>, std::array<uint32_t, 3>> by_signature; // allocation -> (begin, count, long runs)
-    for (uint32_t g = 0; g != (enc ? 0U : nof_grids); ++g) { // an encode-only plan writes no grid
-      for (uint32_t port = 0; port != grid_nof_ports; ++port) {
-        // Everything the coverage of this (grid, port) depends on: grids that repeat an allocation (the normal case
-        // in a batch of slots) reuse its segment list without rebuilding the RE masks.
-        sig.clear();
-        for (uint32_t i : pdus_of_grid[g]) {
-          const nrphy_pdsch_pdu_t& pdu = pdus[i];
-          if (port >= pdu.nof_ports) {
-            continue;
-          }
-          append_allocation_signature(pdu, sig);
-        }
-        auto known = by_signature.find(sig);
-        if (known != by_signature.end()) {
-          if (known->second[1] != 0) {
-            zero_work.push_back({g, port, known->second[0], known->second[1], known->second[2]});
-          }
-          continue;
-        }
-        if (shapes != nullptr) {
-          // The run list of this coverage from an earlier plan of the caller (the grid size is part of the key).
-          sig.push_back(((uint64_t)grid_nof_subc << 32) | port);
-          auto kept = shapes->zero.find(sig);
-          sig.pop_back();
-          if (kept != shapes->zero.end()) {
-            const std::array<uint32_t, 3> where = {(uint32_t)zero_segs.size(), (uint32_t)kept->second.segs.size(),
-                                                   kept->second.nof_long};
-            zero_segs.insert(zero_segs.end(), kept->second.segs.begin(), kept->second.segs.end());
-            by_signature.insert({sig, where});
-            if (where[1] != 0) {
-              zero_work.push_back({g, port, where[0], where[1], where[2]});
-            }
-            continue;
-          }
-        }
-        std::fill(cov.begin(), cov.end(), 0);
-        for (uint32_t i : pdus_of_grid[g]) {
-          const nrphy_pdsch_pdu_t& pdu = pdus[i];
-          if (port >= pdu.nof_ports) {
-            continue;
-          }
-          for (unsigned l = 0; l != NRPHY_NSYMB; ++l) {
-            uint8_t* row = &cov[(size_t)l * grid_nof_subc];
-            data_re_mask(pdu, l, mask);
-            for (unsigned k = 0; k != grid_nof_subc; ++k) {
-              row[k] |= mask[k];
-            }
-            if ((pdu.dmrs_symbol_mask >> l) & 1U) {
-              // RE of a CDM group that is reserved (no data) but carries no pilots of this PDU are zeroed by the
-              // DM-RS waves themselves (dmrs_zero_other_group): as zero-fill work they would be 1-RE segments.
-              const unsigned groups = (pdu.nof_cdm_groups_without_data == 2) ? 2 : (pdu.nof_layers + 1) / 2;
-              for (unsigned prb = 0; 12 * prb < grid_nof_subc; ++prb) {
-                if (mask_test(pdu.prb_mask, prb)) {
-                  for (unsigned k = 0; k != 12; ++k) {
-                    row[12 * prb + k] |= (k % 2) < groups;
-                  }
-                }
-              }
-            }
-          }
-        }
-        key.clear();
-        for (unsigned l = 0; l != NRPHY_NSYMB; ++l) {
-          const uint8_t* row = &cov[(size_t)l * grid_nof_subc];
-          unsigned       k   = 0;
-          while (k < grid_nof_subc) {
-            if (row[k]) {
-              ++k;
-              continue;
-            }
-            unsigned k0 = k;
-            while (k < grid_nof_subc && !row[k]) {
-              ++k;
-            }
-            key.push_back(((uint64_t)l << 32) | ((uint64_t)k0 << 16) | (k - k0));
-          }
-        }
-        if (key.empty()) {
-          by_signature.insert({sig, {0, 0, 0}});
-          if (shapes != nullptr) {
-            sig.push_back(((uint64_t)grid_nof_subc << 32) | port);
-            shapes->zero.insert({sig, PlanShapeCache::Zero()});
-            sig.pop_back();
-          }
-          continue;
-        }
-        auto it = seen.find(key);
-        if (it == seen.end()) {
-          // Long runs first (the wave clears each one together), then the short ones (one lane per run).
-          const uint32_t begin = (uint32_t)zero_segs.size();
-          uint32_t       nof_long = 0;
-          for (int pass = 0; pass != 2; ++pass) {
-            for (uint64_t v : key) {
-              const bool is_long = (v & 0xFFFF) >= ZERO_LONG_RUN;
-              if (is_long == (pass == 0)) {
-                zero_segs.push_back({(uint16_t)(v >> 32), (uint16_t)((v >> 16) & 0xFFFF), (uint16_t)(v & 0xFFFF), 0});
-                nof_long += is_long ? 1U : 0U;
-              }
-            }
-          }
-          it = seen.insert({key, {begin, (uint32_t)key.size(), nof_long}}).first;
-        }
-        by_signature.insert({sig, it->second});
-        zero_work.push_back({g, port, it->second[0], it->second[1], it->second[2]});
-        if (shapes != nullptr) {
-          PlanShapeCache::Zero z;
-          z.segs.assign(zero_segs.begin() + it->second[0], zero_segs.begin() + it->second[0] + it->second[1]);
-          z.nof_long = it->second[2];
-          sig.push_back(((uint64_t)grid_nof_subc << 32) | port);
-          shapes->zero.insert({sig, std::move(z)});
-          sig.pop_back();
-        }
-      }
-    }
-  }
-  plan->n_zero_work = (uint32_t)zero_work.size();
-  plan->cw_bits = cw_bits;
-  plan->n_work  = (uint32_t)work.size();
-  {
-    // One bucket per (modulation order, layers), PDU and codeblock order kept inside (launch_codeblocks).
-    const auto bucket_of = [&](const CbWork& w) { return cb_bucket(plan->pdus[w.pdu].qm, plan->pdus[w.pdu].nof_layers); };
-    std::stable_sort(work.begin(), work.end(), [&](const CbWork& a, const CbWork& b) { return bucket_of(a) < bucket_of(b); });
-    for (const CbWork& w : work) {
-      ++plan->bucket_begin[bucket_of(w) + 1];
-    }
-    for (uint32_t b = 0; b != CB_BUCKETS; ++b) {
-      plan->bucket_begin[b + 1] += plan->bucket_begin[b];
-    }
-    // A PDU's work items stay together and in order (one bucket per PDU, stable sort): where they start.
-    for (size_t k = work.size(); k-- != 0;) {
-      plan->pdus[work[k].pdu].item_first = (uint32_t)k;
-    }
-    // The distinct scrambling sequences behind the DM-RS sequences: their words while those stay within the budget, else their
-    // seeds, 32 words per work item.  One form per plan, so that a launch has one.  The sharing key is the same in both forms
-    // (the words alone would need only c_init).  (A/B and test knob: NRPHY_SCR_WORDS = 0 always seeds, 1 always words.)
-    const uint64_t words_offset = (plan->scr_words + 15U) & ~15ULL; // the words start a 64-byte line
-    plan->scr_as_words = seq_words_fit && (ctx->tune.scr_words < 0 ? seq_words_sum * 4U <= SCR_WORDS_BUDGET_BYTES : ctx->tune.scr_words != 0);
-    if (plan->scr_as_words && place != nullptr &&
-        words_offset + seq_words + std::max<size_t>(4, crc_work.size()) > place->scratch_capacity_words) {
-      plan->scr_as_words = false; // caller-owned scratch sized for seeds
-    }
-    plan->scr_words   = plan->scr_as_words ? words_offset : (plan->scr_words + 3U) & ~3ULL;
-    plan->seed_offset = plan->scr_words;
-    plan->scr_words += plan->scr_as_words ? seq_words : 32ULL * seed_slots;
-    // The codeblock waves load 2 * NRPHY_MAX_PORTS * layers weights whatever the port count (pdsch_kernels.hip, phase_b).
-    weights.insert(weights.end(), 2 * NRPHY_MAX_PORTS * NRPHY_MAX_PORTS, 0.0F);
-  }
-  plan->n_dmrs  = (uint32_t)dmrs.size();
-  plan->n_crc_work = (uint32_t)crc_work.size();
-  plan->n_scr_work = (uint32_t)scr_work.size();
-  {
-    DeviceArena          arena;
-    arena.add(&plan->d_crc_work, crc_work.data(), crc_work.size() * sizeof(CrcWork));
-    arena.add(&plan->d_scr_work, scr_work.data(), scr_work.size() * sizeof(ScrWork));
-    arena.add(&plan->d_pdus, plan->pdus.data(), plan->pdus.size() * sizeof(PduDev));
-    arena.add(&plan->d_work, work.data(), work.size() * sizeof(CbWork));
-    arena.add(&plan->d_dmrs, dmrs.data(), dmrs.size() * sizeof(DmrsWork));
-    arena.add(&plan->d_weights, weights.data(), weights.size() * sizeof(float));
-    arena.add(&plan->d_re_table, re_table.data(), re_table.size() * sizeof(uint16_t));
-    arena.add(&plan->d_zero_work, zero_work.data(), zero_work.size() * sizeof(ZeroWork));
-    arena.add(&plan->d_zero_segs, zero_segs.data(), zero_segs.size() * sizeof(ZeroSeg));
-    void* scratch = nullptr;
-    // Behind the tables: what every run rewrites before it reads it -- the sequences and the TB-CRC shares.
-    const uint64_t scr_alloc = (std::max<uint64_t>(4, plan->scr_words) + 3U) & ~3ULL;
-    const uint64_t scratch_words = scr_alloc + std::max<size_t>(4, crc_work.size());
-    if (place != nullptr) {
-      // Caller-owned memory: no allocation, no copy, no synchronisation here (the asynchronous queue's submit path).
-      if (arena.bytes() > place->table_capacity || scratch_words > place->scratch_capacity_words) {
-        delete plan;
-        return NRPHY_ERR_CAPACITY;
-      }
-      arena.place(place->h_tables, place->d_tables);
-      place->table_bytes  = arena.bytes();
-      plan->arena_external = true;
-      scratch              = place->d_scratch;
-    } else if (arena.commit(&plan->d_arena, sizeof(uint32_t) * scratch_words, &scratch) != hipSuccess) {
-      nrphy_pdsch_plan_destroy(plan);
-      return NRPHY_ERR_DEVICE;
-    }
-    plan->d_scr    = (uint32_t*)scratch;
-    plan->d_tb_crc = plan->d_scr + scr_alloc;
-  }
-  {
-    // A batch that mixes modulations and is big enough for one launch per bucket (launch_codeblocks) runs those launches side by
-    // side: its side streams exist from here on, so that a run makes no HIP object and can be captured in a graph.
-    uint32_t nof_buckets = 0;
-    for (uint32_t b = 0; b != CB_BUCKETS; ++b) {
-      nof_buckets += plan->bucket_begin[b + 1] != plan->bucket_begin[b] ? 1U : 0U;
-    }
-    if (place == nullptr && nof_buckets > 1 && plan->n_work >= CB_MIXED_MAX_WORK &&
-        !plan_side_streams(plan, std::min<uint32_t>(nof_buckets - 1, nrphy_pdsch_plan::MAX_AUX))) {
-      nrphy_pdsch_plan_destroy(plan);
-      return NRPHY_ERR_DEVICE;
-    }
-  }
-  // The dynamic LDS of the codeblock launch also serves the DM-RS waves it may carry.
-  plan->lds_lin_words = std::max<uint32_t>(plan->lds_lin_words, 64);
-  // The scratch region the stages of a codeblock wave share (pdsch_kernels.hip, CbShared): CRC tables, then doubled
-  // systematic blocks + graph rows, then modulation table + symbol bytes.
-  plan->lds_u_words = std::max<uint32_t>({256U * NRPHY_CRC_SLICES, NRPHY_CB_U_GRAPH_OFFSET + plan->lds_graph_words, 512U + plan->lds_symb_words});
-  *out = plan;
-  return NRPHY_OK;
-}
-
-} // namespace
-
-// The plan's side streams and fork / join events for bucket launches that run side by side (nrphy_pdsch_run).
-static bool plan_side_streams(nrphy_pdsch_plan* plan, uint32_t want)
-{
-  while (plan->n_aux < want) {
-    const uint32_t k = plan->n_aux;
-    if (plan->fork_event == nullptr && hipEventCreateWithFlags(&plan->fork_event, hipEventDisableTiming) != hipSuccess) {
-      return false;
-    }
-    if (hipStreamCreateWithFlags(&plan->aux_stream[k], hipStreamNonBlocking) != hipSuccess) {
-      return false;
-    }
-    if (hipEventCreateWithFlags(&plan->join_event[k], hipEventDisableTiming) != hipSuccess) {
-      (void)hipStreamDestroy(plan->aux_stream[k]);
-      return false;
-    }
-    ++plan->n_aux;
-  }
-  return true;
-}
-
-extern "C" int nrphy_pdsch_plan_destroy(nrphy_pdsch_plan_t* plan)
-{
-  if (plan == nullptr) {
-    return NRPHY_OK;
-  }
-  if (!plan->arena_external) {
-    (void)hipSetDevice(plan->ctx->device);
-    (void)hipFree(plan->d_arena); // null for a plan whose creation failed half-way
-  }
-  for (uint32_t k = 0; k != plan->n_aux; ++k) {
-    (void)hipStreamDestroy(plan->aux_stream[k]);
-    (void)hipEventDestroy(plan->join_event[k]);
-  }
-  if (plan->fork_event != nullptr) {
-    (void)hipEventDestroy(plan->fork_event);
-  }
-  for (hipEvent_t e : plan->events) {
-    (void)hipEventDestroy(e);
-  }
-  delete plan;
-  return NRPHY_OK;
-}
-
-extern "C" uint32_t nrphy_pdsch_plan_nof_codeblocks(const nrphy_pdsch_plan_t* plan)
-{
-  return plan ? plan->n_cb : 0;
-}
-
-extern "C" int nrphy_pdsch_plan_nof_sequences(const nrphy_pdsch_plan_t* plan, uint32_t* scrambling, uint32_t* dmrs)
-{
-  if (plan == nullptr) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  if (scrambling != nullptr) {
-    *scrambling = plan->n_scr_seq;
-  }
-  if (dmrs != nullptr) {
-    *dmrs = plan->n_dmrs_seq;
-  }
-  return NRPHY_OK;
-}
-
-extern "C" int nrphy_pdsch_plan_scrambling_form(const nrphy_pdsch_plan_t* plan)
-{
-  return plan == nullptr ? -1 : (plan->scr_as_words ? 1 : 0);
-}
-
-extern "C" uint64_t nrphy_pdsch_plan_codeword_bits(const nrphy_pdsch_plan_t* plan)
-{
-  return plan ? plan->cw_bits : 0;
-}
-
-extern "C" uint64_t nrphy_pdsch_plan_codeword_offset(const nrphy_pdsch_plan_t* plan, uint32_t pdu)
-{
-  return (plan && pdu < plan->cw_offset.size()) ? plan->cw_offset[pdu] : 0;
-}
-
-extern "C" int nrphy_pdsch_run(nrphy_pdsch_plan_t* plan, const uint8_t* d_tb, void* d_grid, uint8_t* d_cw_rm,
-                               uint8_t* d_cw_scrambled, int zero_grids, void* stream)
-{
-  if (plan == nullptr || d_tb == nullptr || (plan->encode_only && d_grid != nullptr)) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  const TraceRange trace_run("process_pdsch");
-  nrphy_ctx*  ctx = plan->ctx;
-  hipStream_t s   = stream ? (hipStream_t)stream : ctx->stream;
-  PdschLaunch p;
-  p.pdus           = plan->d_pdus;
-  p.work           = plan->d_work;
-  p.dmrs_work      = plan->d_dmrs;
-  p.crc_work       = plan->d_crc_work;
-  p.scr_work       = plan->d_scr_work;
-  p.n_scr_work     = plan->n_scr_work;
-  p.tbcrc          = ctx->d_tbcrc;
-  p.n_crc_work     = plan->n_crc_work;
-  p.weights        = plan->d_weights;
-  p.re_table       = plan->d_re_table;
-  p.graphs         = ctx->d_graphs;
-  p.gold           = ctx->d_gold;
-  p.x1_words       = ctx->d_x1;
-  p.tb_crc_part        = plan->d_tb_crc;
-  const bool merge_dmrs = d_grid != nullptr && !plan->dmrs_separate;
-  p.zero_work          = plan->d_zero_work;
-  p.zero_segs          = plan->d_zero_segs;
-  p.scr                = plan->d_scr;
-  p.scr_seq            = plan->d_scr + plan->seed_offset;
-  p.scr_as_words       = plan->scr_as_words ? 1U : 0U;
-  p.n_zero_work        = (d_grid != nullptr && zero_grids) ? plan->n_zero_work : 0;
-  p.zero_fill          = (d_grid != nullptr && zero_grids) ? 1U : 0U;
-  p.n_dmrs_in_launch   = merge_dmrs ? plan->n_dmrs : 0;
-  p.n_pdu          = (uint32_t)plan->pdus.size();
-  p.n_work         = plan->n_work;
-  p.work_base      = 0;
-  p.n_dmrs_work    = plan->n_dmrs;
-  p.grid_nof_ports = plan->grid_nof_ports;
-  p.grid_nof_subc  = plan->grid_nof_subc;
-  p.lds_lin_words  = plan->lds_lin_words;
-  p.lds_u_words    = plan->lds_u_words;
-  // Store policy of the DM-RS / zero-fill waves at the tail of the codeblock launch: non-temporal (NRPHY_EXTRAS_NT=0: default
-  // policy).  It moves time from the OFDM launch that follows to the codeblock launch.  Before the OFDM launch took its grids
-  // last to first the balance depended on the box (+1.2 % whole step where the OFDM launch is slow, 0 ... -1 % where it is
-  // fast); with that order, A/B on one box, two rounds (profiles/r03_codeblock_experiments.txt): codeblock 0.301 -> 0.314 ms,
-  // OFDM 0.500 -> 0.466 ms, whole step +2.0 %.
-  // (Placing those waves first or between the codeblock waves instead: the codeblock launch 0.44 / 0.46 ms -- their stores push
-  // the transport blocks and sequences out of the cache.)
-  p.extras_nt      = ctx->tune.extras_nt;
-  p.prologue_order = ctx->tune.prologue_order;
-#ifdef NRPHY_PROBES
-  // Profiling variant: stop the codeblock waves after a stage to time the stages apart (outputs are then incomplete).
-  p.profile_stage = ctx->tune.profile_stage;
-#else
-  p.profile_stage = 0;
-#endif
-  const size_t cw_bytes = (size_t)(plan->cw_bits / 8);
-  if (d_cw_rm) {
-    HIP_TRY(hipMemsetAsync(d_cw_rm, 0, cw_bytes, s));
-  }
-  if (d_cw_scrambled) {
-    HIP_TRY(hipMemsetAsync(d_cw_scrambled, 0, cw_bytes, s));
-  }
-  hipEvent_t* ev = nullptr;
-  if (plan->timed_runs < plan->max_timed_runs && plan->timing_counter++ % plan->timing_stride == 0) {
-    ev = &plan->events[4 * plan->timed_runs++];
-    HIP_TRY(hipEventRecord(ev[0], s));
-  }
-  HIP_TRY(launch_prologue(p, d_tb, s));
-  if (ev) {
-    HIP_TRY(hipEventRecord(ev[1], s));
-  }
-  {
-    const TraceRange trace_cb("CB batch");
-    // NRPHY_CB_DISPATCH: 1 = the one-launch mixed kernel, 2 = one launch per (Qm, layers) bucket, unset = by plan shape.
-    const int   dispatch     = ctx->tune.cb_dispatch;
-    uint32_t    nof_buckets  = 0;
-    hipStream_t streams[1 + nrphy_pdsch_plan::MAX_AUX] = {s};
-    uint32_t    n_streams = 1;
-    if (codeblocks_take_bucket_launches(p, plan->bucket_begin, dispatch, &nof_buckets) && nof_buckets > 1) {
-      const uint32_t want = std::min<uint32_t>(nof_buckets - 1, nrphy_pdsch_plan::MAX_AUX);
-      // (made at plan creation for a plan that takes bucket launches by its shape; here only when NRPHY_CB_DISPATCH forces
-      // them on a small one -- such a first run creates streams and is not for graph capture)
-      if (!plan_side_streams(plan, want)) {
-        return NRPHY_ERR_DEVICE;
-      }
-      HIP_TRY(hipEventRecord(plan->fork_event, s));
-      for (uint32_t k = 0; k != want; ++k) {
-        HIP_TRY(hipStreamWaitEvent(plan->aux_stream[k], plan->fork_event, 0));
-        streams[n_streams++] = plan->aux_stream[k];
-      }
-    }
-    HIP_TRY(launch_codeblocks(p, plan->bucket_begin, dispatch, d_tb, (uint32_t*)d_grid, (uint32_t*)d_cw_rm,
-                              (uint32_t*)d_cw_scrambled, streams, n_streams));
-    for (uint32_t k = 1; k < n_streams; ++k) {
-      HIP_TRY(hipEventRecord(plan->join_event[k - 1], streams[k]));
-      HIP_TRY(hipStreamWaitEvent(s, plan->join_event[k - 1], 0));
-    }
-  }
-  if (ev) {
-    HIP_TRY(hipEventRecord(ev[2], s));
-  }
-  if (d_grid && !merge_dmrs) {
-    // After the data: when data RE share a CDM group with DM-RS the reference lets DM-RS overwrite them.
-    const TraceRange trace_dmrs("process_dmrs");
-    HIP_TRY(launch_dmrs(p, (uint32_t*)d_grid, s));
-    if (ev) {
-      HIP_TRY(hipEventRecord(ev[3], s));
-    }
-  }
-  if (ev) { // (an event between two launches costs the stream a few microseconds: none where no launch follows)
-    plan->timed_dmrs[plan->timed_runs - 1] = (d_grid && !merge_dmrs) ? 1 : 0;
-  }
-  return NRPHY_OK;
-}
-
-extern "C" int nrphy_pdsch_plan_enable_timing(nrphy_pdsch_plan_t* plan, uint32_t max_runs)
-{
-  if (plan == nullptr) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  for (hipEvent_t e : plan->events) {
-    (void)hipEventDestroy(e);
-  }
-  plan->events.assign(4 * (size_t)max_runs, nullptr);
-  for (hipEvent_t& e : plan->events) {
-    HIP_TRY(hipEventCreate(&e));
-  }
-  plan->timed_dmrs.assign(max_runs, 0);
-  plan->max_timed_runs = max_runs;
-  plan->timed_runs     = 0;
-  plan->timing_counter = 0;
-  return NRPHY_OK;
-}
-
-extern "C" int nrphy_pdsch_plan_timing_stride(nrphy_pdsch_plan_t* plan, uint32_t stride)
-{
-  if (plan == nullptr || stride == 0) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  plan->timing_stride  = stride;
-  plan->timing_counter = 0;
-  return NRPHY_OK;
-}
-
-extern "C" int nrphy_pdsch_plan_kernel_times(nrphy_pdsch_plan_t* plan, float avg_ms[4], uint32_t* nof_runs)
-{
-  if (plan == nullptr || avg_ms == nullptr) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  double sum[4] = {0, 0, 0, 0};
-  for (uint32_t r = 0; r != plan->timed_runs; ++r) {
-    hipEvent_t*    ev   = &plan->events[4 * r];
-    const unsigned last = plan->timed_dmrs[r] ? 3 : 2;
-    HIP_TRY(hipEventSynchronize(ev[last]));
-    float ms = 0;
-    for (unsigned k = 0; k != last; ++k) {
-      HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-      sum[k] += ms;
-    }
-    HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[last]));
-    sum[3] += ms;
-  }
-  for (int k = 0; k != 4; ++k) {
-    avg_ms[k] = plan->timed_runs ? (float)(sum[k] / plan->timed_runs) : 0.f;
-  }
-  if (nof_runs) {
-    *nof_runs = plan->timed_runs;
-  }
-  plan->timed_runs = 0;
-  return NRPHY_OK;
-}
-
-extern "C" int nrphy_pdsch_process_host(nrphy_ctx_t* ctx, const nrphy_pdsch_pdu_t* pdu, const uint8_t* tb, void* grid,
-                                        uint32_t grid_nof_ports, uint32_t grid_nof_subc, uint8_t* cw_rm,
-                                        uint8_t* cw_scrambled)
-{
-  if (ctx == nullptr || pdu == nullptr || tb == nullptr) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  HostCall            call(ctx);
-  nrphy_pdsch_plan_t* plan   = nullptr;
-  uint64_t            tb_off = 0;
-  uint32_t            gi     = 0;
-  int rc = nrphy_pdsch_plan_create(ctx, 1, pdu, &tb_off, &gi, 1, grid_nof_ports, grid_nof_subc, &plan);
-  if (rc != NRPHY_OK) {
-    return rc;
-  }
-  const size_t tb_alloc   = ((size_t)pdu->tb_size_bytes + 7) & ~(size_t)3;
-  const size_t grid_bytes = (size_t)grid_nof_ports * NRPHY_NSYMB * grid_nof_subc * 4;
-  const size_t cw_bytes   = (size_t)(plan->cw_bits / 8);
-  uint8_t* d_tb   = call.mem<uint8_t>(SCRATCH_TB, tb_alloc);
-  uint8_t* d_grid = grid ? call.mem<uint8_t>(SCRATCH_GRID, grid_bytes) : nullptr;
-  uint8_t* d_rm   = cw_rm ? call.mem<uint8_t>(SCRATCH_CW_RM, cw_bytes) : nullptr;
-  uint8_t* d_scr  = cw_scrambled ? call.mem<uint8_t>(SCRATCH_CW_SCR, cw_bytes) : nullptr;
-  rc = NRPHY_ERR_DEVICE;
-  do {
-    if (d_tb == nullptr || (grid && d_grid == nullptr) || (cw_rm && d_rm == nullptr) ||
-        (cw_scrambled && d_scr == nullptr)) {
-      break;
-    }
-    // The transport block is readable to the next multiple of 4: clear the tail word, then the bytes.
-    if (hipMemsetAsync(d_tb + (tb_alloc - 8), 0, 8, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(d_tb, tb, pdu->tb_size_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-      break;
-    }
-    if (grid && hipMemcpyAsync(d_grid, grid, grid_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-      break;
-    }
-    rc = nrphy_pdsch_run(plan, d_tb, d_grid, d_rm, d_scr, 0, ctx->stream);
-    if (rc != NRPHY_OK) {
-      break;
-    }
-    rc = NRPHY_ERR_DEVICE;
-    nrphy_pdsch_derived_t d;
-    nrphy_pdsch_derive(pdu, &d);
-    const size_t cw_out = (d.codeword_bits + 7) / 8;
-    if (grid && hipMemcpyAsync(grid, d_grid, grid_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
-      break;
-    }
-    if (cw_rm && hipMemcpyAsync(cw_rm, d_rm, cw_out, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
-      break;
-    }
-    if (cw_scrambled && hipMemcpyAsync(cw_scrambled, d_scr, cw_out, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) {
-      break;
-    }
-    if (call.sync() != hipSuccess) {
-      break;
-    }
-    rc = NRPHY_OK;
-  } while (false);
-  nrphy_pdsch_plan_destroy(plan);
-  return rc;
-}
-
-extern "C" int nrphy_pdsch_process_slot_host(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus,
-                                             const uint8_t* const* tbs, void* grid, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
-{
-  if (ctx == nullptr || grid == nullptr || (n_pdu != 0 && (pdus == nullptr || tbs == nullptr))) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  if (n_pdu == 0) {
-    return NRPHY_OK;
-  }
-  // One plan for the slot: every PDU's codeblocks in one launch, all into grid 0.
-  std::vector<uint64_t> tb_off(n_pdu);
-  std::vector<uint32_t> grid_of(n_pdu, 0);
-  size_t                tb_total = 0;
-  for (uint32_t i = 0; i != n_pdu; ++i) {
-    if (tbs[i] == nullptr) {
-      return NRPHY_ERR_ARGUMENT;
-    }
-    tb_off[i] = tb_total;
-    tb_total += ((size_t)pdus[i].tb_size_bytes + 7) & ~(size_t)3; // readable to the next multiple of 4
-  }
-  HostCall            call(ctx);
-  nrphy_pdsch_plan_t* plan = nullptr;
-  int rc = nrphy_pdsch_plan_create(ctx, n_pdu, pdus, tb_off.data(), grid_of.data(), 1, grid_nof_ports, grid_nof_subc, &plan);
-  if (rc != NRPHY_OK) {
-    return rc;
-  }
-  const size_t grid_bytes = (size_t)grid_nof_ports * NRPHY_NSYMB * grid_nof_subc * 4;
-  uint8_t* d_tb   = call.mem<uint8_t>(SCRATCH_TB, tb_total + 8);
-  uint8_t* d_grid = call.mem<uint8_t>(SCRATCH_GRID, grid_bytes);
-  rc              = NRPHY_ERR_DEVICE;
-  do {
-    if (d_tb == nullptr || d_grid == nullptr || hipMemsetAsync(d_tb, 0, tb_total + 8, ctx->stream) != hipSuccess) {
-      break;
-    }
-    bool ok = true;
-    for (uint32_t i = 0; ok && i != n_pdu; ++i) {
-      ok = hipMemcpyAsync(d_tb + tb_off[i], tbs[i], pdus[i].tb_size_bytes, hipMemcpyHostToDevice, ctx->stream) == hipSuccess;
-    }
-    if (!ok || hipMemcpyAsync(d_grid, grid, grid_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-      break;
-    }
-    rc = nrphy_pdsch_run(plan, d_tb, d_grid, nullptr, nullptr, 0, ctx->stream);
-    if (rc != NRPHY_OK) {
-      break;
-    }
-    rc = NRPHY_ERR_DEVICE;
-    if (hipMemcpyAsync(grid, d_grid, grid_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        call.sync() != hipSuccess) {
-      break;
-    }
-    rc = NRPHY_OK;
-  } while (false);
-  nrphy_pdsch_plan_destroy(plan);
-  return rc;
-}
-
-extern "C" int nrphy_pdsch_encode_host(nrphy_ctx_t* ctx, const nrphy_pdsch_encoder_cfg_t* cfg, const uint8_t* tb,
-                                       uint8_t* codeword_bits, uint8_t* codeword_packed)
-{
-  if (ctx == nullptr || cfg == nullptr || tb == nullptr || cfg->nof_layers == 0 ||
-      cfg->nof_ch_symbols % cfg->nof_layers != 0) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  nrphy_pdsch_pdu_t pdu;
-  std::memset(&pdu, 0, sizeof(pdu));
-  pdu.qm              = cfg->qm;
-  pdu.rv              = cfg->rv;
-  pdu.nof_codewords   = 1;
-  pdu.ldpc_base_graph = cfg->base_graph;
-  pdu.tb_size_bytes   = cfg->tb_size_bytes;
-  pdu.nof_layers      = cfg->nof_layers;
-  pdu.nof_ports       = 1;
-  pdu.nof_prg         = 1;
-  pdu.prg_size_rb     = NRPHY_MAX_RB;
-  pdu.tbs_lbrm_bytes  = 1; // unused: N_ref is given
-  const EncodeOnly    enc    = {cfg->nof_ch_symbols / cfg->nof_layers, cfg->nref};
-  std::vector<uint8_t> packed_local; // a copy target: declared before `call`, so that it outlives the drain
-  HostCall             call(ctx);
-  nrphy_pdsch_plan_t* plan   = nullptr;
-  uint64_t            tb_off = 0;
-  uint32_t            gi     = 0;
-  int                 rc     = plan_create(ctx, 1, &pdu, &tb_off, &gi, 1, 1, 12, &enc, &plan);
-  if (rc != NRPHY_OK) {
-    return rc;
-  }
-  const size_t cw_bits  = (size_t)cfg->nof_ch_symbols * cfg->qm;
-  const size_t cw_bytes = (size_t)(plan->cw_bits / 8);
-  const size_t tb_alloc = ((size_t)cfg->tb_size_bytes + 7) & ~(size_t)3;
-  uint8_t*     packed   = codeword_packed;
-  if (packed == nullptr) {
-    packed_local.resize((cw_bits + 7) / 8);
-    packed = packed_local.data();
-  }
-  uint8_t* d_tb = call.mem<uint8_t>(SCRATCH_TB, tb_alloc);
-  uint8_t* d_rm = call.mem<uint8_t>(SCRATCH_CW_RM, cw_bytes);
-  rc            = NRPHY_ERR_DEVICE;
-  do {
-    if (d_tb == nullptr || d_rm == nullptr ||
-        hipMemsetAsync(d_tb + (tb_alloc - 8), 0, 8, ctx->stream) != hipSuccess ||
-        hipMemcpyAsync(d_tb, tb, cfg->tb_size_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) {
-      break;
-    }
-    rc = nrphy_pdsch_run(plan, d_tb, nullptr, d_rm, nullptr, 0, ctx->stream);
-    if (rc != NRPHY_OK) {
-      break;
-    }
-    rc = NRPHY_ERR_DEVICE;
-    if (hipMemcpyAsync(packed, d_rm, (cw_bits + 7) / 8, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        call.sync() != hipSuccess) {
-      break;
-    }
-    rc = NRPHY_OK;
-  } while (false);
-  nrphy_pdsch_plan_destroy(plan);
-  if (rc == NRPHY_OK && codeword_bits != nullptr) { // the reference's codeword span: one bit per byte
-    for (size_t i = 0; i != cw_bits; ++i) {
-      codeword_bits[i] = (packed[i >> 3] >> (7U - (i & 7U))) & 1U;
-    }
-  }
-  return rc;
 }
 
 namespace {

@@ -1,5 +1,5 @@
-// Host-side internals shared by the translation units behind the C ABI (nrphy_host.cpp, dl_control_host.cpp, pdsch_async.cpp,
-// dl_slot_async.cpp, pusch_demod_host.cpp, pusch_chest_host.cpp, prach_host.cpp, prach_demod_host.cpp, pucch_host.cpp, pucch2_host.cpp, srs_host.cpp, uci_host.cpp): the context, its staging buffers, small helpers.  Not part
+// Host-side internals shared by the translation units behind the C ABI (nrphy_host.cpp, pdsch_plan_build.cpp, pdsch_host.cpp,
+// dl_control_host.cpp, pdsch_async.cpp, dl_slot_async.cpp, pusch_demod_host.cpp, pusch_chest_host.cpp, prach_host.cpp, prach_demod_host.cpp, pucch_host.cpp, pucch2_host.cpp, srs_host.cpp, uci_host.cpp): the context, its staging buffers, small helpers.  Not part
 // of the ABI.
 #pragma once
 
@@ -57,6 +57,52 @@ struct CrcField {
 };
 const CrcField CRC24A_FIELD = {0x1864CFBU, 24};
 const CrcField CRC16_FIELD  = {0x11021U, 16};
+
+// The LDPC lifting sizes in ascending order (TS 38.212 Table 5.3.2-1) and the place of one among them (-1: not a lifting size).
+const uint16_t LIFTING_SIZES[NOF_LIFTING_SIZES] = {
+    2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13,  14,  15,  16,  18,  20,  22,  24,  26,  28,  30,  32,  36,  40, 44,
+    48, 52, 56, 60, 64, 72, 80, 88, 96, 104, 112, 120, 128, 144, 160, 176, 192, 208, 224, 240, 256, 288, 320, 352, 384};
+
+int lifting_position(unsigned zc)
+{
+  for (int i = 0; i != NOF_LIFTING_SIZES; ++i) {
+    if (LIFTING_SIZES[i] == zc) {
+      return i;
+    }
+  }
+  return -1;
+}
+
+unsigned divide_ceil(unsigned a, unsigned b)
+{
+  return (a + b - 1) / b;
+}
+
+bool mask_test(const uint64_t* w, unsigned i)
+{
+  return (w[i >> 6] >> (i & 63)) & 1U;
+}
+
+int mask_lowest(const uint64_t* w)
+{
+  for (unsigned i = 0; i != 64 * NRPHY_PRB_WORDS; ++i) {
+    if (mask_test(w, i)) {
+      return (int)i;
+    }
+  }
+  return -1;
+}
+
+int mask_highest(const uint64_t* w)
+{
+  int hi = -1;
+  for (unsigned i = 0; i != 64 * NRPHY_PRB_WORDS; ++i) {
+    if (mask_test(w, i)) {
+      hi = (int)i;
+    }
+  }
+  return hi;
+}
 
 template <typename T>
 hipError_t upload(T** dptr, const void* src, size_t bytes)
@@ -149,6 +195,9 @@ struct Tunables {
 #endif
 };
 Tunables read_tunables();
+
+// Lifted graph of base graph `bg` (1 or 2) at lifting size `zc`, as the encoder's kernels read it (nrphy_host.cpp).
+void build_lifted_graph(unsigned bg, unsigned zc, LiftedGraph& g);
 
 enum ScratchSlot { SCRATCH_TB = 0, SCRATCH_GRID, SCRATCH_CW_RM, SCRATCH_CW_SCR, SCRATCH_IQ, SCRATCH_SMALL,
                    SCRATCH_DECODER, SCRATCH_RX, SCRATCH_COUNT };

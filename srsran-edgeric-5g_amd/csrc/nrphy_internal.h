@@ -1,4 +1,4 @@
-// Internal declarations shared by the host side (nrphy_host.cpp) and the HIP kernels of libmi355nrphy.so.
+// Internal declarations shared by the host side (nrphy_host.cpp, pdsch_plan_build.cpp, pdsch_host.cpp and the other *_host.cpp) and the HIP kernels of libmi355nrphy.so.
 // Not part of the ABI (that is include/mi355_nrphy.h).
 #pragma once
 
@@ -220,7 +220,7 @@ struct PdschLaunch {
   //   seeds  [seed slot][32]: the first 31 words of the x2 part of the sequence from every work item's first word on
   //          (PduDev::seed_first; the codeblock waves expand them, gold_expand_seed_wave, and add the x1 table's words);
   //   words  the PduDev::scr_words words of every sequence, c = x1 ^ x2 (PduDev::scr_word_offset): taken while all of them fit
-  //          an L2 (nrphy_host.cpp, SCR_WORDS_BUDGET_BYTES), read by the codeblock waves like the x1 table.
+  //          an L2 (pdsch_plan_build.cpp, SCR_WORDS_BUDGET_BYTES), read by the codeblock waves like the x1 table.
   uint32_t*          scr_seq;
   uint32_t           scr_as_words;    // 1: words, 0: seeds
   const PduDev*      pdus;

@@ -19,7 +19,7 @@
 #define NRPHY_PHASE_A_STAGED 1
 #endif
 
-// Stage stops of the profiling variants (profiles/make_variant.sh NAME "pdsch_kernels.hip ofdm_kernels.hip nrphy_host.cpp"
+// Stage stops of the profiling variants (profiles/make_variant.sh NAME "pdsch_kernels.hip ofdm_kernels.hip nrphy_host.cpp pdsch_host.cpp pdsch_plan_build.cpp"
 // "-DNRPHY_PROBES"; profiles/stage_pmc.sh, stage_times.sh): the codeblock waves return after stage n, the outputs are then
 // incomplete.  The product library is built without them -- the tests compile to nothing.
 #ifdef NRPHY_PROBES
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(TB_CRC_THREADS) void prologue_kernel(PdschLaunch p,
         NRPHY_WG_TRACE_MARK(6);
         return;
       }
-      // The PDU's work items in the order the plan lists them (nrphy_host.cpp: codeblock by codeblock, RE_CHUNK resource
+      // The PDU's work items in the order the plan lists them (pdsch_plan_build.cpp: codeblock by codeblock, RE_CHUNK resource
       // elements per item), walked with scalar arithmetic alongside the blocks: w0 = the word of the item's first bit.
       const uint32_t lq = pd.qm * pd.nof_layers, n_short = pd.n_short, e_short = pd.e_short, e_long = pd.e_long, C = pd.C;
       const uint32_t nre_short = e_short / lq, nre_long = e_long / lq; // (the only divisions: the walk itself has none)

@@ -615,7 +615,7 @@ RE_CHUNK = 512               # resource elements per codeblock work item (nrphy_
 def seed_walk_layout(d, lq, nof_pdus_in_plan=1):
     """Where the prologue's sequence wave meets the work items of a PDU: (items, boundaries).  items = [(first word of the
     item's scrambling bits, resource elements of the item)] in order; boundaries = the word indices at which a block of 31 rows
-    or a part of the sequence ends (plan rule: csrc/nrphy_host.cpp, "parts"; one part in a plan of 128 PDUs or more)."""
+    or a part of the sequence ends (plan rule: csrc/pdsch_plan_build.cpp, "parts"; one part in a plan of 128 PDUs or more)."""
     G, C, n_short = d["codeword_bits"], d["nof_codeblocks"], d["nof_short_segments"]
     items, bit_cb = [], 0
     for cb in range(C):

@@ -774,6 +774,52 @@ def test_pdsch_async_live_traffic_every_pdu_differs(gpu_ctx, oracle, table_cap, 
     q.close()
 
 
+def test_pdsch_async_shape_cache_starts_over(gpu_ctx, oracle, monkeypatch):
+    """A full shape cache starts over (PlanShapeCache::MAX_ENTRIES = 256 in csrc/pdsch_plan.h), and nothing stale survives.
+
+    A queue of depth 1 has one cache.  On a grid of 1 port every distinct allocation adds two entries, one RE mapping and
+    one zero-fill list, and a plan clears the cache first when it finds more than 256 entries: 129 shapes leave 258, so the
+    130th shape arrives at an empty cache.  140 distinct shapes are submitted (the cache then holds shapes 130 ... 140); then
+    the first 10 again under another RNTI and transport block, which have to be rebuilt; then the last 10 again, which the
+    restarted cache serves.  Another MAX_ENTRIES wants another count of shapes here: more than MAX_ENTRIES / 2 + 1 of them
+    before the ones that come back.  Every grid bit-exact, every status 0, every completion exactly once."""
+    import threading
+    monkeypatch.delenv("NRPHY_ASYNC_ZERO_COPY", raising=False)
+    monkeypatch.delenv("NRPHY_ASYNC_TABLE_CAP", raising=False)
+    rng = np.random.default_rng(256)
+    nof_ports, nof_prb = 1, 24
+    nof_subc = 12 * nof_prb
+    runs = [(start, length) for length in range(1, nof_prb + 1) for start in range(0, nof_prb - length + 1)][:140]
+    assert len(set(runs)) == 140
+
+    def job(run, rnti):
+        start, length = run
+        tb_bits = oracle.tbs(4, 12, 0, 2, 300.0, 1, length)  # as cases.random_pdus: 4 symbols, one DM-RS symbol, two CDM groups
+        pdu = abi.make_pdu(slot_index=rnti % 20, rnti=rnti, bwp_start_rb=0, bwp_size_rb=nof_prb, qm=2, n_id=rnti % 1024,
+                           dmrs_symbols=(2,), nof_cdm_groups_without_data=2, prb_start=start, prb_count=length, start_symbol=2,
+                           nof_symbols=4, base_graph=2, precoding=abi.identity_precoding(1), tb_size_bytes=tb_bits // 8)
+        return pdu, cases.random_tb(rng, pdu)
+
+    jobs = [job(run, 1 + k) for k, run in enumerate(runs)]
+    jobs += [job(run, 1001 + k) for k, run in enumerate(runs[:10])]
+    jobs += [job(run, 2001 + k) for k, run in enumerate(runs[-10:])]
+    q = lib.PdschAsyncQueue(gpu_ctx, 1, nof_ports, nof_subc, max(j[0].tb_size_bytes for j in jobs))
+    results, lock = {}, threading.Lock()
+    for n, (pdu, tb) in enumerate(jobs):
+        def on_done(status, grid, n=n):
+            with lock:
+                results.setdefault(n, []).append((status, grid))
+        while not q.submit(pdu, tb, on_done):
+            q.wait_slot()
+    q.wait()
+    assert sorted(results) == list(range(len(jobs))) and all(len(v) == 1 for v in results.values())
+    for n, (pdu, tb) in enumerate(jobs):
+        status, grid = results[n][0]
+        assert status == 0, n
+        assert np.array_equal(grid, oracle.pdsch_process(pdu, tb, nof_ports, nof_subc)), n
+    q.close()
+
+
 def test_host_span_dft_and_slot_modulator(gpu_ctx, oracle):
     """The host-span entry points the srsRAN adaptors call (dft_processor::run, ofdm_slot_modulator::modulate)."""
     rng = np.random.default_rng(77)
