@@ -2,6 +2,7 @@
 // gfx950 only: 64-lane wavefronts are assumed throughout.
 #pragma once
 
+#include "crc24b_fold.h"
 #include "nrphy_internal.h"
 
 namespace nrphy {

@@ -187,20 +187,6 @@ void build_gold_tables(GoldTables& t, std::vector<uint32_t>& x1_words)
     }
     t.crc24b_table[b] = r & (top - 1);
   }
-  // (b x^(8k) x^24) mod g for k = 0..3: table k is table k - 1 advanced by one byte.
-  for (uint32_t b = 0; b != 256; ++b) {
-    uint32_t r            = t.crc24b_table[b];
-    t.crc24b_slice[0][b] = r;
-    for (int k = 1; k != 4; ++k) {
-      for (int s = 0; s != 8; ++s) {
-        r <<= 1;
-        if (r & top) {
-          r ^= poly;
-        }
-      }
-      t.crc24b_slice[k][b] = r;
-    }
-  }
   {
     auto mulx = [&](uint32_t a, unsigned e) { // a x^e mod g
       for (unsigned s = 0; s != e; ++s) {

@@ -241,14 +241,14 @@ hipError_t launch_prologue(const PdschLaunch& p, const uint8_t* d_tb, hipStream_
 // ================================================================================================================
 // LDS of one codeblock wavefront: `lin` (the codeblock, sized per launch from the largest one the plan contains) and one
 // scratch region `u` that the stages of the wave use one after the other:
-//   building the codeblock   u[0, 256 * NRPHY_CRC_SLICES)      byte tables of the codeblock CRC
+//   building the codeblock   --                                (the codeblock CRC folds in registers: crc24b_fold.h)
 //   LDPC                     u[0, LDPC_DBL_WORDS)              the systematic blocks doubled (ldpc_device.h)
 //                            then LdpcScratch (core rows), then row pointers + edges of the lifted graph rows needed
 //   output stage             u[0, 512)                         the modulation table (index = Qm bits, value = ci8 symbol as floats)
 //                            u[512, ...)                       interleaver output: one byte per modulation symbol
-// At the headline configuration that is 1.3 + 3.2 KB of LDS per wave: 8 waves per SIMD fit the CU's 160 KB.  (Measured,
-// A/B on one box: four CRC tables -- a 32-bit word per step, but 4 KB of scratch and 7 waves -- 0.347 ms per 1024 slots,
-// three tables 0.328 ms.)
+// At the headline configuration that is 1.3 + 3.2 KB of LDS per wave: 8 waves per SIMD fit the CU's 160 KB.  (The codeblock
+// CRC once went through three byte tables in u[0, 768); a plan whose graph rows and symbol bytes need less than that -- few
+// parity rows, few RE per work item -- now takes the smaller region.)
 constexpr uint32_t CB_U_QAM_WORDS     = 512;
 constexpr uint32_t CB_U_LDPC_WORDS    = (sizeof(LdpcScratch) / 4u + 3u) & ~3u;
 constexpr uint32_t CB_U_GRAPH_OFFSET  = LDPC_DBL_WORDS + CB_U_LDPC_WORDS;
@@ -264,8 +264,9 @@ struct CbShared {
 
 // Bounding experiment of round 4 (profiles/r04_lds_conflicts.txt; variant builds only, the results are then WRONG): what the
 // LDS bank conflicts of the data-indexed table look-ups cost.  NRPHY_LDS_PROBE bit 0: the modulation table is read at the
-// lane's own entry, bit 1: the codeblock CRC's byte tables likewise -- the same instructions and dependences (the index still
-// depends on the data through an opaque zero), consecutive addresses instead of data-dependent ones: no conflicts.
+// lane's own entry -- the same instructions and dependences (the index still depends on the data through an opaque zero),
+// consecutive addresses instead of data-dependent ones: no conflicts.  (Bit 1 did the same to the codeblock CRC's byte tables,
+// which are gone.)
 #ifndef NRPHY_LDS_PROBE
 #define NRPHY_LDS_PROBE 0
 #endif
@@ -280,40 +281,52 @@ __device__ __forceinline__ uint32_t lds_probe_index(uint32_t idx, uint32_t bit)
   return idx;
 }
 
-// reg <- CRC24B register after the 32 bits of `word`: independent look-ups (tab[k][b] = (b x^(8k) x^24) mod g) instead of
-// four dependent byte steps.
-__device__ __forceinline__ uint32_t crc24_word_step(const uint32_t* tab, uint32_t reg, uint32_t word)
+// Segmentation: lin[0, total_words) <- the `used` transport-block bits from bit `tb_pos` on, then zeros (the TB CRC and the
+// zero padding of the last codeblock, the CB CRC, the filler bits and the parity region).
+// The transport-block words of SEG_UNROLL trips are requested before the first is used: taken trip by trip, every trip
+// waited out a trip to memory (stage timing: this loop alone cost 0.045 ms per 1024 slots for a hundred instructions).
+constexpr uint32_t SEG_UNROLL = 5; // 320 words: a whole high-rate codeblock with its four core parity blocks
+static_assert(WAVE * SEG_UNROLL * 32u >= 22u * 384u, "one trip holds the payload of the largest codeblock");
+
+// The codeblock starts on a word boundary of the transport block: always the first one, and all of them when info_bits is a
+// multiple of 32, as at the headline.  The limits are wave-uniform (seg_aligned, crc24b_fold.h): a row of 64 words below the
+// first limit is load, byte swap, store behind scalar branches; only the one row that holds the limits tests its lanes and
+// masks the codeblock's last word; the rows behind it are zeros.
+constexpr uint32_t SEG_WHOLE_ROWS = 22u * 384u / 32u / WAVE; // 4: rows of whole payload words in the largest codeblock
+__device__ __forceinline__ void segment_aligned(const uint32_t* src, uint32_t used, uint32_t* lin, uint32_t total_words, uint32_t lane)
 {
-#if NRPHY_CRC_SLICES == 4
-  const uint32_t v = (reg << 8) ^ word;
-  return tab[v & 0xFFu] ^ tab[256u + ((v >> 8) & 0xFFu)] ^ tab[512u + ((v >> 16) & 0xFFu)] ^ tab[768u + (v >> 24)];
-#else
-  const uint32_t v = reg ^ (word >> 8); // 24 bits through three tables, then the last byte
-  uint32_t       r = tab[lds_probe_index(v & 0xFFu, 1)] ^ tab[256u + lds_probe_index((v >> 8) & 0xFFu, 1)] ^ tab[512u + lds_probe_index(v >> 16, 1)];
-  return ((r << 8) & 0xFFFFFFu) ^ tab[lds_probe_index(((r >> 16) ^ word) & 0xFFu, 1)];
-#endif
+  const SegAligned seg  = seg_aligned(used);
+  const uint32_t   rows = seg.whole / WAVE; // <= SEG_WHOLE_ROWS
+  const uint32_t   j    = rows * WAVE + lane; // this lane's word of the row with the limits
+  uint32_t         w[SEG_WHOLE_ROWS];
+#pragma unroll
+  for (uint32_t k = 0; k != SEG_WHOLE_ROWS; ++k) {
+    if (k < rows) {
+      w[k] = src[WAVE * k + lane];
+    }
+  }
+  uint32_t edge = 0;
+  if (j < seg.loads) { // never a word that lies entirely beyond the transport block
+    edge = src[j];
+  }
+#pragma unroll
+  for (uint32_t k = 0; k != SEG_WHOLE_ROWS; ++k) {
+    if (k < rows) {
+      lin[WAVE * k + lane] = __builtin_bswap32(w[k]);
+    }
+  }
+  if (j < total_words) {
+    lin[j] = seg_aligned_word(seg, j, __builtin_bswap32(edge)); // (the words behind the last one were not loaded: zero)
+  }
+  for (uint32_t z = j + WAVE; z < total_words; z += WAVE) {
+    lin[z] = 0u;
+  }
 }
 
-// Fills lin with the K bits of codeblock `cb` (payload, TB CRC + zero padding on the last codeblock, CB CRC, filler
-// zeros) and zeroes the parity region up to `total_words`.
-__device__ inline void build_codeblock(PduRef pd, uint32_t cb, const uint32_t* tbw, const uint32_t* tb_crc_part,
-                                       const GoldTables* tables, CbShared* sh, uint32_t total_words, uint32_t lane,
-                                       uint32_t profile_stage)
+// Any bit offset: two words per codeblock word, a funnel shift, and the bounds per word.
+__device__ __forceinline__ void segment_unaligned(const uint32_t* tbw, uint32_t tb_bits, uint32_t tb_pos, uint32_t used, uint32_t* lin,
+                                                  uint32_t total_words, uint32_t lane)
 {
-  const bool     last    = (cb == pd.C - 1);
-  const uint32_t used    = pd.info_bits - (last ? pd.tb_crc_bits + pd.zero_pad : 0u);
-  const uint32_t tb_pos  = cb * pd.info_bits;
-  const uint32_t tb_bits = pd.tb_bytes * 8u;
-  // The CRC's byte tables (16 bytes per lane and step) are requested first and stored behind the segmentation
-  // (unconditionally: a transport block of one codeblock carries no codeblock CRC and simply does not use them).
-  const uint4* crc_src = reinterpret_cast<const uint4*>(&tables->crc24b_slice[0][0]);
-  const uint4  crc_tab0 = crc_src[lane], crc_tab1 = crc_src[lane + WAVE], crc_tab2 = crc_src[lane + 2 * WAVE];
-#if NRPHY_CRC_SLICES == 4
-  const uint4 crc_tab3 = crc_src[lane + 3 * WAVE];
-#endif
-  // The transport-block words of SEG_UNROLL trips are requested before the first is used: taken trip by trip, every trip
-  // waited out a trip to memory (stage timing: this loop alone cost 0.045 ms per 1024 slots for a hundred instructions).
-  constexpr uint32_t SEG_UNROLL = 5; // 320 words: a whole high-rate codeblock with its four core parity blocks
   for (uint32_t base = lane; base < total_words; base += WAVE * SEG_UNROLL) {
     uint32_t hi[SEG_UNROLL], lo[SEG_UNROLL];
 #pragma unroll
@@ -336,24 +349,27 @@ __device__ inline void build_codeblock(PduRef pd, uint32_t cb, const uint32_t* t
       if (j < total_words) {
         uint32_t v = 0;
         if (pos < used) {
-          v = __funnelshift_l(__builtin_bswap32(lo[k]), __builtin_bswap32(hi[k]), (tb_pos + pos) & 31u);
-          const uint32_t remaining = used - pos;
-          if (remaining < 32u) {
-            v &= topmask(remaining);
-          }
+          v = seg_unaligned_word(__builtin_bswap32(hi[k]), __builtin_bswap32(lo[k]), (tb_pos + pos) & 31u, used - pos);
         }
-        sh->lin[j] = v;
+        lin[j] = v;
       }
     }
   }
-  {
-    uint4* dst           = reinterpret_cast<uint4*>(sh->u);
-    dst[lane]            = crc_tab0;
-    dst[lane + WAVE]     = crc_tab1;
-    dst[lane + 2 * WAVE] = crc_tab2;
-#if NRPHY_CRC_SLICES == 4
-    dst[lane + 3 * WAVE] = crc_tab3;
-#endif
+}
+
+// Fills lin with the K bits of codeblock `cb` (payload, TB CRC + zero padding on the last codeblock, CB CRC, filler
+// zeros) and zeroes the parity region up to `total_words`.
+__device__ inline void build_codeblock(PduRef pd, uint32_t cb, const uint32_t* tbw, const uint32_t* tb_crc_part,
+                                       const GoldTables* tables, CbShared* sh, uint32_t total_words, uint32_t lane,
+                                       uint32_t profile_stage)
+{
+  const bool     last   = (cb == pd.C - 1);
+  const uint32_t used   = pd.info_bits - (last ? pd.tb_crc_bits + pd.zero_pad : 0u);
+  const uint32_t tb_pos = cb * pd.info_bits;
+  if ((tb_pos & 31u) == 0) { // wave-uniform
+    segment_aligned(tbw + (tb_pos >> 5), used, sh->lin, total_words, lane);
+  } else {
+    segment_unaligned(tbw, pd.tb_bytes * 8u, tb_pos, used, sh->lin, total_words, lane);
   }
   wave_sync();
   if (profile_stage == 7) {
@@ -377,18 +393,39 @@ __device__ inline void build_codeblock(PduRef pd, uint32_t cb, const uint32_t* t
     uint32_t       b   = a + per;
     a                  = a > nw ? nw : a;
     b                  = b > nw ? nw : b;
-    uint32_t reg       = 0;
-    for (uint32_t j = a; j < b; ++j) {
-      uint32_t word;
-      if (pad == 0) {
-        word = sh->lin[j];
-      } else if (j == 0) {
-        word = sh->lin[0] >> pad;
-      } else {
-        word = ext32(sh->lin, 32u * j - pad);
+    // The lane's words are requested together and folded modulo x^23 + x^5 + 1 in registers, no table (crc24b_fold.h).  Every
+    // lane takes `per` steps that end at its word b - 1: a lane with fewer words leads with `skip` zero words, which leave
+    // the zero residue and the parity alone, so only the reads test the lane.
+    constexpr uint32_t CRC_MAX_PER = (22u * 384u / 32u + WAVE - 1u) / WAVE; // words per lane of the largest codeblock
+    const uint32_t     first = b - per, skip = a - first;
+    uint32_t           word[CRC_MAX_PER];
+    if (pad == 0) { // wave-uniform
+#pragma unroll
+      for (uint32_t i = 0; i != CRC_MAX_PER; ++i) {
+        word[i] = 0;
+        if (i < per && i >= skip) {
+          word[i] = sh->lin[first + i];
+        }
       }
-      reg = crc24_word_step(sh->u, reg, word);
+    } else {
+#pragma unroll
+      for (uint32_t i = 0; i != CRC_MAX_PER; ++i) {
+        const uint32_t j = first + i;
+        word[i]          = 0;
+        if (i < per && i >= skip) {
+          word[i] = (j == 0) ? sh->lin[0] >> pad : ext32(sh->lin, 32u * j - pad);
+        }
+      }
     }
+    uint32_t res = 0, parity = 0;
+#pragma unroll
+    for (uint32_t i = 0; i != CRC_MAX_PER; ++i) {
+      if (i < per) { // wave-uniform
+        res = crc24b_fold_word(res, word[i]);
+        parity ^= word[i];
+      }
+    }
+    const uint32_t reg = crc24b_fold_finish(res, parity); // the CRC24B register after the lane's words
     // The lane's partial times x^(32 (nw - b)): six independent table look-ups (one per nibble).
     uint32_t part = 0;
     {
@@ -1246,7 +1283,7 @@ __device__ __forceinline__ bool codeblock_front(const PdschLaunch& p, PduRef pd,
     return false;
   }
   const uint32_t total_words = (((kb + pd.nof_rows) * zc + 31u) >> 5) + 2u;
-  // The graph rows are requested now and stored where the CRC tables were once the codeblock is built: their trip to memory
+  // The graph rows are requested now and stored in the scratch region once the codeblock is built: their trip to memory
   // rides under the segmentation and the CRC instead of standing between the CRC and the encoder.
   GraphRows rows;
   rows.fetch(&p.graphs[pd.graph], pd.nof_rows, lane);

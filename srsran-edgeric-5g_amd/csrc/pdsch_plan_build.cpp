@@ -966,9 +966,9 @@ int PlanBuilder::build(size_t scratch_capacity_words)
   plan.n_dmrs_seq  = seqs.n_dmrs_seq;
   // The dynamic LDS of the codeblock launch also serves the DM-RS waves it may carry.
   plan.lds_lin_words = std::max<uint32_t>(plan.lds_lin_words, 64);
-  // The scratch region the stages of a codeblock wave share (pdsch_kernels.hip, CbShared): CRC tables, then doubled
-  // systematic blocks + graph rows, then modulation table + symbol bytes.
-  plan.lds_u_words = std::max<uint32_t>({256U * NRPHY_CRC_SLICES, NRPHY_CB_U_GRAPH_OFFSET + plan.lds_graph_words, 512U + plan.lds_symb_words});
+  // The scratch region the stages of a codeblock wave share (pdsch_kernels.hip, CbShared): doubled systematic blocks + graph
+  // rows, then modulation table + symbol bytes.
+  plan.lds_u_words = std::max<uint32_t>(NRPHY_CB_U_GRAPH_OFFSET + plan.lds_graph_words, 512U + plan.lds_symb_words);
   return NRPHY_OK;
 }
 
