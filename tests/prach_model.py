@@ -2,7 +2,8 @@
 (R/lib/phy/upper/channel_processors/prach_generator_impl.cpp:97-287) and prach_detector_generic_impl::detect
 (prach_detector_generic_impl.cpp:89-359, symbols combined), in float32 or float64 (`dtype`).  The integer arithmetic follows the
 reference's order of operations; the order of the floating-point sums is NumPy's, which is what the tolerances of
-tests/test_prach_detector.py are measured against.
+tests/test_prach_detector.py are measured against.  That file holds generate() and detect() against a recording of the
+reference's own classes (tests/golden/prach_detector_reference_*.npy), decision for decision.
 
 The closed form's constants are derived here (f = u^-1 mod L, the offset from the Gauss sum), not read from the library; the
 logical-to-physical root table (TS 38.211 Table 6.3.3.1-3) is read from csrc/prach_tables.inc, and the thresholds from
@@ -189,7 +190,9 @@ def detect(cfg, symbols, dtype=np.float64):
                tie=[False] * 64, metric=[None] * 64, derived=d)
     with np.errstate(divide="ignore"):
         out["rssi_dB"] = float(rdt.type(10) * np.log10(rssi))
-    if not is_normal(np.asarray(rssi)):
+    # The reference's RSSI is a float whatever `dtype` is, and its early return asks whether that float is normal: an occasion
+    # whose RSSI is subnormal in float32 is not searched, although the metric, a ratio, would not mind.
+    if not is_normal(np.asarray(np.float32(rssi))):
         return out
     start, end = cfg["start_preamble_index"], cfg["start_preamble_index"] + cfg["nof_preamble_indices"]
     shifts, win, margin = d["nof_shifts"], d["win_width"], d["win_margin"]

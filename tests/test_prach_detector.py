@@ -1,14 +1,22 @@
 """PRACH generator and detector (nrphy_prach_*).
 
+The reference's own arithmetic is in tests/golden/prach_detector_reference_*.npy: what srsRAN-5G-ER's prach_detector_generic_impl
+and prach_generator_impl answered on 74 occasions (tests/golden/record_prach_detector_reference.cpp wrote them and states every
+layout).  No recorded decision is fragile, so nothing is set aside when the restatement or the device is compared with it.
+
 CPU: the POD mirrors, nrphy_prach_threshold over the whole cross product against tests/golden/prach_thresholds.json, the validator
 over each refused case and over the reference unit test's 60 configurations (tests/golden/prach_detector_configs.json), the
-extractor that wrote both fixtures, and the restatement's generator (tests/prach_model.py) against the definition of the sequence.
-GPU: the device's generator against the restatement's; the reference configurations on buffers built here; parity of every
-output with the float64 restatement on seeded random occasions; physics (zero buffer, noise only, adjacent shifts, unmonitored
-preambles, caller's thresholds); batches against per-occasion host calls, strided input, graph replay, sentinels.
+extractor that wrote both fixtures, the recording's own consistency, and the restatement (tests/prach_model.py): its generator
+against the definition of the sequence and against the recorded sequences, its detect() in float64 and float32 against the
+recording, decision for decision.
+GPU: the device's generator against the restatement's and the recorded sequences; every recorded occasion through nrphy_prach_run
+and a handful through nrphy_prach_detect_host against the recording; the reference configurations on buffers built here; parity of
+every output with the float64 restatement on seeded random occasions; physics (zero buffer, noise only, adjacent shifts,
+unmonitored preambles, caller's thresholds); batches against per-occasion host calls, strided input, graph replay, sentinels.
 """
 import ctypes as C
 import json
+import math
 import os
 import re
 import subprocess
@@ -34,12 +42,23 @@ SENTINEL = 0x5A5AA5A5
 GUARD = 16  # sentinel words on either side of every output
 
 # Largest |float32 restatement - float64 restatement| of a metric sample relative to max(|metric|, 1e-3), measured on the
-# occasions of test_parity_with_the_restatement (the test prints it again on every run): 3.73e-4.  The device may differ from the
-# float64 restatement by 8 x that: its radix-16 transform and window sums order their additions differently from the
-# restatement's FFT and pairwise sums, and both errors grow with log N.  (The reference binary cannot be built for this block,
-# so the float32 restatement stands in for the reference's own error.)
+# occasions of test_parity_with_the_restatement (the test prints it again on every run): 3.73e-4.  It is what single precision
+# costs the whole metric row of an occasion, the samples far below the peak included, in NumPy's order of operations.  The device
+# may differ from the float64 restatement by 8 x that: its radix-16 transform and window sums order their additions differently
+# from the restatement's FFT and pairwise sums, and both errors grow with log N.
 MODEL_SPREAD = 3.73e-4
 METRIC_TOL = 8 * MODEL_SPREAD
+# The reference's own error, measured against the recording by test_restatement_equals_the_recording (which prints both again on
+# every run): the largest |recorded - float64 restatement| of a detection metric relative to the metric, 2.77e-4, and of rssi_dB,
+# 8.79e-6 dB (at -388 dB, where float32 resolves 3.1e-5 dB; where |rssi_dB| < 64 it is 2.4e-6 dB).
+REF_SPREAD = 2.8e-4
+REF_RSSI_SPREAD_DB = 9e-6
+# The same for the generator: the largest |recorded - restatement| of a component relative to sqrt(L), measured by
+# test_restatement_generator_equals_the_recording: 8.09e-8 (the two build the same float32 table with two libms).
+REF_GENERATOR_SPREAD = 1e-7
+# The recording admits no occasion with a monitored peak within this of the threshold, or with the two largest samples of a
+# detected window within this of the larger.
+RECORDING_MARGIN = 0.02
 # rssi_dB = 10 log10f(rssi): two ulp of log10f and the product's rounding, at |dB| < 64 (ulp 3.8e-6), rounded up.
 RSSI_TOL_DB = 2e-5
 
@@ -221,6 +240,191 @@ def test_restatement_generator_equals_the_definition():
     assert worst < 2e-6
 
 
+RECORDED_FORMATS = ("0", "1", "2", "3", "A1", "A2", "A3", "B1", "B4", "C0", "C2")
+_recording = {}
+
+
+def recording():
+    """The recorded occasions, read once: a list of dicts with cfg, x ([ports][symbols][L] complex64: the int16 pairs times
+    2^-e), words, e, rssi_dB, time_resolution, time_advance_max, detections (rows of preamble index, time advance in seconds,
+    detection_metric), group, origin and nof_tx."""
+    if "cases" not in _recording:
+        load = lambda name: np.load(os.path.join(GOLDEN, "prach_detector_reference_%s.npy" % name))
+        rows, results, detections = load("cases"), load("results"), load("detections")
+        inputs = [load("in%d" % k) for k in range(int(rows[:, 8].max()) + 1)]
+        assert rows.shape[1] == 16 and results.shape == (len(rows), 3) and detections.shape[1] == 3
+        out = []
+        for r, res in zip(rows.tolist(), results):
+            cfg = make_cfg(RECORDED_FORMATS[r[0]], r[3], r[6], r[2], model.SPACINGS[r[1]], r[4], r[5])
+            words = inputs[r[8]][r[9]:r[9] + r[10]]
+            value = np.ldexp(words.astype(np.float32), -r[7])
+            assert value.dtype == np.float32
+            x = (value[:, 0] + 1j * value[:, 1]).astype(np.complex64).reshape(r[6], model.NOF_SYMBOLS[cfg["format"]], -1)
+            out.append(dict(cfg=cfg, x=x, words=words, e=r[7], rssi_dB=float(res[0]), time_resolution=float(res[1]),
+                            time_advance_max=float(res[2]), detections=detections[r[11]:r[11] + r[12]], group=r[13], origin=r[14],
+                            nof_tx=r[15]))
+        _recording["cases"] = out
+    return _recording["cases"]
+
+
+def recorded_models():
+    """model.detect(cfg, x, float64) of every recorded occasion, computed once and shared."""
+    if "models" not in _recording:
+        _recording["models"] = [model.detect(k["cfg"], k["x"], np.float64) for k in recording()]
+    return _recording["models"]
+
+
+def recorded_sequences():
+    """[(format, root_sequence_index, zcz, preamble_index, sequence complex64 [L])] of the recording."""
+    pairs = np.load(os.path.join(GOLDEN, "prach_detector_reference_sequences.npy"))
+    out, at = [], 0
+    while at != len(pairs):
+        fmt = RECORDED_FORMATS[int(pairs[at, 0])]
+        L = model.seq_len(fmt)
+        y = pairs[at + 2:at + 2 + L]
+        out.append((fmt, int(pairs[at, 1]), int(pairs[at + 1, 0]), int(pairs[at + 1, 1]), (y[:, 0] + 1j * y[:, 1]).astype(np.complex64)))
+        at += 2 + L
+    return out
+
+
+def is_early_return(case):
+    """The reference left before the search: the RSSI it reported is not a normal float32."""
+    with np.errstate(under="ignore"):
+        return not model.is_normal(np.asarray(np.float32(10.0) ** (np.float32(case["rssi_dB"]) / np.float32(10.0))))
+
+
+def test_recording_is_what_its_header_states():
+    """The files' sizes, the inputs recomputed from the int16 values and the scales, the case table against
+    prach_detector_configs.json, the ground the edge shapes have to cover, and the two conditions under which no recorded decision
+    is fragile, asserted with the float64 restatement."""
+    names = [n for n in os.listdir(GOLDEN) if n.startswith("prach_detector_reference_")]
+    sizes = [os.path.getsize(os.path.join(GOLDEN, n)) for n in names]
+    assert max(sizes) < 900000 and sum(sizes) < 2000000, dict(zip(names, sizes))
+    cases = recording()
+    rows = {(r["ports"], r["scs"], r["format"], r["zcz"]): r["flag"] for r in thresholds_fixture()}
+    for i, k in enumerate(cases):
+        cfg = k["cfg"]
+        assert k["words"].dtype == np.int16 and k["words"].shape == (cfg["nof_rx_ports"] * model.NOF_SYMBOLS[cfg["format"]] *
+                                                                     model.seq_len(cfg["format"]), 2), i
+        # Every input is its int16 times 2^-e exactly, in float32.
+        back = np.ldexp(np.stack([k["x"].real, k["x"].imag], -1).astype(np.float64).reshape(-1, 2), k["e"])
+        assert (back == k["words"]).all(), i
+        assert rows[(cfg["nof_rx_ports"], cfg["ra_scs"], cfg["format"], cfg["zero_correlation_zone"])] != "red", i
+        assert lib.prach_validate(to_abi(cfg)) == abi.OK, i
+    # The first group is the accepted configurations of the reference's unit test, each reporting its preamble at its delay.
+    fixtures = configs_fixture()
+    accepted = accepted_reference_configurations()
+    first = [k for k in cases if k["group"] == 0]
+    assert len(first) == len(accepted) == 48 and all(k["group"] == 0 for k in cases[:48])
+    for k, f in zip(first, accepted):
+        assert fixtures[k["origin"]] == f and k["cfg"] == reference_cfg(f) and k["nof_tx"] == 1
+        assert [int(v) for v in k["detections"][:, 0]] == [f["preamble_index"]]
+        delay = f["true_delay"] * model.dft_size(f["format"]) * model.SCS_HZ[f["ra_scs"]]
+        assert abs(k["detections"][0, 1] / k["time_resolution"] - delay) <= 2.0, f
+    # The ground of the edge shapes.
+    edges = cases[48:]
+    assert all(k["group"] == 1 for k in edges) and [k["origin"] for k in edges] == list(range(len(edges)))
+    derived = [model.derive(k["cfg"]) for k in edges]
+    assert {k["cfg"]["format"] for k in edges} == {"0", "1", "A1", "A2", "B4"}
+    assert {(k["cfg"]["format"], k["cfg"]["ra_scs"]) for k in edges} >= {("A1", "15"), ("A1", "30"), ("A2", "15"), ("A2", "30"),
+                                                                       ("B4", "15"), ("B4", "30")}
+    assert {k["cfg"]["nof_rx_ports"] for k in edges} == {1, 2, 4}
+    assert any(d["n_cs"] == 0 for d in derived) and any(64 % d["nof_shifts"] for d in derived)
+    assert any(k["cfg"]["nof_preamble_indices"] == 1 for k in edges)
+    assert any(k["cfg"]["start_preamble_index"] % d["nof_shifts"] and
+               (k["cfg"]["start_preamble_index"] + k["cfg"]["nof_preamble_indices"]) % d["nof_shifts"] for k, d in zip(edges, derived))
+    assert any(k["cfg"]["root_sequence_index"] + d["nof_sequences"] > d["L"] - 1 for k, d in zip(edges, derived))
+    reported = [(k, d, int(row[0]), int(round(row[1] / k["time_resolution"]))) for k, d in zip(edges, derived) for row in k["detections"]]
+    assert any(p % d["nof_shifts"] == 0 for k, d, p, _ in reported if d["nof_shifts"] > 1)                     # window 0
+    assert any(p % d["nof_shifts"] == d["nof_shifts"] - 1 for k, d, p, _ in reported if d["nof_shifts"] > 1)  # a root's last
+    assert any(delay == math.ceil(0.8 * d["max_delay"]) - 1 for k, d, p, delay in reported)  # the last delay that is reported
+    assert any(len(k["detections"]) >= 4 for k in edges)
+    assert any(np.diff(k["detections"][:, 0]).min(initial=64) == 1 for k in edges)
+    assert any(k["nof_tx"] > len(k["detections"]) and not is_early_return(k) for k in edges)  # transmitted, not reported
+    assert any(k["nof_tx"] == 0 and not is_early_return(k) and len(k["detections"]) == 0 for k in edges)  # noise only
+    assert any(k["rssi_dB"] == -np.inf and not k["words"].any() for k in edges)
+    assert any(np.isfinite(k["rssi_dB"]) and is_early_return(k) and k["nof_tx"] > 0 for k in edges)  # subnormal RSSI
+    assert any(k["words"].any() and not k["x"][-1].any() and len(k["detections"]) for k in edges)  # a port that is all zero
+    assert all(is_early_return(k) == (k["rssi_dB"] < -300) and (not is_early_return(k) or len(k["detections"]) == 0) for k in cases)
+    metrics = np.concatenate([k["detections"][:, 2] for k in cases])
+    assert len(metrics) > 80 and metrics.min() >= 1.05 and metrics.max() <= 50.0
+    # No fragile decision.
+    windows = 0
+    for i, (k, m) in enumerate(zip(cases, recorded_models())):
+        th = m["derived"]["threshold"]
+        for row in m["metric"]:
+            if row is not None:
+                top = np.sort(row)[-2:]
+                windows += 1
+                assert abs(top[1] / th - 1.0) >= RECORDING_MARGIN, (i, k["cfg"], float(top[1]), th)
+                assert top[1] <= th or top[1] - top[0] > RECORDING_MARGIN * top[1], (i, k["cfg"], top)
+    print("%d cases, %d monitored windows, %d detections with metrics %.2f ... %.2f" % (len(cases), windows, len(metrics),
+                                                                                      metrics.min(), metrics.max()))
+
+
+def compare_detections(case, m, what):
+    """The decisions of a restatement result `m` against the recording, exactly; returns the largest relative difference of a
+    detection metric."""
+    assert m["time_resolution"] == case["time_resolution"] and m["time_advance_max"] == case["time_advance_max"], what
+    want = case["detections"]
+    assert [i for i in range(64) if m["detected"][i]] == [int(v) for v in want[:, 0]], what
+    assert m["nof_detected"] == len(want), what
+    worst = 0.0
+    for index, advance, metric in want:
+        assert m["delay"][int(index)] == int(round(advance / case["time_resolution"])), (what, index)
+        assert m["time_advance"][int(index)] == advance, (what, index)
+        worst = max(worst, abs(m["detection_metric"][int(index)] - metric) / metric)
+    return worst
+
+
+def test_restatement_equals_the_recording():
+    """detect() of the restatement against the reference's on every recorded occasion: the detected set, every delay and both
+    times exactly, in float64 and in float32.  The float64 restatement's distance from the recorded detection_metric and rssi_dB
+    is the reference's own single-precision error: REF_SPREAD and REF_RSSI_SPREAD_DB, measured here.  The float32 restatement
+    adds its own: MODEL_SPREAD for a metric, and for rssi_dB the rounding of log10f and of the product, two ulp of the value."""
+    spread = rssi_spread = rssi_spread_audible = spread32 = 0.0
+    for i, (case, m64) in enumerate(zip(recording(), recorded_models())):
+        m32 = model.detect(case["cfg"], case["x"], np.float32)
+        spread = max(spread, compare_detections(case, m64, (i, case["cfg"], "float64")))
+        worst32 = compare_detections(case, m32, (i, case["cfg"], "float32"))
+        spread32 = max(spread32, worst32)
+        assert worst32 <= REF_SPREAD + MODEL_SPREAD, (i, case["cfg"], worst32)
+        if np.isfinite(case["rssi_dB"]):
+            err = abs(m64["rssi_dB"] - case["rssi_dB"])
+            rssi_spread = max(rssi_spread, err)
+            if abs(case["rssi_dB"]) < 64:
+                rssi_spread_audible = max(rssi_spread_audible, err)
+            assert abs(m32["rssi_dB"] - case["rssi_dB"]) <= REF_RSSI_SPREAD_DB + 2 * float(np.spacing(np.float32(abs(case["rssi_dB"])))), i
+        else:
+            assert m64["rssi_dB"] == case["rssi_dB"] == m32["rssi_dB"], i
+    print("recorded - float64 restatement: detection metric %.3g relative (constant %.3g), rssi_dB %.3g dB (constant %.3g; %.3g dB "
+          "where |rssi_dB| < 64); recorded - float32 restatement: detection metric %.3g"
+          % (spread, REF_SPREAD, rssi_spread, REF_RSSI_SPREAD_DB, rssi_spread_audible, spread32))
+    assert spread <= REF_SPREAD and rssi_spread <= REF_RSSI_SPREAD_DB
+    # What the device is granted against the recording stays well inside the margin the recording keeps around every decision.
+    assert 8 * REF_SPREAD < RECORDING_MARGIN / 4
+
+
+def test_restatement_generator_equals_the_recording():
+    """model.generate against prach_generator_impl::generate on the recorded tuples: both lengths, roots 0 and L - 2, zcz 0 and
+    15, preamble 63, root indices that wrap.  A wrong table index moves a sample by at least 2 pi / 4L x sqrt(L), 1.9e-3 sqrt(L)
+    on 839 elements; the measured difference is far below it."""
+    tuples = recorded_sequences()
+    assert len(tuples) == 12 and {len(y) for *_, y in tuples} == {839, 139}
+    assert {(model.seq_len(f), r) for f, r, _, _, _ in tuples} >= {(839, 0), (839, 837), (139, 0), (139, 137)}
+    assert {z for _, _, z, _, _ in tuples} >= {0, 15} and any(p == 63 for _, _, _, p, _ in tuples)
+    assert any(r + (p if model.n_cs(model.default_scs(f), z) == 0 else p // (model.seq_len(f) // model.n_cs(model.default_scs(f), z)))
+               >= model.seq_len(f) - 1 for f, r, z, p, _ in tuples)
+    worst = 0.0
+    for fmt, root, zcz, pre, want in tuples:
+        got = model.generate(fmt, root, zcz, pre)
+        err = max(np.abs(got.real - want.real).max(), np.abs(got.imag - want.imag).max()) / np.sqrt(model.seq_len(fmt))
+        worst = max(worst, float(err))
+    print("recorded - restatement generator: %.3g sqrt(L) (constant %.3g)" % (worst, REF_GENERATOR_SPREAD))
+    assert worst <= REF_GENERATOR_SPREAD
+    assert REF_GENERATOR_SPREAD < 1e-3 * 2 * np.pi / (4 * 839)
+
+
 # =======================================================================================================================
 # GPU
 # =======================================================================================================================
@@ -352,6 +556,104 @@ def test_reference_configurations_are_detected(gpu_ctx):
         worst = max(worst, err)
         assert err <= 2.0, (i, f, err)
     print("48 of 48 detected, worst delay error %.3f samples" % worst)
+
+
+def check_against_recording(case, res, pre_row, what, stats):
+    """One occasion's result header and preamble slots (NumPy records) against the recording."""
+    found = detected_indices(pre_row)
+    want = case["detections"]
+    assert found == [int(v) for v in want[:, 0]], (what, found)
+    assert int(res["nof_detected"]) == len(found) and int(res["detected_mask"]) == sum(1 << i for i in found), what
+    assert res["time_resolution_s"] == np.float32(case["time_resolution"]), what
+    assert res["time_advance_max_s"] == np.float32(case["time_advance_max"]), what
+    if np.isfinite(case["rssi_dB"]):
+        err = abs(float(res["rssi_dB"]) - case["rssi_dB"])
+        stats["rssi"] = max(stats["rssi"], err)
+        assert err <= RSSI_TOL_DB + REF_RSSI_SPREAD_DB, (what, float(res["rssi_dB"]), case["rssi_dB"])
+    else:
+        assert float(res["rssi_dB"]) == case["rssi_dB"], what
+    for index, advance, metric in want:
+        slot = pre_row[int(index)]
+        assert int(slot["delay_samples"]) == int(round(advance / case["time_resolution"])), (what, index)
+        assert abs(float(slot["time_advance_s"]) - advance) <= model.T_C, (what, index)
+        err = abs(float(slot["detection_metric"]) - metric) / metric
+        stats["ref_metric"] = max(stats["ref_metric"], err)
+        assert err <= 8 * REF_SPREAD, (what, index, float(slot["detection_metric"]), metric)
+    start, end = case["cfg"]["start_preamble_index"], case["cfg"]["start_preamble_index"] + case["cfg"]["nof_preamble_indices"]
+    for i in range(64):
+        if not (start <= i < end) or is_early_return(case):
+            assert pre_row[i].tobytes() == bytes(PREAMBLE_DTYPE.itemsize), (what, i)
+
+
+def check_recorded_occasion(case, m64, res, pre_row, metric_rows, what, stats):
+    """Against the recording, and, for what the reference does not expose (the metric rows, the slots it does not report),
+    against the float64 restatement as test_parity_with_the_restatement does."""
+    check_against_recording(case, res, pre_row, what, stats)
+    if is_early_return(case):
+        assert not metric_rows.any(), what
+    else:
+        compare_with_model(case["cfg"], res, pre_row, metric_rows, m64, what, stats)
+
+
+@pytest.mark.gpu
+def test_recorded_occasions_on_the_device(gpu_ctx):
+    """Every recorded occasion through nrphy_prach_run, formats mixed in one plan, against the reference's answers: the detected
+    set, nof_detected, the mask and every delay identical, the times to float32 and T_c, detection_metric within 8 REF_SPREAD
+    (the factor this file grants the device for its order of summation), rssi_dB within RSSI_TOL_DB + REF_RSSI_SPREAD_DB.  Nothing
+    is set aside."""
+    cases, models = recording(), recorded_models()
+    stats = dict(metric=0.0, pairs=0, set_aside=0, ref_metric=0.0, rssi=0.0)
+    for first in range(0, len(cases), 100):
+        part = cases[first:first + 100]
+        cfgs = [k["cfg"] for k in part]
+        res, pre, met = run_plan(gpu_ctx, cfgs, *pack(cfgs, [k["x"] for k in part]))
+        for i, case in enumerate(part):
+            check_recorded_occasion(case, models[first + i], res[i], pre[i], met[i], (first + i, case["cfg"]), stats)
+    print("%d occasions: device - recorded detection metric %.3g relative (allowed %.3g), rssi_dB %.3g dB (allowed %.3g); device - "
+          "float64 restatement metric rows %.3g (allowed %.3g); %d pairs, %d set aside"
+          % (len(cases), stats["ref_metric"], 8 * REF_SPREAD, stats["rssi"], RSSI_TOL_DB + REF_RSSI_SPREAD_DB, stats["metric"], METRIC_TOL,
+             stats["pairs"], stats["set_aside"]))
+    assert stats["set_aside"] == 0
+
+
+@pytest.mark.gpu
+def test_recorded_occasions_through_the_host_entry_point(gpu_ctx):
+    """nrphy_prach_detect_host on recorded occasions of each shape: long and short, 1, 2 and 4 ports, 1, 2, 4 and 12 symbols, zcz
+    0, part of the preambles monitored, and both early returns."""
+    cases, models = recording(), recorded_models()
+    picked, seen = [], set()
+    for i, k in enumerate(cases[48:], 48):  # the first edge shape of each kind
+        cfg = k["cfg"]
+        kind = (cfg["format"], cfg["nof_rx_ports"], cfg["zero_correlation_zone"] == 0, cfg["nof_preamble_indices"] == 64,
+                is_early_return(k), np.isfinite(k["rssi_dB"]))
+        if (kind[0], kind[1]) not in seen or kind[2:] not in seen:
+            picked.append(i)
+        seen.update([(kind[0], kind[1]), kind[2:]])
+    assert 8 <= len(picked) <= 16
+    assert {cases[i]["cfg"]["format"] for i in picked} == {"0", "1", "A1", "A2", "B4"}
+    assert {cases[i]["cfg"]["nof_rx_ports"] for i in picked} == {1, 2, 4}
+    stats = dict(metric=0.0, pairs=0, set_aside=0, ref_metric=0.0, rssi=0.0)
+    for i in picked:
+        case = cases[i]
+        r, p, met = gpu_ctx.prach_detect_host(to_abi(case["cfg"]), case["x"], with_metric=True)
+        check_recorded_occasion(case, models[i], np.frombuffer(bytes(r), RESULT_DTYPE)[0], np.frombuffer(bytes(p), PREAMBLE_DTYPE), met,
+                                (i, case["cfg"]), stats)
+    print("%d occasions: device - recorded detection metric %.3g relative, rssi_dB %.3g dB" % (len(picked), stats["ref_metric"], stats["rssi"]))
+    assert stats["set_aside"] == 0
+
+
+@pytest.mark.gpu
+def test_generator_equals_the_recording(gpu_ctx):
+    """nrphy_prach_generate_host against prach_generator_impl::generate on the recorded tuples, within the 4e-7 sqrt(L) of
+    test_generator_equals_the_restatement plus the restatement's measured distance from the recording."""
+    worst = 0.0
+    for fmt, root, zcz, pre, want in recorded_sequences():
+        got = gpu_ctx.prach_generate_host(abi.make_prach(format=fmt, ra_scs=model.default_scs(fmt), root_sequence_index=root,
+                                                         zero_correlation_zone=zcz), pre)
+        err = max(np.abs(got.real - want.real).max(), np.abs(got.imag - want.imag).max()) / np.sqrt(model.seq_len(fmt))
+        worst = max(worst, float(err))
+        assert err <= 4e-7 + REF_GENERATOR_SPREAD, (fmt, root, zcz, pre, float(err))
+    print("device - recorded generator: %.3g sqrt(L) (allowed %.3g)" % (worst, 4e-7 + REF_GENERATOR_SPREAD))
 
 
 def parity_occasions(rng, count):
