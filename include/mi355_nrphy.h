@@ -1482,6 +1482,121 @@ int nrphy_ofh_ul_prach_validate(uint32_t n, const nrphy_ofh_ul_prach_section_t* 
 int nrphy_ofh_ul_write_prach(nrphy_ctx_t* ctx, uint32_t n, const nrphy_ofh_ul_prach_section_t* sections, const uint8_t* d_payload,
                              uint64_t payload_bytes, void* d_symbols, uint64_t symbols_elems, void* stream);
 
+/* Open Fronthaul uplink frame receiver: received Ethernet frames in device-visible memory -- of any number of slots and
+ * cells -- to the receive grid, with no host step on the frames' bytes.  Replaces, for a batch of frames,
+ * message_receiver_impl::process_new_frame (R/lib/ofh/receiver/ofh_message_receiver.cpp:59-118) with
+ * vlan_frame_decoder_impl, ecpri::packet_decoder_{use,ignore}_header_payload_size, sequence_id_checker_impl (or the dummy),
+ * uplane_peeker, uplane_message_decoder_{static,dynamic}_compression_impl, data_flow_uplane_uplink_data_impl's filter and
+ * uplane_rx_symbol_data_flow_writer::write_to_resource_grid.  What stays with the caller: the control plane (it says what it
+ * announced through nrphy_ofh_rx_expect_t), update_rx_window_statistics, the re_written bookkeeping and symbol-complete
+ * notifications, logging -- all from the per-frame records -- and the PRACH writes (nrphy_ofh_ul_write_prach from the
+ * records of status 22: its range arithmetic needs the prach_context). */
+typedef struct nrphy_ofh_rx_cfg {            /* message_receiver_config + what the decoders are constructed with */
+  uint8_t  mac_dst[6], mac_src[6];           /* should_ethernet_frame_be_filtered compares these two and eth_type */
+  uint16_t eth_type, reserved_;              /* reserved_: 0 */
+  uint32_t vlan_tag_present;                 /* 0: the NIC stripped the tag (14-byte header, as the reference assumes); 1: a 4-byte
+                                                802.1Q tag follows the addresses and is skipped, TCI not compared (18 bytes) */
+  uint32_t ignore_ecpri_payload_size;        /* 1: packet_decoder_ignore_header_payload_size; 0: ..._use_header_payload_size */
+  uint32_t seq_id_check;                     /* 1: sequence_id_checker_impl; 0: the dummy (always 0) */
+  uint32_t numerology;                       /* 0..4 */
+  uint32_t nof_symbols;                      /* 14 or 12 */
+  uint32_t ru_nof_prbs;                      /* 1..275 */
+  uint32_t static_compression;               /* 1: the two cfgs below go into every section; 0: udCompHdr + reserved byte per section */
+  uint32_t n_ul_eaxc, n_prach_eaxc;          /* 0..4 each (MAX_NOF_SUPPORTED_EAXC) */
+  uint16_t ul_eaxc[4], prach_eaxc[4];        /* below 32 (MAX_SUPPORTED_EAXC_ID_VALUE), distinct within a list */
+  nrphy_ofh_compression_cfg_t compression;       /* filter index 0; iq_scaling unused; ignored with static_compression = 0 */
+  nrphy_ofh_compression_cfg_t prach_compression; /* filter indices 1..7 */
+} nrphy_ofh_rx_cfg_t;
+typedef struct nrphy_ofh_rx_frame {          /* one received frame: bytes [offset, offset + length) of d_frames, any alignment */
+  uint64_t offset;
+  uint32_t length;
+  uint32_t reserved_;                        /* 0 */
+} nrphy_ofh_rx_frame_t;
+typedef struct nrphy_ofh_rx_expect {         /* one (slot, eAxC) for which a control-plane message was sent: both repositories */
+  uint32_t grid_index;                       /* the uplink slot context's grid */
+  uint16_t sfn8;                             /* 0..255: slot.sfn() % 256, the key of uplink_cplane_context_repository */
+  uint16_t eaxc;                             /* one of ul_eaxc */
+  uint16_t prb_start, nof_prb;               /* ul_cplane_context */
+  uint16_t context_symbols;                  /* bit s: uplink_context_repository::get(slot, s) is not empty */
+  uint8_t  subframe, slot;                   /* 0..9, 0..2^numerology - 1 */
+  uint8_t  filter_index;                     /* 0..7: radio_hdr.filter_index */
+  uint8_t  start_symbol, nof_symbols;        /* radio_hdr.start_symbol, ul_cplane_context::nof_symbols */
+  uint8_t  reserved_;                        /* 0 */
+} nrphy_ofh_rx_expect_t;
+/* status: 0 accepted and written; 22 a PRACH message decoded, nothing written; any other value names the first of the
+ * reference's checks, in the reference's order, that dropped the frame:
+ *    1 shorter than 64 bytes                          2 a MAC address or the Ethernet type differs
+ *    3 eCPRI revision not 1, or concatenation         4 (payload-size mode) the payload size exceeds what follows the common
+ *                                                       header; library rule: or is below 5 (no message byte; below 4 the
+ *                                                       reference's subspan is ill-formed)
+ *    5 eCPRI message type not IQ data                 6 pc_id in neither eAxC list
+ *    7 sequence identifier from the past              8 peek_slot_symbol_point fails (under 4 bytes, subframe, slot)
+ *    9 filter index reserved (8..15)                 10 not uplink
+ *   11 payload version not 1                         12 symbol >= nof_symbols
+ *   13 reserved dynamic compression type (7..15)     14 a second complete section (the decoder's result list is full)
+ *   15 no section decoded                            16 library rule: dynamic types 2..6, or none with 1 bit (the reference
+ *                                                       has no decompressor for them)
+ *   17 no expectation for (sfn8, subframe, slot, eAxC), or the symbol outside its range, or another filter index
+ *   18 every-other-RB mode                           19 the symbol-increment bit
+ *   20 the section's PRBs outside [prb_start, prb_start + nof_prb)
+ *   21 the symbol's bit of context_symbols is clear
+ * The sequence checker (7) sees every frame that passed 1..6, in batch order per eAxC and across calls in stream order, and
+ * is updated by it also when a later check drops the frame.  Filter indices 1..7 end at 22 after 16; index 0 goes on to 17.
+ * Fields that decoding did not reach are 0: nothing is filled up to status 5; eaxc and seq_id from 6 on; seq_skipped (the
+ * checker's return value: negative for 7, the number of potentially lost messages otherwise) from 7 on; sfn8, subframe, slot,
+ * symbol and filter_index from 9 on; the section (start_prb and nof_prbs after the "0 means ru_nof_prbs, start 0" rule,
+ * type, data_width, payload_offset) for 0 and from 16 on; expect_index, grid_index and port (the eAxC's position in ul_eaxc)
+ * for 0 and 18..21; nof_prbs_written (write_to_resource_grid's clipping to grid_nof_subc / 12, as nrphy_ofh_ul_write_grid
+ * documents it) for 0. */
+typedef struct nrphy_ofh_rx_record {
+  uint64_t payload_offset;                   /* byte of d_frames of the section's first PRB record */
+  uint32_t status;
+  int32_t  seq_skipped;
+  uint32_t grid_index, expect_index;
+  uint16_t eaxc, seq_id;                     /* pc_id and the 16-bit seq_id field (the checker takes seq_id >> 8) */
+  uint16_t start_prb, nof_prbs, nof_prbs_written, port, sfn8;
+  uint8_t  filter_index, subframe, slot, symbol, type, data_width;
+  uint8_t  reserved_[4];
+} nrphy_ofh_rx_record_t;
+typedef struct nrphy_ofh_rx nrphy_ofh_rx_t;
+/* The object owns the device-resident checker state (initialized + one counter per configured eAxC), the per-(grid, port,
+ * symbol, PRB) ownership words a batch needs for "later message wins" (grown to the largest grid batch seen), and refers to
+ * its context.  reset returns the checker to "first packet is always valid", in stream order.  One object serves one
+ * stream of frames: its calls are issued from one thread at a time and take effect in stream order. */
+int nrphy_ofh_rx_create(nrphy_ctx_t* ctx, const nrphy_ofh_rx_cfg_t* cfg, nrphy_ofh_rx_t** rx);
+int nrphy_ofh_rx_destroy(nrphy_ofh_rx_t* rx);
+int nrphy_ofh_rx_reset(nrphy_ofh_rx_t* rx, void* stream);
+/* Host only (no device work).  NRPHY_ERR_ARGUMENT for: a configuration outside the ranges above (a non-zero reserved_,
+ * flags above 1, eAxC values of 32 or more or repeated within a list, more than 4 of them), under static compression a
+ * compression or prach_compression that nrphy_ofh_decompress refuses, non-zero reserved fields of a descriptor, a frame
+ * range outside [0, frames_bytes), two frame ranges that overlap, grid_nof_subc that is no multiple of 12,
+ * n_ul_eaxc > grid_nof_ports, an expectation with eaxc not in ul_eaxc, grid_index >= nof_grids, sfn8 >= 256,
+ * subframe >= 10, slot >= 1 << numerology, filter_index > 7, start_symbol + nof_symbols > cfg->nof_symbols or
+ * prb_start + nof_prb > 275, and two expectations with the same (sfn8, subframe, slot, eaxc). */
+int nrphy_ofh_rx_validate(const nrphy_ofh_rx_cfg_t* cfg, uint32_t n_frames, const nrphy_ofh_rx_frame_t* frames, uint32_t n_expect,
+                          const nrphy_ofh_rx_expect_t* expects, uint64_t frames_bytes, uint32_t nof_grids, uint32_t grid_nof_ports,
+                          uint32_t grid_nof_subc);
+/* Validates, stages the two host arrays in stream order (as nrphy_ofh_ul_write_grid and nrphy_grid_put do) and does three
+ * launches with no host step or synchronisation between them: (1) one thread per frame parses and runs every stateless check;
+ * (2) one workgroup walks the records per eAxC through the sequence checker, finalises the statuses, and the accepted frames
+ * claim their PRBs, the largest frame index winning; (3) one wave per (frame, 16 PRBs) decompresses -- the arithmetic of
+ * nrphy_ofh_decompress -- and stores the PRBs its frame owns at [grid_index][port][symbol][12 * start_prb ...] of d_grid
+ * [nof_grids][grid_nof_ports][14][grid_nof_subc] cbf16.  When accepted frames cover the same PRB of the same (grid, port,
+ * symbol), the later one in batch order stays, as when the reference takes the frames one after another.  Asynchronous on
+ * `stream`, NOT capturable; n_frames = 0 is NRPHY_OK with no work.  The kernels read no byte of d_frames outside the frames'
+ * own ranges, whatever the bytes in a frame claim, and write only d_records (n_frames records, in frame order, 8-byte
+ * aligned) and the resource elements of accepted sections.  d_grid is 4-byte aligned; d_frames has any alignment. */
+int nrphy_ofh_rx_run(nrphy_ofh_rx_t* rx, uint32_t n_frames, const nrphy_ofh_rx_frame_t* frames, uint32_t n_expect,
+                     const nrphy_ofh_rx_expect_t* expects, const uint8_t* d_frames, uint64_t frames_bytes, void* d_grid,
+                     uint32_t nof_grids, uint32_t grid_nof_ports, uint32_t grid_nof_subc, nrphy_ofh_rx_record_t* d_records,
+                     void* stream);
+/* Host-span form for one frame and one grid (blocking): `frame` is the frame's `length` bytes, `grid` the host copy of one
+ * grid [grid_nof_ports][14][grid_nof_subc] cbf16, read and written in place, so every expectation's grid_index must be 0;
+ * `record` receives the frame's record (its payload_offset counts from the frame's first byte).  The checker state is the
+ * object's, as for nrphy_ofh_rx_run.  Through the context's staging like every _host call. */
+int nrphy_ofh_rx_host(nrphy_ofh_rx_t* rx, const uint8_t* frame, uint32_t length, uint32_t n_expect, const nrphy_ofh_rx_expect_t* expects,
+                      void* grid, uint32_t grid_nof_ports, uint32_t grid_nof_subc, nrphy_ofh_rx_record_t* record);
+
 /* Open Fronthaul downlink transmit: OFDM symbols of the device-resident downlink grid
  * [nof_grids][grid_nof_ports][14][grid_nof_subc] cbf16 (what every downlink writer here produces) to complete, ready-to-send
  * Ethernet frames in device (or pinned) memory, byte for byte those of

@@ -563,6 +563,36 @@ class OfhDlSymbol(C.Structure):
                 ("seq_id", C.c_uint8), ("reserved_", C.c_uint8 * 2)]
 
 
+class OfhRxCfg(C.Structure):
+    """nrphy_ofh_rx_cfg_t: what the reference's message receiver, its decoders and its user-plane decoders are constructed with."""
+    _fields_ = [("mac_dst", C.c_uint8 * 6), ("mac_src", C.c_uint8 * 6), ("eth_type", C.c_uint16), ("reserved_", C.c_uint16),
+                ("vlan_tag_present", C.c_uint32), ("ignore_ecpri_payload_size", C.c_uint32), ("seq_id_check", C.c_uint32),
+                ("numerology", C.c_uint32), ("nof_symbols", C.c_uint32), ("ru_nof_prbs", C.c_uint32), ("static_compression", C.c_uint32),
+                ("n_ul_eaxc", C.c_uint32), ("n_prach_eaxc", C.c_uint32), ("ul_eaxc", C.c_uint16 * 4), ("prach_eaxc", C.c_uint16 * 4),
+                ("compression", OfhCompressionCfg), ("prach_compression", OfhCompressionCfg)]
+
+
+class OfhRxFrame(C.Structure):
+    """nrphy_ofh_rx_frame_t: the byte range of one received frame."""
+    _fields_ = [("offset", C.c_uint64), ("length", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+class OfhRxExpect(C.Structure):
+    """nrphy_ofh_rx_expect_t: one (slot, eAxC) for which a control-plane message was sent."""
+    _fields_ = [("grid_index", C.c_uint32), ("sfn8", C.c_uint16), ("eaxc", C.c_uint16), ("prb_start", C.c_uint16), ("nof_prb", C.c_uint16),
+                ("context_symbols", C.c_uint16), ("subframe", C.c_uint8), ("slot", C.c_uint8), ("filter_index", C.c_uint8),
+                ("start_symbol", C.c_uint8), ("nof_symbols", C.c_uint8), ("reserved_", C.c_uint8)]
+
+
+class OfhRxRecord(C.Structure):
+    """nrphy_ofh_rx_record_t: what became of one frame."""
+    _fields_ = [("payload_offset", C.c_uint64), ("status", C.c_uint32), ("seq_skipped", C.c_int32), ("grid_index", C.c_uint32),
+                ("expect_index", C.c_uint32), ("eaxc", C.c_uint16), ("seq_id", C.c_uint16), ("start_prb", C.c_uint16),
+                ("nof_prbs", C.c_uint16), ("nof_prbs_written", C.c_uint16), ("port", C.c_uint16), ("sfn8", C.c_uint16),
+                ("filter_index", C.c_uint8), ("subframe", C.c_uint8), ("slot", C.c_uint8), ("symbol", C.c_uint8), ("type", C.c_uint8),
+                ("data_width", C.c_uint8), ("reserved_", C.c_uint8 * 4)]
+
+
 class OfdmConfig(C.Structure):
     _fields_ = [
         ("numerology", C.c_uint32),
@@ -752,6 +782,12 @@ def declare(lib, prefix="nrphy_"):
     sig("ofh_ul_write_grid", i32, vp, u32, P(OfhUlSection), vp, u64, vp, u32, u32, u32, vp)
     sig("ofh_ul_prach_validate", i32, u32, P(OfhUlPrachSection), u64, u64)
     sig("ofh_ul_write_prach", i32, vp, u32, P(OfhUlPrachSection), vp, u64, vp, u64, vp)
+    sig("ofh_rx_create", i32, vp, P(OfhRxCfg), P(vp))
+    sig("ofh_rx_destroy", i32, vp)
+    sig("ofh_rx_reset", i32, vp, vp)
+    sig("ofh_rx_validate", i32, P(OfhRxCfg), u32, P(OfhRxFrame), u32, P(OfhRxExpect), u64, u32, u32, u32)
+    sig("ofh_rx_run", i32, vp, u32, P(OfhRxFrame), u32, P(OfhRxExpect), vp, u64, vp, u32, u32, u32, vp, vp)
+    sig("ofh_rx_host", i32, vp, vp, u32, u32, P(OfhRxExpect), vp, u32, u32, P(OfhRxRecord))
     sig("ofh_dl_fragments", i32, P(OfhDlFlow), u32, P(OfhDlFragment), P(u32))
     sig("ofh_dl_validate", i32, u32, P(OfhDlFlow), u32, P(OfhDlSymbol), u32, u32, u32, u64, u32)
     sig("ofh_dl_write_frames", i32, vp, u32, P(OfhDlFlow), u32, P(OfhDlSymbol), vp, u32, u32, u32, vp, u64, u32, vp)
@@ -866,6 +902,7 @@ ABI_SYMBOLS = [
     "nrphy_iq_convert_ci16_host", "nrphy_ofdm_run_ci16", "nrphy_ofh_compressed_prb_bytes", "nrphy_ofh_compress",
     "nrphy_ofh_compress_host", "nrphy_ofh_decompress", "nrphy_ofh_decompress_host", "nrphy_ofh_ul_validate", "nrphy_ofh_ul_write_grid",
     "nrphy_ofh_ul_prach_validate", "nrphy_ofh_ul_write_prach",
+    "nrphy_ofh_rx_create", "nrphy_ofh_rx_destroy", "nrphy_ofh_rx_reset", "nrphy_ofh_rx_validate", "nrphy_ofh_rx_run", "nrphy_ofh_rx_host",
     "nrphy_ofh_dl_fragments", "nrphy_ofh_dl_validate", "nrphy_ofh_dl_write_frames", "nrphy_ofh_dl_frames_host",
     "nrphy_dl_slots_create", "nrphy_dl_slots_destroy", "nrphy_dl_slots_wait_free", "nrphy_dl_slot_open", "nrphy_dl_slot_close",
     "nrphy_dl_slot_pdsch", "nrphy_dl_slot_pdcch", "nrphy_dl_slot_ssb", "nrphy_dl_slot_csi_rs", "nrphy_dl_slot_put",

@@ -797,6 +797,26 @@ struct OfhUlItem {
 };
 hipError_t launch_ofh_ul_sections(const OfhUlItem* d_items, uint32_t n, uint32_t nof_chunks, const uint8_t* d_payload, void* d_dst,
                                   bool prach, hipStream_t stream);
+// ---- Open Fronthaul uplink frame receiver (ofh_rx_kernels.hip) ----------------------------------------------------------
+constexpr uint32_t OFH_RX_MAX_EAXC = 8; // distinct values of ul_eaxc and prach_eaxc together: one checker lane each
+// What the three launches of nrphy_ofh_rx_run share.  state[k]: bit 8 = initialized, bits 0..7 = the counter of eaxc[k].
+// own[((grid * ports + port) * 14 + symbol) * grid_prbs + prb]: the largest (frame index + 1) that claimed the PRB, 0 = none.
+struct OfhRxLaunch {
+  const nrphy_ofh_rx_frame_t*  frames;
+  const nrphy_ofh_rx_expect_t* expects;
+  const uint8_t*               d_frames;
+  nrphy_ofh_rx_record_t*       records;
+  uint32_t*                    grid;
+  uint32_t*                    state;
+  uint32_t*                    own;
+  uint32_t n_frames, n_expect, grid_nof_ports, grid_nof_subc, chunks_per_frame;
+  uint32_t eth_header, eth_type, ignore_size, seq_id_check, numerology, nof_symbols, ru_nof_prbs, static_compression;
+  uint32_t n_ul_eaxc, n_prach_eaxc, n_eaxc;
+  uint16_t ul_eaxc[4], prach_eaxc[4], eaxc[OFH_RX_MAX_EAXC];
+  uint8_t  mac[12];                // destination, source
+  uint8_t  type[2], data_width[2]; // static compression: [0] data route, [1] PRACH route
+};
+hipError_t launch_ofh_rx(const OfhRxLaunch& p, hipStream_t stream);
 // ---- Open Fronthaul downlink transmit (ofh_dl_kernels.hip) --------------------------------------------------------------
 constexpr uint32_t OFH_DL_MAX_HEADER = 36; // VLAN Ethernet 18 + eCPRI 8 + radio application, section and udCompHdr 10
 // One OFDM symbol of one eAxC as the kernel reads it.  Its fragments are frames of `stride` bytes apart from byte

@@ -729,6 +729,49 @@ class PuschChestPlan:
             pass
 
 
+class OfhRx:
+    """nrphy_ofh_rx: the uplink frame receiver of one stream of frames; it owns the sequence checker's state on the device."""
+
+    def __init__(self, ctx, cfg):
+        self.ctx = ctx
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_ofh_rx_create(ctx.handle, C.byref(cfg), C.byref(h)), "nrphy_ofh_rx_create")
+        self.handle = h
+
+    def run(self, frames, expects, d_frames, d_grid, nof_grids, grid_nof_ports, grid_nof_subc, d_records, frames_bytes=None, stream=None):
+        """frames: a list of abi.OfhRxFrame; expects: a list of abi.OfhRxExpect; d_frames: a uint8 tensor; d_records: device memory
+        for len(frames) abi.OfhRxRecord; returns the status (NRPHY_OK or NRPHY_ERR_ARGUMENT)."""
+        f_arr = (abi.OfhRxFrame * max(len(frames), 1))(*frames)
+        e_arr = (abi.OfhRxExpect * max(len(expects), 1))(*expects)
+        frames_bytes = d_frames.numel() * d_frames.element_size() if frames_bytes is None else frames_bytes
+        return int(self.ctx.lib.nrphy_ofh_rx_run(self.handle, len(frames), f_arr, len(expects), e_arr, _dptr(d_frames), frames_bytes,
+                                                 _dptr(d_grid), nof_grids, grid_nof_ports, grid_nof_subc, _dptr(d_records), _stream(stream)))
+
+    def host(self, frame, expects, grid):
+        """frame: uint8 array; grid: uint32 [ports][14][subc], written in place; returns (status, abi.OfhRxRecord)."""
+        frame = np.ascontiguousarray(frame, np.uint8)
+        assert grid.dtype == np.uint32 and grid.flags.c_contiguous and grid.ndim == 3 and grid.shape[1] == 14
+        e_arr = (abi.OfhRxExpect * max(len(expects), 1))(*expects)
+        rec = abi.OfhRxRecord()
+        rc = int(self.ctx.lib.nrphy_ofh_rx_host(self.handle, frame.ctypes.data, frame.size, len(expects), e_arr, grid.ctypes.data,
+                                                grid.shape[0], grid.shape[2], C.byref(rec)))
+        return rc, rec
+
+    def reset(self, stream=None):
+        _check(self.ctx.lib.nrphy_ofh_rx_reset(self.handle, _stream(stream)), "nrphy_ofh_rx_reset")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.nrphy_ofh_rx_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class PrachPlan:
     """nrphy_prach_plan: occasions of one buffer of complex64 samples; occasion i reads element sym_offsets[i] + port *
     port_stride + symbol * symbol_stride + k.  run() writes [n] abi.PrachResult, [n][64] abi.PrachPreamble and, optionally,
@@ -941,6 +984,13 @@ def ulsch_demux_sizes(cfg):
 def ofh_ul_validate(sections, payload_bytes, nof_grids, grid_nof_ports, grid_nof_subc):
     arr = (abi.OfhUlSection * max(len(sections), 1))(*sections)
     return load().nrphy_ofh_ul_validate(len(sections), arr, payload_bytes, nof_grids, grid_nof_ports, grid_nof_subc)
+
+
+def ofh_rx_validate(cfg, frames, expects, frames_bytes, nof_grids, grid_nof_ports, grid_nof_subc):
+    f_arr = (abi.OfhRxFrame * max(len(frames), 1))(*frames)
+    e_arr = (abi.OfhRxExpect * max(len(expects), 1))(*expects)
+    return int(load().nrphy_ofh_rx_validate(C.byref(cfg), len(frames), f_arr, len(expects), e_arr, frames_bytes, nof_grids, grid_nof_ports,
+                                            grid_nof_subc))
 
 
 def ofh_dl_fragments(flow):
