@@ -4,7 +4,7 @@
 # 4 +rate matching/interleaving, 0 everything; 11 everything but the data-RE stores).  STAGES="5 6 7 1" selects a subset.
 # Usage (GPU box, repository root): bash profiles/stage_pmc.sh <out_dir>
 # Needs the profiling variant of the library (the product library has no stage stops):
-#   bash profiles/make_variant.sh probes "pdsch_kernels.hip ofdm_kernels.hip nrphy_host.cpp pdsch_host.cpp pdsch_plan_build.cpp" "-DNRPHY_PROBES"
+#   bash profiles/make_variant.sh probes "pdsch_kernels.hip ofdm_kernels.hip nrphy_host.cpp ofdm_host.cpp pdsch_host.cpp pdsch_plan_build.cpp" "-DNRPHY_PROBES"
 set -u
 export NRPHY_LIB_SO=${NRPHY_LIB_SO:-$PWD/build/variants/probes.so}
 OUT=$(realpath -m "$1"); shift

@@ -6,7 +6,7 @@
 
 #include "nrphy_host_internal.h"
 
-namespace {
+#pragma GCC visibility push(hidden)
 
 constexpr float CHEST_RC_FILTER[31] = {-0.0641253f, -0.0660711f, -0.0611526f, -0.0485918f, -0.0281126f, 0.0000000f, 0.0348830f, 0.0751249f,
                                        0.1188406f,  0.1637874f,  0.2075139f,  0.2475302f,  0.2814857f,  0.3073415f, 0.3235207f, 0.3290274f,
@@ -52,4 +52,4 @@ inline void chest_symbol_epochs(uint32_t numerology, float (&epoch)[NRPHY_NSYMB]
   }
 }
 
-} // namespace
+#pragma GCC visibility pop

@@ -12,6 +12,7 @@
 // the slot's stream and returns; completion is a stream callback.  No device allocation (the control-channel writers use
 // their stand-alone forms' stream-ordered staging), no blocking copy, except where the header says "blocking".
 #include "nrphy_host_internal.h"
+#include "pdsch_staging_host.h"
 
 #include <atomic>
 #include <condition_variable>
@@ -139,12 +140,12 @@ extern "C" int nrphy_dl_slots_create(nrphy_ctx_t* ctx, const nrphy_dl_slots_cfg_
     pool->zero_copy = (uint32_t)std::atoi(e) & 3u;
   }
   // Staging: the slot's transport blocks (each call's rounded up to 256 bytes) and, behind each call's blocks, its plan
-  // tables -- a few KB for wideband PDUs, two bytes per RE for fragmented allocations (pdsch_async.cpp sizes one operation
-  // the same way); room for four calls' worth of tables, more calls share what is left.
-  const size_t table_cap = ((size_t)64 * 1024 + (size_t)NRPHY_NSYMB * pool->nof_subc * 6 + 255) & ~(size_t)255;
+  // tables -- a few KB for wideband PDUs, two bytes per RE for fragmented allocations (pdsch_staging_host.h); room for four
+  // calls' worth of tables, more calls share what is left.
+  const size_t table_cap = pdsch_staging_table_capacity(pool->nof_subc);
   pool->tb_cap           = ((size_t)cfg->max_tb_bytes + 7 + 255) & ~(size_t)255;
   pool->stage_bytes      = pool->tb_cap + 4 * table_cap + 64 * 256; // (every call's blocks and tables start on 256 bytes)
-  pool->scratch_words    = (size_t)NRPHY_NSYMB * pool->nof_subc * 2 + 16384;
+  pool->scratch_words    = pdsch_staging_scratch_words(pool->nof_subc);
   if (const char* e = std::getenv("NRPHY_DL_SLOT_STAGE_BYTES")) { // tests: a small value exercises the capacity paths
     pool->stage_bytes = ((size_t)std::max(1024, std::atoi(e)) + 255) & ~(size_t)255;
   }
@@ -321,16 +322,11 @@ extern "C" int nrphy_dl_slot_pdsch(nrphy_dl_slots_t* pool, uint32_t slot_id, uin
   if (s->state.load(std::memory_order_acquire) != SLOT_OPEN) {
     return NRPHY_ERR_ARGUMENT; // the grid has been handed over
   }
-  std::vector<uint64_t> tb_off(n_pdu);
-  size_t                tb_total = 0;
-  for (uint32_t i = 0; i != n_pdu; ++i) {
-    if (tbs[i] == nullptr || pdus[i].tb_size_bytes == 0) {
-      return NRPHY_ERR_ARGUMENT;
-    }
-    tb_off[i] = tb_total;
-    tb_total += ((size_t)pdus[i].tb_size_bytes + 7) & ~(size_t)3; // readable to the next multiple of 4
+  PdschStagingLayout layout;
+  if (pdsch_staging_layout(n_pdu, pdus, tbs, layout) != NRPHY_OK) {
+    return NRPHY_ERR_ARGUMENT;
   }
-  const size_t tables_at = (tb_total + 255) & ~(size_t)255; // relative to this call's region of the staging
+  const size_t tables_at = layout.tables_at; // relative to this call's region of the staging
   size_t       tb_bytes  = 0;
   for (uint32_t i = 0; i != n_pdu; ++i) {
     tb_bytes += pdus[i].tb_size_bytes;
@@ -343,34 +339,15 @@ extern "C" int nrphy_dl_slot_pdsch(nrphy_dl_slots_t* pool, uint32_t slot_id, uin
   }
   uint8_t* const        h_base = s->h_stage + s->stage_used;
   uint8_t* const        d_base = s->d_stage + s->stage_used;
-  std::vector<uint32_t> grid_of(n_pdu, 0);
-  PlanPlacement         place;
-  place.h_tables               = h_base + tables_at;
-  place.d_tables               = d_base + tables_at;
-  place.table_capacity         = (pool->stage_bytes - s->stage_used - tables_at) & ~(size_t)255;
-  place.d_scratch              = s->d_scratch;
-  place.scratch_capacity_words = pool->scratch_words;
-  place.cache                  = s->shapes;
-  nrphy_pdsch_plan_t* plan     = nullptr;
-  int rc = nrphy_pdsch_plan_create_placed(pool->ctx, n_pdu, pdus, tb_off.data(), grid_of.data(), 1, pool->cfg.nof_ports, pool->nof_subc,
-                                          &place, &plan);
-  bool own_memory = false;
-  if (rc == NRPHY_ERR_CAPACITY) {
-    // Tables too big for what is left of the staging: a plan with device memory of its own (an allocation and a blocking
-    // copy -- rare: hundreds of PDUs, or RE tables for most of a fragmented grid, in one slot).
-    rc         = nrphy_pdsch_plan_create(pool->ctx, n_pdu, pdus, tb_off.data(), grid_of.data(), 1, pool->cfg.nof_ports, pool->nof_subc, &plan);
-    own_memory = true;
-  }
+  PdschStagedPlan       staged;
+  int rc = pdsch_staging_create_plan(pool->ctx, n_pdu, pdus, tbs, pool->cfg.nof_ports, pool->nof_subc, layout, h_base, d_base,
+                                     pool->stage_bytes - s->stage_used, s->d_scratch, pool->scratch_words, s->shapes, staged);
   if (rc != NRPHY_OK) {
     return rc;
   }
+  nrphy_pdsch_plan_t* const plan = staged.plan;
   s->plans.push_back(plan);
-  for (uint32_t i = 0; i != n_pdu; ++i) {
-    const size_t span = (i + 1 != n_pdu ? tb_off[i + 1] : tb_total) - tb_off[i];
-    std::memcpy(h_base + tb_off[i], tbs[i], pdus[i].tb_size_bytes);
-    std::memset(h_base + tb_off[i] + pdus[i].tb_size_bytes, 0, span - pdus[i].tb_size_bytes);
-  }
-  const size_t copy_bytes = own_memory ? tb_total : tables_at + place.table_bytes;
+  const size_t copy_bytes = staged.copy_bytes(layout);
   if ((pool->zero_copy & 1u) == 0) {
     HIP_TRY(hipMemcpyAsync(d_base, h_base, copy_bytes, hipMemcpyHostToDevice, s->stream));
   }

@@ -7,7 +7,7 @@
 //
 // The reference walks the buffer sequentially; which stretches it clears, fills, copies into, adds to or leaves alone
 // depends only on the configuration, not on the data.  The host runs the same walk once per call and hands the kernel
-// the resulting list of range operations (DematchOp, nrphy_host.cpp: build_dematch_ops); the kernel is a gather: one
+// the resulting list of range operations (DematchOp, ldpc_dematcher_host.cpp: build_dematch_ops); the kernel is a gather: one
 // thread owns four consecutive soft bits of one codeblock, applies to them, in order, every operation that covers them
 // and writes them back once.  Positions nothing covers keep their content, as in the reference.
 #include "bits_device.h"

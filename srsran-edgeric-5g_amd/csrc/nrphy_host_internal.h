@@ -1,6 +1,5 @@
-// Host-side internals shared by the translation units behind the C ABI (nrphy_host.cpp, pdsch_plan_build.cpp, pdsch_host.cpp,
-// dl_control_host.cpp, pdsch_async.cpp, dl_slot_async.cpp, pusch_demod_host.cpp, pusch_chest_host.cpp, prach_host.cpp, prach_demod_host.cpp, pucch_host.cpp, pucch2_host.cpp, srs_host.cpp, uci_host.cpp): the context, its staging buffers, small helpers.  Not part
-// of the ABI.
+// Host-side internals shared by the translation units behind the C ABI (nrphy_host.cpp, every *_host.cpp, pdsch_plan_build.cpp,
+// pdsch_async.cpp, dl_slot_async.cpp): the context, its staging buffers, small helpers.  Not part of the ABI.
 #pragma once
 
 #include "nrphy_internal.h"
@@ -20,7 +19,8 @@ using namespace nrphy;
     }                                                                                                                  \
   } while (0)
 
-namespace {
+// The helpers below are inline in every translation unit that uses them; hidden, so that none becomes a symbol of the library.
+#pragma GCC visibility push(hidden)
 
 // Remainder arithmetic in GF(2)[x] / poly on the host (plan-time constants of the CRC kernels).
 struct CrcField {
@@ -55,15 +55,15 @@ struct CrcField {
     return r;
   }
 };
-const CrcField CRC24A_FIELD = {0x1864CFBU, 24};
-const CrcField CRC16_FIELD  = {0x11021U, 16};
+inline const CrcField CRC24A_FIELD = {0x1864CFBU, 24};
+inline const CrcField CRC16_FIELD  = {0x11021U, 16};
 
 // The LDPC lifting sizes in ascending order (TS 38.212 Table 5.3.2-1) and the place of one among them (-1: not a lifting size).
-const uint16_t LIFTING_SIZES[NOF_LIFTING_SIZES] = {
+inline constexpr uint16_t LIFTING_SIZES[NOF_LIFTING_SIZES] = {
     2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13,  14,  15,  16,  18,  20,  22,  24,  26,  28,  30,  32,  36,  40, 44,
     48, 52, 56, 60, 64, 72, 80, 88, 96, 104, 112, 120, 128, 144, 160, 176, 192, 208, 224, 240, 256, 288, 320, 352, 384};
 
-int lifting_position(unsigned zc)
+inline int lifting_position(unsigned zc)
 {
   for (int i = 0; i != NOF_LIFTING_SIZES; ++i) {
     if (LIFTING_SIZES[i] == zc) {
@@ -73,17 +73,17 @@ int lifting_position(unsigned zc)
   return -1;
 }
 
-unsigned divide_ceil(unsigned a, unsigned b)
+inline unsigned divide_ceil(unsigned a, unsigned b)
 {
   return (a + b - 1) / b;
 }
 
-bool mask_test(const uint64_t* w, unsigned i)
+inline bool mask_test(const uint64_t* w, unsigned i)
 {
   return (w[i >> 6] >> (i & 63)) & 1U;
 }
 
-int mask_lowest(const uint64_t* w)
+inline int mask_lowest(const uint64_t* w)
 {
   for (unsigned i = 0; i != 64 * NRPHY_PRB_WORDS; ++i) {
     if (mask_test(w, i)) {
@@ -93,7 +93,7 @@ int mask_lowest(const uint64_t* w)
   return -1;
 }
 
-int mask_highest(const uint64_t* w)
+inline int mask_highest(const uint64_t* w)
 {
   int hi = -1;
   for (unsigned i = 0; i != 64 * NRPHY_PRB_WORDS; ++i) {
@@ -105,7 +105,7 @@ int mask_highest(const uint64_t* w)
 }
 
 template <typename T>
-hipError_t upload(T** dptr, const void* src, size_t bytes)
+inline hipError_t upload(T** dptr, const void* src, size_t bytes)
 {
   *dptr = nullptr;
   if (bytes == 0) {
@@ -173,7 +173,7 @@ private:
   size_t            total = 0;
 };
 
-} // namespace
+#pragma GCC visibility pop
 
 // Environment knobs (INTEGRATION.md section 5 lists them): A/B and test aids, none changes a result.  Read ONCE, when the
 // context is created -- never on a submit path, where several threads of the host may be running -- so a process that wants
@@ -188,11 +188,10 @@ struct Tunables {
   int      decoder_pairs   = -1; // NRPHY_DECODER_PAIRS=0: one check per lane whatever the lifting size
   int      decoder_ldsmsg  = -1; // NRPHY_DECODER_LDSMSG: 0 = messages never in LDS, 2 = wherever a workgroup's LDS can hold them
   bool     decoder_slots_all = false; // NRPHY_DECODER_SLOTS_ALL=1: a scratch slot per codeblock (no pooling)
-#ifdef NRPHY_PROBES
-  // Profiling variants only (profiles/make_variant.sh ... -DNRPHY_PROBES): with these set the outputs are INCOMPLETE.
+  // Profiling variants only (profiles/make_variant.sh ... -DNRPHY_PROBES): read and consulted under that flag alone, 0 without
+  // it (the members are always there, so that the context has one layout in both builds); set, the outputs are INCOMPLETE.
   uint32_t profile_stage   = 0;  // NRPHY_PROFILE_STAGE: the codeblock waves stop after a stage
   uint32_t ofdm_probe      = 0;  // NRPHY_OFDM_PROBE: bit 0 drops the IQ stores, bit 1 the grid loads, bit 2 takes the grids first to last
-#endif
 };
 Tunables read_tunables();
 
@@ -219,9 +218,10 @@ struct nrphy_ctx {
   std::map<uint32_t, uint32_t*> d_tb_crc_w;    // transport-block CRC weights of the PUSCH assembly kernel per block size
   std::vector<LiftedGraph> graphs; // host copy (plan creation sizes the LDS staging of graph rows from it)
   // Device staging of the host-span entry points (*_host): grow-only buffers, one call at a time per context.
-  // One lock for everything context-owned and shared: the staging buffers below and the lazily built tables.  The
-  // host-span entry points (*_host) hold it for the whole call (HostCall below), so two of them never interleave on a
-  // buffer; it is recursive because they are built from device-pointer calls that take it briefly.
+  // One lock for everything context-owned and shared: the staging buffers below and the lazily built tables.  Every getter
+  // of such a table (get_twiddle, the decoder's graphs and CRC weights, the PUSCH TB-CRC weights, the PRACH tables) takes it
+  // itself, no caller has to.  The host-span entry points (*_host) hold it for the whole call (HostCall below), so two of
+  // them never interleave on a buffer; it is recursive because they are built from device-pointer calls that take it briefly.
   std::recursive_mutex host_mutex;
   void*      scratch[SCRATCH_COUNT]       = {};
   size_t     scratch_bytes[SCRATCH_COUNT] = {};
@@ -231,32 +231,19 @@ struct nrphy_ctx {
 // current; null for another size or when the upload fails.  It lives as long as the context.
 const float2* get_twiddle(nrphy_ctx* ctx, uint32_t size);
 
-// ---- PDSCH plans in caller-owned memory (the asynchronous queue) ----------------------------------------------------------
-// nrphy_pdsch_plan_create allocates device memory and copies the plan's tables there with a blocking copy: right for a
-// plan that is built once and run many times, wrong on a path that sees a new PDU per call.  The placed form writes the
-// tables into host memory of the caller (pinned staging it copies in stream order, together with the transport block)
-// and points the plan at the device addresses they will have; it makes no HIP call.  NRPHY_ERR_CAPACITY when the plan
-// does not fit.  The plan must be destroyed before the memory is reused.
-struct PlanShapeCache;
-PlanShapeCache* plan_shape_cache_create();
-void            plan_shape_cache_destroy(PlanShapeCache* cache);
-struct PlanPlacement {
-  uint8_t*        h_tables = nullptr; // host memory the tables are written to
-  uint8_t*        d_tables = nullptr; // device address they will be copied to (256-byte aligned)
-  size_t          table_capacity = 0;
-  size_t          table_bytes    = 0; // out: bytes to copy
-  uint32_t*       d_scratch = nullptr; // device memory for what every run rewrites (sequences, TB-CRC shares)
-  size_t          scratch_capacity_words = 0;
-  PlanShapeCache* cache = nullptr;    // may be null; one cache per thread of use
-};
-int nrphy_pdsch_plan_create_placed(nrphy_ctx_t* ctx, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus, const uint64_t* tb_offset,
-                                   const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports,
-                                   uint32_t grid_nof_subc, PlanPlacement* place, nrphy_pdsch_plan_t** out);
+#pragma GCC visibility push(hidden)
 
-namespace {
+// Amplitude controller parameters as the reference's constructors derive them
+// (amplitude_controller_clipping_impl.h:52-62, amplitude_controller_scaling_impl.h); false for a configuration to refuse.
+// Defined in ofdm_host.cpp (the wire-format modulator), used by lower_phy_host.cpp too.
+struct AmplitudeParams {
+  float gain, ceiling;
+  bool  measure, clip;
+};
+bool amplitude_params(const nrphy_amplitude_cfg_t& c, AmplitudeParams& a);
 
 // Staging buffer `slot` of the context with room for `bytes` (reallocated only when it has to grow).
-void* ctx_scratch(nrphy_ctx* ctx, ScratchSlot slot, size_t bytes)
+inline void* ctx_scratch(nrphy_ctx* ctx, ScratchSlot slot, size_t bytes)
 {
   if (bytes > ctx->scratch_bytes[slot]) {
     (void)hipFree(ctx->scratch[slot]);
@@ -352,4 +339,4 @@ private:
   void*       ptr = nullptr;
 };
 
-} // namespace
+#pragma GCC visibility pop

@@ -1,4 +1,4 @@
-// Internal declarations shared by the host side (nrphy_host.cpp, pdsch_plan_build.cpp, pdsch_host.cpp and the other *_host.cpp) and the HIP kernels of libmi355nrphy.so.
+// Internal declarations shared by the host side (nrphy_host.cpp, pdsch_plan_build.cpp and every *_host.cpp) and the HIP kernels of libmi355nrphy.so.
 // Not part of the ABI (that is include/mi355_nrphy.h).
 #pragma once
 

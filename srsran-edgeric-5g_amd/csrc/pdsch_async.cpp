@@ -10,6 +10,7 @@
 // callback on the slot's stream and returns; the callback hands the grid to the caller's handler on a runtime thread.
 // What depends only on the SHAPE of the PDUs (RE mapping tables, zero-fill run lists) is kept per slot across submits.
 #include "nrphy_host_internal.h"
+#include "pdsch_staging_host.h"
 
 #include <atomic>
 #include <cstdlib>
@@ -94,12 +95,10 @@ extern "C" int nrphy_pdsch_async_create(nrphy_ctx_t* ctx, uint32_t depth, uint32
     q->zero_copy = (uint32_t)std::atoi(e);
   }
   q->slots.resize(depth);
-  // Room for the tables of one operation (PDU descriptors, work lists, weights, RE tables, zero-fill lists: a few KB for a
-  // wideband PDU; non-contiguous allocations add two bytes per RE) and for what its run rewrites (one sequence word per
-  // 32 codeword bits -- at most 32 bits per RE -- plus DM-RS sequences).  An operation that needs more gets a plan with
-  // memory of its own (the slow path).
-  q->table_cap     = ((size_t)64 * 1024 + (size_t)NRPHY_NSYMB * grid_nof_subc * 6 + 255) & ~(size_t)255;
-  q->scratch_words = (size_t)NRPHY_NSYMB * grid_nof_subc * 2 + 16384;
+  // Room for the tables of one operation and for what its run rewrites (pdsch_staging_host.h).  An operation that needs more
+  // gets a plan with memory of its own (the slow path).
+  q->table_cap     = pdsch_staging_table_capacity(grid_nof_subc);
+  q->scratch_words = pdsch_staging_scratch_words(grid_nof_subc);
   if (const char* e = std::getenv("NRPHY_ASYNC_TABLE_CAP")) { // tests: a small value sends every operation down the slow path
     q->table_cap = ((size_t)std::max(256, std::atoi(e)) + 255) & ~(size_t)255;
   }
@@ -178,15 +177,11 @@ static int submit_pdus(nrphy_pdsch_async_t* q, uint32_t n_pdu, const nrphy_pdsch
     return NRPHY_ERR_ARGUMENT;
   }
   // The transport blocks, back to back (each readable to the next multiple of 4); the plan's tables follow them.
-  std::vector<uint64_t> tb_off(n_pdu);
-  size_t                tb_total = 0;
-  for (uint32_t i = 0; i != n_pdu; ++i) {
-    if (tbs[i] == nullptr || pdus[i].tb_size_bytes == 0) {
-      return NRPHY_ERR_ARGUMENT;
-    }
-    tb_off[i] = tb_total;
-    tb_total += ((size_t)pdus[i].tb_size_bytes + 7) & ~(size_t)3;
+  PdschStagingLayout layout;
+  if (pdsch_staging_layout(n_pdu, pdus, tbs, layout) != NRPHY_OK) {
+    return NRPHY_ERR_ARGUMENT;
   }
+  const size_t tb_total = layout.tb_total, tables_at = layout.tables_at;
   if (tb_total > (((size_t)q->max_tb_bytes + 7) & ~(size_t)3)) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -222,32 +217,12 @@ static int submit_pdus(nrphy_pdsch_async_t* q, uint32_t n_pdu, const nrphy_pdsch
   // tables into the pinned staging, device pointers into the slot's device buffer, nothing allocated or copied here.
   nrphy_pdsch_plan_destroy(slot->plan);
   slot->plan = nullptr;
-  std::vector<uint32_t> grid_of(n_pdu, 0);
-  PlanPlacement         place;
-  const size_t tables_at       = (tb_total + 255) & ~(size_t)255;
-  place.h_tables               = slot->h_tb + tables_at;
-  place.d_tables               = slot->d_tb + tables_at;
-  place.table_capacity         = q->table_cap;
-  place.d_scratch              = slot->d_scratch;
-  place.scratch_capacity_words = q->scratch_words;
-  place.cache                  = slot->shapes;
-  // (the transport-block offsets the plan records are relative to the pointer nrphy_pdsch_run gets: the staging's start)
-  int rc = nrphy_pdsch_plan_create_placed(q->ctx, n_pdu, pdus, tb_off.data(), grid_of.data(), 1, q->nof_ports, q->nof_subc, &place,
-                                          &slot->plan);
-  bool own_memory = false;
-  if (rc == NRPHY_ERR_CAPACITY) {
-    // Too big for the slot's table space: a plan with device memory of its own (allocation + blocking copy; freed when the
-    // slot is used again).  Rare: hundreds of PDUs or RE tables for most of a fragmented grid.
-    rc        = nrphy_pdsch_plan_create(q->ctx, n_pdu, pdus, tb_off.data(), grid_of.data(), 1, q->nof_ports, q->nof_subc, &slot->plan);
-    own_memory = true;
-  }
+  PdschStagedPlan staged;
+  int rc     = pdsch_staging_create_plan(q->ctx, n_pdu, pdus, tbs, q->nof_ports, q->nof_subc, layout, slot->h_tb, slot->d_tb,
+                                         tables_at + q->table_cap, slot->d_scratch, q->scratch_words, slot->shapes, staged);
+  slot->plan = staged.plan; // (freed when the slot is used again, its own device memory too)
   if (rc != NRPHY_OK) {
     return give_back(rc);
-  }
-  for (uint32_t i = 0; i != n_pdu; ++i) {
-    const size_t span = (i + 1 != n_pdu ? tb_off[i + 1] : tb_total) - tb_off[i];
-    std::memcpy(slot->h_tb + tb_off[i], tbs[i], pdus[i].tb_size_bytes);
-    std::memset(slot->h_tb + tb_off[i] + pdus[i].tb_size_bytes, 0, span - pdus[i].tb_size_bytes); // readable to the next multiple of 4
   }
   slot->done   = done;
   slot->user   = user;
@@ -255,7 +230,7 @@ static int submit_pdus(nrphy_pdsch_async_t* q, uint32_t n_pdu, const nrphy_pdsch
   // ONE copy carries the tables and the transport blocks (zero-copy transport blocks: the tables alone -- every wave reads
   // them, they belong in device memory).
   const size_t copy_from = tb_direct ? tables_at : 0;
-  const size_t copy_to   = own_memory ? tb_total : tables_at + place.table_bytes;
+  const size_t copy_to   = staged.copy_bytes(layout);
   if (copy_to > copy_from &&
       hipMemcpyAsync(slot->d_tb + copy_from, slot->h_tb + copy_from, copy_to - copy_from, hipMemcpyHostToDevice, slot->stream) !=
           hipSuccess) {

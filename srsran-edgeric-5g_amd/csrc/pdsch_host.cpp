@@ -520,3 +520,21 @@ extern "C" int nrphy_pdsch_encode_host(nrphy_ctx_t* ctx, const nrphy_pdsch_encod
   return NRPHY_OK;
 }
 
+extern "C" int nrphy_ldpc_encode(nrphy_ctx_t* ctx, uint32_t base_graph, uint32_t lifting_size, uint32_t n_cb,
+                                 const uint8_t* d_msg, uint32_t msg_stride_bytes, uint32_t out_bits, uint8_t* d_out,
+                                 uint32_t out_stride_bytes, void* stream)
+{
+  if (ctx == nullptr || (base_graph != 1 && base_graph != 2) || d_msg == nullptr || d_out == nullptr) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  const int pos = lifting_position(lifting_size);
+  const unsigned kb = (base_graph == 1) ? 22 : 10, nfull = (base_graph == 1) ? 68 : 52;
+  if (pos < 0 || out_bits == 0 || out_bits > (nfull - 2) * lifting_size ||
+      msg_stride_bytes < (kb * lifting_size + 7) / 8 || out_stride_bytes < (out_bits + 7) / 8) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  HIP_TRY(launch_ldpc_encode(ctx->d_graphs, (base_graph - 1) * NOF_LIFTING_SIZES + (uint32_t)pos, kb, lifting_size,
+                             n_cb, d_msg, msg_stride_bytes, out_bits, d_out, out_stride_bytes,
+                             stream ? (hipStream_t)stream : ctx->stream));
+  return NRPHY_OK;
+}

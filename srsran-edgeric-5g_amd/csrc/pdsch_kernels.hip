@@ -19,7 +19,7 @@
 #define NRPHY_PHASE_A_STAGED 1
 #endif
 
-// Stage stops of the profiling variants (profiles/make_variant.sh NAME "pdsch_kernels.hip ofdm_kernels.hip nrphy_host.cpp pdsch_host.cpp pdsch_plan_build.cpp"
+// Stage stops of the profiling variants (profiles/make_variant.sh NAME "pdsch_kernels.hip ofdm_kernels.hip nrphy_host.cpp ofdm_host.cpp pdsch_host.cpp pdsch_plan_build.cpp"
 // "-DNRPHY_PROBES"; profiles/stage_pmc.sh, stage_times.sh): the codeblock waves return after stage n, the outputs are then
 // incomplete.  The product library is built without them -- the tests compile to nothing.
 #ifdef NRPHY_PROBES

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "nrphy_host_internal.h"
+#include "pdsch_staging_host.h"
 
 #include <map>
 #include <vector>

@@ -5,7 +5,7 @@
 
 #include "nrphy_host_internal.h"
 
-namespace {
+#pragma GCC visibility push(hidden)
 
 constexpr uint32_t MAX_PRB_BITS = NRPHY_PRB_WORDS * 64;
 
@@ -16,12 +16,12 @@ struct PuschAllocation {
   const uint32_t* rx_ports; // [NRPHY_MAX_PORTS]
 };
 template <class Cfg>
-PuschAllocation pusch_allocation(const Cfg& c)
+inline PuschAllocation pusch_allocation(const Cfg& c)
 {
   return {c.prb_mask, c.start_symbol_index, c.nof_symbols, c.dmrs_symbol_mask, c.nof_rx_ports, c.rx_ports};
 }
 
-uint32_t nof_prb(const PuschAllocation& a)
+inline uint32_t nof_prb(const PuschAllocation& a)
 {
   uint32_t n = 0;
   for (uint32_t w = 0; w != NRPHY_PRB_WORDS; ++w) {
@@ -32,7 +32,7 @@ uint32_t nof_prb(const PuschAllocation& a)
 
 // The grid's dimensions; 1 to NRPHY_MAX_PORTS distinct receive ports, each a port of the grid; no PRB beyond the grid; the
 // symbols inside the slot.
-bool allocation_fits_grid(const PuschAllocation& a, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
+inline bool allocation_fits_grid(const PuschAllocation& a, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
 {
   if (grid_nof_subc == 0 || grid_nof_subc % NRPHY_NRE != 0 || grid_nof_subc > NRPHY_MAX_RB * NRPHY_NRE || grid_nof_ports == 0 ||
       grid_nof_ports > NRPHY_MAX_PORTS || a.nof_rx_ports < 1 || a.nof_rx_ports > NRPHY_MAX_PORTS) {
@@ -57,7 +57,7 @@ bool allocation_fits_grid(const PuschAllocation& a, uint32_t grid_nof_ports, uin
 }
 
 // Appends the allocated PRBs (grid-indexed, ascending) to a plan's list; returns how many.
-uint32_t append_prbs(const PuschAllocation& a, uint32_t grid_nof_subc, std::vector<uint16_t>& prbs)
+inline uint32_t append_prbs(const PuschAllocation& a, uint32_t grid_nof_subc, std::vector<uint16_t>& prbs)
 {
   const size_t first = prbs.size();
   for (uint32_t b = 0; b != grid_nof_subc / NRPHY_NRE; ++b) {
@@ -68,4 +68,4 @@ uint32_t append_prbs(const PuschAllocation& a, uint32_t grid_nof_subc, std::vect
   return (uint32_t)(prbs.size() - first);
 }
 
-} // namespace
+#pragma GCC visibility pop

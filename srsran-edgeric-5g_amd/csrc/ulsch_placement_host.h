@@ -9,7 +9,7 @@
 
 #include <vector>
 
-namespace {
+#pragma GCC visibility push(hidden)
 
 enum UlschStream : uint32_t { ULSCH_SCH = 0, ULSCH_HARQ = 1, ULSCH_CSI1 = 2, ULSCH_CSI2 = 3 };
 enum UlschFix : uint32_t { ULSCH_FIX_NONE = 0, ULSCH_FIX_1BIT = 1, ULSCH_FIX_2BIT = 2 };
@@ -27,7 +27,7 @@ struct UlschPlacement {
   std::vector<UlschSpecial> special;
 };
 
-bool ulsch_bits_per_symbol(uint32_t modulation, uint32_t* bps)
+inline bool ulsch_bits_per_symbol(uint32_t modulation, uint32_t* bps)
 {
   switch (modulation) {
     case NRPHY_MOD_PI2_BPSK:
@@ -46,7 +46,7 @@ bool ulsch_bits_per_symbol(uint32_t modulation, uint32_t* bps)
 }
 
 // re_set_select: of the candidates (ascending) every d-th, `count` of them.
-void ulsch_select(const std::vector<uint32_t>& candidates, uint32_t d, uint32_t count, std::vector<uint32_t>& out)
+inline void ulsch_select(const std::vector<uint32_t>& candidates, uint32_t d, uint32_t count, std::vector<uint32_t>& out)
 {
   out.clear();
   for (uint32_t i = 0; i != count; ++i) {
@@ -55,7 +55,7 @@ void ulsch_select(const std::vector<uint32_t>& candidates, uint32_t d, uint32_t 
 }
 
 // false for what the reference asserts on, see nrphy_ulsch_demux_validate.
-bool ulsch_placement(const nrphy_ulsch_demux_cfg_t& c, UlschPlacement& p)
+inline bool ulsch_placement(const nrphy_ulsch_demux_cfg_t& c, UlschPlacement& p)
 {
   uint32_t qm = 0;
   if (!ulsch_bits_per_symbol(c.modulation, &qm) || c.nof_layers < 1 || c.nof_layers > NRPHY_MAX_PORTS || c.nof_prb < 1 ||
@@ -195,4 +195,4 @@ bool ulsch_placement(const nrphy_ulsch_demux_cfg_t& c, UlschPlacement& p)
          p.map.size() <= ULSCH_MAP_INDEX;
 }
 
-} // namespace
+#pragma GCC visibility pop
