@@ -703,10 +703,12 @@ int nrphy_prach_demodulate_host(nrphy_ctx_t* ctx, const nrphy_prach_demod_cfg_t*
  * Time alignment: the reference runs time_alignment_estimator_dft_impl on the smoothed pilots, which under the `mean` strategy
  * are 12 equal values c on consecutive subcarriers.  Their 4096-point inverse DFT has magnitude |c| |sin(12 pi n / 4096) /
  * sin(pi n / 4096)|, whose maximum over the searched bins [0, 144) and [3952, 4096) is at n = 0, 2.8e-5 (relative, in power)
- * above bins 1 and 4095 -- some hundreds of float32 ulps (6e-8), where a transform of 12 log2 4096 stages is expected, not measured, to
- * err by a few tens --, ties go to the delay side and an
- * all-zero input returns index 0.  The peak is bin 0 whatever the grid holds, so the time alignment is 0 and no transform is
- * computed.
+ * above bins 1 and 4095 -- some hundreds of float32 ulps (6e-8) --, ties go to the delay side and an all-zero input returns
+ * index 0.  Measured, not only argued: in the recording of the reference (tests/golden/record_pucch_reference.cpp: 146 format 1
+ * cases of 4 to 14 symbols, 1 to 4 ports, PRBs 1 to 51, with and without hopping, on noisy two-tap channels, noise alone and a
+ * zero grid) the reference's float32 transform put the peak in bin 0 in every one of the 1,240 per-port, per-hop calls and
+ * per-port results, through the real path: the format 1 estimator, both hops and their halved sum.  So the time alignment is 0
+ * whatever the grid holds, and no transform is computed.
  *
  * Group and sequence: u = n_id % 30, v = 0 (group hopping `neither`, as both reference detectors assert).  Cyclic shift
  * alpha_idx = (initial_cyclic_shift + m_cs + n_cs) % 12, n_cs from the Gold sequence with c_init = n_id

@@ -3,17 +3,21 @@
 CPU: the POD mirrors, the validator over each refused case and over the reference unit tests' 186 configurations
 (tests/golden/pucch_configs.json), the extractor that wrote the fixtures and the generator of csrc/pucch_tables.inc, the
 restatement's sequences (tests/pucch_model.py) against their definitions, and a noiseless loop-back of the restatement over every
-fixture configuration.
-GPU: the fixture configurations on grids built here; parity with the restatement on seeded multipath + CFO + AWGN grids;
-physics (zero grid, noise only, CFO and gain measured back, wrong cyclic shift and OCC); batches against per-PUCCH host calls,
-graph replay, sentinels, and a slot with PUSCH and PUCCH on one grid buffer.
+fixture configuration; the restatement in float32 and float64 against a recording of the reference's own answers
+(tests/golden/record_pucch_reference.cpp and pucch_reference_*.npy: 271 cases on noisy two-tap channels), and that recording's
+own consistency.
+GPU: the fixture configurations on grids built here; the recording through one plan and through host calls; parity with the
+restatement on seeded multipath + CFO + AWGN grids; physics (zero grid, noise only, CFO and gain measured back, wrong cyclic
+shift and OCC); batches against per-PUCCH host calls, graph replay, sentinels, and a slot with PUSCH and PUCCH on one grid buffer.
 
 The grids of the known-answer and loop-back tests come from the restatement's own transmitter, not from the reference's test
 vectors (which are not available): they show that transmitter and receivers agree with each other.  What is independent of the
-restatement's author is the low-PAPR and cover-code definitions check, the cyclic shift index against the C oracle's Gold generator,
-and the phi tables, which are extracted from the reference.
+restatement's author is the recording -- the reference's detectors, estimator and equaliser, compiled and run on grids from the
+recorder's transmitter, which takes its sequences from the reference --, the low-PAPR and cover-code definitions check, the
+cyclic shift index against the C oracle's Gold generator, and the phi tables, which are extracted from the reference.
 """
 import ctypes as C
+import functools
 import json
 import os
 import subprocess
@@ -42,13 +46,27 @@ NOF_SUBC = 12 * NOF_PRB
 # Largest |float32 restatement - float64 restatement| over the cases of test_parity_with_the_restatement (the test prints both
 # again on every run), of the detection metric, the three dB values and the per-port measurements relative to max(|value|,
 # FLOOR), and of the CFO in Hz relative to max(|cfo|, CFO_FLOOR_HZ).  The device may differ from the float64 restatement by 8 x
-# that: it folds its double partial sums in another order than the restatement's pairwise sums, and its libm is not NumPy's.  (The
-# reference binary cannot be built for this block, so the float32 restatement stands in for the reference's own error.)
+# that: it folds its double partial sums in another order than the restatement's pairwise sums, and its libm is not NumPy's.
+# This is the float32-to-float64 spread of the parity cases and nothing more; the reference's own error is REF_SPREAD below.
 MODEL_SPREAD = 2.85e-5  # measured 2.843e-05: format 0's metric, whose avg_pwr - corr cancels at the higher SNRs
 CFO_SPREAD = 5.52e-5    # measured 5.517e-05
 FLOOR = 1e-3        # metrics and linear powers
 DB_FLOOR = 1.0      # dB values
 CFO_FLOOR_HZ = 1.0
+
+# The recording (tests/golden/record_pucch_reference.cpp).  Largest distance, in the terms of distance() below, between what the
+# reference answered and the float64 restatement, over every recorded case that is not flagged; test_restatement_equals_the_recording
+# measures and prints them again on every run.  The largest metric distance belongs to cases in which nothing was sent for the
+# configuration (noise only, another cyclic shift or cover code): there the detected symbol is what is left of a sum that
+# cancels, and the reference's float32 sums lose what cancelled.  REF_SIGNAL_SPREAD is the same over the cases whose UE was sent.
+REF_SPREAD = 1.53e-3         # measured 1.521e-03: case 267, read with another cover code, detection_metric 0.0037
+REF_SIGNAL_SPREAD = 9.3e-5   # measured 9.264e-05: case 208, format 1 on 14 symbols
+REF_CFO_SPREAD = 4.37e-4     # measured 4.367e-04: case 96, two UEs on one PRB, Hz relative to max(|CFO|, 1 Hz)
+REF_ESTIMATE_ULPS = 0        # float32 restatement's estimate against the recorded one, in bf16 steps: every word equal
+# The recording admits no case whose decided metric lies in [T / 2, 2 T] and, where a UE was sent, none whose two best format 0
+# candidates, two format 1 statistics or two best per-port SNRs are within this of the larger.
+RECORDING_MARGIN = 0.02
+NOF_RECORDED, NOF_FLAGGED = 271, 2
 
 
 def make_cfg(*args, **kw):
@@ -697,3 +715,294 @@ def test_pusch_and_pucch_share_one_grid_buffer_and_stream(gpu_ctx):
     assert got[1]["sr"] == 1
     chest.close()
     pucch.close()
+
+
+# =======================================================================================================================
+# The recording of the reference (tests/golden/record_pucch_reference.cpp states every layout)
+# =======================================================================================================================
+def recorded_prb(cfg, off):
+    """The grid PRB of the symbol at offset `off` of the allocation, as the recorder's header states the layout (not through the
+    restatement, which is under test here)."""
+    hop = cfg["second_hop_prb"] is not None and (off != 0 if cfg["format"] == 0 else off >= cfg["nof_symbols"] // 2)
+    return cfg["bwp_start_rb"] + (cfg["second_hop_prb"] if hop else cfg["starting_prb"])
+
+
+@functools.lru_cache(maxsize=None)
+def recording():
+    """The recorded cases: dicts of cfg, row (the case table's), grid (index into the second value), want (the reference's answer in
+    the form distance() reads, with status, harq_ack, sr, time_alignment_s, ta [ports][3], estimate [ports][symbols] and top, the
+    recorder's two margin numbers), flagged,
+    sent; and the distinct grids [n_grids][4][14][624] rebuilt from the stored elements."""
+    load = lambda name: np.load(os.path.join(GOLDEN, "pucch_reference_%s.npy" % name))
+    rows, words, results, estimates = load("cases"), load("grids"), load("results"), load("estimates")
+    cases, grids, grid_of = [], [], {}
+    for row, r in zip(rows, results):
+        row = [int(v) for v in row]
+        P = row[14]
+        cfg = model.make_cfg(format=row[0], numerology=row[1], slot_index=row[2], bwp_start_rb=row[3], bwp_size_rb=row[4], starting_prb=row[5],
+                             second_hop_prb=None if row[6] < 0 else row[6], start_symbol_index=row[7], nof_symbols=row[8],
+                             initial_cyclic_shift=row[9], time_domain_occ=row[10], n_id=row[11], nof_harq_ack=row[12],
+                             sr_opportunity=row[13], ports=row[15:15 + P])
+        ns, s0 = cfg["nof_symbols"], cfg["start_symbol_index"]
+        if row[19] not in grid_of:
+            stored = words[row[19]:row[19] + P * ns * 12].reshape(P, ns, 12)
+            grid = np.zeros((NOF_PORTS, 14, NOF_SUBC), np.uint32)
+            for off in range(ns):
+                k = 12 * recorded_prb(cfg, off)
+                grid[cfg["ports"], s0 + off, k:k + 12] = stored[:, off]
+            grid_of[row[19]] = len(grids)
+            grids.append(grid)
+        per_port = r[10:42].reshape(4, 8)[:P]
+        want = dict(status=int(r[0]), harq_ack=None if np.isnan(r[1]) else [int(b) for b in r[1:1 + cfg["nof_harq_ack"]]],
+                    sr=None if np.isnan(r[3]) else int(r[3]), metric=r[4], sinr_dB=r[5], rsrp_dB=r[6], epre_dB=r[7], time_alignment_s=r[8],
+                    cfo_hz=r[9], meas=None, ta=None, estimate=None, top=(r[42], r[43]))
+        if cfg["format"] == 1:
+            want["meas"] = [dict(noise_var=m[0], rsrp=m[1], epre=m[2], snr=m[3], cfo_hz=m[4]) for m in per_port]
+            want["ta"] = per_port[:, 5:8]
+            want["estimate"] = estimates[row[20]:row[20] + P * ns].reshape(P, ns)
+        cases.append(dict(cfg=cfg, row=row, grid=grid_of[row[19]], want=want, flagged=bool(row[21]), sent=row[24] >= 0))
+    return cases, np.stack(grids)
+
+
+def recorded_distance(cfg, got, got_meas, want, what):
+    """distance() against a recorded answer.  The reference's format 0 detector returns no metric (its SINR is 10 log10 of it).
+    rel() and max() let a NaN on one side only pass unseen, so first: every compared field is NaN exactly where the recorded one
+    is (a CFO where the reference has none, a measurement that is no number), as many measurements as ports, and what comes out
+    is a number."""
+    if cfg["format"] == 0:
+        got = dict(got, metric=np.nan)
+    pairs = [(name, got[name], want[name]) for name, _ in FIELDS] + [("cfo_hz", got["cfo_hz"], want["cfo_hz"])]
+    assert want["meas"] is None or len(got_meas) == len(want["meas"]), (what, len(got_meas))  # format 0 has none
+    for p, (m_got, m_want) in enumerate(zip(got_meas, want["meas"] or [])):
+        pairs += [("%s of port %d" % (name, p), m_got[name], m_want[name]) for name in MEAS_FIELDS + ("cfo_hz",)]
+    for name, a, b in pairs:
+        assert bool(np.isnan(a)) == bool(np.isnan(b)), (what, name, a, b)
+    d, c = distance(got, got_meas, want)
+    assert np.isfinite(d) and np.isfinite(c), (what, d, c)
+    return d, c
+
+
+def same_exact_fields(cfg, got, want, what):
+    """Status, bits and SR (where the reference wrote any: a zero grid leaves format 0's message unwritten) and the time alignment."""
+    assert got["status"] == want["status"], (what, got, want)
+    if want["harq_ack"] is not None:
+        assert list(got["harq_ack"][:cfg["nof_harq_ack"]]) == want["harq_ack"] and got["sr"] == want["sr"], (what, got, want)
+    assert got["time_alignment_s"] == want["time_alignment_s"], (what, got, want)
+
+
+def same_special_values(cfg, got, got_meas, want, what):
+    """Every recorded infinity, NaN and zero of a flagged case, exactly (format 0's metric is not recorded: recorded_distance)."""
+    pairs = [(got[name], want[name]) for name, _ in FIELDS[cfg["format"] == 0:]] + [(got["cfo_hz"], want["cfo_hz"])]
+    for m_got, m_want in zip(got_meas, want["meas"] or []):
+        pairs += [(m_got[name], m_want[name]) for name in MEAS_FIELDS + ("cfo_hz",)]
+    for a, b in pairs:
+        if np.isnan(b):
+            assert np.isnan(a), (what, a, b)
+        elif np.isinf(b) or b == 0:
+            assert a == b, (what, a, b)
+
+
+def estimate_of(cfg, ce):
+    """[ports][symbols] words of an estimate [ports][14][subc]: the first subcarrier of every symbol's PRB."""
+    ns, s0 = cfg["nof_symbols"], cfg["start_symbol_index"]
+    return np.array([[ce[p, s0 + off, 12 * recorded_prb(cfg, off)] for off in range(ns)] for p in range(len(cfg["ports"]))])
+
+
+def estimate_steps(cfg, ce, want, what):
+    """Largest distance in bf16 steps between an estimate [ports][14][subc] and the recorded one, which holds one value on the 12
+    subcarriers of every symbol's PRB; the 12 must be equal in `ce` too."""
+    ns, s0 = cfg["nof_symbols"], cfg["start_symbol_index"]
+    for off in range(ns):
+        k = 12 * recorded_prb(cfg, off)
+        block = ce[:len(cfg["ports"]), s0 + off, k:k + 12]
+        assert (block == block[:, :1]).all(), what
+    return max(int(np.abs(a - b).max()) for a, b in zip(bf16_key(estimate_of(cfg, ce)), bf16_key(want["estimate"])))
+
+
+def test_recording_is_consistent():
+    cases, grids = recording()
+    rows = np.load(os.path.join(GOLDEN, "pucch_reference_cases.npy"))
+    words = np.load(os.path.join(GOLDEN, "pucch_reference_grids.npy"))
+    results = np.load(os.path.join(GOLDEN, "pucch_reference_results.npy"))
+    estimates = np.load(os.path.join(GOLDEN, "pucch_reference_estimates.npy"))
+    assert rows.dtype == np.int32 and rows.shape == (NOF_RECORDED, 28) and results.dtype == np.float64 and results.shape == (NOF_RECORDED, 44)
+    assert words.dtype == np.uint32 and words.ndim == 1 and estimates.dtype == np.uint32 and estimates.ndim == 1
+    assert sum(os.path.getsize(os.path.join(GOLDEN, "pucch_reference_%s.npy" % n)) for n in ("cases", "grids", "results", "estimates")) < 400000
+    # The first 186 are the reference's configurations, in the fixtures' order, with the fixtures' bits.
+    fx = fixtures()
+    for f, k in zip(fx, cases):
+        assert k["cfg"] == model.from_fixture(f) and k["row"][22] == 0 and k["sent"], f
+        assert k["row"][24] == sum(b << i for i, b in enumerate(f["ack_bits"])) and k["row"][25] == (-1 if f.get("sr") is None else f["sr"]), f
+    assert [k["row"][22] for k in cases[len(fx):]] == sorted(k["row"][22] for k in cases[len(fx):]) and {k["row"][22] for k in cases} == {0, 1, 2, 3, 4}
+    # Offsets: the grids and the estimates are stored back to back in the order of the cases; cases of one grid share its region.
+    next_grid = next_estimate = 0
+    regions = {}
+    for i, k in enumerate(cases):
+        cfg, row = k["cfg"], k["row"]
+        assert lib.pucch_validate(to_abi(cfg), NOF_PORTS, NOF_SUBC) == abi.OK, (i, cfg)
+        size = len(cfg["ports"]) * cfg["nof_symbols"] * 12
+        region = (cfg["ports"], cfg["start_symbol_index"], [recorded_prb(cfg, off) for off in range(cfg["nof_symbols"])])
+        if row[19] in regions:
+            assert regions[row[19]] == region, i
+        else:
+            assert row[19] == next_grid, i
+            regions[row[19]] = region
+            next_grid += size
+        # Every element the receiver reads is a stored one: the rebuilt grid is zero outside the region and the region is the
+        # configured ports x the PUCCH's symbols x the 12 subcarriers of each symbol's PRB.
+        mask = np.zeros((NOF_PORTS, 14, NOF_SUBC), bool)
+        for off, prb in enumerate(region[2]):
+            mask[cfg["ports"], region[1] + off, 12 * prb:12 * prb + 12] = True
+        assert mask.sum() == size and not grids[k["grid"]][~mask].any(), i
+        if cfg["format"] == 1:
+            assert row[20] == next_estimate, i
+            next_estimate += size // 12
+        else:
+            assert row[20] == -1 and k["want"]["meas"] is None and np.isnan(results[i][10:42]).all(), i
+    assert next_grid == len(words) and next_estimate == len(estimates) and len(grids) == len(regions)
+    # The flagged cases are the two zero grids; every other grid holds noise on every stored element.
+    flagged = [i for i, k in enumerate(cases) if k["flagged"]]
+    assert len(flagged) == NOF_FLAGGED <= 12 and [cases[i]["cfg"]["format"] for i in flagged] == [0, 1]
+    for i, k in enumerate(cases):
+        assert k["flagged"] == (not grids[k["grid"]].any()) == (k["row"][22] == 2), i
+    noise_only = [k for k in cases if k["row"][22] == 3]
+    assert sorted(k["cfg"]["format"] for k in noise_only) == [0] * 13 + [1] * 13 and not any(k["sent"] for k in noise_only)
+    # Every candidate of each of format 0's five tables was sent at least once.
+    for (nack, sr_opp), table in model.FORMAT0_TABLES.items():
+        sent = {(k["row"][24], k["row"][25]) for k in cases if k["sent"] and k["cfg"]["format"] == 0 and k["cfg"]["nof_harq_ack"] == nack and
+                k["cfg"]["sr_opportunity"] == sr_opp}
+        assert sent >= {(sum(b << i for i, b in enumerate(ack)), -1 if sr is None else sr) for _, sr, ack in table}, (nack, sr_opp)
+    # The margins, on recorded numbers alone: the decided metric, the per-port SNRs, and what the recorder evaluated in double for
+    # format 0's two best candidates and format 1's two statistics.
+    T = model.THRESHOLD
+    for i, k in enumerate(cases):
+        cfg, want = k["cfg"], k["want"]
+        if k["flagged"]:
+            continue
+        decided = want["metric"] * T if cfg["format"] == 1 else 10 ** (want["sinr_dB"] / 10)
+        assert not (T / 2 <= decided <= 2 * T), (i, decided)
+        assert (want["status"] != model.INVALID) == (decided > T), (i, decided)
+        if k["row"][22] == 3:
+            continue
+        top = sorted(want["top"])
+        if len(model.FORMAT0_TABLES[(cfg["nof_harq_ack"], cfg["sr_opportunity"])]) > 1 if cfg["format"] == 0 else cfg["nof_harq_ack"] == 2:
+            assert top[1] - top[0] >= RECORDING_MARGIN * top[1] > 0, (i, top)
+        if cfg["format"] == 1 and len(cfg["ports"]) > 1:
+            snr = sorted(m["snr"] for m in want["meas"])
+            assert snr[-1] - snr[-2] >= RECORDING_MARGIN * snr[-1], (i, snr)
+    # Whatever the grid held, the reference's time alignment estimator returned 0 for every port and hop.
+    ta = np.concatenate([k["want"]["ta"].ravel() for k in cases if k["cfg"]["format"] == 1])
+    assert len(ta) == 3 * sum(len(k["cfg"]["ports"]) for k in cases if k["cfg"]["format"] == 1) and not ta[~np.isnan(ta)].any()
+    assert not results[:, 8].any()
+    # Each status is on record; `unknown` is the SR-only format 1 that carries the symbol of a 1 bit.
+    assert {k["want"]["status"] for k in cases} == {model.UNKNOWN, model.VALID, model.INVALID}
+    assert [(k["cfg"]["format"], k["cfg"]["nof_harq_ack"], k["row"][24]) for k in cases if k["want"]["status"] == model.UNKNOWN] == [(1, 0, 1)]
+
+
+def test_restatement_equals_the_recording():
+    """model.process in float32 and float64 on every recorded case: the reference's decisions exactly, its numbers within the
+    spreads above (measured here, printed and held against the constants)."""
+    cases, grids = recording()
+    spread = signal_spread = cfo_spread = 0.0
+    where = [None, None, None]
+    steps = 0
+    for i, k in enumerate(cases):
+        cfg, want = k["cfg"], k["want"]
+        r32, r64 = (model.process(cfg, grids[k["grid"]], dt) for dt in (np.float32, np.float64))
+        for r in (r32, r64):
+            same_exact_fields(cfg, r, want, (i, cfg))
+            assert all(m["ta_s"] == 0 and m["ta_bins"] == 0 for m in r["meas"] or [])
+            if k["flagged"]:
+                same_special_values(cfg, r, r["meas"] or [], want, (i, cfg))
+        if cfg["format"] == 1:
+            steps = max(steps, estimate_steps(cfg, r32["ce"], want, (i, cfg)))
+        if k["flagged"]:
+            continue
+        d, c = recorded_distance(cfg, r64, r64["meas"] or [], want, (i, cfg))
+        if d > spread:
+            spread, where[0] = d, i
+        if k["sent"] and d > signal_spread:
+            signal_spread, where[1] = d, i
+        if c > cfo_spread:
+            cfo_spread, where[2] = c, i
+    print("recording - float64 restatement: spread %.4g at case %s (constant %.3g), with a UE sent %.4g at case %s (constant %.3g), CFO "
+          "%.4g at case %s (constant %.3g); float32 restatement's estimate within %d bf16 step(s) (constant %d); %d cases" %
+          (spread, where[0], REF_SPREAD, signal_spread, where[1], REF_SIGNAL_SPREAD, cfo_spread, where[2], REF_CFO_SPREAD, steps,
+           REF_ESTIMATE_ULPS, len(cases)))
+    assert len(cases) == NOF_RECORDED and sum(k["flagged"] for k in cases) == NOF_FLAGGED
+    assert steps <= REF_ESTIMATE_ULPS
+    assert spread <= REF_SPREAD * 1.0001 and signal_spread <= REF_SIGNAL_SPREAD * 1.0001 and cfo_spread <= REF_CFO_SPREAD * 1.0001, \
+        "the constants no longer describe the cases"
+    # What the device is granted against the recording stays inside the margin the recording keeps around every decision.
+    assert 8 * REF_SPREAD < RECORDING_MARGIN
+
+
+def device_against_recording(i, k, res, meas, ce):
+    """One device result (a RESULT_DTYPE record, MEAS_DTYPE records of the PUCCH's ports, the estimate [ports][14][subc] with
+    sentinel words where nothing is written) against recorded case i: -> (distance, CFO distance, bf16 steps of the estimate)."""
+    cfg, want = k["cfg"], k["want"]
+    what = (i, cfg)
+    P = len(cfg["ports"])
+    same_exact_fields(cfg, res, want, what)
+    assert not res["harq_ack"][cfg["nof_harq_ack"]:].any() and (cfg["sr_opportunity"] or res["sr"] == 0), (what, res)
+    got = dict(metric=res["detection_metric"], sinr_dB=res["sinr_dB"], rsrp_dB=res["rsrp_dB"], epre_dB=res["epre_dB"], cfo_hz=res["cfo_hz"])
+    steps = 0
+    if cfg["format"] == 1:
+        region = np.zeros(ce.shape, bool)
+        for off in range(cfg["nof_symbols"]):
+            prb = recorded_prb(cfg, off)
+            region[:, cfg["start_symbol_index"] + off, 12 * prb:12 * prb + 12] = True
+        assert (ce[~region] == SENTINEL).all(), what
+        steps = estimate_steps(cfg, ce, want, what)
+        assert steps <= 1, (what, steps)
+        assert (meas["ta_s"] == want["ta"][:, 2]).all() and not meas["ta_bins"].any(), (what, meas)
+    else:
+        assert (ce == SENTINEL).all() and not meas.tobytes().strip(b"\0"), what
+    if k["flagged"]:
+        same_special_values(cfg, got, meas, want, what)
+        return 0.0, 0.0, steps
+    d, c = recorded_distance(cfg, got, meas, want, what)
+    assert d <= 8 * (REF_SIGNAL_SPREAD if k["sent"] else REF_SPREAD) and c <= 8 * REF_CFO_SPREAD, (what, d, c, res, meas, want)
+    return d, c, steps
+
+
+@pytest.mark.gpu
+def test_device_equals_the_recording(gpu_ctx):
+    """Every recorded case through nrphy_pucch_run as one plan of mixed formats and one launch.  Decisions, exact fields and the
+    time alignment equal; the estimate within 1 bf16 step (the bound test_parity_with_the_restatement holds the device to);
+    metric, dB values, per-port measurements and CFO within 8 x the reference's own distance from the float64 restatement -- the
+    allowance of the parity test and of the PRACH pin, for the same reason: per-lane double partial sums folded in another order
+    than the reference's float32 vector sums, and another libm."""
+    cases, grids = recording()
+    assert len(cases) == NOF_RECORDED and {k["cfg"]["format"] for k in cases} == {0, 1}
+    res, meas, ce = run_plan(gpu_ctx, [k["cfg"] for k in cases], [k["grid"] for k in cases], grids)
+    worst = worst_signal = worst_cfo = 0.0
+    steps = 0
+    for i, k in enumerate(cases):
+        P = len(k["cfg"]["ports"])
+        assert not meas[i][P:].tobytes().strip(b"\0") and (ce[i][P:] == SENTINEL).all(), i
+        d, c, s = device_against_recording(i, k, res[i], meas[i][:P], ce[i][:P])
+        worst, worst_cfo, steps = max(worst, d), max(worst_cfo, c), max(steps, s)
+        if k["sent"]:
+            worst_signal = max(worst_signal, d)
+    print("device - recording: worst %.3g (allowed %.3g), with a UE sent %.3g (allowed %.3g), CFO %.3g (allowed %.3g); estimate within "
+          "%d bf16 step(s); %d PUCCHs in one launch" % (worst, 8 * REF_SPREAD, worst_signal, 8 * REF_SIGNAL_SPREAD, worst_cfo,
+                                                         8 * REF_CFO_SPREAD, steps, len(cases)))
+
+
+@pytest.mark.gpu
+def test_host_call_equals_the_recording(gpu_ctx):
+    """Three recorded cases of each format through nrphy_pucch_host: the zero grid, the first of the reference's configurations
+    and a small shape on four permuted ports."""
+    cases, grids = recording()
+    picks = []
+    for fmt in (0, 1):
+        of = [i for i, k in enumerate(cases) if k["cfg"]["format"] == fmt]
+        picks += [next(i for i in of if cases[i]["flagged"]), next(i for i in of if cases[i]["row"][22] == 0),
+                  next(i for i in of if cases[i]["row"][22] == 1 and cases[i]["cfg"]["ports"] == [3, 1, 0, 2])]
+    assert len(set(picks)) == 6
+    for i in picks:
+        k = cases[i]
+        P = len(k["cfg"]["ports"])
+        r, m, e = gpu_ctx.pucch_host(to_abi(k["cfg"]), grids[k["grid"]], with_estimate=True, ch_est=np.full((P, 14, NOF_SUBC), SENTINEL, np.uint32))
+        device_against_recording(i, k, np.frombuffer(bytes(r), RESULT_DTYPE)[0], np.frombuffer(b"".join(bytes(x) for x in m), MEAS_DTYPE), e)

@@ -9,7 +9,8 @@ nrphy_channel_equalize, nrphy_demodulate_soft and nrphy_llr_descramble byte for 
 edge inputs, batches against per-PUCCH host calls, graph replay, sentinels, and a slot shared with PUSCH and PUCCH format 1.
 
 The grids come from the restatement's own transmitter, not from the reference's test vectors (which are not available): they show
-that transmitter and receiver agree.  What is independent of the restatement's author: the UCI encoder and decoder (pinned to
+that transmitter and receiver agree.  Format 2 has no recording of the reference's own answers yet; formats 0 and 1 have one
+(tests/golden/record_pucch_reference.cpp).  What is independent of the restatement's author: the UCI encoder and decoder (pinned to
 recorded reference results by tests/test_uci_decoder.py), the QPSK demapper and the Gold sequence (the C oracle's, pinned to the
 compiled reference), and the equaliser's restatement (shared with the PUSCH demodulator's tests).
 """
