@@ -426,10 +426,11 @@ int nrphy_channel_equalize_host(nrphy_ctx_t* ctx, uint32_t algorithm, uint32_t n
  * or all subcarriers; type 2: pairs {0,1,6,7}, {2,3,8,9}, {4,5,10,11} per group); symbols without data RE are skipped.
  * Receive port i reads grid port rx_ports[i].  Post-equalisation SINR (pusch_demodulator_impl.cpp:203-215, 255-262):
  * -10 log10 of the mean of the equalised noise variances that are not infinite, +inf when there are none or their sum is
- * not positive; reduced in a fixed order (two runs give the same bits).  Transform precoding is not supported. */
+ * not positive; reduced in a fixed order (two runs give the same bits).  Transform precoding and pi/2-BPSK are opt-in: see
+ * the _ex forms below. */
 typedef struct nrphy_pusch_demod_cfg {
   uint32_t rnti, n_id;                    /* c_init = rnti * 2^15 + n_id */
-  uint32_t qm;                            /* 2, 4, 6, 8 */
+  uint32_t qm;                            /* 2, 4, 6, 8; 1 (pi/2-BPSK) with NRPHY_PUSCH_DEMOD_PI2_BPSK */
   uint32_t start_symbol_index, nof_symbols;
   uint32_t dmrs_symbol_mask;              /* bit l = symbol l carries DM-RS */
   uint32_t dmrs_type;                     /* 1 or 2 */
@@ -438,7 +439,7 @@ typedef struct nrphy_pusch_demod_cfg {
   uint32_t nof_rx_ports;                  /* 1..4 */
   uint32_t rx_ports[NRPHY_MAX_PORTS];     /* grid port of receive port i */
   uint32_t equalizer;                     /* NRPHY_EQ_ZF, NRPHY_EQ_MMSE (one layer only, as the reference) */
-  uint32_t transform_precoding;           /* must be 0 */
+  uint32_t transform_precoding;           /* 0; 1 with NRPHY_PUSCH_DEMOD_TRANSFORM_PRECODING */
   uint32_t reserved_;
   uint64_t prb_mask[NRPHY_PRB_WORDS];     /* allocated PRBs, grid-indexed */
 } nrphy_pusch_demod_cfg_t;
@@ -468,6 +469,48 @@ int nrphy_pusch_demod_run(nrphy_pusch_demod_plan_t* plan, const void* d_grid, co
  * [layers][nof_rx_ports][14][grid_nof_subc] cbf16, noise_vars[nof_rx_ports] -> llr[G]; sinr_db may be NULL. */
 int nrphy_pusch_demodulate_host(nrphy_ctx_t* ctx, const nrphy_pusch_demod_cfg_t* cfg, const void* grid, uint32_t grid_nof_ports,
                                 uint32_t grid_nof_subc, const void* ch_est, const float* noise_vars, int8_t* llr, float* sinr_db);
+/* The forms with a feature mask.  The three functions above are these with features = 0 (one implementation): a caller written
+ * against them keeps getting the refusal of transform precoding and of qm = 1.  The plan type, nrphy_pusch_demod_run,
+ * nrphy_pusch_demod_plan_codeword_bits and the output layout are the same; a plan may mix plain and transform-precoded PUSCHs.
+ *   NRPHY_PUSCH_DEMOD_TRANSFORM_PRECODING  transform_precoding = 1 is accepted when there is one layer, the DM-RS is type 1 with
+ *     2 CDM groups without data (TS 38.214 Section 6.2.2: every symbol that carries data then carries 12 RE per PRB; the reference
+ *     would silently run a half-size transform on a DM-RS symbol otherwise) and the number of allocated PRBs M_rb is a size of
+ *     nrphy_transform_precoding_nof_prb_valid.  As in the reference the PRBs need not be contiguous: the transform runs over the
+ *     12 M_rb allocated subcarriers in ascending order.  Per OFDM symbol with data: equalise, nrphy_transform_deprecode over the
+ *     whole symbol, then demap symbol j with the equalised noise variance of RE j -- the deprecoder leaves the variances alone
+ *     (pusch_demodulator_impl.cpp:186-215) --, descramble; an RE the equaliser gave up on enters the transform as 0.  One
+ *     workgroup per symbol; bit for bit nrphy_channel_equalize -> nrphy_transform_deprecode -> nrphy_demodulate_soft ->
+ *     nrphy_llr_descramble.  The channel estimate of such a PUSCH comes from the caller (nrphy_pusch_chest_* has no low-PAPR
+ *     DM-RS, like the reference's dmrs_pusch_estimator).
+ *   NRPHY_PUSCH_DEMOD_PI2_BPSK  qm = 1 is accepted, with or without transform precoding: the pi/2-BPSK demapper of
+ *     nrphy_demodulate_soft (NRPHY_MOD_PI2_BPSK), indexed by the symbol's position in its OFDM symbol's span.
+ * Everything else of nrphy_pusch_demod_validate applies; a bit outside the two is NRPHY_ERR_ARGUMENT. */
+#define NRPHY_PUSCH_DEMOD_TRANSFORM_PRECODING 1u
+#define NRPHY_PUSCH_DEMOD_PI2_BPSK 2u
+int nrphy_pusch_demod_validate_ex(const nrphy_pusch_demod_cfg_t* cfg, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
+                                  uint32_t features);
+int nrphy_pusch_demod_plan_create_ex(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_demod_cfg_t* cfgs, const uint32_t* grid_index,
+                                     uint32_t nof_grids, uint32_t grid_nof_ports, uint32_t grid_nof_subc, const uint64_t* ce_offset,
+                                     uint32_t features, nrphy_pusch_demod_plan_t** plan);
+int nrphy_pusch_demodulate_host_ex(nrphy_ctx_t* ctx, const nrphy_pusch_demod_cfg_t* cfg, const void* grid, uint32_t grid_nof_ports,
+                                   uint32_t grid_nof_subc, const void* ch_est, const float* noise_vars, uint32_t features,
+                                   int8_t* llr, float* sinr_db);
+
+/* ---- receive side: transform deprecoder (DFT-s-OFDM) ----------------------------------------------------------------------
+ * Replaces transform_precoder::deprecode_ofdm_symbol (R/include/srsran/phy/generic_functions/transform_precoding/
+ * transform_precoder.h; impl R/lib/phy/generic_functions/transform_precoding/transform_precoder_dft_impl.cpp:31-57): the
+ * unnormalised inverse DFT of 12 * nof_prb points, then a multiplication by the float 1 / sqrt(12 * nof_prb).  Valid sizes
+ * (transform_precoding_helpers.h): nof_prb = 2^a 3^b 5^c up to 275 -- 53 values, the largest 270.  One workgroup per symbol, a
+ * run-time radix-{2,3,4,5} transform in LDS; the twiddles exp(+2 pi i k / N) are evaluated in double and rounded once. */
+/* 1 for a valid size, else 0.  Host only. */
+int nrphy_transform_precoding_nof_prb_valid(uint32_t nof_prb);
+/* `batch` symbols of 12 * nof_prb complex f32 back to back, d_in -> d_out (8-byte aligned); d_out == d_in is allowed, the
+ * reference calls it in place.  NRPHY_ERR_ARGUMENT for an invalid nof_prb; batch = 0 does nothing.  Asynchronous on `stream`;
+ * capturable once the size's twiddle table exists: it is uploaded by a plan creation that needs it or by the first call of that
+ * size (the rule of nrphy_dft_run). */
+int nrphy_transform_deprecode(nrphy_ctx_t* ctx, uint32_t nof_prb, uint32_t batch, const float* d_in, float* d_out, void* stream);
+/* One symbol from and to host memory (blocking). */
+int nrphy_transform_deprecode_host(nrphy_ctx_t* ctx, uint32_t nof_prb, const float* in, float* out);
 
 /* ---- receive side: PUSCH DM-RS channel estimator ------------------------------------------------------------------------
  * Replaces dmrs_pusch_estimator::estimate (R/lib/phy/upper/signal_processors/dmrs_pusch_estimator_impl.cpp:71-212, with

@@ -120,6 +120,8 @@ class PuschDemodCfg(C.Structure):
 
 EQ_ZF = 0
 EQ_MMSE = 1
+PUSCH_DEMOD_TRANSFORM_PRECODING = 1  # NRPHY_PUSCH_DEMOD_*: the feature mask of the _ex forms
+PUSCH_DEMOD_PI2_BPSK = 2
 
 
 def make_pusch_demod(*, prbs, qm=2, rnti=1, n_id=0, start_symbol=0, nof_symbols=14, dmrs_symbols=(), dmrs_type=1,
@@ -823,6 +825,12 @@ def declare(lib, prefix="nrphy_"):
     sig("pusch_demod_plan_codeword_bits", u64, vp, u32)
     sig("pusch_demod_run", i32, vp, vp, vp, vp, vp, u64, vp, vp)
     sig("pusch_demodulate_host", i32, vp, P(PuschDemodCfg), vp, u32, u32, vp, vp, vp, vp)
+    sig("pusch_demod_validate_ex", i32, P(PuschDemodCfg), u32, u32, u32)
+    sig("pusch_demod_plan_create_ex", i32, vp, u32, P(PuschDemodCfg), P(u32), u32, u32, u32, P(u64), u32, P(vp))
+    sig("pusch_demodulate_host_ex", i32, vp, P(PuschDemodCfg), vp, u32, u32, vp, vp, u32, vp, vp)
+    sig("transform_precoding_nof_prb_valid", i32, u32)
+    sig("transform_deprecode", i32, vp, u32, u32, vp, vp, vp)
+    sig("transform_deprecode_host", i32, vp, u32, vp, vp)
     sig("pusch_chest_validate", i32, P(PuschChestCfg), u32, u32)
     sig("pusch_chest_plan_create", i32, vp, u32, P(PuschChestCfg), P(u32), u32, u32, u32, P(u64), P(vp))
     sig("pusch_chest_plan_destroy", i32, vp)
@@ -911,6 +919,8 @@ ABI_SYMBOLS = [
     "nrphy_channel_equalize", "nrphy_channel_equalize_host", "nrphy_pusch_demod_validate", "nrphy_pusch_demod_codeword_bits",
     "nrphy_pusch_demod_plan_create", "nrphy_pusch_demod_plan_destroy", "nrphy_pusch_demod_plan_codeword_bits",
     "nrphy_pusch_demod_run", "nrphy_pusch_demodulate_host",
+    "nrphy_pusch_demod_validate_ex", "nrphy_pusch_demod_plan_create_ex", "nrphy_pusch_demodulate_host_ex",
+    "nrphy_transform_precoding_nof_prb_valid", "nrphy_transform_deprecode", "nrphy_transform_deprecode_host",
     "nrphy_pusch_chest_validate", "nrphy_pusch_chest_plan_create", "nrphy_pusch_chest_plan_destroy", "nrphy_pusch_chest_run",
     "nrphy_pusch_chest_host",
     "nrphy_prach_threshold", "nrphy_prach_validate", "nrphy_prach_window_width", "nrphy_prach_plan_create", "nrphy_prach_plan_destroy",

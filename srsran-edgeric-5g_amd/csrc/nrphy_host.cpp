@@ -370,9 +370,11 @@ extern "C" int nrphy_synchronize(nrphy_ctx_t* ctx, void* stream)
 // exp(+j 2 pi k / N) computed in double precision and rounded once.
 const float2* get_twiddle(nrphy_ctx* ctx, uint32_t size)
 {
-  if (!dft_size_supported(size)) {
-    return nullptr;
-  }
+  return dft_size_supported(size) ? get_twiddle_table(ctx, size) : nullptr;
+}
+
+const float2* get_twiddle_table(nrphy_ctx* ctx, uint32_t size)
+{
   std::lock_guard<std::recursive_mutex> lock(ctx->host_mutex);
   auto it = ctx->d_twiddle.find(size);
   if (it != ctx->d_twiddle.end()) {

@@ -230,6 +230,11 @@ struct nrphy_ctx {
 // The context's table exp(+j 2 pi k / size) of a size nrphy_dft_run supports, built on first use with the context's device
 // current; null for another size or when the upload fails.  It lives as long as the context.
 const float2* get_twiddle(nrphy_ctx* ctx, uint32_t size);
+// The same table for any size >= 1 (the transform-precoding sizes 12 * M_rb); the two share the context's tables.
+const float2* get_twiddle_table(nrphy_ctx* ctx, uint32_t size);
+// The deprecoder of nof_prb PRBs with the context's twiddle table (built on first use, device current): false for an invalid
+// size or a failed upload.  transform_precoder_host.cpp.
+bool transform_deprecode_plan(nrphy_ctx* ctx, uint32_t nof_prb, MixedDftPlan& plan);
 
 #pragma GCC visibility push(hidden)
 

@@ -403,11 +403,32 @@ struct PuschDemodItem {
   uint32_t bit_offset;                        // codeword bit of the first soft bit of the item
   uint32_t span_pos, nof_vector;              // equalised symbols of the OFDM symbol before the item; the span's vector part
 };
+// ---- transform precoding: run-time mixed-radix transform of 12 * M_rb points (dft_mixed_device.h) ------------------------
+constexpr uint32_t MIXED_DFT_THREADS    = 256;  // threads of the workgroup that runs one transform, whatever its size
+constexpr uint32_t MIXED_DFT_MAX_POINTS = 3240; // 12 * 270, the largest valid transform-precoding size
+constexpr uint32_t MIXED_DFT_MAX_STAGES = 8;    // 2916 = 4 * 3^6 takes 7
+struct MixedDftPlan {
+  uint32_t      n, nof_stages;
+  uint8_t       radix[MIXED_DFT_MAX_STAGES];    // each of {2, 3, 4, 5}; their product is n
+  const float2* twiddle;                        // exp(+j 2 pi k / n), k < n
+  float         scale;                          // 1 / sqrt(n) as the reference rounds it: 1.0F / std::sqrt((float)n)
+};
+// The stage list of n = 12 * nof_prb points (twiddle left null); false when nof_prb is not a valid transform-precoding size.
+bool       mixed_dft_stages(uint32_t nof_prb, MixedDftPlan& plan);
+hipError_t launch_transform_deprecode(const MixedDftPlan& plan, uint32_t batch, const float2* in, float2* out, hipStream_t stream);
+
+struct PuschTpItem {                          // one OFDM symbol of a transform-precoded PUSCH: one workgroup
+  uint32_t pusch, symbol, count;              // count = 12 * M_rb data RE, the transform's size
+  uint32_t bit_offset, nof_vector;            // as in PuschDemodItem
+  uint32_t dft;                               // its entry of PuschDemodLaunch::dft
+};
 struct PuschDemodLaunch {
   const PuschDemodDesc* desc;
   const PuschDemodItem* items;
+  const PuschTpItem*    tp_items;             // their partial sums follow those of `items`
+  const MixedDftPlan*   dft;                  // one per distinct transform size of the plan
   const uint16_t*       prbs;
-  const DemodLaunch*    demod;                // [4]: QPSK, 16-QAM, 64-QAM, 256-QAM
+  const DemodLaunch*    demod;                // [5]: QPSK, 16-QAM, 64-QAM, 256-QAM, pi/2-BPSK
   const GoldTables*     gold;
   const uint32_t*       x1_words;
   const uint32_t*       grid;
@@ -417,7 +438,7 @@ struct PuschDemodLaunch {
   uint64_t              llr_stride;
   double*               partial;              // [item][2]: sum and count of the finite equalised noise variances
   float*                sinr;                 // may be null
-  uint32_t              grid_nof_ports, grid_nof_subc, n_pusch, n_items;
+  uint32_t              grid_nof_ports, grid_nof_subc, n_pusch, n_items, n_tp_items;
 };
 hipError_t launch_pusch_demod(const PuschDemodLaunch& p, hipStream_t stream);
 struct EqualizeLaunch {

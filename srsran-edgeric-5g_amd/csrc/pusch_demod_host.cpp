@@ -1,7 +1,9 @@
 // Host side of the channel equaliser and the PUSCH demodulator (pusch_demod_kernels.hip): validation, codeword sizes, the plan's
 // work list, and the host-span forms.  The plan does on the host what pusch_demodulator_impl::demodulate does before its loops
 // (pusch_demodulator_impl.cpp:135-160: the RE masks of data and DM-RS symbols, c_init) and cuts every OFDM symbol's data RE into
-// work items of up to PUSCH_DEMOD_THREADS, each with its codeword bit offset and its place in the symbol's demapper span.
+// work items of up to PUSCH_DEMOD_THREADS, each with its codeword bit offset and its place in the symbol's demapper span.  A
+// transform-precoded PUSCH (the _ex forms with NRPHY_PUSCH_DEMOD_TRANSFORM_PRECODING) gets one item per OFDM symbol, in a list
+// of its own, and the stage list and twiddle table of its transform size.
 #include "pusch_alloc_host.h"
 
 #include <cmath>
@@ -41,10 +43,19 @@ uint32_t symbol_re(const nrphy_pusch_demod_cfg_t& c, uint32_t l, uint32_t nprb, 
   return nprb * (((c.dmrs_symbol_mask >> l) & 1U) ? popcount12(dmrs_mask) : NRPHY_NRE);
 }
 
-int validate(const nrphy_pusch_demod_cfg_t* c, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
+// NRPHY_MOD_* of a configuration's qm (pi/2-BPSK is the only modulation of one bit on PUSCH).
+uint32_t modulation_of(uint32_t qm)
+{
+  return qm == 1 ? NRPHY_MOD_PI2_BPSK : qm;
+}
+
+// `features`: what the caller opted into beyond the first contract (NRPHY_PUSCH_DEMOD_*); 0 refuses both.
+int validate(const nrphy_pusch_demod_cfg_t* c, uint32_t grid_nof_ports, uint32_t grid_nof_subc, uint32_t features)
 {
   uint32_t dmrs_mask = 0;
-  if (c == nullptr || c->transform_precoding != 0 || !(c->qm == 2 || c->qm == 4 || c->qm == 6 || c->qm == 8) ||
+  if (c == nullptr || (features & ~(NRPHY_PUSCH_DEMOD_TRANSFORM_PRECODING | NRPHY_PUSCH_DEMOD_PI2_BPSK)) != 0 ||
+      c->transform_precoding > ((features & NRPHY_PUSCH_DEMOD_TRANSFORM_PRECODING) ? 1U : 0U) ||
+      !(c->qm == 2 || c->qm == 4 || c->qm == 6 || c->qm == 8 || (c->qm == 1 && (features & NRPHY_PUSCH_DEMOD_PI2_BPSK))) ||
       c->nof_tx_layers < 1 || c->nof_tx_layers > 2 || c->equalizer > NRPHY_EQ_MMSE ||
       (c->nof_tx_layers == 2 && (c->equalizer != NRPHY_EQ_ZF || (c->nof_rx_ports != 2 && c->nof_rx_ports != 4))) ||
       !dmrs_data_mask(c->dmrs_type, c->nof_cdm_groups_without_data, dmrs_mask)) {
@@ -55,7 +66,14 @@ int validate(const nrphy_pusch_demod_cfg_t* c, uint32_t grid_nof_ports, uint32_t
     return NRPHY_ERR_ARGUMENT;
   }
   const uint32_t nprb = nof_prb(a);
-  uint32_t       nre  = 0;
+  // Transform precoding: one layer (pusch_demodulator_impl.cpp:188-190); DM-RS type 1 with both CDM groups kept free of data
+  // (TS 38.214 Section 6.2.2), so that every symbol with data carries 12 RE per PRB -- the reference would run a half-size
+  // transform on a DM-RS symbol otherwise; a PRB count the deprecoder has.
+  if (c->transform_precoding != 0 && (c->nof_tx_layers != 1 || c->dmrs_type != 1 || c->nof_cdm_groups_without_data != 2 ||
+                                      !nrphy_transform_precoding_nof_prb_valid(nprb))) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  uint32_t nre = 0;
   for (uint32_t l = 0; l != NRPHY_NSYMB; ++l) {
     nre += symbol_re(*c, l, nprb, dmrs_mask);
   }
@@ -66,12 +84,14 @@ int validate(const nrphy_pusch_demod_cfg_t* c, uint32_t grid_nof_ports, uint32_t
 
 struct nrphy_pusch_demod_plan {
   nrphy_ctx*            ctx = nullptr;
-  uint32_t              n = 0, n_items = 0;
+  uint32_t              n = 0, n_items = 0, n_tp_items = 0;
   uint32_t              nof_grids = 0, grid_nof_ports = 0, grid_nof_subc = 0;
   std::vector<uint64_t> cw_bits;
   void*                 d_arena   = nullptr;
   PuschDemodDesc*       d_desc    = nullptr;
   PuschDemodItem*       d_items   = nullptr;
+  PuschTpItem*          d_tp_items = nullptr;
+  MixedDftPlan*         d_dft     = nullptr;
   uint16_t*             d_prbs    = nullptr;
   DemodLaunch*          d_demod   = nullptr;
   double*               d_partial = nullptr;
@@ -79,7 +99,13 @@ struct nrphy_pusch_demod_plan {
 
 extern "C" int nrphy_pusch_demod_validate(const nrphy_pusch_demod_cfg_t* cfg, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
 {
-  return validate(cfg, grid_nof_ports, grid_nof_subc);
+  return validate(cfg, grid_nof_ports, grid_nof_subc, 0);
+}
+
+extern "C" int nrphy_pusch_demod_validate_ex(const nrphy_pusch_demod_cfg_t* cfg, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
+                                             uint32_t features)
+{
+  return validate(cfg, grid_nof_ports, grid_nof_subc, features);
 }
 
 extern "C" uint64_t nrphy_pusch_demod_codeword_bits(const nrphy_pusch_demod_cfg_t* cfg)
@@ -114,6 +140,14 @@ extern "C" int nrphy_pusch_demod_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
                                              const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports,
                                              uint32_t grid_nof_subc, const uint64_t* ce_offset, nrphy_pusch_demod_plan_t** out)
 {
+  return nrphy_pusch_demod_plan_create_ex(ctx, n, cfgs, grid_index, nof_grids, grid_nof_ports, grid_nof_subc, ce_offset, 0, out);
+}
+
+extern "C" int nrphy_pusch_demod_plan_create_ex(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_demod_cfg_t* cfgs,
+                                                const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports,
+                                                uint32_t grid_nof_subc, const uint64_t* ce_offset, uint32_t features,
+                                                nrphy_pusch_demod_plan_t** out)
+{
   if (out == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -123,11 +157,13 @@ extern "C" int nrphy_pusch_demod_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
   }
   std::vector<PuschDemodDesc> desc(n);
   std::vector<PuschDemodItem> items;
+  std::vector<PuschTpItem>    tp_items; // transform-precoded PUSCHs: one item per OFDM symbol, a kernel of their own
+  std::vector<MixedDftPlan>   dfts;     // one per distinct size
   std::vector<uint16_t>       prbs;
   std::vector<uint64_t>       cw_bits(n);
   for (uint32_t i = 0; i != n; ++i) {
     const nrphy_pusch_demod_cfg_t& c = cfgs[i];
-    if (validate(&c, grid_nof_ports, grid_nof_subc) != NRPHY_OK || grid_index[i] >= nof_grids) {
+    if (validate(&c, grid_nof_ports, grid_nof_subc, features) != NRPHY_OK || grid_index[i] >= nof_grids) {
       return NRPHY_ERR_ARGUMENT;
     }
     uint32_t dmrs_mask = 0;
@@ -154,14 +190,36 @@ extern "C" int nrphy_pusch_demod_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
     const uint32_t nprb = append_prbs(pusch_allocation(c), grid_nof_subc, prbs);
     const uint32_t nb   = c.nof_tx_layers * c.qm;
     uint32_t       bit  = 0;
-    d.item_first        = (uint32_t)items.size();
+    uint32_t       dft  = 0;
+    if (c.transform_precoding != 0) {
+      MixedDftPlan mp;
+      mixed_dft_stages(nprb, mp); // validate() has checked the size
+      for (; dft != dfts.size() && dfts[dft].n != mp.n; ++dft) {
+      }
+      if (dft == dfts.size()) {
+        dfts.push_back(mp);
+      }
+    }
+    d.item_first = (uint32_t)(c.transform_precoding != 0 ? tp_items.size() : items.size());
     for (uint32_t l = 0; l != NRPHY_NSYMB; ++l) {
       const uint32_t nre = symbol_re(c, l, nprb, dmrs_mask);
       if (nre == 0) {
         continue; // pusch_demodulator_impl.cpp:172-175
       }
       DemodLaunch dp;
-      demod_params(c.qm, nre * c.nof_tx_layers, dp);
+      demod_params(modulation_of(c.qm), nre * c.nof_tx_layers, dp);
+      if (c.transform_precoding != 0) {
+        PuschTpItem it;
+        it.pusch      = i;
+        it.symbol     = l;
+        it.count      = nre;
+        it.bit_offset = bit;
+        it.nof_vector = dp.nof_vector;
+        it.dft        = dft;
+        tp_items.push_back(it);
+        bit += nre * nb;
+        continue;
+      }
       for (uint32_t first = 0; first < nre; first += PUSCH_DEMOD_THREADS) {
         PuschDemodItem it;
         it.pusch      = i;
@@ -176,17 +234,34 @@ extern "C" int nrphy_pusch_demod_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
       }
       bit += nre * nb;
     }
-    d.nof_items = (uint32_t)items.size() - d.item_first;
+    d.nof_items = (uint32_t)(c.transform_precoding != 0 ? tp_items.size() : items.size()) - d.item_first;
     cw_bits[i]  = bit;
   }
-  DemodLaunch demod[4];
+  // The partial sums of the transform-precoded items follow those of the plain ones.
+  for (uint32_t i = 0; i != n; ++i) {
+    if (cfgs[i].transform_precoding != 0) {
+      desc[i].item_first += (uint32_t)items.size();
+    }
+  }
+  DemodLaunch demod[5];
   for (uint32_t m = 0; m != 4; ++m) {
     demod_params(2 * (m + 1), 0, demod[m]);
+  }
+  demod_params(NRPHY_MOD_PI2_BPSK, 0, demod[4]);
+  if (hipSetDevice(ctx->device) != hipSuccess) {
+    return NRPHY_ERR_DEVICE;
+  }
+  for (MixedDftPlan& mp : dfts) {
+    mp.twiddle = get_twiddle_table(ctx, mp.n);
+    if (mp.twiddle == nullptr) {
+      return NRPHY_ERR_DEVICE;
+    }
   }
   auto* plan           = new nrphy_pusch_demod_plan;
   plan->ctx            = ctx;
   plan->n              = n;
   plan->n_items        = (uint32_t)items.size();
+  plan->n_tp_items     = (uint32_t)tp_items.size();
   plan->nof_grids      = nof_grids;
   plan->grid_nof_ports = grid_nof_ports;
   plan->grid_nof_subc  = grid_nof_subc;
@@ -197,8 +272,10 @@ extern "C" int nrphy_pusch_demod_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
   arena.add(&plan->d_items, items.data(), items.size() * sizeof(PuschDemodItem));
   arena.add(&plan->d_prbs, prbs.data(), prbs.size() * sizeof(uint16_t));
   arena.add(&plan->d_demod, demod, sizeof(demod));
-  if (hipSetDevice(ctx->device) != hipSuccess ||
-      arena.commit(&plan->d_arena, items.size() * 2 * sizeof(double), (void**)&plan->d_partial) != hipSuccess) {
+  arena.add(&plan->d_tp_items, tp_items.data(), tp_items.size() * sizeof(PuschTpItem));
+  arena.add(&plan->d_dft, dfts.data(), dfts.size() * sizeof(MixedDftPlan));
+  if (arena.commit(&plan->d_arena, (items.size() + tp_items.size()) * 2 * sizeof(double), (void**)&plan->d_partial) !=
+      hipSuccess) {
     nrphy_pusch_demod_plan_destroy(plan);
     return NRPHY_ERR_DEVICE;
   }
@@ -228,7 +305,10 @@ extern "C" int nrphy_pusch_demod_run(nrphy_pusch_demod_plan_t* plan, const void*
   PuschDemodLaunch p;
   p.desc           = plan->d_desc;
   p.items          = plan->d_items;
-  p.prbs           = plan->d_prbs;
+  p.tp_items       = plan->d_tp_items;
+  p.dft            = plan->d_dft;
+  p.n_tp_items     = plan->n_tp_items;
+  p.prbs          = plan->d_prbs;
   p.demod          = plan->d_demod;
   p.gold           = plan->ctx->d_gold;
   p.x1_words       = plan->ctx->d_x1;
@@ -262,8 +342,15 @@ extern "C" int nrphy_pusch_demodulate_host(nrphy_ctx_t* ctx, const nrphy_pusch_d
                                            uint32_t grid_nof_ports, uint32_t grid_nof_subc, const void* ch_est,
                                            const float* noise_vars, int8_t* llr, float* sinr_db)
 {
+  return nrphy_pusch_demodulate_host_ex(ctx, cfg, grid, grid_nof_ports, grid_nof_subc, ch_est, noise_vars, 0, llr, sinr_db);
+}
+
+extern "C" int nrphy_pusch_demodulate_host_ex(nrphy_ctx_t* ctx, const nrphy_pusch_demod_cfg_t* cfg, const void* grid,
+                                              uint32_t grid_nof_ports, uint32_t grid_nof_subc, const void* ch_est,
+                                              const float* noise_vars, uint32_t features, int8_t* llr, float* sinr_db)
+{
   if (ctx == nullptr || grid == nullptr || ch_est == nullptr || noise_vars == nullptr || llr == nullptr ||
-      validate(cfg, grid_nof_ports, grid_nof_subc) != NRPHY_OK) {
+      validate(cfg, grid_nof_ports, grid_nof_subc, features) != NRPHY_OK) {
     return NRPHY_ERR_ARGUMENT;
   }
   const uint64_t G          = nrphy_pusch_demod_codeword_bits(cfg);
@@ -288,7 +375,7 @@ extern "C" int nrphy_pusch_demodulate_host(nrphy_ctx_t* ctx, const nrphy_pusch_d
   const uint32_t            zero = 0;
   const uint64_t            ce0  = 0;
   nrphy_pusch_demod_plan_t* plan = nullptr;
-  int rc = nrphy_pusch_demod_plan_create(ctx, 1, cfg, &zero, 1, grid_nof_ports, grid_nof_subc, &ce0, &plan);
+  int rc = nrphy_pusch_demod_plan_create_ex(ctx, 1, cfg, &zero, 1, grid_nof_ports, grid_nof_subc, &ce0, features, &plan);
   if (rc != NRPHY_OK) {
     return rc;
   }

@@ -13,8 +13,13 @@
 // adjacent along subcarriers), equalises in registers and demaps.  Wave 0 meanwhile generates the item's scrambling bits into
 // LDS.  The soft bits are staged in LDS with the destination's 16-byte phase and leave as 16-byte stores (bytes at the ends).
 // HBM-bound: per RE 4 (ports + layers x ports) bytes in, layers x qm bytes out.
+//
+// A transform-precoded PUSCH (opt-in, nrphy_pusch_demod_plan_create_ex) takes pusch_tp_demod_kernel instead, one workgroup per
+// OFDM symbol with the deprecoder between equaliser and demapper: see it below.  pi/2-BPSK without transform precoding is one
+// more instantiation of the item above.
 #include "bits_device.h"
 #include "demod_device.h"
+#include "dft_mixed_device.h"
 #include "equalize_device.h"
 
 #include <hip/hip_runtime.h>
@@ -60,6 +65,19 @@ __global__ __launch_bounds__(256) void channel_equalize_kernel(EqualizeLaunch p)
 constexpr uint32_t SEQ_WORDS   = 160;                          // >= (31 + 256 * 16) / 32 + 2, and >= the 31 head words
 constexpr uint32_t STAGE_BYTES = PUSCH_DEMOD_THREADS * 16 + 16; // soft bits of an item at the destination's 16-byte phase
 
+// Soft bits per symbol of a demapper instantiation, and its entry of PuschDemodLaunch::demod (pi/2-BPSK, NRPHY_MOD_PI2_BPSK = 0,
+// comes last).
+template <uint32_t MOD>
+constexpr uint32_t demod_qm()
+{
+  return MOD == NRPHY_MOD_PI2_BPSK ? 1u : MOD;
+}
+template <uint32_t MOD>
+constexpr uint32_t demod_slot()
+{
+  return MOD == NRPHY_MOD_PI2_BPSK ? 4u : MOD / 2u - 1u;
+}
+
 struct PuschDemodShared {
   Tables   t;
   uint32_t seq[SEQ_WORDS];
@@ -67,18 +85,41 @@ struct PuschDemodShared {
   __attribute__((aligned(16))) uint8_t stage[STAGE_BYTES];
 };
 
+// Stage bytes [lo, hi) -> base[lo, hi), base 16-byte aligned and the stage at the same phase: 16-byte stores, bytes at the ends.
+__device__ __forceinline__ void store_staged(const uint8_t* stage, int8_t* base, uint32_t lo, uint32_t hi, uint32_t tid)
+{
+  const uint32_t c_first = (lo + 15u) / 16u, c_last = hi / 16u;
+  if (c_first >= c_last) {
+    for (uint32_t b = lo + tid; b < hi; b += PUSCH_DEMOD_THREADS) {
+      base[b] = (int8_t)stage[b];
+    }
+    return;
+  }
+  for (uint32_t c = c_first + tid; c < c_last; c += PUSCH_DEMOD_THREADS) {
+    reinterpret_cast<uint4*>(base)[c] = reinterpret_cast<const uint4*>(stage)[c];
+  }
+  const uint32_t head = 16u * c_first - lo, tail = hi - 16u * c_last;
+  if (tid < head) {
+    base[lo + tid] = (int8_t)stage[lo + tid];
+  } else if (tid >= 16u && tid < 16u + tail) {
+    const uint32_t b = 16u * c_last + (tid - 16u);
+    base[b]          = (int8_t)stage[b];
+  }
+}
+
 template <uint32_t MOD>
 __device__ __forceinline__ void pusch_demod_item(const PuschDemodLaunch& p, const PuschDemodItem& it, const PuschDemodDesc& d,
                                                  PuschDemodShared& s)
 {
-  const DemodLaunch& dm   = p.demod[MOD / 2u - 1u];
+  constexpr uint32_t QM   = demod_qm<MOD>();
+  const DemodLaunch& dm   = p.demod[demod_slot<MOD>()];
   const uint32_t     tid  = threadIdx.x, lane = tid % WAVE;
   if constexpr (MOD >= NRPHY_MOD_QAM64) {
     for (uint32_t k = tid; k < DEMOD_MAX_PAIRS * 16u; k += PUSCH_DEMOD_THREADS) {
       s.t.line[k / 16u][k % 16u] = make_float2(dm.slope[k / 16u][k % 16u], dm.intercept[k / 16u][k % 16u]);
     }
   }
-  const uint32_t L = d.nof_layers, P = d.nof_rx_ports, nb = L * MOD;
+  const uint32_t L = d.nof_layers, P = d.nof_rx_ports, nb = L * QM;
   const bool     active = tid < it.count;
 
   // The lane's RE: data RE r of the symbol -> PRB of the allocation and subcarrier within it.
@@ -132,9 +173,9 @@ __device__ __forceinline__ void pusch_demod_item(const PuschDemodLaunch& p, cons
       if (l < L) {
         const uint32_t j = it.span_pos + tid * L + l; // position in the OFDM symbol's span (the reference's demapper call)
         if (j < it.nof_vector) {
-          demodulate_symbol<MOD, true>(dm, s.t, j, x[l].x, x[l].y, v[l], out, l * MOD);
+          demodulate_symbol<MOD, true>(dm, s.t, j, x[l].x, x[l].y, v[l], out, l * QM);
         } else {
-          demodulate_symbol<MOD, false>(dm, s.t, j, x[l].x, x[l].y, v[l], out, l * MOD);
+          demodulate_symbol<MOD, false>(dm, s.t, j, x[l].x, x[l].y, v[l], out, l * QM);
         }
         if (!__builtin_isinf(v[l])) { // pusch_demodulator_impl.cpp:203-215: the infinite variances (DC, dropped RE) are left out
           vsum += (double)v[l];
@@ -178,25 +219,7 @@ __device__ __forceinline__ void pusch_demod_item(const PuschDemodLaunch& p, cons
     part[0]      = (s.red[0][0] + s.red[0][1]) + (s.red[0][2] + s.red[0][3]);
     part[1]      = (s.red[1][0] + s.red[1][1]) + (s.red[1][2] + s.red[1][3]);
   }
-  const uint32_t lo = shift, hi = shift + it.count * nb; // stage bytes [lo, hi) -> dst[0, hi - lo)
-  const uint32_t c_first = (lo + 15u) / 16u, c_last = hi / 16u;
-  int8_t*        base    = dst - shift; // 16-byte aligned
-  if (c_first >= c_last) {
-    for (uint32_t b = lo + tid; b < hi; b += PUSCH_DEMOD_THREADS) {
-      base[b] = (int8_t)s.stage[b];
-    }
-    return;
-  }
-  for (uint32_t c = c_first + tid; c < c_last; c += PUSCH_DEMOD_THREADS) {
-    reinterpret_cast<uint4*>(base)[c] = reinterpret_cast<const uint4*>(s.stage)[c];
-  }
-  const uint32_t head = 16u * c_first - lo, tail = hi - 16u * c_last;
-  if (tid < head) {
-    base[lo + tid] = (int8_t)s.stage[lo + tid];
-  } else if (tid >= 16u && tid < 16u + tail) {
-    const uint32_t b = 16u * c_last + (tid - 16u);
-    base[b]          = (int8_t)s.stage[b];
-  }
+  store_staged(s.stage, dst - shift, shift, shift + it.count * nb, tid);
 }
 
 __global__ __launch_bounds__(PUSCH_DEMOD_THREADS) void pusch_demod_kernel(PuschDemodLaunch p)
@@ -205,6 +228,9 @@ __global__ __launch_bounds__(PUSCH_DEMOD_THREADS) void pusch_demod_kernel(PuschD
   const PuschDemodItem  it = p.items[blockIdx.x];
   const PuschDemodDesc& d  = p.desc[it.pusch]; // read in place: dmrs_subc is indexed per lane
   switch (d.qm) { // workgroup-uniform
+    case 1:
+      pusch_demod_item<NRPHY_MOD_PI2_BPSK>(p, it, d, s);
+      break;
     case NRPHY_MOD_QPSK:
       pusch_demod_item<NRPHY_MOD_QPSK>(p, it, d, s);
       break;
@@ -216,6 +242,153 @@ __global__ __launch_bounds__(PUSCH_DEMOD_THREADS) void pusch_demod_kernel(PuschD
       break;
     default:
       pusch_demod_item<NRPHY_MOD_QAM256>(p, it, d, s);
+      break;
+  }
+}
+
+// ---- transform-precoded PUSCH: one workgroup per OFDM symbol -----------------------------------------------------------------
+// pusch_demodulator_impl.cpp:186-201 puts precoder->deprecode_ofdm_symbol(eq_re, eq_re) between the equaliser and the demapper,
+// and the transform needs the whole symbol, so the 256-RE items above cannot be used: the workgroup equalises the symbol's
+// 12 M_rb RE (thread t those with r = t mod 256) into LDS, runs mixed_dft_inverse() -- the stand-alone deprecoder's routine --,
+// scales by the float 1 / sqrt(M_sc) and demaps symbol j with the variance of RE j: the reference leaves the variances alone.
+// A dropped RE (symbol 0, variance +inf) enters the transform as 0.  The soft bits are staged in the buffer the transform left
+// free.  LDS: two buffers of 3248 complex + 3248 variances + 832 sequence words + the demapper's lines = 68.9 KB, two
+// workgroups per CU.
+constexpr uint32_t TP_BUF_POINTS = MIXED_DFT_MAX_POINTS + 8;                           // soft bits: 8 x 3240 + the 16-byte phase
+constexpr uint32_t TP_SEQ_WORDS  = (31u + MIXED_DFT_MAX_POINTS * 8u + 31u) / 32u + 21u; // the symbol's words, and one read past them
+static_assert(TP_BUF_POINTS * 8u >= MIXED_DFT_MAX_POINTS * 8u + 32u, "stage");
+static_assert(PUSCH_DEMOD_THREADS == MIXED_DFT_THREADS, "one workgroup shape for the item and the transform");
+
+struct PuschTpShared {
+  __attribute__((aligned(16))) cf buf[2][TP_BUF_POINTS];
+  float    var[TP_BUF_POINTS];
+  Tables   t;
+  uint32_t seq[TP_SEQ_WORDS];
+  double   red[2][PUSCH_DEMOD_THREADS / WAVE];
+};
+
+template <uint32_t MOD>
+__device__ __forceinline__ void pusch_tp_item(const PuschDemodLaunch& p, const PuschTpItem& it, const PuschDemodDesc& d,
+                                              const MixedDftPlan& plan, PuschTpShared& s)
+{
+  constexpr uint32_t QM   = demod_qm<MOD>();
+  const DemodLaunch& dm   = p.demod[demod_slot<MOD>()];
+  const uint32_t     tid  = threadIdx.x, lane = tid % WAVE;
+  if constexpr (MOD >= NRPHY_MOD_QAM64) {
+    for (uint32_t k = tid; k < DEMOD_MAX_PAIRS * 16u; k += PUSCH_DEMOD_THREADS) {
+      s.t.line[k / 16u][k % 16u] = make_float2(dm.slope[k / 16u][k % 16u], dm.intercept[k / 16u][k % 16u]);
+    }
+  }
+  const uint32_t P = d.nof_rx_ports;
+  float          nv[NRPHY_MAX_PORTS];
+#pragma unroll
+  for (uint32_t i = 0; i != NRPHY_MAX_PORTS; ++i) {
+    nv[i] = p.noise[(size_t)it.pusch * NRPHY_MAX_PORTS + i];
+  }
+  const float nv_max = max_noise(nv, P);
+
+  // Gather and equalise: one layer, 12 data RE per PRB on every symbol that carries data.
+  double       vsum = 0.0, vcnt = 0.0;
+  const size_t nsubc = p.grid_nof_subc;
+  for (uint32_t r = tid; r < it.count; r += PUSCH_DEMOD_THREADS) {
+    const uint32_t ord  = r / NRPHY_NRE;
+    const uint32_t subc = NRPHY_NRE * (uint32_t)p.prbs[d.prb_first + ord] + (r - ord * NRPHY_NRE);
+    uint32_t       y[NRPHY_MAX_PORTS] = {}, h[2][NRPHY_MAX_PORTS] = {};
+#pragma unroll
+    for (uint32_t i = 0; i != NRPHY_MAX_PORTS; ++i) {
+      if (i < P) {
+        y[i]    = p.grid[(((size_t)d.grid_index * p.grid_nof_ports + d.rx_ports[i]) * NRPHY_NSYMB + it.symbol) * nsubc + subc];
+        h[0][i] = p.ch[d.ce_offset + ((size_t)i * NRPHY_NSYMB + it.symbol) * nsubc + subc];
+      }
+    }
+    float2 x[2];
+    float  v[2];
+    equalize_re(d.equalizer, 1u, P, y, h, nv, nv_max, 1.0f, x, v);
+    s.buf[0][r] = make_cf(x[0].x, x[0].y);
+    s.var[r]    = v[0];
+    if (!__builtin_isinf(v[0])) { // pusch_demodulator_impl.cpp:203-215
+      vsum += (double)v[0];
+      vcnt += 1.0;
+    }
+  }
+
+  // Wave 0: the symbol's scrambling bits, as in pusch_demod_item.
+  const uint32_t first_word = it.bit_offset >> 5;
+  const uint32_t nwords     = ((it.bit_offset & 31u) + it.count * QM + 31u) >> 5;
+  if (tid < WAVE) {
+    gold_sequence_blocks_wave(p.gold, d.c_init, first_word, nwords, s.seq, lane, [&](uint32_t base, uint32_t avail) {
+      for (uint32_t k = lane; k < avail; k += WAVE) {
+        s.seq[base + k] ^= p.x1_words[first_word + base + k];
+      }
+      wave_lds_fence();
+    });
+  }
+
+  const cf* z     = mixed_dft_inverse(plan, s.buf[0], s.buf[1], tid);
+  uint8_t*  stage = reinterpret_cast<uint8_t*>(z == s.buf[0] ? s.buf[1] : s.buf[0]);
+
+  int8_t*        dst   = p.llr + (size_t)it.pusch * p.llr_stride + it.bit_offset;
+  const uint32_t shift = (uint32_t)(reinterpret_cast<uintptr_t>(dst) & 15u);
+  for (uint32_t r = tid; r < it.count; r += PUSCH_DEMOD_THREADS) {
+    const cf    zr = z[r];
+    const float re = __fmul_rn(zr.x, plan.scale), im = __fmul_rn(zr.y, plan.scale); // transform_precoder_dft_impl.cpp:53-56
+    LlrBytes    out;
+    if (r < it.nof_vector) {
+      demodulate_symbol<MOD, true>(dm, s.t, r, re, im, s.var[r], out, 0);
+    } else {
+      demodulate_symbol<MOD, false>(dm, s.t, r, re, im, s.var[r], out, 0);
+    }
+    const uint32_t b0   = (it.bit_offset & 31u) + r * QM;
+    const uint64_t pair = ((uint64_t)s.seq[b0 >> 5] << 32) | s.seq[(b0 >> 5) + 1u];
+    const uint32_t bits = (uint32_t)(pair >> (48u - (b0 & 31u))) & 0xFFFFu; // first soft bit in bit 15
+#pragma unroll
+    for (uint32_t w = 0; w != (QM + 3u) / 4u; ++w) {
+      out.w[w] = negate_bytes(out.w[w], byte_masks_msb_first((bits >> (12u - 4u * w)) & 0xFu));
+    }
+    uint8_t* st = stage + shift + r * QM;
+#pragma unroll
+    for (uint32_t k = 0; k != QM; ++k) {
+      st[k] = out.get(k);
+    }
+  }
+
+  // SINR partial sums of the symbol: a thread's RE in ascending order, wave sums, then the four waves in order.
+  vsum = wave_sum(vsum);
+  vcnt = wave_sum(vcnt);
+  if (lane == 0) {
+    s.red[0][tid / WAVE] = vsum;
+    s.red[1][tid / WAVE] = vcnt;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double* part = p.partial + 2u * (size_t)(p.n_items + blockIdx.x);
+    part[0]      = (s.red[0][0] + s.red[0][1]) + (s.red[0][2] + s.red[0][3]);
+    part[1]      = (s.red[1][0] + s.red[1][1]) + (s.red[1][2] + s.red[1][3]);
+  }
+  store_staged(stage, dst - shift, shift, shift + it.count * QM, tid);
+}
+
+__global__ __launch_bounds__(PUSCH_DEMOD_THREADS) void pusch_tp_demod_kernel(PuschDemodLaunch p)
+{
+  __shared__ PuschTpShared s;
+  const PuschTpItem     it   = p.tp_items[blockIdx.x];
+  const PuschDemodDesc& d    = p.desc[it.pusch];
+  const MixedDftPlan&   plan = p.dft[it.dft]; // read in place: a copy indexed by the stage would be put in LDS
+  switch (d.qm) { // workgroup-uniform
+    case 1:
+      pusch_tp_item<NRPHY_MOD_PI2_BPSK>(p, it, d, plan, s);
+      break;
+    case NRPHY_MOD_QPSK:
+      pusch_tp_item<NRPHY_MOD_QPSK>(p, it, d, plan, s);
+      break;
+    case NRPHY_MOD_QAM16:
+      pusch_tp_item<NRPHY_MOD_QAM16>(p, it, d, plan, s);
+      break;
+    case NRPHY_MOD_QAM64:
+      pusch_tp_item<NRPHY_MOD_QAM64>(p, it, d, plan, s);
+      break;
+    default:
+      pusch_tp_item<NRPHY_MOD_QAM256>(p, it, d, plan, s);
       break;
   }
 }
@@ -250,10 +423,15 @@ hipError_t launch_channel_equalize(const EqualizeLaunch& p, hipStream_t stream)
 
 hipError_t launch_pusch_demod(const PuschDemodLaunch& p, hipStream_t stream)
 {
-  if (p.n_items == 0) {
+  if (p.n_items == 0 && p.n_tp_items == 0) {
     return hipSuccess;
   }
-  hipLaunchKernelGGL(pusch_demod_kernel, dim3(p.n_items), dim3(PUSCH_DEMOD_THREADS), 0, stream, p);
+  if (p.n_items != 0) {
+    hipLaunchKernelGGL(pusch_demod_kernel, dim3(p.n_items), dim3(PUSCH_DEMOD_THREADS), 0, stream, p);
+  }
+  if (p.n_tp_items != 0) {
+    hipLaunchKernelGGL(pusch_tp_demod_kernel, dim3(p.n_tp_items), dim3(PUSCH_DEMOD_THREADS), 0, stream, p);
+  }
   if (p.sinr != nullptr) {
     hipLaunchKernelGGL(pusch_sinr_kernel, dim3(p.n_pusch), dim3(WAVE), 0, stream, p);
   }

@@ -443,6 +443,18 @@ class Context:
                "nrphy_pusch_demodulate_host")
         return out, float(sinr.value)
 
+    def pusch_demodulate_host_ex(self, cfg, grid, ch_est, noise_vars, features):
+        """pusch_demodulate_host with a feature mask (abi.PUSCH_DEMOD_*): transform precoding and pi/2-BPSK."""
+        grid = np.ascontiguousarray(grid, dtype=np.uint32)
+        ch_est = np.ascontiguousarray(ch_est, dtype=np.uint32)
+        nv = np.ascontiguousarray(noise_vars, dtype=np.float32)
+        out = np.zeros(pusch_demod_codeword_bits(cfg), np.int8)
+        sinr = C.c_float(0)
+        _check(self.lib.nrphy_pusch_demodulate_host_ex(self.handle, C.byref(cfg), grid.ctypes.data, grid.shape[0], grid.shape[-1],
+                                                       ch_est.ctypes.data, nv.ctypes.data, features, out.ctypes.data,
+                                                       C.byref(sinr)), "nrphy_pusch_demodulate_host_ex")
+        return out, float(sinr.value)
+
     def pusch_chest_host(self, cfg, grid, ch_est=None):
         """dmrs_pusch_estimator::estimate + the processor's DC step for one PUSCH: grid [ports][14][subc] raw cbf16 words ->
         (ch_est [layers][rx][14][subc] cbf16 words, noise_vars [rx], measurements [rx][2] of abi.PuschChestMeas).  ch_est: the
@@ -591,6 +603,22 @@ class Context:
         _check(self.lib.nrphy_dft_run(self.handle, size, int(inverse), batch, _dptr(d_in), _dptr(d_out), _stream(stream)),
                "nrphy_dft_run")
 
+    def transform_deprecode(self, nof_prb, batch, d_in, d_out, stream=None):
+        """transform_precoder::deprecode_ofdm_symbol for `batch` symbols of 12 * nof_prb complex64 in device memory; d_out may be
+        d_in."""
+        _check(self.lib.nrphy_transform_deprecode(self.handle, nof_prb, batch, _dptr(d_in), _dptr(d_out), _stream(stream)),
+               "nrphy_transform_deprecode")
+
+    def transform_deprecode_host(self, nof_prb, symbols):
+        """One symbol of 12 * nof_prb complex64 from host memory -> the deprecoded symbol."""
+        x = np.ascontiguousarray(symbols, dtype=np.complex64)
+        if x.shape != (12 * nof_prb,):
+            raise ValueError("a symbol of %d PRB has %d elements" % (nof_prb, 12 * nof_prb))
+        out = np.zeros_like(x)
+        _check(self.lib.nrphy_transform_deprecode_host(self.handle, nof_prb, x.ctypes.data, out.ctypes.data),
+               "nrphy_transform_deprecode_host")
+        return out
+
 
 class PdschPlan:
     """nrphy_pdsch_plan: a batch of PDUs with their grids; run() launches the whole PDSCH path."""
@@ -665,15 +693,16 @@ class PdschPlan:
 class PuschDemodPlan:
     """nrphy_pusch_demod_plan: PUSCHs over a batch of received grids; run() equalises, demaps and descrambles them in one launch."""
 
-    def __init__(self, ctx, cfgs, grid_indices, nof_grids, nof_ports, nof_subc, ce_offsets):
+    def __init__(self, ctx, cfgs, grid_indices, nof_grids, nof_ports, nof_subc, ce_offsets, features=0):
+        """features: abi.PUSCH_DEMOD_* bits (transform precoding, pi/2-BPSK); 0 is nrphy_pusch_demod_plan_create."""
         self.ctx = ctx
         n = len(cfgs)
         arr = (abi.PuschDemodCfg * n)(*cfgs)
         gidx = (C.c_uint32 * n)(*grid_indices)
         offs = (C.c_uint64 * n)(*ce_offsets)
         h = C.c_void_p()
-        _check(ctx.lib.nrphy_pusch_demod_plan_create(ctx.handle, n, arr, gidx, nof_grids, nof_ports, nof_subc, offs, C.byref(h)),
-               "nrphy_pusch_demod_plan_create")
+        _check(ctx.lib.nrphy_pusch_demod_plan_create_ex(ctx.handle, n, arr, gidx, nof_grids, nof_ports, nof_subc, offs, features,
+                                                        C.byref(h)), "nrphy_pusch_demod_plan_create_ex")
         self.handle = h
         self.n = n
 
@@ -1120,6 +1149,16 @@ def pusch_chest_validate(cfg, grid_nof_ports, grid_nof_subc):
 def pusch_demod_validate(cfg, grid_nof_ports, grid_nof_subc):
     """nrphy_pusch_demod_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
     return int(load().nrphy_pusch_demod_validate(C.byref(cfg), grid_nof_ports, grid_nof_subc))
+
+
+def pusch_demod_validate_ex(cfg, grid_nof_ports, grid_nof_subc, features):
+    """nrphy_pusch_demod_validate_ex: the validator with a feature mask (abi.PUSCH_DEMOD_*); host only."""
+    return int(load().nrphy_pusch_demod_validate_ex(C.byref(cfg), grid_nof_ports, grid_nof_subc, features))
+
+
+def transform_precoding_nof_prb_valid(nof_prb):
+    """nrphy_transform_precoding_nof_prb_valid: whether 12 * nof_prb is a transform-precoding size (host only)."""
+    return bool(load().nrphy_transform_precoding_nof_prb_valid(nof_prb))
 
 
 def pusch_demod_codeword_bits(cfg):
