@@ -1797,6 +1797,160 @@ int nrphy_dl_slot_pdcch(nrphy_dl_slots_t* pool, uint32_t slot_id, uint32_t n, co
 int nrphy_dl_slot_ssb(nrphy_dl_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_ssb_pdu_t* pdus);
 int nrphy_dl_slot_csi_rs(nrphy_dl_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_csi_rs_cfg_t* cfgs);
 
+/* ---- receive side: UL-SCH information (TS 38.212 Section 6.3.2.4) ---------------------------------------------------------------
+ * Replaces get_ulsch_information (R/include/srsran/ran/pusch/ulsch_info.h; impl R/lib/ran/pusch/ulsch_info.cpp:30-360 with
+ * get_sch_segmentation_info, R/lib/ran/sch/sch_segmentation.cpp:30-63): the rate-matching sizes of a PUSCH that carries UL-SCH,
+ * HARQ-ACK, CSI part 1 and CSI part 2 -- what nrphy_ulsch_demux_cfg_t, nrphy_uci_decoder_cfg_t and nrphy_pusch_decoder_cfg_t take
+ * as inputs.  The fields are ulsch_configuration and ulsch_information.  Host arithmetic only; the float expressions keep the
+ * reference's order of operations (the function is named ul_sch: the symbols with "ulsch" in them are the demultiplexer's). */
+typedef struct nrphy_ulsch_info_cfg {
+  uint32_t tbs_bits;                    /* transport-block size in bits; 0 = no UL-SCH */
+  uint32_t modulation;                  /* NRPHY_MOD_* */
+  float    target_code_rate;            /* R x 1024, in (0, 1024) */
+  uint32_t nof_harq_ack_bits, nof_csi_part1_bits, nof_csi_part2_bits; /* O^ACK, O^CSI-1, O^CSI-2 */
+  float    alpha_scaling;               /* alpha */
+  float    beta_offset_harq_ack, beta_offset_csi_part1, beta_offset_csi_part2;
+  uint32_t nof_rb;
+  uint32_t start_symbol_index, nof_symbols;
+  uint32_t dmrs_type;                   /* 1 or 2 */
+  uint32_t dmrs_symbol_mask;            /* bit l = symbol l carries DM-RS; every bit inside [start, start + nof) */
+  uint32_t nof_cdm_groups_without_data; /* type 1: 1..2, type 2: 1..3 */
+  uint32_t nof_layers;                  /* 1..4 */
+  uint32_t contains_dc;                 /* 0 or 1: the allocation overlaps the DC subcarrier */
+} nrphy_ulsch_info_cfg_t;
+typedef struct nrphy_ulsch_info {
+  uint32_t has_sch;                     /* tbs_bits > 0; the six segmentation fields below are 0 without it */
+  uint32_t tb_crc_bits, base_graph, nof_cb, nof_filler_bits_per_cb, lifting_size, nof_bits_per_cb; /* sch_information */
+  uint32_t nof_ul_sch_bits, nof_harq_ack_bits, nof_harq_ack_rvd, nof_csi_part1_bits, nof_csi_part2_bits; /* G^UL-SCH, G^ACK, G^ACK_rvd, G^CSI-1, G^CSI-2 */
+  uint32_t nof_harq_ack_re, nof_csi_part1_re, nof_csi_part2_re; /* Q'_ACK, Q'_CSI-1, Q'_CSI-2 */
+  uint32_t nof_dc_overlap_bits;
+} nrphy_ulsch_info_t;
+/* NRPHY_OK, or NRPHY_ERR_ARGUMENT for what the reference asserts on -- a code rate outside (0, 1), CDM groups the DM-RS type does
+ * not allow, no DM-RS symbol or one outside the allocation -- for sizes the structures cannot hold (an unknown modulation, more
+ * than 275 PRB or 4 layers, symbols beyond the slot, a UCI part above 1706 bits, alpha or a beta offset that is negative or not
+ * finite), and where the reference's unsigned subtractions would wrap: ceil(alpha N_RE) below the RE HARQ-ACK took, or more UCI RE
+ * than the allocation has. */
+int nrphy_ul_sch_info(const nrphy_ulsch_info_cfg_t* cfg, nrphy_ulsch_info_t* out);
+
+/* ---- receive side: PUSCH processor ------------------------------------------------------------------------------------------------
+ * Replaces pusch_processor::process (R/include/srsran/phy/upper/channel_processors/pusch/pusch_processor.h; impl
+ * R/lib/phy/upper/channel_processors/pusch/pusch_processor_impl.cpp:115-298) and pusch_pdu_validator::is_valid: from the received
+ * grid to the transport block and its CRC verdict, the HARQ-ACK and CSI part 1 payloads with their status, and the
+ * channel_state_information record -- nrphy_pusch_chest_run, nrphy_pusch_demod_run, nrphy_ulsch_demux_run, nrphy_uci_decoder_run
+ * and nrphy_pusch_decode_batch with the configurations nrphy_pusch_proc_derive gives, on one stream with no host step, followed
+ * by one launch that writes a nrphy_pusch_result_t per PDU.  Not covered, and refused: CSI part 2 (its size depends on the
+ * decoded part 1; the two-plan route of nrphy_ulsch_demux_plan_create stays), the EVM and the EVM-based SINR, DM-RS type 2.
+ * Transform precoding is never enabled, as in the reference's processor. */
+#define NRPHY_PUSCH_SINR_CHANNEL_ESTIMATOR 0u /* channel_state_information::sinr_type */
+#define NRPHY_PUSCH_SINR_POST_EQUALIZATION 1u
+#define NRPHY_PUSCH_SINR_EVM 2u               /* refused */
+typedef struct nrphy_pusch_pdu {              /* pusch_processor::pdu_t */
+  uint32_t numerology, slot_index;            /* slot within the frame: < 10 * 2^numerology */
+  uint32_t rnti, n_id;                        /* data scrambling: c_init = rnti * 2^15 + n_id */
+  uint32_t scrambling_id, n_scid;             /* DM-RS */
+  uint32_t modulation;                        /* mcs_descr: NRPHY_MOD_QPSK .. NRPHY_MOD_QAM256 */
+  float    target_code_rate;                  /* mcs_descr: R x 1024 */
+  uint32_t has_codeword;                      /* 0: no UL-SCH (tb_size_bytes must be 0 then); 1: rv, ldpc_base_graph, new_data hold */
+  uint32_t rv, ldpc_base_graph, new_data;
+  uint32_t tb_size_bytes;                     /* the size of `data` */
+  uint32_t tbs_lbrm_bytes;                    /* > 0 */
+  uint32_t nof_harq_ack, nof_csi_part1;       /* uci: payload bits, 0 = none */
+  uint32_t nof_csi_part2_entries;             /* uci.csi_part2_size.entries.size(): must be 0 */
+  float    alpha_scaling, beta_offset_harq_ack, beta_offset_csi_part1, beta_offset_csi_part2;
+  uint32_t start_symbol_index, nof_symbols;
+  uint32_t dmrs_type;                         /* must be 1 */
+  uint32_t dmrs_symbol_mask;
+  uint32_t nof_cdm_groups_without_data;       /* must be 2 */
+  uint32_t nof_tx_layers;                     /* 1 or 2 */
+  uint32_t nof_rx_ports;                      /* 1..4 */
+  uint32_t rx_ports[NRPHY_MAX_PORTS];         /* grid port of receive port i */
+  uint32_t dc_position;                       /* grid subcarrier of DC, or NRPHY_PUSCH_CHEST_NO_DC */
+  uint32_t reserved_;
+  uint64_t prb_mask[NRPHY_PRB_WORDS];         /* freq_alloc.get_prb_mask(bwp_start_rb, bwp_size_rb): allocated PRBs, grid-indexed */
+} nrphy_pusch_pdu_t;
+typedef struct nrphy_pusch_proc_options {     /* pusch_processor_impl::configuration and the factory's choices */
+  uint32_t dec_nof_iterations;                /* > 0 */
+  uint32_t dec_enable_early_stop;             /* 0 or 1 */
+  uint32_t csi_sinr_calc_method;              /* NRPHY_PUSCH_SINR_CHANNEL_ESTIMATOR or _POST_EQUALIZATION */
+  uint32_t equalizer;                         /* NRPHY_EQ_ZF, NRPHY_EQ_MMSE (one layer only) */
+} nrphy_pusch_proc_options_t;
+/* The configurations of the five stages for one PDU.  uci[]: the messages present, HARQ-ACK before CSI part 1 (nof_uci of them). */
+typedef struct nrphy_pusch_proc_derived {
+  nrphy_ulsch_info_t        info;
+  nrphy_pusch_chest_cfg_t   chest;            /* scaling = (float)10^(3 / 20) for two CDM groups without data */
+  nrphy_pusch_demod_cfg_t   demod;
+  nrphy_ulsch_demux_cfg_t   demux;            /* read only when nof_uci > 0: without UCI the UL-SCH stream is the demodulator's output */
+  nrphy_uci_decoder_cfg_t   uci[2];
+  nrphy_pusch_decoder_cfg_t decoder;          /* read only when has_decoder: nref from tbs_lbrm_bytes and the codeblocks of ldpc_base_graph */
+  uint32_t                  nof_uci, has_decoder;
+  uint32_t                  codeword_bits;    /* soft bits the demodulator writes */
+  uint32_t                  nof_sch_bits;     /* soft bits of the UL-SCH stream (the demultiplexer's, or codeword_bits without UCI) */
+} nrphy_pusch_proc_derived_t;
+typedef struct nrphy_pusch_result {           /* one per PDU */
+  uint32_t has_sch;                           /* the PDU has a codeword; the five fields below are 0 without one */
+  uint32_t tb_crc_ok, nof_codeblocks, nof_codeblocks_ok, ldpc_iterations_sum, ldpc_iterations_max;
+  uint32_t harq_ack_status, csi_part1_status; /* NRPHY_UCI_STATUS_*; UNKNOWN when the PDU carries none */
+  uint32_t nof_harq_ack, nof_csi_part1;       /* payload bits, one per byte ... */
+  uint64_t harq_ack_offset, csi_part1_offset; /* ... at these bytes of d_uci_bits */
+  /* channel_state_information (channel_estimate::get_channel_state_information over layer 0 of the PDU's receive ports) */
+  float    sinr_dB;                           /* the one of the next two that csi_sinr_calc_method selects */
+  float    sinr_ch_estimator_dB, sinr_post_eq_dB;
+  float    epre_dB, rsrp_dB;
+  float    time_alignment_s;                  /* of the receive port with the best SNR */
+  float    cfo_hz;                            /* of that port; 0 with has_cfo = 0 */
+  uint32_t has_cfo;                           /* 0 with a single DM-RS symbol: the reference's optional is empty */
+  uint32_t has_evm;                           /* always 0 */
+  float    evm;                               /* always 0 */
+} nrphy_pusch_result_t;
+typedef struct nrphy_pusch_proc_plan nrphy_pusch_proc_plan_t;
+/* NRPHY_OK, or NRPHY_ERR_ARGUMENT for what pusch_processor_validator_impl and assert_pdu refuse and for what any of the five stage
+ * validators refuses for the derived configuration: a DM-RS type other than 1; CDM groups without data other than 2; layers outside
+ * 1..2; tbs_lbrm_bytes 0; dc_position neither NRPHY_PUSCH_CHEST_NO_DC nor inside the grid; no rx port, more than 4, one outside the
+ * grid or repeated; PRBs beyond the grid or none; symbols beyond the slot; a DM-RS symbol outside the allocation or none; a
+ * modulation outside QPSK..256-QAM; rv above 3, a base graph other than 1 or 2, a codeword without bytes or bytes without a
+ * codeword; sizes nrphy_ul_sch_info refuses, UCI soft bits the placement or the UCI decoder cannot take, an UL-SCH the decoder
+ * cannot take; a CSI part 2 description; a PDU with neither a codeword nor a UCI bit; no decoder iteration; csi_sinr_calc_method
+ * NRPHY_PUSCH_SINR_EVM or unknown; an unknown equaliser or MMSE with two layers.  No device work. */
+int nrphy_pusch_proc_validate(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_proc_options_t* options, uint32_t grid_nof_ports,
+                              uint32_t grid_nof_subc);
+/* The stage configurations of a PDU nrphy_pusch_proc_validate accepts (the grid only bounds the checks).  No device work. */
+int nrphy_pusch_proc_derive(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_proc_options_t* options, uint32_t grid_nof_ports,
+                            uint32_t grid_nof_subc, nrphy_pusch_proc_derived_t* out);
+/* The sizes of the PDU's HARQ blocks, those nrphy_pusch_decoder_sizes(cfg, 1, ...) gives for the derived decoder configuration;
+ * both 0 for a PDU without codeword.  No device work: a caller lays out its arena before it makes a plan. */
+int nrphy_pusch_proc_harq_bytes(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_proc_options_t* options, uint64_t* soft_bytes,
+                                uint64_t* state_bytes);
+/* n PDUs over a batch of grids [nof_grids][grid_nof_ports][14][grid_nof_subc] cbf16; PDU i reads grid grid_index[i].  Each PDU
+ * with a codeword owns one soft block at byte harq_soft_offset[i] and one state block at byte harq_state_offset[i] (a multiple of
+ * 64) of the caller's arena d_harq, which the caller keys by (rnti, HARQ process) across slots; the decoder's state layout is per
+ * batch, not per transport block, so the plan decodes each PDU as a batch of one.  Its transport block goes to byte tb_offset[i]
+ * of d_tb, its UCI payload to byte uci_offset[i] of d_uci_bits: nof_harq_ack bytes, then nof_csi_part1 bytes, one bit each.  The
+ * three HARQ / transport-block arrays are not read for a PDU without codeword and may be NULL when no PDU has one; uci_offset
+ * likewise for UCI.  Validates every PDU, derives everything, creates the stage plans, prepares the decoders and allocates the
+ * plan's workspace: channel estimates, noise variances, measurements, codeword soft bits, the demultiplexed streams, SINR,
+ * decoder results and scratch (blocking). */
+int nrphy_pusch_proc_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, const nrphy_pusch_proc_options_t* options,
+                                 const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
+                                 const uint64_t* harq_soft_offset, const uint64_t* harq_state_offset, const uint64_t* tb_offset,
+                                 const uint64_t* uci_offset, nrphy_pusch_proc_plan_t** plan);
+int nrphy_pusch_proc_plan_destroy(nrphy_pusch_proc_plan_t* plan);
+int nrphy_pusch_proc_plan_harq_bytes(const nrphy_pusch_proc_plan_t* plan, uint32_t i, uint64_t* soft_bytes, uint64_t* state_bytes);
+/* d_result: [n], 8-byte aligned.  d_harq (64-byte aligned), d_tb (both may be NULL when no PDU has a codeword), d_uci_bits (may be
+ * NULL when no PDU has UCI).  The launch
+ * order is the hand-written chain's: estimator; demodulator; demultiplexer, when a PDU of the plan has UCI; UCI decoder;
+ * transport-block decoders, PDU after PDU; the result kernel, one wavefront per PDU, no atomics and no scratch, every sum in a
+ * fixed order.  Asynchronous on `stream`; allocates nothing and touches no host memory (capturable; two runs give identical
+ * bytes).  Runs of one plan must be ordered: the plan owns its workspace. */
+int nrphy_pusch_proc_run(nrphy_pusch_proc_plan_t* plan, const void* d_grid, void* d_harq, uint8_t* d_tb, uint8_t* d_uci_bits,
+                         nrphy_pusch_result_t* d_result, void* stream);
+/* One PDU from and to host memory (blocking, on the GPU): grid [grid_nof_ports][14][grid_nof_subc] cbf16; harq_soft and harq_state
+ * (the sizes of nrphy_pusch_proc_harq_bytes; NULL without codeword) are read and written, so a retransmission finds what the
+ * transmission before it left; tb [tb_size_bytes] and uci_bits [nof_harq_ack + nof_csi_part1] may be NULL where the PDU has none.
+ * Makes and releases a plan inside the call. */
+int nrphy_pusch_proc_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_proc_options_t* options, const void* grid,
+                          uint32_t grid_nof_ports, uint32_t grid_nof_subc, int8_t* harq_soft, uint8_t* harq_state, uint8_t* tb,
+                          uint8_t* uci_bits, nrphy_pusch_result_t* result);
+
 
 #ifdef __cplusplus
 }

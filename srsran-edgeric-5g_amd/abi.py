@@ -375,6 +375,105 @@ def make_uci_decoder(message_length, llr_length, modulation=2):
     return c
 
 
+class UlschInfoCfg(C.Structure):
+    """nrphy_ulsch_info_cfg_t (ulsch_configuration)."""
+    _fields_ = [("tbs_bits", C.c_uint32), ("modulation", C.c_uint32), ("target_code_rate", C.c_float),
+                ("nof_harq_ack_bits", C.c_uint32), ("nof_csi_part1_bits", C.c_uint32), ("nof_csi_part2_bits", C.c_uint32),
+                ("alpha_scaling", C.c_float), ("beta_offset_harq_ack", C.c_float), ("beta_offset_csi_part1", C.c_float),
+                ("beta_offset_csi_part2", C.c_float), ("nof_rb", C.c_uint32), ("start_symbol_index", C.c_uint32),
+                ("nof_symbols", C.c_uint32), ("dmrs_type", C.c_uint32), ("dmrs_symbol_mask", C.c_uint32),
+                ("nof_cdm_groups_without_data", C.c_uint32), ("nof_layers", C.c_uint32), ("contains_dc", C.c_uint32)]
+
+
+class UlschInfo(C.Structure):
+    """nrphy_ulsch_info_t (ulsch_information)."""
+    _fields_ = [(n, C.c_uint32) for n in (
+        "has_sch", "tb_crc_bits", "base_graph", "nof_cb", "nof_filler_bits_per_cb", "lifting_size", "nof_bits_per_cb",
+        "nof_ul_sch_bits", "nof_harq_ack_bits", "nof_harq_ack_rvd", "nof_csi_part1_bits", "nof_csi_part2_bits",
+        "nof_harq_ack_re", "nof_csi_part1_re", "nof_csi_part2_re", "nof_dc_overlap_bits")]
+
+
+def make_ulsch_info_cfg(**fields):
+    """An UlschInfoCfg from keyword fields (those not given are 0)."""
+    c = UlschInfoCfg()
+    for k, v in fields.items():
+        assert hasattr(c, k), k
+        setattr(c, k, v)
+    return c
+
+
+PUSCH_SINR_CHANNEL_ESTIMATOR, PUSCH_SINR_POST_EQUALIZATION, PUSCH_SINR_EVM = 0, 1, 2  # NRPHY_PUSCH_SINR_*
+
+
+class PuschPdu(C.Structure):
+    """nrphy_pusch_pdu_t (pusch_processor::pdu_t)."""
+    _fields_ = [("numerology", C.c_uint32), ("slot_index", C.c_uint32), ("rnti", C.c_uint32), ("n_id", C.c_uint32),
+                ("scrambling_id", C.c_uint32), ("n_scid", C.c_uint32), ("modulation", C.c_uint32), ("target_code_rate", C.c_float),
+                ("has_codeword", C.c_uint32), ("rv", C.c_uint32), ("ldpc_base_graph", C.c_uint32), ("new_data", C.c_uint32),
+                ("tb_size_bytes", C.c_uint32), ("tbs_lbrm_bytes", C.c_uint32), ("nof_harq_ack", C.c_uint32),
+                ("nof_csi_part1", C.c_uint32), ("nof_csi_part2_entries", C.c_uint32), ("alpha_scaling", C.c_float),
+                ("beta_offset_harq_ack", C.c_float), ("beta_offset_csi_part1", C.c_float), ("beta_offset_csi_part2", C.c_float),
+                ("start_symbol_index", C.c_uint32), ("nof_symbols", C.c_uint32), ("dmrs_type", C.c_uint32),
+                ("dmrs_symbol_mask", C.c_uint32), ("nof_cdm_groups_without_data", C.c_uint32), ("nof_tx_layers", C.c_uint32),
+                ("nof_rx_ports", C.c_uint32), ("rx_ports", C.c_uint32 * MAX_PORTS), ("dc_position", C.c_uint32),
+                ("reserved_", C.c_uint32), ("prb_mask", C.c_uint64 * PRB_WORDS)]
+
+
+class PuschProcOptions(C.Structure):
+    """nrphy_pusch_proc_options_t (pusch_processor_impl::configuration and the factory's choices)."""
+    _fields_ = [("dec_nof_iterations", C.c_uint32), ("dec_enable_early_stop", C.c_uint32), ("csi_sinr_calc_method", C.c_uint32),
+                ("equalizer", C.c_uint32)]
+
+
+class PuschProcDerived(C.Structure):
+    """nrphy_pusch_proc_derived_t: the stage configurations of one PDU."""
+    _fields_ = [("info", UlschInfo), ("chest", PuschChestCfg), ("demod", PuschDemodCfg), ("demux", UlschDemuxCfg),
+                ("uci", UciDecoderCfg * 2), ("decoder", PuschDecoderCfg), ("nof_uci", C.c_uint32), ("has_decoder", C.c_uint32),
+                ("codeword_bits", C.c_uint32), ("nof_sch_bits", C.c_uint32)]
+
+
+class PuschResult(C.Structure):
+    """nrphy_pusch_result_t: one per PDU."""
+    _fields_ = [("has_sch", C.c_uint32), ("tb_crc_ok", C.c_uint32), ("nof_codeblocks", C.c_uint32), ("nof_codeblocks_ok", C.c_uint32),
+                ("ldpc_iterations_sum", C.c_uint32), ("ldpc_iterations_max", C.c_uint32), ("harq_ack_status", C.c_uint32),
+                ("csi_part1_status", C.c_uint32), ("nof_harq_ack", C.c_uint32), ("nof_csi_part1", C.c_uint32),
+                ("harq_ack_offset", C.c_uint64), ("csi_part1_offset", C.c_uint64), ("sinr_dB", C.c_float),
+                ("sinr_ch_estimator_dB", C.c_float), ("sinr_post_eq_dB", C.c_float), ("epre_dB", C.c_float), ("rsrp_dB", C.c_float),
+                ("time_alignment_s", C.c_float), ("cfo_hz", C.c_float), ("has_cfo", C.c_uint32), ("has_evm", C.c_uint32),
+                ("evm", C.c_float)]
+
+
+def make_pusch_pdu(*, prbs, modulation=2, target_code_rate=449.0, numerology=0, slot_index=0, rnti=1, n_id=0, scrambling_id=0,
+                   n_scid=0, tb_size_bytes=0, rv=0, ldpc_base_graph=1, new_data=1, tbs_lbrm_bytes=3168, nof_harq_ack=0,
+                   nof_csi_part1=0, nof_csi_part2_entries=0, alpha_scaling=1.0, beta_offset_harq_ack=20.0, beta_offset_csi_part1=6.25,
+                   beta_offset_csi_part2=6.25, start_symbol=0, nof_symbols=14, dmrs_type=1, dmrs_symbols=(2,),
+                   nof_cdm_groups_without_data=2, nof_layers=1, rx_ports=(0,), dc_position=None, has_codeword=None):
+    """A PuschPdu from plain values (prbs: grid-indexed PRB numbers; dc_position None: no DC; has_codeword None: by tb_size_bytes)."""
+    p = PuschPdu()
+    p.numerology, p.slot_index, p.rnti, p.n_id, p.scrambling_id, p.n_scid = numerology, slot_index, rnti, n_id, scrambling_id, n_scid
+    p.modulation, p.target_code_rate = modulation, target_code_rate
+    p.has_codeword = int(tb_size_bytes != 0) if has_codeword is None else int(has_codeword)
+    p.rv, p.ldpc_base_graph, p.new_data, p.tb_size_bytes, p.tbs_lbrm_bytes = rv, ldpc_base_graph, new_data, tb_size_bytes, tbs_lbrm_bytes
+    p.nof_harq_ack, p.nof_csi_part1, p.nof_csi_part2_entries = nof_harq_ack, nof_csi_part1, nof_csi_part2_entries
+    p.alpha_scaling, p.beta_offset_harq_ack = alpha_scaling, beta_offset_harq_ack
+    p.beta_offset_csi_part1, p.beta_offset_csi_part2 = beta_offset_csi_part1, beta_offset_csi_part2
+    p.start_symbol_index, p.nof_symbols = start_symbol, nof_symbols
+    p.dmrs_type, p.dmrs_symbol_mask = dmrs_type, sum(1 << l for l in set(dmrs_symbols))
+    p.nof_cdm_groups_without_data, p.nof_tx_layers, p.nof_rx_ports = nof_cdm_groups_without_data, nof_layers, len(rx_ports)
+    for i, port in enumerate(rx_ports[:MAX_PORTS]):
+        p.rx_ports[i] = port
+    p.dc_position = PUSCH_CHEST_NO_DC if dc_position is None else dc_position
+    for i, w in enumerate(prb_mask_words(prbs)):
+        p.prb_mask[i] = w
+    return p
+
+
+def make_pusch_proc_options(dec_nof_iterations=10, dec_enable_early_stop=1, csi_sinr_calc_method=PUSCH_SINR_CHANNEL_ESTIMATOR,
+                            equalizer=EQ_ZF):
+    """A PuschProcOptions."""
+    return PuschProcOptions(dec_nof_iterations, dec_enable_early_stop, csi_sinr_calc_method, equalizer)
+
+
 class GridRe(C.Structure):
     """nrphy_grid_re_t: one resource element written from the host into a device grid."""
     _fields_ = [("port", C.c_uint16), ("symbol", C.c_uint16), ("subc", C.c_uint32), ("value", C.c_uint32)]
@@ -881,6 +980,16 @@ def declare(lib, prefix="nrphy_"):
     sig("ulsch_demux_run", i32, vp, vp, vp, vp, vp, vp, vp)
     sig("ulsch_demultiplex_host", i32, vp, P(UlschDemuxCfg), vp, vp, vp, vp, vp)
     sig("pusch_decode_codeblock_host", i32, vp, P(LdpcRateDematcherCfg), u32, u32, C.c_float, vp, vp, i32, u8p, P(u32))
+    sig("ul_sch_info", i32, P(UlschInfoCfg), P(UlschInfo))
+    sig("pusch_proc_validate", i32, P(PuschPdu), P(PuschProcOptions), u32, u32)
+    sig("pusch_proc_derive", i32, P(PuschPdu), P(PuschProcOptions), u32, u32, P(PuschProcDerived))
+    sig("pusch_proc_harq_bytes", i32, P(PuschPdu), P(PuschProcOptions), P(u64), P(u64))
+    sig("pusch_proc_plan_create", i32, vp, u32, P(PuschPdu), P(PuschProcOptions), P(u32), u32, u32, u32, P(u64), P(u64), P(u64), P(u64),
+        P(vp))
+    sig("pusch_proc_plan_destroy", i32, vp)
+    sig("pusch_proc_plan_harq_bytes", i32, vp, u32, P(u64), P(u64))
+    sig("pusch_proc_run", i32, vp, vp, vp, vp, vp, vp, vp)
+    sig("pusch_proc_host", i32, vp, P(PuschPdu), P(PuschProcOptions), vp, u32, u32, vp, vp, vp, vp, P(PuschResult))
     return lib
 
 
@@ -935,4 +1044,7 @@ ABI_SYMBOLS = [
     "nrphy_pf2_validate", "nrphy_pf2_sizes", "nrphy_pf2_plan_create", "nrphy_pf2_plan_destroy", "nrphy_pf2_run", "nrphy_pf2_host",
     "nrphy_srs_validate", "nrphy_srs_info", "nrphy_srs_plan_create", "nrphy_srs_plan_destroy", "nrphy_srs_run", "nrphy_srs_host",
     "nrphy_srs_sequence_host",
+    "nrphy_ul_sch_info", "nrphy_pusch_proc_validate", "nrphy_pusch_proc_derive", "nrphy_pusch_proc_harq_bytes",
+    "nrphy_pusch_proc_plan_create", "nrphy_pusch_proc_plan_destroy", "nrphy_pusch_proc_plan_harq_bytes", "nrphy_pusch_proc_run",
+    "nrphy_pusch_proc_host",
 ]

@@ -27,4 +27,9 @@ int ldpc_decode_batch(nrphy_ctx_t* ctx, const nrphy_ldpc_decoder_cfg_t* cfg, uin
                       const uint8_t* d_skip, uint8_t* d_ok_flags, bool crc_at_end, void* d_scratch, void* stream,
                       uint32_t expected_extent = 0);
 
+// The HARQ block sizes and the codeblock count nrphy_pusch_decoder_sizes gives, without a context (pusch_decoder_host.cpp):
+// false for a configuration the decoder refuses.  No device work.
+bool pusch_decoder_harq_sizes(const nrphy_pusch_decoder_cfg_t& cfg, uint32_t n_tb, uint64_t* soft_bytes_per_tb, uint64_t* state_bytes,
+                              uint32_t* nof_codeblocks);
+
 #pragma GCC visibility pop

@@ -712,6 +712,28 @@ struct UlschLaunch {
 };
 hipError_t launch_ulsch_demux(const UlschLaunch& p, hipStream_t stream);
 
+// ---- PUSCH processor: the result kernel (pusch_proc_kernels.hip) ---------------------------------------------------------------
+// One descriptor per PDU: where the stages of the run left what its record is made of.
+constexpr uint32_t PUSCH_PROC_NO_STATUS = 0xFFFFFFFFu;
+struct PuschProcDesc {
+  uint32_t nof_rx_ports;
+  uint32_t has_sch, nof_codeblocks;
+  uint32_t harq_status, csi1_status;     // index into the UCI decoder's statuses, PUSCH_PROC_NO_STATUS without that part
+  uint32_t nof_harq_ack, nof_csi_part1;
+  uint32_t sinr_method;                  // NRPHY_PUSCH_SINR_*
+  uint64_t harq_ack_offset, csi_part1_offset;
+};
+struct PuschProcLaunch {
+  const PuschProcDesc*            desc;
+  const nrphy_pusch_chest_meas_t* meas;    // [n][NRPHY_MAX_PORTS][NRPHY_PUSCH_CHEST_MAX_LAYERS]
+  const float*                    sinr_db; // [n] post-equalisation
+  const uint32_t*                 dec;     // [n][4] the decoder's result words
+  const uint32_t*                 status;  // the UCI decoder's statuses
+  nrphy_pusch_result_t*           result;  // [n]
+  uint32_t                        n;
+};
+hipError_t launch_pusch_proc_result(const PuschProcLaunch& p, hipStream_t stream);
+
 // ---- PDCCH and SS/PBCH block ("next" row: other downlink grid writers) --------------------------------------------------
 // One wavefront per DCI.  Offsets index the launch's shared tables: tab16 (gather table of the polar input, PRB list),
 // bytes (payload bits, one per byte), words (CRC weights), weights (floats).

@@ -81,6 +81,19 @@ nrphy_ldpc_decoder_cfg_t pusch_ldpc_cfg(const nrphy_pusch_decoder_cfg_t& cfg, co
 }
 } // namespace
 
+bool pusch_decoder_harq_sizes(const nrphy_pusch_decoder_cfg_t& cfg, uint32_t n_tb, uint64_t* soft_bytes_per_tb, uint64_t* state_bytes,
+                              uint32_t* nof_codeblocks)
+{
+  PuschLayout l;
+  if (!pusch_layout(cfg, n_tb, l)) {
+    return false;
+  }
+  *soft_bytes_per_tb = (uint64_t)l.d.nof_codeblocks * l.d.full_length;
+  *state_bytes       = l.state_bytes;
+  *nof_codeblocks    = l.d.nof_codeblocks;
+  return true;
+}
+
 extern "C" int nrphy_pusch_decoder_prepare(nrphy_ctx_t* ctx, const nrphy_pusch_decoder_cfg_t* cfg)
 {
   PuschLayout l;

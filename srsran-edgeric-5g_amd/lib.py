@@ -471,6 +471,25 @@ class Context:
         m = [[meas[i * abi.PUSCH_CHEST_MAX_LAYERS + l] for l in range(abi.PUSCH_CHEST_MAX_LAYERS)] for i in range(cfg.nof_rx_ports)]
         return ce, nv, m
 
+    def pusch_proc_host(self, pdu, options, grid, harq_soft=None, harq_state=None):
+        """pusch_processor::process for one PDU: grid [ports][14][subc] raw cbf16 words -> (abi.PuschResult, transport block bytes,
+        UCI payload bits: HARQ-ACK then CSI part 1, one per byte).  harq_soft / harq_state: the PDU's HARQ blocks (int8 / uint8
+        arrays of pusch_proc_harq_bytes(pdu, options)), read and written in place; fresh zeroed ones when None."""
+        grid = np.ascontiguousarray(grid, dtype=np.uint32)
+        soft_bytes, state_bytes = pusch_proc_harq_bytes(pdu, options)
+        soft = np.zeros(soft_bytes, np.int8) if harq_soft is None else harq_soft
+        state = np.zeros(state_bytes, np.uint8) if harq_state is None else harq_state
+        if soft.size != soft_bytes or state.size != state_bytes or not (soft.flags.c_contiguous and state.flags.c_contiguous):
+            raise ValueError("HARQ blocks must be contiguous arrays of %d and %d bytes" % (soft_bytes, state_bytes))
+        tb = np.zeros(pdu.tb_size_bytes, np.uint8)
+        uci = np.zeros(pdu.nof_harq_ack + pdu.nof_csi_part1, np.uint8)
+        result = abi.PuschResult()
+        _check(self.lib.nrphy_pusch_proc_host(self.handle, C.byref(pdu), C.byref(options), grid.ctypes.data, grid.shape[0],
+                                              grid.shape[-1], soft.ctypes.data if soft_bytes else None,
+                                              state.ctypes.data if state_bytes else None, tb.ctypes.data if tb.size else None,
+                                              uci.ctypes.data if uci.size else None, C.byref(result)), "nrphy_pusch_proc_host")
+        return result, tb, uci
+
     def prach_detect_host(self, cfg, symbols, with_metric=False):
         """prach_detector::detect for one occasion: symbols [ports][symbols][L_RA] complex64 -> (abi.PrachResult, the 64
         abi.PrachPreamble slots, and with_metric the metric windows [64][window width] f32 or None)."""
@@ -995,6 +1014,77 @@ class UlschDemuxPlan:
             self.close()
         except Exception:
             pass
+
+
+class PuschProcPlan:
+    """nrphy_pusch_proc_plan: PUSCH PDUs over a batch of received grids; run() goes from the grids to the transport blocks, the
+    UCI payloads and one abi.PuschResult per PDU on one stream.  The plan owns every buffer between the stages; the caller owns
+    the HARQ arena, the transport blocks, the UCI payload bytes and the results."""
+
+    def __init__(self, ctx, pdus, options, grid_indices, nof_grids, nof_ports, nof_subc, harq_soft_offsets=None,
+                 harq_state_offsets=None, tb_offsets=None, uci_offsets=None):
+        self.ctx = ctx
+        n = len(pdus)
+        arr = (abi.PuschPdu * n)(*pdus)
+        gidx = (C.c_uint32 * n)(*grid_indices)
+        offs = [None if o is None else (C.c_uint64 * n)(*o) for o in (harq_soft_offsets, harq_state_offsets, tb_offsets, uci_offsets)]
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_pusch_proc_plan_create(ctx.handle, n, arr, C.byref(options), gidx, nof_grids, nof_ports, nof_subc, *offs,
+                                                    C.byref(h)), "nrphy_pusch_proc_plan_create")
+        self.handle = h
+        self.n = n
+
+    def harq_bytes(self, i):
+        """(soft bytes, state bytes) of PDU i's HARQ blocks; zeros without codeword."""
+        soft, state = C.c_uint64(0), C.c_uint64(0)
+        _check(self.ctx.lib.nrphy_pusch_proc_plan_harq_bytes(self.handle, i, C.byref(soft), C.byref(state)),
+               "nrphy_pusch_proc_plan_harq_bytes")
+        return int(soft.value), int(state.value)
+
+    def run(self, d_grid, d_harq, d_tb, d_uci_bits, d_result, stream=None):
+        """d_harq: the HARQ arena (uint8 / int8); d_tb, d_uci_bits: uint8; d_result: [n] x sizeof(abi.PuschResult) bytes."""
+        _check(self.ctx.lib.nrphy_pusch_proc_run(self.handle, _dptr(d_grid), _dptr(d_harq), _dptr(d_tb), _dptr(d_uci_bits),
+                                                 _dptr(d_result), _stream(stream)), "nrphy_pusch_proc_run")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.nrphy_pusch_proc_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ulsch_info(cfg):
+    """nrphy_ul_sch_info: the abi.UlschInfo of an abi.UlschInfoCfg, or None for a refused configuration (host only)."""
+    out = abi.UlschInfo()
+    if int(load().nrphy_ul_sch_info(C.byref(cfg), C.byref(out))) != abi.OK:
+        return None
+    return out
+
+
+def pusch_proc_validate(pdu, options, grid_nof_ports, grid_nof_subc):
+    """nrphy_pusch_proc_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_pusch_proc_validate(C.byref(pdu), C.byref(options), grid_nof_ports, grid_nof_subc))
+
+
+def pusch_proc_derive(pdu, options, grid_nof_ports, grid_nof_subc):
+    """nrphy_pusch_proc_derive: the abi.PuschProcDerived of a PDU, or None for a refused one (host only)."""
+    out = abi.PuschProcDerived()
+    if int(load().nrphy_pusch_proc_derive(C.byref(pdu), C.byref(options), grid_nof_ports, grid_nof_subc, C.byref(out))) != abi.OK:
+        return None
+    return out
+
+
+def pusch_proc_harq_bytes(pdu, options):
+    """nrphy_pusch_proc_harq_bytes: (soft bytes, state bytes) of the PDU's HARQ blocks (host only)."""
+    soft, state = C.c_uint64(0), C.c_uint64(0)
+    _check(load().nrphy_pusch_proc_harq_bytes(C.byref(pdu), C.byref(options), C.byref(soft), C.byref(state)),
+           "nrphy_pusch_proc_harq_bytes")
+    return int(soft.value), int(state.value)
 
 
 def ulsch_demux_validate(cfg):
