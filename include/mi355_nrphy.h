@@ -1952,6 +1952,110 @@ int nrphy_pusch_proc_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* pdu, const 
                           uint8_t* uci_bits, nrphy_pusch_result_t* result);
 
 
+/* ---- receive side: OFDM demodulation of a run of symbols, from float or int16 samples --------------------------------------------
+ * puxch_processor_impl::process_symbol (R/lib/phy/lower/processors/uplink/puxch/puxch_processor_impl.cpp:30-81) demodulates every
+ * port of ONE symbol into the slot's grid as soon as its samples are in.  nrphy_ofdm_demod_run with a range: the layout is the
+ * same -- d_iq [grid][port][slot_stride] samples, d_grid [grid][port][14][12 * bw_rb] cbf16 -- but only symbols [first_symbol,
+ * first_symbol + nof_symbols) of every (grid, port) are read and only their grid rows are written; the samples of the other
+ * symbols need not be valid.  NRPHY_IQ_CI16: a sample is two int16 (re, im), 4 bytes, at the same sample index, and each component
+ * becomes float(x) * gain with gain = 1.0f / iq_scale formed once in single precision, the product rounded on its own, as
+ * srsvec::convert(span<const int16_t>, float scale, span<cf_t>) does (R/lib/srsvec/conversion.cpp:67-129); the radio's samples
+ * cross PCIe at 4 bytes.  iq_scale is ignored for NRPHY_IQ_CF32.  NRPHY_ERR_ARGUMENT, with no launch, for nof_symbols == 0 or a
+ * range beyond the slot's symbols (12 with extended cyclic prefix), an unknown iq_format, for ci16 an iq_scale that is not positive
+ * and finite, and a window offset not below the shortest cyclic prefix; nof_grids == 0 is NRPHY_OK with no launch.  Asynchronous
+ * on `stream`. */
+#define NRPHY_IQ_CF32 0u
+#define NRPHY_IQ_CI16 1u
+int nrphy_ofdm_demod_symbols(nrphy_ofdm_plan_t* plan, uint32_t nof_grids, const void* d_iq, uint32_t iq_format, float iq_scale,
+                             const uint32_t* d_slot_index, uint32_t first_symbol, uint32_t nof_symbols, uint32_t window_offset,
+                             void* d_grid, void* stream);
+
+/* ---- the uplink slot pipeline: baseband samples to PUSCH, PUCCH and SRS results on one device-resident grid ----------------------
+ * The receive-side twin of nrphy_dl_slots_*.  What the reference does per uplink slot -- the lower PHY demodulates symbol after
+ * symbol into the slot's grid (puxch_processor_impl::process_symbol, puxch_processor_impl.cpp:30-97) and the upper PHY runs
+ * process_pusch, process_pucch and process_srs on that grid (R/lib/phy/upper/uplink_processor_impl.cpp:86-170) -- with the grid
+ * staying in HBM: per slot the samples go down and the results come up.
+ *
+ * A pool owns `depth` slots, each with a stream, a device grid, pinned sample staging and a device and a pinned result block sized
+ * from the max_* fields.  Everything a slot is asked to do is enqueued on its stream in call order; no call allocates device
+ * memory or waits for the device unless it says so -- except that a receiver call makes its plan with the stand-alone
+ * *_plan_create, which allocates and uploads (blocking), under the context's host lock.  Calls on ONE slot are serialised by the
+ * library (a lock per slot); different slots may be driven from different threads.
+ *
+ *   nrphy_ul_slot_open       a free slot (NRPHY_ERR_CAPACITY when all `depth` are open) for slot subframe_slot_index of the
+ *                            subframe; its grid is zeroed on its stream, so symbols never delivered read as zero
+ *   nrphy_ul_slot_samples    process_symbol for a run of symbols: port_samples[port] is a host span of those symbols' samples
+ *                            (cyclic prefix + dft_size each, back to back) in the pool's format; copied into the pinned staging
+ *                            at the symbols' place (a memcpy on the calling thread), then one host-to-device copy per port and
+ *                            one nrphy_ofdm_demod_symbols launch.  Runs must be contiguous and in order, starting at 0.
+ *   nrphy_ul_slot_load_grid  a host grid replaces the slot's grid; all symbols count as delivered
+ *   nrphy_ul_slot_device_grid / _stream / _symbols_written   split 7.2: the caller runs nrphy_ofh_rx_run or
+ *                            nrphy_ofh_ul_write_grid on the slot's stream into the slot's grid and declares that symbols
+ *                            [0, upto) are there (upto may only grow, up to the symbols a slot has: 12 with extended CP)
+ *   nrphy_ul_slot_pusch      process_pusch for n PDUs: nrphy_pusch_proc_plan_create + _run on the slot's grid and stream, with
+ *                            the caller's HARQ arena (the offsets are those of nrphy_pusch_proc_plan_create)
+ *   nrphy_ul_slot_pf01      process_pucch, formats 0 and 1: nrphy_pucch_run
+ *   nrphy_ul_slot_pf2        process_pucch, format 2: nrphy_pf2_run
+ *   nrphy_ul_slot_srs        process_srs: nrphy_srs_run
+ *   nrphy_ul_slot_finish     once per open: after everything enqueued so far, ONE device-to-host copy brings the slot's result
+ *                            block into pinned memory, then `done(user, status, slot_id)` runs on a thread of the HIP runtime (it
+ *                            must not call HIP or this library except the accessors and nrphy_ul_slot_poll)
+ *   nrphy_ul_slot_poll / _wait / _close   as the downlink's; close waits for what is in flight and destroys the slot's plans
+ *   nrphy_ul_slot_read_grid  blocking: everything enqueued so far, then the grid [nof_ports][14][12 * bw_rb] cbf16 to the host
+ * Each receiver call may come more than once per slot (PDUs arrive one by one): results append in call order, index i of an
+ * accessor counts over all calls of its kind, and totals are bounded by the max_* fields (NRPHY_ERR_CAPACITY).  A receiver call
+ * is accepted only when the last symbol of every allocation it reads has been delivered (else NRPHY_ERR_ARGUMENT), which is what
+ * lets a PUCCH of symbols 0-1 run after the first two symbols.  A PDU the stand-alone plan call refuses gives that call's
+ * status.  NRPHY_ERR_ARGUMENT for use out of order: samples not contiguous, anything after finish except poll, wait, the
+ * accessors, read_grid and close, finish twice, an id that is not open.  A refused call enqueues nothing.
+ *
+ * Accessors (nrphy_ul_slot_pusch_results, _tb, _pusch_uci, _pf01_results, _format2_results, _sounding_results): pointer arithmetic
+ * into the pinned result block, valid from completion until close.  Transport block i starts on a 4-byte boundary and holds zeros
+ * where the CRC failed; the UCI bits of PDU i (_pusch_uci) are nof_harq_ack then nof_csi_part1 bytes, one bit each, and
+ * harq_ack_offset / csi_part1_offset of its result are relative to them, as nrphy_pusch_proc_host gives them.  _format2_results
+ * copies the status and the channel state information of format 2 PUCCH i out and points at its message bits;
+ * _sounding_results are the records of nrphy_ul_slot_srs. */
+typedef struct nrphy_ul_slots nrphy_ul_slots_t;
+typedef void (*nrphy_ul_slot_done_fn)(void* user, int status, uint32_t slot_id);
+typedef struct nrphy_ul_slots_cfg {
+  nrphy_ofdm_config_t ofdm;       /* the lower PHY's demodulator configuration */
+  uint32_t nof_ports;             /* grid ports = receive ports of the radio */
+  uint32_t depth;                 /* slots open at once, 1..64 */
+  uint32_t iq_format;             /* NRPHY_IQ_CF32 / NRPHY_IQ_CI16 */
+  float    iq_scale;              /* ci16 only */
+  uint32_t window_offset;
+  uint32_t max_pusch, max_pucch, max_pf2, max_srs;   /* per slot, all calls together */
+  uint32_t max_tb_bytes, max_uci_bits;               /* per slot, all PUSCH (and PF2 payload) together */
+} nrphy_ul_slots_cfg_t;
+/* d_harq: the caller's HARQ arena on the device (64-byte aligned; NULL if no PUSCH will carry a codeword). */
+int nrphy_ul_slots_create(nrphy_ctx_t* ctx, const nrphy_ul_slots_cfg_t* cfg, void* d_harq, nrphy_ul_slots_t** pool);
+int nrphy_ul_slots_destroy(nrphy_ul_slots_t* pool); /* waits for everything in flight, then frees */
+int nrphy_ul_slots_wait_free(nrphy_ul_slots_t* pool); /* blocks while all `depth` slots are open */
+int nrphy_ul_slot_open(nrphy_ul_slots_t* pool, uint32_t subframe_slot_index, uint32_t* slot_id);
+int nrphy_ul_slot_close(nrphy_ul_slots_t* pool, uint32_t slot_id);
+int nrphy_ul_slot_samples(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t first_symbol, uint32_t nof_symbols,
+                          const void* const* port_samples);
+int nrphy_ul_slot_load_grid(nrphy_ul_slots_t* pool, uint32_t slot_id, const void* grid);
+void* nrphy_ul_slot_device_grid(nrphy_ul_slots_t* pool, uint32_t slot_id);
+void* nrphy_ul_slot_stream(nrphy_ul_slots_t* pool, uint32_t slot_id);
+int nrphy_ul_slot_symbols_written(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t upto);
+int nrphy_ul_slot_pusch(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pusch_pdu_t* pdus,
+                        const nrphy_pusch_proc_options_t* options, const uint64_t* harq_soft_offset, const uint64_t* harq_state_offset);
+int nrphy_ul_slot_pf01(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pucch_cfg_t* cfgs);
+int nrphy_ul_slot_pf2(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pf2_cfg_t* cfgs);
+int nrphy_ul_slot_srs(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_srs_cfg_t* cfgs);
+int nrphy_ul_slot_finish(nrphy_ul_slots_t* pool, uint32_t slot_id, nrphy_ul_slot_done_fn done, void* user);
+int nrphy_ul_slot_poll(nrphy_ul_slots_t* pool, uint32_t slot_id);
+int nrphy_ul_slot_wait(nrphy_ul_slots_t* pool, uint32_t slot_id);
+int nrphy_ul_slot_read_grid(nrphy_ul_slots_t* pool, uint32_t slot_id, void* grid);
+const nrphy_pusch_result_t* nrphy_ul_slot_pusch_results(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t* n);
+const uint8_t* nrphy_ul_slot_tb(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t i, uint32_t* nbytes);
+const uint8_t* nrphy_ul_slot_pusch_uci(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t i, uint32_t* nbits);
+const nrphy_pucch_result_t* nrphy_ul_slot_pf01_results(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t* n);
+int nrphy_ul_slot_format2_results(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t i, const uint8_t** message, uint32_t* nbits,
+                              uint32_t* status, nrphy_pf2_csi_t* csi);
+const nrphy_srs_result_t* nrphy_ul_slot_sounding_results(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t* n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -708,6 +708,18 @@ class OfdmConfig(C.Structure):
 DlSlotsCfg._fields_ = [("ofdm", OfdmConfig), ("nof_ports", C.c_uint32), ("depth", C.c_uint32), ("max_tb_bytes", C.c_uint32),
                        ("iq_format", C.c_uint32), ("wire", IqWireCfg)]
 
+IQ_CF32, IQ_CI16 = 0, 1   # NRPHY_IQ_*: the sample format of nrphy_ofdm_demod_symbols and of an uplink slot pool
+
+
+class UlSlotsCfg(C.Structure):
+    """nrphy_ul_slots_cfg_t: the uplink slot pipeline (baseband samples to PUSCH, PUCCH and SRS results on one device-resident grid)."""
+    _fields_ = [("ofdm", OfdmConfig), ("nof_ports", C.c_uint32), ("depth", C.c_uint32), ("iq_format", C.c_uint32),
+                ("iq_scale", C.c_float), ("window_offset", C.c_uint32), ("max_pusch", C.c_uint32), ("max_pucch", C.c_uint32),
+                ("max_pf2", C.c_uint32), ("max_srs", C.c_uint32), ("max_tb_bytes", C.c_uint32), ("max_uci_bits", C.c_uint32)]
+
+
+UL_SLOT_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_uint32)   # nrphy_ul_slot_done_fn
+
 
 def prb_mask_words(prbs):
     """Bit mask words (5 x uint64) with the given PRB indices set."""
@@ -990,6 +1002,31 @@ def declare(lib, prefix="nrphy_"):
     sig("pusch_proc_plan_harq_bytes", i32, vp, u32, P(u64), P(u64))
     sig("pusch_proc_run", i32, vp, vp, vp, vp, vp, vp, vp)
     sig("pusch_proc_host", i32, vp, P(PuschPdu), P(PuschProcOptions), vp, u32, u32, vp, vp, vp, vp, P(PuschResult))
+    sig("ofdm_demod_symbols", i32, vp, u32, vp, u32, C.c_float, vp, u32, u32, u32, vp, vp)
+    sig("ul_slots_create", i32, vp, P(UlSlotsCfg), vp, P(vp))
+    sig("ul_slots_destroy", i32, vp)
+    sig("ul_slots_wait_free", i32, vp)
+    sig("ul_slot_open", i32, vp, u32, P(u32))
+    sig("ul_slot_close", i32, vp, u32)
+    sig("ul_slot_samples", i32, vp, u32, u32, u32, P(vp))
+    sig("ul_slot_load_grid", i32, vp, u32, vp)
+    sig("ul_slot_device_grid", vp, vp, u32)
+    sig("ul_slot_stream", vp, vp, u32)
+    sig("ul_slot_symbols_written", i32, vp, u32, u32)
+    sig("ul_slot_pusch", i32, vp, u32, u32, P(PuschPdu), P(PuschProcOptions), P(u64), P(u64))
+    sig("ul_slot_pf01", i32, vp, u32, u32, P(PucchCfg))
+    sig("ul_slot_pf2", i32, vp, u32, u32, P(Pf2Cfg))
+    sig("ul_slot_srs", i32, vp, u32, u32, P(SrsCfg))
+    sig("ul_slot_finish", i32, vp, u32, vp, vp)
+    sig("ul_slot_poll", i32, vp, u32)
+    sig("ul_slot_wait", i32, vp, u32)
+    sig("ul_slot_read_grid", i32, vp, u32, vp)
+    sig("ul_slot_pusch_results", vp, vp, u32, P(u32))
+    sig("ul_slot_tb", vp, vp, u32, u32, P(u32))
+    sig("ul_slot_pusch_uci", vp, vp, u32, u32, P(u32))
+    sig("ul_slot_pf01_results", vp, vp, u32, P(u32))
+    sig("ul_slot_format2_results", i32, vp, u32, u32, P(vp), P(u32), P(u32), P(Pf2Csi))
+    sig("ul_slot_sounding_results", vp, vp, u32, P(u32))
     return lib
 
 
@@ -1047,4 +1084,11 @@ ABI_SYMBOLS = [
     "nrphy_ul_sch_info", "nrphy_pusch_proc_validate", "nrphy_pusch_proc_derive", "nrphy_pusch_proc_harq_bytes",
     "nrphy_pusch_proc_plan_create", "nrphy_pusch_proc_plan_destroy", "nrphy_pusch_proc_plan_harq_bytes", "nrphy_pusch_proc_run",
     "nrphy_pusch_proc_host",
+    "nrphy_ofdm_demod_symbols",
+    "nrphy_ul_slots_create", "nrphy_ul_slots_destroy", "nrphy_ul_slots_wait_free", "nrphy_ul_slot_open", "nrphy_ul_slot_close",
+    "nrphy_ul_slot_samples", "nrphy_ul_slot_load_grid", "nrphy_ul_slot_device_grid", "nrphy_ul_slot_stream",
+    "nrphy_ul_slot_symbols_written", "nrphy_ul_slot_pusch", "nrphy_ul_slot_pf01", "nrphy_ul_slot_pf2", "nrphy_ul_slot_srs",
+    "nrphy_ul_slot_finish", "nrphy_ul_slot_poll", "nrphy_ul_slot_wait", "nrphy_ul_slot_read_grid", "nrphy_ul_slot_pusch_results",
+    "nrphy_ul_slot_tb", "nrphy_ul_slot_pusch_uci", "nrphy_ul_slot_pf01_results", "nrphy_ul_slot_format2_results",
+    "nrphy_ul_slot_sounding_results",
 ]

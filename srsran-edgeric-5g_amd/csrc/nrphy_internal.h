@@ -882,9 +882,15 @@ hipError_t launch_ofh_dl_frames(const OfhDlSymbol* d_symbols, uint32_t n, uint32
 hipError_t launch_ofdm(const OfdmLaunch& p, uint32_t nof_grids, const uint32_t* d_grid, const uint32_t* d_slot_index,
                        float2* d_iq, hipStream_t stream);
 // OFDM demodulation (the receive-side mirror of launch_ofdm): `p.phase` is the receive table (conjugate phase x scale),
-// window_offset = nof_samples_window_offset of the reference's demodulator configuration.
-hipError_t launch_ofdm_demod(const OfdmLaunch& p, uint32_t nof_grids, const float2* d_iq, const uint32_t* d_slot_index,
-                             uint32_t window_offset, uint32_t* d_grid, hipStream_t stream);
+// window_offset = nof_samples_window_offset of the reference's demodulator configuration.  Symbols [first_symbol, first_symbol +
+// nof_symbols) of every (grid, port) are read and written; d_iq holds complex float, or complex int16 widened by `gain`.
+struct OfdmDemodRange {
+  uint32_t first_symbol, nof_symbols;
+  bool     ci16;
+  float    gain; // ci16: 1 / iq_scale
+};
+hipError_t launch_ofdm_demod(const OfdmLaunch& p, uint32_t nof_grids, const void* d_iq, const OfdmDemodRange& range,
+                             const uint32_t* d_slot_index, uint32_t window_offset, uint32_t* d_grid, hipStream_t stream);
 // size = n1 * n2: n1 = 1 for the sizes one workgroup transforms in LDS (128 ... 6144, what the OFDM kernels take), else
 // a radix-n1 column pass through global memory in front of n1 LDS transforms of size n2 (9216 ... 49152).
 bool       dft_split(uint32_t size, uint32_t* n1, uint32_t* n2);

@@ -251,8 +251,10 @@ extern "C" int nrphy_ofdm_run_ci16(nrphy_ofdm_plan_t* plan, uint32_t nof_grids, 
   return ofdm_run(plan, nof_grids, d_grid, slot_index, d_iq, cfg, d_stats, stream);
 }
 
-extern "C" int nrphy_ofdm_demod_run(nrphy_ofdm_plan_t* plan, uint32_t nof_grids, const float* d_iq,
-                                    const uint32_t* slot_index, uint32_t window_offset, void* d_grid, void* stream)
+namespace {
+
+int ofdm_demod(nrphy_ofdm_plan_t* plan, uint32_t nof_grids, const void* d_iq, const OfdmDemodRange& range,
+               const uint32_t* slot_index, uint32_t window_offset, void* d_grid, void* stream)
 {
   // ofdm_demodulator_impl.cpp:58-63: the window offset must stay inside the shortest cyclic prefix.
   if (plan == nullptr || d_grid == nullptr || d_iq == nullptr ||
@@ -296,9 +298,36 @@ extern "C" int nrphy_ofdm_demod_run(nrphy_ofdm_plan_t* plan, uint32_t nof_grids,
     }
     p.window_phase = it->second;
   }
-  HIP_TRY(launch_ofdm_demod(p, nof_grids, (const float2*)d_iq, slot_index, window_offset, (uint32_t*)d_grid,
+  HIP_TRY(launch_ofdm_demod(p, nof_grids, d_iq, range, slot_index, window_offset, (uint32_t*)d_grid,
                             stream ? (hipStream_t)stream : ctx->stream));
   return NRPHY_OK;
+}
+
+} // namespace
+
+extern "C" int nrphy_ofdm_demod_run(nrphy_ofdm_plan_t* plan, uint32_t nof_grids, const float* d_iq,
+                                    const uint32_t* slot_index, uint32_t window_offset, void* d_grid, void* stream)
+{
+  if (plan == nullptr) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  return ofdm_demod(plan, nof_grids, d_iq, OfdmDemodRange{0, plan->nsymb, false, 1.0f}, slot_index, window_offset, d_grid, stream);
+}
+
+// puxch_processor_impl::process_symbol (R/lib/phy/lower/processors/uplink/puxch/puxch_processor_impl.cpp:30-81) demodulates the
+// ports of one symbol as soon as its samples are in: a run of symbols of every (grid, port), the other rows left alone.
+extern "C" int nrphy_ofdm_demod_symbols(nrphy_ofdm_plan_t* plan, uint32_t nof_grids, const void* d_iq, uint32_t iq_format,
+                                        float iq_scale, const uint32_t* d_slot_index, uint32_t first_symbol, uint32_t nof_symbols,
+                                        uint32_t window_offset, void* d_grid, void* stream)
+{
+  if (plan == nullptr || nof_symbols == 0 || first_symbol >= plan->nsymb || nof_symbols > plan->nsymb - first_symbol ||
+      iq_format > NRPHY_IQ_CI16 || (iq_format == NRPHY_IQ_CI16 && !(iq_scale > 0.f && std::isfinite(iq_scale)))) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  const bool  ci16 = iq_format == NRPHY_IQ_CI16;
+  const float gain = ci16 ? 1.0f / iq_scale : 1.0f; // srsvec::convert: const float gain = 1.0f / scale
+  return ofdm_demod(plan, nof_grids, d_iq, OfdmDemodRange{first_symbol, nof_symbols, ci16, gain}, d_slot_index, window_offset, d_grid,
+                    stream);
 }
 
 extern "C" int nrphy_ofdm_demodulate_slot_host(nrphy_ofdm_plan_t* plan, const float* iq, uint32_t slot_index,

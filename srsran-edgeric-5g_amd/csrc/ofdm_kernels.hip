@@ -473,14 +473,20 @@ hipError_t launch_ofdm(const OfdmLaunch& p, uint32_t nof_grids, const uint32_t* 
 // top bins -> lower half of the grid, bins from DC -> upper half, stored as cbf16 (round to nearest even, what
 // resource_grid_writer::put does with complex floats).
 // ================================================================================================================
-template <int N>
-__global__ __launch_bounds__(Plan<N>::T) void ofdm_demod_kernel(OfdmLaunch p, const float2* __restrict__ d_iq,
+// The samples come as complex float (IQ_CI16 = false) or as the radio's complex int16 (true): two int16 per sample at the same
+// sample index, each widened as srsvec::convert does (R/lib/srsvec/conversion.cpp:67-129), float(x) * gain with gain = 1 / scale
+// rounded once on the host.  The product is a value of its own before the first butterfly (see IqSinkCi16::pack_plain for what
+// the backend does otherwise), so the transform sees exactly the floats the reference's converter hands its demodulator.
+// blockIdx.x counts from first_symbol: a launch covers a run of symbols of every (grid, port) and touches no other row.
+template <int N, bool IQ_CI16>
+__global__ __launch_bounds__(Plan<N>::T) void ofdm_demod_kernel(OfdmLaunch p, const void* __restrict__ d_iq,
                                                                 const uint32_t* __restrict__ d_slot_index,
-                                                                uint32_t window_offset, uint32_t* __restrict__ d_grid)
+                                                                uint32_t window_offset, uint32_t first_symbol, float iq_gain,
+                                                                uint32_t* __restrict__ d_grid)
 {
   __shared__ cf  lds[N + N / 16 + 16];
   const uint32_t tid  = threadIdx.x;
-  const uint32_t l    = blockIdx.x;
+  const uint32_t l    = first_symbol + blockIdx.x;
   const uint32_t gp   = blockIdx.z * p.nof_ports + blockIdx.y; // grid * nof_ports + port
   const uint32_t slot = d_slot_index ? to_constant(d_slot_index)[blockIdx.z] : 0u;
   const uint32_t sym  = slot * p.nsymb + l; // symbol index within the subframe
@@ -489,18 +495,27 @@ __global__ __launch_bounds__(Plan<N>::T) void ofdm_demod_kernel(OfdmLaunch p, co
   const uint32_t half = p.rg_size >> 1;
 
   // The symbol's N samples after the cyclic prefix, straight into the registers of the first stage.
-  const float2* in = d_iq + (size_t)gp * p.slot_stride + to_constant(p.sym_offset)[sym] + (cp - window_offset);
+  constexpr uint32_t SAMPLE_BYTES = IQ_CI16 ? 4u : 8u;
+  const uint8_t*     in = static_cast<const uint8_t*>(d_iq) +
+                      ((size_t)gp * p.slot_stride + to_constant(p.sym_offset)[sym] + (cp - window_offset)) * SAMPLE_BYTES;
   const __amdgpu_buffer_rsrc_t rsrc_in =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<float2*>(in), 0, (int)(N * 8u), 0x00020000);
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(in), 0, (int)(N * SAMPLE_BYTES), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsrc_out = __builtin_amdgcn_make_buffer_rsrc(
       d_grid + ((size_t)gp * NRPHY_NSYMB + l) * p.rg_size, 0, (int)(p.rg_size * 4u), 0x00020000);
   const TwiddleBase<N> tb = load_twiddle_base<-1, N>(p.twiddle, tid);
   cf                   cur[Plan<N>::R0];
 #pragma unroll
   for (int k = 0; k != Plan<N>::R0; ++k) {
-    const u32x2_t raw = __builtin_amdgcn_raw_buffer_load_b64(
-        rsrc_in, (int)((tid + (uint32_t)k * (N / Plan<N>::R0)) * 8u), 0, 0);
-    cur[k] = make_cf(__uint_as_float(raw.x), __uint_as_float(raw.y));
+    const uint32_t i = tid + (uint32_t)k * (N / Plan<N>::R0);
+    if constexpr (IQ_CI16) {
+      const uint32_t raw = __builtin_amdgcn_raw_buffer_load_b32(rsrc_in, (int)(i * 4u), 0, 0);
+      cf v = make_cf(__fmul_rn((float)(int16_t)(raw & 0xFFFFu), iq_gain), __fmul_rn((float)(int16_t)(raw >> 16), iq_gain));
+      asm("" : "+v"(v));
+      cur[k] = v;
+    } else {
+      const u32x2_t raw = __builtin_amdgcn_raw_buffer_load_b64(rsrc_in, (int)(i * 8u), 0, 0);
+      cur[k]            = make_cf(__uint_as_float(raw.x), __uint_as_float(raw.y));
+    }
   }
   auto store = [&](uint32_t q, auto base, auto, cf v) {
     constexpr uint32_t B   = decltype(base)::value;
@@ -525,46 +540,52 @@ __global__ __launch_bounds__(Plan<N>::T) void ofdm_demod_kernel(OfdmLaunch p, co
 }
 
 template <int N>
-static hipError_t launch_ofdm_demod_n(const OfdmLaunch& p, uint32_t nof_grids, const float2* d_iq,
+static hipError_t launch_ofdm_demod_n(const OfdmLaunch& p, uint32_t nof_grids, const void* d_iq, const OfdmDemodRange& r,
                                       const uint32_t* d_slot_index, uint32_t window_offset, uint32_t* d_grid,
                                       hipStream_t stream)
 {
-  hipLaunchKernelGGL((ofdm_demod_kernel<N>), dim3(p.nsymb, p.nof_ports, nof_grids), dim3(Plan<N>::T), 0, stream, p,
-                     d_iq, d_slot_index, window_offset, d_grid);
+  const dim3 blocks(r.nof_symbols, p.nof_ports, nof_grids);
+  if (r.ci16) {
+    hipLaunchKernelGGL((ofdm_demod_kernel<N, true>), blocks, dim3(Plan<N>::T), 0, stream, p, d_iq, d_slot_index, window_offset,
+                       r.first_symbol, r.gain, d_grid);
+  } else {
+    hipLaunchKernelGGL((ofdm_demod_kernel<N, false>), blocks, dim3(Plan<N>::T), 0, stream, p, d_iq, d_slot_index, window_offset,
+                       r.first_symbol, r.gain, d_grid);
+  }
   return hipGetLastError();
 }
 
-hipError_t launch_ofdm_demod(const OfdmLaunch& p, uint32_t nof_grids, const float2* d_iq, const uint32_t* d_slot_index,
-                             uint32_t window_offset, uint32_t* d_grid, hipStream_t stream)
+hipError_t launch_ofdm_demod(const OfdmLaunch& p, uint32_t nof_grids, const void* d_iq, const OfdmDemodRange& r,
+                             const uint32_t* d_slot_index, uint32_t window_offset, uint32_t* d_grid, hipStream_t stream)
 {
-  if (nof_grids == 0) {
+  if (nof_grids == 0 || r.nof_symbols == 0) {
     return hipSuccess;
   }
   switch (p.dft_size) {
     case 6144:
-      return launch_ofdm_demod_n<6144>(p, nof_grids, d_iq, d_slot_index, window_offset, d_grid, stream);
+      return launch_ofdm_demod_n<6144>(p, nof_grids, d_iq, r, d_slot_index, window_offset, d_grid, stream);
     case 4608:
-      return launch_ofdm_demod_n<4608>(p, nof_grids, d_iq, d_slot_index, window_offset, d_grid, stream);
+      return launch_ofdm_demod_n<4608>(p, nof_grids, d_iq, r, d_slot_index, window_offset, d_grid, stream);
     case 4096:
-      return launch_ofdm_demod_n<4096>(p, nof_grids, d_iq, d_slot_index, window_offset, d_grid, stream);
+      return launch_ofdm_demod_n<4096>(p, nof_grids, d_iq, r, d_slot_index, window_offset, d_grid, stream);
     case 3072:
-      return launch_ofdm_demod_n<3072>(p, nof_grids, d_iq, d_slot_index, window_offset, d_grid, stream);
+      return launch_ofdm_demod_n<3072>(p, nof_grids, d_iq, r, d_slot_index, window_offset, d_grid, stream);
     case 2048:
-      return launch_ofdm_demod_n<2048>(p, nof_grids, d_iq, d_slot_index, window_offset, d_grid, stream);
+      return launch_ofdm_demod_n<2048>(p, nof_grids, d_iq, r, d_slot_index, window_offset, d_grid, stream);
     case 1536:
-      return launch_ofdm_demod_n<1536>(p, nof_grids, d_iq, d_slot_index, window_offset, d_grid, stream);
+      return launch_ofdm_demod_n<1536>(p, nof_grids, d_iq, r, d_slot_index, window_offset, d_grid, stream);
     case 1024:
-      return launch_ofdm_demod_n<1024>(p, nof_grids, d_iq, d_slot_index, window_offset, d_grid, stream);
+      return launch_ofdm_demod_n<1024>(p, nof_grids, d_iq, r, d_slot_index, window_offset, d_grid, stream);
     case 768:
-      return launch_ofdm_demod_n<768>(p, nof_grids, d_iq, d_slot_index, window_offset, d_grid, stream);
+      return launch_ofdm_demod_n<768>(p, nof_grids, d_iq, r, d_slot_index, window_offset, d_grid, stream);
     case 512:
-      return launch_ofdm_demod_n<512>(p, nof_grids, d_iq, d_slot_index, window_offset, d_grid, stream);
+      return launch_ofdm_demod_n<512>(p, nof_grids, d_iq, r, d_slot_index, window_offset, d_grid, stream);
     case 384:
-      return launch_ofdm_demod_n<384>(p, nof_grids, d_iq, d_slot_index, window_offset, d_grid, stream);
+      return launch_ofdm_demod_n<384>(p, nof_grids, d_iq, r, d_slot_index, window_offset, d_grid, stream);
     case 256:
-      return launch_ofdm_demod_n<256>(p, nof_grids, d_iq, d_slot_index, window_offset, d_grid, stream);
+      return launch_ofdm_demod_n<256>(p, nof_grids, d_iq, r, d_slot_index, window_offset, d_grid, stream);
     case 128:
-      return launch_ofdm_demod_n<128>(p, nof_grids, d_iq, d_slot_index, window_offset, d_grid, stream);
+      return launch_ofdm_demod_n<128>(p, nof_grids, d_iq, r, d_slot_index, window_offset, d_grid, stream);
     default:
       return hipErrorInvalidValue;
   }

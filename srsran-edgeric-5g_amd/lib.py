@@ -1437,6 +1437,152 @@ class DlSlotPool:
             pass
 
 
+class UlSlots:
+    """nrphy_ul_slots: the uplink slot pipeline -- samples demodulated run by run into ONE device-resident grid, every receiver
+    of the slot on that grid, the results served from pinned host memory (puxch_processor_impl.cpp:30-97,
+    uplink_processor_impl.cpp:86-170).  The calls that the order rules may refuse return the status; the others raise."""
+
+    def __init__(self, ctx, ofdm_cfg, nof_ports, depth, iq_format=abi.IQ_CF32, iq_scale=1.0, window_offset=0, max_pusch=0,
+                 max_pucch=0, max_pf2=0, max_srs=0, max_tb_bytes=0, max_uci_bits=0, d_harq=None):
+        self.ctx, self.cfg, self.nof_ports = ctx, ofdm_cfg, nof_ports
+        self.nof_subc = 12 * ofdm_cfg.bw_rb
+        self.iq_format = iq_format
+        c = abi.UlSlotsCfg()
+        c.ofdm, c.nof_ports, c.depth, c.iq_format, c.iq_scale, c.window_offset = ofdm_cfg, nof_ports, depth, iq_format, iq_scale, window_offset
+        c.max_pusch, c.max_pucch, c.max_pf2, c.max_srs = max_pusch, max_pucch, max_pf2, max_srs
+        c.max_tb_bytes, c.max_uci_bits = max_tb_bytes, max_uci_bits
+        self._harq = d_harq  # the caller's arena stays alive with the pool
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_ul_slots_create(ctx.handle, C.byref(c), _dptr(d_harq), C.byref(h)), "nrphy_ul_slots_create")
+        self.handle = h
+        self._keep = {}
+
+    def open(self, subframe_slot_index=0):
+        """A free slot with an all-zero grid, or None when all `depth` slots are open."""
+        sid = C.c_uint32()
+        rc = self.ctx.lib.nrphy_ul_slot_open(self.handle, subframe_slot_index, C.byref(sid))
+        if rc == abi.ERR_CAPACITY:
+            return None
+        _check(rc, "nrphy_ul_slot_open")
+        return sid.value
+
+    def close(self, sid):
+        _check(self.ctx.lib.nrphy_ul_slot_close(self.handle, sid), "nrphy_ul_slot_close")
+        self._keep.pop(sid, None)
+
+    def wait_free(self):
+        _check(self.ctx.lib.nrphy_ul_slots_wait_free(self.handle), "nrphy_ul_slots_wait_free")
+
+    def samples(self, sid, first_symbol, nof_symbols, port_samples):
+        """port_samples: per port the samples of the run, complex64 [n] or (abi.IQ_CI16 pools) int16 [n][2]."""
+        dtype = np.int16 if self.iq_format == abi.IQ_CI16 else np.complex64
+        keep = [np.ascontiguousarray(x, dtype=dtype) for x in port_samples]
+        assert len(keep) == self.nof_ports
+        ptrs = (C.c_void_p * len(keep))(*[x.ctypes.data for x in keep])
+        return int(self.ctx.lib.nrphy_ul_slot_samples(self.handle, sid, first_symbol, nof_symbols, ptrs))
+
+    def load_grid(self, sid, grid):
+        grid = np.ascontiguousarray(grid, dtype=np.uint16)
+        assert grid.size == self.nof_ports * 14 * self.nof_subc * 2
+        return int(self.ctx.lib.nrphy_ul_slot_load_grid(self.handle, sid, grid.ctypes.data))
+
+    def device_grid(self, sid):
+        return self.ctx.lib.nrphy_ul_slot_device_grid(self.handle, sid)
+
+    def stream(self, sid):
+        return self.ctx.lib.nrphy_ul_slot_stream(self.handle, sid)
+
+    def symbols_written(self, sid, upto):
+        return int(self.ctx.lib.nrphy_ul_slot_symbols_written(self.handle, sid, upto))
+
+    def pusch(self, sid, pdus, options, harq_soft_offsets=None, harq_state_offsets=None):
+        n = len(pdus)
+        arr = (abi.PuschPdu * n)(*pdus)
+        soft = (C.c_uint64 * n)(*harq_soft_offsets) if harq_soft_offsets is not None else None
+        state = (C.c_uint64 * n)(*harq_state_offsets) if harq_state_offsets is not None else None
+        return int(self.ctx.lib.nrphy_ul_slot_pusch(self.handle, sid, n, arr, C.byref(options), soft, state))
+
+    def pucch(self, sid, cfgs):
+        arr = (abi.PucchCfg * len(cfgs))(*cfgs)
+        return int(self.ctx.lib.nrphy_ul_slot_pf01(self.handle, sid, len(cfgs), arr))
+
+    def pf2(self, sid, cfgs):
+        arr = (abi.Pf2Cfg * len(cfgs))(*cfgs)
+        return int(self.ctx.lib.nrphy_ul_slot_pf2(self.handle, sid, len(cfgs), arr))
+
+    def srs(self, sid, cfgs):
+        arr = (abi.SrsCfg * len(cfgs))(*cfgs)
+        return int(self.ctx.lib.nrphy_ul_slot_srs(self.handle, sid, len(cfgs), arr))
+
+    def finish(self, sid, on_done=None):
+        """on_done(status, slot_id) runs on a HIP runtime thread when the slot's results are in pinned host memory."""
+        cb = None
+        if on_done is not None:
+            cb = abi.UL_SLOT_DONE_FN(lambda user, status, slot_id: on_done(status, slot_id))
+            self._keep[sid] = cb
+        return int(self.ctx.lib.nrphy_ul_slot_finish(self.handle, sid, cb, None))
+
+    def poll(self, sid):
+        return int(self.ctx.lib.nrphy_ul_slot_poll(self.handle, sid))
+
+    def wait(self, sid):
+        return int(self.ctx.lib.nrphy_ul_slot_wait(self.handle, sid))
+
+    def read_grid(self, sid):
+        grid = np.zeros((self.nof_ports, 14, self.nof_subc, 2), dtype=np.uint16)
+        _check(self.ctx.lib.nrphy_ul_slot_read_grid(self.handle, sid, grid.ctypes.data), "nrphy_ul_slot_read_grid")
+        return grid
+
+    def _records(self, fn, sid, cls):
+        n = C.c_uint32()
+        ptr = fn(self.handle, sid, C.byref(n))
+        assert ptr
+        out = (cls * n.value)()
+        C.memmove(out, ptr, C.sizeof(cls) * n.value)
+        return list(out)
+
+    def _bytes(self, fn, sid, i):
+        n = C.c_uint32()
+        ptr = fn(self.handle, sid, i, C.byref(n))
+        assert ptr
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(C.c_uint8)), shape=(n.value,)).copy() if n.value else np.zeros(0, np.uint8)
+
+    def pusch_results(self, sid):
+        """Copies of the slot's abi.PuschResult records, in call order."""
+        return self._records(self.ctx.lib.nrphy_ul_slot_pusch_results, sid, abi.PuschResult)
+
+    def tb(self, sid, i):
+        return self._bytes(self.ctx.lib.nrphy_ul_slot_tb, sid, i)
+
+    def uci_bits(self, sid, i):
+        return self._bytes(self.ctx.lib.nrphy_ul_slot_pusch_uci, sid, i)
+
+    def pucch_results(self, sid):
+        return self._records(self.ctx.lib.nrphy_ul_slot_pf01_results, sid, abi.PucchResult)
+
+    def pf2_result(self, sid, i):
+        """(message bits, status, abi.Pf2Csi) of the slot's i-th format 2 PUCCH."""
+        msg, n, status, csi = C.c_void_p(), C.c_uint32(), C.c_uint32(), abi.Pf2Csi()
+        _check(self.ctx.lib.nrphy_ul_slot_format2_results(self.handle, sid, i, C.byref(msg), C.byref(n), C.byref(status), C.byref(csi)),
+               "nrphy_ul_slot_format2_results")
+        bits = np.ctypeslib.as_array(C.cast(msg, C.POINTER(C.c_uint8)), shape=(n.value,)).copy()
+        return bits, int(status.value), csi
+
+    def srs_results(self, sid):
+        return self._records(self.ctx.lib.nrphy_ul_slot_sounding_results, sid, abi.SrsResult)
+
+    def destroy(self):
+        if self.handle:
+            self.ctx.lib.nrphy_ul_slots_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
 class OfdmPlan:
     """nrphy_ofdm_plan: ofdm_modulator_configuration + port count."""
 
@@ -1482,6 +1628,14 @@ class OfdmPlan:
         """ofdm_slot_demodulator::demodulate for every port of nof_grids slots (device buffers)."""
         _check(self.ctx.lib.nrphy_ofdm_demod_run(self.handle, nof_grids, _dptr(d_iq), _dptr(d_slot_index),
                                                  window_offset, _dptr(d_grid), _stream(stream)), "nrphy_ofdm_demod_run")
+
+    def demod_symbols(self, nof_grids, d_iq, d_grid, first_symbol, nof_symbols, iq_format=abi.IQ_CF32, iq_scale=1.0,
+                      d_slot_index=None, window_offset=0, stream=None):
+        """puxch_processor_impl::process_symbol for a run of symbols: demod_run over symbols [first_symbol, first_symbol +
+        nof_symbols) only, from complex float or (abi.IQ_CI16) complex int16 samples widened by 1 / iq_scale.  Returns the
+        status."""
+        return int(self.ctx.lib.nrphy_ofdm_demod_symbols(self.handle, nof_grids, _dptr(d_iq), iq_format, iq_scale, _dptr(d_slot_index),
+                                                         first_symbol, nof_symbols, window_offset, _dptr(d_grid), _stream(stream)))
 
     def demodulate_slot_host(self, iq, slot_index, window_offset=0):
         """Host-span form: iq [nof_ports][slot samples] complex64 -> grid [nof_ports][14][12*bw_rb][2] uint16."""
