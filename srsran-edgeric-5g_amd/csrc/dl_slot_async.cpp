@@ -13,19 +13,16 @@
 // their stand-alone forms' stream-ordered staging), no blocking copy, except where the header says "blocking".
 #include "nrphy_host_internal.h"
 #include "pdsch_staging_host.h"
+#include "slot_pool_host.h"
 
-#include <atomic>
-#include <condition_variable>
 #include <cstdlib>
 #include <new>
 
 namespace {
 
-enum SlotState : uint32_t { SLOT_FREE = 0, SLOT_OPEN, SLOT_MODULATING, SLOT_DONE };
-
-struct DlSlot {
+// (the life cycle of slot_pool_host.h: a slot is FINISHING while it is being modulated)
+struct DlSlot : SlotCore {
   nrphy_dl_slots*     pool    = nullptr;
-  uint32_t            id      = 0;
   hipStream_t         stream  = nullptr;
   uint32_t*           d_grid  = nullptr;
   void*               d_iq    = nullptr;
@@ -38,20 +35,15 @@ struct DlSlot {
   uint32_t*           d_scratch = nullptr; // sequences and TB-CRC shares of the slot's PDSCH runs (ordered on the stream)
   PlanShapeCache*     shapes  = nullptr;
   std::vector<nrphy_pdsch_plan_t*> plans; // of this open; destroyed when the slot is opened again
-  std::mutex          mutex;              // serialises the calls on this slot
   size_t              stage_used = 0;
   size_t              tb_used    = 0;
   bool                grid_defined = false; // false: nothing has written the grid since open (it still has to be zeroed)
   uint32_t            slot_index = 0;       // of the modulate submitted
-  std::atomic<uint32_t> state{SLOT_FREE};
-  std::atomic<int>    status{NRPHY_OK};
-  nrphy_dl_slot_done_fn done = nullptr;
-  void*               user   = nullptr;
 };
 
 } // namespace
 
-struct nrphy_dl_slots {
+struct nrphy_dl_slots : SlotPool<DlSlot> {
   nrphy_ctx*              ctx = nullptr;
   nrphy_dl_slots_cfg_t    cfg;
   nrphy_ofdm_plan_t*      ofdm = nullptr;
@@ -63,10 +55,6 @@ struct nrphy_dl_slots {
   // in place (no copy down), bit 1 = the modulator writes IQ and measurements into the pinned buffer in place (no copy up).
   // hipMemcpyAsync is the most expensive call of a submit (9 us of host time each, DESIGN_HISTORY.md round 2).
   uint32_t                zero_copy = 0;
-  std::vector<DlSlot>     slots;
-  std::mutex              mutex; // open / close
-  std::condition_variable changed;
-  uint32_t                nof_open = 0;
 };
 
 namespace {
@@ -74,27 +62,8 @@ namespace {
 // Runs on a thread of the HIP runtime when the slot's IQ has reached the pinned buffer (or the stream has failed).
 void on_slot_done(hipStream_t, hipError_t error, void* arg)
 {
-  DlSlot*         slot = static_cast<DlSlot*>(arg);
-  nrphy_dl_slots* pool = slot->pool;
-  const int       rc   = error == hipSuccess ? NRPHY_OK : NRPHY_ERR_DEVICE;
-  slot->status.store(rc, std::memory_order_relaxed);
-  slot->state.store(SLOT_DONE, std::memory_order_release);
-  if (slot->done != nullptr) {
-    slot->done(slot->user, rc, slot->id);
-  }
-  {
-    std::lock_guard<std::mutex> lock(pool->mutex);
-  }
-  pool->changed.notify_all();
-}
-
-DlSlot* open_slot(nrphy_dl_slots* pool, uint32_t slot_id)
-{
-  if (pool == nullptr || slot_id >= pool->slots.size()) {
-    return nullptr;
-  }
-  DlSlot* s = &pool->slots[slot_id];
-  return s->state.load(std::memory_order_acquire) == SLOT_FREE ? nullptr : s;
+  DlSlot* slot = static_cast<DlSlot*>(arg);
+  slot_pool_complete(*slot->pool, *slot, error == hipSuccess ? NRPHY_OK : NRPHY_ERR_DEVICE);
 }
 
 // Before the first writer of an open slot: the grid is all zeros (resource_grid::set_all_zero).  A PDSCH run clears what it
@@ -241,12 +210,7 @@ extern "C" int nrphy_dl_slots_destroy(nrphy_dl_slots_t* pool)
 
 extern "C" int nrphy_dl_slots_wait_free(nrphy_dl_slots_t* pool)
 {
-  if (pool == nullptr) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  std::unique_lock<std::mutex> lock(pool->mutex);
-  pool->changed.wait(lock, [pool] { return pool->nof_open < pool->slots.size(); });
-  return NRPHY_OK;
+  return slot_pool_wait_free(pool);
 }
 
 extern "C" int nrphy_dl_slot_open(nrphy_dl_slots_t* pool, uint32_t* slot_id)
@@ -254,18 +218,7 @@ extern "C" int nrphy_dl_slot_open(nrphy_dl_slots_t* pool, uint32_t* slot_id)
   if (pool == nullptr || slot_id == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
-  DlSlot* slot = nullptr;
-  {
-    std::lock_guard<std::mutex> lock(pool->mutex);
-    for (DlSlot& s : pool->slots) {
-      if (s.state.load(std::memory_order_acquire) == SLOT_FREE) {
-        slot = &s;
-        s.state.store(SLOT_OPEN, std::memory_order_release);
-        ++pool->nof_open;
-        break;
-      }
-    }
-  }
+  DlSlot* slot = slot_pool_claim(*pool);
   if (slot == nullptr) {
     return NRPHY_ERR_CAPACITY;
   }
@@ -278,16 +231,13 @@ extern "C" int nrphy_dl_slot_open(nrphy_dl_slots_t* pool, uint32_t* slot_id)
   slot->stage_used   = 0;
   slot->tb_used      = 0;
   slot->grid_defined = false;
-  slot->done         = nullptr;
-  slot->user         = nullptr;
-  slot->status.store(NRPHY_OK, std::memory_order_relaxed);
   *slot_id = slot->id;
   return NRPHY_OK;
 }
 
 extern "C" int nrphy_dl_slot_close(nrphy_dl_slots_t* pool, uint32_t slot_id)
 {
-  DlSlot* s = open_slot(pool, slot_id);
+  DlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -297,29 +247,21 @@ extern "C" int nrphy_dl_slot_close(nrphy_dl_slots_t* pool, uint32_t slot_id)
       // (the slot is given back all the same: a failed stream fails the next use too, and says so)
     }
     // A completion callback of this slot may still be running on its runtime thread: wait for its state.
-    if (s->state.load(std::memory_order_acquire) == SLOT_MODULATING) {
-      std::unique_lock<std::mutex> pool_lock(pool->mutex);
-      pool->changed.wait(pool_lock, [s] { return s->state.load(std::memory_order_acquire) == SLOT_DONE; });
-    }
+    slot_pool_await_callback(*pool, *s);
   }
-  {
-    std::lock_guard<std::mutex> lock(pool->mutex);
-    s->state.store(SLOT_FREE, std::memory_order_release);
-    --pool->nof_open;
-  }
-  pool->changed.notify_all();
+  slot_pool_release(*pool, *s);
   return NRPHY_OK;
 }
 
 extern "C" int nrphy_dl_slot_pdsch(nrphy_dl_slots_t* pool, uint32_t slot_id, uint32_t n_pdu, const nrphy_pdsch_pdu_t* pdus,
                                    const uint8_t* const* tbs)
 {
-  DlSlot* s = open_slot(pool, slot_id);
+  DlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || pdus == nullptr || tbs == nullptr || n_pdu == 0) {
     return NRPHY_ERR_ARGUMENT;
   }
   std::lock_guard<std::mutex> lock(s->mutex);
-  if (s->state.load(std::memory_order_acquire) != SLOT_OPEN) {
+  if (!slot_is_open(*s)) {
     return NRPHY_ERR_ARGUMENT; // the grid has been handed over
   }
   PdschStagingLayout layout;
@@ -365,12 +307,12 @@ extern "C" int nrphy_dl_slot_pdsch(nrphy_dl_slots_t* pool, uint32_t slot_id, uin
 
 extern "C" int nrphy_dl_slot_pdcch(nrphy_dl_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pdcch_pdu_t* pdus)
 {
-  DlSlot* s = open_slot(pool, slot_id);
+  DlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
   std::lock_guard<std::mutex> lock(s->mutex);
-  if (s->state.load(std::memory_order_acquire) != SLOT_OPEN) {
+  if (!slot_is_open(*s)) {
     return NRPHY_ERR_ARGUMENT;
   }
   HIP_TRY(hipSetDevice(pool->ctx->device));
@@ -380,12 +322,12 @@ extern "C" int nrphy_dl_slot_pdcch(nrphy_dl_slots_t* pool, uint32_t slot_id, uin
 
 extern "C" int nrphy_dl_slot_ssb(nrphy_dl_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_ssb_pdu_t* pdus)
 {
-  DlSlot* s = open_slot(pool, slot_id);
+  DlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
   std::lock_guard<std::mutex> lock(s->mutex);
-  if (s->state.load(std::memory_order_acquire) != SLOT_OPEN) {
+  if (!slot_is_open(*s)) {
     return NRPHY_ERR_ARGUMENT;
   }
   HIP_TRY(hipSetDevice(pool->ctx->device));
@@ -395,12 +337,12 @@ extern "C" int nrphy_dl_slot_ssb(nrphy_dl_slots_t* pool, uint32_t slot_id, uint3
 
 extern "C" int nrphy_dl_slot_csi_rs(nrphy_dl_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_csi_rs_cfg_t* cfgs)
 {
-  DlSlot* s = open_slot(pool, slot_id);
+  DlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || n == 0 || n > 4096) {
     return NRPHY_ERR_ARGUMENT;
   }
   std::lock_guard<std::mutex> lock(s->mutex);
-  if (s->state.load(std::memory_order_acquire) != SLOT_OPEN) {
+  if (!slot_is_open(*s)) {
     return NRPHY_ERR_ARGUMENT;
   }
   HIP_TRY(hipSetDevice(pool->ctx->device));
@@ -414,12 +356,12 @@ extern "C" int nrphy_dl_slot_csi_rs(nrphy_dl_slots_t* pool, uint32_t slot_id, ui
 
 extern "C" int nrphy_dl_slot_put(nrphy_dl_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_grid_re_t* entries)
 {
-  DlSlot* s = open_slot(pool, slot_id);
+  DlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
   std::lock_guard<std::mutex> lock(s->mutex);
-  if (s->state.load(std::memory_order_acquire) != SLOT_OPEN) {
+  if (!slot_is_open(*s)) {
     return NRPHY_ERR_ARGUMENT;
   }
   HIP_TRY(hipSetDevice(pool->ctx->device));
@@ -429,12 +371,12 @@ extern "C" int nrphy_dl_slot_put(nrphy_dl_slots_t* pool, uint32_t slot_id, uint3
 
 extern "C" int nrphy_dl_slot_load_grid(nrphy_dl_slots_t* pool, uint32_t slot_id, const void* grid)
 {
-  DlSlot* s = open_slot(pool, slot_id);
+  DlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || grid == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
   std::lock_guard<std::mutex> lock(s->mutex);
-  if (s->state.load(std::memory_order_acquire) != SLOT_OPEN) {
+  if (!slot_is_open(*s)) {
     return NRPHY_ERR_ARGUMENT;
   }
   HIP_TRY(hipSetDevice(pool->ctx->device));
@@ -451,12 +393,12 @@ extern "C" int nrphy_dl_slot_load_grid(nrphy_dl_slots_t* pool, uint32_t slot_id,
 extern "C" int nrphy_dl_slot_modulate(nrphy_dl_slots_t* pool, uint32_t slot_id, uint32_t subframe_slot_index,
                                       nrphy_dl_slot_done_fn done, void* user)
 {
-  DlSlot* s = open_slot(pool, slot_id);
+  DlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || subframe_slot_index >= (1U << pool->cfg.ofdm.numerology)) {
     return NRPHY_ERR_ARGUMENT;
   }
   std::lock_guard<std::mutex> lock(s->mutex);
-  if (s->state.load(std::memory_order_acquire) != SLOT_OPEN) {
+  if (!slot_is_open(*s)) {
     return NRPHY_ERR_ARGUMENT; // once per open
   }
   HIP_TRY(hipSetDevice(pool->ctx->device));
@@ -474,16 +416,13 @@ extern "C" int nrphy_dl_slot_modulate(nrphy_dl_slots_t* pool, uint32_t slot_id, 
     return rc;
   }
   s->slot_index = subframe_slot_index;
-  s->done       = done;
-  s->user       = user;
-  s->state.store(SLOT_MODULATING, std::memory_order_release);
+  slot_arm(*s, done, user);
   // IQ and, for a wire-format pool, the measurements behind it come up in ONE copy -- or were written in place.
   if (((pool->zero_copy & 2u) == 0 &&
        hipMemcpyAsync(s->h_iq, s->d_iq, pool->iq_block_bytes, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
       hipStreamAddCallback(s->stream, on_slot_done, s, 0) != hipSuccess) {
     (void)hipStreamSynchronize(s->stream);
-    s->status.store(NRPHY_ERR_DEVICE, std::memory_order_relaxed);
-    s->state.store(SLOT_DONE, std::memory_order_release);
+    slot_fail_armed(*s);
     return NRPHY_ERR_DEVICE;
   }
   return NRPHY_OK;
@@ -491,29 +430,12 @@ extern "C" int nrphy_dl_slot_modulate(nrphy_dl_slots_t* pool, uint32_t slot_id, 
 
 extern "C" int nrphy_dl_slot_poll(nrphy_dl_slots_t* pool, uint32_t slot_id)
 {
-  if (pool == nullptr || slot_id >= pool->slots.size()) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  const DlSlot& s = pool->slots[slot_id];
-  switch (s.state.load(std::memory_order_acquire)) {
-    case SLOT_DONE:
-      return s.status.load(std::memory_order_relaxed);
-    case SLOT_FREE:
-      return NRPHY_ERR_ARGUMENT;
-    default:
-      return NRPHY_ERR_NOT_READY;
-  }
+  return slot_pool_poll(pool, slot_id);
 }
 
 extern "C" int nrphy_dl_slot_wait(nrphy_dl_slots_t* pool, uint32_t slot_id)
 {
-  DlSlot* s = open_slot(pool, slot_id);
-  if (s == nullptr || s->state.load(std::memory_order_acquire) == SLOT_OPEN) {
-    return NRPHY_ERR_ARGUMENT; // nothing to wait for
-  }
-  std::unique_lock<std::mutex> lock(pool->mutex);
-  pool->changed.wait(lock, [s] { return s->state.load(std::memory_order_acquire) != SLOT_MODULATING; });
-  return s->state.load(std::memory_order_acquire) == SLOT_DONE ? s->status.load(std::memory_order_relaxed) : NRPHY_ERR_ARGUMENT;
+  return slot_pool_wait(pool, slot_id);
 }
 
 extern "C" const void* nrphy_dl_slot_iq(nrphy_dl_slots_t* pool, uint32_t slot_id, uint32_t port, uint32_t* nof_samples)
@@ -538,7 +460,7 @@ extern "C" const nrphy_amplitude_stats_t* nrphy_dl_slot_amplitude_stats(nrphy_dl
 
 extern "C" int nrphy_dl_slot_read_grid(nrphy_dl_slots_t* pool, uint32_t slot_id, void* grid)
 {
-  DlSlot* s = open_slot(pool, slot_id);
+  DlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || grid == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -556,12 +478,12 @@ extern "C" int nrphy_dl_slot_read_grid(nrphy_dl_slots_t* pool, uint32_t slot_id,
 
 extern "C" void* nrphy_dl_slot_device_grid(nrphy_dl_slots_t* pool, uint32_t slot_id)
 {
-  DlSlot* s = open_slot(pool, slot_id);
+  DlSlot* s = slot_pool_lookup(pool, slot_id);
   return s ? s->d_grid : nullptr;
 }
 
 extern "C" void* nrphy_dl_slot_stream(nrphy_dl_slots_t* pool, uint32_t slot_id)
 {
-  DlSlot* s = open_slot(pool, slot_id);
+  DlSlot* s = slot_pool_lookup(pool, slot_id);
   return s ? (void*)s->stream : nullptr;
 }

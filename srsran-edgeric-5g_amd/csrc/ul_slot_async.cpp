@@ -12,20 +12,17 @@
 // the context's host lock, as those calls are not written to run side by side on one context); the plans live until the slot is
 // closed.
 #include "nrphy_host_internal.h"
+#include "slot_pool_host.h"
 #include "ul_slot_state_host.h"
 
-#include <atomic>
 #include <cmath>
-#include <condition_variable>
 #include <new>
 
 namespace {
 
-enum SlotState : uint32_t { SLOT_FREE = 0, SLOT_OPEN, SLOT_FINISHING, SLOT_DONE };
-
-struct UlSlot {
+// (the life cycle of slot_pool_host.h; the order of the calls on an open slot is ul_slot_state_host.h's)
+struct UlSlot : SlotCore {
   nrphy_ul_slots* pool     = nullptr;
-  uint32_t        id       = 0;
   hipStream_t     stream   = nullptr;
   uint32_t*       d_grid   = nullptr;
   uint8_t*        d_iq     = nullptr; // [port][slot_stride] samples
@@ -40,16 +37,11 @@ struct UlSlot {
   std::vector<nrphy_pucch_plan_t*>      pucch_plans;
   std::vector<nrphy_pf2_plan_t*>        pf2_plans;
   std::vector<nrphy_srs_plan_t*>        srs_plans;
-  std::mutex            mutex; // serialises the calls on this slot
-  std::atomic<uint32_t> state{SLOT_FREE};
-  std::atomic<int>      status{NRPHY_OK};
-  nrphy_ul_slot_done_fn done = nullptr;
-  void*                 user = nullptr;
 };
 
 } // namespace
 
-struct nrphy_ul_slots {
+struct nrphy_ul_slots : SlotPool<UlSlot> {
   nrphy_ctx*              ctx = nullptr;
   nrphy_ul_slots_cfg_t    cfg;
   nrphy_ofdm_plan_t*      ofdm = nullptr;
@@ -59,10 +51,6 @@ struct nrphy_ul_slots {
   UlSlotLayout            layout;
   std::vector<uint32_t>   sym_offset; // [slot of the subframe][nsymb + 1]: first sample of a symbol within its slot
   uint32_t*               d_slot_numbers = nullptr; // 0, 1, ... : the demodulator takes the slot index from device memory
-  std::vector<UlSlot>     slots;
-  std::mutex              mutex; // open / close
-  std::condition_variable changed;
-  uint32_t                nof_open = 0;
 };
 
 namespace {
@@ -72,7 +60,6 @@ void on_slot_done(hipStream_t, hipError_t error, void* arg)
 {
   UlSlot*         slot = static_cast<UlSlot*>(arg);
   nrphy_ul_slots* pool = slot->pool;
-  const int       rc   = error == hipSuccess ? NRPHY_OK : NRPHY_ERR_DEVICE;
   // The UCI offsets of a result count from the PDU's own bits, as nrphy_pusch_proc_host gives them.
   auto* results = reinterpret_cast<nrphy_pusch_result_t*>(slot->h_res + pool->layout.pusch);
   for (uint32_t i = 0; i != slot->order.used.n_pusch; ++i) {
@@ -80,24 +67,7 @@ void on_slot_done(hipStream_t, hipError_t error, void* arg)
     results[i].harq_ack_offset -= results[i].nof_harq_ack != 0 ? at : 0;
     results[i].csi_part1_offset -= results[i].nof_csi_part1 != 0 ? at : 0;
   }
-  slot->status.store(rc, std::memory_order_relaxed);
-  slot->state.store(SLOT_DONE, std::memory_order_release);
-  if (slot->done != nullptr) {
-    slot->done(slot->user, rc, slot->id);
-  }
-  {
-    std::lock_guard<std::mutex> lock(pool->mutex);
-  }
-  pool->changed.notify_all();
-}
-
-UlSlot* open_slot(nrphy_ul_slots* pool, uint32_t slot_id)
-{
-  if (pool == nullptr || slot_id >= pool->slots.size()) {
-    return nullptr;
-  }
-  UlSlot* s = &pool->slots[slot_id];
-  return s->state.load(std::memory_order_acquire) == SLOT_FREE ? nullptr : s;
+  slot_pool_complete(*pool, *slot, error == hipSuccess ? NRPHY_OK : NRPHY_ERR_DEVICE);
 }
 
 void destroy_plans(UlSlot& s)
@@ -119,6 +89,36 @@ void destroy_plans(UlSlot& s)
   s.pf2_plans.clear();
   s.srs_plans.clear();
 }
+
+// The gate of the four receiver calls: the slot of `slot_id`, locked, if it is open, not finished and the call brings items;
+// otherwise no lock (NRPHY_ERR_ARGUMENT).
+std::unique_lock<std::mutex> lock_for_receivers(nrphy_ul_slots* pool, uint32_t slot_id, uint32_t n, const void* items, UlSlot*& s)
+{
+  s = slot_pool_lookup(pool, slot_id);
+  if (s == nullptr || n == 0 || items == nullptr) {
+    return {};
+  }
+  std::unique_lock<std::mutex> lock(s->mutex);
+  if (ul_slot_accept_open_call(s->order) != NRPHY_OK) {
+    return {};
+  }
+  return lock;
+}
+
+// One item of a receiver call: its validator's status comes first, then whether its last symbol has been delivered.
+int item_status(const UlSlot& s, int valid, uint32_t start_symbol, uint32_t nof_symbols)
+{
+  return valid != NRPHY_OK ? valid : ul_slot_accept_receiver(s.order, start_symbol, nof_symbols);
+}
+
+// What the tail of the four receiver calls starts with, once nothing of the call can be refused any more: the n items all read
+// grid 0, the plan is made under the context's host lock, on the context's device (`device`: what hipSetDevice said).
+struct PlanCall {
+  const std::vector<uint32_t>           grid_of;
+  std::lock_guard<std::recursive_mutex> host_lock;
+  const hipError_t                      device;
+  PlanCall(nrphy_ul_slots* pool, uint32_t n) : grid_of(n, 0), host_lock(pool->ctx->host_mutex), device(hipSetDevice(pool->ctx->device)) {}
+};
 
 } // namespace
 
@@ -246,12 +246,7 @@ extern "C" int nrphy_ul_slots_destroy(nrphy_ul_slots_t* pool)
 
 extern "C" int nrphy_ul_slots_wait_free(nrphy_ul_slots_t* pool)
 {
-  if (pool == nullptr) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  std::unique_lock<std::mutex> lock(pool->mutex);
-  pool->changed.wait(lock, [pool] { return pool->nof_open < pool->slots.size(); });
-  return NRPHY_OK;
+  return slot_pool_wait_free(pool);
 }
 
 extern "C" int nrphy_ul_slot_open(nrphy_ul_slots_t* pool, uint32_t subframe_slot_index, uint32_t* slot_id)
@@ -259,18 +254,7 @@ extern "C" int nrphy_ul_slot_open(nrphy_ul_slots_t* pool, uint32_t subframe_slot
   if (pool == nullptr || slot_id == nullptr || subframe_slot_index >= (1U << pool->cfg.ofdm.numerology)) {
     return NRPHY_ERR_ARGUMENT;
   }
-  UlSlot* slot = nullptr;
-  {
-    std::lock_guard<std::mutex> lock(pool->mutex);
-    for (UlSlot& s : pool->slots) {
-      if (s.state.load(std::memory_order_acquire) == SLOT_FREE) {
-        slot = &s;
-        s.state.store(SLOT_OPEN, std::memory_order_release);
-        ++pool->nof_open;
-        break;
-      }
-    }
-  }
+  UlSlot* slot = slot_pool_claim(*pool);
   if (slot == nullptr) {
     return NRPHY_ERR_CAPACITY;
   }
@@ -278,23 +262,11 @@ extern "C" int nrphy_ul_slot_open(nrphy_ul_slots_t* pool, uint32_t subframe_slot
   ul_slot_state_open(slot->order);
   slot->slot_index  = subframe_slot_index;
   slot->h_grid_busy = false;
-  slot->done        = nullptr;
-  slot->user        = nullptr;
-  slot->status.store(NRPHY_OK, std::memory_order_relaxed);
   // Symbols never delivered read as zero; a transport block whose CRC fails and the bytes a UCI decoder leaves alone likewise.
-  int rc = NRPHY_OK;
   if (hipSetDevice(pool->ctx->device) != hipSuccess || hipMemsetAsync(slot->d_grid, 0, pool->grid_bytes, slot->stream) != hipSuccess ||
       hipMemsetAsync(slot->d_res, 0, pool->layout.total, slot->stream) != hipSuccess) {
-    rc = NRPHY_ERR_DEVICE;
-  }
-  if (rc != NRPHY_OK) {
-    {
-      std::lock_guard<std::mutex> pool_lock(pool->mutex);
-      slot->state.store(SLOT_FREE, std::memory_order_release);
-      --pool->nof_open;
-    }
-    pool->changed.notify_all();
-    return rc;
+    slot_pool_release(*pool, *slot);
+    return NRPHY_ERR_DEVICE;
   }
   *slot_id = slot->id;
   return NRPHY_OK;
@@ -302,7 +274,7 @@ extern "C" int nrphy_ul_slot_open(nrphy_ul_slots_t* pool, uint32_t subframe_slot
 
 extern "C" int nrphy_ul_slot_close(nrphy_ul_slots_t* pool, uint32_t slot_id)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -312,25 +284,17 @@ extern "C" int nrphy_ul_slot_close(nrphy_ul_slots_t* pool, uint32_t slot_id)
       // (the slot is given back all the same: a failed stream fails the next use too, and says so)
     }
     // A completion callback of this slot may still be running on its runtime thread: wait for its state.
-    if (s->state.load(std::memory_order_acquire) == SLOT_FINISHING) {
-      std::unique_lock<std::mutex> pool_lock(pool->mutex);
-      pool->changed.wait(pool_lock, [s] { return s->state.load(std::memory_order_acquire) == SLOT_DONE; });
-    }
+    slot_pool_await_callback(*pool, *s);
     destroy_plans(*s); // nothing of them is in flight any more
   }
-  {
-    std::lock_guard<std::mutex> lock(pool->mutex);
-    s->state.store(SLOT_FREE, std::memory_order_release);
-    --pool->nof_open;
-  }
-  pool->changed.notify_all();
+  slot_pool_release(*pool, *s);
   return NRPHY_OK;
 }
 
 extern "C" int nrphy_ul_slot_samples(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t first_symbol, uint32_t nof_symbols,
                                      const void* const* port_samples)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || port_samples == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -369,7 +333,7 @@ extern "C" int nrphy_ul_slot_samples(nrphy_ul_slots_t* pool, uint32_t slot_id, u
 
 extern "C" int nrphy_ul_slot_load_grid(nrphy_ul_slots_t* pool, uint32_t slot_id, const void* grid)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || grid == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -391,7 +355,7 @@ extern "C" int nrphy_ul_slot_load_grid(nrphy_ul_slots_t* pool, uint32_t slot_id,
 
 extern "C" int nrphy_ul_slot_symbols_written(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t upto)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -407,25 +371,21 @@ extern "C" int nrphy_ul_slot_pusch(nrphy_ul_slots_t* pool, uint32_t slot_id, uin
                                    const nrphy_pusch_proc_options_t* options, const uint64_t* harq_soft_offset,
                                    const uint64_t* harq_state_offset)
 {
-  UlSlot* s = open_slot(pool, slot_id);
-  if (s == nullptr || n == 0 || pdus == nullptr || options == nullptr) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  std::lock_guard<std::mutex> lock(s->mutex);
-  if (ul_slot_accept_open_call(s->order) != NRPHY_OK) {
+  UlSlot*    s    = nullptr;
+  const auto lock = lock_for_receivers(pool, slot_id, n, pdus, s);
+  if (!lock || options == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
   UlSlotUsed              used = s->order.used;
   std::vector<UlSlotSpan> tb(n), uci(n);
   std::vector<uint64_t>   tb_offset(n), uci_offset(n);
-  const std::vector<uint32_t> grid_of(n, 0);
   for (uint32_t i = 0; i != n; ++i) {
-    int rc = nrphy_pusch_proc_validate(&pdus[i], options, pool->cfg.nof_ports, pool->nof_subc);
+    int rc = item_status(*s, nrphy_pusch_proc_validate(&pdus[i], options, pool->cfg.nof_ports, pool->nof_subc),
+                         pdus[i].start_symbol_index, pdus[i].nof_symbols);
     if (rc != NRPHY_OK) {
       return rc;
     }
-    if (ul_slot_accept_receiver(s->order, pdus[i].start_symbol_index, pdus[i].nof_symbols) != NRPHY_OK ||
-        (pdus[i].has_codeword != 0 && (pool->d_harq == nullptr || harq_soft_offset == nullptr || harq_state_offset == nullptr))) {
+    if (pdus[i].has_codeword != 0 && (pool->d_harq == nullptr || harq_soft_offset == nullptr || harq_state_offset == nullptr)) {
       return NRPHY_ERR_ARGUMENT;
     }
     rc = ul_slot_take_pusch(s->order.lim, used, pdus[i].tb_size_bytes, pdus[i].nof_harq_ack + pdus[i].nof_csi_part1, tb[i], uci[i]);
@@ -435,10 +395,10 @@ extern "C" int nrphy_ul_slot_pusch(nrphy_ul_slots_t* pool, uint32_t slot_id, uin
     tb_offset[i]  = tb[i].at;
     uci_offset[i] = uci[i].at;
   }
-  std::lock_guard<std::recursive_mutex> host_lock(pool->ctx->host_mutex);
-  HIP_TRY(hipSetDevice(pool->ctx->device));
+  const PlanCall call(pool, n);
+  HIP_TRY(call.device);
   nrphy_pusch_proc_plan_t* plan = nullptr;
-  int rc = nrphy_pusch_proc_plan_create(pool->ctx, n, pdus, options, grid_of.data(), 1, pool->cfg.nof_ports, pool->nof_subc,
+  int rc = nrphy_pusch_proc_plan_create(pool->ctx, n, pdus, options, call.grid_of.data(), 1, pool->cfg.nof_ports, pool->nof_subc,
                                         harq_soft_offset, harq_state_offset, tb_offset.data(), uci_offset.data(), &plan);
   if (rc != NRPHY_OK) {
     return rc;
@@ -460,33 +420,27 @@ extern "C" int nrphy_ul_slot_pusch(nrphy_ul_slots_t* pool, uint32_t slot_id, uin
 
 extern "C" int nrphy_ul_slot_pf01(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pucch_cfg_t* cfgs)
 {
-  UlSlot* s = open_slot(pool, slot_id);
-  if (s == nullptr || n == 0 || cfgs == nullptr) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  std::lock_guard<std::mutex> lock(s->mutex);
-  if (ul_slot_accept_open_call(s->order) != NRPHY_OK) {
+  UlSlot*    s    = nullptr;
+  const auto lock = lock_for_receivers(pool, slot_id, n, cfgs, s);
+  if (!lock) {
     return NRPHY_ERR_ARGUMENT;
   }
   UlSlotUsed used = s->order.used;
   for (uint32_t i = 0; i != n; ++i) {
-    const int rc = nrphy_pucch_validate(&cfgs[i], pool->cfg.nof_ports, pool->nof_subc);
+    const int rc = item_status(*s, nrphy_pucch_validate(&cfgs[i], pool->cfg.nof_ports, pool->nof_subc), cfgs[i].start_symbol_index,
+                               cfgs[i].nof_symbols);
     if (rc != NRPHY_OK) {
       return rc;
-    }
-    if (ul_slot_accept_receiver(s->order, cfgs[i].start_symbol_index, cfgs[i].nof_symbols) != NRPHY_OK) {
-      return NRPHY_ERR_ARGUMENT;
     }
   }
   int rc = ul_slot_take_count(s->order.lim.max_pucch, used.n_pucch, n);
   if (rc != NRPHY_OK) {
     return rc;
   }
-  const std::vector<uint32_t>           grid_of(n, 0);
-  std::lock_guard<std::recursive_mutex> host_lock(pool->ctx->host_mutex);
-  HIP_TRY(hipSetDevice(pool->ctx->device));
+  const PlanCall call(pool, n);
+  HIP_TRY(call.device);
   nrphy_pucch_plan_t* plan = nullptr;
-  rc = nrphy_pucch_plan_create(pool->ctx, n, cfgs, grid_of.data(), 1, pool->cfg.nof_ports, pool->nof_subc, nullptr, &plan);
+  rc = nrphy_pucch_plan_create(pool->ctx, n, cfgs, call.grid_of.data(), 1, pool->cfg.nof_ports, pool->nof_subc, nullptr, &plan);
   if (rc != NRPHY_OK) {
     return rc;
   }
@@ -502,12 +456,9 @@ extern "C" int nrphy_ul_slot_pf01(nrphy_ul_slots_t* pool, uint32_t slot_id, uint
 
 extern "C" int nrphy_ul_slot_pf2(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pf2_cfg_t* cfgs)
 {
-  UlSlot* s = open_slot(pool, slot_id);
-  if (s == nullptr || n == 0 || cfgs == nullptr) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  std::lock_guard<std::mutex> lock(s->mutex);
-  if (ul_slot_accept_open_call(s->order) != NRPHY_OK) {
+  UlSlot*    s    = nullptr;
+  const auto lock = lock_for_receivers(pool, slot_id, n, cfgs, s);
+  if (!lock) {
     return NRPHY_ERR_ARGUMENT;
   }
   UlSlotUsed              used  = s->order.used;
@@ -515,13 +466,13 @@ extern "C" int nrphy_ul_slot_pf2(nrphy_ul_slots_t* pool, uint32_t slot_id, uint3
   std::vector<UlSlotSpan> msg(n);
   std::vector<uint64_t>   llr_offset(n), message_offset(n);
   for (uint32_t i = 0; i != n; ++i) {
-    int rc = nrphy_pf2_validate(&cfgs[i], pool->cfg.nof_ports, pool->nof_subc);
+    int rc = item_status(*s, nrphy_pf2_validate(&cfgs[i], pool->cfg.nof_ports, pool->nof_subc), cfgs[i].start_symbol_index,
+                         cfgs[i].nof_symbols);
     if (rc != NRPHY_OK) {
       return rc;
     }
     uint32_t nof_llr = 0, nof_bits = 0;
-    if (ul_slot_accept_receiver(s->order, cfgs[i].start_symbol_index, cfgs[i].nof_symbols) != NRPHY_OK ||
-        nrphy_pf2_sizes(&cfgs[i], &nof_llr, &nof_bits) != NRPHY_OK || nof_llr > UL_SLOT_PF2_LLR_BYTES) {
+    if (nrphy_pf2_sizes(&cfgs[i], &nof_llr, &nof_bits) != NRPHY_OK || nof_llr > UL_SLOT_PF2_LLR_BYTES) {
       return NRPHY_ERR_ARGUMENT;
     }
     rc = ul_slot_take_pf2(s->order.lim, used, nof_bits, msg[i]);
@@ -531,11 +482,10 @@ extern "C" int nrphy_ul_slot_pf2(nrphy_ul_slots_t* pool, uint32_t slot_id, uint3
     llr_offset[i]     = (uint64_t)(first + i) * UL_SLOT_PF2_LLR_BYTES;
     message_offset[i] = msg[i].at;
   }
-  const std::vector<uint32_t>           grid_of(n, 0);
-  std::lock_guard<std::recursive_mutex> host_lock(pool->ctx->host_mutex);
-  HIP_TRY(hipSetDevice(pool->ctx->device));
+  const PlanCall call(pool, n);
+  HIP_TRY(call.device);
   nrphy_pf2_plan_t* plan = nullptr;
-  int rc = nrphy_pf2_plan_create(pool->ctx, n, cfgs, grid_of.data(), 1, pool->cfg.nof_ports, pool->nof_subc, llr_offset.data(),
+  int rc = nrphy_pf2_plan_create(pool->ctx, n, cfgs, call.grid_of.data(), 1, pool->cfg.nof_ports, pool->nof_subc, llr_offset.data(),
                                  message_offset.data(), nullptr, &plan);
   if (rc != NRPHY_OK) {
     return rc;
@@ -556,33 +506,27 @@ extern "C" int nrphy_ul_slot_pf2(nrphy_ul_slots_t* pool, uint32_t slot_id, uint3
 
 extern "C" int nrphy_ul_slot_srs(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_srs_cfg_t* cfgs)
 {
-  UlSlot* s = open_slot(pool, slot_id);
-  if (s == nullptr || n == 0 || cfgs == nullptr) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  std::lock_guard<std::mutex> lock(s->mutex);
-  if (ul_slot_accept_open_call(s->order) != NRPHY_OK) {
+  UlSlot*    s    = nullptr;
+  const auto lock = lock_for_receivers(pool, slot_id, n, cfgs, s);
+  if (!lock) {
     return NRPHY_ERR_ARGUMENT;
   }
   UlSlotUsed used = s->order.used;
   for (uint32_t i = 0; i != n; ++i) {
-    const int rc = nrphy_srs_validate(&cfgs[i], pool->cfg.nof_ports, pool->nof_subc);
+    const int rc = item_status(*s, nrphy_srs_validate(&cfgs[i], pool->cfg.nof_ports, pool->nof_subc), cfgs[i].start_symbol,
+                               cfgs[i].nof_symbols);
     if (rc != NRPHY_OK) {
       return rc;
-    }
-    if (ul_slot_accept_receiver(s->order, cfgs[i].start_symbol, cfgs[i].nof_symbols) != NRPHY_OK) {
-      return NRPHY_ERR_ARGUMENT;
     }
   }
   int rc = ul_slot_take_count(s->order.lim.max_srs, used.n_srs, n);
   if (rc != NRPHY_OK) {
     return rc;
   }
-  const std::vector<uint32_t>           grid_of(n, 0);
-  std::lock_guard<std::recursive_mutex> host_lock(pool->ctx->host_mutex);
-  HIP_TRY(hipSetDevice(pool->ctx->device));
+  const PlanCall call(pool, n);
+  HIP_TRY(call.device);
   nrphy_srs_plan_t* plan = nullptr;
-  rc = nrphy_srs_plan_create(pool->ctx, n, cfgs, grid_of.data(), 1, pool->cfg.nof_ports, pool->nof_subc, &plan);
+  rc = nrphy_srs_plan_create(pool->ctx, n, cfgs, call.grid_of.data(), 1, pool->cfg.nof_ports, pool->nof_subc, &plan);
   if (rc != NRPHY_OK) {
     return rc;
   }
@@ -597,7 +541,7 @@ extern "C" int nrphy_ul_slot_srs(nrphy_ul_slots_t* pool, uint32_t slot_id, uint3
 
 extern "C" int nrphy_ul_slot_finish(nrphy_ul_slots_t* pool, uint32_t slot_id, nrphy_ul_slot_done_fn done, void* user)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -607,15 +551,12 @@ extern "C" int nrphy_ul_slot_finish(nrphy_ul_slots_t* pool, uint32_t slot_id, nr
   }
   HIP_TRY(hipSetDevice(pool->ctx->device));
   s->order.finished = true;
-  s->done           = done;
-  s->user           = user;
-  s->state.store(SLOT_FINISHING, std::memory_order_release);
+  slot_arm(*s, done, user);
   if ((pool->layout.host_bytes != 0 &&
        hipMemcpyAsync(s->h_res, s->d_res, pool->layout.host_bytes, hipMemcpyDeviceToHost, s->stream) != hipSuccess) ||
       hipStreamAddCallback(s->stream, on_slot_done, s, 0) != hipSuccess) {
     (void)hipStreamSynchronize(s->stream);
-    s->status.store(NRPHY_ERR_DEVICE, std::memory_order_relaxed);
-    s->state.store(SLOT_DONE, std::memory_order_release);
+    slot_fail_armed(*s);
     return NRPHY_ERR_DEVICE;
   }
   return NRPHY_OK;
@@ -623,34 +564,17 @@ extern "C" int nrphy_ul_slot_finish(nrphy_ul_slots_t* pool, uint32_t slot_id, nr
 
 extern "C" int nrphy_ul_slot_poll(nrphy_ul_slots_t* pool, uint32_t slot_id)
 {
-  if (pool == nullptr || slot_id >= pool->slots.size()) {
-    return NRPHY_ERR_ARGUMENT;
-  }
-  const UlSlot& s = pool->slots[slot_id];
-  switch (s.state.load(std::memory_order_acquire)) {
-    case SLOT_DONE:
-      return s.status.load(std::memory_order_relaxed);
-    case SLOT_FREE:
-      return NRPHY_ERR_ARGUMENT;
-    default:
-      return NRPHY_ERR_NOT_READY;
-  }
+  return slot_pool_poll(pool, slot_id);
 }
 
 extern "C" int nrphy_ul_slot_wait(nrphy_ul_slots_t* pool, uint32_t slot_id)
 {
-  UlSlot* s = open_slot(pool, slot_id);
-  if (s == nullptr || s->state.load(std::memory_order_acquire) == SLOT_OPEN) {
-    return NRPHY_ERR_ARGUMENT; // nothing to wait for
-  }
-  std::unique_lock<std::mutex> lock(pool->mutex);
-  pool->changed.wait(lock, [s] { return s->state.load(std::memory_order_acquire) != SLOT_FINISHING; });
-  return s->state.load(std::memory_order_acquire) == SLOT_DONE ? s->status.load(std::memory_order_relaxed) : NRPHY_ERR_ARGUMENT;
+  return slot_pool_wait(pool, slot_id);
 }
 
 extern "C" int nrphy_ul_slot_read_grid(nrphy_ul_slots_t* pool, uint32_t slot_id, void* grid)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || grid == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -665,20 +589,20 @@ extern "C" int nrphy_ul_slot_read_grid(nrphy_ul_slots_t* pool, uint32_t slot_id,
 
 extern "C" void* nrphy_ul_slot_device_grid(nrphy_ul_slots_t* pool, uint32_t slot_id)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   return s ? s->d_grid : nullptr;
 }
 
 extern "C" void* nrphy_ul_slot_stream(nrphy_ul_slots_t* pool, uint32_t slot_id)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   return s ? (void*)s->stream : nullptr;
 }
 
 // ---- accessors: pointer arithmetic into the pinned result block ------------------------------------------------------------
 extern "C" const nrphy_pusch_result_t* nrphy_ul_slot_pusch_results(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t* n)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || n == nullptr) {
     return nullptr;
   }
@@ -688,7 +612,7 @@ extern "C" const nrphy_pusch_result_t* nrphy_ul_slot_pusch_results(nrphy_ul_slot
 
 extern "C" const uint8_t* nrphy_ul_slot_tb(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t i, uint32_t* nbytes)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || nbytes == nullptr || i >= s->order.used.n_pusch) {
     return nullptr;
   }
@@ -698,7 +622,7 @@ extern "C" const uint8_t* nrphy_ul_slot_tb(nrphy_ul_slots_t* pool, uint32_t slot
 
 extern "C" const uint8_t* nrphy_ul_slot_pusch_uci(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t i, uint32_t* nbits)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || nbits == nullptr || i >= s->order.used.n_pusch) {
     return nullptr;
   }
@@ -708,7 +632,7 @@ extern "C" const uint8_t* nrphy_ul_slot_pusch_uci(nrphy_ul_slots_t* pool, uint32
 
 extern "C" const nrphy_pucch_result_t* nrphy_ul_slot_pf01_results(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t* n)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || n == nullptr) {
     return nullptr;
   }
@@ -719,7 +643,7 @@ extern "C" const nrphy_pucch_result_t* nrphy_ul_slot_pf01_results(nrphy_ul_slots
 extern "C" int nrphy_ul_slot_format2_results(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t i, const uint8_t** message, uint32_t* nbits,
                                          uint32_t* status, nrphy_pf2_csi_t* csi)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || i >= s->order.used.n_pf2) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -740,7 +664,7 @@ extern "C" int nrphy_ul_slot_format2_results(nrphy_ul_slots_t* pool, uint32_t sl
 
 extern "C" const nrphy_srs_result_t* nrphy_ul_slot_sounding_results(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t* n)
 {
-  UlSlot* s = open_slot(pool, slot_id);
+  UlSlot* s = slot_pool_lookup(pool, slot_id);
   if (s == nullptr || n == nullptr) {
     return nullptr;
   }

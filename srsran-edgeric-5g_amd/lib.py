@@ -1327,9 +1327,62 @@ class PdschAsyncQueue:
             pass
 
 
-class DlSlotPool:
+class _SlotPool:
+    """What DlSlotPool and UlSlots share: the per-slot calls that differ in the C prefix alone (`_PREFIX`: nrphy_dl_slot /
+    nrphy_ul_slot), the two calls on the pool itself (`_WAIT_FREE`, `_DESTROY`: their C names) and the done-callback trampolines
+    (`_DONE_FN`), kept alive until their slot is closed."""
+    _PREFIX = _WAIT_FREE = _DESTROY = _DONE_FN = None
+
+    def _adopt(self, handle):
+        self.handle = handle
+        self._keep = {}
+
+    def _call(self, name, *args):
+        return getattr(self.ctx.lib, self._PREFIX + name)(self.handle, *args)
+
+    def _done_callback(self, sid, on_done):
+        """The C callback that runs on_done(status, slot_id), or None."""
+        if on_done is None:
+            return None
+        cb = self._DONE_FN(lambda user, status, slot_id: on_done(status, slot_id))
+        self._keep[sid] = cb
+        return cb
+
+    def close(self, sid):
+        _check(self._call("_close", sid), self._PREFIX + "_close")
+        self._keep.pop(sid, None)
+
+    def wait_free(self):
+        _check(getattr(self.ctx.lib, self._WAIT_FREE)(self.handle), self._WAIT_FREE)
+
+    def poll(self, sid):
+        return int(self._call("_poll", sid))
+
+    def wait(self, sid):
+        return int(self._call("_wait", sid))
+
+    def read_grid(self, sid):
+        grid = np.zeros((self.nof_ports, 14, self.nof_subc, 2), dtype=np.uint16)
+        _check(self._call("_read_grid", sid, grid.ctypes.data), self._PREFIX + "_read_grid")
+        return grid
+
+    def destroy(self):
+        if self.handle:
+            getattr(self.ctx.lib, self._DESTROY)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+class DlSlotPool(_SlotPool):
     """nrphy_dl_slots: the downlink slot pipeline -- every channel of a slot written into ONE device-resident grid, the
     whole slot modulated at grid hand-over, IQ served from pinned host memory (pdxch_processor_impl.cpp:47-112)."""
+    _PREFIX, _DONE_FN = "nrphy_dl_slot", abi.DL_SLOT_DONE_FN
+    _WAIT_FREE, _DESTROY = "nrphy_dl_slots_wait_free", "nrphy_dl_slots_destroy"
 
     def __init__(self, ctx, ofdm_cfg, nof_ports, depth, max_tb_bytes, wire_cfg=None):
         self.ctx, self.cfg, self.nof_ports = ctx, ofdm_cfg, nof_ports
@@ -1342,8 +1395,7 @@ class DlSlotPool:
         self.wire = wire_cfg is not None
         h = C.c_void_p()
         _check(ctx.lib.nrphy_dl_slots_create(ctx.handle, C.byref(c), C.byref(h)), "nrphy_dl_slots_create")
-        self.handle = h
-        self._keep = {}
+        self._adopt(h)
 
     def open(self):
         """A free slot with an all-zero grid, or None when all `depth` slots are open."""
@@ -1353,13 +1405,6 @@ class DlSlotPool:
             return None
         _check(rc, "nrphy_dl_slot_open")
         return sid.value
-
-    def close(self, sid):
-        _check(self.ctx.lib.nrphy_dl_slot_close(self.handle, sid), "nrphy_dl_slot_close")
-        self._keep.pop(sid, None)
-
-    def wait_free(self):
-        _check(self.ctx.lib.nrphy_dl_slots_wait_free(self.handle), "nrphy_dl_slots_wait_free")
 
     def pdsch(self, sid, pdus, tbs):
         n = len(pdus)
@@ -1391,17 +1436,7 @@ class DlSlotPool:
 
     def modulate(self, sid, subframe_slot_index, on_done=None):
         """on_done(status, slot_id) runs on a HIP runtime thread when the slot's IQ is in pinned host memory."""
-        cb = None
-        if on_done is not None:
-            cb = abi.DL_SLOT_DONE_FN(lambda user, status, slot_id: on_done(status, slot_id))
-            self._keep[sid] = cb
-        return self.ctx.lib.nrphy_dl_slot_modulate(self.handle, sid, subframe_slot_index, cb, None)
-
-    def poll(self, sid):
-        return self.ctx.lib.nrphy_dl_slot_poll(self.handle, sid)
-
-    def wait(self, sid):
-        return self.ctx.lib.nrphy_dl_slot_wait(self.handle, sid)
+        return self.ctx.lib.nrphy_dl_slot_modulate(self.handle, sid, subframe_slot_index, self._done_callback(sid, on_done), None)
 
     def iq(self, sid, port):
         """A copy of the slot's samples of `port`: complex64, or int16 pairs [n][2] for a wire-format pool."""
@@ -1420,27 +1455,13 @@ class DlSlotPool:
         C.memmove(C.byref(st), p, C.sizeof(abi.AmplitudeStats))
         return st
 
-    def read_grid(self, sid):
-        grid = np.zeros((self.nof_ports, 14, self.nof_subc, 2), dtype=np.uint16)
-        _check(self.ctx.lib.nrphy_dl_slot_read_grid(self.handle, sid, grid.ctypes.data), "nrphy_dl_slot_read_grid")
-        return grid
 
-    def destroy(self):
-        if self.handle:
-            self.ctx.lib.nrphy_dl_slots_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
-
-
-class UlSlots:
+class UlSlots(_SlotPool):
     """nrphy_ul_slots: the uplink slot pipeline -- samples demodulated run by run into ONE device-resident grid, every receiver
     of the slot on that grid, the results served from pinned host memory (puxch_processor_impl.cpp:30-97,
     uplink_processor_impl.cpp:86-170).  The calls that the order rules may refuse return the status; the others raise."""
+    _PREFIX, _DONE_FN = "nrphy_ul_slot", abi.UL_SLOT_DONE_FN
+    _WAIT_FREE, _DESTROY = "nrphy_ul_slots_wait_free", "nrphy_ul_slots_destroy"
 
     def __init__(self, ctx, ofdm_cfg, nof_ports, depth, iq_format=abi.IQ_CF32, iq_scale=1.0, window_offset=0, max_pusch=0,
                  max_pucch=0, max_pf2=0, max_srs=0, max_tb_bytes=0, max_uci_bits=0, d_harq=None):
@@ -1454,8 +1475,7 @@ class UlSlots:
         self._harq = d_harq  # the caller's arena stays alive with the pool
         h = C.c_void_p()
         _check(ctx.lib.nrphy_ul_slots_create(ctx.handle, C.byref(c), _dptr(d_harq), C.byref(h)), "nrphy_ul_slots_create")
-        self.handle = h
-        self._keep = {}
+        self._adopt(h)
 
     def open(self, subframe_slot_index=0):
         """A free slot with an all-zero grid, or None when all `depth` slots are open."""
@@ -1465,13 +1485,6 @@ class UlSlots:
             return None
         _check(rc, "nrphy_ul_slot_open")
         return sid.value
-
-    def close(self, sid):
-        _check(self.ctx.lib.nrphy_ul_slot_close(self.handle, sid), "nrphy_ul_slot_close")
-        self._keep.pop(sid, None)
-
-    def wait_free(self):
-        _check(self.ctx.lib.nrphy_ul_slots_wait_free(self.handle), "nrphy_ul_slots_wait_free")
 
     def samples(self, sid, first_symbol, nof_symbols, port_samples):
         """port_samples: per port the samples of the run, complex64 [n] or (abi.IQ_CI16 pools) int16 [n][2]."""
@@ -1516,22 +1529,7 @@ class UlSlots:
 
     def finish(self, sid, on_done=None):
         """on_done(status, slot_id) runs on a HIP runtime thread when the slot's results are in pinned host memory."""
-        cb = None
-        if on_done is not None:
-            cb = abi.UL_SLOT_DONE_FN(lambda user, status, slot_id: on_done(status, slot_id))
-            self._keep[sid] = cb
-        return int(self.ctx.lib.nrphy_ul_slot_finish(self.handle, sid, cb, None))
-
-    def poll(self, sid):
-        return int(self.ctx.lib.nrphy_ul_slot_poll(self.handle, sid))
-
-    def wait(self, sid):
-        return int(self.ctx.lib.nrphy_ul_slot_wait(self.handle, sid))
-
-    def read_grid(self, sid):
-        grid = np.zeros((self.nof_ports, 14, self.nof_subc, 2), dtype=np.uint16)
-        _check(self.ctx.lib.nrphy_ul_slot_read_grid(self.handle, sid, grid.ctypes.data), "nrphy_ul_slot_read_grid")
-        return grid
+        return int(self.ctx.lib.nrphy_ul_slot_finish(self.handle, sid, self._done_callback(sid, on_done), None))
 
     def _records(self, fn, sid, cls):
         n = C.c_uint32()
@@ -1570,17 +1568,6 @@ class UlSlots:
 
     def srs_results(self, sid):
         return self._records(self.ctx.lib.nrphy_ul_slot_sounding_results, sid, abi.SrsResult)
-
-    def destroy(self):
-        if self.handle:
-            self.ctx.lib.nrphy_ul_slots_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.destroy()
-        except Exception:
-            pass
 
 
 class OfdmPlan:
