@@ -1,11 +1,12 @@
 // Arithmetic of port_channel_estimator_average_impl (R/lib/phy/upper/signal_processors/port_channel_estimator_average_impl.cpp)
 // shared by the kernels that run it with the `filter` smoothing strategy: the PUSCH DM-RS estimator (pusch_chest_kernels.hip) and
-// the PUCCH format 2 receiver (pucch2_kernels.hip).  One copy, so that both round alike: transcendentals (atan2, hypot, cos,
-// sin) are evaluated in double and rounded once to float, products are written out per component, contraction is off.  The
-// raised-cosine table and the taps derived from it are plan-time constants: chest_host.h.
+// the PUCCH format 2 receiver (pucch2_kernels.hip).  One copy, so that both round alike.  The operations it is made of --
+// constants, products, the phasor, the time-alignment search's comparison -- are exact_device.h's, which the other receivers
+// share too.  The raised-cosine table and the taps derived from it are plan-time constants: chest_host.h.
 #pragma once
 
 #include "bits_device.h"
+#include "exact_device.h"
 
 #include <hip/hip_runtime.h>
 
@@ -13,26 +14,6 @@ namespace nrphy {
 namespace {
 
 constexpr uint32_t CHEST_TA_BINS = 2 * PUSCH_CHEST_TA_WINDOW;
-constexpr float    TWOPI_F       = 6.28318548f; // 2.0F * static_cast<float>(M_PI)
-constexpr float    PI_F          = 3.14159274f;
-constexpr float    SQRT1_2_F     = 0.707106769f;
-
-__device__ __forceinline__ uint32_t to_cbf16(float re, float im)
-{
-  return to_bf16_bits(re) | (to_bf16_bits(im) << 16);
-}
-
-// std::polar(1.0F, x) with cos and sin evaluated in double and rounded once.
-__device__ __forceinline__ float2 phasor(float x)
-{
-  return make_float2((float)cos((double)x), (float)sin((double)x));
-}
-
-// (a + jb)(c + jd) as std::complex<float> writes it.
-__device__ __forceinline__ float2 cmul(float2 x, float2 h)
-{
-  return make_float2(__fsub_rn(__fmul_rn(x.x, h.x), __fmul_rn(x.y, h.y)), __fadd_rn(__fmul_rn(x.x, h.y), __fmul_rn(x.y, h.x)));
-}
 
 // compute_v_pilots: a linear fit of |.| and of the unwrapped argument of n pilots, evaluated at i + offset.  In two steps, so that
 // a kernel may fit on one lane and evaluate on several: the fit (serial by nature: unwrap_list, R/lib/srsvec/unwrap.cpp, and four

@@ -1,24 +1,14 @@
 // The channel equaliser's per-RE arithmetic, shared by the kernels that equalise: the PUSCH demodulator and the standalone
-// equaliser (pusch_demod_kernels.hip) and the PUCCH format 1 detector (pucch_kernels.hip).  One function, so that every caller
-// gets the same bits.
+// equaliser (pusch_demod_kernels.hip), the PUCCH format 1 detector (pucch_kernels.hip) and the PUCCH format 2 receiver
+// (pucch2_kernels.hip).  One function, so that every caller gets the same bits.  is_normal and the infinity are exact_device.h's.
 #pragma once
 
 #include "bits_device.h"
+#include "exact_device.h"
 
 #include <hip/hip_runtime.h>
 
 namespace nrphy {
-
-constexpr float FLT_NORMAL_MIN = 1.17549435e-38f;
-constexpr float FLT_LARGEST    = 3.40282347e+38f;
-constexpr float F_INF          = __builtin_huge_valf();
-
-// std::isnormal
-__device__ __forceinline__ bool is_normal(float x)
-{
-  const float a = fabsf(x);
-  return a >= FLT_NORMAL_MIN && a <= FLT_LARGEST;
-}
 
 // One RE of channel_equalizer::equalize, the reference's scalar arithmetic operation by operation (std::complex products written
 // out: (a + jb) conj(c + jd) = (ac + bd) + j(bc - ad)), contraction off, exact division.  y[i]: received word of receive port i;

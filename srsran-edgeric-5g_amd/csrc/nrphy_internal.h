@@ -475,7 +475,7 @@ struct PuschChestLaunch {
   const PuschChestDesc*     desc;
   const uint32_t*           jobs;              // (pusch << 8) | (port << 4) | layer
   const uint16_t*           prbs;
-  const float2*             twiddle;           // [2048]: e^{j 2 pi i / 2048}
+  const float2*             twiddle;           // the context's e^{j 2 pi i / 2048}, i < 2048
   const GoldTables*         gold;
   const uint32_t*           x1_words;
   const uint32_t*           grid;
@@ -602,7 +602,7 @@ struct Pf2Desc {                                              // one PUCCH of a 
 };
 struct Pf2Launch {
   const Pf2Desc*            desc;
-  const float2*             twiddle;                          // [PF2_TW_WORDS]
+  const float2*             twiddle;                          // the context's e^{j 2 pi i / 4096}: its first PF2_TW_WORDS are read
   const GoldTables*         gold;
   const uint32_t*           x1_words;
   const uint32_t*           grid;

@@ -13,9 +13,8 @@
 //      the groups form the metric, its maximum and the decision, and write every preamble slot of the sequence exactly once.
 //   3. prach_finish_kernel: one wavefront per occasion; the number of detections and their mask (a ballot, no atomics).
 // Every sum has a fixed order, so two runs give identical bytes.
+#include "exact_device.h"
 #include "fft_device.h"
-
-#include <cfloat>
 
 namespace nrphy {
 
@@ -28,12 +27,6 @@ __device__ __forceinline__ float round_to_tc(double seconds)
   const int64_t tc_units     = (int64_t)(tc_units_dbl * 10.0);
   const int64_t value        = tc_units / 10 + (tc_units % 10) / 5;
   return (float)((double)value * PRACH_T_C);
-}
-
-__device__ __forceinline__ bool is_normal(float v)
-{
-  const float a = fabsf(v);
-  return a >= FLT_MIN && a <= FLT_MAX; // false for zero, subnormals, infinities and NaN
 }
 
 // y[n] = table[(2 (u f n (f n + 1) + 2 C_v n) + offset) mod 4L], every product reduced mod 4L so that 32 bits suffice.

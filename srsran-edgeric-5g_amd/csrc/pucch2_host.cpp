@@ -5,8 +5,6 @@
 // seed, the taps, virtual pilots and symbol epochs of chest_host.h, and the UCI decoder plan over the batch's messages.
 #include "chest_host.h"
 
-#include <cmath>
-
 namespace {
 
 constexpr float MAX_CODE_RATE = 0.80F; // pucch_constants::MAX_CODE_RATE
@@ -84,7 +82,7 @@ struct nrphy_pf2_plan {
   float                     demod_range = 0.f, demod_scale = 0.f;
   void*                     d_arena = nullptr;
   Pf2Desc*                  d_desc  = nullptr;
-  float2*                   d_tw    = nullptr;
+  const float2*             twiddle = nullptr; // the context's e^{j 2 pi i / 4096}: not the plan's to free
   nrphy_uci_decoder_plan_t* uci     = nullptr;
 };
 
@@ -171,13 +169,15 @@ extern "C" int nrphy_pf2_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_p
     d.ce_offset  = ce_offset != nullptr ? ce_offset[i] : 0;
     uci[i]       = {c.nof_harq_ack + c.nof_sr + c.nof_csi_part1, nof_llr(c), NRPHY_MOD_QPSK, 0};
   }
-  std::vector<float2> tw(PF2_TW_WORDS);
-  for (uint32_t i = 0; i != PF2_TW_WORDS; ++i) {
-    const double a = 2.0 * M_PI * i / 4096.0;
-    tw[i]          = make_float2((float)std::cos(a), (float)std::sin(a));
+  // The time-alignment search's twiddles are the first quadrant of the context's table, built on first use.
+  static_assert(PF2_TW_WORDS == 4096 / 4, "the first quadrant");
+  const float2* twiddle = hipSetDevice(ctx->device) == hipSuccess ? get_twiddle_table(ctx, 4096) : nullptr;
+  if (twiddle == nullptr) {
+    return NRPHY_ERR_DEVICE;
   }
   auto* plan           = new nrphy_pf2_plan;
   plan->ctx            = ctx;
+  plan->twiddle        = twiddle;
   plan->n              = n;
   plan->grid_nof_ports = grid_nof_ports;
   plan->grid_nof_subc  = grid_nof_subc;
@@ -191,9 +191,8 @@ extern "C" int nrphy_pf2_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_p
   }
   DeviceArena arena;
   arena.add(&plan->d_desc, desc.data(), desc.size() * sizeof(Pf2Desc));
-  arena.add(&plan->d_tw, tw.data(), tw.size() * sizeof(float2));
   void* unused = nullptr;
-  if (hipSetDevice(ctx->device) != hipSuccess || arena.commit(&plan->d_arena, 0, &unused) != hipSuccess) {
+  if (arena.commit(&plan->d_arena, 0, &unused) != hipSuccess) {
     nrphy_pf2_plan_destroy(plan);
     return NRPHY_ERR_DEVICE;
   }
@@ -212,7 +211,7 @@ extern "C" int nrphy_pf2_run(nrphy_pf2_plan_t* plan, const void* d_grid, int8_t*
   }
   Pf2Launch p;
   p.desc           = plan->d_desc;
-  p.twiddle        = plan->d_tw;
+  p.twiddle        = plan->twiddle;
   p.gold           = plan->ctx->d_gold;
   p.x1_words       = plan->ctx->d_x1;
   p.grid           = (const uint32_t*)d_grid;

@@ -70,21 +70,6 @@ __device__ __forceinline__ float2 twiddle4096(const float2* tw, uint32_t i)
   return q == 0 ? w : q == 1 ? make_float2(-w.y, w.x) : q == 2 ? make_float2(-w.x, -w.y) : make_float2(w.y, -w.x);
 }
 
-// convert_power_to_dB
-__device__ __forceinline__ float to_dB(float v)
-{
-  return __fmul_rn(10.0f, (float)log10((double)v));
-}
-
-// The larger of two (magnitude, bin) candidates; the lower bin on equal magnitudes (max_abs_element returns the first maximum).
-__device__ __forceinline__ void take_max(float& m, uint32_t& i, float m2, uint32_t i2)
-{
-  if (m2 > m || (m2 == m && i2 < i)) {
-    m = m2;
-    i = i2;
-  }
-}
-
 // The plan's descriptor through the constant address space: it never changes while the kernel runs, and saying so lets its
 // fields come by scalar loads that need not be repeated behind the kernel's own stores.
 typedef const NRPHY_CONSTANT Pf2Desc& Pf2DescRef;
@@ -103,14 +88,10 @@ __device__ void pf2_estimate_port(const Pf2Launch& p, Pf2DescRef d, uint32_t ip,
 #pragma unroll
   for (uint32_t l = 0; l != PF2_MAX_SYMBOLS; ++l) {
     if (l < ns && mine) {
-      const uint32_t b  = 8u * d.prb0 + 2u * lane; // the pilot's bits: b even, both in one word
-      const uint32_t w0 = s.seq[l][b >> 5];
-      const uint32_t c0 = (w0 >> (31u - (b & 31u))) & 1u, c1 = (w0 >> (30u - (b & 31u))) & 1u;
-      pl[l]             = make_float2(c0 ? -SQRT1_2_F : SQRT1_2_F, c1 ? -SQRT1_2_F : SQRT1_2_F);
-      y[l]              = cbf16_to_float2(w.rx[l][k_pilot]);
-      epre += (double)__fadd_rn(__fmul_rn(y[l].x, y[l].x), __fmul_rn(y[l].y, y[l].y));
-      ls[l] = make_float2(__fadd_rn(__fmul_rn(y[l].x, pl[l].x), __fmul_rn(y[l].y, pl[l].y)),
-                          __fsub_rn(__fmul_rn(y[l].y, pl[l].x), __fmul_rn(y[l].x, pl[l].y)));
+      pl[l] = qpsk_pilot(s.seq[l], 8u * d.prb0 + 2u * lane);
+      y[l]  = cbf16_to_float2(w.rx[l][k_pilot]);
+      epre += (double)exact::norm(y[l]);
+      ls[l] = exact::mul_conj(y[l], pl[l]);
     }
   }
   epre       = wave_sum(epre);
@@ -119,8 +100,8 @@ __device__ void pf2_estimate_port(const Pf2Launch& p, Pf2DescRef d, uint32_t ip,
   float2 rot[PF2_MAX_SYMBOLS] = {make_float2(1.f, 0.f), make_float2(1.f, 0.f)};
   if (ns >= 2u) { // wave-uniform
     // dot_prod(LS1, LS0) = sum LS1 conj(LS0)
-    const double dr    = wave_sum((double)__fadd_rn(__fmul_rn(ls[1].x, ls[0].x), __fmul_rn(ls[1].y, ls[0].y)));
-    const double di    = wave_sum((double)__fsub_rn(__fmul_rn(ls[1].y, ls[0].x), __fmul_rn(ls[1].x, ls[0].y)));
+    const float2 dot   = exact::mul_conj(ls[1], ls[0]);
+    const double dr = wave_sum((double)dot.x), di = wave_sum((double)dot.y);
     const float  phase = (float)atan2((double)(float)di, (double)(float)dr);
     cfo                = __fdiv_rn(__fdiv_rn(phase, TWOPI_F), __fsub_rn(d.epoch[1], d.epoch[0]));
     // The phasor of a symbol, e^{j 2 pi epoch cfo}, is evaluated once: derotation uses its conjugate (the argument's sign flips
@@ -128,7 +109,7 @@ __device__ void pf2_estimate_port(const Pf2Launch& p, Pf2DescRef d, uint32_t ip,
     rot[0] = phasor(__fmul_rn(__fmul_rn(TWOPI_F, d.epoch[0]), cfo));
     rot[1] = phasor(__fmul_rn(__fmul_rn(TWOPI_F, d.epoch[1]), cfo));
     const float2 r0 = make_float2(rot[0].x, -rot[0].y), r1 = make_float2(rot[1].x, -rot[1].y);
-    const float2 a = cmul(ls[0], r0), c = cmul(ls[1], r1);
+    const float2 a = exact::cmul(ls[0], r0), c = exact::cmul(ls[1], r1);
     A              = make_float2(__fadd_rn(a.x, c.x), __fadd_rn(a.y, c.y));
   }
   A = make_float2(__fmul_rn(A.x, d.ls_scale), __fmul_rn(A.y, d.ls_scale)); // average; the DM-RS-to-data gain is 1
@@ -167,7 +148,7 @@ __device__ void pf2_estimate_port(const Pf2Launch& p, Pf2DescRef d, uint32_t ip,
     }
     w.b[lane] = f;
   }
-  const double pw   = wave_sum(mine ? (double)__fadd_rn(__fmul_rn(f.x, f.x), __fmul_rn(f.y, f.y)) : 0.0);
+  const double pw   = wave_sum(mine ? (double)exact::norm(f) : 0.0);
   const float  rsrp = (float)(pw / (double)N);
 
   // ---- noise (estimate_noise) ---------------------------------------------------------------------------------------------------
@@ -175,12 +156,12 @@ __device__ void pf2_estimate_port(const Pf2Launch& p, Pf2DescRef d, uint32_t ip,
 #pragma unroll
   for (uint32_t l = 0; l != PF2_MAX_SYMBOLS; ++l) {
     if (l < ns) { // wave-uniform
-      float2 e = cmul(make_float2(__fmul_rn(f.x, -1.0f), __fmul_rn(f.y, -1.0f)), pl[l]);
+      float2 e = exact::cmul(make_float2(__fmul_rn(f.x, -1.0f), __fmul_rn(f.y, -1.0f)), pl[l]);
       if (ns >= 2u) {
-        e = cmul(e, rot[l]);
+        e = exact::cmul(e, rot[l]);
       }
       e = make_float2(__fadd_rn(e.x, y[l].x), __fadd_rn(e.y, y[l].y));
-      ne += mine ? (double)__fadd_rn(__fmul_rn(e.x, e.x), __fmul_rn(e.y, e.y)) : 0.0;
+      ne += mine ? (double)exact::norm(e) : 0.0;
     }
   }
   ne = wave_sum(ne); // (its shuffles also order the writes of b)
@@ -197,26 +178,19 @@ __device__ void pf2_estimate_port(const Pf2Launch& p, Pf2DescRef d, uint32_t ip,
       uint32_t       i    = (k0 * n) & 4095u;
       float2         acc  = make_float2(0.f, 0.f);
       for (uint32_t q = 0; q != N; ++q) {
-        const float2 v = w.b[q];
-        const float2 t = twiddle4096(s.tw, i);
-        acc.x          = __fmaf_rn(v.x, t.x, __fmaf_rn(-v.y, t.y, acc.x));
-        acc.y          = __fmaf_rn(v.x, t.y, __fmaf_rn(v.y, t.x, acc.y));
-        i              = (i + step) & 4095u;
+        dft_accumulate(acc, w.b[q], twiddle4096(s.tw, i));
+        i = (i + step) & 4095u;
       }
-      const float m = __fadd_rn(__fmul_rn(acc.x, acc.x), __fmul_rn(acc.y, acc.y));
+      const float m = exact::norm(acc);
       if (b < PUSCH_CHEST_TA_WINDOW) {
         take_max(best_d, id, m, b);
       } else {
         take_max(best_a, ia, m, b - PUSCH_CHEST_TA_WINDOW);
       }
     }
-#pragma unroll
-    for (int o = WAVE / 2; o != 0; o >>= 1) {
-      take_max(best_d, id, __shfl_xor(best_d, o), __shfl_xor(id, o));
-      take_max(best_a, ia, __shfl_xor(best_a, o), __shfl_xor(ia, o));
-    }
+    wave_take_max(best_d, id, best_a, ia);
   }
-  const int ta_bins = best_d >= best_a ? (int)id : (int)ia - (int)PUSCH_CHEST_TA_WINDOW;
+  const int ta_bins = ta_signed_bin(best_d, id, best_a, ia, PUSCH_CHEST_TA_WINDOW);
 
   // ---- measurements ---------------------------------------------------------------------------------------------------------------
   const nrphy_pusch_chest_meas_t m = chest_measurements(rsrp, (float)(epre / (double)(N * ns)), (float)(ne / (double)(N * ns - 1u)), 1.0f,
@@ -261,7 +235,7 @@ __device__ void pf2_estimate_port(const Pf2Launch& p, Pf2DescRef d, uint32_t ip,
       if (l < ns) {
         uint32_t v = base;
         if (ns >= 2u) {
-          const float2 e = cmul(cbf16_to_float2(base), rot[l]);
+          const float2 e = exact::cmul(cbf16_to_float2(base), rot[l]);
           v              = to_cbf16(e.x, e.y);
         }
         w.u.est[l][k] = v;
@@ -311,27 +285,18 @@ __global__ __launch_bounds__(PF2_THREADS) void pf2_kernel(Pf2Launch p)
 
   // ---- channel state information (get_channel_state_information), by one thread of the last wave --------------------------------
   if (tid == PF2_THREADS - 1u) {
-    float    epre_lin = 0.f, rsrp_lin = 0.f, noise_all = 0.f, best_snr = 0.f;
-    uint32_t best = 0;
+    CsiMerge csi;
     for (uint32_t q = 0; q != P; ++q) {
       const nrphy_pusch_chest_meas_t& m = s.port[q].meas;
-      epre_lin  = __fadd_rn(epre_lin, m.epre);
-      rsrp_lin  = __fadd_rn(rsrp_lin, m.rsrp);
-      noise_all = __fadd_rn(noise_all, m.noise_var);
-      if (m.snr > best_snr) { // best_rx_port starts at 0 and moves on a strictly better SNR
-        best_snr = m.snr;
-        best     = q;
-      }
+      csi.add(q, m.noise_var, m.rsrp, m.epre, m.snr, m.ta_s, m.cfo_hz);
     }
-    const float     fp   = (float)P;
-    const float     sinr = is_normal(noise_all) ? __fdiv_rn(rsrp_lin, noise_all) : 1e6f;
-    nrphy_pf2_csi_t c    = {};
-    c.sinr_dB            = to_dB(sinr);
-    c.rsrp_dB            = to_dB(__fdiv_rn(rsrp_lin, fp));
-    c.epre_dB            = to_dB(__fdiv_rn(epre_lin, fp));
-    c.time_alignment_s   = s.port[best].meas.ta_s;
-    c.cfo_hz             = s.port[best].meas.cfo_hz;
-    p.csi[ip]            = c;
+    nrphy_pf2_csi_t c  = {};
+    c.sinr_dB          = csi.sinr_dB();
+    c.rsrp_dB          = csi.rsrp_dB(P);
+    c.epre_dB          = csi.epre_dB(P);
+    c.time_alignment_s = csi.ta_s;
+    c.cfo_hz           = csi.cfo_hz;
+    p.csi[ip]          = c;
   }
 
   // ---- data: thread t, data RE t (symbol by symbol, subcarriers ascending, k mod 3 != 1) -------------------------------------------

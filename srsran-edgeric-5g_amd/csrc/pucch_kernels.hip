@@ -29,38 +29,14 @@
 namespace nrphy {
 namespace {
 
-constexpr uint32_t PUCCH_WAVES = 4;           // PUCCHs per workgroup
-constexpr float    TWOPI_F     = 6.28318548f; // 2.0F * static_cast<float>(M_PI)
+constexpr uint32_t PUCCH_WAVES = 4;    // PUCCHs per workgroup
 constexpr float    THRESHOLD   = 4.0f;
-constexpr uint32_t MAX_DMRS    = 7;           // DM-RS symbols of a hop: 14 symbols without hopping
-
-// (a + jb)(c + jd) as std::complex<float> writes it.
-__device__ __forceinline__ float2 cmul(float2 x, float2 h)
-{
-  return make_float2(__fsub_rn(__fmul_rn(x.x, h.x), __fmul_rn(x.y, h.y)), __fadd_rn(__fmul_rn(x.x, h.y), __fmul_rn(x.y, h.x)));
-}
-
-// y conj(p) (srsvec::prod_conj).
-__device__ __forceinline__ float2 mul_conj(float2 y, float2 p)
-{
-  return make_float2(__fadd_rn(__fmul_rn(y.x, p.x), __fmul_rn(y.y, p.y)), __fsub_rn(__fmul_rn(y.y, p.x), __fmul_rn(y.x, p.y)));
-}
-
-__device__ __forceinline__ float norm(float2 v)
-{
-  return __fadd_rn(__fmul_rn(v.x, v.x), __fmul_rn(v.y, v.y));
-}
-
-// convert_power_to_dB
-__device__ __forceinline__ float to_dB(float v)
-{
-  return __fmul_rn(10.0f, (float)log10((double)v));
-}
+constexpr uint32_t MAX_DMRS    = 7;    // DM-RS symbols of a hop: 14 symbols without hopping
 
 // r_uv^alpha(n), length 12: the base sequence times the cyclic shift (low_papr_sequence_generator_impl::generate).
 __device__ __forceinline__ float2 low_papr(const PucchTables& t, uint32_t u, uint32_t alpha, uint32_t n)
 {
-  return cmul(t.base[u][n], t.shift[(2u * alpha * n) % 24u]);
+  return exact::cmul(t.base[u][n], t.shift[(2u * alpha * n) % 24u]);
 }
 
 // Sum over the 4 lanes of a group in a fixed order; every lane of the group gets the result.
@@ -135,15 +111,15 @@ __device__ void pucch_format0(const PucchLaunch& p, const PucchDesc& d, uint32_t
 #pragma unroll
     for (uint32_t k = 0; k != NRPHY_NRE; ++k) {
       const float2 y   = cbf16_to_float2(word_of(w[k >> 2], k & 3u));
-      const float2 lse = mul_conj(y, low_papr(t, d.u, alpha, k));
-      pw_y += (double)norm(y);
-      pw_l += (double)norm(lse);
+      const float2 lse = exact::mul_conj(y, low_papr(t, d.u, alpha, k));
+      pw_y += (double)exact::norm(y);
+      pw_l += (double)exact::norm(lse);
       sr += (double)lse.x;
       si += (double)lse.y;
     }
     const float  avg_pwr = (float)(pw_l / 12.0);
     const float2 mean    = make_float2(__fdiv_rn((float)sr, 12.0f), __fdiv_rn((float)si, 12.0f));
-    corr                 = norm(mean);
+    corr                 = exact::norm(mean);
     const float diff     = __fsub_rn(avg_pwr, corr);
     nvc                  = __fmul_rn(diff > 0.f ? diff : 0.f, corr);
     avg_y                = (float)(pw_y / 12.0);
@@ -212,15 +188,16 @@ __device__ void pucch_format1(const PucchLaunch& p, const PucchDesc& d, uint32_t
 #pragma unroll
           for (uint32_t i = 0; i != 4; ++i) {
             const float2 y = cbf16_to_float2(word_of(yw[j], i));
-            z[j][i]        = cmul(low_papr(t, d.u, alpha, 4u * chunk + i), w); // z = w_i(m) r_uv^alpha
-            const float2 ls = mul_conj(y, z[j][i]);
-            pw += (double)norm(y);
+            z[j][i]        = exact::cmul(low_papr(t, d.u, alpha, 4u * chunk + i), w); // z = w_i(m) r_uv^alpha
+            const float2 ls = exact::mul_conj(y, z[j][i]);
+            pw += (double)exact::norm(y);
             if (j == 0) {
               lse[i] = ls;
             } else {
               if (j == 1) { // dot_prod(LS1, LS0) = sum LS1 conj(LS0)
-                dr += (double)__fadd_rn(__fmul_rn(ls.x, lse[i].x), __fmul_rn(ls.y, lse[i].y));
-                di += (double)__fsub_rn(__fmul_rn(ls.y, lse[i].x), __fmul_rn(ls.x, lse[i].y));
+                const float2 dot = exact::mul_conj(ls, lse[i]);
+                dr += (double)dot.x;
+                di += (double)dot.y;
               }
               lse[i] = make_float2(__fadd_rn(lse[i].x, ls.x), __fadd_rn(lse[i].y, ls.y));
             }
@@ -244,8 +221,8 @@ __device__ void pucch_format1(const PucchLaunch& p, const PucchDesc& d, uint32_t
       mi += (double)__fmul_rn(lse[i].y, scale);
     }
     const float2 h = make_float2((float)(group_sum4(mr) / 12.0), (float)(group_sum4(mi) / 12.0));
-    rsrp_hop       = __fmul_rn(__fmul_rn(norm(h), 12.0f), (float)nd);
-    h_word         = to_bf16_bits(h.x) | (to_bf16_bits(h.y) << 16);
+    rsrp_hop       = __fmul_rn(__fmul_rn(exact::norm(h), 12.0f), (float)nd);
+    h_word         = to_cbf16(h.x, h.y);
     // Noise (noise_no_cfo): |rx - h z|^2 per DM-RS symbol.
     const float2 neg_h = make_float2(-h.x, -h.y);
 #pragma unroll
@@ -256,8 +233,8 @@ __device__ void pucch_format1(const PucchLaunch& p, const PucchDesc& d, uint32_t
 #pragma unroll
           for (uint32_t i = 0; i != 4; ++i) {
             const float2 y = cbf16_to_float2(word_of(yw[j], i));
-            const float2 e = cmul(neg_h, z[j][i]);
-            pw += (double)norm(make_float2(__fadd_rn(e.x, y.x), __fadd_rn(e.y, y.y)));
+            const float2 e = exact::cmul(neg_h, z[j][i]);
+            pw += (double)exact::norm(make_float2(__fadd_rn(e.x, y.x), __fadd_rn(e.y, y.y)));
           }
         }
         noise_hop = __fadd_rn(noise_hop, __fmul_rn((float)(group_sum4(pw) / 12.0), 12.0f));
@@ -293,7 +270,7 @@ __device__ void pucch_format1(const PucchLaunch& p, const PucchDesc& d, uint32_t
   // ---- hops and ports merged (port_channel_estimator_average_impl::compute, get_channel_state_information) ------------------
   uint32_t hw[2][NRPHY_MAX_PORTS] = {}; // [hop][port]
   float    nv[NRPHY_MAX_PORTS]    = {};
-  float    epre_lin = 0.f, rsrp_lin = 0.f, noise_all = 0.f, rsrp_all = 0.f, best_snr = 0.f, best_cfo_hz = __builtin_nanf("");
+  CsiMerge csi;
   const float nof_pilots = (float)(NRPHY_NRE * nd_all), nof_pilots_1 = (float)(NRPHY_NRE * nd_all - 1u);
 #pragma unroll
   for (uint32_t q = 0; q != NRPHY_MAX_PORTS; ++q) {
@@ -318,17 +295,8 @@ __device__ void pucch_format1(const PucchLaunch& p, const PucchDesc& d, uint32_t
     const float snr       = noise_var != 0.f ? __fdiv_rn(rsrp, noise_var) : 1000.f;
     const float cfo_hz    = has0 || has1 ? __fmul_rn(__fmul_rn(cfo, (float)d.scs_khz), 1000.f) : __builtin_nanf("");
     if (q < P) {
-      nv[q]     = noise_var;
-      epre_lin  = __fadd_rn(epre_lin, epre);
-      rsrp_lin  = __fadd_rn(rsrp_lin, rsrp);
-      noise_all = __fadd_rn(noise_all, noise_var);
-      rsrp_all  = __fadd_rn(rsrp_all, rsrp);
-      if (q == 0 || snr > best_snr) { // best_rx_port starts at 0 and moves on a strictly better SNR
-        best_cfo_hz = cfo_hz;
-      }
-      if (snr > best_snr) {
-        best_snr = snr;
-      }
+      nv[q] = noise_var;
+      csi.add(q, noise_var, rsrp, epre, snr, 0.f, cfo_hz);
     }
     if (p.meas != nullptr && lane == q) {
       nrphy_pusch_chest_meas_t m = {};
@@ -375,7 +343,7 @@ __device__ void pucch_format1(const PucchLaunch& p, const PucchDesc& d, uint32_t
         float  v[2];
         equalize_re(NRPHY_EQ_ZF, 1u, P, y, h, nv, nv_max, 1.0f, x, v);
         const float2 r = low_papr(t, d.u, alpha, 4u * chunk + i);
-        const float2 e = cmul(cmul(x[0], w_star), make_float2(r.x, -r.y));
+        const float2 e = exact::cmul(exact::cmul(x[0], w_star), make_float2(r.x, -r.y));
         sr += (double)e.x;
         si += (double)e.y;
         sv += (double)v[0];
@@ -398,16 +366,14 @@ __device__ void pucch_format1(const PucchLaunch& p, const PucchDesc& d, uint32_t
     if (d.nof_harq_ack > 1u && m2 > m1) {
       bits = bits2;
     }
-    const float metric = __fdiv_rn(norm(det), eq_noise_var);
+    const float metric = __fdiv_rn(exact::norm(det), eq_noise_var);
     const bool  ok     = metric > THRESHOLD;
     uint32_t    status = NRPHY_PUCCH_STATUS_INVALID;
     if (ok) {
       status = d.nof_harq_ack > 0u || (bits & 1u) == 0u ? NRPHY_PUCCH_STATUS_VALID : NRPHY_PUCCH_STATUS_UNKNOWN;
     }
-    const float fp   = (float)P;
-    const float sinr = is_normal(noise_all) ? __fdiv_rn(rsrp_all, noise_all) : 1e6f;
     write_result(p, ip, status, d.nof_harq_ack > 0u ? bits & 1u : 0u, d.nof_harq_ack > 1u ? (bits >> 1) & 1u : 0u, 0u,
-                 __fdiv_rn(metric, THRESHOLD), to_dB(sinr), to_dB(__fdiv_rn(rsrp_lin, fp)), to_dB(__fdiv_rn(epre_lin, fp)), best_cfo_hz);
+                 __fdiv_rn(metric, THRESHOLD), csi.sinr_dB(), csi.rsrp_dB(P), csi.epre_dB(P), csi.cfo_hz);
   }
 }
 

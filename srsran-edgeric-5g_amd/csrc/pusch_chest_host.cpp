@@ -40,7 +40,7 @@ struct nrphy_pusch_chest_plan {
   PuschChestDesc* d_desc  = nullptr;
   uint32_t*       d_jobs  = nullptr;
   uint16_t*       d_prbs  = nullptr;
-  float2*         d_tw    = nullptr;
+  const float2*   twiddle = nullptr; // the context's e^{j 2 pi i / 2048}: not the plan's to free
   uint32_t*       d_rows  = nullptr;
   float2*         d_rot   = nullptr;
 };
@@ -122,13 +122,14 @@ extern "C" int nrphy_pusch_chest_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
       }
     }
   }
-  std::vector<float2> tw(2048);
-  for (uint32_t i = 0; i != 2048; ++i) {
-    const double a = 2.0 * M_PI * i / 2048.0;
-    tw[i]          = make_float2((float)std::cos(a), (float)std::sin(a));
+  // The time-alignment search's twiddles are the context's table, built on first use.
+  const float2* twiddle = hipSetDevice(ctx->device) == hipSuccess ? get_twiddle_table(ctx, 2048) : nullptr;
+  if (twiddle == nullptr) {
+    return NRPHY_ERR_DEVICE;
   }
   auto* plan           = new nrphy_pusch_chest_plan;
   plan->ctx            = ctx;
+  plan->twiddle        = twiddle;
   plan->n              = n;
   plan->n_jobs         = (uint32_t)jobs.size();
   plan->nof_grids      = nof_grids;
@@ -139,10 +140,8 @@ extern "C" int nrphy_pusch_chest_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
   arena.add(&plan->d_desc, desc.data(), desc.size() * sizeof(PuschChestDesc));
   arena.add(&plan->d_jobs, jobs.data(), jobs.size() * sizeof(uint32_t));
   arena.add(&plan->d_prbs, prbs.data(), prbs.size() * sizeof(uint16_t));
-  arena.add(&plan->d_tw, tw.data(), tw.size() * sizeof(float2));
   const size_t rows_bytes = (row_words * sizeof(uint32_t) + 255) & ~(size_t)255;
-  if (hipSetDevice(ctx->device) != hipSuccess ||
-      arena.commit(&plan->d_arena, rows_bytes + jobs.size() * NRPHY_NSYMB * sizeof(float2), (void**)&plan->d_rows) != hipSuccess) {
+  if (arena.commit(&plan->d_arena, rows_bytes + jobs.size() * NRPHY_NSYMB * sizeof(float2), (void**)&plan->d_rows) != hipSuccess) {
     nrphy_pusch_chest_plan_destroy(plan);
     return NRPHY_ERR_DEVICE;
   }
@@ -162,7 +161,7 @@ extern "C" int nrphy_pusch_chest_run(nrphy_pusch_chest_plan_t* plan, const void*
   p.desc           = plan->d_desc;
   p.jobs           = plan->d_jobs;
   p.prbs           = plan->d_prbs;
-  p.twiddle        = plan->d_tw;
+  p.twiddle        = plan->twiddle;
   p.gold           = plan->ctx->d_gold;
   p.x1_words       = plan->ctx->d_x1;
   p.grid           = (const uint32_t*)d_grid;

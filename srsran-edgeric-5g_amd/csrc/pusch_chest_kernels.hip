@@ -14,8 +14,9 @@
 //  (B) pusch_chest_expand_kernel: one workgroup per (job, OFDM symbol): the scratch row rotated by the symbol's CFO phasor and
 //      rounded again (the reference rounds twice), DC zeroed, written to the allocated PRBs with 16-byte stores.
 // Transcendentals (atan2, hypot, cos, sin) are evaluated in double and rounded once to float.  Contraction is off; the only
-// fused multiply-adds are the partial DFT's, which feed a comparison and nothing else.  The virtual pilots, the phasor and the
-// measurements' arithmetic are chest_device.h's, shared with the PUCCH format 2 receiver.
+// fused multiply-adds are the partial DFT's, which feed a comparison and nothing else.  The virtual pilots and the
+// measurements' arithmetic are chest_device.h's, shared with the PUCCH format 2 receiver; the products, the phasor, the pilot
+// and the search's comparison are exact_device.h's, shared with every receiver.
 #include "bits_device.h"
 #include "chest_device.h"
 
@@ -64,11 +65,8 @@ __device__ __forceinline__ double2 block_sum2(double x, double y, ChestShared& s
 __device__ __forceinline__ float2 pilot(const ChestShared& s, uint32_t d, uint32_t q, uint32_t layer, uint32_t& subc)
 {
   const uint32_t n = s.prbs[q / 6u], k = q % 6u;
-  const uint32_t b = 12u * n + 2u * k;
-  subc             = b;
-  const uint32_t w0 = s.seq[d][b >> 5];
-  const uint32_t c0 = (w0 >> (31u - (b & 31u))) & 1u, c1 = (w0 >> (30u - (b & 31u))) & 1u; // b even: same word
-  float2         p  = make_float2(c0 ? -SQRT1_2_F : SQRT1_2_F, c1 ? -SQRT1_2_F : SQRT1_2_F);
+  subc             = 12u * n + 2u * k; // also the pilot's first bit: two bits per pilot, one pilot per two subcarriers
+  float2 p         = qpsk_pilot(s.seq[d], subc);
   if (layer == 1 && (q & 1u)) { // w_f = -1 on the odd pilots of layer 1 (port 1001)
     p = make_float2(-p.x, -p.y);
   }
@@ -107,19 +105,18 @@ __global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_kernel(PuschChestLa
       uint32_t     k;
       const float2 pl = pilot(s, dd, q, layer, k);
       const float2 y  = cbf16_to_float2(row[k]);
-      epre += (double)__fadd_rn(__fmul_rn(y.x, y.x), __fmul_rn(y.y, y.y));
-      const float2 ls = make_float2(__fadd_rn(__fmul_rn(y.x, pl.x), __fmul_rn(y.y, pl.y)),
-                                    __fsub_rn(__fmul_rn(y.y, pl.x), __fmul_rn(y.x, pl.y)));
+      epre += (double)exact::norm(y);
+      const float2 ls = exact::mul_conj(y, pl);
       if (dd == 0) {
         A[q] = ls;
       } else if (dd == 1) {
         s.b[q] = ls;
-        const float2 l0 = A[q]; // dot_prod(LS1, LS0) = sum LS1 conj(LS0)
-        dr += (double)__fadd_rn(__fmul_rn(ls.x, l0.x), __fmul_rn(ls.y, l0.y));
-        di += (double)__fsub_rn(__fmul_rn(ls.y, l0.x), __fmul_rn(ls.x, l0.y));
+        const float2 dot = exact::mul_conj(ls, A[q]); // dot_prod(LS1, LS0) = sum LS1 conj(LS0)
+        dr += (double)dot.x;
+        di += (double)dot.y;
       } else {
         const float2 r = phasor(__fmul_rn(__fmul_rn(-TWOPI_F, d.epoch[d.dmrs_symbol[dd]]), cfo));
-        const float2 a = A[q], c = cmul(ls, r);
+        const float2 a = A[q], c = exact::cmul(ls, r);
         A[q]                     = make_float2(__fadd_rn(a.x, c.x), __fadd_rn(a.y, c.y));
       }
     }
@@ -130,7 +127,7 @@ __global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_kernel(PuschChestLa
       const float2 r0 = phasor(__fmul_rn(__fmul_rn(-TWOPI_F, d.epoch[d.dmrs_symbol[0]]), cfo));
       const float2 r1 = phasor(__fmul_rn(__fmul_rn(-TWOPI_F, d.epoch[d.dmrs_symbol[1]]), cfo));
       for (uint32_t q = tid; q < N; q += CHEST_THREADS) {
-        const float2 a = cmul(A[q], r0), c = cmul(s.b[q], r1);
+        const float2 a = exact::cmul(A[q], r0), c = exact::cmul(s.b[q], r1);
         A[q]           = make_float2(__fadd_rn(a.x, c.x), __fadd_rn(a.y, c.y));
       }
     }
@@ -166,7 +163,7 @@ __global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_kernel(PuschChestLa
       acc           = make_float2(__fadd_rn(acc.x, __fmul_rn(x[i].x, h)), __fadd_rn(acc.y, __fmul_rn(x[i].y, h)));
     }
     s.b[q] = acc;
-    pw += (double)__fadd_rn(__fmul_rn(acc.x, acc.x), __fmul_rn(acc.y, acc.y));
+    pw += (double)exact::norm(acc);
   }
   const double2 pe   = block_sum2(pw, epre, s, tid); // (also orders the writes of b)
   const float   rsrp = (float)(pe.x * (double)d.beta * (double)d.beta / (double)N);
@@ -181,12 +178,12 @@ __global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_kernel(PuschChestLa
       const float2 pl = pilot(s, dd, q, layer, k);
       const float2 y  = cbf16_to_float2(row[k]);
       const float2 f  = s.b[q];
-      float2       e  = cmul(make_float2(__fmul_rn(f.x, -d.beta), __fmul_rn(f.y, -d.beta)), pl);
+      float2       e  = exact::cmul(make_float2(__fmul_rn(f.x, -d.beta), __fmul_rn(f.y, -d.beta)), pl);
       if (nd >= 2u) {
-        e = cmul(e, r);
+        e = exact::cmul(e, r);
       }
       e = make_float2(__fadd_rn(e.x, y.x), __fadd_rn(e.y, y.y));
-      ne += (double)__fadd_rn(__fmul_rn(e.x, e.x), __fmul_rn(e.y, e.y));
+      ne += (double)exact::norm(e);
     }
   }
   const double2 nz = block_sum2(ne, 0.0, s, tid);
@@ -203,21 +200,17 @@ __global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_kernel(PuschChestLa
 #pragma unroll
       for (uint32_t k = 0; k != 6; ++k) {
         const float2 f = s.b[6u * j + k];
-        const float2 w = s.u.tw[i0];
-        acc0.x         = __fmaf_rn(f.x, w.x, __fmaf_rn(-f.y, w.y, acc0.x));
-        acc0.y         = __fmaf_rn(f.x, w.y, __fmaf_rn(f.y, w.x, acc0.y));
+        dft_accumulate(acc0, f, s.u.tw[i0]);
         if (two) {
-          const float2 v = s.u.tw[i1];
-          acc1.x         = __fmaf_rn(f.x, v.x, __fmaf_rn(-f.y, v.y, acc1.x));
-          acc1.y         = __fmaf_rn(f.x, v.y, __fmaf_rn(f.y, v.x, acc1.y));
+          dft_accumulate(acc1, f, s.u.tw[i1]);
         }
         i0 = (i0 + n0) & 2047u;
         i1 = (i1 + n1) & 2047u;
       }
     }
-    s.mag[tid] = __fadd_rn(__fmul_rn(acc0.x, acc0.x), __fmul_rn(acc0.y, acc0.y));
+    s.mag[tid] = exact::norm(acc0);
     if (two) {
-      s.mag[b1] = __fadd_rn(__fmul_rn(acc1.x, acc1.x), __fmul_rn(acc1.y, acc1.y));
+      s.mag[b1] = exact::norm(acc1);
     }
   }
   __syncthreads(); // (the twiddles are dead from here on: u.out reuses them)
@@ -243,19 +236,16 @@ __global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_kernel(PuschChestLa
     }
     out[2u * N - 1u] = tid == 0 ? s.b[N - 1u].x : s.b[N - 1u].y;
   } else if (tid == 64u) { // meanwhile: the measurements
-    float best_d = -1.f, best_a = -1.f;
-    int   id = 0, ia = 0;
+    float    best_d = -1.f, best_a = -1.f;
+    uint32_t id = 0, ia = 0;
     for (uint32_t b = 0; b != PUSCH_CHEST_TA_WINDOW; ++b) {
-      if (s.mag[b] > best_d) {
-        best_d = s.mag[b];
-        id     = (int)b;
-      }
-      if (s.mag[PUSCH_CHEST_TA_WINDOW + b] > best_a) {
-        best_a = s.mag[PUSCH_CHEST_TA_WINDOW + b];
-        ia     = (int)b;
-      }
+      // Ascending, so the bin held is never above b and take_max's tie rule cannot fire: said aloud, the compiler keeps the
+      // strict comparison only, as selects; left to find out, it branches per bin behind every LDS read.
+      __builtin_assume(id <= b && ia <= b);
+      take_max(best_d, id, s.mag[b], b);
+      take_max(best_a, ia, s.mag[PUSCH_CHEST_TA_WINDOW + b], b);
     }
-    const int   ta_bins   = best_d >= best_a ? id : ia - (int)PUSCH_CHEST_TA_WINDOW;
+    const int ta_bins = ta_signed_bin(best_d, id, best_a, ia, PUSCH_CHEST_TA_WINDOW);
     const nrphy_pusch_chest_meas_t m = chest_measurements(rsrp, (float)(pe.y / (double)(N * nd)), (float)(nz.x / (double)(N * nd - 1u)),
                                                           d.beta, ta_bins, nd >= 2u, cfo, d.scs_hz);
     if (layer == 0) {
@@ -297,7 +287,7 @@ __global__ __launch_bounds__(CHEST_THREADS) void pusch_chest_expand_kernel(Pusch
 #pragma unroll
     for (uint32_t i = 0; i != 4; ++i) {
       if (rot) {
-        const float2 e = cmul(cbf16_to_float2(v[i]), r);
+        const float2 e = exact::cmul(cbf16_to_float2(v[i]), r);
         v[i]           = to_cbf16(e.x, e.y);
       }
       if (k0 + i == d.dc) {

@@ -11,29 +11,16 @@
 // scalar (readfirstlane), so the descriptor is read with scalar loads.  Every lane issues at most two 16-byte loads -- lanes 0..3
 // a port's row, lane 4 the decoder words, lanes 5..7 the SINR and the statuses --, the values are handed round with shuffles, the
 // sums over the ports are taken in port order in float as the reference takes them, and lane 0 stores the record once.  log10 is
-// evaluated in double and rounded once (to_dB of pucch_kernels.hip).  Contraction is off.
+// evaluated in double and rounded once (to_dB and the merge, CsiMerge, are exact_device.h's).  Contraction is off.
 #include "bits_device.h"
+#include "exact_device.h"
 
-#include <cfloat>
 #include <hip/hip_runtime.h>
 
 namespace nrphy {
 namespace {
 
 constexpr uint32_t PROC_WAVES = 4; // PDUs per workgroup
-
-// convert_power_to_dB
-__device__ __forceinline__ float to_dB(float v)
-{
-  return __fmul_rn(10.0f, (float)log10((double)v));
-}
-
-// std::isnormal
-__device__ __forceinline__ bool is_normal(float v)
-{
-  const float a = fabsf(v);
-  return a >= FLT_MIN && a <= FLT_MAX;
-}
 
 __global__ __launch_bounds__(PROC_WAVES * WAVE) void pusch_proc_result_kernel(PuschProcLaunch p)
 {
@@ -62,23 +49,14 @@ __global__ __launch_bounds__(PROC_WAVES * WAVE) void pusch_proc_result_kernel(Pu
     a.x = d.csi1_status != PUSCH_PROC_NO_STATUS ? p.status[d.csi1_status] : NRPHY_UCI_STATUS_UNKNOWN;
   }
 
-  float epre_lin = 0.f, rsrp_lin = 0.f, noise_all = 0.f, best_snr = 0.f, best_ta = 0.f, best_cfo = 0.f;
+  CsiMerge csi;
 #pragma unroll
   for (uint32_t q = 0; q != NRPHY_MAX_PORTS; ++q) {
     const float noise = __uint_as_float(__shfl(a.x, q)), rsrp = __uint_as_float(__shfl(a.y, q));
     const float epre = __uint_as_float(__shfl(a.z, q)), snr = __uint_as_float(__shfl(a.w, q));
     const float ta = __uint_as_float(__shfl(b.x, q)), cfo = __uint_as_float(__shfl(b.z, q));
     if (q < P) {
-      epre_lin  = __fadd_rn(epre_lin, epre);
-      rsrp_lin  = __fadd_rn(rsrp_lin, rsrp);
-      noise_all = __fadd_rn(noise_all, noise);
-      if (q == 0 || snr > best_snr) { // best_rx_port starts at 0 and moves on a strictly better SNR
-        best_ta  = ta;
-        best_cfo = cfo;
-      }
-      if (snr > best_snr) {
-        best_snr = snr;
-      }
+      csi.add(q, noise, rsrp, epre, snr, ta, cfo);
     }
   }
   const uint32_t dec0 = __shfl(a.x, 4), dec1 = __shfl(a.y, 4), dec2 = __shfl(a.z, 4), dec3 = __shfl(a.w, 4);
@@ -87,9 +65,8 @@ __global__ __launch_bounds__(PROC_WAVES * WAVE) void pusch_proc_result_kernel(Pu
   if (lane != 0) {
     return;
   }
-  const float fp      = (float)P;
-  const float sinr_ce = to_dB(is_normal(noise_all) ? __fdiv_rn(rsrp_lin, noise_all) : 1e6f); // get_layer_average_snr(0)
-  const bool  has_cfo = best_cfo == best_cfo; // the estimator reports NaN where the reference's optional is empty
+  const float sinr_ce = csi.sinr_dB();
+  const bool  has_cfo = csi.cfo_hz == csi.cfo_hz; // the estimator reports NaN where the reference's optional is empty
 
   nrphy_pusch_result_t r;
   r.has_sch              = d.has_sch;
@@ -107,10 +84,10 @@ __global__ __launch_bounds__(PROC_WAVES * WAVE) void pusch_proc_result_kernel(Pu
   r.sinr_ch_estimator_dB = sinr_ce;
   r.sinr_post_eq_dB      = sinr_post_eq;
   r.sinr_dB              = d.sinr_method == NRPHY_PUSCH_SINR_POST_EQUALIZATION ? sinr_post_eq : sinr_ce;
-  r.epre_dB              = to_dB(__fdiv_rn(epre_lin, fp));
-  r.rsrp_dB              = to_dB(__fdiv_rn(rsrp_lin, fp));
-  r.time_alignment_s     = best_ta;
-  r.cfo_hz               = has_cfo ? best_cfo : 0.f;
+  r.epre_dB              = csi.epre_dB(P);
+  r.rsrp_dB              = csi.rsrp_dB(P);
+  r.time_alignment_s     = csi.ta_s;
+  r.cfo_hz               = has_cfo ? csi.cfo_hz : 0.f;
   r.has_cfo              = has_cfo ? 1u : 0u;
   r.has_evm              = 0u;
   r.evm                  = 0.f;

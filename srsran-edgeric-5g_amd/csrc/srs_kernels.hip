@@ -19,7 +19,7 @@
 //                   writes time_alignment_s and the padding.
 // No atomics, no scratch; contraction is off, fused multiply-adds only where written.
 #include "bits_device.h"
-#include "chest_device.h"
+#include "exact_device.h"
 #include "fft_device.h"
 
 #include <hip/hip_runtime.h>
@@ -32,20 +32,6 @@ constexpr uint32_t SRS_WAVES   = SRS_THREADS / WAVE;
 static_assert(SRS_MAX_SEQ * 2 <= SRS_DFT_SIZE, "the sequence on its comb fits the transform");
 
 typedef const NRPHY_CONSTANT SrsDesc& SrsDescRef;
-
-// complex_exponential_table(size, 1)[index]: polar(1, float(2 pi) float(index) / float(size)), the angle in single precision.
-__device__ __forceinline__ float2 unit_circle(uint32_t index, uint32_t size)
-{
-  const float  a = __fdiv_rn(__fmul_rn(TWOPI_F, (float)index), (float)size);
-  const double x = (double)a;
-  return make_float2((float)cos(x), (float)sin(x));
-}
-
-// srsvec::prod on complex values: (a.re b.re - a.im b.im, a.re b.im + a.im b.re).
-__device__ __forceinline__ float2 srs_cmul(float2 a, float2 b)
-{
-  return make_float2(__fsub_rn(__fmul_rn(a.x, b.x), __fmul_rn(a.y, b.y)), __fadd_rn(__fmul_rn(a.x, b.y), __fmul_rn(a.y, b.x)));
-}
 
 // low_papr_sequence_generator_impl::generate(u, 0, n_cs, n_cs_max)[n] for antenna port `port`.
 __device__ __forceinline__ float2 srs_sequence(SrsDescRef d, const float2* __restrict__ cs_table, uint32_t port, uint32_t n)
@@ -61,7 +47,7 @@ __device__ __forceinline__ float2 srs_sequence(SrsDescRef d, const float2* __res
   }
   const uint32_t step = d.cs_step[port];
   if (step != 0u) {
-    r = srs_cmul(r, cs_table[(n * step) % SRS_CS_SIZE]);
+    r = exact::cmul(r, cs_table[(n * step) % SRS_CS_SIZE]);
   }
   return r;
 }
@@ -75,7 +61,7 @@ __device__ __forceinline__ float2 srs_mean_lse(SrsDescRef d, const SrsLaunch& p,
   float2         acc = make_float2(0.f, 0.f);
   for (uint32_t l = 0; l != d.nof_symbols; ++l) {
     const float2 y = cbf16_to_float2(row[(size_t)l * p.grid_nof_subc + k]);
-    const float2 e = make_float2(__fadd_rn(__fmul_rn(y.x, r.x), __fmul_rn(y.y, r.y)), __fsub_rn(__fmul_rn(y.y, r.x), __fmul_rn(y.x, r.y)));
+    const float2 e = exact::mul_conj(y, r);
     acc            = l == 0u ? e : make_float2(__fadd_rn(acc.x, e.x), __fadd_rn(acc.y, e.y));
   }
   if (d.nof_symbols > 1u) {
@@ -87,15 +73,6 @@ __device__ __forceinline__ float2 srs_mean_lse(SrsDescRef d, const SrsLaunch& p,
 __device__ __forceinline__ const uint32_t* srs_row(SrsDescRef d, const SrsLaunch& p, uint32_t rx)
 {
   return p.grid + (((size_t)d.grid_index * p.grid_nof_ports + d.rx_ports[rx]) * NRPHY_NSYMB + d.first_symbol) * p.grid_nof_subc;
-}
-
-// The larger of two (magnitude, bin) candidates; the lower bin on equal magnitudes (max_abs_element returns the first maximum).
-__device__ __forceinline__ void take_max(float& m, uint32_t& i, float m2, uint32_t i2)
-{
-  if (m2 > m || (m2 == m && i2 < i)) {
-    m = m2;
-    i = i2;
-  }
 }
 
 __global__ __launch_bounds__(SRS_THREADS) void srs_ta_kernel(SrsLaunch p)
@@ -133,7 +110,7 @@ __global__ __launch_bounds__(SRS_THREADS) void srs_ta_kernel(SrsLaunch p)
   auto     sink = [&](uint32_t q, auto base, auto, cf v) {
     constexpr uint32_t B = decltype(base)::value;
     if constexpr (B == 0u || B == SRS_DFT_SIZE - SRS_THREADS) {
-      const float m = __fadd_rn(__fmul_rn(v.x, v.x), __fmul_rn(v.y, v.y));
+      const float m = exact::norm(make_float2(v.x, v.y));
       if (B == 0u) {
         if (q < W) {
           take_max(best_d, id, m, q);
@@ -144,11 +121,7 @@ __global__ __launch_bounds__(SRS_THREADS) void srs_ta_kernel(SrsLaunch p)
     }
   };
   fft_from_registers<+1, SRS_DFT_SIZE>(a, tb, lds, p.twiddle, tid, sink);
-#pragma unroll
-  for (int o = WAVE / 2; o != 0; o >>= 1) {
-    take_max(best_d, id, __shfl_xor(best_d, o), __shfl_xor(id, o));
-    take_max(best_a, ia, __shfl_xor(best_a, o), __shfl_xor(ia, o));
-  }
+  wave_take_max(best_d, id, best_a, ia);
   if (lane == 0) {
     red_m[0][wave] = best_d;
     red_i[0][wave] = id;
@@ -161,7 +134,7 @@ __global__ __launch_bounds__(SRS_THREADS) void srs_ta_kernel(SrsLaunch p)
       take_max(best_d, id, red_m[0][w], red_i[0][w]);
       take_max(best_a, ia, red_m[1][w], red_i[1][w]);
     }
-    *out = best_d >= best_a ? (int32_t)id : (int32_t)ia - (int32_t)W; // -(W - ia)
+    *out = ta_signed_bin(best_d, id, best_a, ia, W); // -(W - ia)
   }
 }
 
@@ -204,7 +177,7 @@ __global__ __launch_bounds__(SRS_THREADS) void srs_coef_kernel(SrsLaunch p)
     // round(1024 * (n * ps + offset) / TWOPI): every step in single precision, half away from zero, negative values wrapped.
     const float  x   = __fdiv_rn(__fmul_rn((float)SRS_CEXP_SIZE, __fadd_rn(__fmul_rn((float)n, ps), off)), TWOPI_F);
     const int    idx = (int)roundf(x);
-    const float2 c   = srs_cmul(e, p.cexp_table[(uint32_t)idx % SRS_CEXP_SIZE]);
+    const float2 c   = exact::cmul(e, p.cexp_table[(uint32_t)idx % SRS_CEXP_SIZE]);
     sum              = make_float2(__fadd_rn(sum.x, c.x), __fadd_rn(sum.y, c.y));
   }
 #pragma unroll

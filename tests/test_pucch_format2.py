@@ -594,6 +594,23 @@ def test_graph_replay_and_two_runs_give_identical_bytes(gpu_ctx):
 
 
 @pytest.mark.gpu
+def test_twiddles_are_built_on_first_use_and_outlive_a_plan(gpu_ctx):
+    """The time-alignment twiddles are the context's: the first plan of a fresh context builds them, destroying that plan leaves
+    them, and a second plan reads the same table.  Both runs give the bytes the session's context gives in link_run (whose
+    parity tests vouch for them), so the table of a first use is the right one."""
+    what, cfg, message, grid = link_cases()[0]
+    ctx = lib.Context(0)
+    try:
+        runs = [run_plan(ctx, [cfg], [0], grid[None])[0] for _ in range(2)]  # each creates its plan, runs it and destroys it
+    finally:
+        ctx.close()
+    for got in runs:
+        for key in ("llr", "message", "csi", "meas", "ce"):
+            assert got[key].tobytes() == link_run(gpu_ctx)[0][key].tobytes(), (what, key)
+        assert got["status"] == abi.UCI_STATUS_VALID and got["message"].tobytes() == message.tobytes(), what
+
+
+@pytest.mark.gpu
 def test_unaligned_soft_bit_offsets_and_no_optional_outputs(gpu_ctx):
     """Soft bits at an offset that is no multiple of 16 take the byte path; d_meas and d_ch_est may be NULL."""
     cases = [link_cases()[i] for i in (1, 7)]

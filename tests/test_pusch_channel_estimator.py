@@ -296,6 +296,23 @@ def test_parity_with_the_restatement(gpu_ctx):
 
 
 @pytest.mark.gpu
+def test_twiddles_are_built_on_first_use_and_outlive_a_plan():
+    """The time-alignment twiddles are the context's: the first plan of a fresh context builds them, destroying that plan leaves
+    them, and a second plan reads the same table.  Same bytes both times, and the restatement's answer, time alignment included."""
+    what, cfg, nports, nsubc = "1 PRB, 1 DM-RS", abi.make_pusch_chest(prbs=[7], dmrs_symbols=(2,), rx_ports=(0,)), 1, 624
+    grid = synthetic_grid(np.random.default_rng(7), cfg, nports, nsubc)
+    ctx = lib.Context(0)
+    try:
+        runs = [run_plan(ctx, [cfg], [grid], [0], nports, nsubc) for _ in range(2)]  # each creates, runs and destroys its plan
+    finally:
+        ctx.close()
+    for (ce,), nv, meas in runs:
+        assert (ce.tobytes(), nv.tobytes(), meas.tobytes()) == (runs[0][0][0].tobytes(), runs[0][1].tobytes(), runs[0][2].tobytes())
+    (ce,), nv, meas = runs[0]
+    check_parity(cfg, grid, ce, nv[0], meas[0], nsubc, what)
+
+
+@pytest.mark.gpu
 def test_flat_noiseless_channel_is_estimated_exactly(gpu_ctx):
     h = 0.8 * np.exp(0.6j)
     cfg = abi.make_pusch_chest(prbs=range(4, 40), dmrs_symbols=(2, 11), rx_ports=(0,))
