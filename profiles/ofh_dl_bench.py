@@ -14,14 +14,14 @@ fragment per symbol is one compress() call of the whole row) and the first symbo
 
     python3 profiles/ofh_dl_bench.py            (GPU box, repository root)
 """
-import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
+
+import bench_harness as harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -37,7 +37,6 @@ def step(rounds, iters, out):
     ctx = lib.Context(0)
     stream = torch.cuda.Stream()
     sp = C.c_void_p(stream.cuda_stream)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     cfg = abi.OfhCompressionCfg(1, WIDTH, 1.0)
     rec, nsubc, max_slots = 3 * WIDTH + 1, 12 * NOF_PRB, 16
     torch.manual_seed(0)
@@ -75,25 +74,8 @@ def step(rounds, iters, out):
         launches[name] = lambda rows=rows: ctx.ofh_compress(cfg, rows, NOF_PRB, d_grid, d_records, stream=sp)
         info[name] = dict(rows=rows, frames=0, bytes_written=rows * NOF_PRB * rec)
     torch.cuda.synchronize()
-    e0.record(stream)
-    settle = 0
-    while True:  # settling: about 30 ms of load before anything is timed
-        for launch in launches.values():
-            launch()
-        settle += 1
-        e1.record(stream)
-        torch.cuda.synchronize()
-        if e0.elapsed_time(e1) >= 30.0 or settle >= 2000:
-            break
-    ms = {k: [] for k in launches}
-    for _ in range(rounds):  # alternating: every round times every launch once
-        for kind, launch in launches.items():
-            e0.record(stream)
-            for _ in range(iters):
-                launch()
-            e1.record(stream)
-            torch.cuda.synchronize()
-            ms[kind].append(e0.elapsed_time(e1) / iters)
+    settle = harness.settle(launches, stream)  # about 30 ms of load before anything is timed
+    ms = harness.time_rounds(launches, stream, rounds, iters)  # alternating: every round times every launch once
     result = {"leg": "ofh_dl", "ports": PORTS, "symbols": NSYMB, "nof_prb": NOF_PRB, "type": "BFP", "data_width": WIDTH, "record_bytes": rec,
               "static_compression": 1, "rounds": rounds, "iters": iters, "settle_rounds": settle, "hbm_roof_GBps": HBM_ROOF_GBPS,
               "counters": "not measured",
@@ -102,9 +84,10 @@ def step(rounds, iters, out):
                       "ofh_compress is a bare launch over the same rows"}
     for kind in launches:
         m = float(np.median(ms[kind]))
+        ms_med, ms_min, ms_max = harness.spread(ms[kind])
         written, read = info[kind]["bytes_written"], info[kind]["rows"] * NOF_PRB * 48
-        result[kind] = {"rows": info[kind]["rows"], "frames": info[kind]["frames"], "bytes_written": written, "ms_per_call": round(m, 5),
-                        "ms_min": round(min(ms[kind]), 5), "ms_max": round(max(ms[kind]), 5), "GBps_written": round(written / (m * 1e-3) / 1e9, 2),
+        result[kind] = {"rows": info[kind]["rows"], "frames": info[kind]["frames"], "bytes_written": written, "ms_per_call": ms_med,
+                        "ms_min": ms_min, "ms_max": ms_max, "GBps_written": round(written / (m * 1e-3) / 1e9, 2),
                         "ns_per_byte_written": round(m * 1e6 / written, 5),
                         "share_of_hbm_roof_read_plus_written": round((read + written) / (m * 1e-3) / 1e9 / HBM_ROOF_GBPS, 4)}
     for kind, launch in launches.items():
@@ -132,21 +115,5 @@ def step(rounds, iters, out):
         f.write(json.dumps(result) + "\n")
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--step", action="store_true", help="run the measurement in this process (what the driver starts)")
-    ap.add_argument("--rounds", type=int, default=15)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds for the GPU step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ofh_dl_bench.json"))
-    args = ap.parse_args()
-    if args.step:
-        step(args.rounds, args.iters, args.out)
-        return 0
-    cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--step", "--rounds", str(args.rounds),
-           "--iters", str(args.iters), "--out", args.out]
-    return subprocess.run(cmd).returncode
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(harness.bench_main(step, (), dict(rounds=15, iters=20, timeout=240, out=os.path.join(ROOT, "profiles", "ofh_dl_bench.json"))))

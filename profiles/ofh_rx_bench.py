@@ -16,15 +16,15 @@ compared and every record is checked to be accepted.  Hardware counters are not 
 
     python3 profiles/ofh_rx_bench.py            (GPU box, repository root)
 """
-import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 import time
 
 import numpy as np
+
+import bench_harness as harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -58,7 +58,6 @@ def measure(ctx, lib, abi, model, mtu, rounds, iters):
     import torch
     stream = torch.cuda.Stream()
     sp = C.c_void_p(stream.cuda_stream)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     cfg = model.default_cfg(ru_nof_prbs=NOF_PRB, ul_eaxc=tuple(range(EAXC)), prach_eaxc=(), compression=(1, WIDTH), prach_compression=(1, WIDTH))
     expects = [model.expect(sfn8=1, subframe=2, slot=1, eaxc=e, nof_prb=NOF_PRB) for e in range(EAXC)]
     buf, ranges = slot_frames(model, cfg, mtu, np.random.default_rng(mtu))
@@ -97,26 +96,12 @@ def measure(ctx, lib, abi, model, mtu, rounds, iters):
         assert rc == abi.OK, rc
 
     launches = {"ofh_rx_run": rx_run, "ofh_ul_write_grid": write_grid}
-    e0.record(stream)
-    settle = 0
-    while True:  # settling: about 30 ms of load before anything is timed
-        for launch in launches.values():
-            launch()
-        settle += 1
-        e1.record(stream)
-        torch.cuda.synchronize()
-        if e0.elapsed_time(e1) >= 30.0 or settle >= 2000:
-            break
+    settle = harness.settle(launches, stream)  # about 30 ms of load before anything is timed
     ms = {k: [] for k in launches}
     host_us = {k: [] for k in launches}
     for _ in range(rounds):  # alternating: every round times every launch once
-        for kind, launch in launches.items():
-            e0.record(stream)
-            for _ in range(iters):
-                launch()
-            e1.record(stream)
-            torch.cuda.synchronize()
-            ms[kind].append(e0.elapsed_time(e1) / iters)
+        for kind, t in harness.time_rounds(launches, stream, 1, iters).items():
+            ms[kind] += t
         for kind, launch in launches.items():  # the host's share: the call alone on an idle stream
             t0 = time.perf_counter()
             launch()
@@ -127,7 +112,8 @@ def measure(ctx, lib, abi, model, mtu, rounds, iters):
               "settle_rounds": settle}
     for kind in launches:
         m = float(np.median(ms[kind]))
-        result[kind] = {"ms_per_call": round(m, 5), "ms_min": round(min(ms[kind]), 5), "ms_max": round(max(ms[kind]), 5),
+        ms_med, ms_min, ms_max = harness.spread(ms[kind])
+        result[kind] = {"ms_per_call": ms_med, "ms_min": ms_min, "ms_max": ms_max,
                         "host_us_per_call": round(float(np.median(host_us[kind])), 1),
                         "GBps_payload_plus_grid": round((payload + EAXC * NSYMB * nsubc * 4) / (m * 1e-3) / 1e9, 1)}
     rx_run()
@@ -154,21 +140,5 @@ def step(rounds, iters, out):
         f.write(json.dumps(result) + "\n")
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--step", action="store_true", help="run the measurement in this process (what the driver starts)")
-    ap.add_argument("--rounds", type=int, default=15)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds for the GPU step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ofh_rx_bench.json"))
-    args = ap.parse_args()
-    if args.step:
-        step(args.rounds, args.iters, args.out)
-        return 0
-    cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--step", "--rounds", str(args.rounds),
-           "--iters", str(args.iters), "--out", args.out]
-    return subprocess.run(cmd).returncode
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(harness.bench_main(step, (), dict(rounds=15, iters=20, timeout=240, out=os.path.join(ROOT, "profiles", "ofh_rx_bench.json"))))

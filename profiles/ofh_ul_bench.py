@@ -13,14 +13,14 @@ timed region both outputs are checked against each other and, on the first grid,
 
     python3 profiles/ofh_ul_bench.py            (GPU box, repository root)
 """
-import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
+
+import bench_harness as harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -36,7 +36,6 @@ def step(rounds, iters, out):
     ctx = lib.Context(0)
     stream = torch.cuda.Stream()
     sp = C.c_void_p(stream.cuda_stream)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     cfg = abi.OfhCompressionCfg(1, WIDTH, 1.0)
     rec, rows, nsubc = 3 * WIDTH + 1, GRIDS * PORTS * NSYMB, 12 * NOF_PRB
     torch.manual_seed(0)
@@ -60,46 +59,18 @@ def step(rounds, iters, out):
     launches = {"ofh_ul_write_grid": write_grid,
                 "ofh_decompress": lambda: ctx.ofh_decompress(cfg, rows, NOF_PRB, d_bytes, d_rows, stream=sp),
                 "ofh_compress": lambda: ctx.ofh_compress(cfg, rows, NOF_PRB, d_src, d_bytes, stream=sp)}
-    # Copy rate: device to device, 256 MiB, read + write counted.
-    a = torch.empty(64 << 20, dtype=torch.int32, device="cuda")
-    b = torch.empty_like(a)
-    with torch.cuda.stream(stream):
-        for _ in range(3):
-            b.copy_(a)
-        e0.record(stream)
-        for _ in range(10):
-            b.copy_(a)
-        e1.record(stream)
-    torch.cuda.synchronize()
-    copy_gbs = 2 * a.numel() * 4 * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    del a, b
-    e0.record(stream)
-    settle = 0
-    while True:  # settling: about 30 ms of load before anything is timed
-        for launch in launches.values():
-            launch()
-        settle += 1
-        e1.record(stream)
-        torch.cuda.synchronize()
-        if e0.elapsed_time(e1) >= 30.0 or settle >= 2000:
-            break
-    ms = {k: [] for k in launches}
-    for _ in range(rounds):  # alternating: every round times every launch once
-        for kind, launch in launches.items():
-            e0.record(stream)
-            for _ in range(iters):
-                launch()
-            e1.record(stream)
-            torch.cuda.synchronize()
-            ms[kind].append(e0.elapsed_time(e1) / iters)
+    copy_gbs = harness.copy_rate(stream)
+    settle = harness.settle(launches, stream)  # about 30 ms of load before anything is timed
+    ms = harness.time_rounds(launches, stream, rounds, iters)  # alternating: every round times every launch once
     result = {"leg": "ofh_ul", "grids": GRIDS, "ports": PORTS, "symbols": NSYMB, "nof_prb": NOF_PRB, "type": "BFP", "data_width": WIDTH,
               "sections": rows, "record_bytes": rec, "bytes_in_plus_out": nbytes, "rounds": rounds, "iters": iters, "settle_rounds": settle,
               "copy_GBps": round(copy_gbs, 1), "hbm_roof_GBps": HBM_ROOF_GBPS, "counters": "not measured",
               "note": "ofh_ul_write_grid is the whole call: host validation and the staging of the descriptors included"}
     for kind in launches:
         m = float(np.median(ms[kind]))
+        ms_med, ms_min, ms_max = harness.spread(ms[kind])
         gbs = nbytes / (m * 1e-3) / 1e9
-        result[kind] = {"ms_per_call": round(m, 5), "ms_min": round(min(ms[kind]), 5), "ms_max": round(max(ms[kind]), 5), "GBps": round(gbs, 1),
+        result[kind] = {"ms_per_call": ms_med, "ms_min": ms_min, "ms_max": ms_max, "GBps": round(gbs, 1),
                         "share_of_hbm_roof": round(gbs / HBM_ROOF_GBPS, 4), "share_of_copy_rate": round(gbs / copy_gbs, 4)}
     write_grid()
     launches["ofh_decompress"]()
@@ -113,21 +84,5 @@ def step(rounds, iters, out):
         f.write(json.dumps(result) + "\n")
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--step", action="store_true", help="run the measurement in this process (what the driver starts)")
-    ap.add_argument("--rounds", type=int, default=15)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds for the GPU step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ofh_ul_bench.json"))
-    args = ap.parse_args()
-    if args.step:
-        step(args.rounds, args.iters, args.out)
-        return 0
-    cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--step", "--rounds", str(args.rounds),
-           "--iters", str(args.iters), "--out", args.out]
-    return subprocess.run(cmd).returncode
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(harness.bench_main(step, (), dict(rounds=15, iters=20, timeout=240, out=os.path.join(ROOT, "profiles", "ofh_ul_bench.json"))))

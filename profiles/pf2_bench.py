@@ -15,14 +15,14 @@ not collected here.  Writes profiles/pf2_bench.json.
 
     python3 profiles/pf2_bench.py            (GPU box, repository root)
 """
-import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
+
+import bench_harness as harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -43,7 +43,6 @@ def step(n, rounds, iters, out):
     rng = np.random.default_rng(0)
     stream = torch.cuda.Stream()
     sp = C.c_void_p(stream.cuda_stream)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     runs = []
     for name, nprb, nsym, A, per_grid in SHAPES:
         n_grids = (n + per_grid - 1) // per_grid
@@ -73,40 +72,11 @@ def step(n, rounds, iters, out):
                     "decoder": (lambda p=decoder, b=bufs: p.run(b["llr"], b["msg"], b["status"], stream=sp), dec_bytes),
                     "both": (lambda p=plan, b=bufs, d=d_grid: p.run(d, b["llr"], b["msg"], b["status"], b["csi"], stream=sp), rx_bytes + dec_bytes)}
         runs.append(dict(name=name, plan=plan, decoder=decoder, grid=d_grid, bufs=bufs, cfgs=cfgs, sent=sent, launches=launches,
-                         ms={k: [] for k in launches}, shape=(nprb, nsym, A, per_grid)))
-    # Copy rate: device to device, 256 MiB, read + write counted.
-    a = torch.empty(64 << 20, dtype=torch.int32, device="cuda")
-    b = torch.empty_like(a)
-    with torch.cuda.stream(stream):
-        for _ in range(3):
-            b.copy_(a)
-        e0.record(stream)
-        for _ in range(10):
-            b.copy_(a)
-        e1.record(stream)
-    torch.cuda.synchronize()
-    copy_gbs = 2 * a.numel() * 4 * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    del a, b
-    # Settling: about 30 ms of load before anything is timed.
-    e0.record(stream)
-    settle = 0
-    while True:
-        for r in runs:
-            r["launches"]["both"][0]()
-        settle += 1
-        e1.record(stream)
-        torch.cuda.synchronize()
-        if e0.elapsed_time(e1) >= 30.0 or settle >= 2000:
-            break
-    for _ in range(rounds):  # alternating: every round times every launch of every shape once
-        for r in runs:
-            for kind, (launch, _) in r["launches"].items():
-                e0.record(stream)
-                for _ in range(iters):
-                    launch()
-                e1.record(stream)
-                torch.cuda.synchronize()
-                r["ms"][kind].append(e0.elapsed_time(e1) / iters)
+                         shape=(nprb, nsym, A, per_grid)))
+    copy_gbs = harness.copy_rate(stream)
+    settle = harness.settle([r["launches"]["both"][0] for r in runs], stream)  # about 30 ms of load before anything is timed
+    # alternating: every round times every launch of every shape once
+    ms = harness.time_rounds({(r["name"], kind): launch for r in runs for kind, (launch, _) in r["launches"].items()}, stream, rounds, iters)
     records = []
     for r in runs:
         nprb, nsym, A, per_grid = r["shape"]
@@ -115,10 +85,11 @@ def step(n, rounds, iters, out):
                "pucch_per_grid": per_grid, "rounds": rounds, "iters": iters, "settle_launches": settle, "copy_GBps": round(copy_gbs, 1),
                "twiddle_bytes_per_pucch_from_cache": TWIDDLE_BYTES, "counters": "not measured"}
         for kind, (_, nbytes) in r["launches"].items():
-            ms = float(np.median(r["ms"][kind]))
-            rec[kind] = {"ms_per_launch": round(ms, 5), "ms_min": round(min(r["ms"][kind]), 5), "ms_max": round(max(r["ms"][kind]), 5),
-                         "ns_per_pucch": round(ms * 1e6 / n, 2), "bytes_per_launch": nbytes, "GBps": round(nbytes / (ms * 1e-3) / 1e9, 2),
-                         "share_of_copy_rate": round(nbytes / (ms * 1e-3) / 1e9 / copy_gbs, 4)}
+            med = float(np.median(ms[r["name"], kind]))
+            ms_med, ms_min, ms_max = harness.spread(ms[r["name"], kind])
+            rec[kind] = {"ms_per_launch": ms_med, "ms_min": ms_min, "ms_max": ms_max,
+                         "ns_per_pucch": round(med * 1e6 / n, 2), "bytes_per_launch": nbytes, "GBps": round(nbytes / (med * 1e-3) / 1e9, 2),
+                         "share_of_copy_rate": round(nbytes / (med * 1e-3) / 1e9 / copy_gbs, 4)}
         rec["pucch_per_s"] = round(n / (rec["both"]["ms_per_launch"] * 1e-3))
         # the first grid's PUCCHs against the restatement, after the timed region (the last launch was `both`)
         r["launches"]["both"][0]()
@@ -143,28 +114,5 @@ def step(n, rounds, iters, out):
         f.write("".join(json.dumps(r) + "\n" for r in records))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--step", type=int, default=0, help="run one batch size in this process (what the driver starts)")
-    ap.add_argument("--rounds", type=int, default=15)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds per GPU step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pf2_bench.json"))
-    args = ap.parse_args()
-    if args.step:
-        step(args.step, args.rounds, args.iters, args.out)
-        return 0
-    if os.path.exists(args.out):
-        os.remove(args.out)
-    for n in SIZES:  # chained: a step that fails or runs out of time ends the benchmark
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--step", str(n), "--rounds",
-               str(args.rounds), "--iters", str(args.iters), "--out", args.out]
-        rc = subprocess.run(cmd).returncode
-        if rc != 0:
-            print("step n=%d ended with status %d: stopping" % (n, rc), file=sys.stderr)
-            return rc
-    return 0
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(harness.bench_main(step, SIZES, dict(rounds=15, iters=20, timeout=240, out=os.path.join(ROOT, "profiles", "pf2_bench.json"))))

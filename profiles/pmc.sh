@@ -2,14 +2,18 @@
 # Collects rocprofv3 PMC counters for the benchmark kernels in separate passes (kernel-trace only, no other trace
 # domains), as /opt/skills/guides/MI355X_MICROARCH.md section HBM prescribes.  Usage (on the GPU box, from the
 # repository root):  bash profiles/pmc.sh <out_dir> [bench args]
+# Every pass runs under a time limit, and the first pass that fails ends the script: nothing more starts on the card after it.
 set -u
 OUT=$(realpath -m "$1"); shift
 mkdir -p "$OUT"
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
 ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-secondary $*"
 run() { # name, counters
-  rocprofv3 --kernel-trace --pmc $2 --output-format csv -d "$OUT/$1" -- python3 "$GRAFT_REPO_ROOT/bench.py" $ARGS > "$OUT/$1.log" 2>&1
-  echo "$1 rc=$?"
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $2 --output-format csv -d "$OUT/$1" -- python3 "$ROOT/bench.py" $ARGS > "$OUT/$1.log" 2>&1
+  local rc=$?
+  echo "$1 rc=$rc"
+  if [ $rc != 0 ]; then tail -20 "$OUT/$1.log" >&2; exit $rc; fi
 }
 run fetch "FETCH_SIZE"
 run write "WRITE_SIZE"

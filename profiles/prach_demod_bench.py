@@ -10,19 +10,20 @@ back-to-back symbols behind the cyclic prefix, writing every bin; the gather of 
 still be to do after it.  A stricter figure is reported next to it: ONE nrphy_dft_run call over a packed copy of all the symbols
 (no prefix between them), which needs a copy the timing leaves out.
 
-Method: both legs run for `--settle` seconds first; then `--rounds` rounds alternate between the legs, each timing `--iters`
-back-to-back repetitions with HIP events on one explicit stream; median and spread (largest - smallest) over the rounds.  The
+Method: one GPU step in a child process of its own under a time limit.  The legs run untimed until the engine clocks have had
+`--settle` seconds of load; then `--rounds` rounds alternate between the legs, each timing `--iters` back-to-back repetitions with
+HIP events on one explicit stream (profiles/bench_harness.py); median and spread (largest - smallest) over the rounds.  The
 demodulator passes a workload when its median does not exceed the yardstick's by more than the larger spread of the two.  After
 the timed region one (occasion, port) is compared with the float64 restatement (tests/prach_demod_model.py).
 Writes profiles/prach_demod_bench.json.  Usage (GPU box, repository root): python3 profiles/prach_demod_bench.py"""
-import argparse
 import ctypes as C
 import json
 import os
 import sys
-import time
 
 import numpy as np
+
+import bench_harness as harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -33,41 +34,18 @@ WORKLOADS = (("format 0, 1 fd", dict(srate_hz=30720000, format="0", nof_fd_occas
              ("B4 at 30 kHz", dict(srate_hz=61440000, format="B4", nof_fd_occasions=1, rb_offset=4, nof_prb_ul_grid=106, pusch_numerology=1)))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, default=64)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--rounds", type=int, default=9)
-    ap.add_argument("--settle", type=float, default=1.0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "prach_demod_bench.json"))
-    args = ap.parse_args()
+def step(rounds, iters, out, n, settle):
     import torch
     import backends
     import prach_demod_model as model
     lib, abi = backends.pkg.lib, backends.abi
     assert torch.cuda.is_available(), "this measurement needs the GPU"
     ctx = lib.Context(0)
-    n, ports = args.n, 4
+    ports = 4
     stream = torch.cuda.Stream()
     sp = C.c_void_p(stream.cuda_stream)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-    def timed(fn, iters):
-        e0.record(stream)
-        for _ in range(iters):
-            fn()
-        e1.record(stream)
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / iters
-
     # The copy rate every "bytes over copy rate" below refers to: a 256 MiB device-to-device copy, read + write counted.
-    a = torch.empty(64 << 20, dtype=torch.float32, device="cuda")
-    b = torch.empty_like(a)
-    with torch.cuda.stream(stream):
-        timed(lambda: b.copy_(a), 3)
-        copy_ms = float(np.median([timed(lambda: b.copy_(a), 5) for _ in range(5)]))
-    copy_gbs = 2 * a.numel() * 4 / copy_ms / 1e6
-    del a, b
+    copy_gbs = harness.copy_rate(stream)
     records = []
     for name, base in WORKLOADS:
         cfg = dict(base, nof_td_occasions=1, start_symbol=0, nof_rx_ports=ports)
@@ -96,21 +74,15 @@ def main():
         def dft_packed():
             assert ctx.lib.nrphy_dft_run(ctx.handle, N, 0, n * ports * nsym, C.c_void_p(d_packed.data_ptr()), C.c_void_p(all_ptr), sp) == abi.OK
 
-        legs = (("demod", demod), ("dft_in_place", dft_in_place), ("dft_packed", dft_packed))
-        t0 = time.time()
-        while time.time() - t0 < args.settle:
-            for _, fn in legs:
-                timed(fn, 2)
-        times = {k: [] for k, _ in legs}
-        for _ in range(args.rounds):
-            for k, fn in legs:
-                times[k].append(timed(fn, args.iters))
+        legs = {"demod": demod, "dft_in_place": dft_in_place, "dft_packed": dft_packed}
+        harness.settle(legs, stream, min_ms=1000 * settle)
+        times = harness.time_rounds(legs, stream, rounds, iters)
         med = {k: float(np.median(v)) for k, v in times.items()}
         spread = {k: float(max(v) - min(v)) for k, v in times.items()}
         symbols = n * ports * nsym
         read_bytes = symbols * N * 8
         rec = {"leg": "prach_demod", "workload": name, "srate_hz": cfg["srate_hz"], "format": cfg["format"], "fd_occasions": nfd,
-               "occasions": n, "rx_ports": ports, "dft_size": N, "symbols_per_launch": symbols, "rounds": args.rounds, "iters": args.iters,
+               "occasions": n, "rx_ports": ports, "dft_size": N, "symbols_per_launch": symbols, "rounds": rounds, "iters": iters,
                "ms_per_launch": round(med["demod"], 4), "ms_spread": round(spread["demod"], 4),
                "ns_per_symbol": round(med["demod"] * 1e6 / symbols, 1),
                "dft_run_in_place_ms": round(med["dft_in_place"], 4), "dft_run_in_place_spread": round(spread["dft_in_place"], 4),
@@ -135,10 +107,11 @@ def main():
         plan.close()
         del d_x, d_buf, d_all, d_packed
         torch.cuda.empty_cache()
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
         f.write("".join(json.dumps(r) + "\n" for r in records))
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(harness.bench_main(step, (), dict(rounds=9, iters=10, timeout=30, out=os.path.join(ROOT, "profiles", "prach_demod_bench.json"),
+                                               n=64, settle=1.0)))

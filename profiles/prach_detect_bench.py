@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """PRACH detector throughput (nrphy_prach_run): 1024 occasions per launch on 4 receive ports, format 0 at zeroCorrelationZone 0
-(64 root sequences per occasion, the worst case) and format B4 (15 kHz) at zeroCorrelationZone 11, timed with HIP events on an
-explicit stream after warm-up, inputs resident in HBM, with and without the metric output.  The occasions are unit-variance
+(64 root sequences per occasion, the worst case) and format B4 (15 kHz) at zeroCorrelationZone 11, inputs resident in HBM, with and
+without the metric output.  One GPU step in a child process under a time limit; per format untimed launches until the clocks have
+had about 30 ms of load, then the two launches in alternating rounds timed with HIP events on an explicit stream, median and spread
+(profiles/bench_harness.py), and the rate of a device-to-device copy measured in the same process.  The occasions are unit-variance
 noise; every eighth carries one preamble.  Where the table's row for a configuration is red its threshold and margin are passed
 as the caller's.  After the timed region one occasion is checked against the NumPy restatement (tests/prach_model.py).
 Writes profiles/prach_detect_bench.json.  Usage (GPU box, repository root): python3 profiles/prach_detect_bench.py [--n 1024]"""
-import argparse
 import ctypes as C
 import json
 import os
@@ -13,26 +14,23 @@ import sys
 
 import numpy as np
 
+import bench_harness as harness
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--n", type=int, default=1024)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "prach_detect_bench.json"))
-    args = ap.parse_args()
+def step(rounds, iters, out, n):
     import torch
     import backends
     import prach_model as model
     lib, abi = backends.pkg.lib, backends.abi
     ctx = lib.Context(0)
-    n, ports = args.n, 4
+    ports = 4
     rng = np.random.default_rng(0)
     s = torch.cuda.Stream()
     sp = C.c_void_p(s.cuda_stream)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    copy_gbs = harness.copy_rate(s)
     records = []
     for fmt, scs, zcz in (("0", "1.25", 0), ("B4", "15", 11)):
         cfg = dict(format=fmt, ra_scs=scs, root_sequence_index=0, zero_correlation_zone=zcz, start_preamble_index=0,
@@ -57,16 +55,12 @@ def main():
                "table_flag": flag, "root_sequences": d["nof_sequences"], "shifts_per_root": d["nof_shifts"],
                "window": d["win_width"], "transforms_per_launch": n * d["nof_sequences"] * ports,
                "input_bytes": int(x.nbytes)}
-        for key, met in (("ms_per_launch", None), ("ms_per_launch_with_metric", d_met)):
-            torch.cuda.synchronize()
-            for _ in range(3):
-                plan.run(d_x, d_res, d_pre, met, stream=sp)
-            e0.record(s)
-            for _ in range(args.iters):
-                plan.run(d_x, d_res, d_pre, met, stream=sp)
-            e1.record(s)
-            torch.cuda.synchronize()
-            rec[key] = round(e0.elapsed_time(e1) / args.iters, 4)
+        launches = {"ms_per_launch": lambda: plan.run(d_x, d_res, d_pre, None, stream=sp),
+                    "ms_per_launch_with_metric": lambda: plan.run(d_x, d_res, d_pre, d_met, stream=sp)}
+        torch.cuda.synchronize()
+        rec.update(rounds=rounds, iters=iters, settle_rounds=harness.settle(launches, s), copy_GBps=round(copy_gbs, 1))
+        for key, ms in harness.time_rounds(launches, s, rounds, iters).items():
+            rec[key], rec[key.replace("ms_per_launch", "ms_min")], rec[key.replace("ms_per_launch", "ms_max")] = harness.spread(ms)
         rec["us_per_occasion"] = round(rec["ms_per_launch"] * 1e3 / n, 3)
         rec["ns_per_transform"] = round(rec["ms_per_launch"] * 1e6 / rec["transforms_per_launch"], 2)
         # one occasion against the restatement, after the timed region
@@ -83,9 +77,10 @@ def main():
         plan.close()
         del d_x, d_met
         torch.cuda.empty_cache()
-    with open(args.out, "w") as f:
+    with open(out, "w") as f:
         f.write("".join(json.dumps(r) + "\n" for r in records))
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(harness.bench_main(step, (), dict(rounds=15, iters=20, timeout=30, out=os.path.join(ROOT, "profiles", "prach_detect_bench.json"),
+                                               n=1024)))

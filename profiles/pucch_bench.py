@@ -13,14 +13,14 @@ collected here.  Writes profiles/pucch_bench.json.
 
     python3 profiles/pucch_bench.py            (GPU box, repository root)
 """
-import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
+
+import bench_harness as harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -50,7 +50,6 @@ def step(n, rounds, iters, out):
     rng = np.random.default_rng(0)
     stream = torch.cuda.Stream()
     sp = C.c_void_p(stream.cuda_stream)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     # Unit-variance noise in every grid; the first grid of every leg also carries its 16 UEs at 6 dB.
     noise = torch.randn((n_grids, PORTS, 14, NOF_SUBC, 2), device="cuda", dtype=torch.float32) * (0.5 ** 0.5)
     runs = []
@@ -70,46 +69,19 @@ def step(n, rounds, iters, out):
         plan = lib.PucchPlan(ctx, [model.to_abi(abi, c) for c in cfgs], [i // PER_GRID for i in range(n)], n_grids, PORTS, NOF_SUBC)
         d_res = torch.zeros((n, RESULT_BYTES // 4), dtype=torch.int32, device="cuda")
         rows = PORTS * nsym * 48
-        runs.append(dict(name=name, plan=plan, grid=d_grid, res=d_res, cfgs=cfgs, sent=sent, ms=[],
+        runs.append(dict(name=name, plan=plan, grid=d_grid, res=d_res, cfgs=cfgs, sent=sent,
                          bytes=n * (rows + DESC_BYTES + RESULT_BYTES)))
     del noise
-    # Copy rate: device to device, 256 MiB, read + write counted.
-    a = torch.empty(64 << 20, dtype=torch.int32, device="cuda")
-    b = torch.empty_like(a)
-    with torch.cuda.stream(stream):
-        for _ in range(3):
-            b.copy_(a)
-        e0.record(stream)
-        for _ in range(10):
-            b.copy_(a)
-        e1.record(stream)
-    torch.cuda.synchronize()
-    copy_gbs = 2 * a.numel() * 4 * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    del a, b
-    # Settling: about 30 ms of load before anything is timed.
-    e0.record(stream)
-    settle = 0
-    while True:
-        for r in runs:
-            r["plan"].run(r["grid"], r["res"], stream=sp)
-        settle += 1
-        e1.record(stream)
-        torch.cuda.synchronize()
-        if e0.elapsed_time(e1) >= 30.0 or settle >= 2000:
-            break
-    for _ in range(rounds):  # alternating: every round times every leg once
-        for r in runs:
-            e0.record(stream)
-            for _ in range(iters):
-                r["plan"].run(r["grid"], r["res"], stream=sp)
-            e1.record(stream)
-            torch.cuda.synchronize()
-            r["ms"].append(e0.elapsed_time(e1) / iters)
+    copy_gbs = harness.copy_rate(stream)
+    launches = {r["name"]: (lambda r=r: r["plan"].run(r["grid"], r["res"], stream=sp)) for r in runs}
+    settle = harness.settle(launches, stream)  # about 30 ms of load before anything is timed
+    times = harness.time_rounds(launches, stream, rounds, iters)  # alternating: every round times every leg once
     records = []
     for r in runs:
-        ms = float(np.median(r["ms"]))
+        ms = float(np.median(times[r["name"]]))
+        ms_med, ms_min, ms_max = harness.spread(times[r["name"]])
         rec = {"leg": "pucch", "case": r["name"], "n": n, "rx_ports": PORTS, "pucch_per_grid": PER_GRID, "rounds": rounds, "iters": iters,
-               "settle_launches": settle, "ms_per_launch": round(ms, 5), "ms_min": round(min(r["ms"]), 5), "ms_max": round(max(r["ms"]), 5),
+               "settle_launches": settle, "ms_per_launch": ms_med, "ms_min": ms_min, "ms_max": ms_max,
                "pucch_per_s": round(n / (ms * 1e-3)), "ns_per_pucch": round(ms * 1e6 / n, 2), "bytes_per_launch": r["bytes"],
                "GBps": round(r["bytes"] / (ms * 1e-3) / 1e9, 2), "copy_GBps": round(copy_gbs, 1),
                "share_of_copy_rate": round(r["bytes"] / (ms * 1e-3) / 1e9 / copy_gbs, 4), "counters": "not measured"}
@@ -132,28 +104,5 @@ def step(n, rounds, iters, out):
         f.write("".join(json.dumps(r) + "\n" for r in records))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--step", type=int, default=0, help="run one batch size in this process (what the driver starts)")
-    ap.add_argument("--rounds", type=int, default=15)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--timeout", type=int, default=240, help="seconds per GPU step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pucch_bench.json"))
-    args = ap.parse_args()
-    if args.step:
-        step(args.step, args.rounds, args.iters, args.out)
-        return 0
-    if os.path.exists(args.out):
-        os.remove(args.out)
-    for n in SIZES:  # chained: a step that fails or runs out of time ends the benchmark
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--step", str(n), "--rounds",
-               str(args.rounds), "--iters", str(args.iters), "--out", args.out]
-        rc = subprocess.run(cmd).returncode
-        if rc != 0:
-            print("step n=%d ended with status %d: stopping" % (n, rc), file=sys.stderr)
-            return rc
-    return 0
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(harness.bench_main(step, SIZES, dict(rounds=15, iters=20, timeout=240, out=os.path.join(ROOT, "profiles", "pucch_bench.json"))))

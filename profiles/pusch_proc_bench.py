@@ -4,18 +4,21 @@ PDUs of 52 PRB each -- QPSK / 16-QAM / 64-QAM, 1 and 2 layers, 1 to 4 receive po
 PDU without codeword (24 PRB, what its polar codeword can fill): the mix of tests/test_pusch_processor.py at 52 PRB -- as one plan of 128 PDUs, every PDU on a grid of its
 own (52 PRB, 4 ports), received at the SNR of the estimator's link cases so that the decoders do a receiver's work.  The hand chain
 is the parent's way and the yardstick: nrphy_pusch_chest_run, nrphy_pusch_demod_run, nrphy_ulsch_demux_run, nrphy_uci_decoder_run
-and one nrphy_pusch_decode_batch per PDU with a codeword, the configurations from nrphy_pusch_proc_derive.  Both are timed with
-HIP events on an explicit stream after warm-up, inputs resident in HBM, `--repeats` times each in alternation; the record holds the
-median and the spread.  Launches are counted as the nodes of one captured run (kernels, memsets and copies).  The two outputs are
+and one nrphy_pusch_decode_batch per PDU with a codeword, the configurations from nrphy_pusch_proc_derive.  One GPU step in a
+child process under a time limit, inputs resident in HBM: both run untimed until the clocks have had about 30 ms of load, then
+`--rounds` alternating rounds time them with HIP events on an explicit stream (profiles/bench_harness.py); the record holds the
+median and the spread, and the rate of a device-to-device copy measured in the same process.  Launches are counted as the nodes
+of one captured run (kernels, memsets and copies).  The two outputs are
 compared byte for byte after the timed region.  Usage (GPU box, repository root):
-python3 profiles/pusch_proc_bench.py [--slots 16] [--iters 10] [--repeats 7]"""
-import argparse
+python3 profiles/pusch_proc_bench.py [--slots 16] [--iters 10] [--rounds 7]"""
 import ctypes as C
 import json
 import os
 import sys
 
 import numpy as np
+
+import bench_harness as harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -46,12 +49,7 @@ def count_nodes(hip, stream, run):
     return int(n.value) if rc == 0 else None
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--slots", type=int, default=16)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--repeats", type=int, default=7)
-    args = ap.parse_args()
+def step(rounds, iters, out, slots):
     import torch
     import backends
     import test_pusch_processor as T
@@ -76,8 +74,8 @@ def main():
     assert None not in derived8
     rng = np.random.default_rng(1)
     sent8 = [T.transmit(ctx, p, d, rng, nsubc) for p, d in zip(slot, derived8)]
-    pdus = slot * args.slots
-    derived = derived8 * args.slots
+    pdus = slot * slots
+    derived = derived8 * slots
     n = len(pdus)
     grids = np.stack([T.noisy(sent8[i % 8], T.GOOD_SNR[(pdus[i].modulation, pdus[i].nof_tx_layers)], rng) for i in range(n)])
     d_grid = T.dev(T.as_i32(grids))
@@ -91,20 +89,9 @@ def main():
     legs = {"processor": lambda: plan.run(d_grid, P.harq, P.tb, P.uci, P.result, stream=sp),
             "hand_chain": lambda: chain.run(d_grid, H, stream=sp)}
     torch.cuda.synchronize()
-    for run in legs.values():
-        for _ in range(3):
-            run()
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    times = {k: [] for k in legs}
-    for r in range(args.repeats):
-        for name in (list(legs) if r % 2 == 0 else list(legs)[::-1]):
-            e0.record(s)
-            for _ in range(args.iters):
-                legs[name]()
-            e1.record(s)
-            torch.cuda.synchronize()
-            times[name].append(e0.elapsed_time(e1) / args.iters)
+    copy_gbs = harness.copy_rate(s)
+    settle = harness.settle(legs, s)
+    times = harness.time_rounds(legs, s, rounds, iters)
     hip = hip_runtime()
     nodes = {name: count_nodes(hip, s.cuda_stream, run) for name, run in legs.items()}
     torch.cuda.synchronize()
@@ -114,16 +101,17 @@ def main():
     torch.cuda.synchronize()
     got, want = P.read(), H.read()
     res = got["result"]
-    rec = {"leg": "pusch_proc", "slots": args.slots, "pdus_per_slot": 8, "nof_prb": NPRB, "grid_ports": T.NPORTS, "n": n,
+    rec = {"leg": "pusch_proc", "slots": slots, "pdus_per_slot": 8, "nof_prb": NPRB, "grid_ports": T.NPORTS, "n": n,
            "pdus_with_codeword": int(sum(p.has_codeword for p in pdus)), "pdus_with_uci": int(sum(d.nof_uci != 0 for d in derived)),
-           "codeblocks": int(res["nof_codeblocks"].sum()), "iters": args.iters, "repeats": args.repeats}
+           "codeblocks": int(res["nof_codeblocks"].sum()), "iters": iters, "repeats": rounds, "rounds": rounds,
+           "settle_rounds": settle, "copy_GBps": round(copy_gbs, 1)}
     for name in legs:
         t = sorted(times[name])
         rec[name + "_ms_per_run"] = round(t[len(t) // 2], 4)
         rec[name + "_ms_min_max"] = [round(t[0], 4), round(t[-1], 4)]
-        rec[name + "_us_per_slot"] = round(1e3 * t[len(t) // 2] / args.slots, 2)
+        rec[name + "_us_per_slot"] = round(1e3 * t[len(t) // 2] / slots, 2)
         rec[name + "_launches_per_run"] = nodes[name]
-        rec[name + "_launches_per_slot"] = None if nodes[name] is None else round(nodes[name] / args.slots, 2)
+        rec[name + "_launches_per_slot"] = None if nodes[name] is None else round(nodes[name] / slots, 2)
     rec["processor_over_hand_chain"] = round(rec["processor_ms_per_run"] / rec["hand_chain_ms_per_run"], 4)
     rec["check_bytes_equal"] = bool(all(got[k].tobytes() == want[k].tobytes() for k in ("tb", "uci", "harq")))
     rec["check_tb_crc_ok"] = int(res["tb_crc_ok"].sum())
@@ -131,7 +119,10 @@ def main():
     print(json.dumps(rec), flush=True)
     plan.close()
     chain.close()
+    with open(out, "w") as f:
+        f.write(json.dumps(rec) + "\n")
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(harness.bench_main(step, (), dict(rounds=7, iters=10, timeout=30, out=os.path.join(ROOT, "profiles", "pusch_proc_bench.json"),
+                                               slots=16)))

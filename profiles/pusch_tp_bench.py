@@ -4,9 +4,14 @@
 1. The 28 recorded reference cases (tests/golden/pusch_tp_reference_*, the transform-precoded configurations of the reference's
    unit test with ZF and MMSE) as ONE plan run, next to the composed path for the same cases: per case nrphy_channel_equalize
    (one batch entry per OFDM symbol with data), nrphy_transform_deprecode, nrphy_demodulate_soft and nrphy_llr_descramble, 112
-   launches in all, on RE already gathered.  Five alternating rounds; the median and the spread are printed.
+   launches in all, on RE already gathered.  `--rounds` alternating rounds of 20 x `--iters` fused runs and `--iters` composed
+   passes; the median and the spread are printed.
 2. A size a cell would run: 16 PUSCHs of 270 PRB, 256-QAM, 4 ports, 12 symbols with data -- the fused launch alone, with the
    bytes it has to move (grid and estimate words in, soft bits out).
+
+One GPU step in a child process under a time limit.  Each part runs untimed until the clocks have had about 30 ms of load and is
+then timed with HIP events on an explicit stream (profiles/bench_harness.py); the rate of a device-to-device copy measured in
+the same process is printed with it.
 
 Usage (GPU box, repository root): python3 profiles/pusch_tp_bench.py
 """
@@ -16,22 +21,13 @@ import sys
 
 import numpy as np
 
+import bench_harness as harness
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def timed(stream, fn, reps):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    for _ in range(reps):
-        fn()
-    e1.record(stream)
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / reps  # microseconds per call of fn
-
-
-def main():
+def step(rounds, iters, out):
     import torch
     import backends
     import pusch_tp_model as model
@@ -93,18 +89,17 @@ def main():
     torch.cuda.synchronize()
     for i, w in enumerate(work):  # the two paths compute the same soft bits
         assert torch.equal(w["d_out"][:w["bits"]], d_llr[i * stride: i * stride + G[i]]), i
-    for _ in range(3):
-        timed(s, fused, 200)
-        timed(s, composed, 20)
-    f = [0.0] * 5
-    c = [0.0] * 5
-    for k in range(5):
-        f[k] = timed(s, fused, 4000)
-        c[k] = timed(s, composed, 200)
+    print("device-to-device copy %.1f GB/s" % harness.copy_rate(s))
+    settle = harness.settle([fused, composed], s)
+    f, c = [], []
+    for _ in range(rounds):  # alternating; microseconds per call
+        f += [1e3 * t for t in harness.time_rounds({"fused": fused}, s, 1, 20 * iters)["fused"]]
+        c += [1e3 * t for t in harness.time_rounds({"composed": composed}, s, 1, iters)["composed"]]
     nre = sum(w["n"] * w["nre"] for w in work)
     print("28 recorded reference cases (%d data RE, %d soft bits): fused run %.1f us (min %.1f, max %.1f), composed device calls "
-          "%.1f us (min %.1f, max %.1f), ratio %.1f" % (nre, sum(G), statistics.median(f), min(f), max(f), statistics.median(c),
-                                                        min(c), max(c), statistics.median(c) / statistics.median(f)))
+          "%.1f us (min %.1f, max %.1f), ratio %.1f; %d rounds after %d settling passes"
+          % (nre, sum(G), statistics.median(f), min(f), max(f), statistics.median(c), min(c), max(c),
+             statistics.median(c) / statistics.median(f), rounds, settle))
     plan.close()
 
     # A cell-sized launch.
@@ -124,16 +119,16 @@ def main():
     def big():
         plan.run(d_grid, d_ce, d_nv, d_llr, bits, d_sinr, stream=sp)
 
-    for _ in range(3):
-        timed(s, big, 50)
-    t = [timed(s, big, 500) for _ in range(5)]
+    settle = harness.settle([big], s)
+    t = [1e3 * ms for ms in harness.time_rounds({"big": big}, s, rounds, 5 * iters // 2)["big"]]
     re = n * 12 * nprb * 12
     nbytes = re * (4 * 4 + 4 * 4) + n * bits
     us = statistics.median(t)
     print("%d PUSCHs x %d PRB x 12 symbols, 256-QAM, 4 ports, MMSE: fused run %.1f us (min %.1f, max %.1f), %.2f G RE/s, %.0f GB/s of "
-          "grid + estimate words in and soft bits out" % (n, nprb, us, min(t), max(t), re / us / 1e3, nbytes / us / 1e3))
+          "grid + estimate words in and soft bits out; %d rounds after %d settling launches"
+          % (n, nprb, us, min(t), max(t), re / us / 1e3, nbytes / us / 1e3, rounds, settle))
     plan.close()
 
 
 if __name__ == "__main__":
-    main()
+    sys.exit(harness.bench_main(step, (), dict(rounds=5, iters=200, timeout=30, out="")))

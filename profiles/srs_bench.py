@@ -12,14 +12,14 @@ are not collected here.  Writes profiles/srs_bench.json.
 
     python3 profiles/srs_bench.py            (GPU box, repository root)
 """
-import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
+
+import bench_harness as harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -38,7 +38,6 @@ def step(n, rounds, iters, out):
     rng = np.random.default_rng(0)
     stream = torch.cuda.Stream()
     sp = C.c_void_p(stream.cuda_stream)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     cfg = abi.make_srs(configuration_index=63, comb_size=2, nof_antenna_ports=4, nof_symbols=SYMBOLS, start_symbol=14 - SYMBOLS,
                        cyclic_shift=1, sequence_id=321, numerology=1, rx_ports=tuple(range(PORTS)))
     M = lib.srs_info(cfg, 0)["sequence_length"]
@@ -51,42 +50,15 @@ def step(n, rounds, iters, out):
     plan = lib.SrsPlan(ctx, [cfg] * n, list(range(n)), n, PORTS, NOF_SUBC)
     d_result = torch.zeros(n * RESULT_BYTES // 4, dtype=torch.int32, device="cuda")
     launch = lambda: plan.run(d_grid, d_result, stream=sp)
-    # Copy rate: device to device, 256 MiB, read + write counted.
-    a = torch.empty(64 << 20, dtype=torch.int32, device="cuda")
-    b = torch.empty_like(a)
-    with torch.cuda.stream(stream):
-        for _ in range(3):
-            b.copy_(a)
-        e0.record(stream)
-        for _ in range(10):
-            b.copy_(a)
-        e1.record(stream)
-    torch.cuda.synchronize()
-    copy_gbs = 2 * a.numel() * 4 * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    del a, b
-    # Settling: about 30 ms of load before anything is timed.
-    e0.record(stream)
-    settle = 0
-    while True:
-        launch()
-        settle += 1
-        e1.record(stream)
-        torch.cuda.synchronize()
-        if e0.elapsed_time(e1) >= 30.0 or settle >= 2000:
-            break
-    ms = []
-    for _ in range(rounds):
-        e0.record(stream)
-        for _ in range(iters):
-            launch()
-        e1.record(stream)
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1) / iters)
+    copy_gbs = harness.copy_rate(stream)
+    settle = harness.settle([launch], stream)  # about 30 ms of load before anything is timed
+    ms = harness.time_rounds({"srs": launch}, stream, rounds, iters)["srs"]
     med = float(np.median(ms))
+    ms_med, ms_min, ms_max = harness.spread(ms)
     nbytes = n * (2 * 16 * SYMBOLS * M * 4 + RESULT_BYTES)  # every path reads its grid words in both launches
     rec = {"leg": "srs", "n": n, "antenna_ports": 4, "rx_ports": PORTS, "nof_symbols": SYMBOLS, "nof_prb": NOF_PRB, "comb": 2, "M": M,
            "workgroups_per_launch": 16 * n, "launches_per_run": 2, "rounds": rounds, "iters": iters, "settle_launches": settle,
-           "ms_per_run": round(med, 5), "ms_min": round(min(ms), 5), "ms_max": round(max(ms), 5), "us_per_srs": round(med * 1e3 / n, 2),
+           "ms_per_run": ms_med, "ms_min": ms_min, "ms_max": ms_max, "us_per_srs": round(med * 1e3 / n, 2),
            "srs_per_s": round(n / (med * 1e-3)), "bytes_per_run": nbytes, "GBps": round(nbytes / (med * 1e-3) / 1e9, 2),
            "copy_GBps": round(copy_gbs, 1), "counters": "not measured"}
     torch.cuda.synchronize()
@@ -102,28 +74,5 @@ def step(n, rounds, iters, out):
         f.write(json.dumps(rec) + "\n")
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--step", type=int, default=0, help="run one batch size in this process (what the driver starts)")
-    ap.add_argument("--rounds", type=int, default=15)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--timeout", type=int, default=120, help="seconds per GPU step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "srs_bench.json"))
-    args = ap.parse_args()
-    if args.step:
-        step(args.step, args.rounds, args.iters, args.out)
-        return 0
-    if os.path.exists(args.out):
-        os.remove(args.out)
-    for n in SIZES:  # chained: a step that fails or runs out of time ends the benchmark
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--step", str(n), "--rounds",
-               str(args.rounds), "--iters", str(args.iters), "--out", args.out]
-        rc = subprocess.run(cmd).returncode
-        if rc != 0:
-            print("step n=%d ended with status %d: stopping" % (n, rc), file=sys.stderr)
-            return rc
-    return 0
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(harness.bench_main(step, SIZES, dict(rounds=15, iters=20, timeout=120, out=os.path.join(ROOT, "profiles", "srs_bench.json"))))

@@ -20,14 +20,14 @@ are not collected here.  Writes profiles/uci_bench.json.
 
     python3 profiles/uci_bench.py            (GPU box, repository root)
 """
-import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
+
+import bench_harness as harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -44,7 +44,6 @@ def step(rounds, iters, out):
     rng = np.random.default_rng(0)
     stream = torch.cuda.Stream()
     sp = C.c_void_p(stream.cuda_stream)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     runs = []
     for name, A, E in LEGS:
         n = N_MESSAGES
@@ -54,7 +53,7 @@ def step(rounds, iters, out):
         plan = lib.UciDecoderPlan(ctx, [abi.make_uci_decoder(A, E, 2)] * n, [i * E for i in range(n)], [i * A for i in range(n)])
         runs.append(dict(name=name, A=A, E=E, n=n, plan=plan, sent=sent, llr=llr, d_llr=torch.from_numpy(llr).cuda(),
                          d_msg=torch.zeros((n, A), dtype=torch.uint8, device="cuda"),
-                         d_status=torch.zeros(n, dtype=torch.int32, device="cuda"), ms=[]))
+                         d_status=torch.zeros(n, dtype=torch.int32, device="cuda")))
     for r in runs:
         r["launch"] = lambda r=r: r["plan"].run(r["d_llr"], r["d_msg"], r["d_status"], stream=sp)
     # The demultiplexer and the copy it is compared with.
@@ -75,36 +74,21 @@ def step(rounds, iters, out):
     d_streams = [torch.zeros(o[-1] + sz, dtype=torch.int8, device="cuda") for o, sz in zip(offs[1:], sizes[1:])]
     dplan = lib.UlschDemuxPlan(ctx, [abi.make_ulsch_demux(**dcfg)] * n_cw, *offs)
     d_copy = torch.empty_like(d_cw)
-    demux = dict(name="ulsch_demux", ms=[], launch=lambda: dplan.run(d_cw, *d_streams, stream=sp))
+    demux = dict(name="ulsch_demux", launch=lambda: dplan.run(d_cw, *d_streams, stream=sp))
 
     def copy_launch():
         with torch.cuda.stream(stream):
             d_copy.copy_(d_cw)
-    copy = dict(name="copy", ms=[], launch=copy_launch)
+    copy = dict(name="copy", launch=copy_launch)
     uci_runs = list(runs)
     runs = uci_runs + [demux, copy]
-    # Settling: about 30 ms of load before anything is timed.
-    e0.record(stream)
-    settle = 0
-    while True:
-        for r in runs:
-            r["launch"]()
-        settle += 1
-        e1.record(stream)
-        torch.cuda.synchronize()
-        if e0.elapsed_time(e1) >= 30.0 or settle >= 2000:
-            break
-    for _ in range(rounds):  # alternating: every round times every leg once
-        for r in runs:
-            e0.record(stream)
-            for _ in range(iters):
-                r["launch"]()
-            e1.record(stream)
-            torch.cuda.synchronize()
-            r["ms"].append(e0.elapsed_time(e1) / iters)
+    launches = {r["name"]: r["launch"] for r in runs}
+    settle = harness.settle(launches, stream)  # about 30 ms of load before anything is timed
+    times = harness.time_rounds(launches, stream, rounds, iters)  # alternating: every round times every leg once
     records = []
     for r in uci_runs:
-        ms = float(np.median(r["ms"]))
+        ms = float(np.median(times[r["name"]]))
+        ms_med, ms_min, ms_max = harness.spread(times[r["name"]])
         got, status = r["d_msg"].cpu().numpy(), r["d_status"].cpu().numpy()
         ok_sent = int(((status == 1) & (got == r["sent"]).all(axis=1)).sum())
         ok_model = 0
@@ -112,8 +96,8 @@ def step(rounds, iters, out):
             want, want_status = model.decode(r["llr"][i], r["A"], 2)
             ok_model += int(status[i] == want_status and np.array_equal(got[i], want))
         rec = {"leg": "uci_decoder", "case": r["name"], "message_length": r["A"], "llr_length": r["E"], "n": r["n"], "rounds": rounds,
-               "iters": iters, "settle_launches": settle, "ms_per_launch": round(ms, 5), "ms_min": round(min(r["ms"]), 5),
-               "ms_max": round(max(r["ms"]), 5), "messages_per_s": round(r["n"] / (ms * 1e-3)), "ns_per_message": round(ms * 1e6 / r["n"], 2),
+               "iters": iters, "settle_launches": settle, "ms_per_launch": ms_med, "ms_min": ms_min,
+               "ms_max": ms_max, "messages_per_s": round(r["n"] / (ms * 1e-3)), "ns_per_message": round(ms * 1e6 / r["n"], 2),
                "input_GBps": round(r["n"] * r["E"] / (ms * 1e-3) / 1e9, 3), "counters": "not measured",
                "check_valid_with_sent_bits": "%d of %d" % (ok_sent, r["n"]), "check_equal_restatement": "%d of 64" % ok_model}
         print(json.dumps(rec), flush=True)
@@ -123,11 +107,12 @@ def step(rounds, iters, out):
     want = model.ulsch_demultiplex(dcfg, cw)
     got = [t.cpu().numpy() for t in d_streams]
     ok = sum(all(got[k][offs[k + 1][i]:offs[k + 1][i] + sizes[k + 1]].tobytes() == want[k].tobytes() for k in range(4)) for i in range(n_cw))
-    ms, ms_copy = float(np.median(demux["ms"])), float(np.median(copy["ms"]))
+    ms, ms_copy = float(np.median(times["ulsch_demux"])), float(np.median(times["copy"]))
+    ms_med, ms_min, ms_max = harness.spread(times["ulsch_demux"])
     moved = n_cw * (total + sum(sizes[1:]))  # bytes read and written by the demultiplexer
     rate, copy_rate = moved / (ms * 1e-3) / 1e9, 2 * d_cw.numel() / (ms_copy * 1e-3) / 1e9
     rec = {"leg": "ulsch_demux", "case": "273prb_13sym_4layers_256qam", "n": n_cw, "codeword_bytes": total, "rounds": rounds, "iters": iters,
-           "ms_per_launch": round(ms, 5), "ms_min": round(min(demux["ms"]), 5), "ms_max": round(max(demux["ms"]), 5),
+           "ms_per_launch": ms_med, "ms_min": ms_min, "ms_max": ms_max,
            "GBps_read_plus_written": round(rate, 1), "copy_ms": round(ms_copy, 5), "copy_GBps_read_plus_written": round(copy_rate, 1),
            "fraction_of_copy_rate": round(rate / copy_rate, 3), "counters": "not measured",
            "check_equal_restatement": "%d of %d" % (ok, n_cw)}
@@ -138,24 +123,5 @@ def step(rounds, iters, out):
         f.write("".join(json.dumps(r) + "\n" for r in records))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--step", action="store_true", help="run the GPU step in this process (what the driver starts)")
-    ap.add_argument("--rounds", type=int, default=15)
-    ap.add_argument("--iters", type=int, default=20)
-    ap.add_argument("--timeout", type=int, default=300, help="seconds for the GPU step")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "uci_bench.json"))
-    args = ap.parse_args()
-    if args.step:
-        step(args.rounds, args.iters, args.out)
-        return 0
-    cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--step", "--rounds", str(args.rounds),
-           "--iters", str(args.iters), "--out", args.out]
-    rc = subprocess.run(cmd).returncode
-    if rc != 0:
-        print("the GPU step ended with status %d" % rc, file=sys.stderr)
-    return rc
-
-
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(harness.bench_main(step, (), dict(rounds=15, iters=20, timeout=300, out=os.path.join(ROOT, "profiles", "uci_bench.json"))))

@@ -23,11 +23,12 @@ import argparse
 import ctypes as C
 import json
 import os
-import subprocess
 import sys
 import time
 
 import numpy as np
+
+import bench_harness as harness
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -42,26 +43,9 @@ def ofdm_cfg(abi):
 
 
 def timed(launch, stream, rounds, iters):
-    import torch
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record(stream)
-    settle = 0
-    while True:  # settling: about 30 ms of load before anything is timed
-        launch()
-        settle += 1
-        e1.record(stream)
-        torch.cuda.synchronize()
-        if e0.elapsed_time(e1) >= 30.0 or settle >= 2000:
-            break
-    ms = []
-    for _ in range(rounds):
-        e0.record(stream)
-        for _ in range(iters):
-            launch()
-        e1.record(stream)
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1) / iters)
-    return {"ms": round(float(np.median(ms)), 5), "ms_min": round(min(ms), 5), "ms_max": round(max(ms), 5), "settle_launches": settle}
+    settle = harness.settle([launch], stream)  # about 30 ms of load before anything is timed
+    ms, ms_min, ms_max = harness.spread(harness.time_rounds({"launch": launch}, stream, rounds, iters)["launch"])
+    return {"ms": ms, "ms_min": ms_min, "ms_max": ms_max, "settle_launches": settle}
 
 
 def step_kernel(tag, rounds, iters):
@@ -80,19 +64,7 @@ def step_kernel(tag, rounds, iters):
     torch.cuda.synchronize()
     samples = SLOTS * PORTS * lib.slot_size(cfg, 1)
     grid_bytes = SLOTS * PORTS * 14 * NOF_SUBC * 4
-    a = torch.empty(64 << 20, dtype=torch.int32, device="cuda")
-    b = torch.empty_like(a)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    with torch.cuda.stream(stream):
-        for _ in range(3):
-            b.copy_(a)
-        e0.record(stream)
-        for _ in range(10):
-            b.copy_(a)
-        e1.record(stream)
-    torch.cuda.synchronize()
-    copy_gbs = 2 * a.numel() * 4 * 10 / (e0.elapsed_time(e1) * 1e-3) / 1e9
-    del a, b
+    copy_gbs = harness.copy_rate(stream)
     legs = [("demod_run", 8, lambda: plan.demod_run(SLOTS, d_iq, d_grid, d_slot_index=d_slot, stream=sp))]
     if hasattr(ctx.lib, "nrphy_ofdm_demod_symbols"):
         legs.append(("demod_symbols_cf32", 8, lambda: plan.demod_symbols(SLOTS, d_iq, d_grid, 0, 14, d_slot_index=d_slot, stream=sp)))
@@ -251,16 +223,12 @@ def main():
     steps = [(["--step", "kernel", "--tag", tag], lib) for tag, lib in libs]
     steps += [(["--step", "hand", "--tag", tag], lib) for tag, lib in libs[:2]]
     steps += [(["--step", "pool", "--depth", str(d), "--symbols-per-run", str(s)], "") for d, s in ((1, 14), (4, 14), (4, 1))]
-    for extra, lib in steps:  # chained: a step that fails or runs out of time ends the benchmark
-        env = dict(os.environ)
-        if lib:
-            env["NRPHY_LIB_SO"] = os.path.abspath(lib)
-        cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--rounds", str(args.rounds), "--iters",
-               str(args.iters), "--slots", str(args.slots), "--out", args.out] + extra
-        rc = subprocess.run(cmd, env=env).returncode
-        if rc != 0:
-            print("step %s ended with status %d: stopping" % (" ".join(extra), rc), file=sys.stderr)
-            return rc
+    common = [sys.executable, os.path.abspath(__file__), "--rounds", str(args.rounds), "--iters", str(args.iters), "--slots", str(args.slots),
+              "--out", args.out]
+    rc = harness.run_steps([("ul_slot_%d_%s" % (i, extra[1]), common + extra, {"NRPHY_LIB_SO": os.path.abspath(lib)} if lib else {}, args.timeout)
+                            for i, (extra, lib) in enumerate(steps)], harness.LOG_DIR)
+    if rc != 0:
+        return rc
     if not args.parent_lib:
         with open(args.out, "a") as f:
             f.write(json.dumps({"leg": "kernel", "library": "parent", "ms": "not measured"}) + "\n")

@@ -20,7 +20,7 @@
 #endif
 
 // Stage stops of the profiling variants (profiles/make_variant.sh NAME "pdsch_kernels.hip ofdm_kernels.hip nrphy_host.cpp ofdm_host.cpp pdsch_host.cpp pdsch_plan_build.cpp"
-// "-DNRPHY_PROBES"; profiles/stage_pmc.sh, stage_times.sh): the codeblock waves return after stage n, the outputs are then
+// "-DNRPHY_PROBES"; profiles/stage_pmc.sh, ab.py stages): the codeblock waves return after stage n, the outputs are then
 // incomplete.  The product library is built without them -- the tests compile to nothing.
 #ifdef NRPHY_PROBES
 #define NRPHY_STAGE(p) ((p).profile_stage)
