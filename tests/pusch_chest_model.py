@@ -161,6 +161,26 @@ def virtual_pilots(abs_, arg, offset):
     return out
 
 
+def interpolate(Fr, Fi):
+    """The smoothed pilots (float32) -> cbf16 words of the allocation [2 N]: the reference's running sum of half steps, the last
+    element repeated, then cbf16."""
+    outs = []
+    for F in (Fr, Fi):
+        hh = ((F[1:] - F[:-1]) * f32(0.5)).astype(np.float32)
+        seq = np.concatenate([F[:1], np.repeat(hh, 2)]).astype(np.float32)
+        o = np.cumsum(seq, dtype=np.float32)
+        outs.append(np.concatenate([o, F[-1:]]).astype(np.float32))
+    return to_words(outs[0], outs[1])
+
+
+def rotate(row, cfo, epoch):
+    """A row of cbf16 words at one symbol: rotated by the CFO's phase at the symbol's start and rounded again (cfo None: as is)."""
+    if cfo is None:
+        return row
+    a, b = from_words(row)
+    return to_words(*cmul(a, b, *phasor(f32(f32(TWOPI * epoch) * cfo))))
+
+
 def estimate_port_layer(cfg, grid, port, layer):
     """Returns (row: interpolated cbf16 words of the allocation [12 nprb], cfo or None, measurements dict)."""
     prbs = prbs_of(cfg)
@@ -244,15 +264,7 @@ def estimate_port_layer(cfg, grid, port, layer):
     top = np.sort(mag)[-2:]
     near_tie = bool(top[1] - top[0] <= 1e-4 * top[1])
 
-    # interpolation: the reference's running sum, then cbf16
-    hr = ((Fr[1:] - Fr[:-1]) * f32(0.5)).astype(np.float32)
-    hi = ((Fi[1:] - Fi[:-1]) * f32(0.5)).astype(np.float32)
-    outs = []
-    for F, hh in ((Fr, hr), (Fi, hi)):
-        seq = np.concatenate([F[:1], np.repeat(hh, 2)]).astype(np.float32)
-        o = np.cumsum(seq, dtype=np.float32)
-        outs.append(np.concatenate([o, F[-1:]]).astype(np.float32))
-    row = to_words(outs[0], outs[1])
+    row = interpolate(Fr, Fi)
 
     epre_f = f32(epre / (N * nd))
     nvar_raw = f32(ne / (N * nd - 1))
@@ -263,7 +275,7 @@ def estimate_port_layer(cfg, grid, port, layer):
     scs = 15000 << cfg.numerology
     meas = {"noise_var": noise_var, "rsrp": rsrp, "epre": epre_f, "snr": snr, "ta_bins": ta_bins,
             "ta_s": f32(ta_bins / (4096.0 * scs)), "cfo_hz": f32(f32(cfo * f32(scs // 1000)) * f32(1000)) if nd >= 2 else f32(np.nan),
-            "ta_near_tie": near_tie, "ta_mag": mag}
+            "ta_near_tie": near_tie, "ta_mag": mag, "smoothed": (Fr + 1j * Fi).astype(np.complex64), "cfo": cfo}
     return row, cfo, meas
 
 
@@ -282,11 +294,7 @@ def estimate(cfg, grid, ce=None):
             row, cfo, m = estimate_port_layer(cfg, grid, p, l)
             meas[p][l] = m
             for s in range(cfg.start_symbol_index, cfg.start_symbol_index + cfg.nof_symbols):
-                w = row
-                if cfo is not None:
-                    a, b = from_words(row)
-                    w = to_words(*cmul(a, b, *phasor(f32(f32(TWOPI * ep[s]) * cfo))))
-                w = w.copy()
+                w = rotate(row, cfo, ep[s]).copy()
                 if cfg.dc_position != NO_DC:
                     w[subc == cfg.dc_position] = 0
                 ce[l, p, s, subc] = w

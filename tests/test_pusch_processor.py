@@ -723,7 +723,9 @@ GOLDEN = os.path.join(backends.ROOT, "tests", "golden")
 RES = ("tb_crc_ok", "nof_codeblocks", "harq_ack_status", "csi_part1_status", "sinr_ch_estimator_dB", "sinr_post_eq_dB", "epre_dB",
        "rsrp_dB", "time_alignment_s", "has_cfo", "cfo_hz", "has_sch")
 DB_FIELDS = ("epre_dB", "rsrp_dB", "sinr_ch_estimator_dB")
-# The project's estimator is pinned to its restatement (tests/pusch_chest_model.py), not to the reference's bits.  REF_DB_SPREAD and
+# The project's estimator and its restatement (tests/pusch_chest_model.py) are pinned to a recording of the reference's estimator
+# in tests/test_pusch_channel_estimator.py (smoothed pilots, estimate, per-path measurements, time alignment bin); here the
+# processor's aggregated channel state information is compared through that restatement.  REF_DB_SPREAD and
 # REF_CFO_SPREAD are the largest distances, over the recorded cases, between what the reference's processor reported and the
 # restatement's per-port measurements carried through get_channel_state_information in float64: dB values relative to
 # max(|value|, DB_FLOOR), the CFO relative to max(|CFO|, CFO_FLOOR_HZ) -- the floors and the factor 8 are those of tests/test_pucch.py.
