@@ -668,7 +668,8 @@ int nrphy_prach_generate_host(nrphy_ctx_t* ctx, const nrphy_prach_cfg_t* cfg, ui
  * srate / ra_scs samples behind the prefix at dft_size * s; its transform is direct and unnormalised, with no phase or frequency
  * correction.  With K = pusch_scs / ra_scs, grid = nof_prb_ul_grid * K * 12 and k_start = K * 12 * (rb_offset + N_RB^RA * i_fd) +
  * k_bar (TS 38.211 Table 6.3.3.2-1), element i < L_RA of frequency-domain occasion i_fd is transform bin
- * (k_start + i - grid / 2) mod dft_size.  Unrestricted by set; float samples only. */
+ * (k_start + i - grid / 2) mod dft_size.  Unrestricted by set; complex float samples here, complex int16 ones through
+ * nrphy_prach_window_demod_run (below, with the pool of PRACH windows that collects them). */
 typedef struct nrphy_prach_demod_cfg {
   uint32_t srate_hz;              /* sampling rate; srate_hz / ra_scs must be a size nrphy_dft_run has */
   uint32_t format;                /* NRPHY_PRACH_FORMAT_* */
@@ -2055,6 +2056,98 @@ const nrphy_pucch_result_t* nrphy_ul_slot_pf01_results(nrphy_ul_slots_t* pool, u
 int nrphy_ul_slot_format2_results(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t i, const uint8_t** message, uint32_t* nbits,
                               uint32_t* status, nrphy_pf2_csi_t* csi);
 const nrphy_srs_result_t* nrphy_ul_slot_sounding_results(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t* n);
+
+/* ---- receive side: the OFDM PRACH demodulator from float or int16 samples -------------------------------------------------------
+ * nrphy_prach_demod_run with a sample format.  The plan is the same: its element offsets (in_offset, in_port_stride) count samples
+ * in either format.  NRPHY_IQ_CF32 is exactly nrphy_prach_demod_run (iq_scale is ignored).  NRPHY_IQ_CI16: a sample is two int16
+ * (re, im), 4 bytes, at the same sample index (d_iq 4-byte aligned), and each component becomes float(x) * gain with gain = 1.0f /
+ * iq_scale formed once in single precision, the product rounded on its own before the first butterfly, as
+ * srsvec::convert(span<const int16_t>, float scale, span<cf_t>) does (R/lib/srsvec/conversion.cpp:67-129); everything behind the
+ * load is the same code, so the two formats give the same bytes on equal values, on the single transform and on the split one.
+ * NRPHY_ERR_ARGUMENT, with no launch, for an unknown iq_format and for ci16 an iq_scale that is not positive and finite.
+ * Asynchronous on `stream`; allocates nothing, touches no host memory, uses no atomics (capturable). */
+int nrphy_prach_window_demod_run(nrphy_prach_demod_plan_t* plan, const void* d_iq, uint32_t iq_format, float iq_scale,
+                                 void* d_symbols, void* stream);
+
+/* ---- the PRACH window pipeline: baseband samples to detected preambles ------------------------------------------------------------
+ * What the reference's lower PHY does per PRACH occasion -- prach_processor_worker appends symbol after symbol to a window buffer
+ * until get_prach_window_duration samples are there, then demodulates into the prach_buffer and notifies
+ * (R/lib/phy/lower/processors/uplink/prach/prach_processor_worker.cpp:31-162) -- and what the upper PHY does with that buffer
+ * (prach_detector::detect), with the buffer staying in HBM: per window the samples go down, in the radio's own format, and the
+ * detections come up.  The sibling of nrphy_ul_slots_* for the one uplink channel whose window is not a slot.
+ *
+ * A pool owns `depth` windows, each with a stream, pinned and device sample staging of max_window_samples per port in the pool's
+ * format, a device prach_buffer sized from the max_* fields, and a device and a pinned result block.  Everything a window is asked
+ * to do is enqueued on its stream in call order; no call allocates device memory or waits for the device unless it says so --
+ * except an open whose configurations differ from the window's last, below.  Calls on ONE window are serialised by the library
+ * (a lock per window); different windows may be driven from different threads.
+ *
+ *   nrphy_prach_window_open     prach_processor_worker::handle_request: a free window (NRPHY_ERR_CAPACITY when all `depth` are
+ *                               open) for one PRACH context, given as the demodulator's and the detector's configuration.  Both
+ *                               must pass nrphy_prach_demod_validate / nrphy_prach_validate and agree (NRPHY_ERR_ARGUMENT): one
+ *                               format; detect->ra_scs the spacing the format and the PUSCH numerology give; one nof_rx_ports;
+ *                               demod->srate_hz the pool's.  PRACH port p takes its samples from radio port radio_port[p], which
+ *                               must be below nof_radio_ports.  NRPHY_ERR_CAPACITY for more samples, ports or occasions than the
+ *                               pool's max_* fields.  The window length is window_samples of nrphy_prach_demod_sizes.  The window
+ *                               has one demodulator plan and one detector plan with an item per (td, fd) occasion, td outer,
+ *                               reading the window's buffer in place.  PRACH configuration is cell-static: a window keeps the
+ *                               plans of its last open and reuses them when both configurations and the port map are byte-equal;
+ *                               only an open that differs makes new plans (an allocation and a blocking upload each, under the
+ *                               context's host lock) and frees the old ones.  The buffer is zeroed on the window's stream.
+ *   nrphy_prach_window_samples  accumulate_samples: radio_port_samples[r] is a host span of nof_samples samples of radio port r in
+ *                               the pool's format (only the mapped ports are read).  *taken = min(window length - collected,
+ *                               nof_samples) of them, from the front, are copied into the pinned staging behind what is there (a
+ *                               memcpy on the calling thread), then one host-to-device copy per PRACH port.  taken may be 0 or
+ *                               fewer than offered: that is no error.  The call that completes the window also enqueues
+ *                               nrphy_prach_window_demod_run, nrphy_prach_run (no metric), ONE device-to-host copy of the result
+ *                               block, and `done(user, status, window_id)` on a thread of the HIP runtime (it must not call HIP or
+ *                               this library except the accessors and nrphy_prach_window_poll).  After that, NRPHY_ERR_ARGUMENT.
+ *   nrphy_prach_window_device_buffer / _stream / _buffer_written   split 7.2: the caller runs nrphy_ofh_ul_write_prach on the
+ *                               window's stream into the window's buffer (C-contiguous [port][td][fd][symbol][L_RA] complex f32 in
+ *                               the dimensions of the open), then _buffer_written enqueues the detector, the result copy and the
+ *                               callback.  Once per open; refused after a samples call, and a samples call after it is refused.
+ *   nrphy_prach_window_poll / _wait / _close   as the slot pools': poll never blocks (NRPHY_ERR_NOT_READY until done), wait
+ *                               blocks for a window whose detector is enqueued (NRPHY_ERR_ARGUMENT for one still collecting),
+ *                               close waits for what is in flight and frees the window (its plans stay for the next open)
+ *   nrphy_prach_window_read_buffer   blocking: everything enqueued so far, then the buffer to the host
+ * NRPHY_ERR_ARGUMENT for an id that is not open.  A refused call enqueues nothing.
+ * A device error in a samples or _buffer_written call that has begun to enqueue ends the window: the call returns the error, nothing
+ * more is accepted, poll and wait give NRPHY_ERR_DEVICE and `done` does not run; close gives the window back.
+ *
+ * Accessors, valid from completion with status NRPHY_OK until close (NULL before, and for a window that failed):
+ * nrphy_prach_window_results gives the n = nof_td * nof_fd result headers, td outer
+ * (occasion = td * nof_fd + fd); nrphy_prach_window_preambles the 64 records of one occasion, as nrphy_prach_run writes them.
+ * nrphy_prach_windows_plans_made counts the plan pairs the pool has made since it was created. */
+typedef struct nrphy_prach_windows nrphy_prach_windows_t;
+typedef void (*nrphy_prach_window_done_fn)(void* user, int status, uint32_t window_id);
+typedef struct nrphy_prach_windows_cfg {
+  uint32_t srate_hz;              /* the radio's sampling rate: every open's demod->srate_hz */
+  uint32_t nof_radio_ports;       /* receive ports of the radio, 1..64 */
+  uint32_t depth;                 /* windows open at once, 1..16 */
+  uint32_t iq_format;             /* NRPHY_IQ_CF32 / NRPHY_IQ_CI16 */
+  uint32_t max_window_samples;    /* per port */
+  float    iq_scale;              /* ci16 only */
+  uint32_t max_ports;             /* PRACH ports per window, 1..4 */
+  uint32_t max_td_occasions;      /* 1..7 */
+  uint32_t max_fd_occasions;      /* 1..8 */
+} nrphy_prach_windows_cfg_t;
+int nrphy_prach_windows_create(nrphy_ctx_t* ctx, const nrphy_prach_windows_cfg_t* cfg, nrphy_prach_windows_t** pool);
+int nrphy_prach_windows_destroy(nrphy_prach_windows_t* pool); /* waits for everything in flight, then frees */
+int nrphy_prach_windows_wait_free(nrphy_prach_windows_t* pool); /* blocks while all `depth` windows are open */
+uint64_t nrphy_prach_windows_plans_made(nrphy_prach_windows_t* pool);
+int nrphy_prach_window_open(nrphy_prach_windows_t* pool, const nrphy_prach_demod_cfg_t* demod, const uint32_t* radio_port,
+                            const nrphy_prach_cfg_t* detect, nrphy_prach_window_done_fn done, void* user, uint32_t* window_id);
+int nrphy_prach_window_close(nrphy_prach_windows_t* pool, uint32_t window_id);
+int nrphy_prach_window_samples(nrphy_prach_windows_t* pool, uint32_t window_id, uint32_t nof_samples,
+                               const void* const* radio_port_samples, uint32_t* taken);
+void* nrphy_prach_window_device_buffer(nrphy_prach_windows_t* pool, uint32_t window_id);
+void* nrphy_prach_window_stream(nrphy_prach_windows_t* pool, uint32_t window_id);
+int nrphy_prach_window_buffer_written(nrphy_prach_windows_t* pool, uint32_t window_id);
+int nrphy_prach_window_poll(nrphy_prach_windows_t* pool, uint32_t window_id);
+int nrphy_prach_window_wait(nrphy_prach_windows_t* pool, uint32_t window_id);
+int nrphy_prach_window_read_buffer(nrphy_prach_windows_t* pool, uint32_t window_id, void* symbols);
+const nrphy_prach_result_t* nrphy_prach_window_results(nrphy_prach_windows_t* pool, uint32_t window_id, uint32_t* n);
+const nrphy_prach_preamble_t* nrphy_prach_window_preambles(nrphy_prach_windows_t* pool, uint32_t window_id, uint32_t occasion);
 
 #ifdef __cplusplus
 }

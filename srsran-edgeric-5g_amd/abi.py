@@ -721,6 +721,16 @@ class UlSlotsCfg(C.Structure):
 UL_SLOT_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_uint32)   # nrphy_ul_slot_done_fn
 
 
+class PrachWindowsCfg(C.Structure):
+    """nrphy_prach_windows_cfg_t: the PRACH window pipeline (baseband samples to detected preambles, the prach_buffer on the device)."""
+    _fields_ = [("srate_hz", C.c_uint32), ("nof_radio_ports", C.c_uint32), ("depth", C.c_uint32), ("iq_format", C.c_uint32),
+                ("max_window_samples", C.c_uint32), ("iq_scale", C.c_float), ("max_ports", C.c_uint32),
+                ("max_td_occasions", C.c_uint32), ("max_fd_occasions", C.c_uint32)]
+
+
+PRACH_WINDOW_DONE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_uint32)   # nrphy_prach_window_done_fn
+
+
 def prb_mask_words(prbs):
     """Bit mask words (5 x uint64) with the given PRB indices set."""
     words = [0] * PRB_WORDS
@@ -1027,6 +1037,22 @@ def declare(lib, prefix="nrphy_"):
     sig("ul_slot_pf01_results", vp, vp, u32, P(u32))
     sig("ul_slot_format2_results", i32, vp, u32, u32, P(vp), P(u32), P(u32), P(Pf2Csi))
     sig("ul_slot_sounding_results", vp, vp, u32, P(u32))
+    sig("prach_window_demod_run", i32, vp, vp, u32, C.c_float, vp, vp)
+    sig("prach_windows_create", i32, vp, P(PrachWindowsCfg), P(vp))
+    sig("prach_windows_destroy", i32, vp)
+    sig("prach_windows_wait_free", i32, vp)
+    sig("prach_windows_plans_made", u64, vp)
+    sig("prach_window_open", i32, vp, P(PrachDemodCfg), P(u32), P(PrachCfg), vp, vp, P(u32))
+    sig("prach_window_close", i32, vp, u32)
+    sig("prach_window_samples", i32, vp, u32, u32, P(vp), P(u32))
+    sig("prach_window_device_buffer", vp, vp, u32)
+    sig("prach_window_stream", vp, vp, u32)
+    sig("prach_window_buffer_written", i32, vp, u32)
+    sig("prach_window_poll", i32, vp, u32)
+    sig("prach_window_wait", i32, vp, u32)
+    sig("prach_window_read_buffer", i32, vp, u32, vp)
+    sig("prach_window_results", vp, vp, u32, P(u32))
+    sig("prach_window_preambles", vp, vp, u32, u32)
     return lib
 
 
@@ -1091,4 +1117,9 @@ ABI_SYMBOLS = [
     "nrphy_ul_slot_finish", "nrphy_ul_slot_poll", "nrphy_ul_slot_wait", "nrphy_ul_slot_read_grid", "nrphy_ul_slot_pusch_results",
     "nrphy_ul_slot_tb", "nrphy_ul_slot_pusch_uci", "nrphy_ul_slot_pf01_results", "nrphy_ul_slot_format2_results",
     "nrphy_ul_slot_sounding_results",
+    "nrphy_prach_window_demod_run",
+    "nrphy_prach_windows_create", "nrphy_prach_windows_destroy", "nrphy_prach_windows_wait_free", "nrphy_prach_windows_plans_made",
+    "nrphy_prach_window_open", "nrphy_prach_window_close", "nrphy_prach_window_samples", "nrphy_prach_window_device_buffer",
+    "nrphy_prach_window_stream", "nrphy_prach_window_buffer_written", "nrphy_prach_window_poll", "nrphy_prach_window_wait",
+    "nrphy_prach_window_read_buffer", "nrphy_prach_window_results", "nrphy_prach_window_preambles",
 ]

@@ -544,9 +544,11 @@ struct PrachDemodLaunch {
   const PrachDemodDesc* desc;
   const PrachDemodJob*  jobs;                  // the jobs of this transform size
   const float2*         tw_lds;                // the table of the LDS transform's size
-  const float2*         samples;
+  const void*           samples;               // complex f32, or complex int16 (ci16): the offsets count samples in either
   float2*               symbols;
   uint32_t              n_jobs;
+  uint32_t              ci16;                  // NRPHY_IQ_CI16
+  float                 iq_gain;               // ci16: 1.0f / iq_scale, rounded once on the host
 };
 hipError_t launch_prach_demod(uint32_t lds_size, const PrachDemodLaunch& p, hipStream_t stream);
 // ---- PUCCH formats 0 and 1 (receive side) ---------------------------------------------------------------------------------

@@ -5,6 +5,8 @@
 // (R/lib/ran/prach/prach_preamble_information.cpp) and prach_frequency_mapping_get (prach_frequency_mapping.cpp) as tables.
 #include "nrphy_host_internal.h"
 
+#include <cmath>
+
 namespace {
 
 struct prach_demod_preamble_row_t {
@@ -255,9 +257,13 @@ extern "C" int nrphy_prach_demod_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
   return NRPHY_OK;
 }
 
-extern "C" int nrphy_prach_demod_run(nrphy_prach_demod_plan_t* plan, const void* d_samples, void* d_symbols, void* stream)
+extern "C" int nrphy_prach_window_demod_run(nrphy_prach_demod_plan_t* plan, const void* d_iq, uint32_t iq_format, float iq_scale,
+                                            void* d_symbols, void* stream)
 {
-  if (plan == nullptr || d_samples == nullptr || d_symbols == nullptr || (((uintptr_t)d_samples | (uintptr_t)d_symbols) & 7U) != 0) {
+  const bool ci16 = iq_format == NRPHY_IQ_CI16;
+  if (plan == nullptr || d_iq == nullptr || d_symbols == nullptr || iq_format > NRPHY_IQ_CI16 ||
+      ((uintptr_t)d_iq & (ci16 ? 3U : 7U)) != 0 || ((uintptr_t)d_symbols & 7U) != 0 ||
+      (ci16 && !(iq_scale > 0.f && std::isfinite(iq_scale)))) {
     return NRPHY_ERR_ARGUMENT;
   }
   HIP_TRY(hipSetDevice(plan->ctx->device));
@@ -266,12 +272,19 @@ extern "C" int nrphy_prach_demod_run(nrphy_prach_demod_plan_t* plan, const void*
     p.desc    = plan->d_desc;
     p.jobs    = plan->d_jobs + g.first;
     p.tw_lds  = g.tw_lds;
-    p.samples = (const float2*)d_samples;
+    p.samples = d_iq;
     p.symbols = (float2*)d_symbols;
     p.n_jobs  = g.count;
+    p.ci16    = ci16 ? 1U : 0U;
+    p.iq_gain = ci16 ? 1.0f / iq_scale : 1.0f;
     HIP_TRY(launch_prach_demod(g.lds_size, p, stream ? (hipStream_t)stream : plan->ctx->stream));
   }
   return NRPHY_OK;
+}
+
+extern "C" int nrphy_prach_demod_run(nrphy_prach_demod_plan_t* plan, const void* d_samples, void* d_symbols, void* stream)
+{
+  return nrphy_prach_window_demod_run(plan, d_samples, NRPHY_IQ_CF32, 1.0f, d_symbols, stream);
 }
 
 extern "C" int nrphy_prach_demodulate_host(nrphy_ctx_t* ctx, const nrphy_prach_demod_cfg_t* cfg, const void* samples,

@@ -17,11 +17,20 @@
 // The wanted bins are nof_fd runs of L_RA, `spacing` bins apart, from first_bin on modulo dft_size.  With rel = (bin - first_bin)
 // mod dft_size a bin is wanted iff rel < span and rel mod spacing < L_RA.  A sink holds bin j of the N2-point transform, that is
 // the bins j, j + N2, ... of X: rel runs over (j - first_bin) mod N2 + t N2 below span.
+//
+// The samples come as complex float (IQ_CI16 = false) or as the radio's complex int16 (true), as in ofdm_demod_kernel: two int16
+// per sample at the same sample index, each widened as srsvec::convert does (R/lib/srsvec/conversion.cpp:67-129), float(x) * gain
+// with gain = 1 / scale rounded once on the host, the product a value of its own before the first butterfly.  A lane takes the
+// registers of its first stage straight from memory in both formats, so it loads one 4-byte sample where the float instance
+// loads 8 bytes: consecutive lanes read consecutive samples (256 contiguous bytes per wave and load in the single transform, one
+// sample in n1 on the decimated path, where the other n1 - 1 passes find the lines in L2 as before).  A wider load per lane would
+// want the lane to own neighbouring samples, which the first stage's x[tid + k N / R0] does not give it without a pass through
+// LDS.  Everything behind the load is the same code for both formats.
 #include "fft_device.h"
 
 namespace nrphy {
 
-template <int N>
+template <int N, bool IQ_CI16>
 __global__ __launch_bounds__(Plan<N>::T) void prach_demod_kernel(PrachDemodLaunch p)
 {
   __shared__ cf       lds[N + N / 16 + 16];
@@ -32,7 +41,9 @@ __global__ __launch_bounds__(Plan<N>::T) void prach_demod_kernel(PrachDemodLaunc
   const uint32_t      first_bin = d.first_bin, first_bin_lds = d.first_bin_lds;
   const uint64_t      fd_stride = d.fd_stride;
   const float2* __restrict__ tw_total = d.tw_total;
-  const float2* __restrict__ in       = p.samples + job.in_offset;
+  const float2* __restrict__ in       = static_cast<const float2*>(p.samples) + job.in_offset;   // IQ_CI16 = false
+  const uint32_t* __restrict__ in16   = static_cast<const uint32_t*>(p.samples) + job.in_offset; // IQ_CI16 = true
+  const float         iq_gain = p.iq_gain;
   float2*             out = p.symbols + job.out_offset;
   const TwiddleBase<N> tb = load_twiddle_base<-1, N>(p.tw_lds, tid);
   for (uint32_t r = 0; r != n1; ++r) {
@@ -40,8 +51,15 @@ __global__ __launch_bounds__(Plan<N>::T) void prach_demod_kernel(PrachDemodLaunc
 #pragma unroll
     for (int k = 0; k != Plan<N>::R0; ++k) {
       const uint32_t i = first_stage_index<N>(tid, k);
-      const float2   v = (i < N) ? in[(size_t)i * n1 + r] : make_float2(0.f, 0.f);
-      a[k]             = make_cf(v.x, v.y);
+      if constexpr (IQ_CI16) {
+        const uint32_t raw = (i < N) ? in16[(size_t)i * n1 + r] : 0u;
+        cf v = make_cf(__fmul_rn((float)(int16_t)(raw & 0xFFFFu), iq_gain), __fmul_rn((float)(int16_t)(raw >> 16), iq_gain));
+        asm("" : "+v"(v));
+        a[k] = v;
+      } else {
+        const float2 v = (i < N) ? in[(size_t)i * n1 + r] : make_float2(0.f, 0.f);
+        a[k]           = make_cf(v.x, v.y);
+      }
     }
     auto store = [&](uint32_t q, auto base, auto, cf v) {
       const uint32_t j = q + decltype(base)::value;
@@ -67,7 +85,11 @@ __global__ __launch_bounds__(Plan<N>::T) void prach_demod_kernel(PrachDemodLaunc
 template <int N>
 static hipError_t launch_n(const PrachDemodLaunch& p, hipStream_t stream)
 {
-  hipLaunchKernelGGL((prach_demod_kernel<N>), dim3(p.n_jobs), dim3(Plan<N>::T), 0, stream, p);
+  if (p.ci16) {
+    hipLaunchKernelGGL((prach_demod_kernel<N, true>), dim3(p.n_jobs), dim3(Plan<N>::T), 0, stream, p);
+  } else {
+    hipLaunchKernelGGL((prach_demod_kernel<N, false>), dim3(p.n_jobs), dim3(Plan<N>::T), 0, stream, p);
+  }
   return hipGetLastError();
 }
 

@@ -1159,6 +1159,11 @@ class PrachDemodPlan:
         _check(self.ctx.lib.nrphy_prach_demod_run(self.handle, _dptr(d_samples), _dptr(d_symbols), _stream(stream)),
                "nrphy_prach_demod_run")
 
+    def run_iq(self, d_iq, d_symbols, iq_format=abi.IQ_CF32, iq_scale=1.0, stream=None):
+        """nrphy_prach_window_demod_run: the same from complex64 or (abi.IQ_CI16) int16-pair samples; returns the status."""
+        return int(self.ctx.lib.nrphy_prach_window_demod_run(self.handle, _dptr(d_iq), iq_format, iq_scale, _dptr(d_symbols),
+                                                             _stream(stream)))
+
     def close(self):
         if self.handle:
             self.ctx.lib.nrphy_prach_demod_plan_destroy(self.handle)
@@ -1568,6 +1573,92 @@ class UlSlots(_SlotPool):
 
     def srs_results(self, sid):
         return self._records(self.ctx.lib.nrphy_ul_slot_sounding_results, sid, abi.SrsResult)
+
+
+class PrachWindows(_SlotPool):
+    """nrphy_prach_windows: the PRACH window pipeline -- the samples of a window collected run by run in the radio's format, the
+    demodulator and the detector on the window's device-resident prach_buffer, the detections served from pinned host memory
+    (prach_processor_worker.cpp:31-162).  The calls that the order rules may refuse return the status; the others raise."""
+    _PREFIX, _DONE_FN = "nrphy_prach_window", abi.PRACH_WINDOW_DONE_FN
+    _WAIT_FREE, _DESTROY = "nrphy_prach_windows_wait_free", "nrphy_prach_windows_destroy"
+
+    def __init__(self, ctx, srate_hz, nof_radio_ports, depth, max_window_samples, iq_format=abi.IQ_CF32, iq_scale=1.0, max_ports=1,
+                 max_td_occasions=1, max_fd_occasions=1):
+        self.ctx, self.nof_radio_ports, self.iq_format = ctx, nof_radio_ports, iq_format
+        c = abi.PrachWindowsCfg()
+        c.srate_hz, c.nof_radio_ports, c.depth, c.iq_format, c.max_window_samples = srate_hz, nof_radio_ports, depth, iq_format, max_window_samples
+        c.iq_scale, c.max_ports, c.max_td_occasions, c.max_fd_occasions = iq_scale, max_ports, max_td_occasions, max_fd_occasions
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_prach_windows_create(ctx.handle, C.byref(c), C.byref(h)), "nrphy_prach_windows_create")
+        self._adopt(h)
+        self._shape = {}
+
+    def open(self, demod_cfg, radio_ports, detect_cfg, on_done=None):
+        """(status, window id or None).  on_done(status, window_id) runs on a HIP runtime thread when the window's detections are
+        in pinned host memory.  radio_ports: per PRACH port the radio port its samples come from."""
+        wid = C.c_uint32()
+        cb = self._done_callback(None, on_done)  # registered under the id once the call has given it
+        ports = (C.c_uint32 * max(len(radio_ports), 1))(*radio_ports)
+        rc = int(self.ctx.lib.nrphy_prach_window_open(self.handle, C.byref(demod_cfg), ports, C.byref(detect_cfg), cb, None, C.byref(wid)))
+        self._keep.pop(None, None)
+        if rc != abi.OK:
+            return rc, None
+        self._keep[wid.value] = cb
+        sz = prach_demod_sizes(demod_cfg)
+        self._shape[wid.value] = (demod_cfg.nof_rx_ports, demod_cfg.nof_td_occasions, demod_cfg.nof_fd_occasions, sz.nof_symbols,
+                                  sz.sequence_length)
+        return rc, wid.value
+
+    def samples(self, wid, radio_port_samples):
+        """radio_port_samples: per RADIO port the samples of the run, complex64 [n] or (abi.IQ_CI16 pools) int16 [n][2]; None for
+        a port no PRACH port maps to.  Returns (status, taken)."""
+        dtype = np.int16 if self.iq_format == abi.IQ_CI16 else np.complex64
+        keep = [None if x is None else np.ascontiguousarray(x, dtype=dtype) for x in radio_port_samples]
+        assert len(keep) == self.nof_radio_ports
+        n = {x.size // (2 if self.iq_format == abi.IQ_CI16 else 1) for x in keep if x is not None}
+        assert len(n) == 1
+        ptrs = (C.c_void_p * len(keep))(*[None if x is None else x.ctypes.data for x in keep])
+        taken = C.c_uint32()
+        rc = int(self.ctx.lib.nrphy_prach_window_samples(self.handle, wid, n.pop(), ptrs, C.byref(taken)))
+        return rc, int(taken.value)
+
+    def read_grid(self, sid):
+        raise AttributeError("a PRACH window has no grid: read_buffer")
+
+    def device_buffer(self, wid):
+        return self.ctx.lib.nrphy_prach_window_device_buffer(self.handle, wid)
+
+    def stream(self, wid):
+        return self.ctx.lib.nrphy_prach_window_stream(self.handle, wid)
+
+    def buffer_written(self, wid):
+        return int(self.ctx.lib.nrphy_prach_window_buffer_written(self.handle, wid))
+
+    def read_buffer(self, wid):
+        """Blocking: the window's prach_buffer [ports][td][fd][symbols][L_RA] complex64."""
+        out = np.zeros(self._shape[wid], np.complex64)
+        _check(self.ctx.lib.nrphy_prach_window_read_buffer(self.handle, wid, out.ctypes.data), "nrphy_prach_window_read_buffer")
+        return out
+
+    def results(self, wid):
+        """Copies of the window's abi.PrachResult headers, one per (td, fd) occasion, td outer."""
+        n = C.c_uint32()
+        ptr = self.ctx.lib.nrphy_prach_window_results(self.handle, wid, C.byref(n))
+        assert ptr
+        out = (abi.PrachResult * n.value)()
+        C.memmove(out, ptr, C.sizeof(abi.PrachResult) * n.value)
+        return list(out)
+
+    def preambles(self, wid, occasion):
+        """A copy of the 64 abi.PrachPreamble records of one occasion."""
+        ptr = self.ctx.lib.nrphy_prach_window_preambles(self.handle, wid, occasion)
+        assert ptr
+        out = (abi.PrachPreamble * abi.PRACH_MAX_PREAMBLES)()
+        C.memmove(out, ptr, C.sizeof(out))
+        return out
+
+    def plans_made(self):
+        return int(self.ctx.lib.nrphy_prach_windows_plans_made(self.handle))
 
 
 class OfdmPlan:
