@@ -1,7 +1,7 @@
 #!/bin/bash
 # Builds a variant of libmi355nrphy.so with extra compiler flags on one or more sources, for A/B runs on one box
 # (profiles/ab.py lib, rx, stages, ofdm-parts).  Build container, repository root:
-#   bash profiles/make_variant.sh NAME "ofdm_kernels.hip" "-DNRPHY_WIRE_EXP=1"              ->  build/variants/NAME.so
+#   bash profiles/make_variant.sh NAME "ofdm_kernels.hip" "-DNRPHY_IQ_STORE_AUX=2"             ->  build/variants/NAME.so
 #   bash profiles/make_variant.sh NAME "pdsch_kernels.hip ofdm_kernels.hip nrphy_host.cpp ofdm_host.cpp pdsch_host.cpp pdsch_plan_build.cpp" "-DNRPHY_PROBES"
 set -eu
 NAME=$1; SRCS=$2; EXTRA=${3:-}

@@ -33,6 +33,15 @@ __device__ uint64_t g_wg_trace[8 * WG_TRACE_MAX];
 #define NRPHY_WG_TRACE_WHERE(role) ((void)0)
 #endif
 
+// Stage stops of the profiling variants (profiles/make_variant.sh NAME "pdsch_kernels.hip ofdm_kernels.hip nrphy_host.cpp ofdm_host.cpp pdsch_host.cpp pdsch_plan_build.cpp"
+// "-DNRPHY_PROBES"; profiles/stage_pmc.sh, ab.py stages): the codeblock waves return after stage n, the outputs are then
+// incomplete.  The product library is built without them -- the tests compile to nothing.
+#ifdef NRPHY_PROBES
+#define NRPHY_STAGE(p) ((p).profile_stage)
+#else
+#define NRPHY_STAGE(p) 0u
+#endif
+
 // Plan tables (PDU descriptors, work lists) never change while a kernel runs.  Reading them through the constant
 // address space tells the compiler so: wave-uniform reads become scalar loads into SGPRs (one s_load_dwordx16 for
 // sixteen fields) instead of vector loads + v_readfirstlane with a full memory round trip each.

@@ -1,5 +1,5 @@
 // CRC24B (TS 38.212 Section 5.1, g = x^24 + x^23 + x^6 + x^5 + x + 1) without tables, and the range arithmetic of the
-// word-aligned segmentation: plain C++ that the codeblock kernel (pdsch_kernels.hip) and a host test program
+// word-aligned segmentation: plain C++ that the codeblock kernel (codeblock_build_device.h) and a host test program
 // (tests/crc24b_fold_check.cpp) compile from this one text.
 //
 // The generator factors: g = (x + 1) (x^23 + x^5 + 1).  Modulo the trinomial p = x^23 + x^5 + 1, x^23 = x^5 + 1: a polynomial

@@ -1001,14 +1001,11 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(5))) void l
 // old messages for nineteen edges -- and runs with the registers of three waves per SIMD (all that the LDS of a high-rate launch
 // holds anyway: four workgroups of three waves per CU at BASELINE config 5; with 128 registers the compiler serialises the LDS
 // reads of an edge pass through two temporaries); base graph 2 stops at degree 10 and fits the registers of four.
-#ifndef NRPHY_DECODER_BG1_SLOT_WAVES
-#define NRPHY_DECODER_BG1_SLOT_WAVES 3
-#endif
 __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(3))) void ldpc_decode_msg_bg1_kernel(LdpcDecodeLaunch p)
 {
   ldpc_decode_body<Form::MESSAGES, 19, false>(p);
 }
-__global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(NRPHY_DECODER_BG1_SLOT_WAVES))) void ldpc_decode_msg_bg1_slot_kernel(LdpcDecodeLaunch p)
+__global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(3))) void ldpc_decode_msg_bg1_slot_kernel(LdpcDecodeLaunch p)
 {
   ldpc_decode_body<Form::MESSAGES, 19, true>(p);
 }

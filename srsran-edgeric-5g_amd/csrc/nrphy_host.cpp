@@ -260,8 +260,6 @@ Tunables read_tunables()
   t.crc_regions       = number("NRPHY_CRC_REGIONS", 0);
   t.scr_parts_big     = number("NRPHY_SCR_PARTS_BIG", 0);
   t.scr_words         = number("NRPHY_SCR_WORDS", -1);
-  t.extras_nt         = (uint32_t)number("NRPHY_EXTRAS_NT", 1);
-  t.prologue_order    = (uint32_t)number("NRPHY_PROLOGUE_ORDER", 0);
   t.decoder_pairs     = number("NRPHY_DECODER_PAIRS", -1);
   t.decoder_ldsmsg    = number("NRPHY_DECODER_LDSMSG", -1);
   t.decoder_slots_all = number("NRPHY_DECODER_SLOTS_ALL", 0) == 1;

@@ -183,8 +183,6 @@ struct Tunables {
   int      crc_regions     = 0;  // NRPHY_CRC_REGIONS: 16 KiB regions per TB-CRC workgroup (0: by batch size)
   int      scr_parts_big   = 0;  // NRPHY_SCR_PARTS_BIG: parts per scrambling sequence in a batch of 128 PDUs or more (0: 1)
   int      scr_words       = -1; // NRPHY_SCR_WORDS: 0 = scrambling sequences always as seeds, 1 = always as words (-1: words within the L2 budget)
-  uint32_t extras_nt       = 1;  // NRPHY_EXTRAS_NT=0: DM-RS / zero-fill stores with the default cache policy
-  uint32_t prologue_order  = 0;  // NRPHY_PROLOGUE_ORDER=1: sequence workgroups spread among the TB-CRC workgroups
   int      decoder_pairs   = -1; // NRPHY_DECODER_PAIRS=0: one check per lane whatever the lifting size
   int      decoder_ldsmsg  = -1; // NRPHY_DECODER_LDSMSG: 0 = messages never in LDS, 2 = wherever a workgroup's LDS can hold them
   bool     decoder_slots_all = false; // NRPHY_DECODER_SLOTS_ALL=1: a scratch slot per codeblock (no pooling)

@@ -62,7 +62,7 @@ struct GoldTables {
 // ---- PDSCH plan ---------------------------------------------------------------------------------------------
 constexpr int RE_CHUNK = 512; // data RE handled by one wavefront
 // Scratch region of a codeblock wave during LDPC encoding: doubled systematic blocks (2 * 22 * 12 words), the core rows'
-// scratch (80 words), then the graph rows (pdsch_kernels.hip, CbShared).
+// scratch (80 words), then the graph rows (codeblock_build_device.h, CbShared).
 #define NRPHY_CB_U_GRAPH_OFFSET (2 * 22 * 12 + 80)
 
 enum SymKind : uint32_t { SYM_NONE = 0, SYM_CONTIGUOUS = 1, SYM_TABLE = 2 };
@@ -238,10 +238,8 @@ struct PdschLaunch {
   uint32_t           grid_nof_ports;
   uint32_t           grid_nof_subc;
   uint32_t           lds_lin_words;  // dynamic LDS carve of the codeblock kernel (words, multiples of 4): the codeblock ...
-  uint32_t           lds_u_words;    // ... and the scratch region its stages share (pdsch_kernels.hip, CbShared)
+  uint32_t           lds_u_words;    // ... and the scratch region its stages share (codeblock_build_device.h, CbShared)
   uint32_t           profile_stage; // 0 = run everything; n > 0 = codeblock waves stop after stage n (NRPHY_PROFILE_STAGE)
-  uint32_t           extras_nt;     // 1: the stores of the DM-RS / zero-fill waves are non-temporal (NRPHY_EXTRAS_NT)
-  uint32_t           prologue_order; // 0: sequence workgroups first; 1: spread among the CRC workgroups (NRPHY_PROLOGUE_ORDER)
   // 1: this run clears what it does not map (zero_grids): the DM-RS waves then also clear the resource elements of a CDM group
   // that is reserved (no data) but carries no pilots of the PDU; 0: like the reference's mapper, they leave those alone --
   // whatever another writer of the slot put there stays.

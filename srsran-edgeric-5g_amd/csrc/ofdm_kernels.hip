@@ -10,7 +10,7 @@
 // dft_processor_generic_impl::run (R/lib/phy/generic_functions/dft_processor_generic_impl.cpp:14-218).
 #include "fft_device.h"
 
-// Probes of the profiling variants (-DNRPHY_PROBES, see pdsch_kernels.hip): bit 0 drops the IQ stores, bit 1 the grid loads
+// Probes of the profiling variants (-DNRPHY_PROBES, see NRPHY_STAGE in bits_device.h): bit 0 drops the IQ stores, bit 1 the grid loads
 // (buffer ranges of zero bytes), bit 2 takes the grids first to last.  Not in the product library.
 #ifdef NRPHY_PROBES
 #define NRPHY_PROBE(p) ((p).probe)
@@ -123,9 +123,6 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
   return wave_reduce_bits(v, [](uint32_t a, uint32_t b) { return a + b; });
 }
 
-#ifndef NRPHY_WIRE_EXP
-#define NRPHY_WIRE_EXP 0 // profiling experiments (profiles/make_variant.sh): 1 = no power measurements, 2 = no exact path, 3 = no atomics
-#endif
 template <int N>
 struct IqSinkCi16 {
   static constexpr bool  all_outputs = NRPHY_SINK_ALL_WIRE != 0;
@@ -151,7 +148,6 @@ struct IqSinkCi16 {
 #pragma clang fp contract(off) // every product is rounded on its own, as the reference's separate steps are (the squares are made
     // values of their own as well: see pack_plain)
     const cf    g  = cmul_uniform(v, ph) * gain; // packed: (re, im) x gain
-#if NRPHY_WIRE_EXP != 1
     cf          sq = g * g;
     asm("" : "+v"(sq));
     const float pw = sq.x + sq.y;
@@ -160,7 +156,6 @@ struct IqSinkCi16 {
     if constexpr (PREFIX) {
       *sum += idx >= N - cp ? pw : 0.f;
     }
-#endif
     return g;
   }
 
@@ -227,11 +222,7 @@ struct IqSinkCi16 {
     });
     *peak = fmaxf(*peak, reach);
     uint32_t w[R];
-#if NRPHY_WIRE_EXP == 2
-    if (false) {
-#else
     if (__builtin_expect(__ballot(reach > limit_sq) != 0, 0)) {
-#endif
       static_for<R>([&](auto J) {
         constexpr uint32_t j = decltype(J)::value;
         w[j]                 = pack_exact<(S * (j + 1) > N - N / 4)>(g[j], q + S * j);
@@ -273,12 +264,8 @@ __device__ __forceinline__ void load_symbol_row(uint32_t (&raw)[Plan<N>::R0], co
 // registers instead of 160 / 165 and four workgroups fit a CU where three did.  The wire-format kernel wants the fourth -- its
 // residents cover one another's barriers and waits: 0.41 -> 0.38 ms per 1024 config-3 slots --, the float kernel, which sits at the
 // memory system's rate, does not: 0.47 -> 0.51 ms with four, so it keeps three (A/B on one box, three rounds,
-// profiles/r04_ofdm_sinks.txt).  -DNRPHY_OFDM_WAVES=n: both kernels at n waves per SIMD (experiments).
-#ifdef NRPHY_OFDM_WAVES
-#define OFDM_OCCUPANCY __attribute__((amdgpu_waves_per_eu(NRPHY_OFDM_WAVES, NRPHY_OFDM_WAVES)))
-#else
+// profiles/r04_ofdm_sinks.txt).
 #define OFDM_OCCUPANCY __attribute__((amdgpu_waves_per_eu(WIRE ? 1 : 3, WIRE ? 4 : 3)))
-#endif
 template <int N, int SPW, bool WIRE>
 __global__ __launch_bounds__(Plan<N>::T) OFDM_OCCUPANCY void ofdm_kernel(OfdmLaunch p, const uint32_t* __restrict__ d_grid,
                                                           const uint32_t* __restrict__ d_slot_index,
@@ -341,7 +328,7 @@ __global__ __launch_bounds__(Plan<N>::T) OFDM_OCCUPANCY void ofdm_kernel(OfdmLau
     // The workgroup's measurements go to its own record (lane 0 of each wave through LDS, then one 16-byte store): atomics
     // on the [grid][port] record from every wave cost 0.13 ms per 1024 slots; wire_stats_kernel adds the records up, in a
     // fixed order.
-    if (p.wire_stats != nullptr && NRPHY_WIRE_EXP != 3) { // wave-uniform
+    if (p.wire_stats != nullptr) { // wave-uniform
       w_sum     = wave_sum(w_sum);
       w_peak    = wave_max(w_peak);
       w_clipped = wave_sum(w_clipped);

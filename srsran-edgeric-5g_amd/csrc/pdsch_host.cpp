@@ -226,15 +226,6 @@ extern "C" int nrphy_pdsch_run(nrphy_pdsch_plan_t* plan, const uint8_t* d_tb, vo
   p.grid_nof_subc  = plan->grid_nof_subc;
   p.lds_lin_words  = plan->lds_lin_words;
   p.lds_u_words    = plan->lds_u_words;
-  // Store policy of the DM-RS / zero-fill waves at the tail of the codeblock launch: non-temporal (NRPHY_EXTRAS_NT=0: default
-  // policy).  It moves time from the OFDM launch that follows to the codeblock launch.  Before the OFDM launch took its grids
-  // last to first the balance depended on the box (+1.2 % whole step where the OFDM launch is slow, 0 ... -1 % where it is
-  // fast); with that order, A/B on one box, two rounds (profiles/r03_codeblock_experiments.txt): codeblock 0.301 -> 0.314 ms,
-  // OFDM 0.500 -> 0.466 ms, whole step +2.0 %.
-  // (Placing those waves first or between the codeblock waves instead: the codeblock launch 0.44 / 0.46 ms -- their stores push
-  // the transport blocks and sequences out of the cache.)
-  p.extras_nt      = ctx->tune.extras_nt;
-  p.prologue_order = ctx->tune.prologue_order;
 #ifdef NRPHY_PROBES
   // Profiling variant: stop the codeblock waves after a stage to time the stages apart (outputs are then incomplete).
   p.profile_stage = ctx->tune.profile_stage;

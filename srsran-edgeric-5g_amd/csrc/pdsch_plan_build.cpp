@@ -954,7 +954,7 @@ int PlanBuilder::build(size_t scratch_capacity_words)
   build_zero_fill();
   sort_into_buckets();
   choose_scrambling_form(scratch_capacity_words);
-  // The codeblock waves load 2 * NRPHY_MAX_PORTS * layers weights whatever the port count (pdsch_kernels.hip, phase_b).
+  // The codeblock waves load 2 * NRPHY_MAX_PORTS * layers weights whatever the port count (re_map_device.h, phase_b).
   t.weights.insert(t.weights.end(), 2 * NRPHY_MAX_PORTS * NRPHY_MAX_PORTS, 0.0F);
   plan.cw_bits     = cw_bits;
   plan.n_work      = (uint32_t)t.work.size();
@@ -966,7 +966,7 @@ int PlanBuilder::build(size_t scratch_capacity_words)
   plan.n_dmrs_seq  = seqs.n_dmrs_seq;
   // The dynamic LDS of the codeblock launch also serves the DM-RS waves it may carry.
   plan.lds_lin_words = std::max<uint32_t>(plan.lds_lin_words, 64);
-  // The scratch region the stages of a codeblock wave share (pdsch_kernels.hip, CbShared): doubled systematic blocks + graph
+  // The scratch region the stages of a codeblock wave share (codeblock_build_device.h, CbShared): doubled systematic blocks + graph
   // rows, then modulation table + symbol bytes.
   plan.lds_u_words = std::max<uint32_t>(NRPHY_CB_U_GRAPH_OFFSET + plan.lds_graph_words, 512U + plan.lds_symb_words);
   return NRPHY_OK;

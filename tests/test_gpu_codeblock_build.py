@@ -1,4 +1,4 @@
-"""GPU tests of the first stage of a codeblock wave (build_codeblock in csrc/pdsch_kernels.hip): segmentation of the transport
+"""GPU tests of the first stage of a codeblock wave (build_codeblock in csrc/codeblock_build_device.h): segmentation of the transport
 block -- the word-aligned path and the one for any bit offset -- and the table-free codeblock CRC (csrc/crc24b_fold.h).  Every
 case runs with the scrambling sequences as words and as seeds (two kernels that share the stage); every grid (uint16 view) and
 every codeword tap is compared bit for bit with the CPU oracle's pdsch_process, and the two forms with each other.  A small CPU
