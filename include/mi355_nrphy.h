@@ -1839,8 +1839,8 @@ int nrphy_ul_sch_info(const nrphy_ulsch_info_cfg_t* cfg, nrphy_ulsch_info_t* out
  * grid to the transport block and its CRC verdict, the HARQ-ACK and CSI part 1 payloads with their status, and the
  * channel_state_information record -- nrphy_pusch_chest_run, nrphy_pusch_demod_run, nrphy_ulsch_demux_run, nrphy_uci_decoder_run
  * and nrphy_pusch_decode_batch with the configurations nrphy_pusch_proc_derive gives, on one stream with no host step, followed
- * by one launch that writes a nrphy_pusch_result_t per PDU.  Not covered, and refused: CSI part 2 (its size depends on the
- * decoded part 1; the two-plan route of nrphy_ulsch_demux_plan_create stays), the EVM and the EVM-based SINR, DM-RS type 2.
+ * by one launch that writes a nrphy_pusch_result_t per PDU.  A PDU with a CSI part 2 description is refused here and taken by
+ * nrphy_pusch_csi2_* (the next section).  Not covered, and refused: the EVM and the EVM-based SINR, DM-RS type 2.
  * Transform precoding is never enabled, as in the reference's processor. */
 #define NRPHY_PUSCH_SINR_CHANNEL_ESTIMATOR 0u /* channel_state_information::sinr_type */
 #define NRPHY_PUSCH_SINR_POST_EQUALIZATION 1u
@@ -1856,7 +1856,7 @@ typedef struct nrphy_pusch_pdu {              /* pusch_processor::pdu_t */
   uint32_t tb_size_bytes;                     /* the size of `data` */
   uint32_t tbs_lbrm_bytes;                    /* > 0 */
   uint32_t nof_harq_ack, nof_csi_part1;       /* uci: payload bits, 0 = none */
-  uint32_t nof_csi_part2_entries;             /* uci.csi_part2_size.entries.size(): must be 0 */
+  uint32_t nof_csi_part2_entries;             /* uci.csi_part2_size.entries.size(): 0 for nrphy_pusch_proc_*, nrphy_pusch_csi2_desc_t::nof_entries for nrphy_pusch_csi2_* */
   float    alpha_scaling, beta_offset_harq_ack, beta_offset_csi_part1, beta_offset_csi_part2;
   uint32_t start_symbol_index, nof_symbols;
   uint32_t dmrs_type;                         /* must be 1 */
@@ -1951,6 +1951,95 @@ int nrphy_pusch_proc_run(nrphy_pusch_proc_plan_t* plan, const void* d_grid, void
 int nrphy_pusch_proc_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_proc_options_t* options, const void* grid,
                           uint32_t grid_nof_ports, uint32_t grid_nof_subc, int8_t* harq_soft, uint8_t* harq_state, uint8_t* tb,
                           uint8_t* uci_bits, nrphy_pusch_result_t* result);
+
+/* ---- receive side: PUSCH processor with CSI part 2 ---------------------------------------------------------------------------------
+ * What pusch_processor_impl::process does with pdu.uci.csi_part2_size (pusch_processor_impl.cpp:57-86 and
+ * pusch_processor_notifier_adaptor.h:268): once CSI part 1 has decoded `valid`, uci_part2_get_size
+ * (R/lib/ran/uci/uci_part2_size_calculator.cpp) turns its payload into the size of part 2; a size above 0 redoes
+ * get_ulsch_information, tells the demultiplexer (set_csi_part2) and the decoder (set_nof_softbits), and part 2 is decoded.  An
+ * invalid part 1 or a size of 0 leaves the PDU as if it had no part 2: what nrphy_pusch_proc_run computes.
+ *
+ * Nothing is sized on the device.  A description has at most 2 entries of at most 4 index bits, so a PDU has few possible sizes:
+ * the plan enumerates the distinct ones ("variants": 0 = no part 2, then the non-zero sizes ascending), derives for each the UL-SCH
+ * information, the demultiplexer's placement, the UCI decoder's code and the transport-block decoder's length on the host with the
+ * code of the stages, and the run chooses among them on the device: the launches of nrphy_pusch_proc_run up to the UCI decoder;
+ * one launch that evaluates every description on its decoded part 1 and writes a select word per PDU; one demultiplexer launch,
+ * one UCI decoder launch and the rate-dematcher launches of every variant, of which only the selected ones act; one LDPC decode
+ * and one assembly per PDU; the result kernels.  One stream, no host step, no allocation.
+ *
+ * Part 2 is placed as TS 38.212 Section 6.2.7 places it and as a UE transmits it: from the first symbol without DM-RS on.  The
+ * reference's demultiplexer is a stream and starts placing part 2 in the symbol that holds the last part 1 RE
+ * (ulsch_demultiplex_impl.cpp:241-251, 539-543); the two differ only when part 1 spans several symbols that also hold REs reserved
+ * for HARQ-ACK of at most 2 bits.  Refused: a description on a PDU without codeword (G^CSI-1 itself depends on whether part 2 is
+ * present there, which the reference does not handle either), and what NRPHY_PUSCH_CSI2_MAX_SIZES bounds. */
+#define NRPHY_PUSCH_CSI2_MAX_ENTRIES 2u     /* uci_part2_size_description::max_nof_entries */
+#define NRPHY_PUSCH_CSI2_MAX_PARAMETERS 2u  /* ::max_nof_parameters */
+#define NRPHY_PUSCH_CSI2_MAX_ENTRY_BITS 4u  /* ::max_nof_entry_bits: the widths of an entry's parameters sum to at most this */
+#define NRPHY_PUSCH_CSI2_MAX_SIZES 16u      /* distinct non-zero sizes of one PDU (two full entries could give up to 256 sums: refused) */
+#define NRPHY_PUSCH_CSI2_MAX_VARIANTS 17u   /* "no part 2" and the sizes */
+typedef struct nrphy_pusch_csi2_entry {     /* uci_part2_size_description::entry */
+  uint32_t nof_parameters;                  /* 0..2; the index is the concatenation of the parameters, the first one highest */
+  uint32_t offset[NRPHY_PUSCH_CSI2_MAX_PARAMETERS]; /* of the parameter in the CSI part 1 payload: that bit is its most significant */
+  uint32_t width[NRPHY_PUSCH_CSI2_MAX_PARAMETERS];  /* bits; offset + width <= nof_csi_part1 */
+  uint32_t map_size;                        /* 1 << sum of the widths */
+  uint32_t map[1u << NRPHY_PUSCH_CSI2_MAX_ENTRY_BITS]; /* index -> bits this entry adds to part 2 */
+} nrphy_pusch_csi2_entry_t;
+typedef struct nrphy_pusch_csi2_desc {      /* pusch_processor::pdu_t::uci.csi_part2_size */
+  uint32_t                 nof_entries;     /* 0..2; 0 = no description */
+  nrphy_pusch_csi2_entry_t entries[NRPHY_PUSCH_CSI2_MAX_ENTRIES];
+} nrphy_pusch_csi2_desc_t;
+typedef struct nrphy_pusch_csi2_result {    /* one per PDU, next to its nrphy_pusch_result_t */
+  uint32_t status;                          /* NRPHY_UCI_STATUS_*; UNKNOWN (0) where no part 2 was extracted */
+  uint32_t nof_csi_part2;                   /* payload bits, one per byte ... */
+  uint64_t csi_part2_offset;                /* ... at this byte of d_uci_bits; both 0 where no part 2 was extracted */
+  uint32_t nof_enc_bits;                    /* G^CSI-2 */
+  uint32_t nof_ul_sch_bits;                 /* G^UL-SCH the transport block was decoded with */
+  uint32_t variant;                         /* the row of nrphy_pusch_csi2_variants that was selected; 0 = no part 2 */
+  uint32_t reserved_;
+} nrphy_pusch_csi2_result_t;
+typedef struct nrphy_pusch_csi2_plan nrphy_pusch_csi2_plan_t;
+/* uci_part2_get_size: csi_part1_bits [nof_csi_part1], one bit per byte.  NRPHY_ERR_ARGUMENT for a description that
+ * nrphy_pusch_csi2_validate would refuse for its structure alone.  Host arithmetic, no device. */
+int nrphy_pusch_csi2_size(const nrphy_pusch_csi2_desc_t* desc, const uint8_t* csi_part1_bits, uint32_t nof_csi_part1, uint32_t* size);
+/* NRPHY_OK, or NRPHY_ERR_ARGUMENT for: everything nrphy_pusch_proc_validate refuses for the PDU with nof_csi_part2_entries 0;
+ * pdu->nof_csi_part2_entries != desc->nof_entries; more than 2 entries or 2 parameters; an entry's widths summing above 4;
+ * map_size != 1 << sum of the widths; offset + width > nof_csi_part1; a description with nof_csi_part1 0 or without codeword; a
+ * size above 1706; more than NRPHY_PUSCH_CSI2_MAX_SIZES distinct non-zero sizes; any size for which nrphy_ul_sch_info, the
+ * placement (no soft bit left for part 2 included), the UCI decoder or the transport-block decoder refuses the configuration.  A
+ * description with nof_entries 0 is the PDU without part 2.  No device work. */
+int nrphy_pusch_csi2_validate(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_csi2_desc_t* desc, const nrphy_pusch_proc_options_t* options,
+                              uint32_t grid_nof_ports, uint32_t grid_nof_subc);
+/* The variant table of an accepted PDU: *nof_variants rows (1..NRPHY_PUSCH_CSI2_MAX_VARIANTS), sizes[0] = 0 and infos[0] the UL-SCH
+ * information without part 2, then the distinct non-zero sizes ascending, each with its information.  sizes and infos have room for
+ * NRPHY_PUSCH_CSI2_MAX_VARIANTS rows.  With these a caller can drive the stages by hand. */
+int nrphy_pusch_csi2_variants(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_csi2_desc_t* desc, const nrphy_pusch_proc_options_t* options,
+                              uint32_t grid_nof_ports, uint32_t grid_nof_subc, uint32_t* nof_variants, uint32_t* sizes,
+                              nrphy_ulsch_info_t* infos);
+/* As nrphy_pusch_proc_harq_bytes: the sizes do not depend on the variant. */
+int nrphy_pusch_csi2_harq_bytes(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_csi2_desc_t* desc,
+                                const nrphy_pusch_proc_options_t* options, uint64_t* soft_bytes, uint64_t* state_bytes);
+/* nrphy_pusch_proc_plan_create with descs[n] (PDUs with and without description mix; pdus[i].nof_csi_part2_entries must equal
+ * descs[i].nof_entries) and csi2_offset[n]: PDU i's part 2 payload goes to byte csi2_offset[i] of d_uci_bits, as many bytes as the
+ * size that was selected, at most the largest of its sizes.  csi2_offset is not read for a PDU without description and may be NULL
+ * when no PDU has one. */
+int nrphy_pusch_csi2_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, const nrphy_pusch_csi2_desc_t* descs,
+                                 const nrphy_pusch_proc_options_t* options, const uint32_t* grid_index, uint32_t nof_grids,
+                                 uint32_t grid_nof_ports, uint32_t grid_nof_subc, const uint64_t* harq_soft_offset,
+                                 const uint64_t* harq_state_offset, const uint64_t* tb_offset, const uint64_t* uci_offset,
+                                 const uint64_t* csi2_offset, nrphy_pusch_csi2_plan_t** plan);
+int nrphy_pusch_csi2_plan_destroy(nrphy_pusch_csi2_plan_t* plan);
+/* The arguments of nrphy_pusch_proc_run and d_csi2_result: [n], 8-byte aligned.  For a PDU without description the
+ * nrphy_pusch_result_t and every output byte are those of nrphy_pusch_proc_run.  The variants that are not selected write nothing:
+ * not the soft buffers, not d_uci_bits, no status.  Asynchronous on `stream`; allocates nothing and touches no host memory.
+ * Runs of one plan must be ordered. */
+int nrphy_pusch_csi2_run(nrphy_pusch_csi2_plan_t* plan, const void* d_grid, void* d_harq, uint8_t* d_tb, uint8_t* d_uci_bits,
+                         nrphy_pusch_result_t* d_result, nrphy_pusch_csi2_result_t* d_csi2_result, void* stream);
+/* One PDU from and to host memory (blocking, on the GPU), as nrphy_pusch_proc_host.  csi2_bits: room for the largest size of the
+ * description (NULL without one); the bytes behind the selected size keep the caller's.  csi2_result->csi_part2_offset is 0. */
+int nrphy_pusch_csi2_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_csi2_desc_t* desc,
+                          const nrphy_pusch_proc_options_t* options, const void* grid, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
+                          int8_t* harq_soft, uint8_t* harq_state, uint8_t* tb, uint8_t* uci_bits, uint8_t* csi2_bits,
+                          nrphy_pusch_result_t* result, nrphy_pusch_csi2_result_t* csi2_result);
 
 
 /* ---- receive side: OFDM demodulation of a run of symbols, from float or int16 samples --------------------------------------------

@@ -474,6 +474,44 @@ def make_pusch_proc_options(dec_nof_iterations=10, dec_enable_early_stop=1, csi_
     return PuschProcOptions(dec_nof_iterations, dec_enable_early_stop, csi_sinr_calc_method, equalizer)
 
 
+PUSCH_CSI2_MAX_ENTRIES, PUSCH_CSI2_MAX_PARAMETERS, PUSCH_CSI2_MAX_ENTRY_BITS = 2, 2, 4  # NRPHY_PUSCH_CSI2_*
+PUSCH_CSI2_MAX_SIZES, PUSCH_CSI2_MAX_VARIANTS = 16, 17
+
+
+class PuschCsi2Entry(C.Structure):
+    """nrphy_pusch_csi2_entry_t (uci_part2_size_description::entry)."""
+    _fields_ = [("nof_parameters", C.c_uint32), ("offset", C.c_uint32 * PUSCH_CSI2_MAX_PARAMETERS),
+                ("width", C.c_uint32 * PUSCH_CSI2_MAX_PARAMETERS), ("map_size", C.c_uint32),
+                ("map", C.c_uint32 * (1 << PUSCH_CSI2_MAX_ENTRY_BITS))]
+
+
+class PuschCsi2Desc(C.Structure):
+    """nrphy_pusch_csi2_desc_t (pusch_processor::pdu_t::uci.csi_part2_size)."""
+    _fields_ = [("nof_entries", C.c_uint32), ("entries", PuschCsi2Entry * PUSCH_CSI2_MAX_ENTRIES)]
+
+
+class PuschCsi2Result(C.Structure):
+    """nrphy_pusch_csi2_result_t: one per PDU, next to its PuschResult."""
+    _fields_ = [("status", C.c_uint32), ("nof_csi_part2", C.c_uint32), ("csi_part2_offset", C.c_uint64), ("nof_enc_bits", C.c_uint32),
+                ("nof_ul_sch_bits", C.c_uint32), ("variant", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
+def make_pusch_csi2_desc(entries=()):
+    """A PuschCsi2Desc from entries (parameters, map): parameters a sequence of (offset, width), map the sizes by index.  Nothing
+    is checked here -- nof_entries and nof_parameters are the lengths given, what the arrays cannot hold is left out -- so that
+    the validator can be shown what it refuses."""
+    d = PuschCsi2Desc()
+    d.nof_entries = len(entries)
+    for e, (parameters, sizes) in zip(d.entries, entries):
+        e.nof_parameters = len(parameters)
+        for k, (offset, width) in enumerate(list(parameters)[:PUSCH_CSI2_MAX_PARAMETERS]):
+            e.offset[k], e.width[k] = offset, width
+        e.map_size = len(sizes)
+        for k, v in enumerate(list(sizes)[:1 << PUSCH_CSI2_MAX_ENTRY_BITS]):
+            e.map[k] = v
+    return d
+
+
 class GridRe(C.Structure):
     """nrphy_grid_re_t: one resource element written from the host into a device grid."""
     _fields_ = [("port", C.c_uint16), ("symbol", C.c_uint16), ("subc", C.c_uint32), ("value", C.c_uint32)]
@@ -1012,6 +1050,16 @@ def declare(lib, prefix="nrphy_"):
     sig("pusch_proc_plan_harq_bytes", i32, vp, u32, P(u64), P(u64))
     sig("pusch_proc_run", i32, vp, vp, vp, vp, vp, vp, vp)
     sig("pusch_proc_host", i32, vp, P(PuschPdu), P(PuschProcOptions), vp, u32, u32, vp, vp, vp, vp, P(PuschResult))
+    sig("pusch_csi2_size", i32, P(PuschCsi2Desc), vp, u32, P(u32))
+    sig("pusch_csi2_validate", i32, P(PuschPdu), P(PuschCsi2Desc), P(PuschProcOptions), u32, u32)
+    sig("pusch_csi2_variants", i32, P(PuschPdu), P(PuschCsi2Desc), P(PuschProcOptions), u32, u32, P(u32), P(u32), P(UlschInfo))
+    sig("pusch_csi2_harq_bytes", i32, P(PuschPdu), P(PuschCsi2Desc), P(PuschProcOptions), P(u64), P(u64))
+    sig("pusch_csi2_plan_create", i32, vp, u32, P(PuschPdu), P(PuschCsi2Desc), P(PuschProcOptions), P(u32), u32, u32, u32, P(u64),
+        P(u64), P(u64), P(u64), P(u64), P(vp))
+    sig("pusch_csi2_plan_destroy", i32, vp)
+    sig("pusch_csi2_run", i32, vp, vp, vp, vp, vp, vp, vp, vp)
+    sig("pusch_csi2_host", i32, vp, P(PuschPdu), P(PuschCsi2Desc), P(PuschProcOptions), vp, u32, u32, vp, vp, vp, vp, vp,
+        P(PuschResult), P(PuschCsi2Result))
     sig("ofdm_demod_symbols", i32, vp, u32, vp, u32, C.c_float, vp, u32, u32, u32, vp, vp)
     sig("ul_slots_create", i32, vp, P(UlSlotsCfg), vp, P(vp))
     sig("ul_slots_destroy", i32, vp)
@@ -1110,6 +1158,8 @@ ABI_SYMBOLS = [
     "nrphy_ul_sch_info", "nrphy_pusch_proc_validate", "nrphy_pusch_proc_derive", "nrphy_pusch_proc_harq_bytes",
     "nrphy_pusch_proc_plan_create", "nrphy_pusch_proc_plan_destroy", "nrphy_pusch_proc_plan_harq_bytes", "nrphy_pusch_proc_run",
     "nrphy_pusch_proc_host",
+    "nrphy_pusch_csi2_size", "nrphy_pusch_csi2_validate", "nrphy_pusch_csi2_variants", "nrphy_pusch_csi2_harq_bytes",
+    "nrphy_pusch_csi2_plan_create", "nrphy_pusch_csi2_plan_destroy", "nrphy_pusch_csi2_run", "nrphy_pusch_csi2_host",
     "nrphy_ofdm_demod_symbols",
     "nrphy_ul_slots_create", "nrphy_ul_slots_destroy", "nrphy_ul_slots_wait_free", "nrphy_ul_slot_open", "nrphy_ul_slot_close",
     "nrphy_ul_slot_samples", "nrphy_ul_slot_load_grid", "nrphy_ul_slot_device_grid", "nrphy_ul_slot_stream",

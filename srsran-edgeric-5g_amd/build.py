@@ -21,8 +21,9 @@ SOURCES = ["nrphy_host.cpp", "pdsch_plan_build.cpp", "pdsch_host.cpp", "dl_contr
            "pucch2_host.cpp", "pucch2_kernels.hip", "srs_host.cpp", "srs_kernels.hip",
            "uci_host.cpp", "uci_kernels.hip", "ulsch_host.cpp", "ulsch_kernels.hip", "ofh_ul_host.cpp", "ofh_ul_kernels.hip",
            "ofh_dl_host.cpp", "ofh_dl_kernels.hip", "ofh_rx_host.cpp", "ofh_rx_kernels.hip",
-           "transform_precoder_host.cpp", "transform_precoder_kernels.hip", "pusch_proc_host.cpp", "pusch_proc_kernels.hip"]
-HEADERS = ["nrphy_internal.h", "nrphy_host_internal.h", "pdsch_plan.h", "pdsch_staging_host.h", "slot_pool_host.h", "ul_slot_state_host.h", "prach_window_state_host.h", "ldpc_receive_host.h", "ldpc_base_graph_host.h", "pusch_alloc_host.h", "ulsch_placement_host.h", "ulsch_info_host.h", "nrphy_trace.h", "bits_device.h", "crc24b_fold.h", "ofh_compress_device.h", "ofh_ul_chunk_device.h", "chest_device.h", "chest_host.h", "demod_device.h", "equalize_device.h", "exact_device.h", "ldpc_device.h", "codeblock_build_device.h", "rate_match_device.h", "re_map_device.h", "pdsch_dmrs_device.h", "fft_device.h", "dft_mixed_device.h","nr_ldpc_bg.inc", "nr_polar_tables.inc", "prach_tables.inc", "prach_demod_tables.inc", "pucch_tables.inc", "srs_tables.inc", "uci_tables.inc",
+           "transform_precoder_host.cpp", "transform_precoder_kernels.hip", "pusch_proc_host.cpp", "pusch_proc_kernels.hip",
+           "pusch_csi2_host.cpp", "pusch_csi2_kernels.hip"]
+HEADERS = ["nrphy_internal.h", "nrphy_host_internal.h", "pdsch_plan.h", "pdsch_staging_host.h", "slot_pool_host.h", "ul_slot_state_host.h", "prach_window_state_host.h", "ldpc_receive_host.h", "ldpc_base_graph_host.h", "pusch_alloc_host.h", "ulsch_placement_host.h", "ulsch_info_host.h", "pusch_csi2_host.h", "pusch_proc_plan_host.h", "pusch_select_host.h", "nrphy_trace.h", "bits_device.h", "crc24b_fold.h", "ofh_compress_device.h", "ofh_ul_chunk_device.h", "chest_device.h", "chest_host.h", "demod_device.h", "equalize_device.h", "exact_device.h", "ldpc_device.h", "codeblock_build_device.h", "rate_match_device.h", "re_map_device.h", "pdsch_dmrs_device.h", "fft_device.h", "dft_mixed_device.h","nr_ldpc_bg.inc", "nr_polar_tables.inc", "prach_tables.inc", "prach_demod_tables.inc", "pucch_tables.inc", "srs_tables.inc", "uci_tables.inc",
            os.path.join(ROOT, "include", "mi355_nrphy.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 MAX_COMPILERS = 16  # in flight at once

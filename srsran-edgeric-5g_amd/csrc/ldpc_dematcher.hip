@@ -104,6 +104,9 @@ __device__ __forceinline__ void dematch_positions(const DematchLaunch& p, const 
 template <uint32_t VEC, bool EXT>
 __global__ __launch_bounds__(256) void ldpc_dematch_kernel(DematchLaunch p)
 {
+  if (p.select != nullptr && *p.select != p.select_value) { // workgroup-uniform: not the launch the select word picks
+    return;
+  }
   const uint32_t first = (blockIdx.x * blockDim.x + threadIdx.x) * VEC;
   if (first >= p.block_length) {
     return;
@@ -125,6 +128,9 @@ constexpr uint32_t DEMATCH_LDS_THREADS = 1024; // 512: the same; 256: 7 % slower
 template <bool EXT>
 __global__ __launch_bounds__(DEMATCH_LDS_THREADS) void ldpc_dematch_lds_kernel(DematchLaunch p)
 {
+  if (p.select != nullptr && *p.select != p.select_value) { // workgroup-uniform: not the launch the select word picks
+    return;
+  }
   extern __shared__ __attribute__((aligned(16))) int8_t dematch_lds[];
   const uint32_t e      = p.cols * p.qm;
   int8_t*        staged = dematch_lds;                       // [e]
@@ -231,6 +237,9 @@ __device__ __forceinline__ void dematch_rows(const uint32_t (&dw)[8], uint32_t (
 template <bool EXT>
 __global__ __launch_bounds__(256) void ldpc_dematch_scatter_kernel(DematchLaunch p)
 {
+  if (p.select != nullptr && *p.select != p.select_value) { // workgroup-uniform: not the launch the select word picks
+    return;
+  }
   const int8_t*  in      = p.in + (size_t)blockIdx.z * p.in_stride_outer + (size_t)blockIdx.y * p.in_stride;
   int8_t*        out_row = p.out + (size_t)blockIdx.z * p.out_stride_outer + (size_t)blockIdx.y * p.out_stride;
   const uint32_t gtid = blockIdx.x * blockDim.x + threadIdx.x, gsize = gridDim.x * blockDim.x;

@@ -49,7 +49,8 @@ void build_dematch_ops(std::vector<DematchOp>& ops, unsigned block_length, unsig
 
 int rate_dematch_batch(nrphy_ctx_t* ctx, const nrphy_ldpc_rate_dematcher_cfg_t* cfg, uint32_t n_cb, uint32_t n_outer,
                        const int8_t* d_in, uint32_t in_stride_bytes, size_t in_outer, int8_t* d_soft,
-                       uint32_t soft_stride_bytes, size_t soft_outer, int new_data, void* stream)
+                       uint32_t soft_stride_bytes, size_t soft_outer, int new_data, void* stream, const uint32_t* d_select,
+                       uint32_t select_value)
 {
   if (ctx == nullptr || cfg == nullptr || d_in == nullptr || d_soft == nullptr ||
       (cfg->base_graph != 1 && cfg->base_graph != 2) || cfg->rv > 3 || lifting_position(cfg->lifting_size) < 0 ||
@@ -116,6 +117,8 @@ int rate_dematch_batch(nrphy_ctx_t* ctx, const nrphy_ldpc_rate_dematcher_cfg_t* 
       }
     }
   }
+  p.select       = d_select;
+  p.select_value = select_value;
   p.in           = d_in;
   p.out          = d_soft;
   p.in_stride    = in_stride_bytes;

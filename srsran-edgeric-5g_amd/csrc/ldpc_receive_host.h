@@ -14,10 +14,12 @@ void build_dematch_ops(std::vector<DematchOp>& ops, unsigned block_length, unsig
                        unsigned nof_systematic, unsigned nof_filler, unsigned e, bool new_data);
 
 // n_outer groups (transport blocks) of n_cb codeblocks: codeblock (g, i) reads d_in + g * in_outer + i * in_stride and
-// owns the soft buffer d_soft + g * soft_outer + i * soft_stride.
+// owns the soft buffer d_soft + g * soft_outer + i * soft_stride.  d_select (may be null: unconditional): the launch acts only
+// when the word it points to holds select_value at the time the kernel runs.
 int rate_dematch_batch(nrphy_ctx_t* ctx, const nrphy_ldpc_rate_dematcher_cfg_t* cfg, uint32_t n_cb, uint32_t n_outer,
                        const int8_t* d_in, uint32_t in_stride_bytes, size_t in_outer, int8_t* d_soft,
-                       uint32_t soft_stride_bytes, size_t soft_outer, int new_data, void* stream);
+                       uint32_t soft_stride_bytes, size_t soft_outer, int new_data, void* stream,
+                       const uint32_t* d_select = nullptr, uint32_t select_value = 0);
 
 // skip / ok_flags: per-codeblock HARQ state of a transport-block decoder; crc_at_end: no early stop.
 // expected_extent: how many of the nof_llr soft bits the caller expects to be in use (the rest zero), 0 = all of them; it
@@ -31,5 +33,18 @@ int ldpc_decode_batch(nrphy_ctx_t* ctx, const nrphy_ldpc_decoder_cfg_t* cfg, uin
 // false for a configuration the decoder refuses.  No device work.
 bool pusch_decoder_harq_sizes(const nrphy_pusch_decoder_cfg_t& cfg, uint32_t n_tb, uint64_t* soft_bytes_per_tb, uint64_t* state_bytes,
                               uint32_t* nof_codeblocks);
+
+// nrphy_pusch_decode_batch for one transport block whose rate-matched length is one of nof_variants candidates, chosen on the
+// device: variant v is the configuration cfgs[v] (all equal but for nof_ch_symbols) reading its soft bits at d_llr[v], and its
+// rate-dematcher launches act only when *d_select == select_values[v]; the LDPC decode and the assembly, which do not depend on
+// the rate-matched length, are launched once.  d_select null with one variant: nrphy_pusch_decode_batch itself.
+struct PuschDecodeVariant {
+  const nrphy_pusch_decoder_cfg_t* cfg;
+  const int8_t*                    d_llr;
+  uint32_t                         select_value;
+};
+int pusch_decode_variants(nrphy_ctx_t* ctx, const PuschDecodeVariant* variants, uint32_t nof_variants, const uint32_t* d_select,
+                          uint32_t n_tb, uint64_t llr_stride_bytes, int8_t* d_soft, uint8_t* d_state, void* d_scratch, uint8_t* d_tb,
+                          uint32_t tb_stride_bytes, uint32_t* d_result, void* stream);
 
 #pragma GCC visibility pop

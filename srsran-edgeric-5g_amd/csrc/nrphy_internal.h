@@ -325,6 +325,10 @@ struct DematchLaunch {
   uint32_t      skip_load; // the operations write every soft bit of the block: the old contents need not be read
   uint32_t      disjoint;  // no two operations touch the same soft bit: they can run in any order, element by element
   const DematchOp* ops_ext; // the list in device memory when it has more than MAX_DEMATCH_OPS entries, else null
+  // Null: unconditional.  Else the launch acts only when *select == select_value (every workgroup tests it and the others return
+  // at once): one of several launches of which a word written earlier on the stream picks one.
+  const uint32_t*  select       = nullptr;
+  uint32_t         select_value = 0;
   DematchOp        ops[MAX_DEMATCH_OPS];
 };
 hipError_t launch_ldpc_dematch(const DematchLaunch& p, uint32_t n_cb, hipStream_t stream, uint32_t n_outer = 1);
@@ -647,6 +651,10 @@ hipError_t launch_srs(const SrsLaunch& p, hipStream_t stream);
 hipError_t launch_srs_sequence(const SrsDesc* desc, const float2* cs_table, uint32_t port, uint32_t M, float2* out, hipStream_t stream);
 hipError_t launch_grid_put(const uint32_t* d_index, const uint32_t* d_value, uint32_t n, uint32_t* d_grid, hipStream_t stream);
 
+// A codeword of the UL-SCH demultiplexer and a message of the UCI decoder may name a select word and a value (UlschCwDesc,
+// UciMsgDesc): its workgroups act only when the word holds the value.  This is the word of those that name none.
+constexpr uint32_t NO_SELECT_WORD = 0xFFFFFFFFu;
+
 // ---- UCI decoder (receive side: short blocks and polar) -------------------------------------------------------------------
 // One wavefront per message.  A polar code (K, E) is built once per plan: its offsets index the plan's tab16 and ops tables.
 constexpr uint32_t UCI_NO_CODE = 0xFFFFFFFFu;
@@ -667,6 +675,7 @@ struct UciMsgDesc {
   uint32_t nof_blocks;
   uint32_t pad_;
   uint64_t llr_offset, message_offset;
+  uint32_t select_word, select_value;          // NO_SELECT_WORD: unconditional, else the message runs only when select[select_word] == select_value
 };
 struct UciLaunch {
   const UciMsgDesc*  msg;
@@ -677,6 +686,7 @@ struct UciLaunch {
   uint8_t*           message;
   uint32_t*          status;
   uint32_t           n;
+  const uint32_t*    select = nullptr;         // the words UciMsgDesc::select_word indexes; null when no message names one
 };
 hipError_t launch_uci_decoder(const UciLaunch& p, hipStream_t stream);
 
@@ -694,6 +704,7 @@ struct UlschCwDesc {
   uint32_t nof_re, bits_per_re, qm, unit;
   uint32_t map_offset, special_offset, nof_special, c_init;
   uint32_t first_block, nof_copy_blocks; // the codeword's blocks: copy blocks first, then the special ones
+  uint32_t select_word, select_value;    // NO_SELECT_WORD: unconditional, else the codeword's blocks act only when select[select_word] == select_value
 };
 struct UlschSpecialDev {
   uint32_t src, dst, stream, fix;
@@ -709,6 +720,7 @@ struct UlschLaunch {
   int8_t*                out[4];
   uint32_t               nof_blocks;
   uint32_t               ptr_unit; // 16, 4 or 1: what the alignment of the five pointers allows
+  const uint32_t*        select = nullptr; // the words UlschCwDesc::select_word indexes; null when no codeword names one
 };
 hipError_t launch_ulsch_demux(const UlschLaunch& p, hipStream_t stream);
 
@@ -733,6 +745,33 @@ struct PuschProcLaunch {
   uint32_t                        n;
 };
 hipError_t launch_pusch_proc_result(const PuschProcLaunch& p, hipStream_t stream);
+
+// ---- PUSCH processor with CSI part 2: the select and result kernels (pusch_csi2_kernels.hip) -----------------------------------
+// One descriptor per PDU of a plan, also for those without description (nof_entries 0, one variant).  Variant v > 0 of a PDU is
+// part 2 of size[v] bits; its UCI decoder status is variant_status[status_base + v - 1].
+struct PuschCsi2Desc {
+  uint32_t nof_entries, nof_variants;
+  uint32_t csi1_status;                  // index into the processor's UCI statuses; PUSCH_PROC_NO_STATUS without description
+  uint32_t status_base;
+  uint64_t csi1_offset, csi2_offset;     // bytes of d_uci_bits: the decoded CSI part 1 payload, the place of part 2
+  uint32_t nof_parameters[NRPHY_PUSCH_CSI2_MAX_ENTRIES];
+  uint32_t offset[NRPHY_PUSCH_CSI2_MAX_ENTRIES][NRPHY_PUSCH_CSI2_MAX_PARAMETERS];
+  uint32_t width[NRPHY_PUSCH_CSI2_MAX_ENTRIES][NRPHY_PUSCH_CSI2_MAX_PARAMETERS];
+  uint32_t map[NRPHY_PUSCH_CSI2_MAX_ENTRIES][1u << NRPHY_PUSCH_CSI2_MAX_ENTRY_BITS];
+  uint32_t size[NRPHY_PUSCH_CSI2_MAX_VARIANTS], nof_enc[NRPHY_PUSCH_CSI2_MAX_VARIANTS], nof_ul_sch[NRPHY_PUSCH_CSI2_MAX_VARIANTS];
+  uint32_t pad_;
+};
+struct PuschCsi2Launch {
+  const PuschCsi2Desc*       desc;
+  const uint32_t*            status;         // the processor's UCI statuses (HARQ-ACK, CSI part 1)
+  uint32_t*                  variant_status; // the statuses of the part 2 messages, one per (PDU, variant > 0)
+  const uint8_t*             uci_bits;
+  uint32_t*                  select;         // [n] the variant of every PDU
+  nrphy_pusch_csi2_result_t* result;         // [n] (the result kernel)
+  uint32_t                   n;
+};
+hipError_t launch_pusch_csi2_select(const PuschCsi2Launch& p, hipStream_t stream);
+hipError_t launch_pusch_csi2_result(const PuschCsi2Launch& p, hipStream_t stream);
 
 // ---- PDCCH and SS/PBCH block ("next" row: other downlink grid writers) --------------------------------------------------
 // One wavefront per DCI.  Offsets index the launch's shared tables: tab16 (gather table of the polar input, PRB list),

@@ -138,17 +138,30 @@ extern "C" int nrphy_pusch_decoder_sizes(nrphy_ctx_t* ctx, const nrphy_pusch_dec
   return NRPHY_OK;
 }
 
-extern "C" int nrphy_pusch_decode_batch(nrphy_ctx_t* ctx, const nrphy_pusch_decoder_cfg_t* cfg, uint32_t n_tb,
-                                        const int8_t* d_llr, uint64_t llr_stride_bytes, int8_t* d_soft, uint8_t* d_state,
-                                        void* d_scratch, uint8_t* d_tb, uint32_t tb_stride_bytes, uint32_t* d_result, void* stream)
+int pusch_decode_variants(nrphy_ctx_t* ctx, const PuschDecodeVariant* variants, uint32_t nof_variants, const uint32_t* d_select,
+                          uint32_t n_tb, uint64_t llr_stride_bytes, int8_t* d_soft, uint8_t* d_state, void* d_scratch, uint8_t* d_tb,
+                          uint32_t tb_stride_bytes, uint32_t* d_result, void* stream)
 {
   const TraceRange trace("process_pusch");
   PuschLayout l;
-  if (ctx == nullptr || cfg == nullptr || d_llr == nullptr || d_soft == nullptr || d_state == nullptr || d_tb == nullptr ||
-      d_scratch == nullptr ||
-      d_result == nullptr || !pusch_layout(*cfg, n_tb, l) || tb_stride_bytes < cfg->tb_size_bytes ||
-      llr_stride_bytes < (uint64_t)cfg->nof_ch_symbols * cfg->qm) {
+  if (ctx == nullptr || variants == nullptr || nof_variants == 0 || (d_select == nullptr && nof_variants != 1) ||
+      variants[0].cfg == nullptr || d_soft == nullptr || d_state == nullptr || d_tb == nullptr || d_scratch == nullptr ||
+      d_result == nullptr || !pusch_layout(*variants[0].cfg, n_tb, l) || tb_stride_bytes < variants[0].cfg->tb_size_bytes) {
     return NRPHY_ERR_ARGUMENT;
+  }
+  const nrphy_pusch_decoder_cfg_t* cfg = variants[0].cfg;
+  // Every variant is the same transport block in the same soft buffers: only the rate-matched lengths may differ.
+  std::vector<PuschLayout> layouts(nof_variants, l);
+  for (uint32_t v = 0; v != nof_variants; ++v) {
+    const nrphy_pusch_decoder_cfg_t* c = variants[v].cfg;
+    if (c == nullptr || variants[v].d_llr == nullptr || !pusch_layout(*c, n_tb, layouts[v]) ||
+        llr_stride_bytes < (uint64_t)c->nof_ch_symbols * c->qm || c->base_graph != cfg->base_graph || c->qm != cfg->qm ||
+        c->rv != cfg->rv || c->nof_layers != cfg->nof_layers || c->nref != cfg->nref || c->tb_size_bytes != cfg->tb_size_bytes ||
+        c->max_iterations != cfg->max_iterations || c->use_early_stop != cfg->use_early_stop || c->new_data != cfg->new_data ||
+        layouts[v].state_bytes != l.state_bytes || layouts[v].d.full_length != l.d.full_length ||
+        layouts[v].d.nof_codeblocks != l.d.nof_codeblocks || layouts[v].d.nof_filler_bits != l.d.nof_filler_bits) {
+      return NRPHY_ERR_ARGUMENT;
+    }
   }
   if (n_tb == 0) {
     return NRPHY_OK;
@@ -165,7 +178,7 @@ extern "C" int nrphy_pusch_decode_batch(nrphy_ctx_t* ctx, const nrphy_pusch_deco
   }
   HIP_TRY(hipMemcpyAsync(skip, ok, n_cb, hipMemcpyDeviceToDevice, s));
   // Rate dematching of every codeblock, also of those decoded earlier (pusch_decoder_impl.cpp:340-350): the short
-  // segments, then the long ones.
+  // segments, then the long ones.  With variants, the launches of each; the soft buffers see those of the selected one only.
   nrphy_ldpc_rate_dematcher_cfg_t dm;
   dm.base_graph      = cfg->base_graph;
   dm.lifting_size    = d.lifting_size;
@@ -173,17 +186,22 @@ extern "C" int nrphy_pusch_decode_batch(nrphy_ctx_t* ctx, const nrphy_pusch_deco
   dm.qm              = cfg->qm;
   dm.nref            = d.n_ref;
   dm.nof_filler_bits = d.nof_filler_bits;
-  const uint32_t n_short = d.nof_short_segments;
-  int            rc      = NRPHY_OK;
-  if (n_short != 0) {
-    dm.rm_length = d.rm_length_short;
-    rc = rate_dematch_batch(ctx, &dm, n_short, n_tb, d_llr, d.rm_length_short, llr_stride_bytes, d_soft, N, (size_t)C * N,
-                            cfg->new_data, s);
-  }
-  if (rc == NRPHY_OK && n_short != C) {
-    dm.rm_length = d.rm_length_long;
-    rc = rate_dematch_batch(ctx, &dm, C - n_short, n_tb, d_llr + (size_t)n_short * d.rm_length_short, d.rm_length_long,
-                            llr_stride_bytes, d_soft + (size_t)n_short * N, N, (size_t)C * N, cfg->new_data, s);
+  int rc = NRPHY_OK;
+  for (uint32_t v = 0; v != nof_variants && rc == NRPHY_OK; ++v) {
+    const nrphy_pdsch_derived_t& dv      = layouts[v].d;
+    const int8_t*                d_llr   = variants[v].d_llr;
+    const uint32_t               n_short = dv.nof_short_segments;
+    if (n_short != 0) {
+      dm.rm_length = dv.rm_length_short;
+      rc = rate_dematch_batch(ctx, &dm, n_short, n_tb, d_llr, dv.rm_length_short, llr_stride_bytes, d_soft, N, (size_t)C * N,
+                              cfg->new_data, s, d_select, variants[v].select_value);
+    }
+    if (rc == NRPHY_OK && n_short != C) {
+      dm.rm_length = dv.rm_length_long;
+      rc = rate_dematch_batch(ctx, &dm, C - n_short, n_tb, d_llr + (size_t)n_short * dv.rm_length_short, dv.rm_length_long,
+                              llr_stride_bytes, d_soft + (size_t)n_short * N, N, (size_t)C * N, cfg->new_data, s, d_select,
+                              variants[v].select_value);
+    }
   }
   if (rc != NRPHY_OK) {
     return rc;
@@ -199,7 +217,12 @@ extern "C" int nrphy_pusch_decode_batch(nrphy_ctx_t* ctx, const nrphy_pusch_deco
     const double   frac = (((cfg->base_graph == 1) ? shift_bg1 : shift_bg2)[cfg->rv] * buffer_length) / N;
     const unsigned k0   = (unsigned)((uint16_t)std::floor(frac)) * zc;
     std::vector<DematchOp> ops;
-    for (uint32_t e : {d.rm_length_short, d.rm_length_long}) {
+    std::vector<uint32_t> lengths; // of every variant: the hint takes the largest extent
+    for (const PuschLayout& lv : layouts) {
+      lengths.push_back(lv.d.rm_length_short);
+      lengths.push_back(lv.d.rm_length_long);
+    }
+    for (uint32_t e : lengths) {
       if (e == 0) {
         continue;
       }
@@ -244,4 +267,13 @@ extern "C" int nrphy_pusch_decode_batch(nrphy_ctx_t* ctx, const nrphy_pusch_deco
                                         (int64_t)divide_ceil(cfg->tb_size_bytes, TB_CRC_REGION_BYTES) * TB_CRC_REGION_BYTES));
   HIP_TRY(launch_pusch_assemble(a, n_tb, s));
   return NRPHY_OK;
+}
+
+extern "C" int nrphy_pusch_decode_batch(nrphy_ctx_t* ctx, const nrphy_pusch_decoder_cfg_t* cfg, uint32_t n_tb,
+                                        const int8_t* d_llr, uint64_t llr_stride_bytes, int8_t* d_soft, uint8_t* d_state,
+                                        void* d_scratch, uint8_t* d_tb, uint32_t tb_stride_bytes, uint32_t* d_result, void* stream)
+{
+  const PuschDecodeVariant one = {cfg, d_llr, 0};
+  return pusch_decode_variants(ctx, &one, 1, nullptr, n_tb, llr_stride_bytes, d_soft, d_state, d_scratch, d_tb, tb_stride_bytes,
+                               d_result, stream);
 }

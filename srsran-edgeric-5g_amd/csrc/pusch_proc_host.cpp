@@ -5,6 +5,7 @@
 // stages themselves are the library's: this file launches nothing but the result kernel.
 #include "ldpc_receive_host.h"
 #include "pusch_alloc_host.h"
+#include "pusch_proc_plan_host.h"
 #include "ulsch_info_host.h"
 
 #include <cmath>
@@ -82,26 +83,7 @@ int derive(const nrphy_pusch_pdu_t* p, const nrphy_pusch_proc_options_t* o, uint
 
   // get_ulsch_information as if there were no CSI part 2 (pusch_processor_impl.cpp:138-164).
   const uint32_t nof_rb = nof_prb(pusch_allocation(ce));
-  nrphy_ulsch_info_cfg_t ic;
-  std::memset(&ic, 0, sizeof(ic));
-  ic.tbs_bits                    = 8 * p->tb_size_bytes;
-  ic.modulation                  = p->modulation;
-  ic.target_code_rate            = p->target_code_rate;
-  ic.nof_harq_ack_bits           = p->nof_harq_ack;
-  ic.nof_csi_part1_bits          = p->nof_csi_part1;
-  ic.nof_csi_part2_bits          = 0;
-  ic.alpha_scaling               = p->alpha_scaling;
-  ic.beta_offset_harq_ack        = p->beta_offset_harq_ack;
-  ic.beta_offset_csi_part1       = p->beta_offset_csi_part1;
-  ic.beta_offset_csi_part2       = p->beta_offset_csi_part2;
-  ic.nof_rb                      = nof_rb;
-  ic.start_symbol_index          = p->start_symbol_index;
-  ic.nof_symbols                 = p->nof_symbols;
-  ic.dmrs_type                   = p->dmrs_type;
-  ic.dmrs_symbol_mask            = p->dmrs_symbol_mask;
-  ic.nof_cdm_groups_without_data = p->nof_cdm_groups_without_data;
-  ic.nof_layers                  = p->nof_tx_layers;
-  ic.contains_dc = (p->dc_position != NRPHY_PUSCH_CHEST_NO_DC && mask_test(p->prb_mask, p->dc_position / NRPHY_NRE)) ? 1 : 0;
+  const nrphy_ulsch_info_cfg_t ic = pusch_proc_info_cfg(*p, nof_rb, 0);
   if (p->tb_size_bytes > NRPHY_MAX_TB_BYTES || ulsch_info(ic, d.info) != NRPHY_OK) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -172,40 +154,7 @@ int derive(const nrphy_pusch_pdu_t* p, const nrphy_pusch_proc_options_t* o, uint
   return NRPHY_OK;
 }
 
-struct ProcDecoder {
-  nrphy_pusch_decoder_cfg_t cfg;
-  uint32_t                  pdu;
-  uint64_t                  llr_offset; // into the UL-SCH stream buffer (with UCI) or the codeword buffer (without)
-  bool                      from_sch;
-  uint64_t                  soft_offset, state_offset, tb_offset;
-};
-
 } // namespace
-
-struct nrphy_pusch_proc_plan {
-  nrphy_ctx*                ctx = nullptr;
-  uint32_t                  n   = 0;
-  nrphy_pusch_chest_plan_t* chest = nullptr;
-  nrphy_pusch_demod_plan_t* demod = nullptr;
-  nrphy_ulsch_demux_plan_t* demux = nullptr;
-  nrphy_uci_decoder_plan_t* uci   = nullptr;
-  std::vector<ProcDecoder>  decoders;
-  std::vector<uint64_t>     soft_bytes, state_bytes; // per PDU
-  uint64_t                  llr_stride = 0;
-  void*                     d_arena = nullptr;
-  PuschProcDesc*            d_desc  = nullptr;
-  // the workspace, pieces of the arena
-  uint32_t*                 d_ce      = nullptr;
-  float*                    d_nv      = nullptr;
-  nrphy_pusch_chest_meas_t* d_meas    = nullptr;
-  float*                    d_sinr    = nullptr;
-  int8_t*                   d_llr     = nullptr;
-  int8_t*                   d_sch     = nullptr;
-  int8_t*                   d_uci_llr = nullptr;
-  uint32_t*                 d_dec     = nullptr;
-  uint32_t*                 d_status  = nullptr;
-  uint8_t*                  d_scratch = nullptr;
-};
 
 extern "C" int nrphy_ul_sch_info(const nrphy_ulsch_info_cfg_t* cfg, nrphy_ulsch_info_t* out)
 {
@@ -431,6 +380,7 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, con
   for (size_t k = 0; k != NP; ++k) {
     at[k + 1] = at[k] + align_up(std::max<uint64_t>(piece[k], 16));
   }
+  plan->desc = desc;
   DeviceArena arena;
   arena.add(&plan->d_desc, desc.data(), desc.size() * sizeof(PuschProcDesc));
   uint8_t* ws = nullptr;
@@ -465,14 +415,8 @@ extern "C" int nrphy_pusch_proc_plan_create(nrphy_ctx_t* ctx, uint32_t n, const 
                      harq_state_offset, tb_offset, uci_offset, out);
 }
 
-extern "C" int nrphy_pusch_proc_run(nrphy_pusch_proc_plan_t* plan, const void* d_grid, void* d_harq, uint8_t* d_tb, uint8_t* d_uci_bits,
-                                    nrphy_pusch_result_t* d_result, void* stream)
+int pusch_proc_run_front(nrphy_pusch_proc_plan_t* plan, const void* d_grid, uint8_t* d_uci_bits, void* stream)
 {
-  if (plan == nullptr || d_grid == nullptr || d_result == nullptr || ((uintptr_t)d_result & 7U) != 0 ||
-      (!plan->decoders.empty() && (d_harq == nullptr || d_tb == nullptr || ((uintptr_t)d_harq & 63U) != 0)) ||
-      (plan->uci != nullptr && d_uci_bits == nullptr)) {
-    return NRPHY_ERR_ARGUMENT;
-  }
   int rc = nrphy_pusch_chest_run(plan->chest, d_grid, plan->d_ce, plan->d_nv, plan->d_meas, stream);
   if (rc == NRPHY_OK) {
     rc = nrphy_pusch_demod_run(plan->demod, d_grid, plan->d_ce, plan->d_nv, plan->d_llr, plan->llr_stride, plan->d_sinr, stream);
@@ -483,16 +427,20 @@ extern "C" int nrphy_pusch_proc_run(nrphy_pusch_proc_plan_t* plan, const void* d
   if (rc == NRPHY_OK && plan->uci != nullptr) {
     rc = nrphy_uci_decoder_run(plan->uci, plan->d_uci_llr, d_uci_bits, plan->d_status, stream);
   }
-  for (size_t k = 0; k != plan->decoders.size() && rc == NRPHY_OK; ++k) {
-    const ProcDecoder& dec = plan->decoders[k];
-    rc = nrphy_pusch_decode_batch(plan->ctx, &dec.cfg, 1, (dec.from_sch ? plan->d_sch : plan->d_llr) + dec.llr_offset,
+  return rc;
+}
+
+int pusch_proc_run_decoder(nrphy_pusch_proc_plan_t* plan, size_t k, void* d_harq, uint8_t* d_tb, void* stream)
+{
+  const ProcDecoder& dec = plan->decoders[k];
+  return nrphy_pusch_decode_batch(plan->ctx, &dec.cfg, 1, (dec.from_sch ? plan->d_sch : plan->d_llr) + dec.llr_offset,
                                   (uint64_t)dec.cfg.nof_ch_symbols * dec.cfg.qm, (int8_t*)d_harq + dec.soft_offset,
                                   (uint8_t*)d_harq + dec.state_offset, plan->d_scratch, d_tb + dec.tb_offset, dec.cfg.tb_size_bytes,
                                   plan->d_dec + 4 * (size_t)dec.pdu, stream);
-  }
-  if (rc != NRPHY_OK) {
-    return rc;
-  }
+}
+
+int pusch_proc_run_result(nrphy_pusch_proc_plan_t* plan, nrphy_pusch_result_t* d_result, void* stream)
+{
   PuschProcLaunch p;
   p.desc    = plan->d_desc;
   p.meas    = plan->d_meas;
@@ -504,6 +452,27 @@ extern "C" int nrphy_pusch_proc_run(nrphy_pusch_proc_plan_t* plan, const void* d
   HIP_TRY(hipSetDevice(plan->ctx->device));
   HIP_TRY(launch_pusch_proc_result(p, stream ? (hipStream_t)stream : plan->ctx->stream));
   return NRPHY_OK;
+}
+
+bool pusch_proc_run_arguments_ok(const nrphy_pusch_proc_plan_t* plan, const void* d_grid, const void* d_harq, const uint8_t* d_tb,
+                                 const uint8_t* d_uci_bits, const nrphy_pusch_result_t* d_result)
+{
+  return !(plan == nullptr || d_grid == nullptr || d_result == nullptr || ((uintptr_t)d_result & 7U) != 0 ||
+           (!plan->decoders.empty() && (d_harq == nullptr || d_tb == nullptr || ((uintptr_t)d_harq & 63U) != 0)) ||
+           (plan->uci != nullptr && d_uci_bits == nullptr));
+}
+
+extern "C" int nrphy_pusch_proc_run(nrphy_pusch_proc_plan_t* plan, const void* d_grid, void* d_harq, uint8_t* d_tb, uint8_t* d_uci_bits,
+                                    nrphy_pusch_result_t* d_result, void* stream)
+{
+  if (!pusch_proc_run_arguments_ok(plan, d_grid, d_harq, d_tb, d_uci_bits, d_result)) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  int rc = pusch_proc_run_front(plan, d_grid, d_uci_bits, stream);
+  for (size_t k = 0; k != plan->decoders.size() && rc == NRPHY_OK; ++k) {
+    rc = pusch_proc_run_decoder(plan, k, d_harq, d_tb, stream);
+  }
+  return rc != NRPHY_OK ? rc : pusch_proc_run_result(plan, d_result, stream);
 }
 
 extern "C" int nrphy_pusch_proc_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_proc_options_t* options,

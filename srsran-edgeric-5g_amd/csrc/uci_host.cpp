@@ -4,6 +4,7 @@
 // polar_code_impl.cpp:421-490), the channel de-interleaver's permutation, the de-allocator's positions, the CRC weights and the
 // decoder's walk over the tree flattened into a list of operations (polar_decoder_impl::simplified_node).
 #include "nrphy_host_internal.h"
+#include "pusch_select_host.h"
 
 namespace {
 
@@ -249,6 +250,7 @@ struct nrphy_uci_decoder_plan {
   UciCodeDesc* d_code  = nullptr;
   uint16_t*    d_tab16 = nullptr;
   uint32_t*    d_ops   = nullptr;
+  bool         selects = false; // some message names a select word
 };
 
 extern "C" int nrphy_uci_decoder_validate(const nrphy_uci_decoder_cfg_t* cfg)
@@ -269,9 +271,9 @@ extern "C" int nrphy_uci_decoder_plan_destroy(nrphy_uci_decoder_plan_t* plan)
   return NRPHY_OK;
 }
 
-extern "C" int nrphy_uci_decoder_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_uci_decoder_cfg_t* cfgs,
-                                             const uint64_t* llr_offset, const uint64_t* message_offset,
-                                             nrphy_uci_decoder_plan_t** out)
+int uci_decoder_plan_create_select(nrphy_ctx_t* ctx, uint32_t n, const nrphy_uci_decoder_cfg_t* cfgs, const uint64_t* llr_offset,
+                                   const uint64_t* message_offset, const uint32_t* select_word, const uint32_t* select_value,
+                                   nrphy_uci_decoder_plan_t** out)
 {
   if (out == nullptr) {
     return NRPHY_ERR_ARGUMENT;
@@ -285,6 +287,7 @@ extern "C" int nrphy_uci_decoder_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
   std::vector<uint16_t>        tab16;
   std::vector<uint32_t>        ops;
   std::map<uint64_t, uint32_t> code_index; // (K, E) -> index: each distinct code is built once
+  bool                         selects = false;
   for (uint32_t i = 0; i != n; ++i) {
     const nrphy_uci_decoder_cfg_t& c = cfgs[i];
     if (validate(&c) != NRPHY_OK) {
@@ -298,6 +301,9 @@ extern "C" int nrphy_uci_decoder_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
     m.nof_blocks     = 1;
     m.llr_offset     = llr_offset[i];
     m.message_offset = message_offset[i];
+    m.select_word    = select_word != nullptr && select_value != nullptr ? select_word[i] : NO_SELECT_WORD;
+    m.select_value   = m.select_word != NO_SELECT_WORD ? select_value[i] : 0;
+    selects          = selects || m.select_word != NO_SELECT_WORD;
     if (c.message_length <= 2) {
       bits_per_symbol(c.modulation, &m.bps);
     }
@@ -342,6 +348,7 @@ extern "C" int nrphy_uci_decoder_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
   auto* plan = new nrphy_uci_decoder_plan;
   plan->ctx  = ctx;
   plan->n    = n;
+  plan->selects = selects;
   DeviceArena arena;
   arena.add(&plan->d_msg, msg.data(), msg.size() * sizeof(UciMsgDesc));
   arena.add(&plan->d_code, codes.data(), codes.size() * sizeof(UciCodeDesc));
@@ -356,13 +363,22 @@ extern "C" int nrphy_uci_decoder_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
   return NRPHY_OK;
 }
 
-extern "C" int nrphy_uci_decoder_run(nrphy_uci_decoder_plan_t* plan, const int8_t* d_llr, uint8_t* d_message, uint32_t* d_status,
-                                     void* stream)
+extern "C" int nrphy_uci_decoder_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_uci_decoder_cfg_t* cfgs,
+                                             const uint64_t* llr_offset, const uint64_t* message_offset,
+                                             nrphy_uci_decoder_plan_t** out)
 {
-  if (plan == nullptr || d_llr == nullptr || d_message == nullptr || d_status == nullptr || ((uintptr_t)d_status & 3U) != 0) {
+  return uci_decoder_plan_create_select(ctx, n, cfgs, llr_offset, message_offset, nullptr, nullptr, out);
+}
+
+int uci_decoder_run_select(nrphy_uci_decoder_plan_t* plan, const int8_t* d_llr, uint8_t* d_message, uint32_t* d_status,
+                           const uint32_t* d_select, void* stream)
+{
+  if (plan == nullptr || d_llr == nullptr || d_message == nullptr || d_status == nullptr || ((uintptr_t)d_status & 3U) != 0 ||
+      (plan->selects && d_select == nullptr)) {
     return NRPHY_ERR_ARGUMENT;
   }
   UciLaunch p;
+  p.select  = plan->selects ? d_select : nullptr;
   p.msg     = plan->d_msg;
   p.code    = plan->d_code;
   p.tab16   = plan->d_tab16;
@@ -374,6 +390,12 @@ extern "C" int nrphy_uci_decoder_run(nrphy_uci_decoder_plan_t* plan, const int8_
   HIP_TRY(hipSetDevice(plan->ctx->device));
   HIP_TRY(launch_uci_decoder(p, stream ? (hipStream_t)stream : plan->ctx->stream));
   return NRPHY_OK;
+}
+
+extern "C" int nrphy_uci_decoder_run(nrphy_uci_decoder_plan_t* plan, const int8_t* d_llr, uint8_t* d_message, uint32_t* d_status,
+                                     void* stream)
+{
+  return uci_decoder_run_select(plan, d_llr, d_message, d_status, nullptr, stream);
 }
 
 extern "C" int nrphy_uci_decode_host(nrphy_ctx_t* ctx, const nrphy_uci_decoder_cfg_t* cfg, const int8_t* llr, uint8_t* message,

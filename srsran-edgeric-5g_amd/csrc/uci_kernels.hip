@@ -285,6 +285,11 @@ __global__ __launch_bounds__(WAVE) void uci_decoder_kernel(UciLaunch p)
   __shared__ UciShared sh;
   const uint32_t       lane = threadIdx.x;
   const UciMsgDesc&    m    = p.msg[blockIdx.x];
+  // A message that names a select word runs only when the word holds its value (workgroup-uniform); otherwise it writes nothing,
+  // its status included.
+  if (p.select != nullptr && m.select_word != NO_SELECT_WORD && p.select[m.select_word] != m.select_value) {
+    return;
+  }
   const int8_t*        llr  = p.llr + m.llr_offset;
   uint8_t*             out  = p.message + m.message_offset;
   uint32_t             status;

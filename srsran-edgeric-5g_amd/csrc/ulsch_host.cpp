@@ -1,5 +1,6 @@
 // Host side of the UL-SCH demultiplexer (ulsch_kernels.hip): validation, sizes, and per codeword of a plan the placement table
 // of ulsch_placement_host.h with the codeword's descriptor.
+#include "pusch_select_host.h"
 #include "ulsch_placement_host.h"
 
 namespace {
@@ -20,6 +21,7 @@ struct nrphy_ulsch_demux_plan {
   UlschSpecialDev* d_special = nullptr;
   uint32_t         nof_blocks = 0;
   bool             uses[4]    = {true, false, false, false}; // streams some codeword writes
+  bool             selects    = false;                       // some codeword names a select word
 };
 
 extern "C" int nrphy_ulsch_demux_validate(const nrphy_ulsch_demux_cfg_t* cfg)
@@ -52,10 +54,10 @@ extern "C" int nrphy_ulsch_demux_plan_destroy(nrphy_ulsch_demux_plan_t* plan)
   return NRPHY_OK;
 }
 
-extern "C" int nrphy_ulsch_demux_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_ulsch_demux_cfg_t* cfgs,
-                                             const uint64_t* in_offset, const uint64_t* sch_offset, const uint64_t* harq_offset,
-                                             const uint64_t* csi1_offset, const uint64_t* csi2_offset,
-                                             nrphy_ulsch_demux_plan_t** out)
+int ulsch_demux_plan_create_select(nrphy_ctx_t* ctx, uint32_t n, const nrphy_ulsch_demux_cfg_t* cfgs, const uint64_t* in_offset,
+                                   const uint64_t* sch_offset, const uint64_t* harq_offset, const uint64_t* csi1_offset,
+                                   const uint64_t* csi2_offset, const uint32_t* select_word, const uint32_t* select_value,
+                                   nrphy_ulsch_demux_plan_t** out)
 {
   if (out == nullptr) {
     return NRPHY_ERR_ARGUMENT;
@@ -100,6 +102,9 @@ extern "C" int nrphy_ulsch_demux_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
     d.special_offset = (uint32_t)special.size();
     d.nof_special    = (uint32_t)p.special.size();
     d.c_init         = c.rnti * (1U << 15) + c.n_id;
+    d.select_word    = select_word != nullptr && select_value != nullptr ? select_word[i] : NO_SELECT_WORD;
+    d.select_value   = d.select_word != NO_SELECT_WORD ? select_value[i] : 0;
+    plan->selects    = plan->selects || d.select_word != NO_SELECT_WORD;
     map.insert(map.end(), p.map.begin(), p.map.end());
     for (const UlschSpecial& s : p.special) {
       special.push_back({s.src, s.dst, s.stream, s.fix});
@@ -126,13 +131,23 @@ extern "C" int nrphy_ulsch_demux_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
   return NRPHY_OK;
 }
 
-extern "C" int nrphy_ulsch_demux_run(nrphy_ulsch_demux_plan_t* plan, const int8_t* d_codeword_llr, int8_t* d_sch, int8_t* d_harq_ack,
-                                     int8_t* d_csi1, int8_t* d_csi2, void* stream)
+extern "C" int nrphy_ulsch_demux_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_ulsch_demux_cfg_t* cfgs,
+                                             const uint64_t* in_offset, const uint64_t* sch_offset, const uint64_t* harq_offset,
+                                             const uint64_t* csi1_offset, const uint64_t* csi2_offset,
+                                             nrphy_ulsch_demux_plan_t** out)
 {
-  if (plan == nullptr || d_codeword_llr == nullptr) {
+  return ulsch_demux_plan_create_select(ctx, n, cfgs, in_offset, sch_offset, harq_offset, csi1_offset, csi2_offset, nullptr, nullptr,
+                                        out);
+}
+
+int ulsch_demux_run_select(nrphy_ulsch_demux_plan_t* plan, const int8_t* d_codeword_llr, int8_t* d_sch, int8_t* d_harq_ack,
+                           int8_t* d_csi1, int8_t* d_csi2, const uint32_t* d_select, void* stream)
+{
+  if (plan == nullptr || d_codeword_llr == nullptr || (plan->selects && d_select == nullptr)) {
     return NRPHY_ERR_ARGUMENT;
   }
   UlschLaunch p;
+  p.select     = plan->selects ? d_select : nullptr;
   p.cw         = plan->d_cw;
   p.block_cw   = plan->d_block;
   p.map        = plan->d_map;
@@ -158,6 +173,12 @@ extern "C" int nrphy_ulsch_demux_run(nrphy_ulsch_demux_plan_t* plan, const int8_
   HIP_TRY(hipSetDevice(plan->ctx->device));
   HIP_TRY(launch_ulsch_demux(p, stream ? (hipStream_t)stream : plan->ctx->stream));
   return NRPHY_OK;
+}
+
+extern "C" int nrphy_ulsch_demux_run(nrphy_ulsch_demux_plan_t* plan, const int8_t* d_codeword_llr, int8_t* d_sch, int8_t* d_harq_ack,
+                                     int8_t* d_csi1, int8_t* d_csi2, void* stream)
+{
+  return ulsch_demux_run_select(plan, d_codeword_llr, d_sch, d_harq_ack, d_csi1, d_csi2, nullptr, stream);
 }
 
 extern "C" int nrphy_ulsch_demultiplex_host(nrphy_ctx_t* ctx, const nrphy_ulsch_demux_cfg_t* cfg, const int8_t* codeword_llr,

@@ -100,6 +100,11 @@ __global__ __launch_bounds__(ULSCH_THREADS) void ulsch_demux_kernel(UlschLaunch 
   const uint32_t     c     = p.block_cw[blockIdx.x];
   const UlschCwDesc& cw    = p.cw[c];
   const uint32_t     block = blockIdx.x - cw.first_block;
+  // A codeword that names a select word acts only when the word holds its value (workgroup-uniform: scalar loads of a kernel
+  // argument and of the block's descriptor).
+  if (p.select != nullptr && cw.select_word != NO_SELECT_WORD && p.select[cw.select_word] != cw.select_value) {
+    return;
+  }
   if (block >= cw.nof_copy_blocks) { // workgroup-uniform
     ulsch_special_block(p, cw, block - cw.nof_copy_blocks);
     return;

@@ -490,6 +490,30 @@ class Context:
                                               uci.ctypes.data if uci.size else None, C.byref(result)), "nrphy_pusch_proc_host")
         return result, tb, uci
 
+    def pusch_csi2_host(self, pdu, desc, options, grid, harq_soft=None, harq_state=None, csi2_fill=0):
+        """pusch_processor::process for one PDU with a CSI part 2 description: as pusch_proc_host, and returns (abi.PuschResult,
+        abi.PuschCsi2Result, transport block bytes, UCI payload bits, CSI part 2 bits).  The part 2 array has room for the largest
+        size of the description and starts filled with csi2_fill; the first nof_csi_part2 bytes are the payload."""
+        grid = np.ascontiguousarray(grid, dtype=np.uint32)
+        soft_bytes, state_bytes = pusch_csi2_harq_bytes(pdu, desc, options)
+        soft = np.zeros(soft_bytes, np.int8) if harq_soft is None else harq_soft
+        state = np.zeros(state_bytes, np.uint8) if harq_state is None else harq_state
+        if soft.size != soft_bytes or state.size != state_bytes or not (soft.flags.c_contiguous and state.flags.c_contiguous):
+            raise ValueError("HARQ blocks must be contiguous arrays of %d and %d bytes" % (soft_bytes, state_bytes))
+        table = pusch_csi2_variants(pdu, desc, options, grid.shape[0], grid.shape[-1])
+        if table is None:
+            raise ValueError("nrphy_pusch_csi2_validate refuses the PDU")
+        tb = np.zeros(pdu.tb_size_bytes, np.uint8)
+        uci = np.zeros(pdu.nof_harq_ack + pdu.nof_csi_part1, np.uint8)
+        csi2 = np.full(table[0][-1], csi2_fill, np.uint8)
+        result, csi2_result = abi.PuschResult(), abi.PuschCsi2Result()
+        _check(self.lib.nrphy_pusch_csi2_host(self.handle, C.byref(pdu), C.byref(desc), C.byref(options), grid.ctypes.data,
+                                              grid.shape[0], grid.shape[-1], soft.ctypes.data if soft_bytes else None,
+                                              state.ctypes.data if state_bytes else None, tb.ctypes.data if tb.size else None,
+                                              uci.ctypes.data if uci.size else None, csi2.ctypes.data if csi2.size else None,
+                                              C.byref(result), C.byref(csi2_result)), "nrphy_pusch_csi2_host")
+        return result, csi2_result, tb, uci, csi2
+
     def prach_detect_host(self, cfg, symbols, with_metric=False):
         """prach_detector::detect for one occasion: symbols [ports][symbols][L_RA] complex64 -> (abi.PrachResult, the 64
         abi.PrachPreamble slots, and with_metric the metric windows [64][window width] f32 or None)."""
@@ -1056,6 +1080,78 @@ class PuschProcPlan:
             self.close()
         except Exception:
             pass
+
+
+class PuschCsi2Plan:
+    """nrphy_pusch_csi2_plan: PuschProcPlan for PDUs of which some carry a CSI part 2 size description (abi.PuschCsi2Desc, one per
+    PDU; nof_entries 0 = none).  run() also writes one abi.PuschCsi2Result per PDU; PDU i's part 2 payload goes to byte
+    csi2_offsets[i] of d_uci_bits."""
+
+    def __init__(self, ctx, pdus, descs, options, grid_indices, nof_grids, nof_ports, nof_subc, harq_soft_offsets=None,
+                 harq_state_offsets=None, tb_offsets=None, uci_offsets=None, csi2_offsets=None):
+        self.ctx = ctx
+        n = len(pdus)
+        arr = (abi.PuschPdu * n)(*pdus)
+        darr = (abi.PuschCsi2Desc * n)(*descs)
+        gidx = (C.c_uint32 * n)(*grid_indices)
+        offs = [None if o is None else (C.c_uint64 * n)(*o)
+                for o in (harq_soft_offsets, harq_state_offsets, tb_offsets, uci_offsets, csi2_offsets)]
+        h = C.c_void_p()
+        _check(ctx.lib.nrphy_pusch_csi2_plan_create(ctx.handle, n, arr, darr, C.byref(options), gidx, nof_grids, nof_ports, nof_subc,
+                                                    *offs, C.byref(h)), "nrphy_pusch_csi2_plan_create")
+        self.handle = h
+        self.n = n
+
+    def run(self, d_grid, d_harq, d_tb, d_uci_bits, d_result, d_csi2_result, stream=None):
+        """As PuschProcPlan.run; d_csi2_result: [n] x sizeof(abi.PuschCsi2Result) bytes."""
+        _check(self.ctx.lib.nrphy_pusch_csi2_run(self.handle, _dptr(d_grid), _dptr(d_harq), _dptr(d_tb), _dptr(d_uci_bits),
+                                                 _dptr(d_result), _dptr(d_csi2_result), _stream(stream)), "nrphy_pusch_csi2_run")
+
+    def close(self):
+        if self.handle:
+            self.ctx.lib.nrphy_pusch_csi2_plan_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def pusch_csi2_size(desc, csi_part1_bits):
+    """nrphy_pusch_csi2_size: uci_part2_get_size of a CSI part 1 payload (one bit per element), or None for a refused description
+    (host only)."""
+    bits = np.ascontiguousarray(csi_part1_bits, dtype=np.uint8)
+    size = C.c_uint32(0)
+    if int(load().nrphy_pusch_csi2_size(C.byref(desc), bits.ctypes.data, bits.size, C.byref(size))) != abi.OK:
+        return None
+    return int(size.value)
+
+
+def pusch_csi2_validate(pdu, desc, options, grid_nof_ports, grid_nof_subc):
+    """nrphy_pusch_csi2_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_pusch_csi2_validate(C.byref(pdu), C.byref(desc), C.byref(options), grid_nof_ports, grid_nof_subc))
+
+
+def pusch_csi2_variants(pdu, desc, options, grid_nof_ports, grid_nof_subc):
+    """nrphy_pusch_csi2_variants: (sizes, infos) -- the PDU's variant table, sizes[0] = 0, then the distinct non-zero sizes
+    ascending, each with its abi.UlschInfo --, or None for a refused PDU (host only)."""
+    n = C.c_uint32(0)
+    sizes = (C.c_uint32 * abi.PUSCH_CSI2_MAX_VARIANTS)()
+    infos = (abi.UlschInfo * abi.PUSCH_CSI2_MAX_VARIANTS)()
+    if int(load().nrphy_pusch_csi2_variants(C.byref(pdu), C.byref(desc), C.byref(options), grid_nof_ports, grid_nof_subc, C.byref(n),
+                                            sizes, infos)) != abi.OK:
+        return None
+    return [int(v) for v in sizes[:n.value]], [abi.UlschInfo.from_buffer_copy(infos[k]) for k in range(n.value)]
+
+
+def pusch_csi2_harq_bytes(pdu, desc, options):
+    """nrphy_pusch_csi2_harq_bytes: (soft bytes, state bytes) of the PDU's HARQ blocks (host only)."""
+    soft, state = C.c_uint64(0), C.c_uint64(0)
+    _check(load().nrphy_pusch_csi2_harq_bytes(C.byref(pdu), C.byref(desc), C.byref(options), C.byref(soft), C.byref(state)),
+           "nrphy_pusch_csi2_harq_bytes")
+    return int(soft.value), int(state.value)
 
 
 def ulsch_info(cfg):
