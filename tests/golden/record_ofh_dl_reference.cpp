@@ -1,28 +1,12 @@
 // Records the Ethernet frames of srsRAN-5G-ER's Open Fronthaul downlink user-plane data flow for tests/test_ofh_downlink.py:
 // the real data_flow_uplane_downlink_data_impl with the real VLAN Ethernet and eCPRI builders, the static and the dynamic
 // user-plane message builders, the AVX2 compressors (the ones nrphy_ofh_compress is pinned to) and an eth_frame_pool of the
-// case's MTU, reading a seeded grid through a plain resource_grid_reader.  Built and run outside the repository; no binary or
-// object is committed.  R = a checkout of srsRAN-5G-ER, OUT = this directory:
+// case's MTU, reading a seeded grid through a plain resource_grid_reader.  Built and run by oracle/recorders.mk, against a
+// checkout of srsRAN-5G-ER and into oracle/_ref/: `make -C oracle recorders`, `make -C oracle rerecord-check`; no binary or
+// object is committed.  The recipe builds this file with -fno-access-control, for one line: the data flow's sequence generator
+// always starts at 0, and the case with sequence identifiers 254, 255, 0 sets its counter.
 //
-//   g++ -std=c++17 -O2 -mavx2 -mfma -DNDEBUG -w -fno-access-control -I$R/include -I$R/external/fmt/include -I$R/external -I$R \
-//     record_ofh_dl_reference.cpp $R/lib/ofh/transmitter/ofh_data_flow_uplane_downlink_data_impl.cpp \
-//     $R/lib/ofh/transmitter/ofh_uplane_fragment_size_calculator.cpp $R/lib/ofh/ethernet/vlan_ethernet_frame_builder_impl.cpp \
-//     $R/lib/ofh/ecpri/ecpri_packet_builder_impl.cpp $R/lib/ofh/serdes/ofh_uplane_message_builder_impl.cpp \
-//     $R/lib/ofh/serdes/ofh_uplane_message_builder_static_compression_impl.cpp \
-//     $R/lib/ofh/serdes/ofh_uplane_message_builder_dynamic_compression_impl.cpp \
-//     $R/lib/ofh/compression/iq_compression_none_impl.cpp $R/lib/ofh/compression/iq_compression_none_avx2.cpp \
-//     $R/lib/ofh/compression/iq_compression_bfp_impl.cpp $R/lib/ofh/compression/iq_compression_bfp_avx2.cpp \
-//     $R/lib/ofh/compression/compressed_prb_packer.cpp $R/lib/ofh/compression/compressed_prb_unpacker.cpp \
-//     $R/lib/instrumentation/traces/ofh_traces.cpp $R/lib/srsvec/conversion.cpp $R/lib/srsvec/aligned_vec.cpp \
-//     $R/lib/srslog/srslog.cpp $R/lib/srslog/backend_worker.cpp $R/lib/srslog/event_trace.cpp $R/lib/srslog/formatters/json_formatter.cpp \
-//     $R/lib/srslog/formatters/text_formatter.cpp $R/external/fmt/src/format.cc $R/external/fmt/src/os.cc -lpthread \
-//     -o record_ofh_dl_reference
-//   ./record_ofh_dl_reference OUT
-//
-// -fno-access-control is for one line: the data flow's sequence generator always starts at 0, and the case with sequence
-// identifiers 254, 255, 0 sets its counter.
-//
-// Grids are not stored.  With mix the 32-bit finaliser below, value i (i = ((port * 14 + symbol) * nof_subc + k) * 2 + re/im)
+// Grids are not stored.  With mix the 32-bit finaliser of recorder_io.h, value i (i = ((port * 14 + symbol) * nof_subc + k) * 2 + re/im)
 // of the grid of seed s comes from h = mix(s + i) and the class c = mix(31 s + k / 12 + 0x51ED) & 3 of its PRB:
 //   magnitude  (h >> 4) & 31                    if (h & 15) < 12 or c < 2     small integers
 //              64 * ((h >> 4) & 127)            else if (h & 15) < 14 or c == 2
@@ -42,49 +26,16 @@
 #include "lib/ofh/serdes/ofh_uplane_message_builder_dynamic_compression_impl.h"
 #include "lib/ofh/serdes/ofh_uplane_message_builder_static_compression_impl.h"
 #include "lib/ofh/transmitter/ofh_data_flow_uplane_downlink_data_impl.h"
+#include "recorder_io.h"
 #include "srsran/ofh/ethernet/ethernet_frame_pool.h"
 #include "srsran/phy/support/resource_grid_reader.h"
 
 #include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <sstream>
-#include <string>
-#include <vector>
 
 using namespace srsran;
 using namespace ofh;
 
 namespace {
-
-uint32_t mix(uint32_t h)
-{
-  h ^= h >> 16;
-  h *= 0x85EBCA6BU;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35U;
-  h ^= h >> 16;
-  return h;
-}
-
-void write_npy(const std::string& path, const std::vector<uint8_t>& data)
-{
-  std::ostringstream shape;
-  shape << "(" << data.size() << ",)";
-  std::string header = std::string("{'descr': '|u1', 'fortran_order': False, 'shape': ") + shape.str() + ", }";
-  while ((10 + header.size() + 1) % 64 != 0) {
-    header += ' ';
-  }
-  header += '\n';
-  std::ofstream  f(path, std::ios::binary);
-  const char     magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
-  const uint16_t len      = (uint16_t)header.size();
-  f.write(magic, 8);
-  f.write((const char*)&len, 2);
-  f.write(header.data(), header.size());
-  f.write((const char*)data.data(), data.size());
-}
 
 // A seeded grid [ports][14][nof_subc] behind the reference's reader interface.
 class seeded_grid : public resource_grid_reader

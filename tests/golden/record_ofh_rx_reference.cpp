@@ -6,28 +6,12 @@
 // forwarding wrappers around the injected parts note how far a frame got; the grid double (over the doubles of
 // R/tests/unittests/ofh/receiver/helpers.h) keeps [ports][14][subcarriers] and is poisoned before every frame, so every write
 // shows.  The PRACH data flow is a spy, as in the reference's ofh_message_receiver_test.cpp: the library reports PRACH messages
-// and leaves them to the caller.  Built and run outside the repository; no binary or object is committed.  R = a checkout of
-// srsRAN-5G-ER, OUT = this directory:
-//
-//   g++ -std=c++17 -O2 -DNDEBUG -w -I$R/include -I$R/external/fmt/include -I$R/external -I$R -I$R/tests/unittests/ofh/receiver \
-//     record_ofh_rx_reference.cpp $R/lib/ofh/receiver/ofh_message_receiver.cpp $R/lib/ofh/receiver/ofh_rx_window_checker.cpp \
-//     $R/lib/ofh/receiver/ofh_data_flow_uplane_uplink_data_impl.cpp $R/lib/ofh/receiver/ofh_uplane_rx_symbol_data_flow_writer.cpp \
-//     $R/lib/ofh/receiver/ofh_uplane_rx_symbol_data_flow_notifier.cpp $R/lib/ofh/ethernet/vlan_ethernet_frame_decoder_impl.cpp \
-//     $R/lib/ofh/ecpri/ecpri_packet_decoder_impl.cpp $R/lib/ofh/serdes/ofh_uplane_message_decoder_impl.cpp \
-//     $R/lib/ofh/serdes/ofh_uplane_message_decoder_static_compression_impl.cpp \
-//     $R/lib/ofh/serdes/ofh_uplane_message_decoder_dynamic_compression_impl.cpp $R/lib/ofh/compression/iq_decompressor_selector.cpp \
-//     $R/lib/ofh/compression/iq_compression_none_impl.cpp $R/lib/ofh/compression/iq_compression_bfp_impl.cpp \
-//     $R/lib/ofh/compression/iq_compression_death_impl.cpp \
-//     $R/lib/ofh/compression/compressed_prb_packer.cpp $R/lib/ofh/compression/compressed_prb_unpacker.cpp \
-//     $R/lib/instrumentation/traces/ofh_traces.cpp $R/lib/srsvec/conversion.cpp $R/lib/srsvec/dot_prod.cpp \
-//     $R/lib/srsvec/aligned_vec.cpp $R/lib/srslog/srslog.cpp $R/lib/srslog/backend_worker.cpp $R/lib/srslog/event_trace.cpp \
-//     $R/lib/srslog/formatters/json_formatter.cpp $R/lib/srslog/formatters/text_formatter.cpp $R/external/fmt/src/format.cc \
-//     $R/external/fmt/src/os.cc -lpthread -o record_ofh_rx_reference
-//   ./record_ofh_rx_reference OUT
+// and leaves them to the caller.  Built and run by oracle/recorders.mk, against a checkout R of srsRAN-5G-ER and into
+// oracle/_ref/: `make -C oracle recorders`, `make -C oracle rerecord-check`; no binary or object is committed.
 //
 // Four batches: eCPRI payload size used or ignored x static (BFP 9 / none 16) or dynamic compression.  The RU has 9 PRBs, the
 // grids 2 ports x 14 x 72 subcarriers (6 PRBs); ul_eaxc = {4, 5}, prach_eaxc = {0, 1}; 30 kHz.  A batch is one receiver and one
-// list of frames taken in order.  The frames are built here: PRB records are seeded bytes (mix below; for BFP the udCompParam
+// list of frames taken in order.  The frames are built here: PRB records are seeded bytes (mix of recorder_io.h; for BFP the udCompParam
 // byte & 0x0F), everything else is stated per frame.  Inputs for which the library defines rules of its own are not fed: an
 // eCPRI payload size below 4, dynamic compression types 2..6, none with 1 bit.  No symbol is ever written completely on both
 // ports (checked: the notifier is never called), so the contexts the batch starts with stay.
@@ -52,50 +36,15 @@
 #include "lib/ofh/receiver/ofh_sequence_id_checker_impl.h"
 #include "lib/ofh/serdes/ofh_uplane_message_decoder_dynamic_compression_impl.h"
 #include "lib/ofh/serdes/ofh_uplane_message_decoder_static_compression_impl.h"
+#include "recorder_io.h"
 #include "srsran/ofh/ethernet/ethernet_unique_buffer.h"
 #include "tests/unittests/ofh/ofh_uplane_rx_symbol_notifier_test_doubles.h"
-
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <sstream>
-#include <string>
-#include <vector>
 
 using namespace srsran;
 using namespace ofh;
 using namespace ofh::testing;
 
 namespace {
-
-uint32_t mix(uint32_t h)
-{
-  h ^= h >> 16;
-  h *= 0x85EBCA6BU;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35U;
-  h ^= h >> 16;
-  return h;
-}
-
-template <typename T>
-void write_npy(const std::string& path, const char* descr, const std::vector<T>& data)
-{
-  std::ostringstream shape;
-  shape << "(" << data.size() << ",)";
-  std::string header = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape.str() + ", }";
-  while ((10 + header.size() + 1) % 64 != 0) {
-    header += ' ';
-  }
-  header += '\n';
-  std::ofstream  f(path, std::ios::binary);
-  const char     magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
-  const uint16_t len      = (uint16_t)header.size();
-  f.write(magic, 8);
-  f.write((const char*)&len, 2);
-  f.write(header.data(), header.size());
-  f.write((const char*)data.data(), data.size() * sizeof(T));
-}
 
 srslog::basic_logger& logger()
 {

@@ -1,21 +1,11 @@
 // Records the answers of srsRAN-5G-ER's Open Fronthaul receive path for tests/test_ofh_uplink.py: the generic decompressors
 // (iq_compression_none_impl, iq_compression_bfp_impl -- the SIMD classes delegate decompress to them) on seeded payloads, and
 // the two data-flow writers (uplane_rx_symbol_data_flow_writer, uplane_prach_symbol_data_flow_writer) with the test doubles
-// of the reference's own unit tests (R/tests/unittests/ofh/receiver/helpers.h) on the section ranges those tests use.  Built
-// and run outside the repository; no binary or object is committed.  R = a checkout of srsRAN-5G-ER, OUT = this directory:
+// of the reference's own unit tests (R/tests/unittests/ofh/receiver/helpers.h, R a checkout of srsRAN-5G-ER) on the section
+// ranges those tests use.  Built and run by oracle/recorders.mk, into oracle/_ref/: `make -C oracle recorders`,
+// `make -C oracle rerecord-check`; no binary or object is committed.
 //
-//   g++ -std=c++17 -O2 -DNDEBUG -w -I$R/include -I$R/external/fmt/include -I$R/external -I$R -I$R/tests/unittests/ofh/receiver \
-//     record_ofh_ul_reference.cpp $R/lib/ofh/compression/iq_compression_none_impl.cpp $R/lib/ofh/compression/iq_compression_bfp_impl.cpp \
-//     $R/lib/ofh/compression/compressed_prb_packer.cpp $R/lib/ofh/compression/compressed_prb_unpacker.cpp \
-//     $R/lib/ofh/receiver/ofh_uplane_rx_symbol_data_flow_writer.cpp $R/lib/ofh/receiver/ofh_uplane_prach_symbol_data_flow_writer.cpp \
-//     $R/lib/ran/prach/prach_frequency_mapping.cpp $R/lib/ran/prach/prach_preamble_information.cpp \
-//     $R/lib/instrumentation/traces/ofh_traces.cpp $R/lib/srsvec/conversion.cpp $R/lib/srsvec/dot_prod.cpp $R/lib/srsvec/aligned_vec.cpp \
-//     $R/lib/srslog/srslog.cpp $R/lib/srslog/backend_worker.cpp $R/lib/srslog/event_trace.cpp $R/lib/srslog/formatters/json_formatter.cpp \
-//     $R/lib/srslog/formatters/text_formatter.cpp $R/external/fmt/src/format.cc $R/external/fmt/src/os.cc -lpthread \
-//     -o record_ofh_ul_reference
-//   ./record_ofh_ul_reference OUT
-//
-// Inputs are not stored.  With mix the 32-bit finaliser below, byte k of a payload of seed s is mix(s + k) & 0xFF.
+// Inputs are not stored.  With mix the 32-bit finaliser of recorder_io.h, byte k of a payload of seed s is mix(s + k) & 0xFF.
 //
 // Decompression case i (seed 0x9E3779B9 * (i + 1)): type none with widths 2..16, then BFP with widths 1..16 x udCompParam
 // 0..30.  Four PRB records: the packed bytes all 0x00, all 0xFF, the most negative value in every field, seeded (bytes
@@ -37,53 +27,14 @@
 #include "lib/ofh/compression/iq_compression_none_impl.h"
 #include "lib/ofh/receiver/ofh_uplane_prach_symbol_data_flow_writer.h"
 #include "lib/ofh/receiver/ofh_uplane_rx_symbol_data_flow_writer.h"
+#include "recorder_io.h"
 #include "srsran/ofh/serdes/ofh_message_decoder_properties.h"
-
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <sstream>
-#include <string>
-#include <vector>
 
 using namespace srsran;
 using namespace ofh;
 using namespace ofh::testing;
 
 namespace {
-
-uint32_t mix(uint32_t h)
-{
-  h ^= h >> 16;
-  h *= 0x85EBCA6BU;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35U;
-  h ^= h >> 16;
-  return h;
-}
-
-template <typename T>
-void write_npy(const std::string& path, const char* descr, const std::vector<T>& data, size_t cols)
-{
-  std::ostringstream shape;
-  if (cols == 0) {
-    shape << "(" << data.size() << ",)";
-  } else {
-    shape << "(" << data.size() / cols << ", " << cols << ")";
-  }
-  std::string header = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape.str() + ", }";
-  while ((10 + header.size() + 1) % 64 != 0) {
-    header += ' ';
-  }
-  header += '\n';
-  std::ofstream  f(path, std::ios::binary);
-  const char     magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
-  const uint16_t len      = (uint16_t)header.size();
-  f.write(magic, 8);
-  f.write((const char*)&len, 2);
-  f.write(header.data(), header.size());
-  f.write((const char*)data.data(), data.size() * sizeof(T));
-}
 
 srslog::basic_logger& logger()
 {

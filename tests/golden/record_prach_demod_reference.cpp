@@ -1,14 +1,11 @@
 // Records the answers of srsRAN-5G-ER's ofdm_prach_demodulator_impl for tests/test_prach_demodulator.py.  It constructs the
 // reference's classes directly (dft_processor_generic_impl, prach_buffer_impl), feeds them seeded inputs and writes the outputs as
-// .npy files; it also prints the reference's preamble, window and frequency mapping tables.  Built and run outside the repository;
-// no binary or object is committed.  R = a checkout of srsRAN-5G-ER, OUT = this directory:
+// .npy files; it also prints the reference's preamble, window and frequency mapping tables.  Built and run by
+// oracle/recorders.mk, against a checkout of srsRAN-5G-ER and into oracle/_ref/: `make -C oracle recorders`,
+// `make -C oracle rerecord-check`; no binary or object is committed.
 //
-//   g++ -std=c++17 -O2 -DNDEBUG -w -I$R/include -I$R/external/fmt/include -I$R/external -I$R record_prach_demod_reference.cpp \
-//     $R/lib/phy/lower/modulation/ofdm_prach_demodulator_impl.cpp $R/lib/phy/generic_functions/dft_processor_generic_impl.cpp \
-//     $R/lib/ran/prach/prach_preamble_information.cpp $R/lib/ran/prach/prach_frequency_mapping.cpp $R/lib/srsvec/aligned_vec.cpp \
-//     $R/external/fmt/src/format.cc $R/external/fmt/src/os.cc -lpthread -o record_prach_demod_reference
-//   ./record_prach_demod_reference prach_demod_configs.json OUT       the recording
-//   ./record_prach_demod_reference --tables > prach_demod_tables.json the tables
+//   record_prach_demod_reference prach_demod_configs.json OUT       the recording
+//   record_prach_demod_reference --tables > prach_demod_tables.json the tables
 //
 // The cases are the entries of prach_demod_configs.json followed by EXTRA below (what the unit test's header leaves out).
 // Inputs are not stored.  Sample n of case c has real part value(2 n) and imaginary part value(2 n + 1) of the sequence
@@ -23,16 +20,11 @@
 #include "lib/phy/generic_functions/dft_processor_generic_impl.h"
 #include "lib/phy/lower/modulation/ofdm_prach_demodulator_impl.h"
 #include "lib/phy/support/prach_buffer_impl.h"
+#include "recorder_io.h"
 #include "srsran/ran/prach/prach_frequency_mapping.h"
 #include "srsran/ran/prach/prach_preamble_information.h"
 
 #include <complex>
-#include <cstdio>
-#include <fstream>
-#include <regex>
-#include <sstream>
-#include <string>
-#include <vector>
 
 using namespace srsran;
 
@@ -75,29 +67,6 @@ const Case EXTRA[] = {
     {92160000, 8, 1, 4, 2, 110, 275, 0}, // B4 on 6144
     {30720000, 2, 1, 2, 2, 20, 79, 0},   // format 2 from symbol 2
 };
-
-template <typename T>
-void write_npy(const std::string& path, const char* descr, const std::vector<T>& data, size_t cols)
-{
-  std::ostringstream shape;
-  if (cols == 0) {
-    shape << "(" << data.size() << ",)";
-  } else {
-    shape << "(" << data.size() / cols << ", " << cols << ")";
-  }
-  std::string header = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape.str() + ", }";
-  while ((10 + header.size() + 1) % 64 != 0) {
-    header += ' ';
-  }
-  header += '\n';
-  std::ofstream  f(path, std::ios::binary);
-  const char     magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
-  const uint16_t len      = (uint16_t)header.size();
-  f.write(magic, 8);
-  f.write((const char*)&len, 2);
-  f.write(header.data(), header.size());
-  f.write((const char*)data.data(), data.size() * sizeof(T));
-}
 
 unsigned kappa(phy_time_unit t)
 {

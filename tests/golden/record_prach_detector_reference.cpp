@@ -1,15 +1,9 @@
 // Records the answers of srsRAN-5G-ER's prach_detector_generic_impl (combine_symbols = true) and prach_generator_impl for
 // tests/test_prach_detector.py.  It constructs the reference's classes directly -- the detector over two
 // dft_processor_generic_impl (1024 and 256 points, inverse) and a prach_generator_impl, on a prach_buffer_impl --, makes an
-// occasion per case with a transmitter of its own, and writes inputs and outputs as .npy files.  Built and run outside the
-// repository; no binary or object is committed.  R = a checkout of srsRAN-5G-ER, OUT = this directory:
-//
-//   C=$R/lib/phy/upper/channel_processors; g++ -std=c++17 -O2 -mavx2 -mfma -DNDEBUG -w -I$R/include -I$R/external/fmt/include \
-//     -I$R/external -I$R record_prach_detector_reference.cpp $C/prach_detector_generic_impl.cpp $C/prach_generator_impl.cpp \
-//     $R/lib/phy/generic_functions/dft_processor_generic_impl.cpp $R/lib/ran/prach/prach_preamble_information.cpp \
-//     $R/lib/ran/prach/prach_cyclic_shifts.cpp $R/lib/support/math_utils.cpp $R/lib/srsvec/*.cpp $R/external/fmt/src/format.cc \
-//     $R/external/fmt/src/os.cc -lpthread -o record_prach_detector_reference
-//   ./record_prach_detector_reference prach_detector_configs.json OUT
+// occasion per case with a transmitter of its own, and writes inputs and outputs as .npy files.  Built and run by
+// oracle/recorders.mk, against a checkout of srsRAN-5G-ER and into oracle/_ref/: `make -C oracle recorders`,
+// `make -C oracle rerecord-check`; no binary or object is committed.
 //
 // Cases: the entries of prach_detector_configs.json that the reference's validator accepts (48 of 60; the others are red rows
 // of its threshold table), each carrying its preamble_index delayed by true_delay, its root sequence index reduced modulo
@@ -50,20 +44,14 @@
 #include "lib/phy/upper/channel_processors/prach_detector_generic_impl.h"
 #include "lib/phy/upper/channel_processors/prach_detector_generic_thresholds.h"
 #include "lib/phy/upper/channel_processors/prach_generator_impl.h"
+#include "recorder_io.h"
 #include "srsran/ran/prach/prach_cyclic_shifts.h"
 #include "srsran/ran/prach/prach_preamble_information.h"
 
 #include <algorithm>
 #include <cmath>
 #include <complex>
-#include <cstdio>
-#include <fstream>
-#include <iterator>
 #include <random>
-#include <regex>
-#include <sstream>
-#include <string>
-#include <vector>
 
 using namespace srsran;
 
@@ -163,29 +151,6 @@ const int SEQUENCES[][4] = {
     {A1, 22, 7, 40},   // N_CS 13
 };
 
-template <typename T>
-void write_npy(const std::string& path, const char* descr, const std::vector<T>& data, size_t cols)
-{
-  std::ostringstream shape;
-  if (cols == 0) {
-    shape << "(" << data.size() << ",)";
-  } else {
-    shape << "(" << data.size() / cols << ", " << cols << ")";
-  }
-  std::string header = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape.str() + ", }";
-  while ((10 + header.size() + 1) % 64 != 0) {
-    header += ' ';
-  }
-  header += '\n';
-  std::ofstream  f(path, std::ios::binary);
-  const char     magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
-  const uint16_t len      = (uint16_t)header.size();
-  f.write(magic, 8);
-  f.write((const char*)&len, 2);
-  f.write(header.data(), header.size());
-  f.write((const char*)data.data(), data.size() * sizeof(T));
-}
-
 // Forwards to the reference's transform and keeps every output.
 class idft_recorder : public dft_processor
 {
@@ -279,16 +244,6 @@ std::vector<Window> evaluate(const std::vector<std::vector<cf_t>>& log, const Sh
     }
   }
   return out;
-}
-
-std::string json_field(const std::string& obj, const char* key)
-{
-  std::smatch m;
-  if (!std::regex_search(obj, m, std::regex(std::string("\"") + key + "\": \"?([^\",}]+)"))) {
-    std::fprintf(stderr, "no %s\n", key);
-    std::exit(1);
-  }
-  return m[1];
 }
 
 template <typename T>

@@ -5,23 +5,9 @@
 // channel_equalizer_generic_impl(zf), the type upper_phy_factories.cpp:388 hands to the detector factory --, calls them in the
 // order and with the field mapping of pucch_processor_impl::process (pucch_processor_impl.cpp:29-128: the BWP offset added to
 // both PRBs, beta_pucch 1, estimate dimensions (bwp_start + bwp_size) PRBs x 14 symbols x ports x 1 layer), makes a grid per case
-// with a transmitter of its own, and writes inputs and outputs as four .npy files.  Built and run outside the repository; no
-// binary or object is committed.  R = a checkout of srsRAN-5G-ER, OUT = this directory:
-//
-//   U=$R/lib/phy/upper; g++ -std=c++17 -O2 -mavx2 -mfma -ffp-contract=off -DNDEBUG -w -I$R/include -I$R/external/fmt/include \
-//     -I$R/external -I$R record_pucch_reference.cpp $U/channel_processors/pucch_detector_format0.cpp \
-//     $U/channel_processors/pucch_detector_format1.cpp $U/signal_processors/pucch/dmrs_pucch_processor_format1_impl.cpp \
-//     $U/signal_processors/port_channel_estimator_average_impl.cpp $U/equalization/channel_equalizer_generic_impl.cpp \
-//     $U/sequence_generators/low_papr_sequence_collection_impl.cpp $U/sequence_generators/low_papr_sequence_generator_impl.cpp \
-//     $U/sequence_generators/pseudo_random_generator_impl.cpp \
-//     $R/lib/phy/support/time_alignment_estimator/time_alignment_estimator_dft_impl.cpp \
-//     $R/lib/phy/support/interpolator/interpolator_linear_impl.cpp $R/lib/phy/generic_functions/dft_processor_generic_impl.cpp \
-//     $R/lib/support/math_utils.cpp $R/lib/srsvec/*.cpp $R/external/fmt/src/format.cc $R/external/fmt/src/os.cc -lpthread \
-//     -o record_pucch_reference
-//   ./record_pucch_reference pucch_configs.json OUT
-//
-// -ffp-contract=off: the recording holds what the source says, operation by operation; g++'s default would fuse a * b + c
-// wherever the target has a fused multiply-add.
+// with a transmitter of its own, and writes inputs and outputs as four .npy files.  Built and run by oracle/recorders.mk,
+// against a checkout of srsRAN-5G-ER and into oracle/_ref/: `make -C oracle recorders`, `make -C oracle rerecord-check`; no
+// binary or object is committed.  The recipe says why the build is without fused multiply-adds.
 //
 // Receive ports.  Format 0 is handed the case's port list as it is.  Format 1 is not: pucch_detector_format1 indexes its own
 // buffers, the estimate and the noise variances by the port's *identifier* (pucch_detector_format1.cpp:121 and 193-198) where
@@ -91,22 +77,15 @@
 #include "lib/phy/upper/sequence_generators/pseudo_random_generator_impl.h"
 #include "lib/phy/upper/signal_processors/port_channel_estimator_average_impl.h"
 #include "lib/phy/upper/signal_processors/pucch/dmrs_pucch_processor_format1_impl.h"
-#include "srsran/phy/support/resource_grid_reader.h"
+#include "recorder_grid.h"
 #include "srsran/phy/upper/pucch_orthogonal_sequence.h"
 
 #include <algorithm>
 #include <cmath>
 #include <complex>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
 #include <limits>
 #include <map>
 #include <random>
-#include <regex>
-#include <sstream>
-#include <string>
-#include <vector>
 
 using namespace srsran;
 
@@ -117,103 +96,7 @@ constexpr double   THRESHOLD = 4.0, MARGIN = 0.02;
 const double       NaN = std::numeric_limits<double>::quiet_NaN();
 using cd = std::complex<double>;
 
-template <typename T>
-void write_npy(const std::string& path, const char* descr, const std::vector<T>& data, size_t cols)
-{
-  std::ostringstream shape;
-  if (cols == 0) {
-    shape << "(" << data.size() << ",)";
-  } else {
-    shape << "(" << data.size() / cols << ", " << cols << ")";
-  }
-  std::string header = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape.str() + ", }";
-  while ((10 + header.size() + 1) % 64 != 0) {
-    header += ' ';
-  }
-  header += '\n';
-  std::ofstream  f(path, std::ios::binary);
-  const char     magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
-  const uint16_t len      = (uint16_t)header.size();
-  f.write(magic, 8);
-  f.write((const char*)&len, 2);
-  f.write(header.data(), header.size());
-  f.write((const char*)data.data(), data.size() * sizeof(T));
-}
-
-uint32_t bf16_bits(float v) // nearest, ties to even
-{
-  uint32_t u;
-  std::memcpy(&u, &v, 4);
-  return (u + 0x7FFFU + ((u >> 16) & 1U)) >> 16;
-}
-float bf16_value(uint32_t bits)
-{
-  const uint32_t u = bits << 16;
-  float          v;
-  std::memcpy(&v, &u, 4);
-  return v;
-}
-uint32_t word_of(cbf16_t v)
-{
-  const cf_t c = to_cf(v);
-  return bf16_bits(c.real()) | (bf16_bits(c.imag()) << 16);
-}
-
-// A grid [4][14][624] of cbf16 words behind the reference's reader interface; reader port i is grid port map[i].
-class word_grid : public resource_grid_reader
-{
-public:
-  std::vector<uint32_t> words;
-  std::vector<unsigned> map;
-
-  word_grid() : words(GRID_PORTS * 14 * GRID_SUBC, 0), map({0, 1, 2, 3}) {}
-  uint32_t& word(unsigned grid_port, unsigned l, unsigned k) { return words[(grid_port * 14 + l) * GRID_SUBC + k]; }
-  cf_t      at(unsigned port, unsigned l, unsigned k) const
-  {
-    const uint32_t w = words[(map[port] * 14 + l) * GRID_SUBC + k];
-    return cf_t(bf16_value(w & 0xFFFFU), bf16_value(w >> 16));
-  }
-  unsigned   get_nof_ports() const override { return GRID_PORTS; }
-  unsigned   get_nof_subc() const override { return GRID_SUBC; }
-  unsigned   get_nof_symbols() const override { return 14; }
-  bool       is_empty(unsigned) const override { return false; }
-  bool       is_empty() const override { return false; }
-  span<cf_t> get(span<cf_t> symbols, unsigned port, unsigned l, unsigned k_init, const bounded_bitset<MAX_RB * NRE>& mask) const override
-  {
-    unsigned n = 0;
-    for (unsigned i = 0; i != mask.size(); ++i) {
-      if (mask.test(i)) {
-        symbols[n++] = at(port, l, k_init + i);
-      }
-    }
-    return symbols.last(symbols.size() - n);
-  }
-  span<cbf16_t> get(span<cbf16_t> symbols, unsigned port, unsigned l, unsigned k_init, const bounded_bitset<MAX_RB * NRE>& mask) const override
-  {
-    unsigned n = 0;
-    for (unsigned i = 0; i != mask.size(); ++i) {
-      if (mask.test(i)) {
-        const cf_t v = at(port, l, k_init + i);
-        symbols[n++] = cbf16_t(v.real(), v.imag());
-      }
-    }
-    return symbols.last(symbols.size() - n);
-  }
-  void get(span<cf_t> symbols, unsigned port, unsigned l, unsigned k_init, unsigned stride) const override
-  {
-    for (unsigned i = 0; i != symbols.size(); ++i) {
-      symbols[i] = at(port, l, k_init + stride * i);
-    }
-  }
-  void get(span<cbf16_t> symbols, unsigned port, unsigned l, unsigned k_init) const override
-  {
-    for (unsigned i = 0; i != symbols.size(); ++i) {
-      const cf_t v = at(port, l, k_init + i);
-      symbols[i]   = cbf16_t(v.real(), v.imag());
-    }
-  }
-  span<const cbf16_t> get_view(unsigned, unsigned) const override { return {}; }
-};
+// The grids are word_grid [4][14][624]; for format 1 the reader's port i is grid port ports[i] (word_grid::map).
 
 // Forwards to the reference's time alignment estimator and keeps what it returned, call by call.
 class ta_recorder : public time_alignment_estimator
@@ -279,18 +162,6 @@ int hop_of(const Cfg& c, int off)
   return c.format == 0 ? (off != 0) : (off >= c.ns / 2);
 }
 int grid_prb(const Cfg& c, int off) { return c.bwp_start + (hop_of(c, off) ? c.prb2 : c.prb); }
-
-std::vector<double> epochs(int numerology)
-{
-  std::vector<double> out;
-  double              e = 0.0;
-  for (int l = 0; l != 14; ++l) {
-    const int cp = (144 >> numerology) + ((l == 0 || l == 7 * (1 << numerology)) ? 16 : 0);
-    e += cp * (1 << numerology) / 2048.0 + (l == 0 ? 0.0 : 1.0);
-    out.push_back(e);
-  }
-  return out;
-}
 
 struct Sequences {
   low_papr_sequence_generator_impl                   generator;
@@ -662,28 +533,6 @@ struct Reference {
   }
 };
 
-int json_int(const std::string& obj, const char* key, int none = -1)
-{
-  std::smatch m;
-  if (!std::regex_search(obj, m, std::regex(std::string("\"") + key + "\": (-?[0-9]+|null|true|false)"))) {
-    return none;
-  }
-  const std::string v = m[1];
-  return v == "null" ? none : v == "true" ? 1 : v == "false" ? 0 : std::stoi(v);
-}
-std::vector<int> json_list(const std::string& obj, const char* key)
-{
-  std::smatch      m;
-  std::vector<int> out;
-  if (std::regex_search(obj, m, std::regex(std::string("\"") + key + "\": \\[([0-9, ]*)\\]"))) {
-    std::stringstream s(std::regex_replace(m[1].str(), std::regex(","), " "));
-    for (int v; s >> v;) {
-      out.push_back(v);
-    }
-  }
-  return out;
-}
-
 // {format, numerology, slot, bwp_start, bwp_size, prb, prb2, start, symbols, m0, occ, n_id, ACK bits, SR opportunity}, ports.
 std::vector<Group> small_shapes()
 {
@@ -766,11 +615,11 @@ int main(int argc, char** argv)
     const std::string o  = it->str();
     const int         mu = json_int(o, "numerology");
     Cfg c = {json_int(o, "format"), mu, json_int(o, "slot_count") % (10 << mu), json_int(o, "bwp_start_rb"), json_int(o, "bwp_size_rb"),
-             json_int(o, "starting_prb"), json_int(o, "second_hop_prb"), json_int(o, "start_symbol_index"), json_int(o, "nof_symbols"),
+             json_int(o, "starting_prb"), json_int(o, "second_hop_prb", -1), json_int(o, "start_symbol_index"), json_int(o, "nof_symbols"),
              json_int(o, "initial_cyclic_shift"), json_int(o, "time_domain_occ", 0), json_int(o, "n_id"), json_int(o, "nof_harq_ack"),
              json_int(o, "sr_opportunity", 0), json_list(o, "ports")};
     const std::vector<int> ack = json_list(o, "ack_bits");
-    const Entry e = {c, (ack.size() > 0 ? ack[0] : 0) + (ack.size() > 1 ? 2 * ack[1] : 0), json_int(o, "sr"), index};
+    const Entry e = {c, (ack.size() > 0 ? ack[0] : 0) + (ack.size() > 1 ? 2 * ack[1] : 0), json_int(o, "sr", -1), index};
     if (c.format == 1) {
       const int id = json_int(o, "case");
       if (by_case.count(id)) {
@@ -843,7 +692,7 @@ int main(int argc, char** argv)
       }
     }
     const std::vector<double> ep = epochs(c.numerology);
-    word_grid                 grid;
+    word_grid                 grid(GRID_PORTS, GRID_SUBC);
     std::vector<Result>       res;
     unsigned                  draws = 0;
     bool                      fragile;
@@ -904,7 +753,7 @@ int main(int argc, char** argv)
         for (int off = 0; off != c.ns; ++off) {
           for (int n = 0; n != 12; ++n) {
             const cd v = acc[(p * 14 + off) * 12 + n] + sigma * cd(normal(rng), normal(rng));
-            grid.word(p, c.start + off, 12 * grid_prb(c, off) + n) = bf16_bits((float)v.real()) | (bf16_bits((float)v.imag()) << 16);
+            grid.set(p, c.start + off, 12 * grid_prb(c, off) + n, (float)v.real(), (float)v.imag());
           }
         }
       }

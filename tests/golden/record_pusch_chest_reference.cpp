@@ -2,20 +2,10 @@
 // dmrs_pusch_estimator_impl over port_channel_estimator_average_impl as signal_processor_factories.cpp does for PUSCH (`filter`
 // smoothing, compensate_cfo = true), with interpolator_linear_impl and time_alignment_estimator_dft_impl over a 4096-point inverse
 // dft_processor_generic_impl, makes a grid per case with a transmitter of its own, and writes inputs and outputs as one .json and
-// four .npy files.  DM-RS type 1, one or two layers: what nrphy_pusch_chest_run supports.  Built and run outside the repository;
-// no binary or object is committed.  R = a checkout of srsRAN-5G-ER, OUT = this directory:
-//
-//   U=$R/lib/phy/upper; g++ -std=c++17 -O2 -mavx2 -mfma -ffp-contract=off -DNDEBUG -w -I$R/include -I$R/external/fmt/include \
-//     -I$R/external -I$R record_pusch_chest_reference.cpp $U/signal_processors/dmrs_pusch_estimator_impl.cpp \
-//     $U/signal_processors/port_channel_estimator_average_impl.cpp $U/sequence_generators/pseudo_random_generator_impl.cpp \
-//     $R/lib/phy/support/time_alignment_estimator/time_alignment_estimator_dft_impl.cpp \
-//     $R/lib/phy/support/interpolator/interpolator_linear_impl.cpp $R/lib/phy/generic_functions/dft_processor_generic_impl.cpp \
-//     $R/lib/support/math_utils.cpp $R/lib/srsvec/*.cpp $R/external/fmt/src/format.cc $R/external/fmt/src/os.cc -lpthread \
-//     -o record_pusch_chest_reference
-//   ./record_pusch_chest_reference pusch_chest_configs.json OUT
-//
-// The flags are those of record_pusch_processor_reference.cpp, so both recordings describe one build of the reference.
-// -ffp-contract=off: the recording holds what the source says, operation by operation.
+// four .npy files.  DM-RS type 1, one or two layers: what nrphy_pusch_chest_run supports.  Built and run by
+// oracle/recorders.mk, against a checkout of srsRAN-5G-ER and into oracle/_ref/: `make -C oracle recorders`,
+// `make -C oracle rerecord-check`; no binary or object is committed.  The flags are those of the archive
+// record_pusch_processor_reference.cpp links, so both recordings describe one build of the reference.
 //
 // The estimator is handed two forwarding objects.  The forwarding interpolator keeps its float32 input per (port, layer): the
 // smoothed pilots, after LS, CFO derotation, averaging, virtual pilots and the FIR and before any bf16 rounding.  The forwarding
@@ -71,22 +61,15 @@
 #include "lib/phy/upper/sequence_generators/pseudo_random_generator_impl.h"
 #include "lib/phy/upper/signal_processors/dmrs_pusch_estimator_impl.h"
 #include "lib/phy/upper/signal_processors/port_channel_estimator_average_impl.h"
-#include "srsran/phy/support/resource_grid_reader.h"
+#include "recorder_grid.h"
 // (needs MAX_RB and the generator's interface from the headers above)
 #include "lib/phy/upper/signal_processors/dmrs_helper.h"
 
 #include <algorithm>
 #include <cmath>
 #include <complex>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
 #include <limits>
 #include <random>
-#include <regex>
-#include <sstream>
-#include <string>
-#include <vector>
 
 using namespace srsran;
 
@@ -96,104 +79,6 @@ constexpr double MARGIN = 0.02;
 constexpr int    TA_WINDOW = 144, DFT = 4096;
 const double     NaN = std::numeric_limits<double>::quiet_NaN();
 using cd = std::complex<double>;
-
-template <typename T>
-void write_npy(const std::string& path, const char* descr, const std::vector<T>& data, size_t cols)
-{
-  std::ostringstream shape;
-  if (cols == 0) {
-    shape << "(" << data.size() << ",)";
-  } else {
-    shape << "(" << data.size() / cols << ", " << cols << ")";
-  }
-  std::string header = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape.str() + ", }";
-  while ((10 + header.size() + 1) % 64 != 0) {
-    header += ' ';
-  }
-  header += '\n';
-  std::ofstream  f(path, std::ios::binary);
-  const char     magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
-  const uint16_t len      = (uint16_t)header.size();
-  f.write(magic, 8);
-  f.write((const char*)&len, 2);
-  f.write(header.data(), header.size());
-  f.write((const char*)data.data(), data.size() * sizeof(T));
-}
-
-uint32_t bf16_bits(float v) // nearest, ties to even
-{
-  uint32_t u;
-  std::memcpy(&u, &v, 4);
-  return (u + 0x7FFFU + ((u >> 16) & 1U)) >> 16;
-}
-float bf16_value(uint32_t bits)
-{
-  const uint32_t u = bits << 16;
-  float          v;
-  std::memcpy(&v, &u, 4);
-  return v;
-}
-uint32_t word_of(cbf16_t v)
-{
-  const cf_t c = to_cf(v);
-  return bf16_bits(c.real()) | (bf16_bits(c.imag()) << 16);
-}
-
-// A grid [ports][14][subc] of cbf16 words behind the reference's reader interface.
-class word_grid : public resource_grid_reader
-{
-public:
-  unsigned              ports, subc;
-  std::vector<uint32_t> words;
-
-  word_grid(unsigned ports_, unsigned subc_) : ports(ports_), subc(subc_), words(ports_ * 14 * subc_, 0) {}
-  uint32_t& word(unsigned port, unsigned l, unsigned k) { return words[(port * 14 + l) * subc + k]; }
-  cf_t      at(unsigned port, unsigned l, unsigned k) const
-  {
-    const uint32_t w = words[(port * 14 + l) * subc + k];
-    return cf_t(bf16_value(w & 0xFFFFU), bf16_value(w >> 16));
-  }
-  unsigned   get_nof_ports() const override { return ports; }
-  unsigned   get_nof_subc() const override { return subc; }
-  unsigned   get_nof_symbols() const override { return 14; }
-  bool       is_empty(unsigned) const override { return false; }
-  bool       is_empty() const override { return false; }
-  span<cf_t> get(span<cf_t> symbols, unsigned port, unsigned l, unsigned k_init, const bounded_bitset<MAX_RB * NRE>& mask) const override
-  {
-    unsigned n = 0;
-    for (unsigned i = 0; i != mask.size(); ++i) {
-      if (mask.test(i)) {
-        symbols[n++] = at(port, l, k_init + i);
-      }
-    }
-    return symbols.last(symbols.size() - n);
-  }
-  span<cbf16_t> get(span<cbf16_t> symbols, unsigned port, unsigned l, unsigned k_init, const bounded_bitset<MAX_RB * NRE>& mask) const override
-  {
-    unsigned n = 0;
-    for (unsigned i = 0; i != mask.size(); ++i) {
-      if (mask.test(i)) {
-        const cf_t v = at(port, l, k_init + i);
-        symbols[n++] = cbf16_t(v.real(), v.imag());
-      }
-    }
-    return symbols.last(symbols.size() - n);
-  }
-  void get(span<cf_t> symbols, unsigned port, unsigned l, unsigned k_init, unsigned stride) const override
-  {
-    for (unsigned i = 0; i != symbols.size(); ++i) {
-      symbols[i] = at(port, l, k_init + stride * i);
-    }
-  }
-  void get(span<cbf16_t> symbols, unsigned port, unsigned l, unsigned k_init) const override
-  {
-    for (unsigned i = 0; i != symbols.size(); ++i) {
-      const cf_t v = at(port, l, k_init + i);
-      symbols[i]   = cbf16_t(v.real(), v.imag());
-    }
-  }
-  span<const cbf16_t> get_view(unsigned, unsigned) const override { return {}; }
-};
 
 // Forwards to the reference's interpolator and keeps the input of every call.
 class interpolator_recorder : public interpolator
@@ -266,33 +151,12 @@ struct Case {
   int              source;
 };
 
-std::vector<int> range(int a, int b)
-{
-  std::vector<int> out;
-  for (int i = a; i != b; ++i) {
-    out.push_back(i);
-  }
-  return out;
-}
-
-std::vector<double> epochs(int numerology)
-{
-  std::vector<double> out;
-  double              e = 0.0;
-  for (int l = 0; l != 14; ++l) {
-    const int cp = (144 >> numerology) + ((l == 0 || l == 7 * (1 << numerology)) ? 16 : 0);
-    e += cp * (1 << numerology) / 2048.0 + (l == 0 ? 0.0 : 1.0);
-    out.push_back(e);
-  }
-  return out;
-}
-
 // name, numerology, slot, scrambling id, n_scid, beta, DM-RS symbols, first symbol, symbols, layers, rx ports, PRBs, grid PRBs, UE,
 // SNR, delay, CFO.
 std::vector<Case> small_shapes()
 {
   const float      b3 = 1.4125F;
-  std::vector<int> ranges = range(3, 9), more = range(15, 40);
+  std::vector<int> ranges = range(3, 6), more = range(15, 25); // range(first, count): PRBs 3-8 and 15-39
   ranges.insert(ranges.end(), more.begin(), more.end());
   ranges.push_back(51);
   std::vector<Case> c = {
@@ -305,12 +169,12 @@ std::vector<Case> small_shapes()
       // 15 taps, 7 virtual pilots; the third symbol derotated with the measured CFO
       {"3 PRB, 3 DM-RS", 0, 2, 600, 0, 1.0F, {2, 7, 11}, 0, 14, 1, {0}, {20, 21, 22}, 52, 1, 20, -2, 250, -1},
       // the epochs of numerology 1; a window that does not start at symbol 0
-      {"4 PRB, 4 DM-RS, mu 1, n_scid 1, window 1..13", 1, 13, 77, 1, 1.0F, {2, 5, 8, 11}, 1, 13, 1, {0}, range(30, 34), 52, 1, 20, 3, -300, -1},
+      {"4 PRB, 4 DM-RS, mu 1, n_scid 1, window 1..13", 1, 13, 77, 1, 1.0F, {2, 5, 8, 11}, 1, 13, 1, {0}, range(30, 4), 52, 1, 20, 3, -300, -1},
       {"24 PRB, 1 DM-RS at symbol 5, window of 3", 0, 5, 9, 0, 1.0F, {5}, 4, 3, 1, {0}, range(0, 24), 52, 1, 20, 0, 150, -1},
       // 258 pilots: the first count above a stride of 256 threads
-      {"43 PRB, 2 layers, 2 ports", 0, 3, 500, 1, b3, {2, 11}, 0, 14, 2, {0, 1}, range(4, 47), 52, 1, 20, 3, 150, -1},
+      {"43 PRB, 2 layers, 2 ports", 0, 3, 500, 1, b3, {2, 11}, 0, 14, 2, {0, 1}, range(4, 43), 52, 1, 20, 3, 150, -1},
       // more than two strides
-      {"86 PRB, 1 layer", 0, 6, 1001, 0, 1.0F, {2, 7, 11}, 0, 14, 1, {0}, range(10, 96), 106, 1, 20, -1, -100, -1},
+      {"86 PRB, 1 layer", 0, 6, 1001, 0, 1.0F, {2, 7, 11}, 0, 14, 1, {0}, range(10, 86), 106, 1, 20, -1, -100, -1},
       // scatter of non-contiguous PRBs; the time alignment sums over the gaps
       {"PRBs 0, 2, 4, 6, 8", 0, 7, 45, 1, 1.0F, {3, 7, 10}, 2, 12, 1, {1}, {0, 2, 4, 6, 8}, 52, 1, 20, 2, 200, -1},
       {"PRBs 3-8, 15-39, 51, ports (3, 1, 0, 2), 2 layers", 0, 8, 123, 0, b3, {2, 5, 8, 11}, 0, 14, 2, {3, 1, 0, 2}, ranges, 52, 1, 20, 1, -150, -1},
@@ -318,53 +182,18 @@ std::vector<Case> small_shapes()
       {"273 PRB, 1 port, 1 layer, 2 DM-RS", 0, 9, 1001, 0, 1.0F, {2, 11}, 0, 14, 1, {0}, range(0, 273), 273, 1, 20, 3, 150, -1},
   };
   for (int d : {-40, -3, 3, 40}) { // both halves of the time alignment window
-    c.push_back({"25 PRB, delay " + std::to_string(d), 0, 2, 64, 0, 1.0F, {2, 11}, 0, 14, 1, {0}, range(13, 38), 52, 1, 20, (double)d, 100, -1});
+    c.push_back({"25 PRB, delay " + std::to_string(d), 0, 2, 64, 0, 1.0F, {2, 11}, 0, 14, 1, {0}, range(13, 25), 52, 1, 20, (double)d, 100, -1});
   }
-  c.push_back({"25 PRB at 0 dB", 0, 3, 64, 0, 1.0F, {2, 11}, 0, 14, 1, {0}, range(13, 38), 52, 1, 0, 2, -100, -1});
-  c.push_back({"25 PRB at 40 dB", 0, 4, 64, 0, 1.0F, {2, 11}, 0, 14, 1, {0}, range(13, 38), 52, 1, 40, 2, -100, -1});
-  c.push_back({"25 PRB, noise only", 0, 5, 64, 0, 1.0F, {2, 11}, 0, 14, 1, {0}, range(13, 38), 52, 0, 0, 0, 0, -1});
+  c.push_back({"25 PRB at 0 dB", 0, 3, 64, 0, 1.0F, {2, 11}, 0, 14, 1, {0}, range(13, 25), 52, 1, 0, 2, -100, -1});
+  c.push_back({"25 PRB at 40 dB", 0, 4, 64, 0, 1.0F, {2, 11}, 0, 14, 1, {0}, range(13, 25), 52, 1, 40, 2, -100, -1});
+  c.push_back({"25 PRB, noise only", 0, 5, 64, 0, 1.0F, {2, 11}, 0, 14, 1, {0}, range(13, 25), 52, 0, 0, 0, 0, -1});
   return c;
 }
 
-int json_int(const std::string& obj, const char* key)
+// pusch_chest_configs.json is written with an indent: its lists hold line breaks.
+std::vector<int> json_lines(const std::string& obj, const char* key)
 {
-  std::smatch m;
-  if (!std::regex_search(obj, m, std::regex(std::string("\"") + key + "\": (-?[0-9]+)"))) {
-    std::fprintf(stderr, "no %s\n", key);
-    std::exit(1);
-  }
-  return std::stoi(m[1]);
-}
-double json_float(const std::string& obj, const char* key)
-{
-  std::smatch m;
-  if (!std::regex_search(obj, m, std::regex(std::string("\"") + key + "\": (-?[0-9.eE+-]+)"))) {
-    std::fprintf(stderr, "no %s\n", key);
-    std::exit(1);
-  }
-  return std::stod(m[1]);
-}
-std::vector<int> json_list(const std::string& obj, const char* key)
-{
-  std::smatch      m;
-  std::vector<int> out;
-  if (std::regex_search(obj, m, std::regex(std::string("\"") + key + "\": \\[([0-9, \n]*)\\]"))) {
-    std::stringstream s(std::regex_replace(m[1].str(), std::regex(","), " "));
-    for (int v; s >> v;) {
-      out.push_back(v);
-    }
-  }
-  return out;
-}
-std::string json_of(const std::vector<int>& v)
-{
-  std::ostringstream s;
-  s << "[";
-  for (size_t i = 0; i != v.size(); ++i) {
-    s << (i ? ", " : "") << v[i];
-  }
-  s << "]";
-  return s.str();
+  return json_list(obj, key, "0-9, \n");
 }
 
 struct PathResult {
@@ -474,14 +303,14 @@ int main(int argc, char** argv)
         continue;
       }
       const int        i    = parity++; // its index in parity_cases() of the test file
-      std::vector<int> prbs = json_list(o, "rb_mask");
+      std::vector<int> prbs = json_lines(o, "rb_mask");
       if (prbs.size() > 111) {
         continue;
       }
       cases.push_back({"configuration " + std::to_string(index) + ", " + std::to_string(prbs.size()) + " PRB", json_int(o, "numerology"),
                        json_int(o, "slot_index"), json_int(o, "scrambling_id"), json_int(o, "n_scid"), (float)json_float(o, "scaling"),
-                       json_list(o, "dmrs_symbols"), json_int(o, "first_symbol"), json_int(o, "nof_symbols"), json_int(o, "nof_tx_layers"),
-                       json_list(o, "rx_ports"), prbs, json_int(o, "nof_rb"), 1, 15.0 + 5 * (i % 3), (double)(i % 5) - 2.0,
+                       json_lines(o, "dmrs_symbols"), json_int(o, "first_symbol"), json_int(o, "nof_symbols"), json_int(o, "nof_tx_layers"),
+                       json_lines(o, "rx_ports"), prbs, json_int(o, "nof_rb"), 1, 15.0 + 5 * (i % 3), (double)(i % 5) - 2.0,
                        100.0 * ((i % 7) - 3), index});
     }
   }
@@ -546,7 +375,7 @@ int main(int argc, char** argv)
           const cd rot = std::polar(1.0, 2 * M_PI * (c.cfo_hz / scs) * ep[c.dmrs[dd]]);
           for (unsigned j = 0; j != 12 * nprb; ++j) {
             const cd v = acc[dd * 12 * nprb + j] * rot + sigma * cd(normal(rng), normal(rng));
-            grid.word(p, c.dmrs[dd], subc[j]) = bf16_bits((float)v.real()) | (bf16_bits((float)v.imag()) << 16);
+            grid.set(p, c.dmrs[dd], subc[j], (float)v.real(), (float)v.imag());
           }
         }
       }
@@ -658,9 +487,9 @@ int main(int argc, char** argv)
     char num[128];
     std::snprintf(num, sizeof(num), "\"scaling\": %.9g, \"snr_db\": %.17g, \"delay\": %.17g, \"cfo_hz\": %.17g", (double)c.scaling, c.snr_db, delay, c.cfo_hz);
     json << (ic ? ",\n" : "") << "{\"name\": \"" << c.name << "\", \"numerology\": " << c.numerology << ", \"slot_index\": " << c.slot
-         << ", \"scrambling_id\": " << c.scrambling_id << ", \"n_scid\": " << c.n_scid << ", " << num << ", \"dmrs_symbols\": " << json_of(c.dmrs)
+         << ", \"scrambling_id\": " << c.scrambling_id << ", \"n_scid\": " << c.n_scid << ", " << num << ", \"dmrs_symbols\": " << list_json(c.dmrs)
          << ", \"first_symbol\": " << c.start << ", \"nof_symbols\": " << c.ns << ", \"nof_tx_layers\": " << c.layers
-         << ", \"rx_ports\": " << json_of(c.ports) << ", \"prbs\": " << json_of(c.prbs) << ", \"grid_prb\": " << c.grid_prb << ", \"ue\": " << c.ue
+         << ", \"rx_ports\": " << list_json(c.ports) << ", \"prbs\": " << list_json(c.prbs) << ", \"grid_prb\": " << c.grid_prb << ", \"ue\": " << c.ue
          << ", \"source\": " << c.source << ", \"draws\": " << draws << ", \"grid_off\": " << grid_off << ", \"pilot_off\": " << pilot_off
          << ", \"est_off\": " << est_off << ", \"res_row\": " << res_row << "}";
     std::printf("case %2zu: %u draws, lead asked %.3g  %s\n", ic, draws, asked, c.name.c_str());

@@ -4,23 +4,10 @@
 // SINR on), the UL-SCH demultiplexer, the UCI decoder (short block detector, polar, CRC) and the software PUSCH decoder (AVX2 LDPC
 // decoder and rate dematcher, 10 iterations with early stop) --, reads the received grids the test's transmitter wrote
 // (`python tests/test_pusch_processor.py DIR` on a GPU: DIR/inputs_grids.npy, DIR/inputs_cases.txt) and writes one .json and four
-// .npy files.  Built and run outside the repository; no binary or object is committed.  R = a checkout of srsRAN-5G-ER, OUT = this
-// directory:
-//
-//   F="-std=c++17 -O2 -ffp-contract=off -DNDEBUG -w -I$R/include -I$R/external/fmt/include -I$R/external -I$R"
-//   for every .cpp under $R/lib/{phy/upper,phy/support,phy/generic_functions,srsvec,srslog,ran,support} except *neon*, *fftw*,
-//   generic_functions_factories.cpp and what needs further libraries (lib/support/{network,build_info,version,config_yaml}), and
-//   $R/external/fmt/src/{format,os}.cc:
-//     g++ $F -mavx2 -mfma -c FILE -o OBJ      -- but channel_equalizer_generic_impl.cpp WITHOUT -mavx2 -mfma, and the *avx512*
-//     files and crc_calculator_clmul_impl.cpp, which the factories name but this program never selects, with
-//     -mavx512f -mavx512bw -mavx512vl -mavx512dq -mavx512vbmi -mpclmul -msse4.1 added
-//   ar rcs libref.a OBJ...
-//   g++ $F -mavx2 -mfma record_pusch_processor_reference.cpp libref.a -lpthread -o record_pusch_processor_reference
-//   ./record_pusch_processor_reference DIR OUT
-//
-// -ffp-contract=off and the equaliser without -mavx2: as tests/golden/record_pusch_tp_reference.cpp explains (the library's equaliser
-// is pinned to the reference's scalar loops with exact division).  Everything else is the AVX2 build.  The DFT factory is this
-// program's own three lines over dft_processor_generic_impl, because the reference's factory file needs FFTW's header.
+// .npy files.  Built and run by oracle/recorders.mk, against a checkout of srsRAN-5G-ER and into oracle/_ref/, from an archive of
+// the reference's library sources: `make -C oracle recorders`, `make -C oracle rerecord-check PUSCH_PROC_INPUTS=DIR`; no binary or
+// object is committed.  The recipe says why the build is without fused multiply-adds and why the equaliser alone is compiled
+// without AVX2; recorder_pusch_processor.h holds the processor and why its DFT factory is the recorders' own.
 //
 // Receive ports: as in record_pusch_tp_reference.cpp the reference is handed the list 0 .. n - 1 and a grid whose port i holds what
 // receive port i reads.  The grid is 25 PRB wide and zero outside the PDU's allocation, as the test's.
@@ -34,184 +21,11 @@
 //                                     rsrp_dB, time_alignment_s, has_cfo, cfo_hz, has_sch
 //   pusch_proc_reference_tb.npy       uint8: the transport block the decoder delivered (tb_size_bytes per case with a codeword)
 //   pusch_proc_reference_uci.npy      uint8: HARQ-ACK then CSI part 1 payload bits, one per byte
-#include "lib/phy/generic_functions/dft_processor_generic_impl.h"
-#include "srsran/phy/generic_functions/generic_functions_factories.h"
-#include "srsran/phy/generic_functions/transform_precoding/transform_precoding_factories.h"
-#include "srsran/phy/support/resource_grid_reader.h"
-#include "srsran/phy/support/time_alignment_estimator/time_alignment_estimator_factories.h"
-#include "srsran/phy/upper/channel_coding/channel_coding_factories.h"
-#include "srsran/phy/upper/channel_modulation/channel_modulation_factories.h"
-#include "srsran/phy/upper/channel_processors/pusch/factories.h"
-#include "srsran/phy/upper/channel_processors/pusch/pusch_processor_result_notifier.h"
-#include "srsran/phy/upper/channel_processors/uci/factories.h"
-#include "srsran/phy/upper/equalization/equalization_factories.h"
-#include "srsran/phy/upper/rx_buffer_pool.h"
-#include "srsran/phy/upper/sequence_generators/sequence_generator_factories.h"
-#include "srsran/phy/upper/signal_processors/signal_processor_factories.h"
-#include "srsran/phy/upper/unique_rx_buffer.h"
-
-#include <cstdio>
-#include <cstring>
-#include <fstream>
-#include <sstream>
-#include <string>
-#include <vector>
+#include "recorder_pusch_processor.h"
 
 using namespace srsran;
 
-namespace {
-
-constexpr unsigned NPRB_GRID = 25, NSUBC = 12 * NPRB_GRID, NOF_RESULT = 12;
-
-template <typename T>
-void write_npy(const std::string& path, const char* descr, const std::vector<T>& data, size_t cols)
-{
-  std::ostringstream shape;
-  if (cols == 0) {
-    shape << "(" << data.size() << ",)";
-  } else {
-    shape << "(" << data.size() / cols << ", " << cols << ")";
-  }
-  std::string header = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape.str() + ", }";
-  while ((10 + header.size() + 1) % 64 != 0) {
-    header += ' ';
-  }
-  header += '\n';
-  std::ofstream  f(path, std::ios::binary);
-  const char     magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
-  const uint16_t len      = (uint16_t)header.size();
-  f.write(magic, 8);
-  f.write((const char*)&len, 2);
-  f.write(header.data(), header.size());
-  f.write((const char*)data.data(), data.size() * sizeof(T));
-}
-
-std::vector<uint32_t> read_npy_u32(const std::string& path)
-{
-  std::ifstream f(path, std::ios::binary);
-  char          head[10];
-  f.read(head, 10);
-  const unsigned len = (unsigned char)head[8] | ((unsigned char)head[9] << 8);
-  f.seekg(10 + len);
-  std::vector<char>     bytes((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
-  std::vector<uint32_t> out(bytes.size() / 4);
-  std::memcpy(out.data(), bytes.data(), out.size() * 4);
-  return out;
-}
-
-cbf16_t cbf16_of(uint32_t w)
-{
-  uint32_t lo = w << 16, hi = w & 0xFFFF0000U;
-  float    re, im;
-  std::memcpy(&re, &lo, 4);
-  std::memcpy(&im, &hi, 4);
-  return cbf16_t(re, im); // exact: the halves are bf16 values
-}
-
-// A grid [ports][14][NSUBC] of cbf16 behind the reference's reader interface.
-class word_grid : public resource_grid_reader
-{
-public:
-  unsigned             ports;
-  std::vector<cbf16_t> re;
-
-  explicit word_grid(unsigned ports_) : ports(ports_), re(ports_ * 14 * NSUBC) {}
-  cbf16_t&   at(unsigned port, unsigned l, unsigned k) { return re[(port * 14 + l) * NSUBC + k]; }
-  unsigned   get_nof_ports() const override { return ports; }
-  unsigned   get_nof_subc() const override { return NSUBC; }
-  unsigned   get_nof_symbols() const override { return 14; }
-  bool       is_empty(unsigned) const override { return false; }
-  bool       is_empty() const override { return false; }
-  span<cf_t> get(span<cf_t> symbols, unsigned port, unsigned l, unsigned k_init, const bounded_bitset<MAX_RB * NRE>& mask) const override
-  {
-    unsigned n = 0;
-    mask.for_each(0, mask.size(), [&](unsigned k) { symbols[n++] = to_cf(re[(port * 14 + l) * NSUBC + k_init + k]); });
-    return symbols.last(symbols.size() - n);
-  }
-  span<cbf16_t> get(span<cbf16_t> symbols, unsigned port, unsigned l, unsigned k_init, const bounded_bitset<MAX_RB * NRE>& mask) const override
-  {
-    unsigned n = 0;
-    mask.for_each(0, mask.size(), [&](unsigned k) { symbols[n++] = re[(port * 14 + l) * NSUBC + k_init + k]; });
-    return symbols.last(symbols.size() - n);
-  }
-  void get(span<cf_t> symbols, unsigned port, unsigned l, unsigned k_init, unsigned stride) const override
-  {
-    for (unsigned k = 0; k != symbols.size(); ++k) {
-      symbols[k] = to_cf(re[(port * 14 + l) * NSUBC + k_init + k * stride]);
-    }
-  }
-  void get(span<cbf16_t> symbols, unsigned port, unsigned l, unsigned k_init) const override
-  {
-    for (unsigned k = 0; k != symbols.size(); ++k) {
-      symbols[k] = re[(port * 14 + l) * NSUBC + k_init + k];
-    }
-  }
-  span<const cbf16_t> get_view(unsigned port, unsigned l) const override
-  {
-    return span<const cbf16_t>(re).subspan((port * 14 + l) * NSUBC, NSUBC);
-  }
-};
-
-class dft_factory : public dft_processor_factory
-{
-public:
-  std::unique_ptr<dft_processor> create(const dft_processor::configuration& config) override
-  {
-    auto dft = std::make_unique<dft_processor_generic_impl>(config);
-    return dft->is_valid() ? std::move(dft) : nullptr;
-  }
-};
-
-struct Answer : public pusch_processor_result_notifier {
-  bool                           has_sch = false, has_uci = false;
-  pusch_processor_result_data    sch;
-  pusch_processor_result_control uci;
-  void on_uci(const pusch_processor_result_control& u) override
-  {
-    uci     = u;
-    has_uci = true;
-  }
-  void on_sch(const pusch_processor_result_data& s) override
-  {
-    sch     = s;
-    has_sch = true;
-  }
-};
-
-std::unique_ptr<pusch_processor> make_processor(channel_equalizer_algorithm_type eq, channel_state_information::sinr_type sinr)
-{
-  auto prg     = create_pseudo_random_generator_sw_factory();
-  auto dft     = std::make_shared<dft_factory>();
-  auto ta      = create_time_alignment_estimator_dft_factory(dft);
-  auto port    = create_port_channel_estimator_factory_sw(ta);
-  auto crc     = create_crc_calculator_factory_sw("lut");
-  auto dec_cfg = pusch_decoder_factory_sw_configuration{};
-  dec_cfg.crc_factory       = crc;
-  dec_cfg.decoder_factory   = create_ldpc_decoder_factory_sw("avx2");
-  dec_cfg.dematcher_factory = create_ldpc_rate_dematcher_factory_sw("avx2");
-  dec_cfg.segmenter_factory = create_ldpc_segmenter_rx_factory_sw();
-  dec_cfg.nof_prb           = NPRB_GRID;
-  dec_cfg.nof_layers        = 2;
-  pusch_processor_factory_sw_configuration cfg;
-  cfg.estimator_factory   = create_dmrs_pusch_estimator_factory_sw(prg, port);
-  cfg.demodulator_factory = create_pusch_demodulator_factory_sw(create_channel_equalizer_generic_factory(eq),
-                                                                create_dft_transform_precoder_factory(dft, NPRB_GRID),
-                                                                create_channel_modulation_sw_factory(), prg, NPRB_GRID, false, true);
-  cfg.demux_factory       = create_ulsch_demultiplex_factory_sw();
-  cfg.decoder_factory     = create_pusch_decoder_factory_sw(dec_cfg);
-  cfg.uci_dec_factory     = create_uci_decoder_factory_generic(create_short_block_detector_factory_sw(), create_polar_factory_sw(), crc);
-  cfg.ch_estimate_dimensions.nof_prb       = NPRB_GRID;
-  cfg.ch_estimate_dimensions.nof_symbols   = 14;
-  cfg.ch_estimate_dimensions.nof_rx_ports  = 4;
-  cfg.ch_estimate_dimensions.nof_tx_layers = 2;
-  cfg.dec_nof_iterations                   = 10;
-  cfg.dec_enable_early_stop                = true;
-  cfg.max_nof_concurrent_threads           = 1;
-  cfg.csi_sinr_calc_method                 = sinr;
-  return create_pusch_processor_factory_sw(cfg)->create();
-}
-
-} // namespace
+constexpr unsigned NOF_RESULT = 12;
 
 int main(int argc, char** argv)
 {
@@ -222,13 +36,7 @@ int main(int argc, char** argv)
   const std::string           in = argv[1], out = argv[2];
   const std::vector<uint32_t> grids = read_npy_u32(in + "/inputs_grids.npy");
   std::ifstream               cases(in + "/inputs_cases.txt");
-  rx_buffer_pool_config       pool_cfg;
-  pool_cfg.max_codeblock_size   = ldpc::MAX_CODEBLOCK_SIZE;
-  pool_cfg.nof_buffers          = 64;
-  pool_cfg.nof_codeblocks       = 256;
-  pool_cfg.expire_timeout_slots = 1000;
-  pool_cfg.external_soft_bits   = false;
-  auto pool = create_rx_buffer_pool(pool_cfg);
+  auto                        pool = make_rx_buffer_pool();
 
   std::vector<double>  results;
   std::vector<uint8_t> tbs, ucis;
@@ -251,14 +59,7 @@ int main(int argc, char** argv)
         has_codeword >> rv >> bg >> new_data >> tb_bytes >> lbrm >> nharq >> ncsi1 >> alpha >> beta_harq >> beta_csi1 >> beta_csi2 >> start >>
         nsym >> dmrs_mask >> layers >> ports >> dc >> prb_start >> prb_count >> equalizer >> grid_off;
 
-    word_grid grid(ports);
-    for (unsigned p = 0; p != ports; ++p) {
-      for (unsigned l = 0; l != 14; ++l) {
-        for (unsigned k = 0; k != 12 * prb_count; ++k) {
-          grid.at(p, l, 12 * prb_start + k) = cbf16_of(grids[grid_off + (p * 14 + l) * 12 * prb_count + k]);
-        }
-      }
-    }
+    const word_grid        grid = grid_of(grids, grid_off, ports, prb_start, prb_count);
     pusch_processor::pdu_t pdu;
     pdu.slot         = slot_point(numerology, slot_index);
     pdu.rnti         = rnti;

@@ -4,25 +4,9 @@
 // transform_precoder_dft_impl over a dft_processor of this program's own: the direct sum in double, rounded once to float (the
 // reference's deprecoder needs a dft_processor for sizes its generic implementation does not have; its unit test uses FFTW) --,
 // makes a grid and an estimate per case with a transmitter and channel of its own, and writes inputs and outputs as one .json and
-// six .npy files.  Built and run outside the repository; no binary or object is committed.  R = a checkout of srsRAN-5G-ER, OUT =
-// this directory:
-//
-//   U=$R/lib/phy/upper; F="-std=c++17 -O2 -ffp-contract=off -DNDEBUG -w -I$R/include -I$R/external/fmt/include -I$R/external -I$R"
-//   g++ $F -c $U/equalization/channel_equalizer_generic_impl.cpp -o equalizer_scalar.o
-//   g++ $F -mavx2 -mfma record_pusch_tp_reference.cpp equalizer_scalar.o $U/channel_processors/pusch/pusch_demodulator_impl.cpp \
-//     $U/channel_modulation/demodulation_mapper_impl.cpp \
-//     $U/channel_modulation/demodulation_mapper_qpsk.cpp $U/channel_modulation/demodulation_mapper_qam16.cpp \
-//     $U/channel_modulation/demodulation_mapper_qam64.cpp $U/channel_modulation/demodulation_mapper_qam256.cpp \
-//     $U/sequence_generators/pseudo_random_generator_impl.cpp $U/log_likelihood_ratio.cpp \
-//     $R/lib/phy/generic_functions/transform_precoding/transform_precoder_dft_impl.cpp $R/lib/support/math_utils.cpp \
-//     $R/lib/srsvec/*.cpp $R/external/fmt/src/format.cc $R/external/fmt/src/os.cc -lpthread -o record_pusch_tp_reference
-//   ./record_pusch_tp_reference pusch_demodulator_configs.json OUT
-//
-// -ffp-contract=off: the recording holds what the source says, operation by operation; g++'s default would fuse a * b + c
-// wherever the target has a fused multiply-add.  The equaliser is compiled on its own without -mavx2: the library's equaliser is
-// pinned to the reference's scalar loops with exact division (include/mi355_nrphy.h, nrphy_channel_equalize), and under
-// __AVX2__ equalize_zf_1xn.h:65-126 and equalize_zf_2xn.h:79-179 replace them, for the first floor(n / 8) * 8 RE, by a form with
-// an approximate reciprocal (srsran_simd_f_rcp, about 1e-4 off).  Everything else is the AVX2 build the demapper is pinned to.
+// six .npy files.  Built and run by oracle/recorders.mk, against a checkout of srsRAN-5G-ER and into oracle/_ref/:
+// `make -C oracle recorders`, `make -C oracle rerecord-check`; no binary or object is committed.  The recipe says why the build
+// is without fused multiply-adds and why the equaliser alone is compiled without AVX2.
 //
 // Receive ports.  pusch_demodulator_impl reads a contiguous allocation through grid.get_view(i_port, ...) -- the port's position
 // in the list -- and any other through grid.get(..., rx_ports[i_port], ...) -- its identifier (pusch_demodulator_impl.h:104-128).
@@ -59,20 +43,13 @@
 #include "lib/phy/upper/channel_processors/pusch/pusch_demodulator_impl.h"
 #include "lib/phy/upper/equalization/channel_equalizer_generic_impl.h"
 #include "lib/phy/upper/sequence_generators/pseudo_random_generator_impl.h"
-#include "srsran/phy/support/resource_grid_reader.h"
+#include "recorder_grid.h"
 #include "srsran/phy/upper/channel_processors/pusch/pusch_codeword_buffer.h"
 #include "srsran/phy/upper/channel_processors/pusch/pusch_demodulator_notifier.h"
 
 #include <cmath>
 #include <complex>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
 #include <random>
-#include <regex>
-#include <sstream>
-#include <string>
-#include <vector>
 
 using namespace srsran;
 
@@ -80,79 +57,10 @@ namespace {
 
 using cd = std::complex<double>;
 
-template <typename T>
-void write_npy(const std::string& path, const char* descr, const std::vector<T>& data, size_t cols)
-{
-  std::ostringstream shape;
-  if (cols == 0) {
-    shape << "(" << data.size() << ",)";
-  } else {
-    shape << "(" << data.size() / cols << ", " << cols << ")";
-  }
-  std::string header = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape.str() + ", }";
-  while ((10 + header.size() + 1) % 64 != 0) {
-    header += ' ';
-  }
-  header += '\n';
-  std::ofstream  f(path, std::ios::binary);
-  const char     magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
-  const uint16_t len      = (uint16_t)header.size();
-  f.write(magic, 8);
-  f.write((const char*)&len, 2);
-  f.write(header.data(), header.size());
-  f.write((const char*)data.data(), data.size() * sizeof(T));
-}
-
-uint32_t bf16_bits(float v) // nearest, ties to even
-{
-  uint32_t u;
-  std::memcpy(&u, &v, 4);
-  return (u + 0x7FFFU + ((u >> 16) & 1U)) >> 16;
-}
-float bf16_value(uint32_t bits)
-{
-  const uint32_t u = bits << 16;
-  float          v;
-  std::memcpy(&v, &u, 4);
-  return v;
-}
 uint32_t cbf16_word(cd v)
 {
   return bf16_bits((float)v.real()) | (bf16_bits((float)v.imag()) << 16);
 }
-cbf16_t cbf16_of(uint32_t w)
-{
-  return cbf16_t(bf16_value(w & 0xFFFFU), bf16_value(w >> 16)); // exact: the halves are bf16 values
-}
-
-// A grid [ports][14][nof_subc] of cbf16 behind the reference's reader interface.
-class word_grid : public resource_grid_reader
-{
-public:
-  unsigned             ports, nof_subc;
-  std::vector<cbf16_t> re;
-
-  word_grid(unsigned ports_, unsigned nof_subc_) : ports(ports_), nof_subc(nof_subc_), re(ports_ * 14 * nof_subc_) {}
-  cbf16_t&   at(unsigned port, unsigned l, unsigned k) { return re[(port * 14 + l) * nof_subc + k]; }
-  unsigned   get_nof_ports() const override { return ports; }
-  unsigned   get_nof_subc() const override { return nof_subc; }
-  unsigned   get_nof_symbols() const override { return 14; }
-  bool       is_empty(unsigned) const override { return false; }
-  bool       is_empty() const override { return false; }
-  span<cf_t> get(span<cf_t> symbols, unsigned, unsigned, unsigned, const bounded_bitset<MAX_RB * NRE>&) const override { return symbols; }
-  span<cbf16_t> get(span<cbf16_t> symbols, unsigned port, unsigned l, unsigned k_init, const bounded_bitset<MAX_RB * NRE>& mask) const override
-  {
-    unsigned n = 0;
-    mask.for_each(0, mask.size(), [&](unsigned k) { symbols[n++] = re[(port * 14 + l) * nof_subc + k_init + k]; });
-    return symbols.last(symbols.size() - n);
-  }
-  void                get(span<cf_t>, unsigned, unsigned, unsigned, unsigned) const override {}
-  void                get(span<cbf16_t>, unsigned, unsigned, unsigned) const override {}
-  span<const cbf16_t> get_view(unsigned port, unsigned l) const override
-  {
-    return span<const cbf16_t>(re).subspan((port * 14 + l) * nof_subc, nof_subc);
-  }
-};
 
 // The deprecoder's transform: the direct sum in double, rounded once to float.
 class dft_direct : public dft_processor
@@ -254,44 +162,6 @@ struct Case {
   std::vector<int> prbs;
   std::vector<float> noise; // per receive port
 };
-
-int json_int(const std::string& obj, const char* key)
-{
-  std::smatch m;
-  if (!std::regex_search(obj, m, std::regex(std::string("\"") + key + "\": (-?[0-9]+)"))) {
-    std::fprintf(stderr, "no %s\n", key);
-    std::exit(1);
-  }
-  return std::stoi(m[1]);
-}
-std::vector<int> json_list(const std::string& obj, const char* key)
-{
-  std::smatch m;
-  std::regex_search(obj, m, std::regex(std::string("\"") + key + "\": \\[([0-9, ]*)\\]"));
-  std::stringstream s(std::regex_replace(m[1].str(), std::regex(","), " "));
-  std::vector<int>  out;
-  for (int v; s >> v;) {
-    out.push_back(v);
-  }
-  return out;
-}
-std::string list_json(const std::vector<int>& v)
-{
-  std::string s = "[";
-  for (size_t i = 0; i != v.size(); ++i) {
-    s += (i ? ", " : "") + std::to_string(v[i]);
-  }
-  return s + "]";
-}
-
-std::vector<int> range(int first, int count)
-{
-  std::vector<int> v;
-  for (int i = 0; i != count; ++i) {
-    v.push_back(first + i);
-  }
-  return v;
-}
 
 // group, rnti, n_id, qm, start, nsym, dmrs symbols, dmrs type, cdm, layers, rx ports, equaliser, tp, prbs, noise per port.
 std::vector<Case> small_shapes()
@@ -446,7 +316,7 @@ int main(int argc, char** argv)
           }
           const uint32_t w                                       = cbf16_word(y);
           grids[grid_off + ((size_t)p * c.nsym + s) * nsc + j] = w;
-          grid.at(p, sym, subc[j])                               = cbf16_of(w);
+          grid.set(p, sym, subc[j], w);
           for (unsigned l = 0; l != L; ++l) {
             const uint32_t hw = j == zero_j ? 0U : cbf16_word(h[(l * P + p) * nsc + j]);
             ces[ce_off + ((size_t)l * P + p) * nsc + j]                = hw;

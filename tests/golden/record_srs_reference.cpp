@@ -1,20 +1,13 @@
 // Records the answers of srsRAN-5G-ER's srs_estimator_generic_impl for tests/test_srs_estimator.py.  It constructs the reference's
 // classes directly -- the estimator with low_papr_sequence_generator_impl and time_alignment_estimator_dft_impl over
 // dft_processor_generic_impl --, makes a grid per case with a transmitter of its own, and writes inputs and outputs as four .npy
-// files.  Built and run outside the repository; no binary or object is committed.  R = a checkout of srsRAN-5G-ER, OUT = this
-// directory:
+// files.  Built and run by oracle/recorders.mk, against a checkout of srsRAN-5G-ER and into oracle/_ref/:
+// `make -C oracle recorders`, `make -C oracle rerecord-check`; no binary or object is committed.  The run takes several minutes:
+// channels are drawn again, see below.
 //
-//   S=$R/lib/phy; g++ -std=c++17 -O2 -mavx2 -mfma -ffp-contract=off -DNDEBUG -w -I$R/include -I$R/external/fmt/include -I$R/external \
-//     -I$R record_srs_reference.cpp $S/upper/signal_processors/srs/srs_estimator_generic_impl.cpp \
-//     $S/upper/sequence_generators/low_papr_sequence_generator_impl.cpp \
-//     $S/support/time_alignment_estimator/time_alignment_estimator_dft_impl.cpp $S/generic_functions/dft_processor_generic_impl.cpp \
-//     $R/lib/ran/srs/srs_information.cpp $R/lib/ran/srs/srs_bandwidth_configuration.cpp $R/lib/support/math_utils.cpp \
-//     $R/lib/srsvec/prod.cpp $R/lib/srsvec/add.cpp $R/lib/srsvec/sc_prod.cpp $R/lib/srsvec/compare.cpp $R/lib/srsvec/aligned_vec.cpp \
-//     $R/external/fmt/src/format.cc $R/external/fmt/src/os.cc -lpthread -o record_srs_reference
-//   ./record_srs_reference srs_configs.json OUT          (several minutes: channels are drawn again, see below)
-//
-// -ffp-contract=off: the estimator's phase index is a chain of single-precision operations in the source, and the recording holds
-// what the source says; g++'s default would fuse n * ps + offset wherever the target has a fused multiply-add.
+// -ffp-contract=off (the recipe's avx2nc flags): the estimator's phase index is a chain of single-precision operations in the
+// source, and the recording holds what the source says; the compiler's default would fuse n * ps + offset wherever the target has a
+// fused multiply-add.
 //
 // Cases: the 72 configurations of srs_configs.json ("estimator"), each with a seeded channel, then the small shapes of the table
 // below.  Per case the transmitter puts antenna port p's sequence (the reference generator's) on its comb, gives receive port i
@@ -40,96 +33,19 @@
 #include "lib/phy/support/time_alignment_estimator/time_alignment_estimator_dft_impl.h"
 #include "lib/phy/upper/sequence_generators/low_papr_sequence_generator_impl.h"
 #include "lib/phy/upper/signal_processors/srs/srs_estimator_generic_impl.h"
-#include "srsran/phy/support/resource_grid_reader.h"
+#include "recorder_grid.h"
 #include "srsran/phy/upper/signal_processors/srs/srs_estimator_configuration.h"
 #include "srsran/phy/upper/signal_processors/srs/srs_estimator_result.h"
 #include "srsran/ran/srs/srs_information.h"
 
 #include <cmath>
-#include <cstdio>
-#include <cstring>
-#include <fstream>
+#include <complex>
 #include <random>
-#include <regex>
 #include <set>
-#include <sstream>
-#include <string>
-#include <vector>
 
 using namespace srsran;
 
 namespace {
-
-template <typename T>
-void write_npy(const std::string& path, const char* descr, const std::vector<T>& data, size_t cols)
-{
-  std::ostringstream shape;
-  if (cols == 0) {
-    shape << "(" << data.size() << ",)";
-  } else {
-    shape << "(" << data.size() / cols << ", " << cols << ")";
-  }
-  std::string header = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape.str() + ", }";
-  while ((10 + header.size() + 1) % 64 != 0) {
-    header += ' ';
-  }
-  header += '\n';
-  std::ofstream  f(path, std::ios::binary);
-  const char     magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
-  const uint16_t len      = (uint16_t)header.size();
-  f.write(magic, 8);
-  f.write((const char*)&len, 2);
-  f.write(header.data(), header.size());
-  f.write((const char*)data.data(), data.size() * sizeof(T));
-}
-
-uint32_t bf16_bits(float v) // nearest, ties to even
-{
-  uint32_t u;
-  std::memcpy(&u, &v, 4);
-  return (u + 0x7FFFU + ((u >> 16) & 1U)) >> 16;
-}
-float bf16_value(uint32_t bits)
-{
-  const uint32_t u = bits << 16;
-  float          v;
-  std::memcpy(&v, &u, 4);
-  return v;
-}
-
-// A grid [ports][14][nof_subc] of cbf16 words behind the reference's reader interface.
-class word_grid : public resource_grid_reader
-{
-public:
-  unsigned              ports, nof_subc;
-  std::vector<uint32_t> words;
-
-  word_grid(unsigned ports_, unsigned nof_subc_) : ports(ports_), nof_subc(nof_subc_), words(ports_ * 14 * nof_subc_, 0) {}
-  cf_t at(unsigned port, unsigned l, unsigned k) const
-  {
-    const uint32_t w = words[(port * 14 + l) * nof_subc + k];
-    return cf_t(bf16_value(w & 0xFFFFU), bf16_value(w >> 16));
-  }
-  void set(unsigned port, unsigned l, unsigned k, float re, float im) { words[(port * 14 + l) * nof_subc + k] = bf16_bits(re) | (bf16_bits(im) << 16); }
-  unsigned   get_nof_ports() const override { return ports; }
-  unsigned   get_nof_subc() const override { return nof_subc; }
-  unsigned   get_nof_symbols() const override { return 14; }
-  bool       is_empty(unsigned) const override { return false; }
-  bool       is_empty() const override { return false; }
-  span<cf_t> get(span<cf_t> symbols, unsigned, unsigned, unsigned, const bounded_bitset<MAX_RB * NRE>&) const override { return symbols; }
-  span<cbf16_t> get(span<cbf16_t> symbols, unsigned, unsigned, unsigned, const bounded_bitset<MAX_RB * NRE>&) const override
-  {
-    return symbols;
-  }
-  void get(span<cf_t> symbols, unsigned port, unsigned l, unsigned k_init, unsigned stride) const override
-  {
-    for (unsigned i = 0; i != symbols.size(); ++i) {
-      symbols[i] = at(port, l, k_init + stride * i);
-    }
-  }
-  void                get(span<cbf16_t>, unsigned, unsigned, unsigned) const override {}
-  span<const cbf16_t> get_view(unsigned, unsigned) const override { return {}; }
-};
 
 // Forwards to the reference's estimator and keeps what it returned, call by call.  It also evaluates the searched bins of the
 // call's symbols in double and says whether the two largest magnitudes lie within 2e-4 of each other: such a channel is drawn again.
@@ -185,16 +101,6 @@ struct Case {
   int grid_ports, grid_subc, delay, noise; // noise in 1e-4
 };
 
-int json_int(const std::string& obj, const char* key)
-{
-  std::smatch m;
-  if (!std::regex_search(obj, m, std::regex(std::string("\"") + key + "\": (-?[0-9]+)"))) {
-    std::fprintf(stderr, "no %s\n", key);
-    std::exit(1);
-  }
-  return std::stoi(m[1]);
-}
-
 srs_estimator_configuration to_config(const Case& c)
 {
   srs_estimator_configuration cfg;
@@ -241,13 +147,7 @@ int main(int argc, char** argv)
     Case c = {json_int(o, "numerology"), json_int(o, "nof_antenna_ports"), json_int(o, "nof_symbols"), json_int(o, "start_symbol"),
               json_int(o, "configuration_index"), json_int(o, "sequence_id"), json_int(o, "bandwidth_index"), json_int(o, "comb_size"),
               json_int(o, "comb_offset"), json_int(o, "cyclic_shift"), json_int(o, "freq_position"), json_int(o, "freq_shift"),
-              json_int(o, "freq_hopping"), {}, 0, 0, 0, 500};
-    std::smatch m;
-    std::regex_search(o, m, std::regex("\"rx_ports\": \\[([0-9, ]*)\\]"));
-    std::stringstream ports(std::regex_replace(m[1].str(), std::regex(","), " "));
-    for (int p; ports >> p;) {
-      c.rx.push_back(p);
-    }
+              json_int(o, "freq_hopping"), json_list(o, "rx_ports"), 0, 0, 0, 500};
     c.grid_ports = c.rx.back() + 1;
     // A delay within half the search window of the comb: 256 bins for comb 2, 85 for comb 4.
     const int w = c.comb == 2 ? 256 : 85;
@@ -371,7 +271,7 @@ int main(int argc, char** argv)
     for (int port = 0; port != c.grid_ports; ++port) {
       for (int l = c.start; l != c.start + c.nsym; ++l) {
         for (unsigned j = 0; j != count; ++j) {
-          grids.push_back(grid.words[(port * 14 + l) * c.grid_subc + k_lo + stride * j]);
+          grids.push_back(grid.word(port, l, k_lo + stride * j));
         }
       }
     }

@@ -1,17 +1,7 @@
 // Records the answers of srsRAN-5G-ER's uci_decoder_impl for tests/test_uci_decoder.py.  It constructs the reference's classes
-// directly, feeds them seeded inputs and writes inputs and outputs as four .npy files.  Built and run outside the repository; no
-// binary or object is committed.  R = a checkout of srsRAN-5G-ER, OUT = this directory:
-//
-//   S=$R/lib/phy/upper; g++ -std=c++17 -O2 -mavx2 -mfma -DNDEBUG -w -I$R/include -I$R/external/fmt/include -I$R/external -I$R \
-//     record_uci_reference.cpp $S/channel_processors/uci/uci_decoder_impl.cpp $S/channel_coding/short/short_block_detector_impl.cpp \
-//     $S/channel_coding/short/short_block_encoder_impl.cpp $S/channel_coding/polar/polar_code_impl.cpp \
-//     $S/channel_coding/polar/polar_rate_dematcher_impl.cpp $S/channel_coding/polar/polar_decoder_impl.cpp \
-//     $S/channel_coding/polar/polar_deallocator_impl.cpp $S/channel_coding/polar/polar_encoder_impl.cpp \
-//     $S/channel_coding/polar/polar_allocator_impl.cpp $S/channel_coding/polar/polar_rate_matcher_impl.cpp \
-//     $S/channel_coding/crc_calculator_generic_impl.cpp $S/log_likelihood_ratio.cpp $R/lib/srsvec/bit.cpp $R/lib/srsvec/dot_prod.cpp \
-//     $R/lib/srsvec/aligned_vec.cpp $R/lib/srsvec/compare.cpp $R/external/fmt/src/format.cc \
-//     $R/external/fmt/src/os.cc -lpthread -o record_uci_reference
-//   ./record_uci_reference uci_decoder_configs.json OUT
+// directly, feeds them seeded inputs and writes inputs and outputs as four .npy files.  Built and run by oracle/recorders.mk,
+// against a checkout of srsRAN-5G-ER and into oracle/_ref/: `make -C oracle recorders`, `make -C oracle rerecord-check`; no
+// binary or object is committed.
 //
 // Files (case i is row i of `cases`):
 //   uci_reference_cases.npy  int32 [n][8]: message length A, LLR length E, modulation (bits per symbol; 0 = pi/2-BPSK), input kind,
@@ -33,17 +23,12 @@
 #include "lib/phy/upper/channel_coding/short/short_block_detector_impl.h"
 #include "lib/phy/upper/channel_coding/short/short_block_encoder_impl.h"
 #include "lib/phy/upper/channel_processors/uci/uci_decoder_impl.h"
+#include "recorder_io.h"
 #include "srsran/ran/uci/uci_info.h"
 
 #include <cmath>
-#include <cstdio>
-#include <fstream>
 #include <random>
-#include <regex>
 #include <set>
-#include <sstream>
-#include <string>
-#include <vector>
 
 using namespace srsran;
 
@@ -115,28 +100,6 @@ bool size_ok(const Size& s)
   return block_ok(s.A, s.E, &K, &Eb);
 }
 
-template <typename T>
-void write_npy(const std::string& path, const char* descr, const std::vector<T>& data, size_t cols)
-{
-  std::ostringstream shape;
-  if (cols == 0) {
-    shape << "(" << data.size() << ",)";
-  } else {
-    shape << "(" << data.size() / cols << ", " << cols << ")";
-  }
-  std::string header = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape.str() + ", }";
-  while ((10 + header.size() + 1) % 64 != 0) {
-    header += ' ';
-  }
-  header += '\n';
-  std::ofstream     f(path, std::ios::binary);
-  const char        magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
-  const uint16_t    len      = (uint16_t)header.size();
-  f.write(magic, 8);
-  f.write((const char*)&len, 2);
-  f.write(header.data(), header.size());
-  f.write((const char*)data.data(), data.size() * sizeof(T));
-}
 
 } // namespace
 

@@ -1,16 +1,10 @@
 // Records the answers of srsRAN-5G-ER's ulsch_demultiplex_impl for tests/test_ulsch_demultiplex.py.  It constructs the reference's
 // class directly, feeds it seeded soft bits with the scrambling sequence of the reference's own generator, and writes the four
-// streams it hands to its decoder buffers.  Built and run outside the repository; no binary or object is committed.
-// R = a checkout of srsRAN-5G-ER, OUT = this directory:
-//
-//   S=$R/lib/phy/upper; g++ -std=c++17 -O2 -mavx2 -mfma -DNDEBUG -w -I$R/include -I$R/external/fmt/include -I$R/external -I$R \
-//     record_ulsch_demultiplex_reference.cpp $S/channel_processors/pusch/ulsch_demultiplex_impl.cpp \
-//     $S/sequence_generators/pseudo_random_generator_impl.cpp $S/log_likelihood_ratio.cpp $R/lib/srsvec/bit.cpp \
-//     $R/lib/srsvec/compare.cpp $R/lib/srsvec/aligned_vec.cpp $R/external/fmt/src/format.cc $R/external/fmt/src/os.cc -lpthread -o record_ulsch_demultiplex_reference
-//   ./record_ulsch_demultiplex_reference ulsch_demultiplex_configs.json OUT
+// streams it hands to its decoder buffers.  Built and run by oracle/recorders.mk, against a checkout of srsRAN-5G-ER and into
+// oracle/_ref/: `make -C oracle recorders`, `make -C oracle rerecord-check`; no binary or object is committed.
 //
 // Case i is configuration i of the JSON.  Its input is not stored: soft bit k is (mix(seed_i + k) mod 255) - 127 with
-// seed_i = 0x9E3779B9 * (i + 1) and mix the 32-bit finaliser below; rnti = mix(seed_i ^ 0xAAAA) mod 65535 + 1 and
+// seed_i = 0x9E3779B9 * (i + 1) and mix the 32-bit finaliser of recorder_io.h; rnti = mix(seed_i ^ 0xAAAA) mod 65535 + 1 and
 // n_id = mix(seed_i ^ 0x5555) mod 1024.  Files:
 //   ulsch_reference_cases.npy  int64 [n][8]: rnti, n_id, soft bits of the codeword, soft bits of the UL-SCH stream, offset of the
 //                              case's UCI streams in uci (HARQ-ACK, CSI part 1, CSI part 2 back to back, the configuration's
@@ -20,28 +14,12 @@
 //   ulsch_reference_sch.npy    int8, the UL-SCH streams of the cases of at most 20000 soft bits
 #include "lib/phy/upper/channel_processors/pusch/ulsch_demultiplex_impl.h"
 #include "lib/phy/upper/sequence_generators/pseudo_random_generator_impl.h"
+#include "recorder_io.h"
 #include "srsran/phy/upper/channel_processors/pusch/pusch_decoder_buffer.h"
-
-#include <cstdio>
-#include <fstream>
-#include <regex>
-#include <sstream>
-#include <string>
-#include <vector>
 
 using namespace srsran;
 
 namespace {
-
-uint32_t mix(uint32_t h)
-{
-  h ^= h >> 16;
-  h *= 0x85EBCA6BU;
-  h ^= h >> 13;
-  h *= 0xC2B2AE35U;
-  h ^= h >> 16;
-  return h;
-}
 
 class stream_spy : public pusch_decoder_buffer
 {
@@ -65,39 +43,6 @@ private:
   std::vector<log_likelihood_ratio> view;
 };
 
-template <typename T>
-void write_npy(const std::string& path, const char* descr, const std::vector<T>& data, size_t cols)
-{
-  std::ostringstream shape;
-  if (cols == 0) {
-    shape << "(" << data.size() << ",)";
-  } else {
-    shape << "(" << data.size() / cols << ", " << cols << ")";
-  }
-  std::string header = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape.str() + ", }";
-  while ((10 + header.size() + 1) % 64 != 0) {
-    header += ' ';
-  }
-  header += '\n';
-  std::ofstream  f(path, std::ios::binary);
-  const char     magic[8] = {'\x93', 'N', 'U', 'M', 'P', 'Y', 1, 0};
-  const uint16_t len      = (uint16_t)header.size();
-  f.write(magic, 8);
-  f.write((const char*)&len, 2);
-  f.write(header.data(), header.size());
-  f.write((const char*)data.data(), data.size() * sizeof(T));
-}
-
-unsigned field(const std::string& line, const char* name)
-{
-  std::smatch m;
-  if (!std::regex_search(line, m, std::regex(std::string("\"") + name + "\": (\\d+)"))) {
-    std::fprintf(stderr, "no field %s\n", name);
-    std::exit(1);
-  }
-  return (unsigned)std::stoul(m[1]);
-}
-
 } // namespace
 
 int main(int argc, char** argv)
@@ -116,26 +61,26 @@ int main(int argc, char** argv)
       continue;
     }
     ulsch_demultiplex::configuration cfg;
-    const unsigned                   code = field(line, "modulation");
+    const unsigned                   code = json_int(line, "modulation");
     cfg.modulation         = code == 0 ? modulation_scheme::PI_2_BPSK : code == 1 ? modulation_scheme::BPSK : code == 2 ? modulation_scheme::QPSK
                              : code == 4 ? modulation_scheme::QAM16 : code == 6 ? modulation_scheme::QAM64 : modulation_scheme::QAM256;
-    cfg.nof_layers         = field(line, "nof_layers");
-    cfg.nof_prb            = field(line, "nof_prb");
-    cfg.start_symbol_index = field(line, "start_symbol_index");
-    cfg.nof_symbols        = field(line, "nof_symbols");
-    cfg.nof_harq_ack_rvd   = field(line, "nof_harq_ack_rvd");
-    cfg.dmrs               = field(line, "dmrs_type") == 0 ? dmrs_type::TYPE1 : dmrs_type::TYPE2;
-    const unsigned mask    = field(line, "dmrs_symbol_mask");
+    cfg.nof_layers         = json_int(line, "nof_layers");
+    cfg.nof_prb            = json_int(line, "nof_prb");
+    cfg.start_symbol_index = json_int(line, "start_symbol_index");
+    cfg.nof_symbols        = json_int(line, "nof_symbols");
+    cfg.nof_harq_ack_rvd   = json_int(line, "nof_harq_ack_rvd");
+    cfg.dmrs               = json_int(line, "dmrs_type") == 0 ? dmrs_type::TYPE1 : dmrs_type::TYPE2;
+    const unsigned mask    = json_int(line, "dmrs_symbol_mask");
     cfg.dmrs_symbol_mask   = symbol_slot_mask(14);
     for (unsigned l = 0; l != 14; ++l) {
       cfg.dmrs_symbol_mask.set(l, (mask >> l) & 1U);
     }
-    cfg.nof_cdm_groups_without_data = field(line, "nof_cdm_groups_without_data");
-    cfg.nof_harq_ack_bits           = field(line, "nof_harq_ack_bits");
-    cfg.nof_enc_harq_ack_bits       = field(line, "nof_enc_harq_ack_bits");
-    cfg.nof_csi_part1_bits          = field(line, "nof_csi_part1_bits");
-    cfg.nof_enc_csi_part1_bits      = field(line, "nof_enc_csi_part1_bits");
-    const unsigned csi2_bits = field(line, "nof_csi_part2_bits"), csi2_enc = field(line, "nof_enc_csi_part2_bits");
+    cfg.nof_cdm_groups_without_data = json_int(line, "nof_cdm_groups_without_data");
+    cfg.nof_harq_ack_bits           = json_int(line, "nof_harq_ack_bits");
+    cfg.nof_enc_harq_ack_bits       = json_int(line, "nof_enc_harq_ack_bits");
+    cfg.nof_csi_part1_bits          = json_int(line, "nof_csi_part1_bits");
+    cfg.nof_enc_csi_part1_bits      = json_int(line, "nof_enc_csi_part1_bits");
+    const unsigned csi2_bits = json_int(line, "nof_csi_part2_bits"), csi2_enc = json_int(line, "nof_enc_csi_part2_bits");
 
     // The codeword's length: the data REs of every symbol.
     const unsigned nbre    = get_bits_per_symbol(cfg.modulation) * cfg.nof_layers;
