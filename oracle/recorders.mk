@@ -1,7 +1,7 @@
 # TEST INFRASTRUCTURE -- builds and runs the golden recorders, tests/golden/record_*_reference.cpp, never the product.
 # Included from oracle/Makefile (HERE, REPO, REF, OUT, OBJ, CXX).  Only possible where $(REF) exists; outputs only into oracle/_ref/.
 #
-#   make recorders       -> the 13 programs under oracle/_ref/obj/recorders/
+#   make recorders       -> the 14 programs under oracle/_ref/obj/recorders/
 #   make rerecord        -> runs those that make their own inputs (all but pusch_processor and pusch_csi2, which read grids a
 #                           GPU wrote: `python tests/test_pusch_processor.py DIR`, `python tests/test_pusch_csi2.py DIR`; they
 #                           run too when PUSCH_PROC_INPUTS=DIR, PUSCH_CSI2_INPUTS=DIR name such directories); recordings go to
@@ -108,6 +108,16 @@ SRCS_pusch_tp    := $(U)/channel_processors/pusch/pusch_demodulator_impl.cpp $(U
 LINK_pusch_tp    := $(EQUALIZER_SCALAR)
 ARGS_pusch_tp    := $(GOLDEN)/pusch_demodulator_configs.json $(RECORDED)
 
+# PUCCH format 2: the flags of the processors' archive, and the scalar equaliser for the reason pusch_tp has it.
+FLAVOUR_pf2 := avx2nc
+SRCS_pf2    := $(filter-out $(FMT) lib/srsvec/%,$(SRCS_uci)) $(CHEST) \
+               $(U)/signal_processors/pucch/dmrs_pucch_processor_format2_impl.cpp $(U)/channel_processors/pucch_demodulator_impl.cpp \
+               $(U)/channel_modulation/demodulation_mapper_impl.cpp $(U)/channel_modulation/demodulation_mapper_qpsk.cpp \
+               $(U)/channel_modulation/demodulation_mapper_qam16.cpp $(U)/channel_modulation/demodulation_mapper_qam64.cpp \
+               $(U)/channel_modulation/demodulation_mapper_qam256.cpp $(FMT)
+LINK_pf2    := $(EQUALIZER_SCALAR)
+ARGS_pf2    := $(GOLDEN)/pf2_configs.json $(RECORDED)
+
 OFH_RECEIVER_DOUBLES := -I$(REF)/tests/unittests/ofh/receiver
 
 FLAVOUR_ofh_ul := plain
@@ -168,7 +178,7 @@ FLAVOUR_pusch_csi2      := avx2nc
 LINK_pusch_csi2         := $(REC)/libref.a
 ARGS_pusch_csi2         := $(PUSCH_CSI2_INPUTS) $(RECORDED)
 
-SELF_CONTAINED := ulsch_demultiplex uci prach_demod prach_detector pucch pusch_chest srs pusch_tp ofh_ul ofh_rx ofh_dl
+SELF_CONTAINED := ulsch_demultiplex uci prach_demod prach_detector pucch pf2 pusch_chest srs pusch_tp ofh_ul ofh_rx ofh_dl
 RECORDERS      := $(SELF_CONTAINED) pusch_processor pusch_csi2
 RERECORDED     := $(SELF_CONTAINED) $(if $(PUSCH_PROC_INPUTS),pusch_processor) $(if $(PUSCH_CSI2_INPUTS),pusch_csi2)
 

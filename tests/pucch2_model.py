@@ -259,7 +259,7 @@ def estimate_port(cfg, grid, port, dt=np.float32):
         snr = dt(rsrp / noise_var) if noise_var != 0 else dt(1000)
     scs = 15000 << cfg["numerology"]
     meas = {"noise_var": noise_var, "rsrp": rsrp, "epre": epre_f, "snr": snr, "ta_bins": ta_bins, "ta_s": dt(ta_bins / (4096.0 * scs)),
-            "cfo_hz": dt(dt(cfo * dt(scs // 1000)) * dt(1000)) if ns == 2 else dt(np.nan), "ta_mag": mag}
+            "cfo_hz": dt(dt(cfo * dt(scs // 1000)) * dt(1000)) if ns == 2 else dt(np.nan), "ta_mag": mag, "smoothed": Fr + 1j * Fi}
     return np.stack(est), meas
 
 
