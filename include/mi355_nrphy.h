@@ -495,6 +495,22 @@ int nrphy_pusch_demod_plan_create_ex(nrphy_ctx_t* ctx, uint32_t n, const nrphy_p
 int nrphy_pusch_demodulate_host_ex(nrphy_ctx_t* ctx, const nrphy_pusch_demod_cfg_t* cfg, const void* grid, uint32_t grid_nof_ports,
                                    uint32_t grid_nof_subc, const void* ch_est, const float* noise_vars, uint32_t features,
                                    int8_t* llr, float* sinr_db);
+/* The forms with the EVM: what pusch_demodulator_impl reports when it is constructed with an evm_calculator
+ * (R/lib/phy/upper/channel_modulation/evm_calculator_generic_impl.cpp, pusch_demodulator_impl.cpp:157-162, 244-252, 266-278).
+ * Per OFDM symbol s with data, over its n_s = data RE x layers equalised symbols x_j -- after the deprecoder for a
+ * transform-precoded PUSCH -- and the demapper's soft bits before descrambling: hard bit 1 where the soft bit is <= 0 (an RE the
+ * equaliser gave up on decides all ones and counts like any other), the hard bits mapped to the constellation point m_j of
+ * modulation_mapper_lut_impl, P_s = sum |m_j - x_j|^2, e_s = sqrtf(P_s / n_s); over the symbols in ascending order in float
+ * acc += n_s * e_s, cnt += n_s; EVM = acc / cnt.  Every term of P_s is formed in float with the reference's roundings and the
+ * terms are added in double in a fixed order (lanes, waves, work items), so the value differs from the reference's float chain
+ * by rounding only, and two runs give the same bytes.  d_evm[i] is the EVM of PUSCH i; either of d_sinr_db and d_evm may be
+ * NULL, and with d_evm == NULL the call is exactly nrphy_pusch_demod_run (the same kernels).  Works on the plans of both
+ * creation calls.  The host form takes the feature mask of nrphy_pusch_demodulate_host_ex; sinr_db and evm may be NULL. */
+int nrphy_pusch_demod_run_evm(nrphy_pusch_demod_plan_t* plan, const void* d_grid, const void* d_ch_est, const float* d_noise_vars,
+                              int8_t* d_llr, uint64_t llr_stride, float* d_sinr_db, float* d_evm, void* stream);
+int nrphy_pusch_demodulate_host_evm(nrphy_ctx_t* ctx, const nrphy_pusch_demod_cfg_t* cfg, const void* grid, uint32_t grid_nof_ports,
+                                    uint32_t grid_nof_subc, const void* ch_est, const float* noise_vars, uint32_t features,
+                                    int8_t* llr, float* sinr_db, float* evm);
 
 /* ---- receive side: transform deprecoder (DFT-s-OFDM) ----------------------------------------------------------------------
  * Replaces transform_precoder::deprecode_ofdm_symbol (R/include/srsran/phy/generic_functions/transform_precoding/
@@ -1840,11 +1856,13 @@ int nrphy_ul_sch_info(const nrphy_ulsch_info_cfg_t* cfg, nrphy_ulsch_info_t* out
  * channel_state_information record -- nrphy_pusch_chest_run, nrphy_pusch_demod_run, nrphy_ulsch_demux_run, nrphy_uci_decoder_run
  * and nrphy_pusch_decode_batch with the configurations nrphy_pusch_proc_derive gives, on one stream with no host step, followed
  * by one launch that writes a nrphy_pusch_result_t per PDU.  A PDU with a CSI part 2 description is refused here and taken by
- * nrphy_pusch_csi2_* (the next section).  Not covered, and refused: the EVM and the EVM-based SINR, DM-RS type 2.
- * Transform precoding is never enabled, as in the reference's processor. */
+ * nrphy_pusch_csi2_* (the next section).  Not covered, and refused: DM-RS type 2.  The EVM and the EVM-based SINR are not part
+ * of these calls either -- they keep refusing NRPHY_PUSCH_SINR_EVM and reporting has_evm = 0 -- but of nrphy_pusch_evm_* below,
+ * which take the EVM from the demodulator (nrphy_pusch_demod_run_evm).  Transform precoding is never enabled, as in the
+ * reference's processor. */
 #define NRPHY_PUSCH_SINR_CHANNEL_ESTIMATOR 0u /* channel_state_information::sinr_type */
 #define NRPHY_PUSCH_SINR_POST_EQUALIZATION 1u
-#define NRPHY_PUSCH_SINR_EVM 2u               /* refused */
+#define NRPHY_PUSCH_SINR_EVM 2u               /* nrphy_pusch_evm_* with enable_evm = 1 only; refused by nrphy_pusch_proc_* */
 typedef struct nrphy_pusch_pdu {              /* pusch_processor::pdu_t */
   uint32_t numerology, slot_index;            /* slot within the frame: < 10 * 2^numerology */
   uint32_t rnti, n_id;                        /* data scrambling: c_init = rnti * 2^15 + n_id */
@@ -1900,8 +1918,8 @@ typedef struct nrphy_pusch_result {           /* one per PDU */
   float    time_alignment_s;                  /* of the receive port with the best SNR */
   float    cfo_hz;                            /* of that port; 0 with has_cfo = 0 */
   uint32_t has_cfo;                           /* 0 with a single DM-RS symbol: the reference's optional is empty */
-  uint32_t has_evm;                           /* always 0 */
-  float    evm;                               /* always 0 */
+  uint32_t has_evm;                           /* 1 from nrphy_pusch_evm_* with enable_evm = 1, else 0 */
+  float    evm;                               /* the demodulator's EVM (nrphy_pusch_demod_run_evm); 0 with has_evm = 0 */
 } nrphy_pusch_result_t;
 typedef struct nrphy_pusch_proc_plan nrphy_pusch_proc_plan_t;
 /* NRPHY_OK, or NRPHY_ERR_ARGUMENT for what pusch_processor_validator_impl and assert_pdu refuse and for what any of the five stage
@@ -1911,7 +1929,8 @@ typedef struct nrphy_pusch_proc_plan nrphy_pusch_proc_plan_t;
  * modulation outside QPSK..256-QAM; rv above 3, a base graph other than 1 or 2, a codeword without bytes or bytes without a
  * codeword; sizes nrphy_ul_sch_info refuses, UCI soft bits the placement or the UCI decoder cannot take, an UL-SCH the decoder
  * cannot take; a CSI part 2 description; a PDU with neither a codeword nor a UCI bit; no decoder iteration; csi_sinr_calc_method
- * NRPHY_PUSCH_SINR_EVM or unknown; an unknown equaliser or MMSE with two layers.  No device work. */
+ * NRPHY_PUSCH_SINR_EVM (accepted by nrphy_pusch_evm_validate with enable_evm = 1 only) or unknown; an unknown equaliser or MMSE
+ * with two layers.  No device work. */
 int nrphy_pusch_proc_validate(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_proc_options_t* options, uint32_t grid_nof_ports,
                               uint32_t grid_nof_subc);
 /* The stage configurations of a PDU nrphy_pusch_proc_validate accepts (the grid only bounds the checks).  No device work. */
@@ -1951,6 +1970,29 @@ int nrphy_pusch_proc_run(nrphy_pusch_proc_plan_t* plan, const void* d_grid, void
 int nrphy_pusch_proc_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_proc_options_t* options, const void* grid,
                           uint32_t grid_nof_ports, uint32_t grid_nof_subc, int8_t* harq_soft, uint8_t* harq_state, uint8_t* tb,
                           uint8_t* uci_bits, nrphy_pusch_result_t* result);
+/* The processor with the EVM: pusch_processor_impl built over a demodulator that has an EVM calculator, and
+ * pusch_processor_notifier_adaptor.h:154-163.  The three calls take the arguments of their nrphy_pusch_proc_* namesakes with the
+ * options below, and there is one implementation: nrphy_pusch_proc_* are these calls with enable_evm = 0, and with enable_evm = 0
+ * every result byte is theirs.  enable_evm above 1 or a non-zero reserved_ is NRPHY_ERR_ARGUMENT; NRPHY_PUSCH_SINR_EVM is
+ * accepted only with enable_evm = 1.  With enable_evm = 1 the demodulator stage is nrphy_pusch_demod_run_evm, every record has
+ * has_evm = 1 and the demodulator's EVM -- a PDU without codeword too --, and sinr_dB follows csi_sinr_calc_method: with
+ * NRPHY_PUSCH_SINR_EVM it is -20 log10f(evm) - 3.7f, evaluated in float in the result kernel, +inf for an EVM of 0.  The plan is
+ * a nrphy_pusch_proc_plan_t: nrphy_pusch_proc_run, nrphy_pusch_proc_plan_destroy and nrphy_pusch_proc_plan_harq_bytes take it
+ * as they are.  nrphy_pusch_csi2_* keeps has_evm = 0. */
+typedef struct nrphy_pusch_evm_options {
+  nrphy_pusch_proc_options_t proc;
+  uint32_t enable_evm;                        /* 0 or 1 */
+  uint32_t reserved_;                         /* 0 */
+} nrphy_pusch_evm_options_t;
+int nrphy_pusch_evm_validate(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_evm_options_t* options, uint32_t grid_nof_ports,
+                             uint32_t grid_nof_subc);
+int nrphy_pusch_evm_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, const nrphy_pusch_evm_options_t* options,
+                                const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
+                                const uint64_t* harq_soft_offset, const uint64_t* harq_state_offset, const uint64_t* tb_offset,
+                                const uint64_t* uci_offset, nrphy_pusch_proc_plan_t** plan);
+int nrphy_pusch_evm_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_evm_options_t* options, const void* grid,
+                         uint32_t grid_nof_ports, uint32_t grid_nof_subc, int8_t* harq_soft, uint8_t* harq_state, uint8_t* tb,
+                         uint8_t* uci_bits, nrphy_pusch_result_t* result);
 
 /* ---- receive side: PUSCH processor with CSI part 2 ---------------------------------------------------------------------------------
  * What pusch_processor_impl::process does with pdu.uci.csi_part2_size (pusch_processor_impl.cpp:57-86 and
@@ -2131,6 +2173,10 @@ void* nrphy_ul_slot_stream(nrphy_ul_slots_t* pool, uint32_t slot_id);
 int nrphy_ul_slot_symbols_written(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t upto);
 int nrphy_ul_slot_pusch(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pusch_pdu_t* pdus,
                         const nrphy_pusch_proc_options_t* options, const uint64_t* harq_soft_offset, const uint64_t* harq_state_offset);
+/* nrphy_ul_slot_pusch with the options of nrphy_pusch_evm_plan_create: the same operation, the results append to the same list,
+ * and a slot may mix both calls. */
+int nrphy_pusch_evm_slot(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pusch_pdu_t* pdus,
+                         const nrphy_pusch_evm_options_t* options, const uint64_t* harq_soft_offset, const uint64_t* harq_state_offset);
 int nrphy_ul_slot_pf01(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pucch_cfg_t* cfgs);
 int nrphy_ul_slot_pf2(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pf2_cfg_t* cfgs);
 int nrphy_ul_slot_srs(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_srs_cfg_t* cfgs);

@@ -425,6 +425,11 @@ class PuschProcOptions(C.Structure):
                 ("equalizer", C.c_uint32)]
 
 
+class PuschEvmOptions(C.Structure):
+    """nrphy_pusch_evm_options_t: the processor's options and whether the demodulator takes the EVM."""
+    _fields_ = [("proc", PuschProcOptions), ("enable_evm", C.c_uint32), ("reserved_", C.c_uint32)]
+
+
 class PuschProcDerived(C.Structure):
     """nrphy_pusch_proc_derived_t: the stage configurations of one PDU."""
     _fields_ = [("info", UlschInfo), ("chest", PuschChestCfg), ("demod", PuschDemodCfg), ("demux", UlschDemuxCfg),
@@ -472,6 +477,11 @@ def make_pusch_proc_options(dec_nof_iterations=10, dec_enable_early_stop=1, csi_
                             equalizer=EQ_ZF):
     """A PuschProcOptions."""
     return PuschProcOptions(dec_nof_iterations, dec_enable_early_stop, csi_sinr_calc_method, equalizer)
+
+
+def make_pusch_evm_options(enable_evm=1, reserved_=0, **proc):
+    """A PuschEvmOptions; the keywords of make_pusch_proc_options fill its `proc`."""
+    return PuschEvmOptions(make_pusch_proc_options(**proc), enable_evm, reserved_)
 
 
 PUSCH_CSI2_MAX_ENTRIES, PUSCH_CSI2_MAX_PARAMETERS, PUSCH_CSI2_MAX_ENTRY_BITS = 2, 2, 4  # NRPHY_PUSCH_CSI2_*
@@ -987,6 +997,8 @@ def declare(lib, prefix="nrphy_"):
     sig("pusch_demod_validate_ex", i32, P(PuschDemodCfg), u32, u32, u32)
     sig("pusch_demod_plan_create_ex", i32, vp, u32, P(PuschDemodCfg), P(u32), u32, u32, u32, P(u64), u32, P(vp))
     sig("pusch_demodulate_host_ex", i32, vp, P(PuschDemodCfg), vp, u32, u32, vp, vp, u32, vp, vp)
+    sig("pusch_demod_run_evm", i32, vp, vp, vp, vp, vp, u64, vp, vp, vp)
+    sig("pusch_demodulate_host_evm", i32, vp, P(PuschDemodCfg), vp, u32, u32, vp, vp, u32, vp, vp, vp)
     sig("transform_precoding_nof_prb_valid", i32, u32)
     sig("transform_deprecode", i32, vp, u32, u32, vp, vp, vp)
     sig("transform_deprecode_host", i32, vp, u32, vp, vp)
@@ -1050,6 +1062,11 @@ def declare(lib, prefix="nrphy_"):
     sig("pusch_proc_plan_harq_bytes", i32, vp, u32, P(u64), P(u64))
     sig("pusch_proc_run", i32, vp, vp, vp, vp, vp, vp, vp)
     sig("pusch_proc_host", i32, vp, P(PuschPdu), P(PuschProcOptions), vp, u32, u32, vp, vp, vp, vp, P(PuschResult))
+    sig("pusch_evm_validate", i32, P(PuschPdu), P(PuschEvmOptions), u32, u32)
+    sig("pusch_evm_plan_create", i32, vp, u32, P(PuschPdu), P(PuschEvmOptions), P(u32), u32, u32, u32, P(u64), P(u64), P(u64), P(u64),
+        P(vp))
+    sig("pusch_evm_host", i32, vp, P(PuschPdu), P(PuschEvmOptions), vp, u32, u32, vp, vp, vp, vp, P(PuschResult))
+    sig("pusch_evm_slot", i32, vp, u32, u32, P(PuschPdu), P(PuschEvmOptions), P(u64), P(u64))
     sig("pusch_csi2_size", i32, P(PuschCsi2Desc), vp, u32, P(u32))
     sig("pusch_csi2_validate", i32, P(PuschPdu), P(PuschCsi2Desc), P(PuschProcOptions), u32, u32)
     sig("pusch_csi2_variants", i32, P(PuschPdu), P(PuschCsi2Desc), P(PuschProcOptions), u32, u32, P(u32), P(u32), P(UlschInfo))
@@ -1140,6 +1157,7 @@ ABI_SYMBOLS = [
     "nrphy_pusch_demod_plan_create", "nrphy_pusch_demod_plan_destroy", "nrphy_pusch_demod_plan_codeword_bits",
     "nrphy_pusch_demod_run", "nrphy_pusch_demodulate_host",
     "nrphy_pusch_demod_validate_ex", "nrphy_pusch_demod_plan_create_ex", "nrphy_pusch_demodulate_host_ex",
+    "nrphy_pusch_demod_run_evm", "nrphy_pusch_demodulate_host_evm",
     "nrphy_transform_precoding_nof_prb_valid", "nrphy_transform_deprecode", "nrphy_transform_deprecode_host",
     "nrphy_pusch_chest_validate", "nrphy_pusch_chest_plan_create", "nrphy_pusch_chest_plan_destroy", "nrphy_pusch_chest_run",
     "nrphy_pusch_chest_host",
@@ -1158,6 +1176,7 @@ ABI_SYMBOLS = [
     "nrphy_ul_sch_info", "nrphy_pusch_proc_validate", "nrphy_pusch_proc_derive", "nrphy_pusch_proc_harq_bytes",
     "nrphy_pusch_proc_plan_create", "nrphy_pusch_proc_plan_destroy", "nrphy_pusch_proc_plan_harq_bytes", "nrphy_pusch_proc_run",
     "nrphy_pusch_proc_host",
+    "nrphy_pusch_evm_validate", "nrphy_pusch_evm_plan_create", "nrphy_pusch_evm_host", "nrphy_pusch_evm_slot",
     "nrphy_pusch_csi2_size", "nrphy_pusch_csi2_validate", "nrphy_pusch_csi2_variants", "nrphy_pusch_csi2_harq_bytes",
     "nrphy_pusch_csi2_plan_create", "nrphy_pusch_csi2_plan_destroy", "nrphy_pusch_csi2_run", "nrphy_pusch_csi2_host",
     "nrphy_ofdm_demod_symbols",

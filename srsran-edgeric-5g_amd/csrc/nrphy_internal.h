@@ -424,6 +424,11 @@ struct PuschTpItem {                          // one OFDM symbol of a transform-
   uint32_t bit_offset, nof_vector;            // as in PuschDemodItem
   uint32_t dft;                               // its entry of PuschDemodLaunch::dft
 };
+struct PuschEvmDesc {                         // one PUSCH of a plan, for the EVM: its OFDM symbols with data, ascending
+  uint32_t nof_symbols;
+  uint32_t item_first[NRPHY_NSYMB + 1];       // symbol k's partial sums are [item_first[k], item_first[k + 1]) of evm_partial
+  uint32_t count[NRPHY_NSYMB];                // n_s = data RE x layers: the block evm_calculator::calculate is handed
+};
 struct PuschDemodLaunch {
   const PuschDemodDesc* desc;
   const PuschDemodItem* items;
@@ -441,6 +446,11 @@ struct PuschDemodLaunch {
   double*               partial;              // [item][2]: sum and count of the finite equalised noise variances
   float*                sinr;                 // may be null
   uint32_t              grid_nof_ports, grid_nof_subc, n_pusch, n_items, n_tp_items;
+  // The EVM (nrphy_pusch_demod_run_evm); evm null: not computed, and nothing below is read.
+  const PuschEvmDesc*   evm_desc;
+  double*               evm_partial;          // [item]: sum of |m - x|^2 over the item's equalised symbols
+  float*                evm;                  // [pusch]
+  float                 evm_scale[5];         // the mapper's float scale per entry of `demod`
 };
 hipError_t launch_pusch_demod(const PuschDemodLaunch& p, hipStream_t stream);
 struct EqualizeLaunch {
@@ -734,6 +744,7 @@ struct PuschProcDesc {
   uint32_t nof_harq_ack, nof_csi_part1;
   uint32_t sinr_method;                  // NRPHY_PUSCH_SINR_*
   uint64_t harq_ack_offset, csi_part1_offset;
+  uint32_t has_evm, reserved_;           // the demodulator ran with the EVM (nrphy_pusch_evm_*): one value over a plan
 };
 struct PuschProcLaunch {
   const PuschProcDesc*            desc;
@@ -743,6 +754,7 @@ struct PuschProcLaunch {
   const uint32_t*                 status;  // the UCI decoder's statuses
   nrphy_pusch_result_t*           result;  // [n]
   uint32_t                        n;
+  const float*                    evm;     // [n] the demodulator's EVM; read where the descriptor has has_evm
 };
 hipError_t launch_pusch_proc_result(const PuschProcLaunch& p, hipStream_t stream);
 

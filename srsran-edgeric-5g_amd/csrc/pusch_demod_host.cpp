@@ -3,7 +3,8 @@
 // (pusch_demodulator_impl.cpp:135-160: the RE masks of data and DM-RS symbols, c_init) and cuts every OFDM symbol's data RE into
 // work items of up to PUSCH_DEMOD_THREADS, each with its codeword bit offset and its place in the symbol's demapper span.  A
 // transform-precoded PUSCH (the _ex forms with NRPHY_PUSCH_DEMOD_TRANSFORM_PRECODING) gets one item per OFDM symbol, in a list
-// of its own, and the stage list and twiddle table of its transform size.
+// of its own, and the stage list and twiddle table of its transform size.  For the EVM (nrphy_pusch_demod_run_evm) the plan also
+// says where each OFDM symbol's items start and how many equalised symbols it has, and holds one more partial sum per item.
 #include "pusch_alloc_host.h"
 
 #include <cmath>
@@ -95,6 +96,8 @@ struct nrphy_pusch_demod_plan {
   uint16_t*             d_prbs    = nullptr;
   DemodLaunch*          d_demod   = nullptr;
   double*               d_partial = nullptr;
+  PuschEvmDesc*         d_evm_desc = nullptr;
+  double*               d_evm_partial = nullptr; // behind d_partial
 };
 
 extern "C" int nrphy_pusch_demod_validate(const nrphy_pusch_demod_cfg_t* cfg, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
@@ -156,6 +159,7 @@ extern "C" int nrphy_pusch_demod_plan_create_ex(nrphy_ctx_t* ctx, uint32_t n, co
     return NRPHY_ERR_ARGUMENT;
   }
   std::vector<PuschDemodDesc> desc(n);
+  std::vector<PuschEvmDesc>   evm_desc(n);
   std::vector<PuschDemodItem> items;
   std::vector<PuschTpItem>    tp_items; // transform-precoded PUSCHs: one item per OFDM symbol, a kernel of their own
   std::vector<MixedDftPlan>   dfts;     // one per distinct size
@@ -201,11 +205,15 @@ extern "C" int nrphy_pusch_demod_plan_create_ex(nrphy_ctx_t* ctx, uint32_t n, co
       }
     }
     d.item_first = (uint32_t)(c.transform_precoding != 0 ? tp_items.size() : items.size());
+    PuschEvmDesc& e = evm_desc[i];
+    std::memset(&e, 0, sizeof(e));
     for (uint32_t l = 0; l != NRPHY_NSYMB; ++l) {
       const uint32_t nre = symbol_re(c, l, nprb, dmrs_mask);
       if (nre == 0) {
         continue; // pusch_demodulator_impl.cpp:172-175
       }
+      e.item_first[e.nof_symbols] = (uint32_t)(c.transform_precoding != 0 ? tp_items.size() : items.size());
+      e.count[e.nof_symbols++]    = nre * c.nof_tx_layers;
       DemodLaunch dp;
       demod_params(modulation_of(c.qm), nre * c.nof_tx_layers, dp);
       if (c.transform_precoding != 0) {
@@ -235,12 +243,16 @@ extern "C" int nrphy_pusch_demod_plan_create_ex(nrphy_ctx_t* ctx, uint32_t n, co
       bit += nre * nb;
     }
     d.nof_items = (uint32_t)(c.transform_precoding != 0 ? tp_items.size() : items.size()) - d.item_first;
+    e.item_first[e.nof_symbols] = d.item_first + d.nof_items;
     cw_bits[i]  = bit;
   }
   // The partial sums of the transform-precoded items follow those of the plain ones.
   for (uint32_t i = 0; i != n; ++i) {
     if (cfgs[i].transform_precoding != 0) {
       desc[i].item_first += (uint32_t)items.size();
+      for (uint32_t k = 0; k <= evm_desc[i].nof_symbols; ++k) {
+        evm_desc[i].item_first[k] += (uint32_t)items.size();
+      }
     }
   }
   DemodLaunch demod[5];
@@ -266,7 +278,8 @@ extern "C" int nrphy_pusch_demod_plan_create_ex(nrphy_ctx_t* ctx, uint32_t n, co
   plan->grid_nof_ports = grid_nof_ports;
   plan->grid_nof_subc  = grid_nof_subc;
   plan->cw_bits        = std::move(cw_bits);
-  // One allocation, one upload of the host-built tables; behind them what the kernel writes: two partial sums per item.
+  // One allocation, one upload of the host-built tables; behind them what the kernel writes: two partial sums per item, and a
+  // third, in an array of its own behind those, where a run takes the EVM.
   DeviceArena arena;
   arena.add(&plan->d_desc, desc.data(), desc.size() * sizeof(PuschDemodDesc));
   arena.add(&plan->d_items, items.data(), items.size() * sizeof(PuschDemodItem));
@@ -274,11 +287,13 @@ extern "C" int nrphy_pusch_demod_plan_create_ex(nrphy_ctx_t* ctx, uint32_t n, co
   arena.add(&plan->d_demod, demod, sizeof(demod));
   arena.add(&plan->d_tp_items, tp_items.data(), tp_items.size() * sizeof(PuschTpItem));
   arena.add(&plan->d_dft, dfts.data(), dfts.size() * sizeof(MixedDftPlan));
-  if (arena.commit(&plan->d_arena, (items.size() + tp_items.size()) * 2 * sizeof(double), (void**)&plan->d_partial) !=
+  arena.add(&plan->d_evm_desc, evm_desc.data(), evm_desc.size() * sizeof(PuschEvmDesc));
+  if (arena.commit(&plan->d_arena, (items.size() + tp_items.size()) * 3 * sizeof(double), (void**)&plan->d_partial) !=
       hipSuccess) {
     nrphy_pusch_demod_plan_destroy(plan);
     return NRPHY_ERR_DEVICE;
   }
+  plan->d_evm_partial = plan->d_partial + 2 * (items.size() + tp_items.size());
   *out = plan;
   return NRPHY_OK;
 }
@@ -291,8 +306,15 @@ extern "C" uint64_t nrphy_pusch_demod_plan_codeword_bits(const nrphy_pusch_demod
 extern "C" int nrphy_pusch_demod_run(nrphy_pusch_demod_plan_t* plan, const void* d_grid, const void* d_ch_est,
                                      const float* d_noise_vars, int8_t* d_llr, uint64_t llr_stride, float* d_sinr_db, void* stream)
 {
+  return nrphy_pusch_demod_run_evm(plan, d_grid, d_ch_est, d_noise_vars, d_llr, llr_stride, d_sinr_db, nullptr, stream);
+}
+
+extern "C" int nrphy_pusch_demod_run_evm(nrphy_pusch_demod_plan_t* plan, const void* d_grid, const void* d_ch_est,
+                                         const float* d_noise_vars, int8_t* d_llr, uint64_t llr_stride, float* d_sinr_db,
+                                         float* d_evm, void* stream)
+{
   if (plan == nullptr || d_grid == nullptr || d_ch_est == nullptr || d_noise_vars == nullptr || d_llr == nullptr ||
-      (((uintptr_t)d_grid | (uintptr_t)d_ch_est | (uintptr_t)d_noise_vars | (uintptr_t)d_sinr_db) & 3U) != 0) {
+      (((uintptr_t)d_grid | (uintptr_t)d_ch_est | (uintptr_t)d_noise_vars | (uintptr_t)d_sinr_db | (uintptr_t)d_evm) & 3U) != 0) {
     return NRPHY_ERR_ARGUMENT;
   }
   if (plan->n > 1) {
@@ -323,6 +345,16 @@ extern "C" int nrphy_pusch_demod_run(nrphy_pusch_demod_plan_t* plan, const void*
   p.grid_nof_subc  = plan->grid_nof_subc;
   p.n_pusch        = plan->n;
   p.n_items        = plan->n_items;
+  p.evm_desc       = plan->d_evm_desc;
+  p.evm_partial    = plan->d_evm_partial;
+  p.evm            = d_evm;
+  // modulation_mapper_lut_impl.cpp:58-64: scaling = std::sqrt(1 / avg_power) in float, avg_power = 2, 10, 42, 170; the
+  // pi/2-BPSK tables hold (float)M_SQRT1_2.
+  const float avg_power[4] = {2.0f, 10.0f, 42.0f, 170.0f};
+  for (uint32_t m = 0; m != 4; ++m) {
+    p.evm_scale[m] = std::sqrt(1.0f / avg_power[m]);
+  }
+  p.evm_scale[4] = (float)M_SQRT1_2;
   HIP_TRY(hipSetDevice(plan->ctx->device));
   HIP_TRY(launch_pusch_demod(p, stream ? (hipStream_t)stream : plan->ctx->stream));
   return NRPHY_OK;
@@ -349,6 +381,14 @@ extern "C" int nrphy_pusch_demodulate_host_ex(nrphy_ctx_t* ctx, const nrphy_pusc
                                               uint32_t grid_nof_ports, uint32_t grid_nof_subc, const void* ch_est,
                                               const float* noise_vars, uint32_t features, int8_t* llr, float* sinr_db)
 {
+  return nrphy_pusch_demodulate_host_evm(ctx, cfg, grid, grid_nof_ports, grid_nof_subc, ch_est, noise_vars, features, llr, sinr_db,
+                                         nullptr);
+}
+
+extern "C" int nrphy_pusch_demodulate_host_evm(nrphy_ctx_t* ctx, const nrphy_pusch_demod_cfg_t* cfg, const void* grid,
+                                               uint32_t grid_nof_ports, uint32_t grid_nof_subc, const void* ch_est,
+                                               const float* noise_vars, uint32_t features, int8_t* llr, float* sinr_db, float* evm)
+{
   if (ctx == nullptr || grid == nullptr || ch_est == nullptr || noise_vars == nullptr || llr == nullptr ||
       validate(cfg, grid_nof_ports, grid_nof_subc, features) != NRPHY_OK) {
     return NRPHY_ERR_ARGUMENT;
@@ -361,14 +401,15 @@ extern "C" int nrphy_pusch_demodulate_host_ex(nrphy_ctx_t* ctx, const nrphy_pusc
     nv[i] = noise_vars[i];
   }
   HostCall call(ctx);
-  uint8_t* d[5]; // grid, estimates, noise variances, soft bits, SINR
-  if (!call.carve(SCRATCH_RX, {grid_bytes, ce_bytes, sizeof(nv), (size_t)G, sizeof(float)}, d)) {
+  uint8_t* d[6]; // grid, estimates, noise variances, soft bits, SINR, EVM
+  if (!call.carve(SCRATCH_RX, {grid_bytes, ce_bytes, sizeof(nv), (size_t)G, sizeof(float), sizeof(float)}, d)) {
     return NRPHY_ERR_DEVICE;
   }
   void *  d_grid = d[0], *d_ce = d[1];
   float*  d_nv   = (float*)d[2];
   int8_t* d_llr  = (int8_t*)d[3];
   float*  d_sinr = (float*)d[4];
+  float*  d_evm  = evm != nullptr ? (float*)d[5] : nullptr; // without it the launches are those of nrphy_pusch_demod_run
   HIP_TRY(hipMemcpy(d_grid, grid, grid_bytes, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_ce, ch_est, ce_bytes, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_nv, nv, sizeof(nv), hipMemcpyHostToDevice));
@@ -379,10 +420,11 @@ extern "C" int nrphy_pusch_demodulate_host_ex(nrphy_ctx_t* ctx, const nrphy_pusc
   if (rc != NRPHY_OK) {
     return rc;
   }
-  rc = nrphy_pusch_demod_run(plan, d_grid, d_ce, d_nv, d_llr, G, d_sinr, ctx->stream);
+  rc = nrphy_pusch_demod_run_evm(plan, d_grid, d_ce, d_nv, d_llr, G, d_sinr, d_evm, ctx->stream);
   if (rc == NRPHY_OK && (call.sync() != hipSuccess ||
                          hipMemcpy(llr, d_llr, G, hipMemcpyDeviceToHost) != hipSuccess ||
-                         (sinr_db != nullptr && hipMemcpy(sinr_db, d_sinr, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))) {
+                         (sinr_db != nullptr && hipMemcpy(sinr_db, d_sinr, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) ||
+                         (evm != nullptr && hipMemcpy(evm, d_evm, sizeof(float), hipMemcpyDeviceToHost) != hipSuccess))) {
     rc = NRPHY_ERR_DEVICE;
   }
   nrphy_pusch_demod_plan_destroy(plan);

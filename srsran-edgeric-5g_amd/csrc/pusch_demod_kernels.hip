@@ -83,7 +83,46 @@ struct PuschDemodShared {
   uint32_t seq[SEQ_WORDS];
   double   red[2][PUSCH_DEMOD_THREADS / WAVE];
   __attribute__((aligned(16))) uint8_t stage[STAGE_BYTES];
+  double   evm_red[PUSCH_DEMOD_THREADS / WAVE]; // behind what the path without EVM uses, which stays where it was
 };
+
+// ---- EVM (nrphy_pusch_demod_run_evm) -------------------------------------------------------------------------------------------
+// evm_calculator_generic_impl::calculate (R/lib/phy/upper/channel_modulation/evm_calculator_generic_impl.cpp:30-73) is handed,
+// per OFDM symbol, the equalised (deprecoded) symbols x_j and the demapper's soft bits before descrambling
+// (pusch_demodulator_impl.cpp:244-252): hard decisions (1 where the soft bit is <= 0), those mapped to the constellation point
+// m_j (modulation_mapper_lut_impl.cpp:39-65: levels +-1, +-3, ... times one float per modulation; pi/2-BPSK alternates two
+// tables by the parity of j), then sqrt(sum |m_j - x_j|^2 / n).  A lane has x_j and the soft bits in registers at one point of
+// the item; evm_term is what it adds there: the float term with the reference's roundings (srsvec::subtract, then the
+// re * re + im * im of srsvec::dot_prod), summed in double by the reduction the SINR sums take.
+template <uint32_t MOD>
+__device__ __forceinline__ float evm_term(const LlrBytes& out, uint32_t first, uint32_t j, float re, float im, float scale)
+{
+  constexpr uint32_t QM = demod_qm<MOD>();
+  int                s[QM]; // 1 - 2 b of the symbol's hard bits b
+#pragma unroll
+  for (uint32_t k = 0; k != QM; ++k) {
+    s[k] = (int8_t)out.get(first + k) <= 0 ? -1 : 1;
+  }
+  int lr, li;
+  if constexpr (MOD == NRPHY_MOD_PI2_BPSK) {
+    lr = (j & 1u) ? -s[0] : s[0];
+    li = s[0];
+  } else if constexpr (MOD == NRPHY_MOD_QPSK) {
+    lr = s[0];
+    li = s[1];
+  } else if constexpr (MOD == NRPHY_MOD_QAM16) {
+    lr = s[0] * (2 - s[2]);
+    li = s[1] * (2 - s[3]);
+  } else if constexpr (MOD == NRPHY_MOD_QAM64) {
+    lr = s[0] * (4 - s[2] * (2 - s[4]));
+    li = s[1] * (4 - s[3] * (2 - s[5]));
+  } else {
+    lr = s[0] * (8 - s[2] * (4 - s[4] * (2 - s[6])));
+    li = s[1] * (8 - s[3] * (4 - s[5] * (2 - s[7])));
+  }
+  const float dr = __fsub_rn(__fmul_rn((float)lr, scale), re), di = __fsub_rn(__fmul_rn((float)li, scale), im);
+  return __fadd_rn(__fmul_rn(dr, dr), __fmul_rn(di, di));
+}
 
 // Stage bytes [lo, hi) -> base[lo, hi), base 16-byte aligned and the stage at the same phase: 16-byte stores, bytes at the ends.
 __device__ __forceinline__ void store_staged(const uint8_t* stage, int8_t* base, uint32_t lo, uint32_t hi, uint32_t tid)
@@ -107,7 +146,7 @@ __device__ __forceinline__ void store_staged(const uint8_t* stage, int8_t* base,
   }
 }
 
-template <uint32_t MOD>
+template <uint32_t MOD, bool EVM>
 __device__ __forceinline__ void pusch_demod_item(const PuschDemodLaunch& p, const PuschDemodItem& it, const PuschDemodDesc& d,
                                                  PuschDemodShared& s)
 {
@@ -158,7 +197,7 @@ __device__ __forceinline__ void pusch_demod_item(const PuschDemodLaunch& p, cons
   __syncthreads();
 
   LlrBytes out;
-  double   vsum = 0.0, vcnt = 0.0;
+  double   vsum = 0.0, vcnt = 0.0, esum = 0.0;
   if (active) {
     float nv[NRPHY_MAX_PORTS];
 #pragma unroll
@@ -181,6 +220,9 @@ __device__ __forceinline__ void pusch_demod_item(const PuschDemodLaunch& p, cons
           vsum += (double)v[l];
           vcnt += 1.0;
         }
+        if constexpr (EVM) { // the RE with infinite variance count: soft bits 0, hard bits 1
+          esum += (double)evm_term<MOD>(out, l * QM, j, x[l].x, x[l].y, p.evm_scale[demod_slot<MOD>()]);
+        }
       }
     }
     // Descrambling: this lane's nb <= 16 soft bits start at bit b0 of the sequence words.
@@ -200,6 +242,12 @@ __device__ __forceinline__ void pusch_demod_item(const PuschDemodLaunch& p, cons
     s.red[0][tid / WAVE] = vsum;
     s.red[1][tid / WAVE] = vcnt;
   }
+  if constexpr (EVM) {
+    esum = wave_sum(esum);
+    if (lane == 0) {
+      s.evm_red[tid / WAVE] = esum;
+    }
+  }
 
   // Soft bits staged at the destination's 16-byte phase.
   int8_t*        dst   = p.llr + (size_t)it.pusch * p.llr_stride + it.bit_offset;
@@ -218,10 +266,15 @@ __device__ __forceinline__ void pusch_demod_item(const PuschDemodLaunch& p, cons
     double* part = p.partial + 2u * (size_t)(blockIdx.x);
     part[0]      = (s.red[0][0] + s.red[0][1]) + (s.red[0][2] + s.red[0][3]);
     part[1]      = (s.red[1][0] + s.red[1][1]) + (s.red[1][2] + s.red[1][3]);
+    if constexpr (EVM) {
+      p.evm_partial[blockIdx.x] = (s.evm_red[0] + s.evm_red[1]) + (s.evm_red[2] + s.evm_red[3]);
+    }
   }
   store_staged(s.stage, dst - shift, shift, shift + it.count * nb, tid);
 }
 
+// EVM: whether the launch computes the EVM's partial sums as well; the instantiation without is the kernel as it was.
+template <bool EVM>
 __global__ __launch_bounds__(PUSCH_DEMOD_THREADS) void pusch_demod_kernel(PuschDemodLaunch p)
 {
   __shared__ PuschDemodShared s;
@@ -229,19 +282,19 @@ __global__ __launch_bounds__(PUSCH_DEMOD_THREADS) void pusch_demod_kernel(PuschD
   const PuschDemodDesc& d  = p.desc[it.pusch]; // read in place: dmrs_subc is indexed per lane
   switch (d.qm) { // workgroup-uniform
     case 1:
-      pusch_demod_item<NRPHY_MOD_PI2_BPSK>(p, it, d, s);
+      pusch_demod_item<NRPHY_MOD_PI2_BPSK, EVM>(p, it, d, s);
       break;
     case NRPHY_MOD_QPSK:
-      pusch_demod_item<NRPHY_MOD_QPSK>(p, it, d, s);
+      pusch_demod_item<NRPHY_MOD_QPSK, EVM>(p, it, d, s);
       break;
     case NRPHY_MOD_QAM16:
-      pusch_demod_item<NRPHY_MOD_QAM16>(p, it, d, s);
+      pusch_demod_item<NRPHY_MOD_QAM16, EVM>(p, it, d, s);
       break;
     case NRPHY_MOD_QAM64:
-      pusch_demod_item<NRPHY_MOD_QAM64>(p, it, d, s);
+      pusch_demod_item<NRPHY_MOD_QAM64, EVM>(p, it, d, s);
       break;
     default:
-      pusch_demod_item<NRPHY_MOD_QAM256>(p, it, d, s);
+      pusch_demod_item<NRPHY_MOD_QAM256, EVM>(p, it, d, s);
       break;
   }
 }
@@ -265,9 +318,10 @@ struct PuschTpShared {
   Tables   t;
   uint32_t seq[TP_SEQ_WORDS];
   double   red[2][PUSCH_DEMOD_THREADS / WAVE];
+  double   evm_red[PUSCH_DEMOD_THREADS / WAVE];
 };
 
-template <uint32_t MOD>
+template <uint32_t MOD, bool EVM>
 __device__ __forceinline__ void pusch_tp_item(const PuschDemodLaunch& p, const PuschTpItem& it, const PuschDemodDesc& d,
                                               const MixedDftPlan& plan, PuschTpShared& s)
 {
@@ -288,7 +342,7 @@ __device__ __forceinline__ void pusch_tp_item(const PuschDemodLaunch& p, const P
   const float nv_max = max_noise(nv, P);
 
   // Gather and equalise: one layer, 12 data RE per PRB on every symbol that carries data.
-  double       vsum = 0.0, vcnt = 0.0;
+  double       vsum = 0.0, vcnt = 0.0, esum = 0.0;
   const size_t nsubc = p.grid_nof_subc;
   for (uint32_t r = tid; r < it.count; r += PUSCH_DEMOD_THREADS) {
     const uint32_t ord  = r / NRPHY_NRE;
@@ -338,6 +392,9 @@ __device__ __forceinline__ void pusch_tp_item(const PuschDemodLaunch& p, const P
     } else {
       demodulate_symbol<MOD, false>(dm, s.t, r, re, im, s.var[r], out, 0);
     }
+    if constexpr (EVM) { // the deprecoded symbol and its soft bits before descrambling
+      esum += (double)evm_term<MOD>(out, 0, r, re, im, p.evm_scale[demod_slot<MOD>()]);
+    }
     const uint32_t b0   = (it.bit_offset & 31u) + r * QM;
     const uint64_t pair = ((uint64_t)s.seq[b0 >> 5] << 32) | s.seq[(b0 >> 5) + 1u];
     const uint32_t bits = (uint32_t)(pair >> (48u - (b0 & 31u))) & 0xFFFFu; // first soft bit in bit 15
@@ -359,15 +416,25 @@ __device__ __forceinline__ void pusch_tp_item(const PuschDemodLaunch& p, const P
     s.red[0][tid / WAVE] = vsum;
     s.red[1][tid / WAVE] = vcnt;
   }
+  if constexpr (EVM) { // a thread's symbols in ascending order, then as the SINR sums
+    esum = wave_sum(esum);
+    if (lane == 0) {
+      s.evm_red[tid / WAVE] = esum;
+    }
+  }
   __syncthreads();
   if (tid == 0) {
     double* part = p.partial + 2u * (size_t)(p.n_items + blockIdx.x);
     part[0]      = (s.red[0][0] + s.red[0][1]) + (s.red[0][2] + s.red[0][3]);
     part[1]      = (s.red[1][0] + s.red[1][1]) + (s.red[1][2] + s.red[1][3]);
+    if constexpr (EVM) {
+      p.evm_partial[p.n_items + blockIdx.x] = (s.evm_red[0] + s.evm_red[1]) + (s.evm_red[2] + s.evm_red[3]);
+    }
   }
   store_staged(stage, dst - shift, shift, shift + it.count * QM, tid);
 }
 
+template <bool EVM>
 __global__ __launch_bounds__(PUSCH_DEMOD_THREADS) void pusch_tp_demod_kernel(PuschDemodLaunch p)
 {
   __shared__ PuschTpShared s;
@@ -376,19 +443,19 @@ __global__ __launch_bounds__(PUSCH_DEMOD_THREADS) void pusch_tp_demod_kernel(Pus
   const MixedDftPlan&   plan = p.dft[it.dft]; // read in place: a copy indexed by the stage would be put in LDS
   switch (d.qm) { // workgroup-uniform
     case 1:
-      pusch_tp_item<NRPHY_MOD_PI2_BPSK>(p, it, d, plan, s);
+      pusch_tp_item<NRPHY_MOD_PI2_BPSK, EVM>(p, it, d, plan, s);
       break;
     case NRPHY_MOD_QPSK:
-      pusch_tp_item<NRPHY_MOD_QPSK>(p, it, d, plan, s);
+      pusch_tp_item<NRPHY_MOD_QPSK, EVM>(p, it, d, plan, s);
       break;
     case NRPHY_MOD_QAM16:
-      pusch_tp_item<NRPHY_MOD_QAM16>(p, it, d, plan, s);
+      pusch_tp_item<NRPHY_MOD_QAM16, EVM>(p, it, d, plan, s);
       break;
     case NRPHY_MOD_QAM64:
-      pusch_tp_item<NRPHY_MOD_QAM64>(p, it, d, plan, s);
+      pusch_tp_item<NRPHY_MOD_QAM64, EVM>(p, it, d, plan, s);
       break;
     default:
-      pusch_tp_item<NRPHY_MOD_QAM256>(p, it, d, plan, s);
+      pusch_tp_item<NRPHY_MOD_QAM256, EVM>(p, it, d, plan, s);
       break;
   }
 }
@@ -410,6 +477,39 @@ __global__ __launch_bounds__(WAVE) void pusch_sinr_kernel(PuschDemodLaunch p)
   }
 }
 
+// One wave per PUSCH: lane k adds the partial sums of the PUSCH's k-th OFDM symbol with data in item order and takes the symbol's
+// EVM, e_s = sqrt(P_s / n_s) (evm_calculator_generic_impl.cpp:72); then every lane runs pusch_demodulator_impl.cpp:249-251 and
+// :275 over the symbols in ascending order in float -- acc += n_s * e_s, cnt += n_s, acc / cnt -- and lane 0 stores.
+__global__ __launch_bounds__(WAVE) void pusch_evm_kernel(PuschDemodLaunch p)
+{
+  const uint32_t      lane = threadIdx.x;
+  const PuschEvmDesc& d    = p.evm_desc[blockIdx.x];
+  float               e    = 0.f;
+  uint32_t            n    = 0;
+  if (lane < d.nof_symbols) {
+    double sum = 0.0;
+    for (uint32_t k = d.item_first[lane]; k != d.item_first[lane + 1u]; ++k) {
+      sum += p.evm_partial[k];
+    }
+    n = d.count[lane];
+    e = __fsqrt_rn((float)(sum / (double)n));
+  }
+  float    acc = 0.f;
+  uint32_t cnt = 0;
+#pragma unroll
+  for (uint32_t k = 0; k != NRPHY_NSYMB; ++k) {
+    const float    ek = __shfl(e, k);
+    const uint32_t nk = __shfl(n, k);
+    if (k < d.nof_symbols) {
+      acc = __fadd_rn(acc, __fmul_rn((float)nk, ek));
+      cnt += nk;
+    }
+  }
+  if (lane == 0) {
+    p.evm[blockIdx.x] = __fdiv_rn(acc, (float)cnt); // a plan has no PUSCH without data RE
+  }
+}
+
 } // namespace
 
 hipError_t launch_channel_equalize(const EqualizeLaunch& p, hipStream_t stream)
@@ -426,14 +526,20 @@ hipError_t launch_pusch_demod(const PuschDemodLaunch& p, hipStream_t stream)
   if (p.n_items == 0 && p.n_tp_items == 0) {
     return hipSuccess;
   }
+  const bool evm = p.evm != nullptr; // uniform over the launch: the kernels without EVM are the ones of nrphy_pusch_demod_run
   if (p.n_items != 0) {
-    hipLaunchKernelGGL(pusch_demod_kernel, dim3(p.n_items), dim3(PUSCH_DEMOD_THREADS), 0, stream, p);
+    hipLaunchKernelGGL(evm ? pusch_demod_kernel<true> : pusch_demod_kernel<false>, dim3(p.n_items), dim3(PUSCH_DEMOD_THREADS), 0,
+                       stream, p);
   }
   if (p.n_tp_items != 0) {
-    hipLaunchKernelGGL(pusch_tp_demod_kernel, dim3(p.n_tp_items), dim3(PUSCH_DEMOD_THREADS), 0, stream, p);
+    hipLaunchKernelGGL(evm ? pusch_tp_demod_kernel<true> : pusch_tp_demod_kernel<false>, dim3(p.n_tp_items),
+                       dim3(PUSCH_DEMOD_THREADS), 0, stream, p);
   }
   if (p.sinr != nullptr) {
     hipLaunchKernelGGL(pusch_sinr_kernel, dim3(p.n_pusch), dim3(WAVE), 0, stream, p);
+  }
+  if (evm) {
+    hipLaunchKernelGGL(pusch_evm_kernel, dim3(p.n_pusch), dim3(WAVE), 0, stream, p);
   }
   return hipGetLastError();
 }

@@ -2,7 +2,8 @@
 // stages (R/lib/phy/upper/channel_processors/pusch/pusch_processor_impl.cpp:115-336) -- the checks of assert_pdu and of the PDU
 // validator, the UL-SCH information, one PDU turned into the configurations of the estimator, the demodulator, the demultiplexer,
 // the UCI decoders and the transport-block decoder -- and the plan that owns the stage plans and the buffers between them.  The
-// stages themselves are the library's: this file launches nothing but the result kernel.
+// stages themselves are the library's: this file launches nothing but the result kernel.  One implementation serves
+// nrphy_pusch_proc_* and nrphy_pusch_evm_*: the former are the latter with enable_evm = 0.
 #include "ldpc_receive_host.h"
 #include "pusch_alloc_host.h"
 #include "pusch_proc_plan_host.h"
@@ -19,16 +20,30 @@ uint64_t align_up(uint64_t v, uint64_t a = ALIGN)
   return (v + a - 1) / a * a;
 }
 
-int derive(const nrphy_pusch_pdu_t* p, const nrphy_pusch_proc_options_t* o, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
+// The options of a nrphy_pusch_proc_* call as those of its nrphy_pusch_evm_* namesake (null stays null).
+struct WithoutEvm {
+  nrphy_pusch_evm_options_t        value;
+  const nrphy_pusch_evm_options_t* ptr;
+  explicit WithoutEvm(const nrphy_pusch_proc_options_t* o) : value{}, ptr(o != nullptr ? &value : nullptr)
+  {
+    if (o != nullptr) {
+      value.proc = *o;
+    }
+  }
+};
+
+int derive(const nrphy_pusch_pdu_t* p, const nrphy_pusch_evm_options_t* eo, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
            nrphy_pusch_proc_derived_t& d)
 {
   std::memset(&d, 0, sizeof(d));
-  if (p == nullptr || o == nullptr) {
+  if (p == nullptr || eo == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
-  // The processor's configuration.
-  if (o->dec_nof_iterations == 0 || o->dec_enable_early_stop > 1 ||
-      (o->csi_sinr_calc_method != NRPHY_PUSCH_SINR_CHANNEL_ESTIMATOR && o->csi_sinr_calc_method != NRPHY_PUSCH_SINR_POST_EQUALIZATION) ||
+  const nrphy_pusch_proc_options_t* o = &eo->proc;
+  // The processor's configuration; the EVM-based SINR needs the EVM.
+  if (o->dec_nof_iterations == 0 || o->dec_enable_early_stop > 1 || eo->enable_evm > 1 || eo->reserved_ != 0 ||
+      (o->csi_sinr_calc_method != NRPHY_PUSCH_SINR_CHANNEL_ESTIMATOR && o->csi_sinr_calc_method != NRPHY_PUSCH_SINR_POST_EQUALIZATION &&
+       !(o->csi_sinr_calc_method == NRPHY_PUSCH_SINR_EVM && eo->enable_evm == 1)) ||
       (o->equalizer != NRPHY_EQ_ZF && o->equalizer != NRPHY_EQ_MMSE)) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -168,6 +183,13 @@ extern "C" int nrphy_pusch_proc_validate(const nrphy_pusch_pdu_t* pdu, const nrp
                                          uint32_t grid_nof_ports, uint32_t grid_nof_subc)
 {
   nrphy_pusch_proc_derived_t d;
+  return derive(pdu, WithoutEvm(options).ptr, grid_nof_ports, grid_nof_subc, d);
+}
+
+extern "C" int nrphy_pusch_evm_validate(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_evm_options_t* options,
+                                        uint32_t grid_nof_ports, uint32_t grid_nof_subc)
+{
+  nrphy_pusch_proc_derived_t d;
   return derive(pdu, options, grid_nof_ports, grid_nof_subc, d);
 }
 
@@ -177,7 +199,7 @@ extern "C" int nrphy_pusch_proc_derive(const nrphy_pusch_pdu_t* pdu, const nrphy
   if (out == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
-  const int rc = derive(pdu, options, grid_nof_ports, grid_nof_subc, *out);
+  const int rc = derive(pdu, WithoutEvm(options).ptr, grid_nof_ports, grid_nof_subc, *out);
   if (rc != NRPHY_OK) {
     std::memset(out, 0, sizeof(*out));
   }
@@ -200,7 +222,7 @@ extern "C" int nrphy_pusch_proc_harq_bytes(const nrphy_pusch_pdu_t* pdu, const n
     subc = std::max(subc, std::min<uint32_t>(pdu->dc_position / NRPHY_NRE + 1, NRPHY_MAX_RB) * NRPHY_NRE);
   }
   nrphy_pusch_proc_derived_t d;
-  const int                  rc = derive(pdu, options, ports, subc, d);
+  const int                  rc = derive(pdu, WithoutEvm(options).ptr, ports, subc, d);
   if (rc != NRPHY_OK) {
     return rc;
   }
@@ -243,7 +265,7 @@ extern "C" int nrphy_pusch_proc_plan_harq_bytes(const nrphy_pusch_proc_plan_t* p
 namespace {
 // The plan of PDUs whose records are at hand: `pre` (may be null) holds one accepted derivation per PDU, so that a caller that
 // derived already -- the host form -- does not derive again.
-int plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, const nrphy_pusch_proc_options_t* options,
+int plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, const nrphy_pusch_evm_options_t* options,
                 const nrphy_pusch_proc_derived_t* pre, const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports,
                 uint32_t grid_nof_subc, const uint64_t* harq_soft_offset, const uint64_t* harq_state_offset, const uint64_t* tb_offset,
                 const uint64_t* uci_offset, nrphy_pusch_proc_plan_t** out)
@@ -294,7 +316,8 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, con
     pd.nof_rx_ports = d.chest.nof_rx_ports;
     pd.has_sch      = d.has_decoder;
     pd.harq_status = pd.csi1_status = PUSCH_PROC_NO_STATUS;
-    pd.sinr_method                  = options->csi_sinr_calc_method;
+    pd.sinr_method                  = options->proc.csi_sinr_calc_method;
+    pd.has_evm                      = options->enable_evm;
   }
   // Offsets that need the common codeword stride.
   for (uint32_t i = 0; i != n && rc == NRPHY_OK; ++i) {
@@ -374,7 +397,8 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, con
                             uci_llr_bytes,
                             (uint64_t)n * 4 * sizeof(uint32_t),
                             (uint64_t)uci.size() * sizeof(uint32_t),
-                            scratch_bytes};
+                            scratch_bytes,
+                            (uint64_t)n * sizeof(float)};
   constexpr size_t NP = sizeof(piece) / sizeof(piece[0]);
   uint64_t         at[NP + 1] = {};
   for (size_t k = 0; k != NP; ++k) {
@@ -399,6 +423,7 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, con
   plan->d_dec     = (uint32_t*)(ws + at[7]);
   plan->d_status  = (uint32_t*)(ws + at[8]);
   plan->d_scratch = ws + at[9];
+  plan->d_evm     = options->enable_evm != 0 ? (float*)(ws + at[10]) : nullptr;
   *out            = plan;
   return NRPHY_OK;
 }
@@ -411,6 +436,16 @@ extern "C" int nrphy_pusch_proc_plan_create(nrphy_ctx_t* ctx, uint32_t n, const 
                                             const uint64_t* harq_state_offset, const uint64_t* tb_offset, const uint64_t* uci_offset,
                                             nrphy_pusch_proc_plan_t** out)
 {
+  return plan_create(ctx, n, pdus, WithoutEvm(options).ptr, nullptr, grid_index, nof_grids, grid_nof_ports, grid_nof_subc,
+                     harq_soft_offset, harq_state_offset, tb_offset, uci_offset, out);
+}
+
+extern "C" int nrphy_pusch_evm_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus,
+                                           const nrphy_pusch_evm_options_t* options, const uint32_t* grid_index, uint32_t nof_grids,
+                                           uint32_t grid_nof_ports, uint32_t grid_nof_subc, const uint64_t* harq_soft_offset,
+                                           const uint64_t* harq_state_offset, const uint64_t* tb_offset, const uint64_t* uci_offset,
+                                           nrphy_pusch_proc_plan_t** out)
+{
   return plan_create(ctx, n, pdus, options, nullptr, grid_index, nof_grids, grid_nof_ports, grid_nof_subc, harq_soft_offset,
                      harq_state_offset, tb_offset, uci_offset, out);
 }
@@ -419,7 +454,8 @@ int pusch_proc_run_front(nrphy_pusch_proc_plan_t* plan, const void* d_grid, uint
 {
   int rc = nrphy_pusch_chest_run(plan->chest, d_grid, plan->d_ce, plan->d_nv, plan->d_meas, stream);
   if (rc == NRPHY_OK) {
-    rc = nrphy_pusch_demod_run(plan->demod, d_grid, plan->d_ce, plan->d_nv, plan->d_llr, plan->llr_stride, plan->d_sinr, stream);
+    rc = nrphy_pusch_demod_run_evm(plan->demod, d_grid, plan->d_ce, plan->d_nv, plan->d_llr, plan->llr_stride, plan->d_sinr,
+                                   plan->d_evm, stream); // d_evm null: nrphy_pusch_demod_run
   }
   if (rc == NRPHY_OK && plan->demux != nullptr) {
     rc = nrphy_ulsch_demux_run(plan->demux, plan->d_llr, plan->d_sch, plan->d_uci_llr, plan->d_uci_llr, nullptr, stream);
@@ -449,6 +485,7 @@ int pusch_proc_run_result(nrphy_pusch_proc_plan_t* plan, nrphy_pusch_result_t* d
   p.status  = plan->d_status;
   p.result  = d_result;
   p.n       = plan->n;
+  p.evm     = plan->d_evm;
   HIP_TRY(hipSetDevice(plan->ctx->device));
   HIP_TRY(launch_pusch_proc_result(p, stream ? (hipStream_t)stream : plan->ctx->stream));
   return NRPHY_OK;
@@ -478,6 +515,14 @@ extern "C" int nrphy_pusch_proc_run(nrphy_pusch_proc_plan_t* plan, const void* d
 extern "C" int nrphy_pusch_proc_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_proc_options_t* options,
                                      const void* grid, uint32_t grid_nof_ports, uint32_t grid_nof_subc, int8_t* harq_soft,
                                      uint8_t* harq_state, uint8_t* tb, uint8_t* uci_bits, nrphy_pusch_result_t* result)
+{
+  return nrphy_pusch_evm_host(ctx, pdu, WithoutEvm(options).ptr, grid, grid_nof_ports, grid_nof_subc, harq_soft, harq_state, tb,
+                              uci_bits, result);
+}
+
+extern "C" int nrphy_pusch_evm_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_evm_options_t* options,
+                                    const void* grid, uint32_t grid_nof_ports, uint32_t grid_nof_subc, int8_t* harq_soft,
+                                    uint8_t* harq_state, uint8_t* tb, uint8_t* uci_bits, nrphy_pusch_result_t* result)
 {
   nrphy_pusch_proc_derived_t d;
   if (ctx == nullptr || grid == nullptr || result == nullptr) {

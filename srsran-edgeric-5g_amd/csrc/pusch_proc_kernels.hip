@@ -9,7 +9,7 @@
 // A record is made of at most four 32-byte measurement rows, four decoder words, two statuses and one float, so the split is the
 // PUCCH receivers': one wavefront per PDU, four per workgroup, no LDS, no barrier, no atomics, no scratch.  The PDU index is made
 // scalar (readfirstlane), so the descriptor is read with scalar loads.  Every lane issues at most two 16-byte loads -- lanes 0..3
-// a port's row, lane 4 the decoder words, lanes 5..7 the SINR and the statuses --, the values are handed round with shuffles, the
+// a port's row, lane 4 the decoder words, lanes 5..7 the SINR (with the EVM, where the plan takes one) and the statuses --, the values are handed round with shuffles, the
 // sums over the ports are taken in port order in float as the reference takes them, and lane 0 stores the record once.  log10 is
 // evaluated in double and rounded once (to_dB and the merge, CsiMerge, are exact_device.h's).  Contraction is off.
 #include "bits_device.h"
@@ -43,6 +43,9 @@ __global__ __launch_bounds__(PROC_WAVES * WAVE) void pusch_proc_result_kernel(Pu
     }
   } else if (lane == 5) {
     a.x = __float_as_uint(p.sinr_db[ip]);
+    if (d.has_evm != 0) {
+      a.y = __float_as_uint(p.evm[ip]);
+    }
   } else if (lane == 6) {
     a.x = d.harq_status != PUSCH_PROC_NO_STATUS ? p.status[d.harq_status] : NRPHY_UCI_STATUS_UNKNOWN;
   } else if (lane == 7) {
@@ -60,7 +63,7 @@ __global__ __launch_bounds__(PROC_WAVES * WAVE) void pusch_proc_result_kernel(Pu
     }
   }
   const uint32_t dec0 = __shfl(a.x, 4), dec1 = __shfl(a.y, 4), dec2 = __shfl(a.z, 4), dec3 = __shfl(a.w, 4);
-  const float    sinr_post_eq = __uint_as_float(__shfl(a.x, 5));
+  const float    sinr_post_eq = __uint_as_float(__shfl(a.x, 5)), evm = __uint_as_float(__shfl(a.y, 5));
   const uint32_t harq_status = __shfl(a.x, 6), csi1_status = __shfl(a.x, 7);
   if (lane != 0) {
     return;
@@ -84,13 +87,16 @@ __global__ __launch_bounds__(PROC_WAVES * WAVE) void pusch_proc_result_kernel(Pu
   r.sinr_ch_estimator_dB = sinr_ce;
   r.sinr_post_eq_dB      = sinr_post_eq;
   r.sinr_dB              = d.sinr_method == NRPHY_PUSCH_SINR_POST_EQUALIZATION ? sinr_post_eq : sinr_ce;
+  if (d.sinr_method == NRPHY_PUSCH_SINR_EVM) { // pusch_processor_notifier_adaptor.h:157-162, in float as there
+    r.sinr_dB = evm == 0.f ? F_INF : __fsub_rn(__fmul_rn(-20.0f, log10f(evm)), 3.7f);
+  }
   r.epre_dB              = csi.epre_dB(P);
   r.rsrp_dB              = csi.rsrp_dB(P);
   r.time_alignment_s     = csi.ta_s;
   r.cfo_hz               = has_cfo ? csi.cfo_hz : 0.f;
   r.has_cfo              = has_cfo ? 1u : 0u;
-  r.has_evm              = 0u;
-  r.evm                  = 0.f;
+  r.has_evm              = d.has_evm;
+  r.evm                  = evm; // 0 without has_evm: lane 5 left the word as it was
   p.result[ip]           = r;
 }
 

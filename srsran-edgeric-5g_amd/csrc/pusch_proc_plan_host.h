@@ -68,6 +68,7 @@ struct nrphy_pusch_proc_plan {
   uint32_t*                 d_dec     = nullptr;
   uint32_t*                 d_status  = nullptr;
   uint8_t*                  d_scratch = nullptr;
+  float*                    d_evm     = nullptr; // null unless the plan takes the EVM (nrphy_pusch_evm_plan_create)
 };
 
 #pragma GCC visibility push(hidden)

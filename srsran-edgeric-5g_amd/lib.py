@@ -455,6 +455,18 @@ class Context:
                                                        C.byref(sinr)), "nrphy_pusch_demodulate_host_ex")
         return out, float(sinr.value)
 
+    def pusch_demodulate_host_evm(self, cfg, grid, ch_est, noise_vars, features=0):
+        """pusch_demodulate_host_ex with the EVM of the reference's evm_calculator: (soft bits, SINR in dB, EVM as np.float32)."""
+        grid = np.ascontiguousarray(grid, dtype=np.uint32)
+        ch_est = np.ascontiguousarray(ch_est, dtype=np.uint32)
+        nv = np.ascontiguousarray(noise_vars, dtype=np.float32)
+        out = np.zeros(pusch_demod_codeword_bits(cfg), np.int8)
+        sinr, evm = C.c_float(0), C.c_float(0)
+        _check(self.lib.nrphy_pusch_demodulate_host_evm(self.handle, C.byref(cfg), grid.ctypes.data, grid.shape[0], grid.shape[-1],
+                                                        ch_est.ctypes.data, nv.ctypes.data, features, out.ctypes.data,
+                                                        C.byref(sinr), C.byref(evm)), "nrphy_pusch_demodulate_host_evm")
+        return out, float(sinr.value), np.float32(evm.value)
+
     def pusch_chest_host(self, cfg, grid, ch_est=None):
         """dmrs_pusch_estimator::estimate + the processor's DC step for one PUSCH: grid [ports][14][subc] raw cbf16 words ->
         (ch_est [layers][rx][14][subc] cbf16 words, noise_vars [rx], measurements [rx][2] of abi.PuschChestMeas).  ch_est: the
@@ -471,12 +483,23 @@ class Context:
         m = [[meas[i * abi.PUSCH_CHEST_MAX_LAYERS + l] for l in range(abi.PUSCH_CHEST_MAX_LAYERS)] for i in range(cfg.nof_rx_ports)]
         return ce, nv, m
 
+    def pusch_evm_host(self, pdu, options, grid, harq_soft=None, harq_state=None):
+        """pusch_proc_host with abi.PuschEvmOptions (nrphy_pusch_evm_host): with enable_evm the result carries the EVM."""
+        return self.pusch_proc_host(pdu, options, grid, harq_soft, harq_state)
+
     def pusch_proc_host(self, pdu, options, grid, harq_soft=None, harq_state=None):
         """pusch_processor::process for one PDU: grid [ports][14][subc] raw cbf16 words -> (abi.PuschResult, transport block bytes,
         UCI payload bits: HARQ-ACK then CSI part 1, one per byte).  harq_soft / harq_state: the PDU's HARQ blocks (int8 / uint8
-        arrays of pusch_proc_harq_bytes(pdu, options)), read and written in place; fresh zeroed ones when None."""
+        arrays of pusch_proc_harq_bytes(pdu, options)), read and written in place; fresh zeroed ones when None.  options: an
+        abi.PuschProcOptions, or an abi.PuschEvmOptions for nrphy_pusch_evm_host."""
         grid = np.ascontiguousarray(grid, dtype=np.uint32)
-        soft_bytes, state_bytes = pusch_proc_harq_bytes(pdu, options)
+        with_evm = isinstance(options, abi.PuschEvmOptions)
+        call = self.lib.nrphy_pusch_evm_host if with_evm else self.lib.nrphy_pusch_proc_host
+        sizing = options
+        if with_evm:  # the HARQ sizes do not depend on the SINR method, and nrphy_pusch_proc_harq_bytes refuses the EVM-based one
+            sizing = abi.PuschProcOptions(options.proc.dec_nof_iterations, options.proc.dec_enable_early_stop,
+                                          abi.PUSCH_SINR_CHANNEL_ESTIMATOR, options.proc.equalizer)
+        soft_bytes, state_bytes = pusch_proc_harq_bytes(pdu, sizing)
         soft = np.zeros(soft_bytes, np.int8) if harq_soft is None else harq_soft
         state = np.zeros(state_bytes, np.uint8) if harq_state is None else harq_state
         if soft.size != soft_bytes or state.size != state_bytes or not (soft.flags.c_contiguous and state.flags.c_contiguous):
@@ -484,10 +507,11 @@ class Context:
         tb = np.zeros(pdu.tb_size_bytes, np.uint8)
         uci = np.zeros(pdu.nof_harq_ack + pdu.nof_csi_part1, np.uint8)
         result = abi.PuschResult()
-        _check(self.lib.nrphy_pusch_proc_host(self.handle, C.byref(pdu), C.byref(options), grid.ctypes.data, grid.shape[0],
-                                              grid.shape[-1], soft.ctypes.data if soft_bytes else None,
-                                              state.ctypes.data if state_bytes else None, tb.ctypes.data if tb.size else None,
-                                              uci.ctypes.data if uci.size else None, C.byref(result)), "nrphy_pusch_proc_host")
+        _check(call(self.handle, C.byref(pdu), C.byref(options), grid.ctypes.data, grid.shape[0],
+                    grid.shape[-1], soft.ctypes.data if soft_bytes else None,
+                    state.ctypes.data if state_bytes else None, tb.ctypes.data if tb.size else None,
+                    uci.ctypes.data if uci.size else None, C.byref(result)),
+               "nrphy_pusch_evm_host" if with_evm else "nrphy_pusch_proc_host")
         return result, tb, uci
 
     def pusch_csi2_host(self, pdu, desc, options, grid, harq_soft=None, harq_state=None, csi2_fill=0):
@@ -752,7 +776,13 @@ class PuschDemodPlan:
     def codeword_bits(self, i):
         return int(self.ctx.lib.nrphy_pusch_demod_plan_codeword_bits(self.handle, i))
 
-    def run(self, d_grid, d_ch_est, d_noise_vars, d_llr, llr_stride, d_sinr=None, stream=None):
+    def run(self, d_grid, d_ch_est, d_noise_vars, d_llr, llr_stride, d_sinr=None, stream=None, d_evm=None):
+        """d_evm: [n] float32 for the EVM per PUSCH (nrphy_pusch_demod_run_evm); None is nrphy_pusch_demod_run."""
+        if d_evm is not None:
+            _check(self.ctx.lib.nrphy_pusch_demod_run_evm(self.handle, _dptr(d_grid), _dptr(d_ch_est), _dptr(d_noise_vars),
+                                                          _dptr(d_llr), llr_stride, _dptr(d_sinr), _dptr(d_evm), _stream(stream)),
+                   "nrphy_pusch_demod_run_evm")
+            return
         _check(self.ctx.lib.nrphy_pusch_demod_run(self.handle, _dptr(d_grid), _dptr(d_ch_est), _dptr(d_noise_vars), _dptr(d_llr),
                                                   llr_stride, _dptr(d_sinr), _stream(stream)), "nrphy_pusch_demod_run")
 
@@ -1043,7 +1073,8 @@ class UlschDemuxPlan:
 class PuschProcPlan:
     """nrphy_pusch_proc_plan: PUSCH PDUs over a batch of received grids; run() goes from the grids to the transport blocks, the
     UCI payloads and one abi.PuschResult per PDU on one stream.  The plan owns every buffer between the stages; the caller owns
-    the HARQ arena, the transport blocks, the UCI payload bytes and the results."""
+    the HARQ arena, the transport blocks, the UCI payload bytes and the results.  options: an abi.PuschProcOptions, or an
+    abi.PuschEvmOptions for nrphy_pusch_evm_plan_create (the results then carry the EVM)."""
 
     def __init__(self, ctx, pdus, options, grid_indices, nof_grids, nof_ports, nof_subc, harq_soft_offsets=None,
                  harq_state_offsets=None, tb_offsets=None, uci_offsets=None):
@@ -1053,8 +1084,10 @@ class PuschProcPlan:
         gidx = (C.c_uint32 * n)(*grid_indices)
         offs = [None if o is None else (C.c_uint64 * n)(*o) for o in (harq_soft_offsets, harq_state_offsets, tb_offsets, uci_offsets)]
         h = C.c_void_p()
-        _check(ctx.lib.nrphy_pusch_proc_plan_create(ctx.handle, n, arr, C.byref(options), gidx, nof_grids, nof_ports, nof_subc, *offs,
-                                                    C.byref(h)), "nrphy_pusch_proc_plan_create")
+        with_evm = isinstance(options, abi.PuschEvmOptions)
+        create = ctx.lib.nrphy_pusch_evm_plan_create if with_evm else ctx.lib.nrphy_pusch_proc_plan_create
+        _check(create(ctx.handle, n, arr, C.byref(options), gidx, nof_grids, nof_ports, nof_subc, *offs, C.byref(h)),
+               "nrphy_pusch_evm_plan_create" if with_evm else "nrphy_pusch_proc_plan_create")
         self.handle = h
         self.n = n
 
@@ -1165,6 +1198,11 @@ def ulsch_info(cfg):
 def pusch_proc_validate(pdu, options, grid_nof_ports, grid_nof_subc):
     """nrphy_pusch_proc_validate: abi.OK or abi.ERR_ARGUMENT (host only)."""
     return int(load().nrphy_pusch_proc_validate(C.byref(pdu), C.byref(options), grid_nof_ports, grid_nof_subc))
+
+
+def pusch_evm_validate(pdu, options, grid_nof_ports, grid_nof_subc):
+    """nrphy_pusch_evm_validate with an abi.PuschEvmOptions: abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_pusch_evm_validate(C.byref(pdu), C.byref(options), grid_nof_ports, grid_nof_subc))
 
 
 def pusch_proc_derive(pdu, options, grid_nof_ports, grid_nof_subc):
@@ -1615,6 +1653,14 @@ class UlSlots(_SlotPool):
         soft = (C.c_uint64 * n)(*harq_soft_offsets) if harq_soft_offsets is not None else None
         state = (C.c_uint64 * n)(*harq_state_offsets) if harq_state_offsets is not None else None
         return int(self.ctx.lib.nrphy_ul_slot_pusch(self.handle, sid, n, arr, C.byref(options), soft, state))
+
+    def pusch_evm(self, sid, pdus, options, harq_soft_offsets=None, harq_state_offsets=None):
+        """pusch() with an abi.PuschEvmOptions (nrphy_pusch_evm_slot); the results append to the same list."""
+        n = len(pdus)
+        arr = (abi.PuschPdu * n)(*pdus)
+        soft = (C.c_uint64 * n)(*harq_soft_offsets) if harq_soft_offsets is not None else None
+        state = (C.c_uint64 * n)(*harq_state_offsets) if harq_state_offsets is not None else None
+        return int(self.ctx.lib.nrphy_pusch_evm_slot(self.handle, sid, n, arr, C.byref(options), soft, state))
 
     def pucch(self, sid, cfgs):
         arr = (abi.PucchCfg * len(cfgs))(*cfgs)
