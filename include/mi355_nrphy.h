@@ -106,7 +106,8 @@ typedef struct nrphy_pdsch_pdu {
   uint32_t nof_ports;
   uint32_t prg_size_rb;
   uint32_t nof_prg;          /* 1 .. NRPHY_MAX_PRG (prg_size_rb: 1 .. NRPHY_MAX_RB, NRPHY_MAX_RB = wideband) */
-  const float* precoding;    /* host pointer: [nof_prg][nof_ports][nof_layers] complex (re, im) */
+  const float* precoding;    /* host pointer: [nof_prg][nof_ports][nof_layers] complex (re, im).  PRGs count from PRB 0 of the
+                              * grid: PRB b, data and DM-RS alike, takes the weights of PRG min(b / prg_size_rb, nof_prg - 1) */
 } nrphy_pdsch_pdu_t;
 
 /* Scalars the reference derives per PDU (pdsch_processor_impl.cpp:75-136, ldpc_segmenter_impl.cpp:90-160,
@@ -204,6 +205,11 @@ int nrphy_pdsch_plan_nof_sequences(const nrphy_pdsch_plan_t* plan, uint32_t* scr
  * waves: 1 = whole words (the sequences of the plan fit a level-2 cache), 0 = one 31-word seed per work item,
  * which the waves expand.  The outputs do not depend on it.  -1: plan is NULL. */
 int nrphy_pdsch_plan_scrambling_form(const nrphy_pdsch_plan_t* plan);
+
+/* How a run of the plan launches its codeblock waves: 1 = one launch of the mixed kernel, which selects (Qm, layers)
+ * per wave, 2 = one launch per (Qm, layers) bucket of the plan.  The choice follows the plan's shape unless the
+ * context was created under NRPHY_CB_DISPATCH=1 or =2.  The outputs do not depend on it.  -1: plan is NULL. */
+int nrphy_pdsch_plan_codeblock_dispatch(const nrphy_pdsch_plan_t* plan);
 
 /* Runs the whole PDSCH path of every PDU of the plan: TB CRC, segmentation, CB CRC, LDPC encoding,
  * rate matching, bit interleaving, scrambling, modulation, layer mapping, precoding, RE mapping and

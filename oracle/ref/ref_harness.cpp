@@ -389,6 +389,59 @@ int ref_pdsch_process(const nrphy_pdsch_pdu_t* in,
   return NRPHY_OK;
 }
 
+// pdsch_modulator::modulate alone (scrambling, modulation, layer mapping, precoding, RE mapping) on a zeroed grid, with the
+// PDU's precoding configuration as it stands, several PRGs included: the modulator and the grid mapper are well defined for
+// them (the mapper counts PRGs from subcarrier 0 of the grid), which the DM-RS processor is not.  codeword: the rate-matched
+// codeword packed MSB first, nof_bits of it.  The configuration is the one pdsch_processor_impl::modulate builds.
+int ref_pdsch_modulate(const nrphy_pdsch_pdu_t* in,
+                       const uint8_t*           codeword,
+                       unsigned                 nof_bits,
+                       uint16_t*                grid_out,
+                       unsigned                 nof_ports,
+                       unsigned                 nof_subc,
+                       int                      simd)
+{
+  pdsch_processor::pdu_t         pdu = to_pdu(*in);
+  pdsch_processor_validator_impl validator;
+  if (!validator.is_valid(pdu)) {
+    return NRPHY_ERR_INVALID_PDU;
+  }
+  // The mapper reads no weights beyond the last PRG and leaves what lies beyond it unprecoded: refuse such a shape.
+  if (in->nof_prg > 1 && highest_bit(in->prb_mask) > in->nof_prg * in->prg_size_rb) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  resource_grid_impl grid(nof_ports, 14, nof_subc, make_precoder(simd));
+  grid.set_all_zero();
+
+  pdsch_modulator::config_t cfg;
+  cfg.rnti                        = pdu.rnti;
+  cfg.bwp_size_rb                 = pdu.bwp_size_rb;
+  cfg.bwp_start_rb                = pdu.bwp_start_rb;
+  cfg.modulation1                 = pdu.codewords[0].modulation;
+  cfg.modulation2                 = modulation_scheme::BPSK;
+  cfg.freq_allocation             = pdu.freq_alloc;
+  cfg.start_symbol_index          = pdu.start_symbol_index;
+  cfg.nof_symbols                 = pdu.nof_symbols;
+  cfg.dmrs_symb_pos               = pdu.dmrs_symbol_mask;
+  cfg.dmrs_config_type            = pdu.dmrs;
+  cfg.nof_cdm_groups_without_data = pdu.nof_cdm_groups_without_data;
+  cfg.n_id                        = pdu.n_id;
+  cfg.scaling                     = convert_dB_to_amplitude(-pdu.ratio_pdsch_data_to_sss_dB);
+  cfg.reserved                    = pdu.reserved;
+  cfg.precoding                   = pdu.precoding;
+
+  dynamic_bit_buffer cw(nof_bits);
+  std::memcpy(cw.get_buffer().data(), codeword, (nof_bits + 7) / 8);
+  std::vector<bit_buffer> codewords;
+  codewords.emplace_back(cw);
+
+  auto modulator = std::make_unique<pdsch_modulator_impl>(std::make_unique<modulation_mapper_lut_impl>(),
+                                                          std::make_unique<pseudo_random_generator_impl>());
+  modulator->modulate(grid.get_mapper(), codewords, cfg);
+  copy_grid_out(grid_out, grid.get_reader(), nof_ports, nof_subc);
+  return NRPHY_OK;
+}
+
 // pdsch_encoder::encode: rate-matched, interleaved codeword as UNPACKED bits (one per byte).
 int ref_pdsch_encode(unsigned       bg,
                      unsigned       rv,

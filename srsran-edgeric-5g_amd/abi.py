@@ -890,6 +890,7 @@ def declare(lib, prefix="nrphy_"):
     sig("pdsch_plan_codeword_offset", u64, vp, u32)
     sig("pdsch_plan_nof_sequences", i32, vp, P(u32), P(u32))
     sig("pdsch_plan_scrambling_form", i32, vp)
+    sig("pdsch_plan_codeblock_dispatch", i32, vp)
     sig("pdsch_run", i32, vp, u8p, vp, u8p, u8p, i32, vp)
     sig("pdsch_plan_enable_timing", i32, vp, u32)
     sig("pdsch_plan_kernel_times", i32, vp, P(C.c_float), P(u32))
@@ -1127,7 +1128,7 @@ ABI_SYMBOLS = [
     "nrphy_pdsch_validate", "nrphy_pdsch_derive", "nrphy_tbs_calculate", "nrphy_ofdm_symbol_size",
     "nrphy_ofdm_slot_size", "nrphy_pdsch_plan_create", "nrphy_pdsch_plan_destroy",
     "nrphy_pdsch_plan_nof_codeblocks", "nrphy_pdsch_plan_codeword_bits", "nrphy_pdsch_plan_codeword_offset",
-    "nrphy_pdsch_plan_nof_sequences", "nrphy_pdsch_plan_scrambling_form",
+    "nrphy_pdsch_plan_nof_sequences", "nrphy_pdsch_plan_scrambling_form", "nrphy_pdsch_plan_codeblock_dispatch",
     "nrphy_pdsch_run", "nrphy_pdsch_plan_enable_timing", "nrphy_pdsch_plan_kernel_times", "nrphy_pdsch_plan_timing_stride",
     "nrphy_ofdm_plan_enable_timing", "nrphy_ofdm_plan_kernel_time", "nrphy_ofdm_plan_timing_stride", "nrphy_pdsch_process_host", "nrphy_pdsch_encode_host", "nrphy_ldpc_encode", "nrphy_ofdm_plan_create",
     "nrphy_ofdm_plan_destroy", "nrphy_ofdm_plan_slot_stride", "nrphy_ofdm_run",

@@ -175,6 +175,18 @@ extern "C" int nrphy_pdsch_plan_scrambling_form(const nrphy_pdsch_plan_t* plan)
   return plan == nullptr ? -1 : (plan->scr_as_words ? 1 : 0);
 }
 
+// The decision launch_codeblocks takes in a run of the plan, from the same rule and the same inputs.
+extern "C" int nrphy_pdsch_plan_codeblock_dispatch(const nrphy_pdsch_plan_t* plan)
+{
+  if (plan == nullptr) {
+    return -1;
+  }
+  PdschLaunch p;
+  p.n_work             = plan->n_work;
+  uint32_t nof_buckets = 0;
+  return codeblocks_take_bucket_launches(p, plan->bucket_begin, plan->ctx->tune.cb_dispatch, &nof_buckets) ? 2 : 1;
+}
+
 extern "C" uint64_t nrphy_pdsch_plan_codeword_bits(const nrphy_pdsch_plan_t* plan)
 {
   return plan ? plan->cw_bits : 0;

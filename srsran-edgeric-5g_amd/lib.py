@@ -729,6 +729,14 @@ class PdschPlan:
             raise NrphyError(abi.ERR_ARGUMENT, "nrphy_pdsch_plan_scrambling_form")
         return "words" if form else "seeds"
 
+    @property
+    def codeblock_dispatch(self):
+        """"mixed" or "bucket": one launch of the mixed codeblock kernel, or one launch per (Qm, layers) bucket."""
+        dispatch = int(self.ctx.lib.nrphy_pdsch_plan_codeblock_dispatch(self.handle))
+        if dispatch < 0:
+            raise NrphyError(abi.ERR_ARGUMENT, "nrphy_pdsch_plan_codeblock_dispatch")
+        return "mixed" if dispatch == 1 else "bucket"
+
     def run(self, d_tb, d_grid, d_cw_rm=None, d_cw_scr=None, zero_grids=True, stream=None):
         _check(self.ctx.lib.nrphy_pdsch_run(self.handle, _dptr(d_tb), _dptr(d_grid), _dptr(d_cw_rm), _dptr(d_cw_scr),
                                             int(zero_grids), _stream(stream)), "nrphy_pdsch_run")

@@ -221,6 +221,20 @@ class CpuBackend:
         assert rc == 0, rc
         return grid
 
+    def pdsch_modulate(self, pdu, codeword_packed, nof_bits, nof_ports, nof_subc, simd=1):
+        """pdsch_modulator::modulate of the compiled reference alone, on the rate-matched codeword (packed MSB first), with the
+        PDU's precoding configuration, several PRGs included: grid [nof_ports][14][nof_subc][2] uint16 with the data RE only."""
+        assert self.is_ref
+        cw = np.ascontiguousarray(codeword_packed, dtype=np.uint8)
+        assert cw.size >= (nof_bits + 7) // 8
+        grid = np.zeros((nof_ports, 14, nof_subc, 2), np.uint16)
+        f = self._f("pdsch_modulate")
+        f.restype = _i
+        f.argtypes = [_P(abi.PdschPdu), _vp, _u32, _vp, _u32, _u32, _i]
+        rc = f(C.byref(pdu), _ptr(cw), nof_bits, _ptr(grid), nof_ports, nof_subc, simd)
+        assert rc == 0, rc
+        return grid
+
     # ---- OFDM ---------------------------------------------------------------------------------------
     def dft(self, x, inverse):
         x = np.ascontiguousarray(x, dtype=np.complex64)

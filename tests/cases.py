@@ -347,6 +347,38 @@ def random_pdus(tbs, rng, count):
     return out
 
 
+def random_pdus_per_prg(tbs, rng, count):
+    """[(pdu, nof_ports, nof_subc)]: PDUs of random_pdus (drawn from rng as it stands, so its own draws stay what they are)
+    with the precoding replaced by 2-4 PRGs of random complex weights from a second generator.  prg_size_rb is drawn among the
+    sizes at which the allocation spans all of the PRGs -- its first PRB in PRG 0, its last in the last PRG or, at the smaller
+    sizes, beyond it, where the last PRG's weights hold (include/mi355_nrphy.h; the reference is undefined there and its DM-RS
+    processor for any several PRGs, so the oracle is the yardstick for these).  Kept: allocations of two PRBs or more that
+    the library accepts and that have data RE."""
+    lib = backends.pkg.lib
+    out, wrng = [], None
+    while len(out) < count:
+        batch = random_pdus(tbs, rng, count - len(out))
+        if wrng is None:
+            wrng = np.random.default_rng([int(rng.integers(0, 1 << 32)), 0x505247])
+        for pdu, ports, nof_subc in batch:
+            prbs = [p for p in range(nof_subc // 12) if (int(pdu.prb_mask[p // 64]) >> (p % 64)) & 1]
+            first, last = prbs[0], prbs[-1]
+            if last == first:
+                continue
+            nof_prg = int(wrng.integers(2, 5))
+            while (nof_prg - 1) * (first + 1) > last:   # a size with PRB `first` in PRG 0 and PRB `last` in the last PRG
+                nof_prg -= 1
+            pdu.nof_prg = nof_prg
+            pdu.prg_size_rb = int(wrng.integers(first + 1, last // (nof_prg - 1) + 1))
+            layers = pdu.nof_layers
+            w = ((wrng.standard_normal((nof_prg, ports, layers)) + 1j * wrng.standard_normal((nof_prg, ports, layers))) / 2)
+            w = w.astype(np.complex64)
+            attach_weights(pdu, np.stack([w.real, w.imag], axis=-1))
+            if lib.validate(pdu) == 0 and lib.derive(pdu)["nof_re"] > 0:
+                out.append((pdu, ports, nof_subc))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Downlink control side (SURVEY.md section 8f-2): random PDCCH and SS/PBCH PDUs within what the validators accept
 # ---------------------------------------------------------------------------------------------------------------------

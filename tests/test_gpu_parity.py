@@ -2133,6 +2133,33 @@ def test_pdsch_random_pdus(gpu_ctx, oracle):
     assert refused <= 3
 
 
+def per_prg_reach(pdu, nof_subc):
+    """(PRGs the allocation touches, whether a PRB of it lies beyond the last PRG and takes that PRG's weights)."""
+    prbs = [p for p in range(nof_subc // 12) if (int(pdu.prb_mask[p // 64]) >> (p % 64)) & 1]
+    return {min(p // pdu.prg_size_rb, pdu.nof_prg - 1) for p in prbs}, prbs[-1] >= pdu.nof_prg * pdu.prg_size_rb
+
+
+def test_pdsch_random_pdus_per_prg(gpu_ctx, oracle):
+    """Fuzz with weights per PRG: 24 random PDUs with 2-4 PRGs of random complex weights, each a host call of its own, codeword
+    taps and grid bit-exact against the oracle.  The allocation spans all of its PRGs; in some draws it runs on beyond the
+    last one."""
+    rng = np.random.default_rng(20250321)
+    draws = cases.random_pdus_per_prg(oracle.tbs, rng, 24)
+    assert len(draws) == 24
+    beyond = 0
+    for i, (pdu, nof_ports, nof_subc) in enumerate(draws):
+        touched, runs_on = per_prg_reach(pdu, nof_subc)
+        assert 2 <= pdu.nof_prg <= 4 and touched == set(range(pdu.nof_prg)), i
+        beyond += runs_on
+        assert oracle.validate(pdu) == 0, i
+        try:
+            run_single(gpu_ctx, oracle, pdu, cases.random_tb(rng, pdu), nof_ports, nof_subc)
+        except AssertionError as e:
+            raise AssertionError("draw %d (Qm %d, %d layers, %d ports, %d PRGs of %d PRB): %s" % (
+                i, pdu.qm, pdu.nof_layers, pdu.nof_ports, pdu.nof_prg, pdu.prg_size_rb, e))
+    assert 0 < beyond < len(draws)
+
+
 def test_receive_side_random_configurations(gpu_ctx, oracle):
     """Fuzz of the receive-side coding kernels against the oracle: random (base graph, lifting size, lengths, filler bits,
     CRC, noise, iterations, scaling) for the decoder; random (lifting size, E, rv, modulation, Nref, filler bits, new data

@@ -420,6 +420,29 @@ def test_oracle_vs_ref_pdsch_processor(oracle, ref):
             assert np.array_equal(grid, ref.pdsch_process(pdu, tb, nof_ports, nof_subc, simd=simd, impl=impl)), (name, simd, impl)
 
 
+def test_oracle_vs_ref_modulator_per_prg(oracle, ref):
+    """The oracle's data RE with weights per PRG, bit for bit against the reference's pdsch_modulator_impl run on its own over
+    the oracle's rate-matched codeword: the 40 per-PRG PDUs of tests/test_gpu_codeblock_matrix.py.  The modulator and the grid
+    mapper are well defined for several PRGs (resource_grid_mapper_impl.cpp:95-104, 230-235: PRGs counted from subcarrier 0 of
+    the grid); the reference's DM-RS processor is not, so the processor as a whole cannot serve here."""
+    import test_gpu_codeblock_matrix as matrix
+    combinations = matrix.per_prg_combinations()
+    assert len(combinations) == 40
+    for c in combinations:
+        pdu, name = c["pdu"], matrix.combination_name(c)
+        assert pdu.nof_prg > 1 and oracle.validate(pdu) == ref.validate(pdu) == 0, name
+        g = c["derived"]["codeword_bits"]
+        grid, rm, _ = oracle.pdsch_process(pdu, c["tb"], matrix.NOF_PORTS, matrix.NOF_SUBC, taps=True, codeword_bits=g)
+        mask = matrix.data_re_mask(pdu, matrix.NOF_SUBC)
+        assert int(mask.sum()) == c["derived"]["nof_re"], name
+        for simd in (1, 0):
+            want = ref.pdsch_modulate(pdu, rm, g, matrix.NOF_PORTS, matrix.NOF_SUBC, simd=simd)
+            assert not want[:, ~mask].any(), (name, simd)               # the modulator writes the data RE and nothing else
+            assert want[:pdu.nof_ports][:, mask].any(axis=(1, 2)).all(), (name, simd)
+            bad = np.argwhere(grid[:, mask] != want[:, mask])
+            assert bad.size == 0, "%s, simd %d: %d data RE words differ, first (port, RE, re/im) %s" % (name, simd, len(bad), bad[0].tolist())
+
+
 def test_oracle_vs_ref_validator(oracle, ref):
     def variants():
         base = dict(bwp_start_rb=1, bwp_size_rb=25, qm=4, dmrs_symbols=(2, 7), prb_start=3, prb_count=10, start_symbol=2,
