@@ -486,8 +486,8 @@ int nrphy_pusch_demodulate_host(nrphy_ctx_t* ctx, const nrphy_pusch_demod_cfg_t*
  *     whole symbol, then demap symbol j with the equalised noise variance of RE j -- the deprecoder leaves the variances alone
  *     (pusch_demodulator_impl.cpp:186-215) --, descramble; an RE the equaliser gave up on enters the transform as 0.  One
  *     workgroup per symbol; bit for bit nrphy_channel_equalize -> nrphy_transform_deprecode -> nrphy_demodulate_soft ->
- *     nrphy_llr_descramble.  The channel estimate of such a PUSCH comes from the caller (nrphy_pusch_chest_* has no low-PAPR
- *     DM-RS, like the reference's dmrs_pusch_estimator).
+ *     nrphy_llr_descramble.  The channel estimate of such a PUSCH comes from nrphy_pusch_chest_plan_create_ex with the
+ *     low-PAPR DM-RS enabled (the reference's dmrs_pusch_estimator of this release has Gold DM-RS only).
  *   NRPHY_PUSCH_DEMOD_PI2_BPSK  qm = 1 is accepted, with or without transform precoding: the pi/2-BPSK demapper of
  *     nrphy_demodulate_soft (NRPHY_MOD_PI2_BPSK), indexed by the symbol's position in its OFDM symbol's span.
  * Everything else of nrphy_pusch_demod_validate applies; a bit outside the two is NRPHY_ERR_ARGUMENT. */
@@ -597,6 +597,42 @@ int nrphy_pusch_chest_run(nrphy_pusch_chest_plan_t* plan, const void* d_grid, vo
  * [nof_rx_ports][NRPHY_PUSCH_CHEST_MAX_LAYERS] (may be NULL). */
 int nrphy_pusch_chest_host(nrphy_ctx_t* ctx, const nrphy_pusch_chest_cfg_t* cfg, const void* grid, uint32_t grid_nof_ports,
                            uint32_t grid_nof_subc, void* ch_est, float* noise_vars, nrphy_pusch_chest_meas_t* meas);
+/* The forms with the low-PAPR DM-RS of a transform-precoded PUSCH (TS 38.211 Section 6.4.1.1.1.2).  The three functions above
+ * are these without a description (lp / lps == NULL; one implementation, the same bytes); the plan type and
+ * nrphy_pusch_chest_run are the same, and a plan may mix Gold and low-PAPR PUSCHs (lps[i].enabled per PUSCH).  The reference's
+ * dmrs_pusch_estimator generates Gold pilots only; its releases after 24.04 feed
+ * low_papr_sequence_generator::generate(seq, n_rs_id % 30, 0, 0, 1) into the unchanged port_channel_estimator, and that is what
+ * enabled = 1 does.  Group and sequence hopping are off: u = n_rs_id mod 30, v = 0, alpha = 0, delta = 1.  Pilot q,
+ * q = 0 .. 6 M_rb - 1, is r_{u,0}(q) of length M_zc = 6 M_rb, over the allocated PRBs in ascending order (they need not be
+ * contiguous, as in the demodulator), on the grid subcarrier the Gold pilot has (12 n + 2 k), the same on every DM-RS symbol,
+ * with amplitude 1.  Every element is the entry low_papr_sequence_generator_impl takes of its exponential table
+ * (R/lib/phy/upper/sequence_generators/low_papr_sequence_generator_impl.cpp:158-244): M_zc = 6, 12, 18, 24 from the phi tables
+ * of TS 38.211 Section 5.2.2.2, M_zc >= 36 the Zadoff-Chu sequence of the largest prime below M_zc, q from the reference's float
+ * evaluation.  The table's entries are std::polar(1.0F, float(2 pi) index / size) with the bits the reference's build gives them:
+ * its cosf and sinf are the C library's (glibc 2.28 and later), which are not correctly rounded -- one float32 step from the
+ * exact value's rounding in about 1 % of the entries -- and the kernel restates that routine, so the sequence equals the
+ * reference's bit for bit.  M_zc = 30 (5 PRB) is ours and not the reference's,
+ * whose generator terminates on that length: TS 38.211 Section 5.2.2.1, exp(-j pi (u + 1)(n + 1)(n + 2) / 31), as entry
+ * (62 - ((u + 1)(n + 1)(n + 2) mod 62)) mod 62 of the reference's 62-point exponential table.  Everything behind the pilot is
+ * nrphy_pusch_chest_run's.  With enabled = 1, NRPHY_ERR_ARGUMENT also for: more than one layer; n_scid other than 0; n_rs_id
+ * above 1007; a number of allocated PRBs that nrphy_transform_precoding_nof_prb_valid rejects; scrambling_id is ignored (its range
+ * is still checked).  enabled above 1 is NRPHY_ERR_ARGUMENT. */
+typedef struct nrphy_pusch_chest_lowpapr {
+  uint32_t enabled; /* 0: Gold DM-RS, 1: low-PAPR DM-RS */
+  uint32_t n_rs_id; /* 0..1007 */
+} nrphy_pusch_chest_lowpapr_t;
+int nrphy_pusch_chest_validate_ex(const nrphy_pusch_chest_cfg_t* cfg, const nrphy_pusch_chest_lowpapr_t* lp, uint32_t grid_nof_ports,
+                                  uint32_t grid_nof_subc);
+int nrphy_pusch_chest_plan_create_ex(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_chest_cfg_t* cfgs,
+                                     const nrphy_pusch_chest_lowpapr_t* lps, const uint32_t* grid_index, uint32_t nof_grids,
+                                     uint32_t grid_nof_ports, uint32_t grid_nof_subc, const uint64_t* ce_offset,
+                                     nrphy_pusch_chest_plan_t** plan);
+int nrphy_pusch_chest_host_ex(nrphy_ctx_t* ctx, const nrphy_pusch_chest_cfg_t* cfg, const nrphy_pusch_chest_lowpapr_t* lp,
+                              const void* grid, uint32_t grid_nof_ports, uint32_t grid_nof_subc, void* ch_est, float* noise_vars,
+                              nrphy_pusch_chest_meas_t* meas);
+/* The low-PAPR DM-RS itself, from the kernel's generator: out[2 n], out[2 n + 1] = re, im of r_{u,0}(n), u = n_rs_id mod 30,
+ * n < 6 nof_prb (blocking, as nrphy_srs_sequence_host).  NRPHY_ERR_ARGUMENT for n_rs_id above 1007 or an invalid nof_prb. */
+int nrphy_pusch_lowpapr_sequence_host(nrphy_ctx_t* ctx, uint32_t n_rs_id, uint32_t nof_prb, float* out);
 
 /* ---- receive side: PRACH detector -----------------------------------------------------------------------------------------
  * Replaces prach_detector_generic_impl::detect (R/lib/phy/upper/channel_processors/prach_detector_generic_impl.cpp:89-359, with
@@ -1864,8 +1900,8 @@ int nrphy_ul_sch_info(const nrphy_ulsch_info_cfg_t* cfg, nrphy_ulsch_info_t* out
  * by one launch that writes a nrphy_pusch_result_t per PDU.  A PDU with a CSI part 2 description is refused here and taken by
  * nrphy_pusch_csi2_* (the next section).  Not covered, and refused: DM-RS type 2.  The EVM and the EVM-based SINR are not part
  * of these calls either -- they keep refusing NRPHY_PUSCH_SINR_EVM and reporting has_evm = 0 -- but of nrphy_pusch_evm_* below,
- * which take the EVM from the demodulator (nrphy_pusch_demod_run_evm).  Transform precoding is never enabled, as in the
- * reference's processor. */
+ * which take the EVM from the demodulator (nrphy_pusch_demod_run_evm).  Transform precoding is never enabled by these calls, as
+ * in the reference's processor of this release; nrphy_pusch_tp_* below enable it per PDU. */
 #define NRPHY_PUSCH_SINR_CHANNEL_ESTIMATOR 0u /* channel_state_information::sinr_type */
 #define NRPHY_PUSCH_SINR_POST_EQUALIZATION 1u
 #define NRPHY_PUSCH_SINR_EVM 2u               /* nrphy_pusch_evm_* with enable_evm = 1 only; refused by nrphy_pusch_proc_* */
@@ -1873,7 +1909,7 @@ typedef struct nrphy_pusch_pdu {              /* pusch_processor::pdu_t */
   uint32_t numerology, slot_index;            /* slot within the frame: < 10 * 2^numerology */
   uint32_t rnti, n_id;                        /* data scrambling: c_init = rnti * 2^15 + n_id */
   uint32_t scrambling_id, n_scid;             /* DM-RS */
-  uint32_t modulation;                        /* mcs_descr: NRPHY_MOD_QPSK .. NRPHY_MOD_QAM256 */
+  uint32_t modulation;                        /* mcs_descr: NRPHY_MOD_QPSK .. NRPHY_MOD_QAM256; NRPHY_MOD_PI2_BPSK with nrphy_pusch_tp_* */
   float    target_code_rate;                  /* mcs_descr: R x 1024 */
   uint32_t has_codeword;                      /* 0: no UL-SCH (tb_size_bytes must be 0 then); 1: rv, ldpc_base_graph, new_data hold */
   uint32_t rv, ldpc_base_graph, new_data;
@@ -1999,6 +2035,41 @@ int nrphy_pusch_evm_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_
 int nrphy_pusch_evm_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_evm_options_t* options, const void* grid,
                          uint32_t grid_nof_ports, uint32_t grid_nof_subc, int8_t* harq_soft, uint8_t* harq_state, uint8_t* tb,
                          uint8_t* uci_bits, nrphy_pusch_result_t* result);
+/* The processor with transform precoding (DFT-s-OFDM): what the reference's releases after 24.04 do for a pusch_processor::pdu_t
+ * whose dmrs is a dmrs_transform_precoding_configuration{n_rs_id}.  The calls take the arguments of their nrphy_pusch_evm_*
+ * (nrphy_pusch_proc_*) namesakes and one descriptor per PDU, and there is one implementation: nrphy_pusch_evm_* and
+ * nrphy_pusch_proc_* are these calls without descriptors (tp / tps == NULL), every byte as before; a descriptor with
+ * transform_precoding = 0 is no descriptor.  A plan, and a slot, may mix PDUs with and without transform precoding.  With
+ * transform_precoding = 1: the estimator stage is created with the low-PAPR DM-RS {1, n_rs_id} (nrphy_pusch_chest_plan_create_ex;
+ * the PDU's scrambling_id is ignored), the derived demodulator configuration has transform_precoding = 1 and the demodulator
+ * plan is created with NRPHY_PUSCH_DEMOD_TRANSFORM_PRECODING | NRPHY_PUSCH_DEMOD_PI2_BPSK; NRPHY_MOD_PI2_BPSK is accepted as the
+ * PDU's modulation, and then qm = 1 in the demodulator, demultiplexer and decoder configurations and the UCI decoder's modulation
+ * is pi/2-BPSK.  HARQ-ACK and CSI part 1 on the PUSCH and the EVM (enable_evm = 1, measured after the deprecoder) work as without
+ * transform precoding.  NRPHY_ERR_ARGUMENT also for: pi/2-BPSK without transform precoding; transform precoding with two layers,
+ * with n_scid other than 0, with a number of PRBs nrphy_transform_precoding_nof_prb_valid rejects or with n_rs_id above 1007;
+ * transform_precoding above 1; everything the stage validators refuse; a CSI part 2 description (nrphy_pusch_csi2_* takes no
+ * descriptor: CSI part 2 with transform precoding is not covered).  nrphy_pusch_tp_derive also writes the estimator's low-PAPR
+ * description to lp_out (may be NULL).  The plan is a nrphy_pusch_proc_plan_t: nrphy_pusch_proc_run,
+ * nrphy_pusch_proc_plan_destroy and nrphy_pusch_proc_plan_harq_bytes take it as they are. */
+typedef struct nrphy_pusch_tp_desc {
+  uint32_t transform_precoding;               /* 0 or 1 */
+  uint32_t n_rs_id;                           /* 0..1007: dmrs_transform_precoding_configuration::n_rs_id */
+} nrphy_pusch_tp_desc_t;
+int nrphy_pusch_tp_validate(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_tp_desc_t* tp, const nrphy_pusch_evm_options_t* options,
+                            uint32_t grid_nof_ports, uint32_t grid_nof_subc);
+int nrphy_pusch_tp_derive(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_tp_desc_t* tp, const nrphy_pusch_evm_options_t* options,
+                          uint32_t grid_nof_ports, uint32_t grid_nof_subc, nrphy_pusch_proc_derived_t* out,
+                          nrphy_pusch_chest_lowpapr_t* lp_out);
+int nrphy_pusch_tp_harq_bytes(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_tp_desc_t* tp, const nrphy_pusch_evm_options_t* options,
+                              uint64_t* soft_bytes, uint64_t* state_bytes);
+int nrphy_pusch_tp_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, const nrphy_pusch_tp_desc_t* tps,
+                               const nrphy_pusch_evm_options_t* options, const uint32_t* grid_index, uint32_t nof_grids,
+                               uint32_t grid_nof_ports, uint32_t grid_nof_subc, const uint64_t* harq_soft_offset,
+                               const uint64_t* harq_state_offset, const uint64_t* tb_offset, const uint64_t* uci_offset,
+                               nrphy_pusch_proc_plan_t** plan);
+int nrphy_pusch_tp_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_tp_desc_t* tp,
+                        const nrphy_pusch_evm_options_t* options, const void* grid, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
+                        int8_t* harq_soft, uint8_t* harq_state, uint8_t* tb, uint8_t* uci_bits, nrphy_pusch_result_t* result);
 
 /* ---- receive side: PUSCH processor with CSI part 2 ---------------------------------------------------------------------------------
  * What pusch_processor_impl::process does with pdu.uci.csi_part2_size (pusch_processor_impl.cpp:57-86 and
@@ -2183,6 +2254,11 @@ int nrphy_ul_slot_pusch(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, co
  * and a slot may mix both calls. */
 int nrphy_pusch_evm_slot(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pusch_pdu_t* pdus,
                          const nrphy_pusch_evm_options_t* options, const uint64_t* harq_soft_offset, const uint64_t* harq_state_offset);
+/* nrphy_pusch_evm_slot with the descriptors of nrphy_pusch_tp_plan_create (tps may be NULL): the same operation, the results append
+ * to the same list, and a slot may mix all three calls. */
+int nrphy_pusch_tp_slot(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pusch_pdu_t* pdus,
+                        const nrphy_pusch_tp_desc_t* tps, const nrphy_pusch_evm_options_t* options, const uint64_t* harq_soft_offset,
+                        const uint64_t* harq_state_offset);
 int nrphy_ul_slot_pf01(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pucch_cfg_t* cfgs);
 int nrphy_ul_slot_pf2(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pf2_cfg_t* cfgs);
 int nrphy_ul_slot_srs(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_srs_cfg_t* cfgs);

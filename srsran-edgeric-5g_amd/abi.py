@@ -160,6 +160,11 @@ class PuschChestMeas(C.Structure):
                 ("ta_bins", C.c_int32), ("cfo_hz", C.c_float), ("reserved_", C.c_uint32)]
 
 
+class PuschChestLowpapr(C.Structure):
+    """nrphy_pusch_chest_lowpapr_t: the low-PAPR DM-RS of a transform-precoded PUSCH (enabled 0: Gold DM-RS)."""
+    _fields_ = [("enabled", C.c_uint32), ("n_rs_id", C.c_uint32)]
+
+
 def make_pusch_chest(*, prbs, numerology=0, slot_index=0, scrambling_id=0, n_scid=0, scaling=1.0, dmrs_type=1,
                      dmrs_symbols=(2,), start_symbol=0, nof_symbols=14, nof_layers=1, rx_ports=(0,), dc_position=None):
     """A PuschChestCfg from plain values (prbs: grid-indexed PRB numbers; dc_position None: no DC)."""
@@ -477,6 +482,11 @@ def make_pusch_proc_options(dec_nof_iterations=10, dec_enable_early_stop=1, csi_
                             equalizer=EQ_ZF):
     """A PuschProcOptions."""
     return PuschProcOptions(dec_nof_iterations, dec_enable_early_stop, csi_sinr_calc_method, equalizer)
+
+
+class PuschTpDesc(C.Structure):
+    """nrphy_pusch_tp_desc_t: transform precoding of one PUSCH PDU and its DM-RS sequence identity."""
+    _fields_ = [("transform_precoding", C.c_uint32), ("n_rs_id", C.c_uint32)]
 
 
 def make_pusch_evm_options(enable_evm=1, reserved_=0, **proc):
@@ -1008,6 +1018,10 @@ def declare(lib, prefix="nrphy_"):
     sig("pusch_chest_plan_destroy", i32, vp)
     sig("pusch_chest_run", i32, vp, vp, vp, vp, vp, vp)
     sig("pusch_chest_host", i32, vp, P(PuschChestCfg), vp, u32, u32, vp, vp, vp)
+    sig("pusch_chest_validate_ex", i32, P(PuschChestCfg), P(PuschChestLowpapr), u32, u32)
+    sig("pusch_chest_plan_create_ex", i32, vp, u32, P(PuschChestCfg), P(PuschChestLowpapr), P(u32), u32, u32, u32, P(u64), P(vp))
+    sig("pusch_chest_host_ex", i32, vp, P(PuschChestCfg), P(PuschChestLowpapr), vp, u32, u32, vp, vp, vp)
+    sig("pusch_lowpapr_sequence_host", i32, vp, u32, u32, vp)
     sig("prach_threshold", i32, P(PrachCfg), P(C.c_float), P(u32), P(u32))
     sig("prach_validate", i32, P(PrachCfg))
     sig("prach_window_width", u32, P(PrachCfg))
@@ -1068,6 +1082,13 @@ def declare(lib, prefix="nrphy_"):
         P(vp))
     sig("pusch_evm_host", i32, vp, P(PuschPdu), P(PuschEvmOptions), vp, u32, u32, vp, vp, vp, vp, P(PuschResult))
     sig("pusch_evm_slot", i32, vp, u32, u32, P(PuschPdu), P(PuschEvmOptions), P(u64), P(u64))
+    sig("pusch_tp_validate", i32, P(PuschPdu), P(PuschTpDesc), P(PuschEvmOptions), u32, u32)
+    sig("pusch_tp_derive", i32, P(PuschPdu), P(PuschTpDesc), P(PuschEvmOptions), u32, u32, P(PuschProcDerived), P(PuschChestLowpapr))
+    sig("pusch_tp_harq_bytes", i32, P(PuschPdu), P(PuschTpDesc), P(PuschEvmOptions), P(u64), P(u64))
+    sig("pusch_tp_plan_create", i32, vp, u32, P(PuschPdu), P(PuschTpDesc), P(PuschEvmOptions), P(u32), u32, u32, u32, P(u64), P(u64),
+        P(u64), P(u64), P(vp))
+    sig("pusch_tp_host", i32, vp, P(PuschPdu), P(PuschTpDesc), P(PuschEvmOptions), vp, u32, u32, vp, vp, vp, vp, P(PuschResult))
+    sig("pusch_tp_slot", i32, vp, u32, u32, P(PuschPdu), P(PuschTpDesc), P(PuschEvmOptions), P(u64), P(u64))
     sig("pusch_csi2_size", i32, P(PuschCsi2Desc), vp, u32, P(u32))
     sig("pusch_csi2_validate", i32, P(PuschPdu), P(PuschCsi2Desc), P(PuschProcOptions), u32, u32)
     sig("pusch_csi2_variants", i32, P(PuschPdu), P(PuschCsi2Desc), P(PuschProcOptions), u32, u32, P(u32), P(u32), P(UlschInfo))
@@ -1162,6 +1183,8 @@ ABI_SYMBOLS = [
     "nrphy_transform_precoding_nof_prb_valid", "nrphy_transform_deprecode", "nrphy_transform_deprecode_host",
     "nrphy_pusch_chest_validate", "nrphy_pusch_chest_plan_create", "nrphy_pusch_chest_plan_destroy", "nrphy_pusch_chest_run",
     "nrphy_pusch_chest_host",
+    "nrphy_pusch_chest_validate_ex", "nrphy_pusch_chest_plan_create_ex", "nrphy_pusch_chest_host_ex",
+    "nrphy_pusch_lowpapr_sequence_host",
     "nrphy_prach_threshold", "nrphy_prach_validate", "nrphy_prach_window_width", "nrphy_prach_plan_create", "nrphy_prach_plan_destroy",
     "nrphy_prach_plan_metric_stride", "nrphy_prach_run", "nrphy_prach_detect_host", "nrphy_prach_generate_host",
     "nrphy_prach_demod_validate", "nrphy_prach_demod_sizes", "nrphy_prach_demod_plan_create", "nrphy_prach_demod_plan_destroy",
@@ -1178,6 +1201,8 @@ ABI_SYMBOLS = [
     "nrphy_pusch_proc_plan_create", "nrphy_pusch_proc_plan_destroy", "nrphy_pusch_proc_plan_harq_bytes", "nrphy_pusch_proc_run",
     "nrphy_pusch_proc_host",
     "nrphy_pusch_evm_validate", "nrphy_pusch_evm_plan_create", "nrphy_pusch_evm_host", "nrphy_pusch_evm_slot",
+    "nrphy_pusch_tp_validate", "nrphy_pusch_tp_derive", "nrphy_pusch_tp_harq_bytes", "nrphy_pusch_tp_plan_create",
+    "nrphy_pusch_tp_host", "nrphy_pusch_tp_slot",
     "nrphy_pusch_csi2_size", "nrphy_pusch_csi2_validate", "nrphy_pusch_csi2_variants", "nrphy_pusch_csi2_harq_bytes",
     "nrphy_pusch_csi2_plan_create", "nrphy_pusch_csi2_plan_destroy", "nrphy_pusch_csi2_run", "nrphy_pusch_csi2_host",
     "nrphy_ofdm_demod_symbols",

@@ -16,14 +16,14 @@ SOURCES = ["nrphy_host.cpp", "pdsch_plan_build.cpp", "pdsch_host.cpp", "dl_contr
            "ofdm_host.cpp", "lower_phy_host.cpp", "demod_host.cpp", "ldpc_dematcher_host.cpp", "ldpc_decoder_host.cpp", "pusch_decoder_host.cpp",
            "csi_rs_host.cpp", "pdsch_kernels.hip", "ofdm_kernels.hip", "ldpc_decoder.hip",
            "ldpc_dematcher.hip", "pusch_decoder.hip", "csi_rs_kernels.hip", "dl_control_kernels.hip", "lower_phy_kernels.hip", "demod_kernels.hip",
-           "pusch_demod_host.cpp", "pusch_demod_kernels.hip", "pusch_chest_host.cpp", "pusch_chest_kernels.hip",
+           "pusch_demod_host.cpp", "pusch_demod_kernels.hip", "pusch_chest_host.cpp", "pusch_chest_kernels.hip", "pusch_chest_lowpapr_kernels.hip",
            "prach_host.cpp", "prach_kernels.hip", "prach_demod_host.cpp", "prach_demod_kernels.hip", "pucch_host.cpp", "pucch_kernels.hip",
            "pucch2_host.cpp", "pucch2_kernels.hip", "srs_host.cpp", "srs_kernels.hip",
            "uci_host.cpp", "uci_kernels.hip", "ulsch_host.cpp", "ulsch_kernels.hip", "ofh_ul_host.cpp", "ofh_ul_kernels.hip",
            "ofh_dl_host.cpp", "ofh_dl_kernels.hip", "ofh_rx_host.cpp", "ofh_rx_kernels.hip",
            "transform_precoder_host.cpp", "transform_precoder_kernels.hip", "pusch_proc_host.cpp", "pusch_proc_kernels.hip",
            "pusch_csi2_host.cpp", "pusch_csi2_kernels.hip"]
-HEADERS = ["nrphy_internal.h", "nrphy_host_internal.h", "pdsch_plan.h", "pdsch_staging_host.h", "slot_pool_host.h", "ul_slot_state_host.h", "prach_window_state_host.h", "ldpc_receive_host.h", "ldpc_base_graph_host.h", "pusch_alloc_host.h", "ulsch_placement_host.h", "ulsch_info_host.h", "pusch_csi2_host.h", "pusch_proc_plan_host.h", "pusch_select_host.h", "nrphy_trace.h", "bits_device.h", "crc24b_fold.h", "ofh_compress_device.h", "ofh_ul_chunk_device.h", "chest_device.h", "chest_host.h", "demod_device.h", "equalize_device.h", "exact_device.h", "ldpc_device.h", "codeblock_build_device.h", "rate_match_device.h", "re_map_device.h", "pdsch_dmrs_device.h", "fft_device.h", "dft_mixed_device.h","nr_ldpc_bg.inc", "nr_polar_tables.inc", "prach_tables.inc", "prach_demod_tables.inc", "pucch_tables.inc", "srs_tables.inc", "uci_tables.inc",
+HEADERS = ["nrphy_internal.h", "nrphy_host_internal.h", "pdsch_plan.h", "pdsch_staging_host.h", "slot_pool_host.h", "ul_slot_state_host.h", "prach_window_state_host.h", "ldpc_receive_host.h", "ldpc_base_graph_host.h", "pusch_alloc_host.h", "ulsch_placement_host.h", "ulsch_info_host.h", "pusch_csi2_host.h", "pusch_proc_plan_host.h", "pusch_select_host.h", "nrphy_trace.h", "bits_device.h", "crc24b_fold.h", "ofh_compress_device.h", "ofh_ul_chunk_device.h", "chest_device.h", "chest_host.h", "pusch_chest_kernel_device.h", "low_papr_device.h", "low_papr_host.h", "demod_device.h", "equalize_device.h", "exact_device.h", "ldpc_device.h", "codeblock_build_device.h", "rate_match_device.h", "re_map_device.h", "pdsch_dmrs_device.h", "fft_device.h", "dft_mixed_device.h","nr_ldpc_bg.inc", "nr_polar_tables.inc", "prach_tables.inc", "prach_demod_tables.inc", "pucch_tables.inc", "srs_tables.inc", "pusch_lowpapr_tables.inc", "uci_tables.inc",
            os.path.join(ROOT, "include", "mi355_nrphy.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 MAX_COMPILERS = 16  # in flight at once

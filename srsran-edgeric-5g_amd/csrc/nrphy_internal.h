@@ -476,7 +476,15 @@ struct PuschChestDesc {                        // one PUSCH of a plan
   uint32_t scs_hz;
   uint32_t rx_ports[NRPHY_MAX_PORTS];
   uint32_t dmrs_symbol[NRPHY_NSYMB];
-  uint32_t c_init[NRPHY_NSYMB];                // per DM-RS symbol
+  union {
+    uint32_t c_init[NRPHY_NSYMB];              // Gold DM-RS: per DM-RS symbol
+    struct {                                   // low-PAPR DM-RS (low_papr_device.h): the same sequence on every DM-RS symbol
+      uint32_t circle;                         // 8 (tables), 62 (5 PRB) or 2 N_zc: the size of the unit circle
+      uint32_t u;                              // n_rs_id mod 30
+      uint32_t n_zc, q;                        // 6 nprb >= 36: largest prime below it and the Zadoff-Chu root
+      int8_t   phi[24];                        // 1 .. 4 PRB: phi(n) of group u
+    } lp;
+  };
   float    epoch[NRPHY_NSYMB];                 // symbol start epochs (initialize_symbol_start_epochs), in symbols
   float    taps[16];
   float    beta, ls_scale;                     // ls_scale = 1 / (nof_dmrs * beta), in float
@@ -498,7 +506,12 @@ struct PuschChestLaunch {
   float2*                   rot;               // scratch: [job][14] CFO phasors
   uint32_t                  grid_nof_ports, grid_nof_subc, n_jobs;
 };
-hipError_t launch_pusch_chest(const PuschChestLaunch& p, hipStream_t stream);
+// The first n_gold jobs are of PUSCHs with Gold DM-RS, the others of PUSCHs with low-PAPR DM-RS (desc.lp).
+hipError_t launch_pusch_chest(const PuschChestLaunch& p, uint32_t n_gold, hipStream_t stream);
+// The first kernel alone, for p.n_jobs low-PAPR jobs (launch_pusch_chest calls it; pusch_chest_lowpapr_kernels.hip).
+void launch_pusch_chest_lowpapr(const PuschChestLaunch& p, hipStream_t stream);
+// out[n] = the low-PAPR DM-RS of desc[0], n < 6 nprb.
+hipError_t launch_pusch_lowpapr_sequence(const PuschChestDesc* desc, float2* out, hipStream_t stream);
 // ---- PRACH detector (receive side) ----------------------------------------------------------------------------------------
 constexpr uint32_t PRACH_L_LONG = 839, PRACH_L_SHORT = 139, PRACH_N_LONG = 1024, PRACH_N_SHORT = 256;
 struct PrachTables {                           // per context

@@ -1,14 +1,45 @@
 // Host side of the PUSCH DM-RS channel estimator (pusch_chest_kernels.hip): validation, and the plan's per-PUSCH constants --
 // what dmrs_pusch_estimator_impl and port_channel_estimator_average_impl compute before touching the grid: c_init per DM-RS
-// symbol (dmrs_pusch_estimator_impl.cpp:136-149), and the symbol start epochs and raised-cosine taps of chest_host.h.
+// symbol (dmrs_pusch_estimator_impl.cpp:136-149), and the symbol start epochs and raised-cosine taps of chest_host.h.  For a
+// transform-precoded PUSCH, in place of c_init, the constants of its low-PAPR DM-RS (low_papr_host.h and the phi tables).  One
+// implementation: the calls without a low-PAPR description are the _ex calls with none.
 #include "chest_host.h"
+#include "low_papr_host.h"
 #include "pusch_alloc_host.h"
 
 #include <cmath>
 
 namespace {
 
-int validate(const nrphy_pusch_chest_cfg_t* c, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
+#include "pucch_tables.inc"
+#include "pusch_lowpapr_tables.inc"
+#include "srs_tables.inc"
+
+bool low_papr(const nrphy_pusch_chest_lowpapr_t* lp)
+{
+  return lp != nullptr && lp->enabled != 0;
+}
+
+// The constants of r_{u,0}, u = n_rs_id mod 30, of length 6 nprb (group and sequence hopping off).
+void fill_low_papr(PuschChestDesc& d, uint32_t n_rs_id, uint32_t nprb)
+{
+  const uint32_t u = n_rs_id % 30;
+  d.lp.u           = u;
+  if (nprb < 5) {
+    d.lp.circle = 8;
+    for (uint32_t n = 0; n != 6 * nprb; ++n) {
+      d.lp.phi[n] = nprb == 1 ? PUSCH_PHI_6[u][n] : nprb == 2 ? PUCCH_PHI_12[u][n] : nprb == 3 ? PUSCH_PHI_18[u][n] : SRS_PHI_24[u][n];
+    }
+  } else if (nprb == 5) {
+    d.lp.circle = 62;
+  } else {
+    d.lp.n_zc   = low_papr_prime_below(6 * nprb);
+    d.lp.q      = low_papr_zc_root(u, d.lp.n_zc);
+    d.lp.circle = 2 * d.lp.n_zc;
+  }
+}
+
+int validate(const nrphy_pusch_chest_cfg_t* c, const nrphy_pusch_chest_lowpapr_t* lp, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
 {
   if (c == nullptr || c->dmrs_type != 1 || c->nof_tx_layers < 1 || c->nof_tx_layers > NRPHY_PUSCH_CHEST_MAX_LAYERS ||
       c->numerology > 4 || c->slot_index >= (10U << c->numerology) || c->scrambling_id > 65535U || c->n_scid > 1 ||
@@ -27,6 +58,10 @@ int validate(const nrphy_pusch_chest_cfg_t* c, uint32_t grid_nof_ports, uint32_t
   if (c->dc_position != NRPHY_PUSCH_CHEST_NO_DC && c->dc_position >= grid_nof_subc) {
     return NRPHY_ERR_ARGUMENT;
   }
+  if (lp != nullptr && (lp->enabled > 1 || (lp->enabled == 1 && (c->nof_tx_layers != 1 || c->n_scid != 0 || lp->n_rs_id > 1007U ||
+                                                                 !nrphy_transform_precoding_nof_prb_valid(nof_prb(a)))))) {
+    return NRPHY_ERR_ARGUMENT;
+  }
   return NRPHY_OK;
 }
 
@@ -34,7 +69,7 @@ int validate(const nrphy_pusch_chest_cfg_t* c, uint32_t grid_nof_ports, uint32_t
 
 struct nrphy_pusch_chest_plan {
   nrphy_ctx*      ctx = nullptr;
-  uint32_t        n = 0, n_jobs = 0;
+  uint32_t        n = 0, n_jobs = 0, n_gold = 0; // the jobs of the Gold PUSCHs come first
   uint32_t        nof_grids = 0, grid_nof_ports = 0, grid_nof_subc = 0;
   void*           d_arena = nullptr;
   PuschChestDesc* d_desc  = nullptr;
@@ -47,7 +82,13 @@ struct nrphy_pusch_chest_plan {
 
 extern "C" int nrphy_pusch_chest_validate(const nrphy_pusch_chest_cfg_t* cfg, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
 {
-  return validate(cfg, grid_nof_ports, grid_nof_subc);
+  return validate(cfg, nullptr, grid_nof_ports, grid_nof_subc);
+}
+
+extern "C" int nrphy_pusch_chest_validate_ex(const nrphy_pusch_chest_cfg_t* cfg, const nrphy_pusch_chest_lowpapr_t* lp,
+                                             uint32_t grid_nof_ports, uint32_t grid_nof_subc)
+{
+  return validate(cfg, lp, grid_nof_ports, grid_nof_subc);
 }
 
 extern "C" int nrphy_pusch_chest_plan_destroy(nrphy_pusch_chest_plan_t* plan)
@@ -67,6 +108,14 @@ extern "C" int nrphy_pusch_chest_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
                                              const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports,
                                              uint32_t grid_nof_subc, const uint64_t* ce_offset, nrphy_pusch_chest_plan_t** out)
 {
+  return nrphy_pusch_chest_plan_create_ex(ctx, n, cfgs, nullptr, grid_index, nof_grids, grid_nof_ports, grid_nof_subc, ce_offset, out);
+}
+
+extern "C" int nrphy_pusch_chest_plan_create_ex(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_chest_cfg_t* cfgs,
+                                                const nrphy_pusch_chest_lowpapr_t* lps, const uint32_t* grid_index, uint32_t nof_grids,
+                                                uint32_t grid_nof_ports, uint32_t grid_nof_subc, const uint64_t* ce_offset,
+                                                nrphy_pusch_chest_plan_t** out)
+{
   if (out == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
@@ -75,12 +124,13 @@ extern "C" int nrphy_pusch_chest_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
     return NRPHY_ERR_ARGUMENT;
   }
   std::vector<PuschChestDesc> desc(n);
-  std::vector<uint32_t>       jobs;
+  std::vector<uint32_t>       jobs, lp_jobs;
   std::vector<uint16_t>       prbs;
   uint64_t                    row_words = 0;
   for (uint32_t i = 0; i != n; ++i) {
-    const nrphy_pusch_chest_cfg_t& c = cfgs[i];
-    if (validate(&c, grid_nof_ports, grid_nof_subc) != NRPHY_OK || grid_index[i] >= nof_grids) {
+    const nrphy_pusch_chest_cfg_t&     c  = cfgs[i];
+    const nrphy_pusch_chest_lowpapr_t* lp = lps != nullptr ? &lps[i] : nullptr;
+    if (validate(&c, lp, grid_nof_ports, grid_nof_subc) != NRPHY_OK || grid_index[i] >= nof_grids) {
       return NRPHY_ERR_ARGUMENT;
     }
     PuschChestDesc& d = desc[i];
@@ -97,11 +147,16 @@ extern "C" int nrphy_pusch_chest_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
       if ((c.dmrs_symbol_mask >> l) & 1U) {
         const uint64_t nid = c.scrambling_id;
         d.dmrs_symbol[d.nof_dmrs] = l;
-        d.c_init[d.nof_dmrs]      = (uint32_t)(((NRPHY_NSYMB * (uint64_t)c.slot_index + l + 1) * (2 * nid + 1) * (1ULL << 17) +
-                                           2 * nid + c.n_scid) %
-                                          (1ULL << 31));
+        if (!low_papr(lp)) {
+          d.c_init[d.nof_dmrs] = (uint32_t)(((NRPHY_NSYMB * (uint64_t)c.slot_index + l + 1) * (2 * nid + 1) * (1ULL << 17) +
+                                             2 * nid + c.n_scid) %
+                                            (1ULL << 31));
+        }
         ++d.nof_dmrs;
       }
+    }
+    if (low_papr(lp)) {
+      fill_low_papr(d, lp->n_rs_id, d.nprb);
     }
     chest_symbol_epochs(c.numerology, d.epoch);
     d.ntaps = chest_filter_taps(d.nprb, 2, d.taps);
@@ -118,10 +173,12 @@ extern "C" int nrphy_pusch_chest_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
     row_words += (uint64_t)c.nof_rx_ports * c.nof_tx_layers * NRPHY_NRE * d.nprb;
     for (uint32_t p = 0; p != c.nof_rx_ports; ++p) {
       for (uint32_t l = 0; l != c.nof_tx_layers; ++l) {
-        jobs.push_back((i << 8) | (p << 4) | l);
+        (low_papr(lp) ? lp_jobs : jobs).push_back((i << 8) | (p << 4) | l);
       }
     }
   }
+  const uint32_t n_gold = (uint32_t)jobs.size();
+  jobs.insert(jobs.end(), lp_jobs.begin(), lp_jobs.end());
   // The time-alignment search's twiddles are the context's table, built on first use.
   const float2* twiddle = hipSetDevice(ctx->device) == hipSuccess ? get_twiddle_table(ctx, 2048) : nullptr;
   if (twiddle == nullptr) {
@@ -132,6 +189,7 @@ extern "C" int nrphy_pusch_chest_plan_create(nrphy_ctx_t* ctx, uint32_t n, const
   plan->twiddle        = twiddle;
   plan->n              = n;
   plan->n_jobs         = (uint32_t)jobs.size();
+  plan->n_gold         = n_gold;
   plan->nof_grids      = nof_grids;
   plan->grid_nof_ports = grid_nof_ports;
   plan->grid_nof_subc  = grid_nof_subc;
@@ -174,7 +232,7 @@ extern "C" int nrphy_pusch_chest_run(nrphy_pusch_chest_plan_t* plan, const void*
   p.grid_nof_subc  = plan->grid_nof_subc;
   p.n_jobs         = plan->n_jobs;
   HIP_TRY(hipSetDevice(plan->ctx->device));
-  HIP_TRY(launch_pusch_chest(p, stream ? (hipStream_t)stream : plan->ctx->stream));
+  HIP_TRY(launch_pusch_chest(p, plan->n_gold, stream ? (hipStream_t)stream : plan->ctx->stream));
   return NRPHY_OK;
 }
 
@@ -182,8 +240,37 @@ extern "C" int nrphy_pusch_chest_host(nrphy_ctx_t* ctx, const nrphy_pusch_chest_
                                       uint32_t grid_nof_ports, uint32_t grid_nof_subc, void* ch_est, float* noise_vars,
                                       nrphy_pusch_chest_meas_t* meas)
 {
+  return nrphy_pusch_chest_host_ex(ctx, cfg, nullptr, grid, grid_nof_ports, grid_nof_subc, ch_est, noise_vars, meas);
+}
+
+extern "C" int nrphy_pusch_lowpapr_sequence_host(nrphy_ctx_t* ctx, uint32_t n_rs_id, uint32_t nof_prb, float* out)
+{
+  if (ctx == nullptr || out == nullptr || n_rs_id > 1007U || !nrphy_transform_precoding_nof_prb_valid(nof_prb)) {
+    return NRPHY_ERR_ARGUMENT;
+  }
+  PuschChestDesc desc;
+  std::memset(&desc, 0, sizeof(desc));
+  desc.nprb = nof_prb;
+  fill_low_papr(desc, n_rs_id, nof_prb);
+  const size_t out_bytes = (size_t)6 * nof_prb * sizeof(float2);
+  HostCall     call(ctx);
+  uint8_t*     d[2]; // descriptor, sequence
+  if (!call.carve(SCRATCH_RX, {sizeof(desc), out_bytes}, d)) {
+    return NRPHY_ERR_DEVICE;
+  }
+  HIP_TRY(hipMemcpy(d[0], &desc, sizeof(desc), hipMemcpyHostToDevice));
+  HIP_TRY(launch_pusch_lowpapr_sequence((const PuschChestDesc*)d[0], (float2*)d[1], ctx->stream));
+  HIP_TRY(call.sync());
+  HIP_TRY(hipMemcpy(out, d[1], out_bytes, hipMemcpyDeviceToHost));
+  return NRPHY_OK;
+}
+
+extern "C" int nrphy_pusch_chest_host_ex(nrphy_ctx_t* ctx, const nrphy_pusch_chest_cfg_t* cfg, const nrphy_pusch_chest_lowpapr_t* lp,
+                                         const void* grid, uint32_t grid_nof_ports, uint32_t grid_nof_subc, void* ch_est,
+                                         float* noise_vars, nrphy_pusch_chest_meas_t* meas)
+{
   if (ctx == nullptr || grid == nullptr || ch_est == nullptr || noise_vars == nullptr ||
-      validate(cfg, grid_nof_ports, grid_nof_subc) != NRPHY_OK) {
+      validate(cfg, lp, grid_nof_ports, grid_nof_subc) != NRPHY_OK) {
     return NRPHY_ERR_ARGUMENT;
   }
   const size_t grid_bytes = (size_t)grid_nof_ports * NRPHY_NSYMB * grid_nof_subc * 4;
@@ -199,7 +286,7 @@ extern "C" int nrphy_pusch_chest_host(nrphy_ctx_t* ctx, const nrphy_pusch_chest_
   const uint32_t            zero = 0;
   const uint64_t            ce0  = 0;
   nrphy_pusch_chest_plan_t* plan = nullptr;
-  int rc = nrphy_pusch_chest_plan_create(ctx, 1, cfg, &zero, 1, grid_nof_ports, grid_nof_subc, &ce0, &plan);
+  int rc = nrphy_pusch_chest_plan_create_ex(ctx, 1, cfg, lp, &zero, 1, grid_nof_ports, grid_nof_subc, &ce0, &plan);
   if (rc != NRPHY_OK) {
     return rc;
   }

@@ -3,7 +3,8 @@
 // validator, the UL-SCH information, one PDU turned into the configurations of the estimator, the demodulator, the demultiplexer,
 // the UCI decoders and the transport-block decoder -- and the plan that owns the stage plans and the buffers between them.  The
 // stages themselves are the library's: this file launches nothing but the result kernel.  One implementation serves
-// nrphy_pusch_proc_* and nrphy_pusch_evm_*: the former are the latter with enable_evm = 0.
+// nrphy_pusch_proc_*, nrphy_pusch_evm_* and nrphy_pusch_tp_*: the first are the second with enable_evm = 0, the second the third
+// without a transform-precoding descriptor.
 #include "ldpc_receive_host.h"
 #include "pusch_alloc_host.h"
 #include "pusch_proc_plan_host.h"
@@ -32,12 +33,26 @@ struct WithoutEvm {
   }
 };
 
-int derive(const nrphy_pusch_pdu_t* p, const nrphy_pusch_evm_options_t* eo, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
-           nrphy_pusch_proc_derived_t& d)
+bool transform_precoded(const nrphy_pusch_tp_desc_t* tp)
+{
+  return tp != nullptr && tp->transform_precoding != 0;
+}
+
+// The feature mask of the demodulator's _ex forms for a PDU (a plan: for any of its PDUs) with transform precoding.
+constexpr uint32_t TP_DEMOD_FEATURES = NRPHY_PUSCH_DEMOD_TRANSFORM_PRECODING | NRPHY_PUSCH_DEMOD_PI2_BPSK;
+
+// tp (may be null): the PDU's transform-precoding descriptor; lp: the estimator's low-PAPR DM-RS description that goes with d.chest.
+int derive(const nrphy_pusch_pdu_t* p, const nrphy_pusch_tp_desc_t* tp, const nrphy_pusch_evm_options_t* eo, uint32_t grid_nof_ports,
+           uint32_t grid_nof_subc, nrphy_pusch_proc_derived_t& d, nrphy_pusch_chest_lowpapr_t& lp)
 {
   std::memset(&d, 0, sizeof(d));
-  if (p == nullptr || eo == nullptr) {
+  lp = {0, 0};
+  if (p == nullptr || eo == nullptr || (tp != nullptr && tp->transform_precoding > 1)) {
     return NRPHY_ERR_ARGUMENT;
+  }
+  const bool tpre = transform_precoded(tp);
+  if (tpre) {
+    lp = {1, tp->n_rs_id};
   }
   const nrphy_pusch_proc_options_t* o = &eo->proc;
   // The processor's configuration; the EVM-based SINR needs the EVM.
@@ -53,11 +68,11 @@ int derive(const nrphy_pusch_pdu_t* p, const nrphy_pusch_evm_options_t* eo, uint
       p->has_codeword > 1 || (p->has_codeword != 0) != (p->tb_size_bytes != 0) || p->new_data > 1 ||
       (p->has_codeword == 0 && p->nof_harq_ack == 0 && p->nof_csi_part1 == 0) ||
       (p->modulation != NRPHY_MOD_QPSK && p->modulation != NRPHY_MOD_QAM16 && p->modulation != NRPHY_MOD_QAM64 &&
-       p->modulation != NRPHY_MOD_QAM256) ||
+       p->modulation != NRPHY_MOD_QAM256 && !(tpre && p->modulation == NRPHY_MOD_PI2_BPSK)) ||
       (p->has_codeword != 0 && (p->rv > 3 || (p->ldpc_base_graph != 1 && p->ldpc_base_graph != 2)))) {
     return NRPHY_ERR_ARGUMENT;
   }
-  const uint32_t qm = p->modulation;
+  const uint32_t qm = p->modulation == NRPHY_MOD_PI2_BPSK ? 1 : p->modulation;
 
   nrphy_pusch_chest_cfg_t& ce = d.chest;
   ce.numerology         = p->numerology;
@@ -87,11 +102,12 @@ int derive(const nrphy_pusch_pdu_t* p, const nrphy_pusch_evm_options_t* eo, uint
   dm.nof_tx_layers               = p->nof_tx_layers;
   dm.nof_rx_ports                = p->nof_rx_ports;
   dm.equalizer                   = o->equalizer;
-  dm.transform_precoding         = 0; // pusch_processor_impl.cpp:294
+  dm.transform_precoding         = tpre ? 1 : 0; // 0: pusch_processor_impl.cpp:294
   std::memcpy(dm.rx_ports, p->rx_ports, sizeof(dm.rx_ports));
   std::memcpy(dm.prb_mask, p->prb_mask, sizeof(dm.prb_mask));
-  if (nrphy_pusch_chest_validate(&ce, grid_nof_ports, grid_nof_subc) != NRPHY_OK ||
-      nrphy_pusch_demod_validate(&dm, grid_nof_ports, grid_nof_subc) != NRPHY_OK || p->rnti > 65535U || p->n_id > 1023U) {
+  if (nrphy_pusch_chest_validate_ex(&ce, &lp, grid_nof_ports, grid_nof_subc) != NRPHY_OK ||
+      nrphy_pusch_demod_validate_ex(&dm, grid_nof_ports, grid_nof_subc, tpre ? TP_DEMOD_FEATURES : 0) != NRPHY_OK ||
+      p->rnti > 65535U || p->n_id > 1023U) {
     return NRPHY_ERR_ARGUMENT;
   }
   d.codeword_bits = (uint32_t)nrphy_pusch_demod_codeword_bits(&dm);
@@ -182,32 +198,56 @@ extern "C" int nrphy_ul_sch_info(const nrphy_ulsch_info_cfg_t* cfg, nrphy_ulsch_
 extern "C" int nrphy_pusch_proc_validate(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_proc_options_t* options,
                                          uint32_t grid_nof_ports, uint32_t grid_nof_subc)
 {
-  nrphy_pusch_proc_derived_t d;
-  return derive(pdu, WithoutEvm(options).ptr, grid_nof_ports, grid_nof_subc, d);
+  return nrphy_pusch_tp_validate(pdu, nullptr, WithoutEvm(options).ptr, grid_nof_ports, grid_nof_subc);
 }
 
 extern "C" int nrphy_pusch_evm_validate(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_evm_options_t* options,
                                         uint32_t grid_nof_ports, uint32_t grid_nof_subc)
 {
-  nrphy_pusch_proc_derived_t d;
-  return derive(pdu, options, grid_nof_ports, grid_nof_subc, d);
+  return nrphy_pusch_tp_validate(pdu, nullptr, options, grid_nof_ports, grid_nof_subc);
+}
+
+extern "C" int nrphy_pusch_tp_validate(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_tp_desc_t* tp,
+                                       const nrphy_pusch_evm_options_t* options, uint32_t grid_nof_ports, uint32_t grid_nof_subc)
+{
+  nrphy_pusch_proc_derived_t  d;
+  nrphy_pusch_chest_lowpapr_t lp;
+  return derive(pdu, tp, options, grid_nof_ports, grid_nof_subc, d, lp);
 }
 
 extern "C" int nrphy_pusch_proc_derive(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_proc_options_t* options,
                                        uint32_t grid_nof_ports, uint32_t grid_nof_subc, nrphy_pusch_proc_derived_t* out)
 {
+  return nrphy_pusch_tp_derive(pdu, nullptr, WithoutEvm(options).ptr, grid_nof_ports, grid_nof_subc, out, nullptr);
+}
+
+extern "C" int nrphy_pusch_tp_derive(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_tp_desc_t* tp,
+                                     const nrphy_pusch_evm_options_t* options, uint32_t grid_nof_ports, uint32_t grid_nof_subc,
+                                     nrphy_pusch_proc_derived_t* out, nrphy_pusch_chest_lowpapr_t* lp_out)
+{
   if (out == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
-  const int rc = derive(pdu, WithoutEvm(options).ptr, grid_nof_ports, grid_nof_subc, *out);
+  nrphy_pusch_chest_lowpapr_t lp;
+  const int                   rc = derive(pdu, tp, options, grid_nof_ports, grid_nof_subc, *out, lp);
   if (rc != NRPHY_OK) {
     std::memset(out, 0, sizeof(*out));
+    lp = {0, 0};
+  }
+  if (lp_out != nullptr) {
+    *lp_out = lp;
   }
   return rc;
 }
 
 extern "C" int nrphy_pusch_proc_harq_bytes(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_proc_options_t* options,
                                            uint64_t* soft_bytes, uint64_t* state_bytes)
+{
+  return nrphy_pusch_tp_harq_bytes(pdu, nullptr, WithoutEvm(options).ptr, soft_bytes, state_bytes);
+}
+
+extern "C" int nrphy_pusch_tp_harq_bytes(const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_tp_desc_t* tp,
+                                         const nrphy_pusch_evm_options_t* options, uint64_t* soft_bytes, uint64_t* state_bytes)
 {
   if (pdu == nullptr || soft_bytes == nullptr || state_bytes == nullptr) {
     return NRPHY_ERR_ARGUMENT;
@@ -221,8 +261,9 @@ extern "C" int nrphy_pusch_proc_harq_bytes(const nrphy_pusch_pdu_t* pdu, const n
   if (pdu->dc_position != NRPHY_PUSCH_CHEST_NO_DC) {
     subc = std::max(subc, std::min<uint32_t>(pdu->dc_position / NRPHY_NRE + 1, NRPHY_MAX_RB) * NRPHY_NRE);
   }
-  nrphy_pusch_proc_derived_t d;
-  const int                  rc = derive(pdu, WithoutEvm(options).ptr, ports, subc, d);
+  nrphy_pusch_proc_derived_t  d;
+  nrphy_pusch_chest_lowpapr_t lp;
+  const int                   rc = derive(pdu, tp, options, ports, subc, d, lp);
   if (rc != NRPHY_OK) {
     return rc;
   }
@@ -265,8 +306,8 @@ extern "C" int nrphy_pusch_proc_plan_harq_bytes(const nrphy_pusch_proc_plan_t* p
 namespace {
 // The plan of PDUs whose records are at hand: `pre` (may be null) holds one accepted derivation per PDU, so that a caller that
 // derived already -- the host form -- does not derive again.
-int plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, const nrphy_pusch_evm_options_t* options,
-                const nrphy_pusch_proc_derived_t* pre, const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports,
+int plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, const nrphy_pusch_tp_desc_t* tps,
+                const nrphy_pusch_evm_options_t* options, const nrphy_pusch_proc_derived_t* pre, const uint32_t* grid_index, uint32_t nof_grids, uint32_t grid_nof_ports,
                 uint32_t grid_nof_subc, const uint64_t* harq_soft_offset, const uint64_t* harq_state_offset, const uint64_t* tb_offset,
                 const uint64_t* uci_offset, nrphy_pusch_proc_plan_t** out)
 {
@@ -279,6 +320,8 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, con
   }
   std::vector<nrphy_pusch_proc_derived_t> derived(n);
   std::vector<nrphy_pusch_chest_cfg_t>    chest(n);
+  std::vector<nrphy_pusch_chest_lowpapr_t> lowpapr(n, nrphy_pusch_chest_lowpapr_t{0, 0});
+  bool                                    any_tp = false;
   std::vector<nrphy_pusch_demod_cfg_t>    demod(n);
   std::vector<uint64_t>                   ce_offset(n);
   std::vector<PuschProcDesc>              desc(n);
@@ -295,11 +338,16 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, con
   int      rc = NRPHY_OK;
   for (uint32_t i = 0; i != n && rc == NRPHY_OK; ++i) {
     nrphy_pusch_proc_derived_t& d = derived[i];
+    const nrphy_pusch_tp_desc_t* tp = tps != nullptr ? &tps[i] : nullptr;
     if (pre != nullptr) {
       d = pre[i];
-    } else if ((rc = derive(&pdus[i], options, grid_nof_ports, grid_nof_subc, d)) != NRPHY_OK) {
+      if (transform_precoded(tp)) {
+        lowpapr[i] = {1, tp->n_rs_id};
+      }
+    } else if ((rc = derive(&pdus[i], tp, options, grid_nof_ports, grid_nof_subc, d, lowpapr[i])) != NRPHY_OK) {
       break;
     }
+    any_tp = any_tp || transform_precoded(tp);
     if (grid_index[i] >= nof_grids || (d.nof_uci != 0 && uci_offset == nullptr) ||
         (d.has_decoder != 0 && (harq_soft_offset == nullptr || harq_state_offset == nullptr || tb_offset == nullptr ||
                                 harq_state_offset[i] % 64 != 0))) {
@@ -366,12 +414,12 @@ int plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, con
     }
   }
   if (rc == NRPHY_OK) {
-    rc = nrphy_pusch_chest_plan_create(ctx, n, chest.data(), grid_index, nof_grids, grid_nof_ports, grid_nof_subc, ce_offset.data(),
-                                       &plan->chest);
+    rc = nrphy_pusch_chest_plan_create_ex(ctx, n, chest.data(), any_tp ? lowpapr.data() : nullptr, grid_index, nof_grids, grid_nof_ports,
+                                          grid_nof_subc, ce_offset.data(), &plan->chest);
   }
   if (rc == NRPHY_OK) {
-    rc = nrphy_pusch_demod_plan_create(ctx, n, demod.data(), grid_index, nof_grids, grid_nof_ports, grid_nof_subc, ce_offset.data(),
-                                       &plan->demod);
+    rc = nrphy_pusch_demod_plan_create_ex(ctx, n, demod.data(), grid_index, nof_grids, grid_nof_ports, grid_nof_subc, ce_offset.data(),
+                                          any_tp ? TP_DEMOD_FEATURES : 0, &plan->demod);
   }
   if (rc == NRPHY_OK && !demux.empty()) {
     rc = nrphy_ulsch_demux_plan_create(ctx, (uint32_t)demux.size(), demux.data(), dx_in.data(), dx_sch.data(), dx_harq.data(),
@@ -436,7 +484,7 @@ extern "C" int nrphy_pusch_proc_plan_create(nrphy_ctx_t* ctx, uint32_t n, const 
                                             const uint64_t* harq_state_offset, const uint64_t* tb_offset, const uint64_t* uci_offset,
                                             nrphy_pusch_proc_plan_t** out)
 {
-  return plan_create(ctx, n, pdus, WithoutEvm(options).ptr, nullptr, grid_index, nof_grids, grid_nof_ports, grid_nof_subc,
+  return plan_create(ctx, n, pdus, nullptr, WithoutEvm(options).ptr, nullptr, grid_index, nof_grids, grid_nof_ports, grid_nof_subc,
                      harq_soft_offset, harq_state_offset, tb_offset, uci_offset, out);
 }
 
@@ -446,7 +494,17 @@ extern "C" int nrphy_pusch_evm_plan_create(nrphy_ctx_t* ctx, uint32_t n, const n
                                            const uint64_t* harq_state_offset, const uint64_t* tb_offset, const uint64_t* uci_offset,
                                            nrphy_pusch_proc_plan_t** out)
 {
-  return plan_create(ctx, n, pdus, options, nullptr, grid_index, nof_grids, grid_nof_ports, grid_nof_subc, harq_soft_offset,
+  return plan_create(ctx, n, pdus, nullptr, options, nullptr, grid_index, nof_grids, grid_nof_ports, grid_nof_subc, harq_soft_offset,
+                     harq_state_offset, tb_offset, uci_offset, out);
+}
+
+extern "C" int nrphy_pusch_tp_plan_create(nrphy_ctx_t* ctx, uint32_t n, const nrphy_pusch_pdu_t* pdus, const nrphy_pusch_tp_desc_t* tps,
+                                          const nrphy_pusch_evm_options_t* options, const uint32_t* grid_index, uint32_t nof_grids,
+                                          uint32_t grid_nof_ports, uint32_t grid_nof_subc, const uint64_t* harq_soft_offset,
+                                          const uint64_t* harq_state_offset, const uint64_t* tb_offset, const uint64_t* uci_offset,
+                                          nrphy_pusch_proc_plan_t** out)
+{
+  return plan_create(ctx, n, pdus, tps, options, nullptr, grid_index, nof_grids, grid_nof_ports, grid_nof_subc, harq_soft_offset,
                      harq_state_offset, tb_offset, uci_offset, out);
 }
 
@@ -524,11 +582,21 @@ extern "C" int nrphy_pusch_evm_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* p
                                     const void* grid, uint32_t grid_nof_ports, uint32_t grid_nof_subc, int8_t* harq_soft,
                                     uint8_t* harq_state, uint8_t* tb, uint8_t* uci_bits, nrphy_pusch_result_t* result)
 {
-  nrphy_pusch_proc_derived_t d;
+  return nrphy_pusch_tp_host(ctx, pdu, nullptr, options, grid, grid_nof_ports, grid_nof_subc, harq_soft, harq_state, tb, uci_bits,
+                             result);
+}
+
+extern "C" int nrphy_pusch_tp_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* pdu, const nrphy_pusch_tp_desc_t* tp,
+                                   const nrphy_pusch_evm_options_t* options, const void* grid, uint32_t grid_nof_ports,
+                                   uint32_t grid_nof_subc, int8_t* harq_soft, uint8_t* harq_state, uint8_t* tb, uint8_t* uci_bits,
+                                   nrphy_pusch_result_t* result)
+{
+  nrphy_pusch_proc_derived_t  d;
+  nrphy_pusch_chest_lowpapr_t lp;
   if (ctx == nullptr || grid == nullptr || result == nullptr) {
     return NRPHY_ERR_ARGUMENT;
   }
-  int rc = derive(pdu, options, grid_nof_ports, grid_nof_subc, d);
+  int rc = derive(pdu, tp, options, grid_nof_ports, grid_nof_subc, d, lp);
   if (rc != NRPHY_OK) {
     return rc;
   }
@@ -562,7 +630,7 @@ extern "C" int nrphy_pusch_evm_host(nrphy_ctx_t* ctx, const nrphy_pusch_pdu_t* p
   const uint32_t           zero = 0;
   const uint64_t           soft_off = 0, state_off = soft_room, tb_off = 0, uci_off = align_up(pdu->tb_size_bytes);
   nrphy_pusch_proc_plan_t* plan = nullptr;
-  rc = plan_create(ctx, 1, pdu, options, &d, &zero, 1, grid_nof_ports, grid_nof_subc, &soft_off, &state_off, &tb_off, &uci_off, &plan);
+  rc = plan_create(ctx, 1, pdu, tp, options, &d, &zero, 1, grid_nof_ports, grid_nof_subc, &soft_off, &state_off, &tb_off, &uci_off, &plan);
   if (rc != NRPHY_OK) {
     return rc;
   }

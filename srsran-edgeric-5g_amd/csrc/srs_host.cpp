@@ -2,7 +2,7 @@
 // (R/lib/phy/upper/signal_processors/srs/srs_validator_generic_impl.cpp) and the assertions of
 // srs_estimator_generic_impl::estimate and get_srs_information refuse --, the mapping of get_srs_information
 // (R/lib/ran/srs/srs_information.cpp:39-105) and the plan's per-SRS constants: everything that does not depend on the grid.
-#include "nrphy_host_internal.h"
+#include "low_papr_host.h"
 
 #include <cmath>
 #include <complex>
@@ -86,33 +86,6 @@ int validate(const nrphy_srs_cfg_t* cp, uint32_t grid_nof_ports, uint32_t grid_n
   return NRPHY_OK;
 }
 
-// prime_lower_than: the largest prime below n (n >= 36 here).
-uint32_t prime_below(uint32_t n)
-{
-  for (uint32_t v = n - 1; v > 2; --v) {
-    bool prime = true;
-    for (uint32_t f = 2; f * f <= v; ++f) {
-      if (v % f == 0) {
-        prime = false;
-        break;
-      }
-    }
-    if (prime) {
-      return v;
-    }
-  }
-  return 2;
-}
-
-// zc_sequence_q(u, 0, N_zc) (low_papr_sequence_generator_impl.cpp:134-147): single precision, the half added in double.
-uint32_t zc_root(uint32_t u, uint32_t n_zc)
-{
-  const float n_sz  = (float)n_zc;
-  const float q_hat = n_sz * (float)(u + 1) / 31;
-  const float q     = (float)((double)q_hat + 0.5);
-  return (uint32_t)(int)q;
-}
-
 // complex_exponential_table(size, 1): polar(1, float(2 pi) float(n) / float(size)).
 std::vector<float2> unit_circle(uint32_t size)
 {
@@ -144,8 +117,8 @@ SrsDesc make_desc(const nrphy_srs_cfg_t& c, uint32_t grid_index)
   d.scs_hz       = scs_khz * 1000;
   d.symbol_scale = (float)(1.0 / static_cast<float>(c.nof_symbols));
   if (s0.M >= 36) {
-    d.n_zc = prime_below(s0.M);
-    d.q    = zc_root(s0.u, d.n_zc);
+    d.n_zc = low_papr_prime_below(s0.M);
+    d.q    = low_papr_zc_root(s0.u, d.n_zc);
   } else {
     for (uint32_t n = 0; n != s0.M; ++n) {
       d.phi[n] = s0.M == 12 ? PUCCH_PHI_12[s0.u][n] : SRS_PHI_24[s0.u][n];

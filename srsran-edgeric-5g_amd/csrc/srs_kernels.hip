@@ -21,6 +21,7 @@
 #include "bits_device.h"
 #include "exact_device.h"
 #include "fft_device.h"
+#include "low_papr_device.h"
 
 #include <hip/hip_runtime.h>
 
@@ -36,14 +37,11 @@ typedef const NRPHY_CONSTANT SrsDesc& SrsDescRef;
 // low_papr_sequence_generator_impl::generate(u, 0, n_cs, n_cs_max)[n] for antenna port `port`.
 __device__ __forceinline__ float2 srs_sequence(SrsDescRef d, const float2* __restrict__ cs_table, uint32_t port, uint32_t n)
 {
-  float2 r;
-  if (d.M < 36u) { // the tables: exp(j phi pi / 4), entry (8 + phi) mod 8 of the 8-point circle
-    r = unit_circle((uint32_t)(8 + (int)d.phi[n]) & 7u, 8u);
-  } else { // Zadoff-Chu: entry (2 N_zc - (q m (m + 1) mod 2 N_zc)) mod 2 N_zc
-    const uint32_t size = 2u * d.n_zc;
-    const uint64_t m    = n % d.n_zc;
-    const uint32_t arg  = (uint32_t)(((uint64_t)d.q * m * (m + 1u)) % size);
-    r                   = unit_circle(arg == 0u ? 0u : size - arg, size);
+  float2 r; // the element's entry of its unit circle is low_papr_device.h's
+  if (d.M < 36u) {
+    r = unit_circle(low_papr_table_index(d.phi[n]), LOW_PAPR_TABLE_CIRCLE);
+  } else {
+    r = unit_circle(low_papr_zc_index(d.q, d.n_zc, n), 2u * d.n_zc);
   }
   const uint32_t step = d.cs_step[port];
   if (step != 0u) {

@@ -378,10 +378,18 @@ extern "C" int nrphy_ul_slot_pusch(nrphy_ul_slots_t* pool, uint32_t slot_id, uin
   return nrphy_pusch_evm_slot(pool, slot_id, n, pdus, &without_evm, harq_soft_offset, harq_state_offset);
 }
 
-// The PUSCH operation of a slot; nrphy_ul_slot_pusch is this one with enable_evm = 0.
 extern "C" int nrphy_pusch_evm_slot(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pusch_pdu_t* pdus,
                                     const nrphy_pusch_evm_options_t* options, const uint64_t* harq_soft_offset,
                                     const uint64_t* harq_state_offset)
+{
+  return nrphy_pusch_tp_slot(pool, slot_id, n, pdus, nullptr, options, harq_soft_offset, harq_state_offset);
+}
+
+// The PUSCH operation of a slot; nrphy_pusch_evm_slot is this one without transform-precoding descriptors, nrphy_ul_slot_pusch
+// that one with enable_evm = 0.
+extern "C" int nrphy_pusch_tp_slot(nrphy_ul_slots_t* pool, uint32_t slot_id, uint32_t n, const nrphy_pusch_pdu_t* pdus,
+                                   const nrphy_pusch_tp_desc_t* tps, const nrphy_pusch_evm_options_t* options,
+                                   const uint64_t* harq_soft_offset, const uint64_t* harq_state_offset)
 {
   UlSlot*    s    = nullptr;
   const auto lock = lock_for_receivers(pool, slot_id, n, pdus, s);
@@ -392,7 +400,8 @@ extern "C" int nrphy_pusch_evm_slot(nrphy_ul_slots_t* pool, uint32_t slot_id, ui
   std::vector<UlSlotSpan> tb(n), uci(n);
   std::vector<uint64_t>   tb_offset(n), uci_offset(n);
   for (uint32_t i = 0; i != n; ++i) {
-    int rc = item_status(*s, nrphy_pusch_evm_validate(&pdus[i], options, pool->cfg.nof_ports, pool->nof_subc),
+    int rc = item_status(*s, nrphy_pusch_tp_validate(&pdus[i], tps != nullptr ? &tps[i] : nullptr, options, pool->cfg.nof_ports,
+                                                     pool->nof_subc),
                          pdus[i].start_symbol_index, pdus[i].nof_symbols);
     if (rc != NRPHY_OK) {
       return rc;
@@ -410,8 +419,8 @@ extern "C" int nrphy_pusch_evm_slot(nrphy_ul_slots_t* pool, uint32_t slot_id, ui
   const PlanCall call(pool, n);
   HIP_TRY(call.device);
   nrphy_pusch_proc_plan_t* plan = nullptr;
-  int rc = nrphy_pusch_evm_plan_create(pool->ctx, n, pdus, options, call.grid_of.data(), 1, pool->cfg.nof_ports, pool->nof_subc,
-                                       harq_soft_offset, harq_state_offset, tb_offset.data(), uci_offset.data(), &plan);
+  int rc = nrphy_pusch_tp_plan_create(pool->ctx, n, pdus, tps, options, call.grid_of.data(), 1, pool->cfg.nof_ports, pool->nof_subc,
+                                      harq_soft_offset, harq_state_offset, tb_offset.data(), uci_offset.data(), &plan);
   if (rc != NRPHY_OK) {
     return rc;
   }

@@ -467,10 +467,11 @@ class Context:
                                                         C.byref(sinr), C.byref(evm)), "nrphy_pusch_demodulate_host_evm")
         return out, float(sinr.value), np.float32(evm.value)
 
-    def pusch_chest_host(self, cfg, grid, ch_est=None):
+    def pusch_chest_host(self, cfg, grid, ch_est=None, lowpapr=None, ex=False):
         """dmrs_pusch_estimator::estimate + the processor's DC step for one PUSCH: grid [ports][14][subc] raw cbf16 words ->
         (ch_est [layers][rx][14][subc] cbf16 words, noise_vars [rx], measurements [rx][2] of abi.PuschChestMeas).  ch_est: the
-        buffer to write into (only the allocated region changes); zeros when None."""
+        buffer to write into (only the allocated region changes); zeros when None.  lowpapr: an abi.PuschChestLowpapr for
+        nrphy_pusch_chest_host_ex; ex = True calls that form with whatever lowpapr is (None: a null pointer)."""
         grid = np.ascontiguousarray(grid, dtype=np.uint32)
         shape = (cfg.nof_tx_layers, cfg.nof_rx_ports, 14, grid.shape[-1])
         ce = np.zeros(shape, np.uint32) if ch_est is None else np.array(ch_est, dtype=np.uint32, order="C")
@@ -478,10 +479,40 @@ class Context:
             raise ValueError("ch_est must be %s" % (shape,))
         nv = np.zeros(cfg.nof_rx_ports, np.float32)
         meas = (abi.PuschChestMeas * (cfg.nof_rx_ports * abi.PUSCH_CHEST_MAX_LAYERS))()
-        _check(self.lib.nrphy_pusch_chest_host(self.handle, C.byref(cfg), grid.ctypes.data, grid.shape[0], grid.shape[-1],
-                                               ce.ctypes.data, nv.ctypes.data, meas), "nrphy_pusch_chest_host")
+        if ex or lowpapr is not None:
+            _check(self.lib.nrphy_pusch_chest_host_ex(self.handle, C.byref(cfg), None if lowpapr is None else C.byref(lowpapr),
+                                                      grid.ctypes.data, grid.shape[0], grid.shape[-1], ce.ctypes.data, nv.ctypes.data,
+                                                      meas), "nrphy_pusch_chest_host_ex")
+        else:
+            _check(self.lib.nrphy_pusch_chest_host(self.handle, C.byref(cfg), grid.ctypes.data, grid.shape[0], grid.shape[-1],
+                                                   ce.ctypes.data, nv.ctypes.data, meas), "nrphy_pusch_chest_host")
         m = [[meas[i * abi.PUSCH_CHEST_MAX_LAYERS + l] for l in range(abi.PUSCH_CHEST_MAX_LAYERS)] for i in range(cfg.nof_rx_ports)]
         return ce, nv, m
+
+    def pusch_lowpapr_sequence_host(self, n_rs_id, nof_prb):
+        """The low-PAPR DM-RS of a transform-precoded PUSCH from the kernel's generator: complex64 [6 nof_prb]
+        (nrphy_pusch_lowpapr_sequence_host)."""
+        out = np.zeros(6 * nof_prb, np.complex64)
+        _check(self.lib.nrphy_pusch_lowpapr_sequence_host(self.handle, n_rs_id, nof_prb, out.ctypes.data),
+               "nrphy_pusch_lowpapr_sequence_host")
+        return out
+
+    def pusch_tp_host(self, pdu, tp, options, grid, harq_soft=None, harq_state=None):
+        """pusch_proc_host with an abi.PuschTpDesc (or None: a null pointer) and an abi.PuschEvmOptions (nrphy_pusch_tp_host)."""
+        grid = np.ascontiguousarray(grid, dtype=np.uint32)
+        soft_bytes, state_bytes = pusch_tp_harq_bytes(pdu, tp, options)
+        soft = np.zeros(soft_bytes, np.int8) if harq_soft is None else harq_soft
+        state = np.zeros(state_bytes, np.uint8) if harq_state is None else harq_state
+        if soft.size != soft_bytes or state.size != state_bytes or not (soft.flags.c_contiguous and state.flags.c_contiguous):
+            raise ValueError("HARQ blocks must be contiguous arrays of %d and %d bytes" % (soft_bytes, state_bytes))
+        tb = np.zeros(pdu.tb_size_bytes, np.uint8)
+        uci = np.zeros(pdu.nof_harq_ack + pdu.nof_csi_part1, np.uint8)
+        result = abi.PuschResult()
+        _check(self.lib.nrphy_pusch_tp_host(self.handle, C.byref(pdu), None if tp is None else C.byref(tp), C.byref(options),
+                                            grid.ctypes.data, grid.shape[0], grid.shape[-1], soft.ctypes.data if soft_bytes else None,
+                                            state.ctypes.data if state_bytes else None, tb.ctypes.data if tb.size else None,
+                                            uci.ctypes.data if uci.size else None, C.byref(result)), "nrphy_pusch_tp_host")
+        return result, tb, uci
 
     def pusch_evm_host(self, pdu, options, grid, harq_soft=None, harq_state=None):
         """pusch_proc_host with abi.PuschEvmOptions (nrphy_pusch_evm_host): with enable_evm the result carries the EVM."""
@@ -810,15 +841,22 @@ class PuschChestPlan:
     """nrphy_pusch_chest_plan: PUSCHs over a batch of received grids; run() writes their channel estimates (the layout
     PuschDemodPlan reads), the noise variances PuschDemodPlan.run takes and, optionally, the measurements."""
 
-    def __init__(self, ctx, cfgs, grid_indices, nof_grids, nof_ports, nof_subc, ce_offsets):
+    def __init__(self, ctx, cfgs, grid_indices, nof_grids, nof_ports, nof_subc, ce_offsets, lowpapr=None, ex=False):
+        """lowpapr: one abi.PuschChestLowpapr per PUSCH for nrphy_pusch_chest_plan_create_ex; ex = True calls that form with
+        whatever lowpapr is (None: a null pointer)."""
         self.ctx = ctx
         n = len(cfgs)
         arr = (abi.PuschChestCfg * n)(*cfgs)
         gidx = (C.c_uint32 * n)(*grid_indices)
         offs = (C.c_uint64 * n)(*ce_offsets)
         h = C.c_void_p()
-        _check(ctx.lib.nrphy_pusch_chest_plan_create(ctx.handle, n, arr, gidx, nof_grids, nof_ports, nof_subc, offs, C.byref(h)),
-               "nrphy_pusch_chest_plan_create")
+        if ex or lowpapr is not None:
+            lps = None if lowpapr is None else (abi.PuschChestLowpapr * n)(*lowpapr)
+            _check(ctx.lib.nrphy_pusch_chest_plan_create_ex(ctx.handle, n, arr, lps, gidx, nof_grids, nof_ports, nof_subc, offs,
+                                                            C.byref(h)), "nrphy_pusch_chest_plan_create_ex")
+        else:
+            _check(ctx.lib.nrphy_pusch_chest_plan_create(ctx.handle, n, arr, gidx, nof_grids, nof_ports, nof_subc, offs, C.byref(h)),
+                   "nrphy_pusch_chest_plan_create")
         self.handle = h
         self.n = n
 
@@ -1123,6 +1161,26 @@ class PuschProcPlan:
             pass
 
 
+class PuschTpPlan(PuschProcPlan):
+    """PuschProcPlan made by nrphy_pusch_tp_plan_create: tps is one abi.PuschTpDesc per PDU, or None (a null pointer: the plan of
+    nrphy_pusch_evm_plan_create); options is an abi.PuschEvmOptions."""
+
+    def __init__(self, ctx, pdus, tps, options, grid_indices, nof_grids, nof_ports, nof_subc, harq_soft_offsets=None,
+                 harq_state_offsets=None, tb_offsets=None, uci_offsets=None):
+        self.ctx = ctx
+        n = len(pdus)
+        arr = (abi.PuschPdu * n)(*pdus)
+        tarr = None if tps is None else (abi.PuschTpDesc * n)(*tps)
+        gidx = (C.c_uint32 * n)(*grid_indices)
+        offs = [None if o is None else (C.c_uint64 * n)(*o) for o in (harq_soft_offsets, harq_state_offsets, tb_offsets, uci_offsets)]
+        h = C.c_void_p()
+        self.handle = None
+        _check(ctx.lib.nrphy_pusch_tp_plan_create(ctx.handle, n, arr, tarr, C.byref(options), gidx, nof_grids, nof_ports, nof_subc, *offs,
+                                                  C.byref(h)), "nrphy_pusch_tp_plan_create")
+        self.handle = h
+        self.n = n
+
+
 class PuschCsi2Plan:
     """nrphy_pusch_csi2_plan: PuschProcPlan for PDUs of which some carry a CSI part 2 size description (abi.PuschCsi2Desc, one per
     PDU; nof_entries 0 = none).  run() also writes one abi.PuschCsi2Result per PDU; PDU i's part 2 payload goes to byte
@@ -1211,6 +1269,29 @@ def pusch_proc_validate(pdu, options, grid_nof_ports, grid_nof_subc):
 def pusch_evm_validate(pdu, options, grid_nof_ports, grid_nof_subc):
     """nrphy_pusch_evm_validate with an abi.PuschEvmOptions: abi.OK or abi.ERR_ARGUMENT (host only)."""
     return int(load().nrphy_pusch_evm_validate(C.byref(pdu), C.byref(options), grid_nof_ports, grid_nof_subc))
+
+
+def pusch_tp_validate(pdu, tp, options, grid_nof_ports, grid_nof_subc):
+    """nrphy_pusch_tp_validate with an abi.PuschTpDesc (or None) and an abi.PuschEvmOptions: abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_pusch_tp_validate(C.byref(pdu), None if tp is None else C.byref(tp), C.byref(options), grid_nof_ports,
+                                              grid_nof_subc))
+
+
+def pusch_tp_derive(pdu, tp, options, grid_nof_ports, grid_nof_subc):
+    """nrphy_pusch_tp_derive: (abi.PuschProcDerived, abi.PuschChestLowpapr) of a PDU, or None for a refused one (host only)."""
+    out, lp = abi.PuschProcDerived(), abi.PuschChestLowpapr()
+    if int(load().nrphy_pusch_tp_derive(C.byref(pdu), None if tp is None else C.byref(tp), C.byref(options), grid_nof_ports,
+                                        grid_nof_subc, C.byref(out), C.byref(lp))) != abi.OK:
+        return None
+    return out, lp
+
+
+def pusch_tp_harq_bytes(pdu, tp, options):
+    """nrphy_pusch_tp_harq_bytes: (soft bytes, state bytes) of the PDU's HARQ blocks (host only)."""
+    soft, state = C.c_uint64(0), C.c_uint64(0)
+    _check(load().nrphy_pusch_tp_harq_bytes(C.byref(pdu), None if tp is None else C.byref(tp), C.byref(options), C.byref(soft),
+                                            C.byref(state)), "nrphy_pusch_tp_harq_bytes")
+    return int(soft.value), int(state.value)
 
 
 def pusch_proc_derive(pdu, options, grid_nof_ports, grid_nof_subc):
@@ -1376,6 +1457,12 @@ def pf2_sizes(cfg):
     if load().nrphy_pf2_sizes(C.byref(cfg), C.byref(e), C.byref(a)) != abi.OK:
         return None
     return int(e.value), int(a.value)
+
+
+def pusch_chest_validate_ex(cfg, lowpapr, grid_nof_ports, grid_nof_subc):
+    """nrphy_pusch_chest_validate_ex with an abi.PuschChestLowpapr (or None): abi.OK or abi.ERR_ARGUMENT (host only)."""
+    return int(load().nrphy_pusch_chest_validate_ex(C.byref(cfg), None if lowpapr is None else C.byref(lowpapr), grid_nof_ports,
+                                                    grid_nof_subc))
 
 
 def pusch_chest_validate(cfg, grid_nof_ports, grid_nof_subc):
@@ -1669,6 +1756,15 @@ class UlSlots(_SlotPool):
         soft = (C.c_uint64 * n)(*harq_soft_offsets) if harq_soft_offsets is not None else None
         state = (C.c_uint64 * n)(*harq_state_offsets) if harq_state_offsets is not None else None
         return int(self.ctx.lib.nrphy_pusch_evm_slot(self.handle, sid, n, arr, C.byref(options), soft, state))
+
+    def pusch_tp(self, sid, pdus, tps, options, harq_soft_offsets=None, harq_state_offsets=None):
+        """pusch_evm() with one abi.PuschTpDesc per PDU, or None (nrphy_pusch_tp_slot); the results append to the same list."""
+        n = len(pdus)
+        arr = (abi.PuschPdu * n)(*pdus)
+        tarr = None if tps is None else (abi.PuschTpDesc * n)(*tps)
+        soft = (C.c_uint64 * n)(*harq_soft_offsets) if harq_soft_offsets is not None else None
+        state = (C.c_uint64 * n)(*harq_state_offsets) if harq_state_offsets is not None else None
+        return int(self.ctx.lib.nrphy_pusch_tp_slot(self.handle, sid, n, arr, tarr, C.byref(options), soft, state))
 
     def pucch(self, sid, cfgs):
         arr = (abi.PucchCfg * len(cfgs))(*cfgs)
